@@ -9,7 +9,7 @@ byte-aligned streams are concatenated on rank 0 over RCCL.  For N > 1 the shardi
 rounds (global piece g = k*N + rank), so the gather of round k (sizes all_gather + one point-to-point send per
 rank, straight to the final offset) overlaps the compression of round k+1 (starflate_amd/multigpu.py).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--bytes B] [--workload text|random|mixed]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--bytes B] [--workload text|random|mixed] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (k_lz77), its launch time measured live
@@ -100,6 +100,29 @@ def run_steps(step, fence, steps, warmup):
         step()
     fence()
     return time.perf_counter() - t0
+
+
+DUMP_SAMPLE = 4 << 20  # stream bytes kept by --dump-outputs: float32 values + float64 positions = 48 MiB at most
+DUMP_SEED = 7
+
+
+def dump_outputs(path, out, total):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the stream (`out[:total]`) and its
+    length.  A stream longer than DUMP_SAMPLE bytes is sampled at DUMP_SAMPLE positions drawn with a fixed seed (the
+    same positions for the same length), so two builds can be compared output for output."""
+    import numpy as np
+    import torch
+
+    total = int(total)
+    if total <= DUMP_SAMPLE:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, DUMP_SAMPLE, replace=False))
+    vals = out[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "stream.npy"), vals.astype(np.float32))
+    np.save(os.path.join(path, "stream_positions.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "compressed_bytes.npy"), np.array([total], dtype=np.float64))
 
 
 def pipelined_step(compress_fn, pieces, gathered, container="raw", checksum_fn=None, group=None, validate=True, bound_fn=None, timing=None):
@@ -400,7 +423,12 @@ def main():
     ap.add_argument("--input-file", default=None,
                     help="compress this file's bytes (tiled / cut to --bytes) instead of a generator; also: $STARFLATE_CORPUS_DIR "
                          "(enwik9 / enwik8 / dickens / alice29.txt, first one found) when --workload text")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's stream (a seeded sample past 4 Mi bytes) and its length "
+                         "to DIR/*.npy (float32 / float64; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -530,6 +558,8 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:  # before anything reuses the buffers of the last timed step
+        dump_outputs(args.dump_outputs, result["out"], result["total"])
 
     ms_per_step = dt / args.steps * 1e3
     # ---- N > 1: what the record needs to be read without DESIGN.md -- who took part, what the gather cost, what was expected ----

@@ -5,6 +5,7 @@ import json
 import os
 import subprocess
 import sys
+import zlib
 
 import pytest
 
@@ -38,6 +39,43 @@ def test_bench_self_launch_gloo(gpus, container):
     pr = m["prediction"]
     assert {"model", "T_c_ms", "T_x_ms", "predicted_step_ms", "predicted_efficiency", "bound"} <= set(pr)
     assert 0 < pr["predicted_efficiency"] <= 1 and pr["T_x_ms"] > 0
+
+
+def _check_dump(d, dump):
+    """The files of --dump-outputs: float32 / float64 only, 64 MB at most, the length the line reports, sorted positions."""
+    import numpy as np
+
+    files = {p.name: np.load(p) for p in dump.iterdir()}
+    assert set(files) == {"stream.npy", "stream_positions.npy", "compressed_bytes.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in dump.iterdir()) <= 64_000_000
+    total = int(files["compressed_bytes.npy"][0])
+    assert total == d["compressed_bytes"]
+    pos = files["stream_positions.npy"]
+    assert pos.size == files["stream.npy"].size == min(total, 4 << 20) and np.all(np.diff(pos) > 0) and pos[-1] < total
+    return files
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's stream and length; the same arguments give the same files."""
+    import numpy as np
+
+    runs = []
+    for k in range(2):
+        dump = tmp_path / f"dump{k}"
+        r = _run("--gpus", "2", "--backend", "gloo", "--bytes", str(1 << 20), "--rounds", "2", "--steps", "3", "--warmup", "1",
+                 "--dump-outputs", str(dump))
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(r.stdout.strip())
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        runs.append(_check_dump(d, dump))
+    a, b = runs
+    assert all(np.array_equal(a[name], b[name]) for name in a)
+    # a stream this short is dumped whole: it inflates to every rank's input
+    stream = a["stream.npy"].astype(np.uint8).tobytes()
+    assert len(zlib.decompress(stream, -15)) == 2 * (1 << 20)
+    r = _run("--gpus", "2", "--backend", "gloo", "--bytes", str(1 << 20), "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr
 
 
 def test_bench_self_launch_propagates_failure():
@@ -162,15 +200,26 @@ def test_bench_line_layout_and_size():
 
 
 @pytest.mark.gpu
-def test_bench_line_on_the_gpu_is_compact(tmp_path):
+def test_bench_line_on_the_gpu_is_compact(tmp_path, compressor):
     """The real command at a reduced size: one line under the driver's 8 KB, `configs` last with config[3]'s bytes and config[4], and --sweep
-    writes its table to a file instead of the line."""
-    sweep = tmp_path / "sweep.json"
-    r = _run("--bytes", str(64 << 20), "--secondary-bytes", str(32 << 20), "--cpu-sample-bytes", str(16 << 20), "--steps", "2", "--warmup", "1")
+    writes its table to a file instead of the line.  --dump-outputs samples the timed step's stream: the bytes a compress of the same
+    input gives at those positions."""
+    import numpy as np
+
+    from starflate_amd import synth
+
+    sweep, dump = tmp_path / "sweep.json", tmp_path / "dump"
+    r = _run("--bytes", str(64 << 20), "--secondary-bytes", str(32 << 20), "--cpu-sample-bytes", str(16 << 20), "--steps", "2", "--warmup", "1",
+             "--dump-outputs", str(dump))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and len(lines[0]) < 8192, len(lines[0])
     d = json.loads(lines[0])
+    files = _check_dump(d, dump)
+    out, n = compressor.compress_tensor(synth.gen_text_torch(64 << 20, seed=3, device="cuda"), block_bytes=d["config"]["block_bytes"])
+    assert n == d["compressed_bytes"]
+    pos = files["stream_positions.npy"].astype(np.int64)
+    assert np.array_equal(out[:n].cpu().numpy()[pos], files["stream.npy"].astype(np.uint8))
     assert list(d)[-1] == "configs" and {"config2_text", "config3_mixed_1gpu", "config4_random"} <= set(d["configs"])
     assert d["roundtrip_ok"] is True and all(c["roundtrip_ok"] for c in d["configs"].values())
     assert d["roofline"]["frac"] > 0 and d["cpu_baseline"]["value"] > 0 and d["decompress"]["sub_indexed"]["equal_to_input"]
