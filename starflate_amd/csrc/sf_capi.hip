@@ -17,8 +17,10 @@ struct sfh_ctx {
   int device = 0;
   hipStream_t stream = nullptr;  // used when the caller passes no stream
   sf::Workspace ws{};
-  uint32_t cap_chunks = 0;       // chunks the workspace can hold
+  uint32_t cap_chunks = 0;       // chunks of a call the compressor's index arrays (ws.offsets, ws.subidx) can hold
+  uint32_t cap_batch = 0;        // chunks the compressor's batch arrays can hold
   uint32_t cap_dtok = 0;         // segments the decoder's token buffer can hold
+  size_t seginfo_cap = 0;        // bytes of ws.seginfo
   size_t sums_cap = 0;           // bytes of ws.sums
   uint32_t last_chunks = 0;
   uint32_t last_block_bytes = 0; // strip size the last compress call used
@@ -60,7 +62,6 @@ struct sfh_ctx {
   int sizes_cap = 0;
   int order_ok[2] = {0, 0};      // sfh_lds_order_check per op (0 exchange: chains, 1 masked-or: recent): 0 not run, 1 holds, -1 does not
   int force_order_fail = 0;      // SFH_FORCE_ORDER_FAIL=1: the library's own check reports failure (tests)
-  int plan_fused = 0;            // SFH_PLAN_FUSED=1: k_plan as one launch (the rounds 1-5 kernel; A/B)
   int inflate_serial = 0;        // SFH_INFLATE_SERIAL=1: index-only streams through the lane-serial kernel alone (tests, A/B)
   char err[256] = {0};
 };
@@ -91,10 +92,10 @@ int grow(sfh_ctx* ctx, T** p, size_t* cap_bytes, size_t bytes, const char* what)
   return SFH_OK;
 }
 
-void free_ws(sfh_ctx* c) {
+// the compressor's scratch; the decoder's (tokens, seginfo) and the checksum partials are sized on their own
+void free_compress_ws(sfh_ctx* c) {
   (void)hipFree(c->ws.items);
   (void)hipFree(c->ws.nitems);
-  (void)hipFree(c->ws.tokens);
   (void)hipFree(c->ws.ntok);
   (void)hipFree(c->ws.hist);
   (void)hipFree(c->ws.plan);
@@ -102,14 +103,15 @@ void free_ws(sfh_ctx* c) {
   (void)hipFree(c->ws.ptree);
   (void)hipFree(c->ws.offsets);
   (void)hipFree(c->ws.stamps);
-  (void)hipFree(c->ws.seginfo);
   (void)hipFree(c->ws.rtok);
   (void)hipFree(c->ws.subidx);
-  uint32_t* keep = c->ws.sums;  // sized on its own (ensure_sums)
+  const sf::Workspace keep = c->ws;
   c->ws = sf::Workspace{};
-  c->ws.sums = keep;
+  c->ws.tokens = keep.tokens;
+  c->ws.seginfo = keep.seginfo;
+  c->ws.sums = keep.sums;
   c->cap_chunks = 0;
-  c->cap_dtok = 0;
+  c->cap_batch = 0;
 }
 
 // checksum partials: 4 bytes per chunk, needed without the rest of the workspace by sfh_checksum_device
@@ -117,11 +119,11 @@ int ensure_sums(sfh_ctx* ctx, uint32_t nchunks) {
   return grow(ctx, &ctx->ws.sums, &ctx->sums_cap, (size_t)nchunks * sizeof(uint32_t), "checksum scratch");
 }
 
-// The per-batch arrays hold min(nchunks, kBatchChunks) chunks, the index arrays (offsets, sub-index, segment records)
-// every chunk of the call.
-int ensure_ws(sfh_ctx* ctx, uint32_t nchunks) {
+// The compressor's batch arrays hold min(nchunks, kBatchChunks) chunks, its index arrays (offsets, sub-index) every
+// chunk of the call.
+int ensure_compress_ws(sfh_ctx* ctx, uint32_t nchunks) {
   if (nchunks <= ctx->cap_chunks) return SFH_OK;
-  free_ws(ctx);
+  free_compress_ws(ctx);
   // (a strip larger than a batch is its own batch: kMaxStrip / kChunk = 512 chunks at most)
   const size_t nc = nchunks, nb = std::min<uint32_t>(nchunks, std::max<uint32_t>(ctx->batch_chunks, sf::kMaxStrip / sf::kChunk));
   hipError_t e;
@@ -134,16 +136,16 @@ int ensure_ws(sfh_ctx* ctx, uint32_t nchunks) {
       (e = hipMalloc(&ctx->ws.ptree, nb * sizeof(sf::PlanTree))) != hipSuccess ||
       (e = hipMalloc(&ctx->ws.rtok, nb * sf::kSubRegions * sizeof(uint32_t))) != hipSuccess ||
       (e = hipMalloc(&ctx->ws.offsets, (nc + 1) * sizeof(uint64_t))) != hipSuccess ||
-      (e = hipMalloc(&ctx->ws.seginfo, nc * sizeof(sf::SegInfo))) != hipSuccess ||
       (e = hipMalloc(&ctx->ws.subidx, nc * 2 * sf::kSubRegions * sizeof(uint32_t))) != hipSuccess) {
-    free_ws(ctx);
+    free_compress_ws(ctx);
     return fail(ctx, SFH_E_NOMEM, "workspace hipMalloc", e);
   }
   if (ctx->k1_stamps && (e = hipMalloc(&ctx->ws.stamps, nb * 16 * sizeof(uint64_t))) != hipSuccess) {
-    free_ws(ctx);
+    free_compress_ws(ctx);
     return fail(ctx, SFH_E_NOMEM, "stamps hipMalloc", e);
   }
   ctx->cap_chunks = nchunks;
+  ctx->cap_batch = (uint32_t)nb;
   return SFH_OK;
 }
 
@@ -249,7 +251,7 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
   (void)hipGetLastError();  // launches are checked with hipGetLastError(): drop whatever an earlier caller on this thread left
   const uint32_t nchunks = chunks_of(n);
-  int rc = ensure_ws(ctx, nchunks);
+  int rc = ensure_compress_ws(ctx, nchunks);
   if (!rc && o.container) rc = ensure_sums(ctx, nchunks);
   if (rc) return rc;
   ctx->last_chunks = nchunks;
@@ -264,7 +266,7 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
                        ef == SFH_EFFORT_MAX ? 1u : 0u,
                        !ef_chain ? 0u : o.chain_depth ? o.chain_depth
                        : ef == SFH_EFFORT_BEST ? 8u : ef == SFH_EFFORT_ULTRA ? 16u : 32u,
-                       ef_recent ? 1u : 0u, ctx->plan_fused ? 1u : 0u};
+                       ef_recent ? 1u : 0u};
   if ((ko.chain_depth || ko.recent) && (rc = ensure_order(ctx, ko.recent ? 1 : 0)) != SFH_OK) return rc;
   ctx->last_block_bytes = ko.strip_bytes;
   const bool prof = ctx->profiling != 0;
@@ -450,8 +452,6 @@ int sfh_create(sfh_ctx** out, int device) {
     if (b && atoi(b) > 0) ctx->batch_chunks = std::min<uint32_t>((uint32_t)atoi(b), sf::kBatchChunks);
     const char* f = getenv("SFH_FORCE_ORDER_FAIL");
     ctx->force_order_fail = (f && f[0] == '1');
-    const char* pf = getenv("SFH_PLAN_FUSED");
-    ctx->plan_fused = (pf && pf[0] == '1');
     const char* q = getenv("SFH_INFLATE_SERIAL");
     ctx->inflate_serial = (q && q[0] == '1');
   }
@@ -482,7 +482,9 @@ void sfh_destroy(sfh_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  free_ws(ctx);
+  free_compress_ws(ctx);
+  (void)hipFree(ctx->ws.tokens);
+  (void)hipFree(ctx->ws.seginfo);
   (void)hipFree(ctx->ws.sums);
   (void)hipFree(ctx->d_total);
   if (ctx->h_total) (void)hipHostFree(ctx->h_total);
@@ -640,11 +642,11 @@ int sfh_decompress_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const u
   // that of one pass over everything.
   const uint32_t batch = std::max(sps, ctx->batch_chunks / sps * sps);  // (a strip larger than a batch is its own batch)
   const uint32_t nbatches = (uint32_t)((nseg + batch - 1) / batch);
-  int rc = ensure_ws(ctx, (uint32_t)nseg);
+  int rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, nseg * sizeof(sf::SegInfo), "segment records");
   if (!rc) rc = ensure_dtok(ctx, (uint32_t)std::min<size_t>(nseg, batch));
   if (rc) return rc;
   ctx->last_dtok_bytes = std::min<size_t>(nseg, batch) * sf::kChunk * sizeof(uint32_t);
-  ctx->index_valid = false;  // the decoder reuses the scratch: what sfh_debug_read returns now belongs to this call
+  ctx->index_valid = false;  // the last call is now this one: what sfh_debug_read returns belongs to it
   ctx->last_chunks = (uint32_t)nseg;
   const bool prof = ctx->profiling != 0;
   if ((rc = order_behind_last_call(ctx, s)) != SFH_OK) return rc;
@@ -977,25 +979,26 @@ const char* sfh_stage_name(int stage) {
 
 int sfh_debug_read(sfh_ctx* ctx, int what, void* host_dst, size_t bytes) {
   if (!ctx || !host_dst || !ctx->last_chunks) return SFH_E_INVALID_ARG;
-  // per-batch arrays hold the last batch of the call (all of it for up to kBatchChunks chunks)
-  const size_t nc = std::min<size_t>(ctx->last_chunks, std::max<uint32_t>(ctx->batch_chunks, sf::kMaxStrip / sf::kChunk));
-  const size_t nall = ctx->last_chunks;
+  // per-batch arrays hold the last batch of the call (all of it for up to kBatchChunks chunks); each array is read no
+  // further than it was allocated: the last call may be a decode on a context whose compressor arrays are smaller or absent
+  const size_t nlast = std::min<size_t>(ctx->last_chunks, std::max<uint32_t>(ctx->batch_chunks, sf::kMaxStrip / sf::kChunk));
+  const size_t nc = std::min<size_t>(nlast, ctx->cap_batch), nidx = std::min<size_t>(ctx->last_chunks, ctx->cap_chunks);
   if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // whatever stream it ran on
   const void* p = nullptr;
   size_t avail = 0;
   switch (what) {
     case SFH_DBG_NTOK: p = ctx->ws.ntok; avail = nc * 4; break;
-    case SFH_DBG_TOKENS: p = ctx->ws.tokens; avail = ctx->cap_dtok >= nc ? nc * sf::kChunk * 4 : 0; break;
+    case SFH_DBG_TOKENS: p = ctx->ws.tokens; avail = ctx->cap_dtok >= nlast ? nlast * sf::kChunk * 4 : 0; break;
     case SFH_DBG_ITEMS: p = ctx->ws.items; avail = nc * sf::kChunk * 2; break;
     case SFH_DBG_NITEMS: p = ctx->ws.nitems; avail = nc * 4; break;
     case SFH_DBG_HIST: p = ctx->ws.hist; avail = nc * sf::kHistStride * 4; break;
     case SFH_DBG_PLAN: p = ctx->ws.plan; avail = nc * sizeof(sf::ChunkPlan); break;
-    case SFH_DBG_OFFSETS: p = ctx->ws.offsets; avail = nall * 8; break;
-    case SFH_DBG_SUBINDEX: p = ctx->ws.subidx; avail = nall * SFH_SUBINDEX_WORDS * 4; break;
+    case SFH_DBG_OFFSETS: p = ctx->ws.offsets; avail = nidx * 8; break;
+    case SFH_DBG_SUBINDEX: p = ctx->ws.subidx; avail = nidx * SFH_SUBINDEX_WORDS * 4; break;
     case SFH_DBG_STAMPS: p = ctx->ws.stamps; avail = p ? nc * 128 : 0; break;
-    case SFH_DBG_SEGINFO: p = ctx->ws.seginfo; avail = nall * sizeof(sf::SegInfo); break;
+    case SFH_DBG_SEGINFO: p = ctx->ws.seginfo; avail = std::min<size_t>(ctx->last_chunks * sizeof(sf::SegInfo), ctx->seginfo_cap); break;
     case SFH_DBG_LENS: {
-      if (bytes > nc * 320) return SFH_E_INVALID_ARG;
+      if (!ctx->ws.codes || bytes > nc * 320) return SFH_E_INVALID_ARG;
       SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
       SF_HIP(hipMemcpy2D(host_dst, 320, (const uint8_t*)ctx->ws.codes + offsetof(sf::ChunkCodes, lens),
                          sizeof(sf::ChunkCodes), 320, bytes / 320, hipMemcpyDeviceToHost), "debug copy");
@@ -1003,7 +1006,7 @@ int sfh_debug_read(sfh_ctx* ctx, int what, void* host_dst, size_t bytes) {
     }
     default: return SFH_E_INVALID_ARG;
   }
-  if (bytes > avail) return SFH_E_INVALID_ARG;
+  if (!p || bytes > avail) return SFH_E_INVALID_ARG;
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
   SF_HIP(hipMemcpy(host_dst, p, bytes, hipMemcpyDeviceToHost), "debug copy");
   return SFH_OK;

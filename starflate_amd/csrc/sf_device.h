@@ -65,6 +65,39 @@ constexpr uint32_t kHistD = 288;
 constexpr uint32_t kHistLen = 320;      // k_lz77 counts match lengths raw; k_plan folds them into ll[257..285]
 constexpr uint32_t kHeaderWords = 152;  // 608 bytes >= 4495-bit worst-case dynamic header + 3
 
+// Wave-wide scans on the DPP network (no LDS round trips), for the encoder's and the decoder's kernels alike.  Identity 0;
+// a lane whose source does not exist keeps the identity (`old` operand, bound_ctrl off).  row_shr:n = 0x110+n,
+// row_bcast:15 = 0x142 (rows 1 and 3), row_bcast:31 = 0x143 (rows 2 and 3), wave_shr:1 = 0x138.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_from(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_add_from(uint32_t v) {
+  return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
+}
+__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v) {
+  v = dpp_add_from<0x111, 0xF>(v);
+  v = dpp_add_from<0x112, 0xF>(v);
+  v = dpp_add_from<0x114, 0xF>(v);
+  v = dpp_add_from<0x118, 0xF>(v);
+  v = dpp_add_from<0x142, 0xA>(v);
+  v = dpp_add_from<0x143, 0xC>(v);
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_excl_max(uint32_t v) {
+  v = max(v, dpp_from<0x111, 0xF>(v));
+  v = max(v, dpp_from<0x112, 0xF>(v));
+  v = max(v, dpp_from<0x114, 0xF>(v));
+  v = max(v, dpp_from<0x118, 0xF>(v));
+  v = max(v, dpp_from<0x142, 0xA>(v));
+  v = max(v, dpp_from<0x143, 0xC>(v));
+  return dpp_from<0x138, 0xF>(v);
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_add(v), 63);
+}
+
 // per-chunk plan record written by K2, read by K3/K4
 struct ChunkPlan {
   uint32_t btype;        // 0 stored, 1 fixed, 2 dynamic
@@ -129,7 +162,7 @@ struct Options {
   uint32_t strategy;
   uint32_t final_stream;
   uint32_t lazy;
-  uint32_t fast_skip;     // 0: off; 1: stored fast path; 2: ... and a chunk may be stored by its probe (strategy 0: sf_capi.hip)
+  uint32_t fast_skip;     // 0: off; 1: stored fast path; 2: ... and a chunk may be stored by its probe (strategy 0 only: launch_lz77)
   uint32_t strip_bytes;  // multiple of kChunk
   uint32_t depth2;       // 1: both history levels of a hash bucket are tried, 0: the newer one only
   uint32_t near;         // 1: the step-local candidate is tried as well (always with depth2)
@@ -137,7 +170,6 @@ struct Options {
   uint32_t long_table;   // 1: two tables of 4096 buckets, keyed by four and by seven bytes (with stride2 = 0: SFH_EFFORT_MAX)
   uint32_t chain_depth;  // > 0: exact hash chains of this depth instead of the step tables (SFH_EFFORT_BEST 8, _ULTRA 16, _EXTREME 32)
   uint32_t recent;       // 1: exact recency (SFH_EFFORT_RECENT): buckets {latest, the one before the latest inserting step} + the exact predecessor
-  uint32_t plan_fused;   // 1: k_plan as ONE launch, its merges on lane 0 of every chunk's wave (the rounds 1-5 kernel; SFH_PLAN_FUSED=1, for A/B)
 };
 
 hipError_t launch_lz77(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws,

@@ -905,24 +905,6 @@ __global__ __launch_bounds__(64, 2) void k_inflate_tokens_spec(const uint8_t* __
   tokens_wave_spec(src, src_n, index, nseg, dst_n, tokens, info, sps);
 }
 
-// inclusive wave scan on the DPP network (row_shr 1/2/4/8, row_bcast 15/31): no LDS round trips
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_add_from(uint32_t v) {
-  return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
-}
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, uint32_t /*lane*/) {
-  v = dpp_add_from<0x111, 0xF>(v);
-  v = dpp_add_from<0x112, 0xF>(v);
-  v = dpp_add_from<0x114, 0xF>(v);
-  v = dpp_add_from<0x118, 0xF>(v);
-  v = dpp_add_from<0x142, 0xA>(v);
-  v = dpp_add_from<0x143, 0xC>(v);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_incl(v, 0), 63);
-}
-
 __device__ __forceinline__ uint32_t load_word_guarded(const uint8_t* base, uint64_t src_n, uint64_t w) {
   const uint64_t b = 4 * w;
   if (b + 4 <= src_n) return reinterpret_cast<const uint32_t*>(base)[w];
@@ -1050,7 +1032,7 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
       len[k] = val[k] ? (mat[k] ? ((tok[k] >> 16) & 0xFFu) + 3u : 1u) : 0u;
       mine += len[k];
     }
-    const uint32_t incl = wave_scan_incl(mine, lane);
+    const uint32_t incl = wave_incl_add(mine);
     if (lane == 63) s_w[wave] = incl;
     __syncthreads();
     uint32_t pre = 0;
@@ -1075,7 +1057,7 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
     }
     {
       // where the next step starts: the fitting tokens are a prefix, so their count and the largest end say it
-      const uint32_t nfit_w = wave_sum_u32(nfit);
+      const uint32_t nfit_w = wave_sum(nfit);
       const uint64_t fitting = __ballot(nfit != 0);
       if (fitting) {
         // (a prefix of the tokens fits: the wave's last fitting lane knows the largest end)
@@ -1110,7 +1092,7 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
       // tokens starting before each bitmap word: one wave, two words per lane
       const uint32_t a = 2 * lane < kWords ? (uint32_t)__popc(s_mark[2 * lane]) : 0u;
       const uint32_t b2 = 2 * lane + 1 < kWords ? (uint32_t)__popc(s_mark[2 * lane + 1]) : 0u;
-      const uint32_t inc2 = wave_scan_incl(a + b2, lane);
+      const uint32_t inc2 = wave_incl_add(a + b2);
       if (2 * lane < kWords) s_wpre[2 * lane] = inc2 - a - b2;
       if (2 * lane + 1 < kWords) s_wpre[2 * lane + 1] = inc2 - b2;
     }
@@ -1145,7 +1127,7 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
     // kernel's 3.25 per GiB went into those two passes).  A step with more pointers than the lists hold -- runs,
     // short periods -- takes the passes over every byte, as before.
     const uint32_t pcnt = (uint32_t)__popc(pm);
-    const uint32_t pincl = wave_scan_incl(pcnt, lane);
+    const uint32_t pincl = wave_incl_add(pcnt);
     const uint32_t wtotal = (uint32_t)__builtin_amdgcn_readlane((int)pincl, 63);
     if (!wg_any(wtotal > kListCap)) {
       uint16_t* lst = reinterpret_cast<uint16_t*>(s_tinfo) + wave * kListCap;

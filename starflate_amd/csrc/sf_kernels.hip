@@ -45,37 +45,6 @@ __device__ __forceinline__ uint32_t fixed_ll_len(uint32_t s) {
   return s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
 }
 
-// Wave-wide scans on the DPP network (no LDS round trips).  Identity 0; a lane whose source does not exist keeps
-// the identity (`old` operand, bound_ctrl off).  row_shr:n = 0x110+n, row_bcast:15 = 0x142 (rows 1 and 3),
-// row_bcast:31 = 0x143 (rows 2 and 3), wave_shr:1 = 0x138.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_from(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
-}
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v) {
-  v += dpp_from<0x111, 0xF>(v);
-  v += dpp_from<0x112, 0xF>(v);
-  v += dpp_from<0x114, 0xF>(v);
-  v += dpp_from<0x118, 0xF>(v);
-  v += dpp_from<0x142, 0xA>(v);
-  v += dpp_from<0x143, 0xC>(v);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_excl_max(uint32_t v) {
-  v = max(v, dpp_from<0x111, 0xF>(v));
-  v = max(v, dpp_from<0x112, 0xF>(v));
-  v = max(v, dpp_from<0x114, 0xF>(v));
-  v = max(v, dpp_from<0x118, 0xF>(v));
-  v = max(v, dpp_from<0x142, 0xA>(v));
-  v = max(v, dpp_from<0x143, 0xC>(v));
-  return dpp_from<0x138, 0xF>(v);
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_add(v), 63);
-}
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t /*lane*/) { return wave_incl_add(v); }
-
 // est_log2(x) ~ 256 * log2(x) for x >= 1: the exponent and the top six mantissa bits through a table -- plain integers, the
 // same in the specification (oracle: est_log2), so the stored-without-a-code rule of k_plan and the stored-by-the-probe rule of k_lz77 decide alike on both sides
 __constant__ uint8_t c_est_lg64[64] = {0, 6, 11, 17, 22, 28, 33, 38, 44, 49, 54, 59, 63, 68, 73, 78, 82, 87, 92, 96, 100, 105, 109, 113, 118, 122,
@@ -221,27 +190,6 @@ __device__ __forceinline__ void rank8x2(const uint32_t* d32, uint32_t a0, uint32
   la = rank_of(a0, a1, p0, p1, p2, ca & 3, maxlen);
   lb = rank_of(a0, a1, q0, q1, q2, cb & 3, maxlen);
 }
-
-// SENSITIVITY PROBE (diagnostic builds only: -DSF_PROBE_STAGE / _MATCH / _PARSE / _EMIT=<n>, tools/exp/probe_phases.sh): n dead
-// vector instructions (v_xor of a register with itself, the cheap issue class) in one phase of k_lz77 -- what a phase's
-// time costs the kernel per instruction says whether taking instructions OUT of it can pay.  Compiled out otherwise.
-template <int N>
-__device__ __forceinline__ void probe_valu(uint32_t& r) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) asm volatile("v_xor_b32 %0, %0, %0" : "+v"(r));
-}
-#ifndef SF_PROBE_STAGE
-#define SF_PROBE_STAGE 0
-#endif
-#ifndef SF_PROBE_MATCH
-#define SF_PROBE_MATCH 0
-#endif
-#ifndef SF_PROBE_PARSE
-#define SF_PROBE_PARSE 0
-#endif
-#ifndef SF_PROBE_EMIT
-#define SF_PROBE_EMIT 0
-#endif
 
 // Workgroup barrier that orders LDS traffic only: the match step keeps a global store (the position's distance, see
 // k_lz77) in flight across its barriers, which __syncthreads() would wait for twice per step
@@ -425,7 +373,6 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         if (t < kUnits - 2 * K1_THREADS) s4[2 * K1_THREADS + t] = c2;
       }
       if (!reload) *reinterpret_cast<uint2*>(&s_data[(kWindow + kLook) / 4 + 2 * t]) = make_uint2(pre_lo, pre_hi);
-      if constexpr (SF_PROBE_STAGE > 0) { uint32_t pr = t; probe_valu<SF_PROBE_STAGE>(pr); }
       // (RECENT asks for them behind the match phase, whose serial pass wants the registers: parse and emit hide the latency)
       if (!RECENT && r + 1 < nrounds) {
         pre_lo = load4(rb + kRound + kLook + 8 * t);
@@ -981,7 +928,6 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
               }
             }
           }
-          if constexpr (SF_PROBE_MATCH > 0) { uint32_t pr = t; probe_valu<SF_PROBE_MATCH>(pr); }
           // @phase match.barrier trips=8 depth=2
           if (it == nsteps) break;
           lds_barrier();  // every read of the table as it stands before step `it` precedes the step's insertions
@@ -1068,7 +1014,6 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
       // then one barrier and
       //   emit    : every lane writes its (at most eight) items at their compact place, + histogram
       const uint32_t pb = 8 * t;                       // the lane's first position, round-relative
-      if constexpr (SF_PROBE_PARSE > 0) { uint32_t pr = t; probe_valu<SF_PROBE_PARSE>(pr); }
       const uint32_t nv = qn > pb ? (qn - pb < 8 ? qn - pb : 8u) : 0u;  // its valid positions
       uint32_t T = 0;                                  // take bits of the eight positions
       uint32_t N = 0;                                  // their 4-bit lengths
@@ -1405,7 +1350,6 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
       // @phase emit.head trips=1
       // ---- emit: the lane's chain positions -> items (compact, chunk order) + histogram ----
       if (marks) {
-        if constexpr (SF_PROBE_EMIT > 0) { uint32_t pr = t; probe_valu<SF_PROBE_EMIT>(pr); }
         const uint32_t before = wbase + incl - mine;
         const uint32_t ib0 = 2u * (tot_items + (before & 0xFFFFu) + (before >> 16));  // byte offset of the lane's first item
         // items of the lane before position k: one per token before it, one more per match before it -- one
@@ -1697,10 +1641,10 @@ __device__ void finish_lengths(PlanSmem& S, uint32_t m, uint32_t maxbits, uint8_
   __syncthreads();
 }
 
-template <uint32_t NG>
+// all three parts in one wave, the merge on lane 0: for the 19-symbol code-length code, whose merges are few
 __device__ void build_lengths(PlanSmem& S, const uint32_t* freq, uint32_t n, uint32_t maxbits,
                               uint8_t* lens, uint32_t lane) {
-  const uint32_t m = sort_symbols<NG>(S, freq, n, lens, lane);
+  const uint32_t m = sort_symbols<1>(S, freq, n, lens, lane);
   if (m < 2) return;
   for (uint32_t k = lane; k < m; k += 64) S.w[k] = (uint16_t)(S.key[k] >> 9);
   __syncthreads();
@@ -1714,8 +1658,9 @@ __device__ void build_lengths(PlanSmem& S, const uint32_t* freq, uint32_t n, uin
 // canonical codes (RFC 1951 3.2.2 == huffman::table::canonicalize,
 // /root/reference/huffman/src/table.hpp:177-216), stored bit-reversed because the
 // decoder shifts code bits in MSB-first (huffman/src/decode.hpp:90-91).
-// out[s] = reversed code | len << 16.  n <= 320, all lanes call it.
-__device__ void canonical_codes(const uint8_t* lens, uint32_t n, uint32_t* out, uint32_t lane) {
+// out[s] = reversed code | len << 16.  n <= 320, all lanes call it.  Out of line: inlined at k_plan_finish's three
+// calls it spills scalar registers to lanes (plan stage 0.274 against 0.265 ms per GiB of text).
+__device__ __noinline__ void canonical_codes(const uint8_t* lens, uint32_t n, uint32_t* out, uint32_t lane) {
   uint32_t base[16];
 #pragma unroll
   for (int l = 0; l < 16; ++l) base[l] = 0;
@@ -1807,7 +1752,7 @@ __device__ uint32_t rle_parallel(PlanSmem& S, const uint8_t* lens, uint32_t n, u
         cnt = 1 + q + ((rem >= 3) ? 1u : rem);
       }
     }
-    const uint32_t incl = wave_incl_scan(cnt, lane);
+    const uint32_t incl = wave_incl_add(cnt);
     uint32_t k = base + total + incl - cnt;
     auto put = [&](uint32_t sym, uint32_t ext) {
       S.rle_sym[k] = (uint8_t)sym;
@@ -1835,11 +1780,11 @@ __device__ uint32_t rle_parallel(PlanSmem& S, const uint8_t* lens, uint32_t n, u
 
 __constant__ uint8_t c_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
-// MODE 0 (k_plan): the whole plan in one launch (rounds 1-5; SFH_PLAN_FUSED=1).  Round 6 -- three launches: MODE 1 (k_plan_sort)
-// loads, folds, decides "stored without a code", SORTS both alphabets and leaves keys and weights in PlanTree; k_plan_merge
-// builds the trees, one chunk per LANE; MODE 2 (k_plan_finish) picks the parents up, finishes the lengths and does the rest.  The two-queue merge is serial in the
-// merges: on lane 0 of a chunk's wave it was 46 % of k_plan's cycles at 1/64 of the lanes -- 58 merges per chunk on text,
-// 280 on machine code (1.0 ms per GiB there) -- and with a chunk per lane 64 of them share every instruction.
+// K2 in three launches: MODE 1 (k_plan_sort) loads, folds, decides "stored without a code", SORTS both alphabets and leaves
+// keys and weights in PlanTree; k_plan_merge builds the trees, one chunk per LANE; MODE 2 (k_plan_finish) picks the parents
+// up, finishes the lengths and does the rest.  The two-queue merge is serial in the merges: on lane 0 of a chunk's wave it
+// was 46 % of the stage's cycles at 1/64 of the lanes -- 58 merges per chunk on text, 280 on machine code (1.0 ms per GiB
+// there) -- and with a chunk per lane 64 of them share every instruction.
 template <int MODE>
 __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
                                            uint32_t* __restrict__ hist, const uint32_t* __restrict__ ntok,
@@ -1865,13 +1810,13 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
   const uint32_t n_raw = (uint32_t)((n_total - cbase) < (uint64_t)kChunk ? (n_total - cbase) : kChunk);
   const bool fin = (chunk + 1 == nchunks) && final_stream;
 
-  [[maybe_unused]] PlanTree* const T = MODE ? ptree + chunk : nullptr;
+  PlanTree* const T = ptree + chunk;
   if constexpr (MODE == 2) {
     if (T->done) return;  // (uniform: stored without a code by the sorting pass)
   }
   // A chunk with bytes but NO tokens was stored by k_lz77's probe (round 6; probe_span_is_noise in the specification, only ever
   // with strategy 0): it has no histogram -- k_lz77 wrote none -- and nothing to plan
-  if (MODE != 2 && strategy == 0 && n_raw != 0 && ntok[chunk] == 0) {  // (uniform)
+  if (MODE == 1 && strategy == 0 && n_raw != 0 && ntok[chunk] == 0) {  // (uniform)
     ChunkCodes& C0 = codes[chunk];
     for (uint32_t s0 = lane; s0 < 320; s0 += 64) C0.lens[s0] = 0;
     if (lane == 0) {
@@ -1882,20 +1827,20 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
       P.header_bits = 3;
       P.body_bits = 0;
       plan[chunk] = P;
-      if constexpr (MODE == 1) T->done = 1;
+      T->done = 1;
     }
     return;
   }
   // both halves of the chunk's histogram are requested at once (one memory round trip, not two in a row)
   uint32_t rawf[4] = {0, 0, 0, 0};
-  if constexpr (MODE != 2) {
+  if constexpr (MODE == 1) {
 #pragma unroll
     for (uint32_t q = 0; q < 4; ++q) rawf[q] = hist[(uint64_t)chunk * kHistStride + kHistLen + lane + 64 * q];
   }
   for (uint32_t s = lane; s < 320; s += 64) S.freq[s] = hist[(uint64_t)chunk * kHistStride + s];
   for (uint32_t s = lane; s < 320; s += 64) S.lens[s] = 0;
   __syncthreads();
-  if constexpr (MODE != 2) {  // (the finishing pass finds the counts folded: the sorting pass wrote them back)
+  if constexpr (MODE == 1) {  // (the finishing pass finds the counts folded: the sorting pass wrote them back)
     // k_lz77 counted match lengths raw (len-3 at kHistLen + 0..255): fold them into the length symbols 257..285
 #pragma unroll
     for (uint32_t q = 0; q < 4; ++q) {
@@ -1907,7 +1852,7 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
   }
 
   stamp();  // 0 load
-  if (MODE != 2 && strategy == 0) {
+  if (MODE == 1 && strategy == 0) {
     // A chunk that is (all but) incompressible is STORED without building a code: when the fixed block is no shorter than
     // the stored one and the ESTIMATE of the dynamic block -- the symbols' entropy in fixed point (est_log2: a 64-entry
     // table, the same integers in the specification) + extra bits + the shortest header -- comes within kStoreMargin
@@ -1946,17 +1891,12 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
         P.header_bits = 3;
         P.body_bits = 0;
         plan[chunk] = P;
-        if constexpr (MODE == 1) T->done = 1;
+        T->done = 1;
       }
       return;
     }
   }
-  if constexpr (MODE == 0) {
-    build_lengths<5>(S, S.freq, 286, 15, S.lens, lane);
-    stamp();  // 1 lit/len lengths
-    build_lengths<1>(S, S.freq + kHistD, 30, 15, S.lens + 288, lane);
-    stamp();  // 2 distance lengths
-  } else if constexpr (MODE == 1) {
+  if constexpr (MODE == 1) {
     // the sorting pass: both alphabets' used symbols ascending by (count, symbol), keys and weights for the merge pass
     const uint32_t m_ll = sort_symbols<5>(S, S.freq, 286, S.lens, lane);
     if (m_ll >= 2)
@@ -1976,7 +1916,7 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
     return;
   } else {
     // the finishing pass: the sorted keys and the merge pass's parents -> lengths (an alphabet of fewer than two used symbols
-    // needs no tree: sort_symbols settles it, as in the one-launch kernel)
+    // needs no tree: sort_symbols settles it)
     const uint32_t m_ll = T->m_ll, m_d = T->m_d;
     if (m_ll < 2) {
       sort_symbols<5>(S, S.freq, 286, S.lens, lane);
@@ -2038,7 +1978,7 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
   const uint32_t nitems = nl + nd;
   __syncthreads();
   stamp();  // 3 costs + RLE
-  build_lengths<1>(S, S.clfreq, 19, 7, S.cl_lens, lane);
+  build_lengths(S, S.clfreq, 19, 7, S.cl_lens, lane);
   canonical_codes(S.cl_lens, 19, S.cl_code, lane);
   __syncthreads();
   stamp();  // 4 code-length code
@@ -2065,7 +2005,7 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
         v = (uint64_t)(c & 0xFFFF) | ((uint64_t)S.rle_ext[k] << cl);
         nb = cl + eb;
       }
-      const uint32_t incl = wave_incl_scan(nb, lane);
+      const uint32_t incl = wave_incl_add(nb);
       if (nb) or_bits(s_header, bitbase + incl - nb, v);
       bitbase += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     }
@@ -2124,7 +2064,6 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
                                              uint64_t* __restrict__ stamps, PlanTree* __restrict__ ptree) {                   \
     plan_chunk<MODE>(n_total, nchunks, hist, ntok, plan, codes, strategy, final_stream, stamps, ptree);                       \
   }
-SF_PLAN_KERNEL(k_plan, 0)         // one launch (rounds 1-5; SFH_PLAN_FUSED=1)
 SF_PLAN_KERNEL(k_plan_sort, 1)    // K2a
 SF_PLAN_KERNEL(k_plan_finish, 2)  // K2c
 #undef SF_PLAN_KERNEL
@@ -2478,7 +2417,7 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
         starts |= ((e[k] & (kItemTok | kItemRegion)) == (kItemTok | kItemRegion) && i_now + k < nit) ? 1u << k : 0u;
     }
     // @phase k4.scan trips=1
-    const uint32_t incl = wave_incl_scan(mine, lane);
+    const uint32_t incl = wave_incl_add(mine);
     if (lane == 63) s_wtot[buf][wave] = incl;
     __syncthreads();
     uint32_t pre = 0, all = 0;
@@ -2562,6 +2501,8 @@ hipError_t init_kernels() { return hipSuccess; }
 hipError_t launch_lz77(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws,
                        const Options& opt, hipStream_t s) {
   if (opt.strip_bytes == 0 || opt.strip_bytes % kChunk || opt.strip_bytes > kMaxStrip) return hipErrorInvalidValue;
+  // a chunk stored by its probe gets no tokens and no histogram: k_plan_sort stores such a chunk only under strategy 0
+  if (opt.fast_skip == 2 && opt.strategy != 0) return hipErrorInvalidValue;
   const uint32_t per = opt.strip_bytes / kChunk;
   const uint32_t nstrips = (nchunks + per - 1) / per;
   const auto launch = [&](auto kernel, uint64_t* stamps) {
@@ -2602,11 +2543,7 @@ hipError_t launch_lz77(const uint8_t* src, uint64_t n, uint32_t nchunks, const W
 }
 hipError_t launch_plan(uint64_t n, uint32_t nchunks, const Workspace& ws, const Options& opt,
                        hipStream_t s) {
-  if (opt.plan_fused || !ws.ptree) {
-    hipLaunchKernelGGL(k_plan, dim3(nchunks), dim3(64), 0, s, n, nchunks, ws.hist, ws.ntok, ws.plan, ws.codes,
-                       opt.strategy, opt.final_stream, ws.stamps, (PlanTree*)nullptr);
-    return hipGetLastError();
-  }
+  if (!ws.ptree) return hipErrorInvalidValue;
   // sort (a wave per chunk) -> merge (a lane per chunk) -> finish (a wave per chunk)
   hipLaunchKernelGGL(k_plan_sort, dim3(nchunks), dim3(64), 0, s, n, nchunks, ws.hist, ws.ntok, ws.plan, ws.codes,
                      opt.strategy, opt.final_stream, (uint64_t*)nullptr, ws.ptree);

@@ -117,3 +117,13 @@ def test_item_format_constants_match_the_python_decoder():
     with open(os.path.join(ROOT, "include", "starflate_hip.h")) as f:
         doc = f.read()
     assert "0x8000 | byte" in doc and "0x8100 | len-3" in doc and "bits 9..13" in doc
+
+
+def test_cmake_builds_the_same_sources_as_build_py():
+    """CMakeLists.txt and starflate_amd/build.py compile the library from one list of HIP sources: a file missing from
+    either leaves that build's library with undefined symbols."""
+    with open(os.path.join(ROOT, "CMakeLists.txt")) as f:
+        m = re.search(r"set\(HIP_SOURCES\s+([^)]*)\)", f.read())
+    assert m, "no set(HIP_SOURCES ...) in CMakeLists.txt"
+    cmake = [os.path.basename(s) for s in m.group(1).split()]
+    assert sorted(cmake) == sorted(build.SOURCES), (cmake, build.SOURCES)

@@ -508,3 +508,39 @@ def test_decoder_batches(monkeypatch):
     finally:
         small.close()
         ref.close()
+
+
+def test_decode_only_context_holds_no_compressor_scratch():
+    """A context that only decodes allocates the decoder's scratch alone: the compressor's arrays do not exist, so reading
+    them is refused, while the segment records are there.  A decode of more segments than an earlier compress had chunks
+    does not grow the compressor's arrays either, so a read of them sized by the decode is refused."""
+    from starflate_amd import Compressor, StarflateError
+
+    nseg = 100
+    data = synth.gen_text(nseg * CHUNK - 5, seed=21)
+    enc = Compressor(0)
+    try:
+        stream = np.frombuffer(enc.compress(data), np.uint8)
+        index, bb = enc.last_index(), enc.last_block_bytes()
+    finally:
+        enc.close()
+    dec = Compressor(0)
+    try:
+        back, st = dec.decompress(stream, index, data.size, block_bytes=bb)
+        assert st == 0 and back == data.tobytes()
+        for what in (_capi.DBG_ITEMS, _capi.DBG_HIST, _capi.DBG_PLAN):
+            with pytest.raises(StarflateError) as e:
+                dec.debug(what, 1)
+            assert e.value.code == -1, what  # SFH_E_INVALID_ARG
+        info = dec.debug(_capi.DBG_SEGINFO, nseg)
+        assert (info[:, 0] == 0).all() and int(info[:, 3].sum()) == data.size
+        # one chunk compressed, then the hundred segments decoded
+        dec.compress(data[:CHUNK])
+        back, st = dec.decompress(stream, index, data.size, block_bytes=bb)
+        assert st == 0 and back == data.tobytes()
+        dec.debug(_capi.DBG_ITEMS, 1)  # (the one chunk the compressor's arrays hold)
+        with pytest.raises(StarflateError) as e:
+            dec.debug(_capi.DBG_ITEMS, nseg)
+        assert e.value.code == -1
+    finally:
+        dec.close()

@@ -178,11 +178,10 @@ def test_batches_give_the_stream_of_one_launch(monkeypatch):
         c.close()
 
 
-def test_plan_in_three_launches_and_in_one(monkeypatch):
-    """k_plan runs as sort / merge (a chunk per LANE) / finish since round 6; SFH_PLAN_FUSED=1 (read at sfh_create) is the one
-    launch of rounds 1-5.  Both give the specification's code lengths: alphabets of every width (one symbol, two, all 256
-    literals + every length + every distance), chunk counts that do not fill the merge kernel's waves (1, 63, 64, 65, 130),
-    stored and fixed chunks in between (their lanes leave early), and more than one batch."""
+def test_plan_in_three_launches(monkeypatch):
+    """k_plan runs as sort / merge (a chunk per LANE) / finish and gives the specification's code lengths: alphabets of every
+    width (one symbol, two, all 256 literals + every length + every distance), chunk counts that do not fill the merge kernel's
+    waves (1, 63, 64, 65, 130), stored and fixed chunks in between (their lanes leave early), and more than one batch."""
     from starflate_amd import Compressor
 
     rng = np.random.default_rng(66)
@@ -191,15 +190,14 @@ def test_plan_in_three_launches_and_in_one(monkeypatch):
               np.frombuffer(rng.bytes(9000) * 11, np.uint8), rng.integers(0, 64, CHUNK - 1, dtype=np.uint8)]
     wide = np.concatenate(pieces)
     cases = [wide[:1], wide[:CHUNK], wide[: 63 * CHUNK // 4], np.concatenate([wide] * 5)[: 130 * CHUNK - 3], synth.gen_text(65 * CHUNK, seed=63)]
-    for fused, bc in (("0", None), ("1", None), ("0", "3")):
-        monkeypatch.setenv("SFH_PLAN_FUSED", fused)
+    for bc in (None, "3"):
         if bc:
             monkeypatch.setenv("SFH_BATCH_CHUNKS", bc)
         c = Compressor(0)
         for k, data in enumerate(cases):
             for effort, ekw in (("default", {}), ("best", dict(chain_depth=8))):
                 got = np.frombuffer(c.compress(data, effort=effort), np.uint8)
-                assert np.array_equal(got, O.compress(data, O.default_params(**ekw))), (fused, bc, k, effort)
+                assert np.array_equal(got, O.compress(data, O.default_params(**ekw))), (bc, k, effort)
         c.close()
 
 
