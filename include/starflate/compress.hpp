@@ -140,6 +140,31 @@ class compressor {
     if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
     return n;
   }
+  /// host spans, many independent items in one call: item i's stream goes to dsts[i] (dsts[i].size() >=
+  /// compress_bound(srcs[i].size())), its size to sizes[i]; byte-identical to compress(srcs[i], dsts[i], opt).
+  /// Returns the bytes of all streams together.
+  auto compress_batch(std::span<const std::span<const std::byte>> srcs, std::span<const std::span<std::byte>> dsts,
+                      std::span<std::size_t> sizes, const compress_options& opt = {})
+      -> compat::expected<std::size_t, CompressStatus> {
+    if (!ctx_) return compat::unexpected{init_};
+    if (dsts.size() != srcs.size() || sizes.size() != srcs.size()) return compat::unexpected{CompressStatus::InvalidArgument};
+    const std::size_t k = srcs.size();
+    std::vector<const void*> sp(k);
+    std::vector<void*> dp(k);
+    std::vector<std::uint64_t> n(k), cap(k), out(k);
+    for (std::size_t i = 0; i < k; ++i) {
+      sp[i] = srcs[i].data();
+      n[i] = srcs[i].size();
+      dp[i] = dsts[i].data();
+      cap[i] = dsts[i].size();
+    }
+    const auto c = detail::to_c(opt);
+    const int rc = sfh_compress_batch(ctx_, k, sp.data(), n.data(), dp.data(), cap.data(), out.data(), &c);
+    if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+    std::size_t total = 0;
+    for (std::size_t i = 0; i < k; ++i) total += sizes[i] = static_cast<std::size_t>(out[i]);
+    return total;
+  }
   /// index of the last compress call on this object (with_regions: also the per-region sub-index)
   auto index(bool with_regions = true) -> compat::expected<stream_index, CompressStatus> {
     if (!ctx_) return compat::unexpected{init_};

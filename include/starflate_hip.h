@@ -221,6 +221,29 @@ int sfh_compress_device(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, 
 int sfh_compress_device_async(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap,
                               uint64_t* d_out_n, const sfh_options* opt, void* stream);
 
+/* ---- batched compression: `count` independent items, each its own complete stream, in one call ----
+ * Item i's stream (raw, or zlib / gzip with its own header and trailer) is byte-identical to what
+ * sfh_compress(ctx, item_i, n_i, ..., opt) writes alone; block_bytes = 0 resolves per item, from n_i (so items below
+ * 16 MiB get 32 KiB strips).  The items are cut into launch batches of whole items (at most 32768 chunks, 1 GiB of input;
+ * SFH_BATCH_CHUNKS lowers it; a larger item gets launch batches of its own) that run the single call's kernels over
+ * descriptor tables, so a call on many small items fills the GPU as one large call does.
+ * Everything is checked before anything is enqueued: bad options, a null array or pointer, a device source not 16-byte
+ * or a device destination not 4-byte aligned, an item above 2^44 bytes and two overlapping destination ranges
+ * [dst_i, dst_i + dst_cap[i]) are SFH_E_INVALID_ARG; dst_cap[i] < sfh_compress_bound(src_n[i], 0) is SFH_E_DST_TOO_SMALL.
+ * count == 0 is SFH_OK and does nothing.  After a batch call the context has no block index: sfh_index_entries() is 0,
+ * sfh_copy_index / sfh_copy_subindex are SFH_E_INVALID_ARG, sfh_last_block_bytes() is 0; sfh_last_stage_ms works.
+ *
+ * Device buffers, enqueued on `stream` (NULL: the context's), no host synchronisation.  The host arrays are read before
+ * the call returns; item i's stream size lands in d_out_n[i] (device memory, uint64). */
+int sfh_compress_batch_device_async(sfh_ctx* ctx, size_t count,
+                                    const void* const* d_srcs, const uint64_t* src_n,
+                                    void* const* d_dsts, const uint64_t* dst_cap,
+                                    uint64_t* d_out_n, const sfh_options* opt, void* stream);
+/* Host buffers, synchronous: the items travel through pinned staging, packed (one copy per 64 MiB each way, not one per
+ * item); out_n[i] on the host. */
+int sfh_compress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n,
+                       void* const* dsts, const uint64_t* dst_cap, uint64_t* out_n, const sfh_options* opt);
+
 /* ---- measurement hooks (bench.py, tests) ---- */
 
 /* ---- block index + GPU decompress ----

@@ -98,6 +98,54 @@ class Compressor:
         self._check(self._lib.sfh_compress_device_async(self._h, src.data_ptr() if n else None, n, out.data_ptr(),
                                                         out.numel(), size_out.data_ptr(), C.byref(opt), C.c_void_p(s)))
 
+    # ---- many independent items, each its own stream, in one call (sfh_compress_batch*) ----
+    def compress_batch(self, items, strategy="auto", final_stream=True, lazy=True, stored_fast_path=True, container="raw",
+                       block_bytes=0, effort="default"):
+        """Host buffers: a sequence of bytes-like items -> list of streams, item i's byte-identical to compress(items[i])
+        with the same options (block_bytes=0 resolves per item)."""
+        srcs = [np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else np.ascontiguousarray(d, dtype=np.uint8).ravel()
+                for d in items]
+        k = len(srcs)
+        n = (C.c_uint64 * k)(*[a.size for a in srcs])
+        caps = [self.compress_bound(a.size) for a in srcs]
+        dsts = [np.empty(c, dtype=np.uint8) for c in caps]
+        sp = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a in srcs])
+        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
+        out_n = (C.c_uint64 * k)()
+        opt = _capi.make_options(strategy, final_stream, lazy, stored_fast_path, container, block_bytes, effort)
+        self._check(self._lib.sfh_compress_batch(self._h, k, sp, n, dp, (C.c_uint64 * k)(*caps), out_n, C.byref(opt)))
+        return [dsts[i][: out_n[i]].tobytes() for i in range(k)]
+
+    def compress_batch_tensors(self, srcs, outs=None, stream=None, strategy="auto", final_stream=True, lazy=True,
+                               stored_fast_path=True, container="raw", block_bytes=0, effort="default"):
+        """Device buffers: 1-D uint8 tensors on this device -> (outs, sizes).  Enqueued on `stream` (default: the current
+        one) without a host synchronisation; sizes is an int64 tensor on the device, valid once the stream gets there.
+        outs default to new tensors of compress_bound(n) bytes."""
+        import torch
+
+        srcs = list(srcs)
+        for t in srcs:
+            self._check_tensor(t)
+        k = len(srcs)
+        dev = torch.device("cuda", self.device)
+        if outs is None:
+            outs = [torch.empty(self.compress_bound(t.numel()), dtype=torch.uint8, device=dev) for t in srcs]
+        outs = list(outs)
+        if len(outs) != k:
+            raise ValueError("outs must hold one tensor per item")
+        for t in outs:
+            self._check_tensor(t)
+        sizes = torch.empty(k, dtype=torch.int64, device=dev)  # (every entry is written by the call)
+        sp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in srcs])
+        dp = (C.c_void_p * k)(*[t.data_ptr() for t in outs])
+        n = (C.c_uint64 * k)(*[t.numel() for t in srcs])
+        caps = (C.c_uint64 * k)(*[t.numel() for t in outs])
+        opt = _capi.make_options(strategy, final_stream, lazy, stored_fast_path, container, block_bytes, effort)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        self._check(self._lib.sfh_compress_batch_device_async(self._h, k, sp, n, dp, caps, C.c_void_p(sizes.data_ptr()),
+                                                              C.byref(opt), C.c_void_p(s)))
+        return outs, sizes
+
     # ---- block index + GPU decompress (the reference's decompress(), /root/reference/src/decompress.hpp:63-71,
     #      for streams whose independently decodable 32 KiB segments are known) ----
     def last_block_bytes(self):
@@ -319,3 +367,11 @@ def compress(data, device=0, **kw):
     if c is None:
         c = _DEFAULT[device] = Compressor(device)
     return c.compress(data, **kw)
+
+
+def compress_batch(items, device=0, **kw):
+    """A sequence of bytes-like items -> one stream per item, all in one call (Compressor.compress_batch)."""
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    return c.compress_batch(items, **kw)

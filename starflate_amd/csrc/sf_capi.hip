@@ -63,6 +63,17 @@ struct sfh_ctx {
   int order_ok[2] = {0, 0};      // sfh_lds_order_check per op (0 exchange: chains, 1 masked-or: recent): 0 not run, 1 holds, -1 does not
   int force_order_fail = 0;      // SFH_FORCE_ORDER_FAIL=1: the library's own check reports failure (tests)
   int inflate_serial = 0;        // SFH_INFLATE_SERIAL=1: index-only streams through the lane-serial kernel alone (tests, A/B)
+  // batched compression: the call's descriptor tables, built in pinned memory and uploaded with one copy; the next call
+  // refills the pinned rows only once that copy (ev_tab) has read them
+  uint8_t* h_tab = nullptr;
+  uint8_t* d_tab = nullptr;
+  size_t h_tab_cap = 0, d_tab_cap = 0;
+  hipEvent_t ev_tab = nullptr;
+  bool tab_pending = false;
+  uint8_t* h_stage = nullptr;    // sfh_compress_batch: pinned staging of the packed items (kStageBytes)
+  uint64_t* d_bn = nullptr;      // ... the items' sizes on the device and in pinned memory
+  uint64_t* h_bn = nullptr;
+  size_t bn_cap = 0;             // items d_bn / h_bn hold
   char err[256] = {0};
 };
 
@@ -240,6 +251,21 @@ struct HostPipe {
 };
 constexpr uint32_t kPipeBatchChunks = 2048;  // 64 MiB of input per batch on the host-buffer path
 
+// effort -> what the match kernel does: {both levels, near candidate, even positions only, second table, chain depth, exact recency}
+sf::Options kernel_options(const sfh_options& o, uint32_t strip_bytes) {
+  const uint32_t ef = o.effort;
+  const bool ef_chain = ef >= SFH_EFFORT_BEST && ef <= SFH_EFFORT_EXTREME, ef_recent = ef == SFH_EFFORT_RECENT || ef == SFH_EFFORT_RECENT_ALL;
+  const bool ef_all = ef == SFH_EFFORT_THOROUGH || ef == SFH_EFFORT_MAX || ef_chain || ef == SFH_EFFORT_RECENT_ALL;  // every position searched
+  return sf::Options{o.strategy, o.final_stream, o.lazy, o.no_stored_fast_path ? 0u : (o.strategy == 0 ? 2u : 1u),
+                     strip_bytes,
+                     (ef == SFH_EFFORT_FAST || ef == SFH_EFFORT_FASTEST) ? 0u : 1u,
+                     ef == SFH_EFFORT_FASTEST ? 0u : 1u, ef_all ? 0u : 1u,
+                     ef == SFH_EFFORT_MAX ? 1u : 0u,
+                     !ef_chain ? 0u : o.chain_depth ? o.chain_depth
+                     : ef == SFH_EFFORT_BEST ? 8u : ef == SFH_EFFORT_ULTRA ? 16u : 32u,
+                     ef_recent ? 1u : 0u};
+}
+
 int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, uint64_t* d_out_n,
             const sfh_options* opt, hipStream_t s, HostPipe* pipe = nullptr) {
   if (!ctx || (!d_src && n) || !d_dst || !d_out_n || check_opt(opt)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
@@ -255,18 +281,7 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
   if (!rc && o.container) rc = ensure_sums(ctx, nchunks);
   if (rc) return rc;
   ctx->last_chunks = nchunks;
-  // effort -> what the match kernel does: {both levels, near candidate, even positions only, second table, chain depth, exact recency}
-  const uint32_t ef = o.effort;
-  const bool ef_chain = ef >= SFH_EFFORT_BEST && ef <= SFH_EFFORT_EXTREME, ef_recent = ef == SFH_EFFORT_RECENT || ef == SFH_EFFORT_RECENT_ALL;
-  const bool ef_all = ef == SFH_EFFORT_THOROUGH || ef == SFH_EFFORT_MAX || ef_chain || ef == SFH_EFFORT_RECENT_ALL;  // every position searched
-  const sf::Options ko{o.strategy, o.final_stream, o.lazy, o.no_stored_fast_path ? 0u : (o.strategy == 0 ? 2u : 1u),
-                       resolve_block_bytes(o.block_bytes, n, o.effort),
-                       (ef == SFH_EFFORT_FAST || ef == SFH_EFFORT_FASTEST) ? 0u : 1u,
-                       ef == SFH_EFFORT_FASTEST ? 0u : 1u, ef_all ? 0u : 1u,
-                       ef == SFH_EFFORT_MAX ? 1u : 0u,
-                       !ef_chain ? 0u : o.chain_depth ? o.chain_depth
-                       : ef == SFH_EFFORT_BEST ? 8u : ef == SFH_EFFORT_ULTRA ? 16u : 32u,
-                       ef_recent ? 1u : 0u};
+  const sf::Options ko = kernel_options(o, resolve_block_bytes(o.block_bytes, n, o.effort));
   if ((ko.chain_depth || ko.recent) && (rc = ensure_order(ctx, ko.recent ? 1 : 0)) != SFH_OK) return rc;
   ctx->last_block_bytes = ko.strip_bytes;
   const bool prof = ctx->profiling != 0;
@@ -343,6 +358,185 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
   }
   ctx->ev_valid = prof;
   ctx->index_valid = true;
+  return mark_call_end(ctx, s);
+}
+
+// ---- batched compression (sfh_compress_batch*) ----
+// Everything a batch call checks before it enqueues anything (`dev`: device buffers, the single call's alignment rules).
+int check_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, void* const* dsts,
+                const uint64_t* dst_cap, const void* out_n, const sfh_options* opt, bool dev) {
+  if (!ctx || check_opt(opt)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  if (count == 0) return SFH_OK;
+  if (!srcs || !src_n || !dsts || !dst_cap || !out_n) return fail(ctx, SFH_E_INVALID_ARG, "null array", hipSuccess);
+  if (count > ((size_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "too many items", hipSuccess);
+  uint64_t chunks = 0;
+  for (size_t i = 0; i < count; ++i) {
+    if ((!srcs[i] && src_n[i]) || !dsts[i]) return fail(ctx, SFH_E_INVALID_ARG, "null item pointer", hipSuccess);
+    if (dev && (((uintptr_t)srcs[i] & 15) || ((uintptr_t)dsts[i] & 3)))
+      return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 16, dst 4)", hipSuccess);
+    if (src_n[i] > ((uint64_t)1 << 44)) return fail(ctx, SFH_E_INVALID_ARG, "item too large", hipSuccess);
+    if (dst_cap[i] < sfh_compress_bound((size_t)src_n[i], 0)) return fail(ctx, SFH_E_DST_TOO_SMALL, "dst_cap < sfh_compress_bound(n)", hipSuccess);
+    chunks += chunks_of((size_t)src_n[i]);
+  }
+  if (chunks > ((uint64_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 chunks in one call", hipSuccess);
+  // destinations must not overlap: sorted by address, each ends before the next begins
+  std::vector<size_t> ord;
+  try {
+    ord.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (size_t i = 0; i < count; ++i) ord[i] = i;
+  std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return (uintptr_t)dsts[a] < (uintptr_t)dsts[b]; });
+  for (size_t k = 1; k < count; ++k)
+    if ((uintptr_t)dsts[ord[k - 1]] + dst_cap[ord[k - 1]] > (uintptr_t)dsts[ord[k]])
+      return fail(ctx, SFH_E_INVALID_ARG, "destination ranges overlap", hipSuccess);
+  return SFH_OK;
+}
+
+// One launch batch: its rows in the call's tables (chunk rows are the call's, in item order; strip and item rows per batch).
+struct LaunchBatch {
+  uint32_t c0 = 0, nchunks = 0, s0 = 0, nstrips = 0, i0 = 0, nitems = 0;
+};
+
+// Device buffers, arguments checked (check_batch).  The host builds the descriptor tables -- per strip, per chunk, per item
+// of a launch batch, and with a container per item of the call -- and uploads them in one copy; then every launch batch
+// runs k_lz77 .. k_emit over its rows, and with a container k_checksum / k_wrap run once over the call's rows.
+int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, void* const* d_dsts,
+                  uint64_t* d_out_n, const sfh_options* opt, hipStream_t s) {
+  sfh_options o;
+  if (opt) o = *opt; else sfh_default_options(&o);
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();  // see enqueue()
+  std::vector<sf::BatchStrip> strips;
+  std::vector<sf::BatchChunk> chunks;
+  std::vector<sf::BatchItem> items;
+  std::vector<sf::WrapItem> wraps;
+  std::vector<LaunchBatch> lbs;
+  const uint32_t cap = ctx->batch_chunks;
+  try {
+    LaunchBatch cur;
+    auto close = [&] {
+      if (cur.nchunks) lbs.push_back(cur);
+      cur = LaunchBatch{};
+      cur.c0 = (uint32_t)chunks.size();
+      cur.s0 = (uint32_t)strips.size();
+      cur.i0 = (uint32_t)items.size();
+    };
+    // chunks [k0, k1) of item i (whole strips of it, k0 on a strip boundary) into the current launch batch
+    auto add = [&](size_t i, uint32_t strip_bytes, uint32_t k0, uint32_t k1, uint32_t nc) {
+      const uint8_t* src = (const uint8_t*)d_srcs[i];
+      const uint64_t n = src_n[i];
+      const uint32_t per = strip_bytes / sf::kChunk, it = cur.nitems++;
+      items.push_back(sf::BatchItem{(uint8_t*)d_dsts[i], 0, (uint32_t)i, cur.nchunks, k1 - k0, k0 ? 1u : 0u});
+      for (uint32_t k = k0; k < k1; k += per) {
+        const uint64_t b = (uint64_t)k * sf::kChunk;
+        strips.push_back(sf::BatchStrip{src + b, (uint32_t)std::min<uint64_t>(strip_bytes, n - b), cur.nchunks + (k - k0)});
+        ++cur.nstrips;
+      }
+      for (uint32_t k = k0; k < k1; ++k) {
+        const uint64_t b = (uint64_t)k * sf::kChunk;
+        chunks.push_back(sf::BatchChunk{src + b, (uint32_t)std::min<uint64_t>(sf::kChunk, n - b), it << 1 | (k + 1 == nc ? 1u : 0u)});
+      }
+      cur.nchunks += k1 - k0;
+    };
+    close();
+    for (size_t i = 0; i < count; ++i) {
+      const uint32_t sb = resolve_block_bytes(o.block_bytes, (size_t)src_n[i], o.effort), per = sb / sf::kChunk;
+      const uint32_t nc = chunks_of((size_t)src_n[i]);
+      if (o.container) wraps.push_back(sf::WrapItem{(uint8_t*)d_dsts[i], src_n[i], (uint32_t)i, (uint32_t)chunks.size(), nc, 0});
+      if (nc <= cap) {  // whole, in the current launch batch or the next
+        if (cur.nchunks + nc > cap) close();
+        add(i, sb, 0, nc, nc);
+        continue;
+      }
+      // larger than a launch batch: batches of its own, cut at its strips as the single call cuts them (its stream carries on)
+      close();
+      const uint32_t piece = std::max(per, cap / per * per);
+      for (uint32_t k0 = 0; k0 < nc; k0 += piece) {
+        add(i, sb, k0, std::min(nc, k0 + piece), nc);
+        close();
+      }
+    }
+    close();
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory for the descriptor tables", hipSuccess);
+  }
+  const uint32_t nchunks = (uint32_t)chunks.size();
+  uint32_t widest = 0;
+  for (const LaunchBatch& b : lbs) widest = std::max(widest, b.nchunks);
+  int rc = ensure_compress_ws(ctx, widest);
+  if (!rc && o.container) rc = ensure_sums(ctx, nchunks);
+  if (rc) return rc;
+  const sf::Options ko = kernel_options(o, sf::kChunk);  // (strip_bytes: the strip table's)
+  if ((ko.chain_depth || ko.recent) && (rc = ensure_order(ctx, ko.recent ? 1 : 0)) != SFH_OK) return rc;
+  // the tables, in one pinned block: chunks | strips | items | wraps (rows of 16 and 32 bytes)
+  const size_t b_chunks = chunks.size() * sizeof(sf::BatchChunk), b_strips = strips.size() * sizeof(sf::BatchStrip);
+  const size_t b_items = items.size() * sizeof(sf::BatchItem), b_wraps = wraps.size() * sizeof(sf::WrapItem);
+  const size_t bytes = b_chunks + b_strips + b_items + b_wraps;
+  if (!ctx->ev_tab) SF_HIP(hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming), "event");
+  if (ctx->tab_pending) SF_HIP(hipEventSynchronize(ctx->ev_tab), "wait for the previous call's table copy");  // (it reads h_tab)
+  ctx->tab_pending = false;
+  if (ctx->h_tab_cap < bytes) {
+    if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
+    ctx->h_tab = nullptr;
+    ctx->h_tab_cap = 0;
+    const hipError_t e = hipHostMalloc((void**)&ctx->h_tab, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(ctx, SFH_E_NOMEM, "pinned descriptor tables", e);
+    ctx->h_tab_cap = bytes;
+  }
+  if (ctx->d_tab_cap < bytes && ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (its kernels read d_tab)
+  if ((rc = grow(ctx, &ctx->d_tab, &ctx->d_tab_cap, bytes, "descriptor tables"))) return rc;
+  memcpy(ctx->h_tab, chunks.data(), b_chunks);
+  memcpy(ctx->h_tab + b_chunks, strips.data(), b_strips);
+  memcpy(ctx->h_tab + b_chunks + b_strips, items.data(), b_items);
+  memcpy(ctx->h_tab + b_chunks + b_strips + b_items, wraps.data(), b_wraps);
+  const sf::BatchChunk* d_chunks = (const sf::BatchChunk*)ctx->d_tab;
+  const sf::BatchStrip* d_strips = (const sf::BatchStrip*)(ctx->d_tab + b_chunks);
+  sf::BatchItem* d_items = (sf::BatchItem*)(ctx->d_tab + b_chunks + b_strips);
+  const sf::WrapItem* d_wraps = (const sf::WrapItem*)(ctx->d_tab + b_chunks + b_strips + b_items);
+
+  ctx->index_valid = false;  // a batch has no single index: the index functions refuse until the next single call
+  ctx->last_chunks = lbs.back().nchunks;
+  const bool prof = ctx->profiling != 0;
+  if ((rc = order_behind_last_call(ctx, s)) != SFH_OK) return rc;
+  SF_HIP(hipMemcpyAsync(ctx->d_tab, ctx->h_tab, bytes, hipMemcpyHostToDevice, s), "descriptor tables");
+  SF_HIP(hipEventRecord(ctx->ev_tab, s), "event");
+  ctx->tab_pending = true;
+  const uint32_t nbatches = (uint32_t)lbs.size();
+  ctx->ev_valid = false;
+  if (prof) {
+    const size_t need = (size_t)nbatches * sfh_ctx::kEvPerBatch + 1;
+    while (ctx->ev.size() < need) {
+      hipEvent_t e = nullptr;
+      SF_HIP(hipEventCreate(&e), "event");
+      ctx->ev.push_back(e);
+    }
+  }
+  const uint64_t hdr = sf::wrapper_header_bytes(o.container);
+  for (uint32_t bi = 0; bi < nbatches; ++bi) {
+    const LaunchBatch& b = lbs[bi];
+    const sf::BatchTables bt{d_strips + b.s0, b.nstrips, d_chunks + b.c0, d_items + b.i0, b.nitems};
+    hipEvent_t* ev = prof ? &ctx->ev[(size_t)bi * sfh_ctx::kEvPerBatch] : nullptr;
+    if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
+    SF_HIP(sf::launch_lz77(nullptr, 0, b.nchunks, ctx->ws, ko, s, &bt), "launch k_lz77");
+    if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
+    SF_HIP(sf::launch_plan(0, b.nchunks, ctx->ws, ko, s, &bt), "launch k_plan");
+    if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
+    SF_HIP(sf::launch_scan(b.nchunks, ctx->ws, hdr, false, d_out_n, s, &bt), "launch k_scan");
+    if (ev) SF_HIP(hipEventRecord(ev[3], s), "event");
+    SF_HIP(sf::launch_emit(nullptr, 0, b.nchunks, ctx->ws, nullptr, s, &bt), "launch k_emit");
+    if (ev) SF_HIP(hipEventRecord(ev[4], s), "event");
+  }
+  if (o.container) {
+    SF_HIP(sf::launch_checksum_batch(d_chunks, nchunks, o.container, ctx->ws.sums, s), "launch k_checksum");
+    SF_HIP(sf::launch_wrap_batch(ctx->ws.sums, d_wraps, (uint32_t)count, o.container, d_out_n, s), "launch k_wrap");
+  }
+  if (prof) {
+    SF_HIP(hipEventRecord(ctx->ev[(size_t)nbatches * sfh_ctx::kEvPerBatch], s), "event");
+    ctx->ev_batches = nbatches;
+  }
+  ctx->ev_valid = prof;
   return mark_call_end(ctx, s);
 }
 
@@ -505,6 +699,13 @@ void sfh_destroy(sfh_ctx* ctx) {
   if (ctx->h_tot) (void)hipHostFree(ctx->h_tot);
   (void)hipFree(ctx->d_sizes);
   if (ctx->h_sizes) (void)hipHostFree(ctx->h_sizes);
+  if (ctx->ev_tab) (void)hipEventSynchronize(ctx->ev_tab);
+  if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
+  (void)hipFree(ctx->d_tab);
+  if (ctx->ev_tab) (void)hipEventDestroy(ctx->ev_tab);
+  if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
+  (void)hipFree(ctx->d_bn);
+  if (ctx->h_bn) (void)hipHostFree(ctx->h_bn);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -590,6 +791,96 @@ int sfh_compress(sfh_ctx* ctx, const void* src, size_t n, void* dst, size_t cap,
     SF_HIP(hipMemcpyAsync((uint8_t*)dst + pipe.copied, ctx->d_out + pipe.copied, total - pipe.copied, hipMemcpyDeviceToHost, ctx->s_out), "D2H trailer");
   SF_HIP(hipStreamSynchronize(ctx->s_out), "stream sync");
   *out_n = (size_t)total;
+  return SFH_OK;
+}
+
+int sfh_compress_batch_device_async(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n,
+                                    void* const* d_dsts, const uint64_t* dst_cap, uint64_t* d_out_n,
+                                    const sfh_options* opt, void* stream) {
+  int rc = check_batch(ctx, count, d_srcs, src_n, d_dsts, dst_cap, d_out_n, opt, true);
+  if (rc || count == 0) return rc;
+  return enqueue_batch(ctx, count, d_srcs, src_n, d_dsts, d_out_n, opt, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int sfh_compress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, void* const* dsts,
+                       const uint64_t* dst_cap, uint64_t* out_n, const sfh_options* opt) {
+  int rc = check_batch(ctx, count, srcs, src_n, dsts, dst_cap, out_n, opt, false);
+  if (rc || count == 0) return rc;
+  // The items are packed into the device staging (sources 16-byte aligned, destinations a bound apart) through one pinned
+  // buffer: one copy per kStageBytes each way, then the device path over the staged items.
+  constexpr size_t kStageBytes = (size_t)kPipeBatchChunks * sf::kChunk;
+  std::vector<uint64_t> in_off, out_off;
+  std::vector<const void*> d_srcs;
+  std::vector<void*> d_dsts;
+  try {
+    in_off.resize(count + 1);
+    out_off.resize(count + 1);
+    d_srcs.resize(count);
+    d_dsts.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (size_t i = 0; i < count; ++i) {
+    in_off[i + 1] = (in_off[i] + src_n[i] + 15) / 16 * 16;
+    out_off[i + 1] = out_off[i] + sfh_compress_bound((size_t)src_n[i], 0);
+  }
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t s = ctx->stream;
+  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
+  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_off[count], "output staging");
+  if (!rc && ctx->bn_cap < count) {
+    (void)hipFree(ctx->d_bn);
+    if (ctx->h_bn) (void)hipHostFree(ctx->h_bn);
+    ctx->d_bn = ctx->h_bn = nullptr;
+    ctx->bn_cap = 0;
+    if (hipMalloc(&ctx->d_bn, count * sizeof(uint64_t)) != hipSuccess ||
+        hipHostMalloc((void**)&ctx->h_bn, count * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess)
+      rc = fail(ctx, SFH_E_NOMEM, "batch sizes", hipSuccess);
+    else
+      ctx->bn_cap = count;
+  }
+  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
+    ctx->h_stage = nullptr;
+    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
+  }
+  if (rc) return rc;
+  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
+  // up: the packed layout [0, in_off[count]) in pieces of kStageBytes (an item may straddle two pieces)
+  size_t item = 0;
+  for (uint64_t p0 = 0; p0 < in_off[count]; p0 += kStageBytes) {
+    const uint64_t p1 = std::min<uint64_t>(in_off[count], p0 + kStageBytes);
+    while (item < count && in_off[item] + src_n[item] <= p0) ++item;
+    for (size_t i = item; i < count && in_off[i] < p1; ++i) {
+      const uint64_t a = std::max(p0, in_off[i]), b = std::min(p1, in_off[i] + src_n[i]);
+      if (a < b) memcpy(ctx->h_stage + (a - p0), (const uint8_t*)srcs[i] + (a - in_off[i]), b - a);
+    }
+    SF_HIP(hipMemcpyAsync(ctx->d_in + p0, ctx->h_stage, p1 - p0, hipMemcpyHostToDevice, s), "H2D");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");  // (the next piece refills h_stage)
+  }
+  for (size_t i = 0; i < count; ++i) {
+    d_srcs[i] = ctx->d_in + in_off[i];
+    d_dsts[i] = ctx->d_out + out_off[i];
+  }
+  if ((rc = enqueue_batch(ctx, count, d_srcs.data(), src_n, d_dsts.data(), ctx->d_bn, opt, s)) != SFH_OK) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  SF_HIP(hipMemcpyAsync(ctx->h_bn, ctx->d_bn, count * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "copy sizes");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  for (size_t i = 0; i < count; ++i) out_n[i] = ctx->h_bn[i];
+  // down: [0, end of the last stream) of the output staging in pieces, each item's stream out of the pieces it lies in
+  const uint64_t end = out_off[count - 1] + out_n[count - 1];
+  item = 0;
+  for (uint64_t p0 = 0; p0 < end; p0 += kStageBytes) {
+    const uint64_t p1 = std::min<uint64_t>(end, p0 + kStageBytes);
+    SF_HIP(hipMemcpyAsync(ctx->h_stage, ctx->d_out + p0, p1 - p0, hipMemcpyDeviceToHost, s), "D2H");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+    while (item < count && out_off[item] + out_n[item] <= p0) ++item;
+    for (size_t i = item; i < count && out_off[i] < p1; ++i) {
+      const uint64_t a = std::max(p0, out_off[i]), b = std::min(p1, out_off[i] + out_n[i]);
+      if (a < b) memcpy((uint8_t*)dsts[i] + (a - out_off[i]), ctx->h_stage + (a - p0), b - a);
+    }
+  }
   return SFH_OK;
 }
 

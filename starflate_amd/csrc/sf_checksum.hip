@@ -10,7 +10,7 @@
 //                           counted from the padded chunk end.
 //                     (CRC: table-driven per 128-byte thread segment, each remainder then multiplied by
 //                     x^(8 * bytes behind it) mod P and all of them xor-ed)
-//   k_wrap            one workgroup: folds the per-chunk values in order (CRC: a tree of multiplications
+//   k_wrap            one workgroup (k_wrap_batch: one per item of a batch): folds the per-chunk values in order (CRC: a tree of multiplications
 //                     by x^(8*length) mod P, then the right padding is divided out with x^-1 and the
 //                     0xFFFFFFFF preset / final inversion are applied; Adler: plain modular sums),
 //                     writes the wrapper header and trailer, bumps the stream size.
@@ -68,18 +68,16 @@ constexpr SegShift make_seg_shift() {
 __constant__ SegShift c_seg = make_seg_shift();
 constexpr uint32_t kChunkOp = gf2_pow(kX8, kChunk);  // x^(8*32768): appends one chunk
 
+// the partial of one chunk: `valid` bytes at cp (16-byte aligned), zero-padded to kChunk, into *out
 template <uint32_t KIND>
-__global__ __launch_bounds__(KC_THREADS) void k_checksum(const uint8_t* __restrict__ src, uint64_t n,
-                                                         uint32_t* __restrict__ sums) {
+__device__ __forceinline__ void checksum_chunk(const uint8_t* __restrict__ cp, uint32_t valid, uint32_t* __restrict__ out) {
   __shared__ uint32_t s_data[KC_STAGE];
   __shared__ uint32_t s_tab[KIND == kChecksumCrc32 ? 1024 : 1];
   __shared__ uint32_t s_part[KC_THREADS / 64][2];
   const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const uint64_t cbase = (uint64_t)blockIdx.x * kChunk;
-  const uint32_t valid = (uint32_t)(n - cbase < kChunk ? n - cbase : kChunk);  // n == 0: one empty chunk
 
   // stage: dword d of the chunk -> s_data[d + d/32]; bytes past the end of the input are zero
-  const uint4* s16 = reinterpret_cast<const uint4*>(src + cbase);
+  const uint4* s16 = reinterpret_cast<const uint4*>(cp);
 #pragma unroll
   for (uint32_t i = 0; i < kChunk / 16 / KC_THREADS; ++i) {
     const uint32_t k = t + KC_THREADS * i, byte0 = 16 * k;
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_checksum(const uint8_t* __restri
       q = s16[k];
     } else if (byte0 < valid) {
       uint32_t w[4] = {0, 0, 0, 0};
-      for (uint32_t b = 0; byte0 + b < valid; ++b) w[b >> 2] |= (uint32_t)src[cbase + byte0 + b] << (8 * (b & 3));
+      for (uint32_t b = 0; byte0 + b < valid; ++b) w[b >> 2] |= (uint32_t)cp[byte0 + b] << (8 * (b & 3));
       q = make_uint4(w[0], w[1], w[2], w[3]);
     }
     const uint32_t d = 4 * k, p = d + (d >> 5);
@@ -127,7 +125,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_checksum(const uint8_t* __restri
     if (t == 0) {
       uint32_t acc = 0;
       for (uint32_t w = 0; w < KC_THREADS / 64; ++w) acc ^= s_part[w][0];
-      sums[blockIdx.x] = acc;
+      *out = acc;
     }
   } else {
     __syncthreads();
@@ -158,17 +156,31 @@ __global__ __launch_bounds__(KC_THREADS) void k_checksum(const uint8_t* __restri
         sa += s_part[w][0];
         sb += s_part[w][1];
       }
-      sums[blockIdx.x] = ((sb % kAdlerMod) << 16) | (sa % kAdlerMod);
+      *out = ((sb % kAdlerMod) << 16) | (sa % kAdlerMod);
     }
   }
 }
 
+template <uint32_t KIND>
+__global__ __launch_bounds__(KC_THREADS) void k_checksum(const uint8_t* __restrict__ src, uint64_t n,
+                                                         uint32_t* __restrict__ sums) {
+  const uint64_t cbase = (uint64_t)blockIdx.x * kChunk;
+  const uint32_t valid = (uint32_t)(n - cbase < kChunk ? n - cbase : kChunk);  // n == 0: one empty chunk
+  checksum_chunk<KIND>(src + cbase, valid, sums + blockIdx.x);
+}
+
+// sfh_compress_batch*: chunk c of the call's chunk table (every item's chunks, in order)
+template <uint32_t KIND>
+__global__ __launch_bounds__(KC_THREADS) void k_checksum_batch(const BatchChunk* __restrict__ chunks, uint32_t* __restrict__ sums) {
+  const BatchChunk B = chunks[blockIdx.x];
+  checksum_chunk<KIND>(B.src, B.n_raw, sums + blockIdx.x);
+}
+
 // One workgroup.  total: in = header bytes + raw stream bytes (k_scan ran with that base), out += trailer.
 // dst == nullptr: only *value is written (the checksum of the n input bytes).
-__global__ __launch_bounds__(KW_THREADS) void k_wrap(const uint32_t* __restrict__ sums, uint32_t nchunks, uint64_t n,
-                                                     uint32_t kind, uint8_t* __restrict__ dst,
-                                                     uint64_t* __restrict__ total, uint32_t* __restrict__ value,
-                                                     uint32_t chunk_op) {
+__device__ __forceinline__ void wrap_stream(const uint32_t* __restrict__ sums, uint32_t nchunks, uint64_t n, uint32_t kind,
+                                            uint8_t* __restrict__ dst, uint64_t* __restrict__ total,
+                                            uint32_t* __restrict__ value, uint32_t chunk_op) {
   __shared__ uint32_t s_v[KW_THREADS];
   __shared__ uint32_t s_w[KW_THREADS];
   const uint32_t t = threadIdx.x;
@@ -248,6 +260,20 @@ __global__ __launch_bounds__(KW_THREADS) void k_wrap(const uint32_t* __restrict_
   }
 }
 
+__global__ __launch_bounds__(KW_THREADS) void k_wrap(const uint32_t* __restrict__ sums, uint32_t nchunks, uint64_t n,
+                                                     uint32_t kind, uint8_t* __restrict__ dst,
+                                                     uint64_t* __restrict__ total, uint32_t* __restrict__ value,
+                                                     uint32_t chunk_op) {
+  wrap_stream(sums, nchunks, n, kind, dst, total, value, chunk_op);
+}
+
+// sfh_compress_batch*: one workgroup per item, its own partials, header and trailer
+__global__ __launch_bounds__(KW_THREADS) void k_wrap_batch(const uint32_t* __restrict__ sums, const WrapItem* __restrict__ items,
+                                                           uint32_t kind, uint64_t* __restrict__ total, uint32_t chunk_op) {
+  const WrapItem I = items[blockIdx.x];
+  wrap_stream(sums + I.sum0, I.nchunks, I.n, kind, I.dst, total + I.out, nullptr, chunk_op);
+}
+
 }  // namespace
 
 uint32_t wrapper_header_bytes(uint32_t kind) { return kind == kChecksumAdler32 ? 2u : kind == kChecksumCrc32 ? 10u : 0u; }
@@ -265,6 +291,20 @@ hipError_t launch_wrap(const uint32_t* sums, uint32_t nchunks, uint64_t n, uint3
                        uint64_t* d_total, uint32_t* d_value, hipStream_t s) {
   hipLaunchKernelGGL(k_wrap, dim3(1), dim3(KW_THREADS), 0, s, sums, nchunks, n, kind, dst, d_total, d_value,
                      kChunkOp);
+  return hipGetLastError();
+}
+
+hipError_t launch_checksum_batch(const BatchChunk* chunks, uint32_t nchunks, uint32_t kind, uint32_t* sums, hipStream_t s) {
+  if (kind == kChecksumCrc32)
+    hipLaunchKernelGGL(k_checksum_batch<kChecksumCrc32>, dim3(nchunks), dim3(KC_THREADS), 0, s, chunks, sums);
+  else
+    hipLaunchKernelGGL(k_checksum_batch<kChecksumAdler32>, dim3(nchunks), dim3(KC_THREADS), 0, s, chunks, sums);
+  return hipGetLastError();
+}
+
+hipError_t launch_wrap_batch(const uint32_t* sums, const WrapItem* items, uint32_t nitems, uint32_t kind,
+                             uint64_t* d_total, hipStream_t s) {
+  hipLaunchKernelGGL(k_wrap_batch, dim3(nitems), dim3(KW_THREADS), 0, s, sums, items, kind, d_total, kChunkOp);
   return hipGetLastError();
 }
 

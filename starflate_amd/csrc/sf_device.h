@@ -20,7 +20,8 @@
 //   K5 k_checksum  one workgroup per chunk: Adler-32 / CRC-32 partial of the chunk's input bytes
 //   K6 k_wrap      one workgroup: fold the partials, write wrapper header + trailer
 // A call on more than kBatchChunks chunks runs K1..K4 batch after batch (bounded scratch); the host-buffer entry
-// point pipelines smaller batches with their copies.
+// point pipelines smaller batches with their copies.  A batched call (sfh_compress_batch*: many items, each its own
+// stream) runs the same kernels over descriptor tables (BatchStrip / BatchChunk / BatchItem below).
 // The decoder (sf_inflate.hip, sf_inflate_core.h) runs the other way: k_inflate_tokens[_sub] (Huffman codes ->
 // tokens, all segments at once), k_inflate_bytes (tokens -> bytes, strip by strip), k_inflate_status.
 #pragma once
@@ -172,15 +173,56 @@ struct Options {
   uint32_t recent;       // 1: exact recency (SFH_EFFORT_RECENT): buckets {latest, the one before the latest inserting step} + the exact predecessor
 };
 
+// Batched compression (sfh_compress_batch*): many independent items, each its own stream, in one launch batch.  The
+// host's descriptor tables stand in for the single call's implicit geometry (strip = blockIdx.x * strip_bytes, chunk =
+// blockIdx.x * kChunk of one input, BFINAL on the last chunk of the launch).
+struct BatchStrip {   // per strip of the launch batch (k_lz77)
+  const uint8_t* src; // the strip's first byte (16-byte aligned)
+  uint32_t n;         // its bytes
+  uint32_t chunk0;    // its first chunk in the launch batch
+};
+struct BatchChunk {   // per chunk (k_plan, k_emit; k_checksum over the whole call)
+  const uint8_t* src; // the chunk's first byte
+  uint32_t n_raw;     // its bytes (0: an empty item's one chunk)
+  uint32_t item;      // index into the launch batch's item table << 1 | 1 on the last chunk of its item
+};
+struct BatchItem {    // per item (or piece of an item) in the launch batch (k_scan, k_emit)
+  uint8_t* dst;       // the item's stream
+  uint64_t shift;     // written by k_scan: stream offset of a chunk = its offset in the batch's global scan + shift
+  uint32_t out;       // the item's index in the call (d_out_n[out])
+  uint32_t chunk0;    // its first chunk in the launch batch
+  uint32_t nchunks;   // its chunks in the launch batch
+  uint32_t carry;     // 1: a piece after the item's first: its stream goes on from d_out_n[out]
+};
+struct WrapItem {     // per item of the call (the batched k_checksum / k_wrap)
+  uint8_t* dst;
+  uint64_t n;         // the item's bytes
+  uint32_t out;
+  uint32_t sum0;      // its first chunk's checksum partial
+  uint32_t nchunks;
+  uint32_t pad;
+};
+static_assert(sizeof(BatchStrip) == 16 && sizeof(BatchChunk) == 16 && sizeof(BatchItem) == 32 && sizeof(WrapItem) == 32,
+              "descriptor rows (the host packs them into one upload)");
+struct BatchTables {  // the device tables of one launch batch (null: the single call's implicit geometry)
+  const BatchStrip* strips;
+  uint32_t nstrips;
+  const BatchChunk* chunks;
+  BatchItem* items;
+  uint32_t nitems;
+};
+
 hipError_t launch_lz77(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws,
-                       const Options& opt, hipStream_t s);
+                       const Options& opt, hipStream_t s, const BatchTables* bt = nullptr);
 hipError_t launch_plan(uint64_t n, uint32_t nchunks, const Workspace& ws, const Options& opt,
-                       hipStream_t s);
+                       hipStream_t s, const BatchTables* bt = nullptr);
 // offsets start at `base` (bytes of wrapper header in front of the stream), or with `carry` at the current *d_total
-// (the end of the previous batch); *d_total = the end of this batch
-hipError_t launch_scan(uint32_t nchunks, const Workspace& ws, uint64_t base, bool carry, uint64_t* d_total, hipStream_t s);
+// (the end of the previous batch); *d_total = the end of this batch.  With tables: every item's offsets start at `base`
+// (or, carried, at d_total[item.out]) and d_total[item.out] = the end of the item's stream so far
+hipError_t launch_scan(uint32_t nchunks, const Workspace& ws, uint64_t base, bool carry, uint64_t* d_total, hipStream_t s,
+                       const BatchTables* bt = nullptr);
 hipError_t launch_emit(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws,
-                       uint8_t* dst, hipStream_t s);
+                       uint8_t* dst, hipStream_t s, const BatchTables* bt = nullptr);
 hipError_t init_kernels();
 
 // sf_checksum.hip
@@ -190,6 +232,10 @@ hipError_t launch_checksum(const uint8_t* src, uint64_t n, uint32_t nchunks, uin
 // dst != null: header at dst[0..), trailer at dst[*d_total..), *d_total += trailer bytes; d_value (nullable) = checksum
 hipError_t launch_wrap(const uint32_t* sums, uint32_t nchunks, uint64_t n, uint32_t kind, uint8_t* dst,
                        uint64_t* d_total, uint32_t* d_value, hipStream_t s);
+// batched: sums[c] for the call's chunk table; one k_wrap workgroup per item (header at dst, trailer at d_total[out])
+hipError_t launch_checksum_batch(const BatchChunk* chunks, uint32_t nchunks, uint32_t kind, uint32_t* sums, hipStream_t s);
+hipError_t launch_wrap_batch(const uint32_t* sums, const WrapItem* items, uint32_t nitems, uint32_t kind,
+                             uint64_t* d_total, hipStream_t s);
 // sf_inflate.hip
 hipError_t init_inflate_kernels();
 // sps: segments per strip (1: every segment independent); a segment's matches may reach its strip's earlier segments

@@ -228,12 +228,15 @@ __device__ __forceinline__ uint32_t entry_rel(uint32_t v) {
 // searched, most recent candidate first, `chain_depth` of them at most (the specification's chain_depth; zlib's
 // structure).  One workgroup per CU (the links take 80 KiB of LDS), 128 vector registers.
 // RECENT (SFH_EFFORT_RECENT): the step tables with EXACT RECENCY -- see R_L_POST above and the match phase.
-template <bool STAMPS, bool DEPTH2, bool NEAR, bool STRIDE2, bool LONG, bool CHAIN = false, bool RECENT = false>
+// BATCH (sfh_compress_batch*): the strip's bytes, size and first chunk come from the launch batch's strip table (src,
+// n_total and strip_bytes are unused); the rest is the same kernel.  The choice is made in the prologue, at compile
+// time: the single call's instantiations are the code they were.
+template <bool STAMPS, bool DEPTH2, bool NEAR, bool STRIDE2, bool LONG, bool CHAIN = false, bool RECENT = false, bool BATCH = false>
 __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREADS / 256) void k_lz77(
     const uint8_t* __restrict__ src, uint64_t n_total, uint32_t strip_bytes, uint16_t* __restrict__ items,
     uint32_t* __restrict__ nitems_out, uint32_t* __restrict__ ntok_out, uint32_t* __restrict__ hist_out,
     uint32_t* __restrict__ rtok_out, uint32_t lazy, uint32_t fast_skip, uint64_t* __restrict__ stamps,
-    uint32_t chain_depth) {
+    uint32_t chain_depth, const BatchStrip* __restrict__ strips) {
   static_assert(!CHAIN || (!STRIDE2 && !LONG && DEPTH2 && NEAR), "chains: every position searched, no step tables");
   static_assert(!RECENT || (!LONG && !CHAIN && DEPTH2 && NEAR), "recent: the step tables' search patterns (stride 2 or every position)");
   constexpr uint32_t LH = CHAIN ? C_L_HIST : L_HIST, LW = CHAIN ? C_L_WTOT : L_WTOT, LD = CHAIN ? C_L_DSYM : L_DSYM;
@@ -272,10 +275,20 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
   // t >> 6 is wave-uniform, but only readfirstlane tells the compiler so
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(t >> 6)), lane = t & 63;
   const uint32_t strip = blockIdx.x;
-  const uint64_t sbase = (uint64_t)strip * strip_bytes;
-  const uint32_t n = (uint32_t)((n_total - sbase) < (uint64_t)strip_bytes ? (n_total - sbase) : strip_bytes);
-  const uint32_t chunk0 = strip * (strip_bytes / kChunk);
-  const uint8_t* const sp = src + sbase;
+  // the strip: from the batch's strip table (sfh_compress_batch*), else the single call's arithmetic
+  uint32_t n, chunk0;
+  const uint8_t* sp;
+  if constexpr (BATCH) {
+    const BatchStrip S = strips[strip];
+    sp = S.src;
+    n = S.n;
+    chunk0 = S.chunk0;
+  } else {
+    const uint64_t sbase = (uint64_t)strip * strip_bytes;
+    n = (uint32_t)((n_total - sbase) < (uint64_t)strip_bytes ? (n_total - sbase) : strip_bytes);
+    chunk0 = strip * (strip_bytes / kChunk);
+    sp = src + sbase;
+  }
   // @phase inherit
   // four bytes of the strip at `pos` (multiple of 4), zero beyond n
   auto load4 = [&](uint32_t pos) -> uint32_t {
@@ -1441,6 +1454,7 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
   }
 }
 
+
 // ---------------------------------------------------------------------------
 // K2: per-chunk code plan.  One wave (64-thread workgroup) per chunk.
 // ---------------------------------------------------------------------------
@@ -1790,7 +1804,8 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
                                            uint32_t* __restrict__ hist, const uint32_t* __restrict__ ntok,
                                            ChunkPlan* __restrict__ plan, ChunkCodes* __restrict__ codes,
                                            uint32_t strategy, uint32_t final_stream,
-                                           uint64_t* __restrict__ stamps, PlanTree* __restrict__ ptree) {
+                                           uint64_t* __restrict__ stamps, PlanTree* __restrict__ ptree,
+                                           const BatchChunk* __restrict__ bchunks) {
   __shared__ PlanSmem S;
   uint32_t* const s_header = S.key + kHeaderAt;
   // diagnostic (stamps != nullptr, SFH_K1_STAMPS=1): cycles per phase at stamps[chunk*8 + 8*nchunks..]
@@ -1806,9 +1821,17 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
   };
   const uint32_t lane = threadIdx.x;
   const uint32_t chunk = blockIdx.x;
-  const uint64_t cbase = (uint64_t)chunk * kChunk;
-  const uint32_t n_raw = (uint32_t)((n_total - cbase) < (uint64_t)kChunk ? (n_total - cbase) : kChunk);
-  const bool fin = (chunk + 1 == nchunks) && final_stream;
+  uint32_t n_raw;
+  bool fin;
+  if (bchunks) {  // a batch: the chunk's bytes and "last of its item" from the chunk table (uniform)
+    const BatchChunk B = bchunks[chunk];
+    n_raw = B.n_raw;
+    fin = (B.item & 1u) && final_stream;
+  } else {
+    const uint64_t cbase = (uint64_t)chunk * kChunk;
+    n_raw = (uint32_t)((n_total - cbase) < (uint64_t)kChunk ? (n_total - cbase) : kChunk);
+    fin = (chunk + 1 == nchunks) && final_stream;
+  }
 
   PlanTree* const T = ptree + chunk;
   if constexpr (MODE == 2) {
@@ -2061,8 +2084,9 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
   __global__ __launch_bounds__(64) void NAME(uint64_t n_total, uint32_t nchunks, uint32_t* __restrict__ hist,                 \
                                              const uint32_t* __restrict__ ntok, ChunkPlan* __restrict__ plan,                 \
                                              ChunkCodes* __restrict__ codes, uint32_t strategy, uint32_t final_stream,        \
-                                             uint64_t* __restrict__ stamps, PlanTree* __restrict__ ptree) {                   \
-    plan_chunk<MODE>(n_total, nchunks, hist, ntok, plan, codes, strategy, final_stream, stamps, ptree);                       \
+                                             uint64_t* __restrict__ stamps, PlanTree* __restrict__ ptree,                     \
+                                             const BatchChunk* __restrict__ bchunks) {                                        \
+    plan_chunk<MODE>(n_total, nchunks, hist, ntok, plan, codes, strategy, final_stream, stamps, ptree, bchunks);              \
   }
 SF_PLAN_KERNEL(k_plan_sort, 1)    // K2a
 SF_PLAN_KERNEL(k_plan_finish, 2)  // K2c
@@ -2106,12 +2130,19 @@ static_assert((uint64_t)kBatchChunks * (kChunk + kChunk / 8 + 656) < (1ull << 32
 // Round 5: every thread takes chunk t of every tile -- coalesced loads, all 32 in flight at once -- instead of 32 consecutive
 // chunks (a 512-byte stride between lanes, one dependent pass for the sums and one for the offsets: 46 us per GiB); the
 // tiles' wave totals meet in LDS, one 16-lane DPP row per tile, then the tiles' totals in one wave.
+// BATCH (sfh_compress_batch*): the same scan from 0 over the launch batch's chunks, then per item: its stream starts at
+// `base` (the wrapper header) or, carried, at total[item.out]; item.shift turns a chunk's offset in the batch into its
+// offset in the item's stream (k_emit), and total[item.out] = the item's end so far.
+template <bool BATCH>
 __global__ __launch_bounds__(K3_THREADS) void k_scan(uint32_t nchunks, const ChunkPlan* __restrict__ plan,
                                                      uint64_t base, uint32_t carry, uint64_t* __restrict__ offsets,
-                                                     uint64_t* __restrict__ total) {
+                                                     uint64_t* __restrict__ total, BatchItem* __restrict__ bitems,
+                                                     uint32_t nitems) {
   __shared__ uint32_t s_wt[K3_TILES][16];  // [tile][wave]: the wave's bytes in the tile, then the bytes of the tile's waves before it
   __shared__ uint32_t s_tile[K3_TILES + 1];  // bytes of the tiles before, [K3_TILES]: of all
-  if (carry) base = *total;
+  const uint64_t hdr = base;
+  if constexpr (BATCH) base = 0;
+  else if (carry) base = *total;
   const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
   uint32_t v[K3_TILES], ex[K3_TILES];
 #pragma unroll
@@ -2152,8 +2183,18 @@ __global__ __launch_bounds__(K3_THREADS) void k_scan(uint32_t nchunks, const Chu
   }
   if (t == 0) {
     const uint64_t all = base + s_tile[K3_TILES];
-    *total = all;
+    if constexpr (!BATCH) *total = all;
     offsets[nchunks] = all;  // closes the index: chunk c occupies [offsets[c], offsets[c + 1])
+  }
+  if constexpr (BATCH) {
+    __syncthreads();  // (the offsets above are this workgroup's own stores)
+    for (uint32_t i = t; i < nitems; i += K3_THREADS) {
+      BatchItem& I = bitems[i];
+      const uint64_t g0 = offsets[I.chunk0], g1 = offsets[I.chunk0 + I.nchunks];
+      const uint64_t start = I.carry ? total[I.out] : hdr;
+      I.shift = start - g0;
+      total[I.out] = start + (g1 - g0);
+    }
   }
 }
 
@@ -2199,6 +2240,8 @@ __device__ __forceinline__ void match_bits(uint32_t l3, uint32_t d1, const uint3
   nb = p;
 }
 
+// BATCH (sfh_compress_batch*): the chunk's bytes, its stream and its place there come from the batch's tables
+template <bool BATCH>
 __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restrict__ src, uint64_t n_total,
                                                      uint32_t /*nchunks*/, uint16_t* items,
                                                      const uint32_t* __restrict__ nitems_in,
@@ -2208,7 +2251,9 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
                                                      const uint64_t* __restrict__ offsets,
                                                      const uint32_t* __restrict__ rtok,
                                                      uint32_t* __restrict__ subidx,
-                                                     uint8_t* __restrict__ dst) {
+                                                     uint8_t* __restrict__ dst_all,
+                                                     const BatchChunk* __restrict__ bchunks,
+                                                     const BatchItem* __restrict__ bitems) {
   // @phase k4.setup trips=0 note=per chunk: tables, header
   __shared__ __attribute__((aligned(16))) uint32_t s_stage[K4_STAGE_WORDS];
   __shared__ uint32_t s_lcode[288];
@@ -2228,9 +2273,24 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(t >> 6));
   const uint32_t chunk = blockIdx.x;
   const ChunkPlan P = plan[chunk];
-  const uint64_t off = offsets[chunk];
-  const uint64_t cbase = (uint64_t)chunk * kChunk;
-  const uint32_t n_raw = (uint32_t)((n_total - cbase) < (uint64_t)kChunk ? (n_total - cbase) : kChunk);
+  // the chunk's bytes and where its stream goes: the batch's tables (its item's stream), else the one input and stream
+  const uint8_t* csrc;
+  uint8_t* dst;
+  uint64_t off = offsets[chunk];
+  uint32_t n_raw;
+  if constexpr (BATCH) {
+    const BatchChunk B = bchunks[chunk];
+    const BatchItem& I = bitems[B.item >> 1];
+    csrc = B.src;
+    n_raw = B.n_raw;
+    dst = I.dst;
+    off += I.shift;
+  } else {
+    const uint64_t cbase = (uint64_t)chunk * kChunk;
+    csrc = src + cbase;
+    n_raw = (uint32_t)((n_total - cbase) < (uint64_t)kChunk ? (n_total - cbase) : kChunk);
+    dst = dst_all;
+  }
   const ChunkCodes& C = codes[chunk];
   // what a coded chunk needs next, requested before the plan has arrived (a stored chunk does not use it): one memory
   // round trip for the plan and the tables together instead of two in a row
@@ -2252,7 +2312,7 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
       o[4] = (uint8_t)((~n_raw >> 8) & 0xFF);
     }
     uint8_t* d = o + 5;
-    const uint8_t* sp = src + cbase;  // 32 KiB aligned
+    const uint8_t* sp = csrc;  // 16-byte aligned
     if (n_raw >= 64) {
       // 16 bytes per thread and step: destination blocks aligned (bytes up to the first one singly), every block from
       // the two aligned source blocks it straddles -- the same byte shift for the whole chunk (uniform), so the dword it
@@ -2351,7 +2411,7 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
     // write them now, into the chunk's own item slots, and go on as for any chunk (nit == n_raw: every position a literal)
     uint16_t* const wr = items + (uint64_t)chunk * kChunk;
     for (uint32_t pos = t; pos < nit; pos += K4_THREADS) {
-      const uint32_t b = src[cbase + pos];
+      const uint32_t b = csrc[pos];
       wr[pos] = (uint16_t)(kItemTok | ((pos & (kSubBytes - 1)) == 0 ? (b | kItemRegion | ((pos / kSubBytes) << kItemRegionShift)) : b));
     }
     __threadfence_block();
@@ -2499,68 +2559,71 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
 hipError_t init_kernels() { return hipSuccess; }
 
 hipError_t launch_lz77(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws,
-                       const Options& opt, hipStream_t s) {
+                       const Options& opt, hipStream_t s, const BatchTables* bt) {
   if (opt.strip_bytes == 0 || opt.strip_bytes % kChunk || opt.strip_bytes > kMaxStrip) return hipErrorInvalidValue;
   // a chunk stored by its probe gets no tokens and no histogram: k_plan_sort stores such a chunk only under strategy 0
   if (opt.fast_skip == 2 && opt.strategy != 0) return hipErrorInvalidValue;
   const uint32_t per = opt.strip_bytes / kChunk;
-  const uint32_t nstrips = (nchunks + per - 1) / per;
+  const uint32_t nstrips = bt ? bt->nstrips : (nchunks + per - 1) / per;
+  const BatchStrip* strips = bt ? bt->strips : nullptr;
   const auto launch = [&](auto kernel, uint64_t* stamps) {
     hipLaunchKernelGGL(kernel, dim3(nstrips), dim3(K1_THREADS), 0, s, src, n, opt.strip_bytes, ws.items, ws.nitems, ws.ntok,
-                       ws.hist, ws.rtok, opt.lazy, opt.fast_skip, stamps, opt.chain_depth);
+                       ws.hist, ws.rtok, opt.lazy, opt.fast_skip, stamps, opt.chain_depth, strips);
   };
+  // k_lz77 (with stamps in the diagnostic build), or a batch's k_lz77<.., BATCH> (no stamps)
+#define SF_K1(D2, NR, S2, LG, CH, RC)                                                                                     \
+  (ws.stamps && !bt ? launch(k_lz77<true, D2, NR, S2, LG, CH, RC>, ws.stamps)                                          \
+   : !bt ? launch(k_lz77<false, D2, NR, S2, LG, CH, RC>, (uint64_t*)nullptr)                                           \
+         : launch(k_lz77<false, D2, NR, S2, LG, CH, RC, true>, (uint64_t*)nullptr))
   if (opt.recent) {  // exact recency (SFH_EFFORT_RECENT: even positions searched; SFH_EFFORT_RECENT_ALL: every position)
-    if (opt.stride2) {
-      if (ws.stamps) launch(k_lz77<true, true, true, true, false, false, true>, ws.stamps);
-      else launch(k_lz77<false, true, true, true, false, false, true>, (uint64_t*)nullptr);
-    } else {
-      if (ws.stamps) launch(k_lz77<true, true, true, false, false, false, true>, ws.stamps);
-      else launch(k_lz77<false, true, true, false, false, false, true>, (uint64_t*)nullptr);
-    }
-    return hipGetLastError();
-  }
-  if (opt.chain_depth) {  // exact hash chains (SFH_EFFORT_BEST / _ULTRA / _EXTREME)
-    if (ws.stamps) launch(k_lz77<true, true, true, false, false, true>, ws.stamps);
-    else launch(k_lz77<false, true, true, false, false, true>, (uint64_t*)nullptr);
-    return hipGetLastError();
-  }
-  // effort: {even positions: both levels + near, newer level + near, newer level only} {every position: one table, two tables}
-  const uint32_t kind = !opt.stride2 ? (opt.long_table ? 4u : 3u) : opt.depth2 ? 0u : (opt.near ? 1u : 2u);
-  if (ws.stamps) {
-    if (kind == 0) launch(k_lz77<true, true, true, true, false>, ws.stamps);
-    else if (kind == 1) launch(k_lz77<true, false, true, true, false>, ws.stamps);
-    else if (kind == 2) launch(k_lz77<true, false, false, true, false>, ws.stamps);
-    else if (kind == 3) launch(k_lz77<true, true, true, false, false>, ws.stamps);
-    else launch(k_lz77<true, true, true, false, true>, ws.stamps);
+    if (opt.stride2) SF_K1(true, true, true, false, false, true);
+    else SF_K1(true, true, false, false, false, true);
+  } else if (opt.chain_depth) {  // exact hash chains (SFH_EFFORT_BEST / _ULTRA / _EXTREME)
+    SF_K1(true, true, false, false, true, false);
   } else {
-    if (kind == 0) launch(k_lz77<false, true, true, true, false>, (uint64_t*)nullptr);
-    else if (kind == 1) launch(k_lz77<false, false, true, true, false>, (uint64_t*)nullptr);
-    else if (kind == 2) launch(k_lz77<false, false, false, true, false>, (uint64_t*)nullptr);
-    else if (kind == 3) launch(k_lz77<false, true, true, false, false>, (uint64_t*)nullptr);
-    else launch(k_lz77<false, true, true, false, true>, (uint64_t*)nullptr);
+    // effort: {even positions: both levels + near, newer level + near, newer level only} {every position: one table, two tables}
+    const uint32_t kind = !opt.stride2 ? (opt.long_table ? 4u : 3u) : opt.depth2 ? 0u : (opt.near ? 1u : 2u);
+    if (kind == 0) SF_K1(true, true, true, false, false, false);
+    else if (kind == 1) SF_K1(false, true, true, false, false, false);
+    else if (kind == 2) SF_K1(false, false, true, false, false, false);
+    else if (kind == 3) SF_K1(true, true, false, false, false, false);
+    else SF_K1(true, true, false, true, false, false);
   }
+#undef SF_K1
   return hipGetLastError();
 }
 hipError_t launch_plan(uint64_t n, uint32_t nchunks, const Workspace& ws, const Options& opt,
-                       hipStream_t s) {
+                       hipStream_t s, const BatchTables* bt) {
+  const BatchChunk* bchunks = bt ? bt->chunks : nullptr;
   if (!ws.ptree) return hipErrorInvalidValue;
   // sort (a wave per chunk) -> merge (a lane per chunk) -> finish (a wave per chunk)
   hipLaunchKernelGGL(k_plan_sort, dim3(nchunks), dim3(64), 0, s, n, nchunks, ws.hist, ws.ntok, ws.plan, ws.codes,
-                     opt.strategy, opt.final_stream, (uint64_t*)nullptr, ws.ptree);
+                     opt.strategy, opt.final_stream, (uint64_t*)nullptr, ws.ptree, bchunks);
   hipLaunchKernelGGL(k_plan_merge, dim3((nchunks + 63) / 64), dim3(64), 0, s, nchunks, ws.ptree);
   hipLaunchKernelGGL(k_plan_finish, dim3(nchunks), dim3(64), 0, s, n, nchunks, ws.hist, ws.ntok, ws.plan, ws.codes,
-                     opt.strategy, opt.final_stream, ws.stamps, ws.ptree);
+                     opt.strategy, opt.final_stream, ws.stamps, ws.ptree, bchunks);
   return hipGetLastError();
 }
-hipError_t launch_scan(uint32_t nchunks, const Workspace& ws, uint64_t base, bool carry, uint64_t* d_total, hipStream_t s) {
+hipError_t launch_scan(uint32_t nchunks, const Workspace& ws, uint64_t base, bool carry, uint64_t* d_total, hipStream_t s,
+                       const BatchTables* bt) {
   if (nchunks > kBatchChunks) return hipErrorInvalidValue;  // k_scan covers one batch (K3_TILES tiles, 32-bit sums): more would get no offset
-  hipLaunchKernelGGL(k_scan, dim3(1), dim3(K3_THREADS), 0, s, nchunks, ws.plan, base, carry ? 1u : 0u, ws.offsets, d_total);
+  if (bt)
+    hipLaunchKernelGGL(k_scan<true>, dim3(1), dim3(K3_THREADS), 0, s, nchunks, ws.plan, base, 0u, ws.offsets, d_total, bt->items,
+                       bt->nitems);
+  else
+    hipLaunchKernelGGL(k_scan<false>, dim3(1), dim3(K3_THREADS), 0, s, nchunks, ws.plan, base, carry ? 1u : 0u, ws.offsets, d_total,
+                       (BatchItem*)nullptr, 0u);
   return hipGetLastError();
 }
 hipError_t launch_emit(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws,
-                       uint8_t* dst, hipStream_t s) {
-  hipLaunchKernelGGL(k_emit, dim3(nchunks), dim3(K4_THREADS), 0, s, src, n, nchunks, ws.items, ws.nitems, ws.ntok,
-                     ws.plan, ws.codes, ws.offsets, ws.rtok, ws.subidx, dst);
+                       uint8_t* dst, hipStream_t s, const BatchTables* bt) {
+  if (bt)
+    hipLaunchKernelGGL(k_emit<true>, dim3(nchunks), dim3(K4_THREADS), 0, s, src, n, nchunks, ws.items, ws.nitems, ws.ntok,
+                       ws.plan, ws.codes, ws.offsets, ws.rtok, ws.subidx, dst, bt->chunks, (const BatchItem*)bt->items);
+  else
+    hipLaunchKernelGGL(k_emit<false>, dim3(nchunks), dim3(K4_THREADS), 0, s, src, n, nchunks, ws.items, ws.nitems, ws.ntok,
+                       ws.plan, ws.codes, ws.offsets, ws.rtok, ws.subidx, dst, (const BatchChunk*)nullptr,
+                       (const BatchItem*)nullptr);
   return hipGetLastError();
 }
 
