@@ -80,6 +80,17 @@ struct stream_index {
   [[nodiscard]] auto segments() const -> std::size_t { return offsets.empty() ? 0 : offsets.size() - 1; }
 };
 
+/// The index of a compress batch (compressor::batch_index): every item's stream_index, flattened item after item.  Item i's
+/// segments + 1 offsets (relative to its own stream) are offsets[first[i] .. first[i + 1]), its sub-index words
+/// regions[64 * (first[i] - i) ..) (64 per segment; empty: none), its strip size block_bytes[i].
+struct batch_stream_index {
+  std::vector<std::uint64_t> offsets;
+  std::vector<std::uint32_t> regions;
+  std::vector<std::uint32_t> block_bytes;
+  std::vector<std::size_t> first;  // items + 1
+  [[nodiscard]] auto items() const -> std::size_t { return block_bytes.size(); }
+};
+
 namespace detail {
 inline auto to_status(int rc) -> CompressStatus {
   switch (rc) {
@@ -112,17 +123,19 @@ inline auto to_c(const compress_options& o) -> sfh_options {
 class compressor {
   sfh_ctx* ctx_{nullptr};
   CompressStatus init_{CompressStatus::Success};
+  std::vector<std::uint64_t> batch_n_;  // the items' sizes of the last compress_batch() (what batch_index() cuts the index by)
 
  public:
   explicit compressor(int device = 0) { init_ = detail::to_status(sfh_create(&ctx_, device)); }
   compressor(const compressor&) = delete;
   auto operator=(const compressor&) -> compressor& = delete;
-  compressor(compressor&& o) noexcept : ctx_{std::exchange(o.ctx_, nullptr)}, init_{o.init_} {}
+  compressor(compressor&& o) noexcept : ctx_{std::exchange(o.ctx_, nullptr)}, init_{o.init_}, batch_n_{std::move(o.batch_n_)} {}
   auto operator=(compressor&& o) noexcept -> compressor& {
     if (this != &o) {
       sfh_destroy(ctx_);
       ctx_ = std::exchange(o.ctx_, nullptr);
       init_ = o.init_;
+      batch_n_ = std::move(o.batch_n_);
     }
     return *this;
   }
@@ -161,9 +174,58 @@ class compressor {
     const auto c = detail::to_c(opt);
     const int rc = sfh_compress_batch(ctx_, k, sp.data(), n.data(), dp.data(), cap.data(), out.data(), &c);
     if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+    batch_n_ = std::move(n);
     std::size_t total = 0;
     for (std::size_t i = 0; i < k; ++i) total += sizes[i] = static_cast<std::size_t>(out[i]);
     return total;
+  }
+  /// index of the last call on this object when it was compress_batch() (with_regions: also the sub-index)
+  auto batch_index(bool with_regions = true) -> compat::expected<batch_stream_index, CompressStatus> {
+    if (!ctx_) return compat::unexpected{init_};
+    std::size_t k = 0, entries = 0;
+    if (sfh_batch_index_size(ctx_, &k, &entries) != SFH_OK || k != batch_n_.size())
+      return compat::unexpected{CompressStatus::InvalidArgument};
+    batch_stream_index ix;
+    ix.offsets.resize(entries);
+    ix.block_bytes.resize(k);
+    ix.first.resize(k + 1);
+    for (std::size_t i = 0; i < k; ++i)
+      ix.first[i + 1] = ix.first[i] + static_cast<std::size_t>(batch_n_[i] ? (batch_n_[i] + SFH_SEGMENT_BYTES - 1) / SFH_SEGMENT_BYTES : 1) + 1;
+    if (with_regions) ix.regions.resize((entries - k) * SFH_SUBINDEX_WORDS);
+    const int rc = sfh_copy_batch_index(ctx_, ix.offsets.data(), with_regions ? ix.regions.data() : nullptr, ix.block_bytes.data(), 0, nullptr);
+    if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+    return ix;
+  }
+  /// Many independent streams decoded in one call: srcs[i] into exactly dsts[i].size() bytes at dsts[i], its status into
+  /// statuses[i] -- a raw item's what decompress(src, dst, ix) gives on it alone, a wrapped one's what
+  /// decompress(srcs[i], dsts[i], container) (container.hpp) gives.  ix: batch_index() of the compress_batch() that wrote
+  /// the streams (or any index of that layout); nullptr when every dsts[i].size() <= 32768 (each stream one segment: pages
+  /// from other tools).  dsts[i] is written only where statuses[i] is Success.  A refused call (arguments, no device) is the
+  /// return value; the statuses are then not written.
+  auto decompress_batch(std::span<const std::span<const std::byte>> srcs, std::span<const std::span<std::byte>> dsts,
+                        const batch_stream_index* ix, Container container, std::span<DecompressStatus> statuses) -> CompressStatus {
+    if (!ctx_) return init_;
+    const std::size_t k = srcs.size();
+    if (dsts.size() != k || statuses.size() != k) return CompressStatus::InvalidArgument;
+    if (ix != nullptr && (ix->items() != k || ix->first.size() != k + 1 || ix->offsets.size() != ix->first[k] ||
+                          (!ix->regions.empty() && ix->regions.size() != (ix->first[k] - k) * SFH_SUBINDEX_WORDS)))
+      return CompressStatus::InvalidArgument;
+    std::vector<const void*> sp(k);
+    std::vector<void*> dp(k);
+    std::vector<std::uint64_t> n(k), dn(k);
+    std::vector<std::uint32_t> st(k);
+    for (std::size_t i = 0; i < k; ++i) {
+      sp[i] = srcs[i].data();
+      n[i] = srcs[i].size();
+      dp[i] = dsts[i].data();
+      dn[i] = dsts[i].size();
+    }
+    const int rc = sfh_decompress_batch(ctx_, k, sp.data(), n.data(), ix ? ix->offsets.data() : nullptr,
+                                        (ix && !ix->regions.empty()) ? ix->regions.data() : nullptr, dp.data(), dn.data(),
+                                        ix ? ix->block_bytes.data() : nullptr, static_cast<std::uint32_t>(container), st.data());
+    if (rc != SFH_OK) return detail::to_status(rc);
+    for (std::size_t i = 0; i < k; ++i) statuses[i] = st[i] > 7 ? DecompressStatus::Error : static_cast<DecompressStatus>(st[i]);
+    return CompressStatus::Success;
   }
   /// index of the last compress call on this object (with_regions: also the per-region sub-index)
   auto index(bool with_regions = true) -> compat::expected<stream_index, CompressStatus> {

@@ -244,6 +244,16 @@ int sfh_compress_batch_device_async(sfh_ctx* ctx, size_t count,
 int sfh_compress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n,
                        void* const* dsts, const uint64_t* dst_cap, uint64_t* out_n, const sfh_options* opt);
 
+/* The index of the last call when it was an sfh_compress_batch* call (SFH_E_INVALID_ARG after any other call, or before any):
+ * *items = the call's items, *entries = sum over i of (nseg_i + 1), nseg_i = max(1, ceil(n_i / 32768)).  The sub-index has
+ * (entries - items) * SFH_SUBINDEX_WORDS words. */
+int sfh_batch_index_size(const sfh_ctx* ctx, size_t* items, size_t* entries);
+/* Copies that index, item after item: item i's nseg_i + 1 offsets relative to ITS stream's first byte (header included, trailer
+ * excluded: the single call's convention), its nseg_i * SFH_SUBINDEX_WORDS sub-index words, and its resolved block_bytes (one
+ * uint32 per item).  Any of the three may be NULL.  dst_on_device: device memory, else host.  Synchronises `stream`. */
+int sfh_copy_batch_index(sfh_ctx* ctx, uint64_t* index, uint32_t* subindex, uint32_t* block_bytes, int dst_on_device,
+                         void* stream);
+
 /* ---- measurement hooks (bench.py, tests) ---- */
 
 /* ---- block index + GPU decompress ----
@@ -298,6 +308,43 @@ int sfh_decompress_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const u
 /* Host buffers: H2D (stream + index [+ sub-index, may be NULL]), decode, D2H. */
 int sfh_decompress(sfh_ctx* ctx, const void* src, size_t src_n, const uint64_t* index, const uint32_t* subindex,
                    size_t nseg, void* dst, size_t dst_n, uint32_t block_bytes, uint32_t* status);
+
+/* ---- batched decompression: `count` independent streams, each decoded into its own buffer, in one call ----
+ * Item i: stream srcs[i] of src_n[i] bytes (raw, or zlib / gzip: `container`, the same for every item), decoded into exactly
+ * dst_n[i] bytes at dsts[i]; its DecompressStatus into status[i].
+ * index: every item's segment index, item after item in sfh_copy_batch_index's layout (nseg_i + 1 offsets into ITS stream,
+ *   nseg_i = max(1, ceil(dst_n[i] / 32768))), or NULL when every dst_n[i] <= 32768: each item is then one segment, from the
+ *   end of its wrapper header to src_n[i] minus its trailer (pages that other tools wrote).
+ * subindex: flattened the same way (SFH_SUBINDEX_WORDS per segment), or NULL.  block_bytes: per item (0 = 32768), or NULL =
+ *   32768 for all.
+ * A raw item's bytes and status are those of sfh_decompress_device on it alone with the same index, sub-index and block_bytes;
+ * a wrapped one's status is include/starflate/container.hpp's decompress(src_i, dst_i, container): the wrapper (SrcTooSmall
+ * for a stream too short for it; gzip's FEXTRA / FNAME / FCOMMENT / FHCRC are read), ISIZE against dst_n[i], the body, then
+ * the Adler-32 / CRC-32 (a mismatch is Error); with an index, a wrapped item's entry 0 must be the header's end (else Error;
+ * a raw item's entry 0 is not checked, as in sfh_decompress_device).  A gzip item with ISIZE below dst_n[i] is decoded into
+ * its first ISIZE bytes, as container.hpp does; a wrapped body that ends short of its output is Error.  One
+ * item's failure changes no other item's bytes or status, and nothing is written outside [dsts[i], dsts[i] + dst_n[i]).
+ * Refused before anything is enqueued (SFH_E_INVALID_ARG): a null context or an unknown container (also with count == 0), a
+ * null array (count > 0), a device pointer out of the single decoder's alignment (src 4, dst 16, index 8, sub-index 4,
+ * status 4), dst_n above 2^44, a bad block_bytes (not a multiple of 32768, or above 16 MiB), overlapping destination ranges
+ * (a destination of no bytes overlaps nothing),
+ * no index while some dst_n[i] > 32768, a sub-index without an index, more than 2^31 - 1 segments.  count == 0: SFH_OK.
+ * The items run in launch batches of whole items (at most SFH_BATCH_CHUNKS segments; a larger item in batches of its own, cut
+ * at its strips, as sfh_decompress_device cuts a call), so the token scratch is that of one batch
+ * (sfh_last_decode_scratch_bytes, at most 4 GiB).  Afterwards the context has no index, as after sfh_decompress*;
+ * sfh_last_inflate_ms sums both stages over the launch batches.
+ *
+ * Device buffers, enqueued on `stream` (NULL: the context's), no host synchronisation; the host arrays (src_n, dst_n,
+ * block_bytes) are read before the call returns; status: device uint32[count]. */
+int sfh_decompress_batch_device_async(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n,
+                                      const uint64_t* d_index, const uint32_t* d_subindex, void* const* d_dsts,
+                                      const uint64_t* dst_n, const uint32_t* block_bytes, uint32_t container,
+                                      uint32_t* d_status, void* stream);
+/* Host buffers, synchronous (through pinned staging, as sfh_compress_batch): status[i] on the host; dsts[i] is written only
+ * when status[i] == 0. */
+int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n,
+                         const uint64_t* index, const uint32_t* subindex, void* const* dsts, const uint64_t* dst_n,
+                         const uint32_t* block_bytes, uint32_t container, uint32_t* status);
 
 /* bytes of decoder token scratch the last sfh_decompress* call on this ctx used (0 before the first) */
 size_t sfh_last_decode_scratch_bytes(const sfh_ctx* ctx);

@@ -26,7 +26,8 @@ SUBINDEX_WORDS = 64
 EXPORTS = [
     "sfh_default_options", "sfh_device_count", "sfh_get_device_props", "sfh_create", "sfh_destroy", "sfh_last_error",
     "sfh_compress_bound", "sfh_compress", "sfh_compress_multi", "sfh_compress_device", "sfh_compress_device_async",
-    "sfh_compress_batch_device_async", "sfh_compress_batch",
+    "sfh_compress_batch_device_async", "sfh_compress_batch", "sfh_batch_index_size", "sfh_copy_batch_index",
+    "sfh_decompress_batch_device_async", "sfh_decompress_batch",
     "sfh_last_block_bytes", "sfh_index_entries", "sfh_copy_index", "sfh_copy_subindex", "sfh_decompress_device", "sfh_decompress", "sfh_last_inflate_ms", "sfh_last_decode_scratch_bytes",
     "sfh_inflate_stage_name", "sfh_checksum_device", "sfh_crc32_combine", "sfh_adler32_combine",
     "sfh_set_profiling", "sfh_last_stage_ms", "sfh_stage_name", "sfh_debug_read",
@@ -96,6 +97,14 @@ def lib():
     L.sfh_compress_batch_device_async.restype = C.c_int
     L.sfh_compress_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, C.POINTER(vp), u64p, u64p, C.POINTER(Options)]
     L.sfh_compress_batch.restype = C.c_int
+    L.sfh_batch_index_size.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+    L.sfh_batch_index_size.restype = C.c_int
+    L.sfh_copy_batch_index.argtypes = [vp, vp, vp, vp, C.c_int, vp]
+    L.sfh_copy_batch_index.restype = C.c_int
+    L.sfh_decompress_batch_device_async.argtypes = [vp, sz, C.POINTER(vp), u64p, vp, vp, C.POINTER(vp), u64p, vp, C.c_uint32, vp, vp]
+    L.sfh_decompress_batch_device_async.restype = C.c_int
+    L.sfh_decompress_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, vp, vp, C.POINTER(vp), u64p, vp, C.c_uint32, vp]
+    L.sfh_decompress_batch.restype = C.c_int
     L.sfh_gather_offsets.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     L.sfh_gather_offsets.restype = C.c_int
     L.sfh_comm_ranks.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

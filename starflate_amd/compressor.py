@@ -146,6 +146,20 @@ class Compressor:
                                                               C.byref(opt), C.c_void_p(s)))
         return outs, sizes
 
+    def last_batch_index(self):
+        """Index of the last call when it was a compress batch: (index, subindex, block_bytes) -- the items' offsets
+        flattened item after item (numpy uint64; item i of n_i bytes has max(1, ceil(n_i / 32768)) + 1 of them, relative to
+        its own stream), their sub-index words (numpy uint32, 64 per segment) and every item's resolved block_bytes (numpy
+        uint32): what decompress_batch takes."""
+        items, entries = C.c_size_t(0), C.c_size_t(0)
+        self._check(self._lib.sfh_batch_index_size(self._h, C.byref(items), C.byref(entries)))
+        k, e = items.value, entries.value
+        idx = np.empty(e, dtype=np.uint64)
+        sub = np.empty(max((e - k) * _capi.SUBINDEX_WORDS, 1), dtype=np.uint32)
+        bb = np.empty(max(k, 1), dtype=np.uint32)
+        self._check(self._lib.sfh_copy_batch_index(self._h, idx.ctypes.data, sub.ctypes.data, bb.ctypes.data, 0, None))
+        return idx, sub[: (e - k) * _capi.SUBINDEX_WORDS], bb[:k]
+
     # ---- block index + GPU decompress (the reference's decompress(), /root/reference/src/decompress.hpp:63-71,
     #      for streams whose independently decodable 32 KiB segments are known) ----
     def last_block_bytes(self):
@@ -237,6 +251,57 @@ class Compressor:
                                              sub.ctypes.data if sub is not None else None, idx.size - 1,
                                              dst.ctypes.data if out_n else None, int(out_n), int(block_bytes), C.byref(st)))
         return (dst[:out_n].tobytes() if st.value == 0 else b""), st.value
+
+    # ---- many independent streams, each decoded into its own buffer, in one call (sfh_decompress_batch*) ----
+    def decompress_batch(self, streams, sizes, index=None, subindex=None, block_bytes=None, container="raw"):
+        """Host buffers: bytes-like streams and their decoded sizes -> (list of bytes, list of DecompressStatus ints).  index /
+        subindex / block_bytes: last_batch_index()'s layout (flattened, item after item), or index=None when every size is at
+        most 32768 (each stream one segment: pages from other tools).  An item whose status is not 0 comes back as b""."""
+        srcs, n, dst_n, idx, sub, bb, kind = _batch_inflate_args(streams, sizes, index, subindex, block_bytes, container)
+        k = len(srcs)
+        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in dst_n]
+        sp = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a in srcs])
+        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
+        st = np.zeros(max(k, 1), dtype=np.uint32)
+        self._check(self._lib.sfh_decompress_batch(
+            self._h, k, sp, n, idx.ctypes.data if idx is not None else None, sub.ctypes.data if sub is not None else None, dp,
+            (C.c_uint64 * k)(*dst_n), bb.ctypes.data if bb is not None else None, kind, st.ctypes.data))
+        return [dsts[i][: dst_n[i]].tobytes() if st[i] == 0 else b"" for i in range(k)], [int(v) for v in st[:k]]
+
+    def decompress_batch_tensors(self, streams, sizes, index=None, subindex=None, block_bytes=None, container="raw",
+                                 outs=None, stream=None):
+        """Device buffers: 1-D uint8 CUDA tensors -> (outs, status).  Enqueued on `stream` (default: the current one) without
+        a host synchronisation.  index: int64 CUDA tensor, subindex: int32 CUDA tensor (last_batch_index()'s layout), or
+        None; block_bytes: a host sequence.  outs: one uint8 tensor per item of at least sizes[i] bytes (default: new ones;
+        each item's decoded bytes are outs[i][:sizes[i]]); status: an int32 tensor on the device, one DecompressStatus per item."""
+        import torch
+
+        streams = list(streams)
+        for t in streams:
+            self._check_tensor(t)
+        dst_n, bb, kind = _batch_lengths(len(streams), sizes, None if index is None else index.numel(),
+                                         None if subindex is None else subindex.numel(), block_bytes, container)
+        k = len(streams)
+        for t, dt in ((index, torch.int64), (subindex, torch.int32)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+                raise ValueError("index / subindex must be contiguous int64 / int32 CUDA tensors")
+        dev = torch.device("cuda", self.device)
+        if outs is None:
+            outs = [torch.empty(max(m, 1), dtype=torch.uint8, device=dev) for m in dst_n]
+        outs = list(outs)
+        if len(outs) != k or any(o.numel() < m for o, m in zip(outs, dst_n)):
+            raise ValueError("outs must hold one tensor of at least sizes[i] bytes per item")
+        for t in outs:
+            self._check_tensor(t)
+        status = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+        sp = (C.c_void_p * k)(*[t.data_ptr() for t in streams])
+        dp = (C.c_void_p * k)(*[o.data_ptr() for o in outs])
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        self._check(self._lib.sfh_decompress_batch_device_async(
+            self._h, k, sp, (C.c_uint64 * k)(*[t.numel() for t in streams]), index.data_ptr() if index is not None else None,
+            subindex.data_ptr() if subindex is not None else None, dp, (C.c_uint64 * k)(*dst_n),
+            bb.ctypes.data if bb is not None else None, kind, C.c_void_p(status.data_ptr()), C.c_void_p(s)))
+        return outs, status[:k]
 
     def inflate_ms(self):
         ms = (C.c_float * _capi.INFLATE_NSTAGES)()
@@ -358,6 +423,47 @@ def wrapper_bytes(kind, checksum, n):
     return b"", b""
 
 
+def _batch_lengths(k, sizes, index_n, subindex_n, block_bytes, container):
+    """decompress_batch's lengths, checked before anything reaches the device: k streams, their decoded sizes, the entries of
+    the index and words of the sub-index (None: not given) -> (dst_n list, block_bytes array or None, container code)."""
+    dst_n = [int(m) for m in sizes]
+    if len(dst_n) != k:
+        raise ValueError(f"{k} streams but {len(dst_n)} sizes")
+    if any(m < 0 for m in dst_n):
+        raise ValueError("sizes must not be negative")
+    if container not in _capi.CONTAINER:
+        raise ValueError(f"container must be one of {sorted(_capi.CONTAINER)}")
+    nseg = sum(max(1, -(-m // CHUNK_BYTES)) for m in dst_n)
+    if index_n is None:
+        if subindex_n is not None:
+            raise ValueError("a subindex needs an index")
+        if any(m > CHUNK_BYTES for m in dst_n):
+            raise ValueError("without an index every size must be at most 32768")
+    else:
+        if index_n != nseg + k:
+            raise ValueError(f"index must hold sum(segments + 1) = {nseg + k} entries, not {index_n}")
+        if subindex_n is not None and subindex_n != nseg * _capi.SUBINDEX_WORDS:
+            raise ValueError(f"subindex must hold {nseg * _capi.SUBINDEX_WORDS} words, not {subindex_n}")
+    bb = None
+    if block_bytes is not None:
+        bb = np.ascontiguousarray(block_bytes, dtype=np.uint32).ravel()
+        if bb.size != k:
+            raise ValueError("block_bytes must hold one value per item")
+    return dst_n, bb, _capi.CONTAINER[container]
+
+
+def _batch_inflate_args(streams, sizes, index, subindex, block_bytes, container):
+    """decompress_batch's host arguments, checked (_batch_lengths): (sources, src_n, dst_n, index, subindex, block_bytes,
+    container) as the C-ABI takes them."""
+    srcs = [np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else np.ascontiguousarray(d, dtype=np.uint8).ravel()
+            for d in streams]
+    idx = None if index is None else np.ascontiguousarray(index, dtype=np.uint64).ravel()
+    sub = None if subindex is None else np.ascontiguousarray(subindex, dtype=np.uint32).ravel()
+    dst_n, bb, kind = _batch_lengths(len(srcs), sizes, None if idx is None else idx.size, None if sub is None else sub.size,
+                                     block_bytes, container)
+    return srcs, (C.c_uint64 * len(srcs))(*[a.size for a in srcs]), dst_n, idx, sub, bb, kind
+
+
 _DEFAULT = {}
 
 
@@ -375,3 +481,13 @@ def compress_batch(items, device=0, **kw):
     if c is None:
         c = _DEFAULT[device] = Compressor(device)
     return c.compress_batch(items, **kw)
+
+
+def decompress_batch(streams, sizes, device=0, **kw):
+    """Streams and their decoded sizes -> (list of bytes, list of statuses), all in one call (Compressor.decompress_batch).
+    The arguments are checked before a device is touched."""
+    _batch_inflate_args(streams, sizes, kw.get("index"), kw.get("subindex"), kw.get("block_bytes"), kw.get("container", "raw"))
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    return c.decompress_batch(streams, sizes, **kw)

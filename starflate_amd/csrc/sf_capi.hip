@@ -74,6 +74,18 @@ struct sfh_ctx {
   uint64_t* d_bn = nullptr;      // ... the items' sizes on the device and in pinned memory
   uint64_t* h_bn = nullptr;
   size_t bn_cap = 0;             // items d_bn / h_bn hold
+  // the index of the last call when it was a compress batch (sfh_copy_batch_index): every item's entries, item after item, in
+  // d_bix; the sub-index is ws.subidx (the call's chunks are the items' segments in order)
+  bool bix_valid = false;
+  uint64_t* d_bix = nullptr;
+  size_t d_bix_cap = 0;
+  size_t bix_items = 0, bix_entries = 0;
+  std::vector<uint32_t> bix_block_bytes;
+  uint64_t* d_implied = nullptr; // sfh_decompress_batch* without an index: every item's two implied entries
+  size_t d_implied_cap = 0;
+  uint32_t* d_bstatus = nullptr; // sfh_decompress_batch: the statuses on the device and in pinned memory
+  uint32_t* h_bstatus = nullptr;
+  size_t bstatus_cap = 0;
   char err[256] = {0};
 };
 
@@ -281,6 +293,7 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
   if (!rc && o.container) rc = ensure_sums(ctx, nchunks);
   if (rc) return rc;
   ctx->last_chunks = nchunks;
+  ctx->bix_valid = false;
   const sf::Options ko = kernel_options(o, resolve_block_bytes(o.block_bytes, n, o.effort));
   if ((ko.chain_depth || ko.recent) && (rc = ensure_order(ctx, ko.recent ? 1 : 0)) != SFH_OK) return rc;
   ctx->last_block_bytes = ko.strip_bytes;
@@ -361,6 +374,25 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
   return mark_call_end(ctx, s);
 }
 
+// The descriptor tables of a batched call (compress or decompress) are built in pinned memory and uploaded with one copy:
+// ctx->h_tab / ctx->d_tab hold at least `bytes` afterwards, and the previous call's copy has read h_tab (ev_tab) -- and, when
+// d_tab had to grow, its kernels have read d_tab.
+int stage_tables(sfh_ctx* ctx, size_t bytes) {
+  if (!ctx->ev_tab) SF_HIP(hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming), "event");
+  if (ctx->tab_pending) SF_HIP(hipEventSynchronize(ctx->ev_tab), "wait for the previous call's table copy");  // (it reads h_tab)
+  ctx->tab_pending = false;
+  if (ctx->h_tab_cap < bytes) {
+    if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
+    ctx->h_tab = nullptr;
+    ctx->h_tab_cap = 0;
+    const hipError_t e = hipHostMalloc((void**)&ctx->h_tab, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(ctx, SFH_E_NOMEM, "pinned descriptor tables", e);
+    ctx->h_tab_cap = bytes;
+  }
+  if (ctx->d_tab_cap < bytes && ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (its kernels read d_tab)
+  return grow(ctx, &ctx->d_tab, &ctx->d_tab_cap, bytes, "descriptor tables");
+}
+
 // ---- batched compression (sfh_compress_batch*) ----
 // Everything a batch call checks before it enqueues anything (`dev`: device buffers, the single call's alignment rules).
 int check_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, void* const* dsts,
@@ -412,9 +444,11 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
   std::vector<sf::BatchChunk> chunks;
   std::vector<sf::BatchItem> items;
   std::vector<sf::WrapItem> wraps;
+  std::vector<sf::BatchIndexRow> ixrows;
   std::vector<LaunchBatch> lbs;
   const uint32_t cap = ctx->batch_chunks;
   try {
+    ctx->bix_block_bytes.resize(count);
     LaunchBatch cur;
     auto close = [&] {
       if (cur.nchunks) lbs.push_back(cur);
@@ -437,6 +471,7 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
       for (uint32_t k = k0; k < k1; ++k) {
         const uint64_t b = (uint64_t)k * sf::kChunk;
         chunks.push_back(sf::BatchChunk{src + b, (uint32_t)std::min<uint64_t>(sf::kChunk, n - b), it << 1 | (k + 1 == nc ? 1u : 0u)});
+        ixrows.push_back(sf::BatchIndexRow{(uint32_t)items.size() - 1, (uint32_t)i});
       }
       cur.nchunks += k1 - k0;
     };
@@ -444,6 +479,7 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
     for (size_t i = 0; i < count; ++i) {
       const uint32_t sb = resolve_block_bytes(o.block_bytes, (size_t)src_n[i], o.effort), per = sb / sf::kChunk;
       const uint32_t nc = chunks_of((size_t)src_n[i]);
+      ctx->bix_block_bytes[i] = sb;
       if (o.container) wraps.push_back(sf::WrapItem{(uint8_t*)d_dsts[i], src_n[i], (uint32_t)i, (uint32_t)chunks.size(), nc, 0});
       if (nc <= cap) {  // whole, in the current launch batch or the next
         if (cur.nchunks + nc > cap) close();
@@ -463,38 +499,30 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
     return fail(ctx, SFH_E_NOMEM, "host memory for the descriptor tables", hipSuccess);
   }
   const uint32_t nchunks = (uint32_t)chunks.size();
-  uint32_t widest = 0;
-  for (const LaunchBatch& b : lbs) widest = std::max(widest, b.nchunks);
-  int rc = ensure_compress_ws(ctx, widest);
+  // the batch arrays hold the widest launch batch (at most a batch or a strip: ensure_compress_ws), the index arrays the call
+  ctx->bix_valid = false;
+  int rc = ensure_compress_ws(ctx, nchunks);
   if (!rc && o.container) rc = ensure_sums(ctx, nchunks);
+  if (!rc) rc = grow(ctx, &ctx->d_bix, &ctx->d_bix_cap, ((size_t)nchunks + count) * sizeof(uint64_t), "batch index");
   if (rc) return rc;
   const sf::Options ko = kernel_options(o, sf::kChunk);  // (strip_bytes: the strip table's)
   if ((ko.chain_depth || ko.recent) && (rc = ensure_order(ctx, ko.recent ? 1 : 0)) != SFH_OK) return rc;
-  // the tables, in one pinned block: chunks | strips | items | wraps (rows of 16 and 32 bytes)
+  // the tables, in one pinned block: chunks | strips | items | wraps | index rows (rows of 16, 32 and 8 bytes)
   const size_t b_chunks = chunks.size() * sizeof(sf::BatchChunk), b_strips = strips.size() * sizeof(sf::BatchStrip);
   const size_t b_items = items.size() * sizeof(sf::BatchItem), b_wraps = wraps.size() * sizeof(sf::WrapItem);
-  const size_t bytes = b_chunks + b_strips + b_items + b_wraps;
-  if (!ctx->ev_tab) SF_HIP(hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming), "event");
-  if (ctx->tab_pending) SF_HIP(hipEventSynchronize(ctx->ev_tab), "wait for the previous call's table copy");  // (it reads h_tab)
-  ctx->tab_pending = false;
-  if (ctx->h_tab_cap < bytes) {
-    if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
-    ctx->h_tab = nullptr;
-    ctx->h_tab_cap = 0;
-    const hipError_t e = hipHostMalloc((void**)&ctx->h_tab, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(ctx, SFH_E_NOMEM, "pinned descriptor tables", e);
-    ctx->h_tab_cap = bytes;
-  }
-  if (ctx->d_tab_cap < bytes && ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (its kernels read d_tab)
-  if ((rc = grow(ctx, &ctx->d_tab, &ctx->d_tab_cap, bytes, "descriptor tables"))) return rc;
+  const size_t b_ixrows = ixrows.size() * sizeof(sf::BatchIndexRow);
+  const size_t bytes = b_chunks + b_strips + b_items + b_wraps + b_ixrows;
+  if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
   memcpy(ctx->h_tab, chunks.data(), b_chunks);
   memcpy(ctx->h_tab + b_chunks, strips.data(), b_strips);
   memcpy(ctx->h_tab + b_chunks + b_strips, items.data(), b_items);
   memcpy(ctx->h_tab + b_chunks + b_strips + b_items, wraps.data(), b_wraps);
+  memcpy(ctx->h_tab + b_chunks + b_strips + b_items + b_wraps, ixrows.data(), b_ixrows);
   const sf::BatchChunk* d_chunks = (const sf::BatchChunk*)ctx->d_tab;
   const sf::BatchStrip* d_strips = (const sf::BatchStrip*)(ctx->d_tab + b_chunks);
   sf::BatchItem* d_items = (sf::BatchItem*)(ctx->d_tab + b_chunks + b_strips);
   const sf::WrapItem* d_wraps = (const sf::WrapItem*)(ctx->d_tab + b_chunks + b_strips + b_items);
+  const sf::BatchIndexRow* d_ixrows = (const sf::BatchIndexRow*)(ctx->d_tab + b_chunks + b_strips + b_items + b_wraps);
 
   ctx->index_valid = false;  // a batch has no single index: the index functions refuse until the next single call
   ctx->last_chunks = lbs.back().nchunks;
@@ -517,17 +545,22 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
   for (uint32_t bi = 0; bi < nbatches; ++bi) {
     const LaunchBatch& b = lbs[bi];
     const sf::BatchTables bt{d_strips + b.s0, b.nstrips, d_chunks + b.c0, d_items + b.i0, b.nitems};
+    sf::Workspace w = ctx->ws;  // k_scan's offsets and k_emit's sub-index land at the batch's places in the call's index arrays
+    w.offsets += b.c0;
+    w.subidx += (size_t)b.c0 * 2 * sf::kSubRegions;
     hipEvent_t* ev = prof ? &ctx->ev[(size_t)bi * sfh_ctx::kEvPerBatch] : nullptr;
     if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
     SF_HIP(sf::launch_lz77(nullptr, 0, b.nchunks, ctx->ws, ko, s, &bt), "launch k_lz77");
     if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
     SF_HIP(sf::launch_plan(0, b.nchunks, ctx->ws, ko, s, &bt), "launch k_plan");
     if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
-    SF_HIP(sf::launch_scan(b.nchunks, ctx->ws, hdr, false, d_out_n, s, &bt), "launch k_scan");
+    SF_HIP(sf::launch_scan(b.nchunks, w, hdr, false, d_out_n, s, &bt), "launch k_scan");
     if (ev) SF_HIP(hipEventRecord(ev[3], s), "event");
-    SF_HIP(sf::launch_emit(nullptr, 0, b.nchunks, ctx->ws, nullptr, s, &bt), "launch k_emit");
+    SF_HIP(sf::launch_emit(nullptr, 0, b.nchunks, w, nullptr, s, &bt), "launch k_emit");
     if (ev) SF_HIP(hipEventRecord(ev[4], s), "event");
   }
+  // (behind the launch batches and ahead of k_wrap_batch: d_out_n is still every stream's end before its trailer)
+  SF_HIP(sf::launch_batch_index(d_chunks, d_ixrows, d_items, ctx->ws.offsets, d_out_n, nchunks, ctx->d_bix, s), "launch k_batch_index");
   if (o.container) {
     SF_HIP(sf::launch_checksum_batch(d_chunks, nchunks, o.container, ctx->ws.sums, s), "launch k_checksum");
     SF_HIP(sf::launch_wrap_batch(ctx->ws.sums, d_wraps, (uint32_t)count, o.container, d_out_n, s), "launch k_wrap");
@@ -537,6 +570,181 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
     ctx->ev_batches = nbatches;
   }
   ctx->ev_valid = prof;
+  ctx->bix_valid = true;
+  ctx->bix_items = count;
+  ctx->bix_entries = (size_t)nchunks + count;
+  return mark_call_end(ctx, s);
+}
+
+// ---- batched decompression (sfh_decompress_batch*) ----
+// Everything the call checks before it enqueues anything (`dev`: device buffers, the single decoder's alignment rules).
+int check_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, const uint64_t* index,
+                        const uint32_t* subindex, void* const* dsts, const uint64_t* dst_n, const uint32_t* block_bytes,
+                        uint32_t container, const uint32_t* status, bool dev) {
+  if (!ctx || container > SFH_GZIP) return fail(ctx, SFH_E_INVALID_ARG, "argument (container)", hipSuccess);
+  if (count == 0) return SFH_OK;
+  if (!srcs || !src_n || !dsts || !dst_n || !status) return fail(ctx, SFH_E_INVALID_ARG, "null array", hipSuccess);
+  if (count > ((size_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "too many items", hipSuccess);
+  if (subindex && !index) return fail(ctx, SFH_E_INVALID_ARG, "a sub-index without an index", hipSuccess);
+  if (dev && (((uintptr_t)index & 7) || ((uintptr_t)subindex & 3) || ((uintptr_t)status & 3)))
+    return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (index 8, sub-index 4, status 4)", hipSuccess);
+  uint64_t segs = 0;
+  for (size_t i = 0; i < count; ++i) {
+    if ((!srcs[i] && src_n[i]) || (!dsts[i] && dst_n[i])) return fail(ctx, SFH_E_INVALID_ARG, "null item pointer", hipSuccess);
+    if (dev && (((uintptr_t)srcs[i] & 3) || ((uintptr_t)dsts[i] & 15)))
+      return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, dst 16)", hipSuccess);
+    if (dst_n[i] > ((uint64_t)1 << 44)) return fail(ctx, SFH_E_INVALID_ARG, "item too large", hipSuccess);
+    const uint32_t bb = block_bytes ? block_bytes[i] : 0u;
+    if (bb % sf::kChunk || bb > sf::kMaxStrip)
+      return fail(ctx, SFH_E_INVALID_ARG, "block_bytes: a multiple of 32768 up to 16 MiB (0 = 32768)", hipSuccess);
+    if (!index && dst_n[i] > sf::kChunk) return fail(ctx, SFH_E_INVALID_ARG, "no index, and an item above 32768 bytes", hipSuccess);
+    segs += chunks_of((size_t)dst_n[i]);
+  }
+  if (segs > ((uint64_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 segments in one call", hipSuccess);
+  std::vector<size_t> ord;
+  try {
+    ord.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  // (a destination of no bytes is written nothing and overlaps nothing: it is left out)
+  size_t m = 0;
+  for (size_t i = 0; i < count; ++i)
+    if (dst_n[i]) ord[m++] = i;
+  std::sort(ord.begin(), ord.begin() + (std::ptrdiff_t)m, [&](size_t a, size_t b) { return (uintptr_t)dsts[a] < (uintptr_t)dsts[b]; });
+  for (size_t k = 1; k < m; ++k)
+    if ((uintptr_t)dsts[ord[k - 1]] + dst_n[ord[k - 1]] > (uintptr_t)dsts[ord[k]])
+      return fail(ctx, SFH_E_INVALID_ARG, "destination ranges overlap", hipSuccess);
+  return SFH_OK;
+}
+
+struct InflateBatch {
+  uint32_t r0 = 0, nseg = 0, s0 = 0, nstrips = 0;  // its rows in the call's segment and strip tables
+};
+
+// Device buffers, arguments checked.  The host builds the tables -- per segment, per strip (both cut into launch batches of
+// whole items, an item larger than a batch into batches of its own at its strips, as sfh_decompress_device cuts a call),
+// per item, and with a container per checksum chunk -- uploads them in one copy, and then: k_inflate_head (wrappers,
+// implied index entries), the token and byte kernels batch after batch, k_checksum_batch over the decoded bytes and
+// k_inflate_fold (every item's status).
+int enqueue_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, const uint64_t* d_index,
+                          const uint32_t* d_subindex, void* const* d_dsts, const uint64_t* dst_n, const uint32_t* block_bytes,
+                          uint32_t container, uint32_t* d_status, hipStream_t s) {
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();  // see enqueue()
+  const uint64_t trailer = container == SFH_ZLIB ? 4 : container == SFH_GZIP ? 8 : 0;
+  std::vector<sf::InflateSeg> segs;
+  std::vector<sf::InflateStrip> strips;
+  std::vector<sf::InflateItem> items;
+  std::vector<sf::BatchChunk> sums;
+  std::vector<InflateBatch> lbs;
+  const uint32_t cap = ctx->batch_chunks;
+  int rc = SFH_OK;
+  if (!d_index && (rc = grow(ctx, &ctx->d_implied, &ctx->d_implied_cap, 2 * count * sizeof(uint64_t), "implied index")))
+    return rc;
+  try {
+    items.resize(count);
+    InflateBatch cur;
+    auto close = [&] {
+      if (cur.nseg) lbs.push_back(cur);
+      cur = InflateBatch{};
+      cur.r0 = (uint32_t)segs.size();
+      cur.s0 = (uint32_t)strips.size();
+    };
+    close();
+    uint64_t entry = 0;  // the item's first index entry (items before: their segments + 1 each)
+    for (size_t i = 0; i < count; ++i) {
+      const uint32_t nseg = chunks_of((size_t)dst_n[i]);
+      const uint32_t sps = (block_bytes && block_bytes[i]) ? block_bytes[i] / sf::kChunk : 1u;
+      const uint8_t* src = (const uint8_t*)d_srcs[i];
+      uint8_t* dst = (uint8_t*)d_dsts[i];
+      const uint64_t* ix = d_index ? d_index + entry : ctx->d_implied + 2 * i;
+      const uint64_t body_n = container ? (src_n[i] > trailer ? src_n[i] - trailer : 0) : src_n[i];
+      items[i] = sf::InflateItem{src, src_n[i], dst_n[i], d_index ? nullptr : ctx->d_implied + 2 * i, d_index ? ix : nullptr,
+                                 (uint32_t)segs.size(), nseg, 0, 0, 0, 0};
+      // whole, in the current launch batch or the next; an item larger than a batch: batches of its own, of whole strips
+      const uint32_t piece = nseg <= cap ? nseg : std::max(sps, cap / sps * sps);
+      if (nseg > cap || cur.nseg + nseg > cap) close();
+      for (uint32_t k0 = 0; k0 < nseg; k0 += piece) {
+        if (k0) close();
+        const uint32_t k1 = std::min(nseg, k0 + piece);
+        for (uint32_t k = k0; k < k1; k += sps) {
+          strips.push_back(sf::InflateStrip{cur.nseg + (k - k0), std::min(sps, k1 - k)});
+          ++cur.nstrips;
+        }
+        for (uint32_t k = k0; k < k1; ++k) {
+          const uint64_t ob = (uint64_t)k * sf::kChunk;
+          const uint32_t on = (uint32_t)std::min<uint64_t>(sf::kChunk, dst_n[i] - ob);
+          // (the segments are the call's in item order: the flattened sub-index holds segment g at g * SFH_SUBINDEX_WORDS)
+          segs.push_back(sf::InflateSeg{src, ix + k, d_subindex ? d_subindex + segs.size() * SFH_SUBINDEX_WORDS : nullptr,
+                                        dst + ob, body_n, on, (k % sps) * sf::kChunk | (container ? sf::kSegWrapped : 0u)});
+          if (container) sums.push_back(sf::BatchChunk{dst + ob, on, 0u});
+        }
+        cur.nseg += k1 - k0;
+      }
+      if (nseg > cap) close();
+      entry += nseg + 1;
+    }
+    close();
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory for the descriptor tables", hipSuccess);
+  }
+  const uint32_t nseg = (uint32_t)segs.size();
+  uint32_t widest = 0;
+  for (const InflateBatch& b : lbs) widest = std::max(widest, b.nseg);
+  rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, (size_t)nseg * sizeof(sf::SegInfo), "segment records");
+  if (!rc) rc = ensure_dtok(ctx, widest);
+  if (!rc && container) rc = ensure_sums(ctx, nseg);
+  if (rc) return rc;
+  // the tables, in one pinned block: segments | items | strips | checksum chunks (rows of 48, 64, 8 and 16 bytes)
+  const size_t b_segs = segs.size() * sizeof(sf::InflateSeg), b_items = items.size() * sizeof(sf::InflateItem);
+  const size_t b_strips = strips.size() * sizeof(sf::InflateStrip), b_sums = sums.size() * sizeof(sf::BatchChunk);
+  const size_t o_sums = (b_segs + b_items + b_strips + 15) / 16 * 16, bytes = o_sums + b_sums;
+  if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
+  memcpy(ctx->h_tab, segs.data(), b_segs);
+  memcpy(ctx->h_tab + b_segs, items.data(), b_items);
+  memcpy(ctx->h_tab + b_segs + b_items, strips.data(), b_strips);
+  memcpy(ctx->h_tab + o_sums, sums.data(), b_sums);
+  sf::InflateSeg* t_segs = (sf::InflateSeg*)ctx->d_tab;
+  sf::InflateItem* t_items = (sf::InflateItem*)(ctx->d_tab + b_segs);
+  const sf::InflateStrip* t_strips = (const sf::InflateStrip*)(ctx->d_tab + b_segs + b_items);
+  sf::BatchChunk* t_sums = (sf::BatchChunk*)(ctx->d_tab + o_sums);
+
+  ctx->index_valid = false;
+  ctx->bix_valid = false;
+  ctx->last_chunks = nseg;
+  ctx->last_dtok_bytes = (size_t)widest * sf::kChunk * sizeof(uint32_t);
+  const bool prof = ctx->profiling != 0;
+  if ((rc = order_behind_last_call(ctx, s)) != SFH_OK) return rc;
+  SF_HIP(hipMemcpyAsync(ctx->d_tab, ctx->h_tab, bytes, hipMemcpyHostToDevice, s), "descriptor tables");
+  SF_HIP(hipEventRecord(ctx->ev_tab, s), "event");
+  ctx->tab_pending = true;
+  const uint32_t nbatches = (uint32_t)lbs.size();
+  ctx->ev_inf_valid = false;
+  if (prof) {
+    const size_t need = (size_t)nbatches * (SFH_INFLATE_NSTAGES + 1);
+    while (ctx->ev_inf.size() < need) {
+      hipEvent_t e = nullptr;
+      SF_HIP(hipEventCreate(&e), "event");
+      ctx->ev_inf.push_back(e);
+    }
+  }
+  SF_HIP(sf::launch_inflate_head(t_items, (uint32_t)count, container, t_segs, container ? t_sums : nullptr, s), "launch k_inflate_head");
+  for (uint32_t bi = 0; bi < nbatches; ++bi) {
+    const InflateBatch& b = lbs[bi];
+    sf::SegInfo* binfo = ctx->ws.seginfo + b.r0;
+    hipEvent_t* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
+    if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
+    SF_HIP(sf::launch_inflate_tokens_batch(t_segs + b.r0, b.nseg, ctx->ws.tokens, binfo, d_subindex != nullptr,
+                                           !ctx->inflate_serial, s), "launch k_inflate_tokens");
+    if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
+    SF_HIP(sf::launch_inflate_bytes_batch(t_segs + b.r0, t_strips + b.s0, b.nstrips, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes");
+    if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
+  }
+  ctx->ev_inf_batches = nbatches;
+  ctx->ev_inf_valid = prof;
+  if (container) SF_HIP(sf::launch_checksum_batch(t_sums, nseg, container, ctx->ws.sums, s), "launch k_checksum");
+  SF_HIP(sf::launch_inflate_fold(t_items, (uint32_t)count, ctx->ws.seginfo, ctx->ws.sums, container, d_status, s), "launch k_inflate_fold");
   return mark_call_end(ctx, s);
 }
 
@@ -706,6 +914,10 @@ void sfh_destroy(sfh_ctx* ctx) {
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   (void)hipFree(ctx->d_bn);
   if (ctx->h_bn) (void)hipHostFree(ctx->h_bn);
+  (void)hipFree(ctx->d_bix);
+  (void)hipFree(ctx->d_implied);
+  (void)hipFree(ctx->d_bstatus);
+  if (ctx->h_bstatus) (void)hipHostFree(ctx->h_bstatus);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -884,6 +1096,135 @@ int sfh_compress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, cons
   return SFH_OK;
 }
 
+int sfh_batch_index_size(const sfh_ctx* ctx, size_t* items, size_t* entries) {
+  if (!ctx || !items || !entries || !ctx->bix_valid) return SFH_E_INVALID_ARG;
+  *items = ctx->bix_items;
+  *entries = ctx->bix_entries;
+  return SFH_OK;
+}
+
+int sfh_copy_batch_index(sfh_ctx* ctx, uint64_t* index, uint32_t* subindex, uint32_t* block_bytes, int dst_on_device, void* stream) {
+  if (!ctx || !ctx->bix_valid) return fail(ctx, SFH_E_INVALID_ARG, "batch index: the last call on this context was no compress batch", hipSuccess);
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  if (int rc = order_behind_last_call(ctx, s)) return rc;  // written by the batch call's kernels, maybe on another stream
+  const hipMemcpyKind kind = dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t segs = ctx->bix_entries - ctx->bix_items;
+  if (index) SF_HIP(hipMemcpyAsync(index, ctx->d_bix, ctx->bix_entries * sizeof(uint64_t), kind, s), "copy batch index");
+  if (subindex) SF_HIP(hipMemcpyAsync(subindex, ctx->ws.subidx, segs * SFH_SUBINDEX_WORDS * sizeof(uint32_t), kind, s), "copy batch sub-index");
+  if (block_bytes && dst_on_device)
+    SF_HIP(hipMemcpyAsync(block_bytes, ctx->bix_block_bytes.data(), ctx->bix_items * sizeof(uint32_t), hipMemcpyHostToDevice, s),
+           "copy block_bytes");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  if (block_bytes && !dst_on_device) memcpy(block_bytes, ctx->bix_block_bytes.data(), ctx->bix_items * sizeof(uint32_t));
+  return SFH_OK;
+}
+
+int sfh_decompress_batch_device_async(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n,
+                                      const uint64_t* d_index, const uint32_t* d_subindex, void* const* d_dsts,
+                                      const uint64_t* dst_n, const uint32_t* block_bytes, uint32_t container,
+                                      uint32_t* d_status, void* stream) {
+  int rc = check_inflate_batch(ctx, count, d_srcs, src_n, d_index, d_subindex, d_dsts, dst_n, block_bytes, container, d_status, true);
+  if (rc || count == 0) return rc;
+  return enqueue_inflate_batch(ctx, count, d_srcs, src_n, d_index, d_subindex, d_dsts, dst_n, block_bytes, container, d_status,
+                               stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, const uint64_t* index,
+                         const uint32_t* subindex, void* const* dsts, const uint64_t* dst_n, const uint32_t* block_bytes,
+                         uint32_t container, uint32_t* status) {
+  int rc = check_inflate_batch(ctx, count, srcs, src_n, index, subindex, dsts, dst_n, block_bytes, container, status, false);
+  if (rc || count == 0) return rc;
+  // As sfh_compress_batch: the items packed into the device staging (16-byte aligned) through one pinned buffer, one copy per
+  // kStageBytes each way; only the items whose status is 0 are copied out of it.
+  constexpr size_t kStageBytes = (size_t)kPipeBatchChunks * sf::kChunk;
+  std::vector<uint64_t> in_off, out_off;
+  std::vector<const void*> d_srcs;
+  std::vector<void*> d_dsts;
+  size_t entries = 0, segs = 0;
+  try {
+    in_off.resize(count + 1);
+    out_off.resize(count + 1);
+    d_srcs.resize(count);
+    d_dsts.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (size_t i = 0; i < count; ++i) {
+    in_off[i + 1] = (in_off[i] + src_n[i] + 15) / 16 * 16;
+    out_off[i + 1] = (out_off[i] + dst_n[i] + 15) / 16 * 16;
+    segs += chunks_of((size_t)dst_n[i]);
+  }
+  entries = segs + count;
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t s = ctx->stream;
+  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
+  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_off[count] ? out_off[count] : 16, "output staging");
+  if (!rc && index) rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, entries * sizeof(uint64_t), "index staging");
+  if (!rc && subindex) rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, segs * SFH_SUBINDEX_WORDS * sizeof(uint32_t), "sub-index staging");
+  if (!rc && ctx->bstatus_cap < count) {
+    (void)hipFree(ctx->d_bstatus);
+    if (ctx->h_bstatus) (void)hipHostFree(ctx->h_bstatus);
+    ctx->d_bstatus = ctx->h_bstatus = nullptr;
+    ctx->bstatus_cap = 0;
+    if (hipMalloc(&ctx->d_bstatus, count * sizeof(uint32_t)) != hipSuccess ||
+        hipHostMalloc((void**)&ctx->h_bstatus, count * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+      rc = fail(ctx, SFH_E_NOMEM, "batch statuses", hipSuccess);
+    else
+      ctx->bstatus_cap = count;
+  }
+  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
+    ctx->h_stage = nullptr;
+    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
+  }
+  if (rc) return rc;
+  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
+  size_t item = 0;
+  for (uint64_t p0 = 0; p0 < in_off[count]; p0 += kStageBytes) {
+    const uint64_t p1 = std::min<uint64_t>(in_off[count], p0 + kStageBytes);
+    while (item < count && in_off[item] + src_n[item] <= p0) ++item;
+    for (size_t i = item; i < count && in_off[i] < p1; ++i) {
+      const uint64_t a = std::max(p0, in_off[i]), b = std::min(p1, in_off[i] + src_n[i]);
+      if (a < b) memcpy(ctx->h_stage + (a - p0), (const uint8_t*)srcs[i] + (a - in_off[i]), b - a);
+    }
+    SF_HIP(hipMemcpyAsync(ctx->d_in + p0, ctx->h_stage, p1 - p0, hipMemcpyHostToDevice, s), "H2D");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");  // (the next piece refills h_stage)
+  }
+  if (index) SF_HIP(hipMemcpyAsync(ctx->d_index, index, entries * sizeof(uint64_t), hipMemcpyHostToDevice, s), "H2D index");
+  if (subindex)
+    SF_HIP(hipMemcpyAsync(ctx->d_sub, subindex, segs * SFH_SUBINDEX_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, s), "H2D sub-index");
+  for (size_t i = 0; i < count; ++i) {
+    d_srcs[i] = ctx->d_in + in_off[i];
+    d_dsts[i] = ctx->d_out + out_off[i];
+  }
+  if ((rc = enqueue_inflate_batch(ctx, count, d_srcs.data(), src_n, index ? ctx->d_index : nullptr, subindex ? ctx->d_sub : nullptr,
+                                  d_dsts.data(), dst_n, block_bytes, container, ctx->d_bstatus, s)) != SFH_OK) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy statuses");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  for (size_t i = 0; i < count; ++i) status[i] = ctx->h_bstatus[i];
+  // down: the packed output in pieces, each item with status 0 out of the pieces it lies in
+  const uint64_t end = out_off[count];
+  item = 0;
+  for (uint64_t p0 = 0; p0 < end; p0 += kStageBytes) {
+    const uint64_t p1 = std::min<uint64_t>(end, p0 + kStageBytes);
+    while (item < count && out_off[item] + dst_n[item] <= p0) ++item;
+    bool any = false;
+    for (size_t i = item; i < count && out_off[i] < p1 && !any; ++i) any = status[i] == 0 && dst_n[i] && out_off[i] + dst_n[i] > p0;
+    if (!any) continue;
+    SF_HIP(hipMemcpyAsync(ctx->h_stage, ctx->d_out + p0, p1 - p0, hipMemcpyDeviceToHost, s), "D2H");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+    for (size_t i = item; i < count && out_off[i] < p1; ++i) {
+      if (status[i] != 0) continue;
+      const uint64_t a = std::max(p0, out_off[i]), b = std::min(p1, out_off[i] + dst_n[i]);
+      if (a < b) memcpy((uint8_t*)dsts[i] + (a - out_off[i]), ctx->h_stage + (a - p0), b - a);
+    }
+  }
+  return SFH_OK;
+}
+
 uint32_t sfh_last_block_bytes(const sfh_ctx* ctx) { return (ctx && ctx->index_valid) ? ctx->last_block_bytes : 0u; }
 
 size_t sfh_index_entries(const sfh_ctx* ctx) { return (ctx && ctx->index_valid) ? (size_t)ctx->last_chunks + 1 : 0; }
@@ -938,6 +1279,7 @@ int sfh_decompress_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const u
   if (rc) return rc;
   ctx->last_dtok_bytes = std::min<size_t>(nseg, batch) * sf::kChunk * sizeof(uint32_t);
   ctx->index_valid = false;  // the last call is now this one: what sfh_debug_read returns belongs to it
+  ctx->bix_valid = false;
   ctx->last_chunks = (uint32_t)nseg;
   const bool prof = ctx->profiling != 0;
   if ((rc = order_behind_last_call(ctx, s)) != SFH_OK) return rc;

@@ -274,7 +274,122 @@ __global__ __launch_bounds__(KW_THREADS) void k_wrap_batch(const uint32_t* __res
   wrap_stream(sums + I.sum0, I.nchunks, I.n, kind, I.dst, total + I.out, nullptr, chunk_op);
 }
 
+// ---- sfh_decompress_batch*: the wrappers of the items, and every item's status ----
+// the reference's DecompressStatus values these kernels produce themselves (src/decompress.hpp:13-23)
+constexpr uint32_t kStOk = 0, kStError = 1, kStDstTooSmall = 4, kStSrcTooSmall = 5;
+
+// One lane per item, before the token kernels: the wrapper checks of include/starflate/container.hpp in its order (the
+// header, the stream long enough for it, gzip's ISIZE against the output), the trailer's checksum, and with an index its
+// first entry against the header's end.  An index-free call gets the item's one segment here: from the header's end to the
+// trailer (nothing, for an item whose wrapper failed: its status is the wrapper's whatever the segment does).  A gzip item
+// whose ISIZE is below its output size is decoded, as container.hpp decodes it, into the first ISIZE bytes only: its segment
+// rows (segs) and checksum rows (sums) are cut down to them, and a body longer than that runs into DstTooSmall there.
+__global__ __launch_bounds__(256) void k_inflate_head(InflateItem* __restrict__ items, uint32_t nitems, uint32_t kind,
+                                                      InflateSeg* __restrict__ segs, BatchChunk* __restrict__ sums) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nitems) return;
+  InflateItem& I = items[i];
+  const uint8_t* p = I.src;
+  const uint64_t n = I.src_n;
+  uint32_t st = kStOk, want = 0, isize = 0;
+  uint64_t hdr = 0, end = n;
+  if (kind == kChecksumAdler32) {
+    if (n < 6) {
+      st = kStSrcTooSmall;
+    } else {
+      const uint32_t cmf = p[0], flg = p[1];
+      if ((cmf & 0x0Fu) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0 || (flg & 0x20u) != 0) st = kStError;
+      hdr = 2;
+      end = n - 4;
+      want = (uint32_t)p[n - 4] << 24 | (uint32_t)p[n - 3] << 16 | (uint32_t)p[n - 2] << 8 | p[n - 1];
+    }
+  } else if (kind == kChecksumCrc32) {
+    if (n < 18) {
+      st = kStSrcTooSmall;
+    } else if (p[0] != 0x1F || p[1] != 0x8B || p[2] != 8 || (p[3] & 0xE0u) != 0) {
+      st = kStError;
+    } else {
+      const uint32_t flg = p[3];
+      end = n - 8;
+      uint64_t at = 10;
+      if (flg & 0x04u) {  // FEXTRA
+        if (at + 2 > end) st = kStSrcTooSmall;
+        else at += 2 + (p[at] | (uint32_t)p[at + 1] << 8);
+      }
+      for (uint32_t bit = 0x08u; st == kStOk && bit <= 0x10u; bit <<= 1) {  // FNAME, FCOMMENT: zero-terminated
+        if (!(flg & bit)) continue;
+        while (at < end && p[at] != 0) ++at;
+        ++at;
+      }
+      if (flg & 0x02u) at += 2;  // FHCRC
+      if (st == kStOk && at > end) st = kStSrcTooSmall;
+      hdr = at;
+      want = p[n - 8] | (uint32_t)p[n - 7] << 8 | (uint32_t)p[n - 6] << 16 | (uint32_t)p[n - 5] << 24;
+      isize = p[n - 4] | (uint32_t)p[n - 3] << 8 | (uint32_t)p[n - 2] << 16 | (uint32_t)p[n - 1] << 24;
+      if (st == kStOk && isize > I.dst_n) st = kStDstTooSmall;
+    }
+  }
+  // (a raw item's index is the caller's business, as in sfh_decompress_device: its first entry need not be 0)
+  if (kind != 0 && st == kStOk && I.ix0 && *I.ix0 != hdr) st = kStError;
+  if (kind == kChecksumCrc32 && st == kStOk && isize < I.dst_n)
+    for (uint32_t k = 0; k < I.nseg; ++k) {
+      const uint64_t ob = (uint64_t)k * kChunk;
+      const uint32_t on = isize > ob ? (isize - ob < kChunk ? (uint32_t)(isize - ob) : kChunk) : 0u;
+      segs[I.seg0 + k].out_n = on;
+      sums[I.seg0 + k].n_raw = on;
+    }
+  if (I.implied) {
+    I.implied[0] = st == kStOk ? hdr : 0;
+    I.implied[1] = st == kStOk ? end : 0;
+  }
+  I.wst = st;
+  I.want = want;
+  I.isize = isize;
+}
+
+// One workgroup per item, behind every launch batch: the first failing segment in the item's stream order (what
+// k_inflate_status is to the single call) after the wrapper's status; with a container and a clean body the checksum of the
+// decoded bytes, folded from k_checksum_batch's partials by wrap_stream -- the compressor's fold -- against the trailer's.
+__global__ __launch_bounds__(KW_THREADS) void k_inflate_fold(const InflateItem* __restrict__ items, const SegInfo* __restrict__ info,
+                                                             const uint32_t* __restrict__ sums, uint32_t kind,
+                                                             uint32_t* __restrict__ status, uint32_t chunk_op) {
+  __shared__ uint32_t s_first, s_sum;
+  const uint32_t t = threadIdx.x;
+  const InflateItem I = items[blockIdx.x];
+  if (t == 0) s_first = 0xFFFFFFFFu;
+  __syncthreads();
+  for (uint32_t k = t; k < I.nseg; k += KW_THREADS)
+    if (info[I.seg0 + k].status != kStOk) {
+      atomicMin(&s_first, k);
+      break;
+    }
+  __syncthreads();
+  const uint32_t f = s_first;
+  uint32_t st = I.wst != kStOk ? I.wst : (f == 0xFFFFFFFFu ? kStOk : info[I.seg0 + f].status);
+  if (kind != 0 && st == kStOk) {  // (uniform)
+    // the checksum of what was decoded: gzip's first ISIZE bytes (k_inflate_head cut the rows down to them), else all
+    const uint64_t n = (kind == kChecksumCrc32 && I.isize < I.dst_n) ? I.isize : I.dst_n;
+    const uint32_t nch = n ? (uint32_t)((n + kChunk - 1) / kChunk) : 1u;
+    wrap_stream(sums + I.seg0, nch, n, kind, nullptr, nullptr, &s_sum, chunk_op);
+    __syncthreads();
+    if (s_sum != I.want) st = kStError;
+  }
+  if (t == 0) status[blockIdx.x] = st;
+}
+
 }  // namespace
+
+hipError_t launch_inflate_head(InflateItem* items, uint32_t nitems, uint32_t container, InflateSeg* segs, BatchChunk* sums,
+                               hipStream_t s) {
+  hipLaunchKernelGGL(k_inflate_head, dim3((nitems + 255) / 256), dim3(256), 0, s, items, nitems, container, segs, sums);
+  return hipGetLastError();
+}
+
+hipError_t launch_inflate_fold(const InflateItem* items, uint32_t nitems, const SegInfo* info, const uint32_t* sums,
+                               uint32_t container, uint32_t* status, hipStream_t s) {
+  hipLaunchKernelGGL(k_inflate_fold, dim3(nitems), dim3(KW_THREADS), 0, s, items, info, sums, container, status, kChunkOp);
+  return hipGetLastError();
+}
 
 uint32_t wrapper_header_bytes(uint32_t kind) { return kind == kChecksumAdler32 ? 2u : kind == kChecksumCrc32 ? 10u : 0u; }
 

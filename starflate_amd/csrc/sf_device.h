@@ -202,8 +202,40 @@ struct WrapItem {     // per item of the call (the batched k_checksum / k_wrap)
   uint32_t nchunks;
   uint32_t pad;
 };
+struct BatchIndexRow { // per chunk of the call (k_batch_index: the batch's index, sfh_copy_batch_index)
+  uint32_t piece;     // its row in the call's item table (the piece of its item in one launch batch)
+  uint32_t item;      // its item's index in the call
+};
 static_assert(sizeof(BatchStrip) == 16 && sizeof(BatchChunk) == 16 && sizeof(BatchItem) == 32 && sizeof(WrapItem) == 32,
               "descriptor rows (the host packs them into one upload)");
+// Batched decompression (sfh_decompress_batch*): the decoder's kernels with a compile-time BATCH parameter read these rows
+// where the single call derives a segment's stream, index entries, output and history from its number.
+struct InflateSeg {      // per segment of a launch batch (k_inflate_tokens*, k_inflate_bytes)
+  const uint8_t* src;    // its item's stream (index entries are offsets into it)
+  const uint64_t* ix;    // its two index entries: [ix[0], ix[1]) are its stream bytes
+  const uint32_t* sub;   // its SFH_SUBINDEX_WORDS sub-index words (k_inflate_tokens_sub only)
+  uint8_t* dst;          // its first output byte (16-byte aligned)
+  uint64_t src_n;        // stream bytes the decoder may read (a wrapped item: its trailer excluded)
+  uint32_t out_n;        // output bytes
+  uint32_t hist;         // bytes of its strip before it (how far back a match may reach beyond it) | kSegWrapped
+};
+constexpr uint32_t kSegWrapped = 0x80000000u;  // InflateSeg.hist: a zlib / gzip item's segment (a body that ends short is Error)
+struct InflateStrip {    // per strip of a launch batch (k_inflate_bytes: one workgroup each)
+  uint32_t seg0, nseg;   // its first segment in the launch batch, its segments
+};
+struct InflateItem {     // per item of the call (k_inflate_head, k_inflate_fold)
+  const uint8_t* src;
+  uint64_t src_n;
+  uint64_t dst_n;
+  uint64_t* implied;     // index-free call: where k_inflate_head writes the item's two index entries (null: an index is given)
+  const uint64_t* ix0;   // with an index: the item's first entry (checked against the wrapper header's end)
+  uint32_t seg0, nseg;   // its first segment in the call's segment records (and checksum partials), its segments
+  uint32_t wst;          // written by k_inflate_head: the wrapper's status (0: in order)
+  uint32_t want;         //   the checksum the trailer carries
+  uint32_t isize;        //   gzip: ISIZE
+  uint32_t pad;
+};
+static_assert(sizeof(InflateSeg) == 48 && sizeof(InflateStrip) == 8 && sizeof(InflateItem) == 64, "decoder descriptor rows");
 struct BatchTables {  // the device tables of one launch batch (null: the single call's implicit geometry)
   const BatchStrip* strips;
   uint32_t nstrips;
@@ -223,6 +255,9 @@ hipError_t launch_scan(uint32_t nchunks, const Workspace& ws, uint64_t base, boo
                        const BatchTables* bt = nullptr);
 hipError_t launch_emit(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws,
                        uint8_t* dst, hipStream_t s, const BatchTables* bt = nullptr);
+// after every launch batch of a batched call: the items' index entries (item-relative offsets, item after item) into `index`
+hipError_t launch_batch_index(const BatchChunk* chunks, const BatchIndexRow* rows, const BatchItem* pieces, const uint64_t* offsets,
+                              const uint64_t* total, uint32_t nchunks, uint64_t* index, hipStream_t s);
 hipError_t init_kernels();
 
 // sf_checksum.hip
@@ -247,6 +282,17 @@ hipError_t launch_inflate_tokens_sub(const uint8_t* src, uint64_t src_n, const u
 hipError_t launch_inflate_bytes(const uint8_t* src, uint64_t src_n, uint32_t nseg, const uint32_t* tokens, SegInfo* info,
                                 uint8_t* dst, uint32_t sps, hipStream_t s);
 hipError_t launch_inflate_status(const SegInfo* info, uint32_t nseg, uint32_t* d_result, hipStream_t s);
+// batched: the launch batch's segment rows stand in for src / index / dst_n / sps (info and tokens: the batch's own)
+hipError_t launch_inflate_tokens_batch(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool sub,
+                                       bool speculate, hipStream_t s);
+hipError_t launch_inflate_bytes_batch(const InflateSeg* rows, const InflateStrip* strips, uint32_t nstrips,
+                                      const uint32_t* tokens, SegInfo* info, hipStream_t s);
+// per item of the call: the wrapper (before the token kernels), then the status fold (behind every launch batch)
+// (segs, sums: the call's segment and checksum rows, which a gzip item with ISIZE below its output size cuts down to ISIZE)
+hipError_t launch_inflate_head(InflateItem* items, uint32_t nitems, uint32_t container, InflateSeg* segs, BatchChunk* sums,
+                               hipStream_t s);
+hipError_t launch_inflate_fold(const InflateItem* items, uint32_t nitems, const SegInfo* info, const uint32_t* sums,
+                               uint32_t container, uint32_t* status, hipStream_t s);
 
 // sf_guard.hip: does the LDS execute a returning atomic's lanes in ascending order (op 0: ds_wrxchg_rtn_b32, 1: ds_mskor_rtn_b32)?
 // d_result[0] = mismatches against the sequential model, [1] = positions checked

@@ -47,23 +47,44 @@ constexpr uint32_t KB_LDS = KB_RING + KB_AUX;            // 52,000 B: three work
 static_assert(3 * KB_LDS <= 160 * 1024, "k_inflate_bytes: three workgroups per CU");
 static_assert(KB_SPAN <= KB_RING - kWindow && KB_RING % 16 == 0 && kChunk % 4 == 0, "ring geometry");
 
+// BATCH (sfh_decompress_batch*): segment `seg` of the launch batch is rows[seg] -- its stream, index entries, size and
+// history -- instead of what the single call derives from seg; the rows are read here, in the prologue, only.
+template <bool BATCH>
 __global__ __launch_bounds__(KT_LANES) void k_inflate_tokens(const uint8_t* __restrict__ src, uint64_t src_n,
                                                             const uint64_t* __restrict__ index, uint32_t nseg,
                                                             uint64_t dst_n, uint32_t* __restrict__ tokens,
                                                             SegInfo* __restrict__ info, uint32_t sps,
-                                                            uint32_t only_retry) {
+                                                            uint32_t only_retry, const InflateSeg* __restrict__ rows) {
   extern __shared__ __align__(16) uint8_t s_tables[];
   const uint32_t seg = blockIdx.x * KT_LANES + threadIdx.x;
   if (seg >= nseg) return;
   if (only_retry && info[seg].status != kRetrySerial) return;  // behind k_inflate_tokens_spec: what that one left
-  const uint64_t lo = index[seg], hi = index[seg + 1];
-  const uint64_t obase = (uint64_t)seg * kChunk;
-  const uint32_t out_n = dst_n > obase ? (uint32_t)(dst_n - obase < kChunk ? dst_n - obase : kChunk) : 0u;
+  uint64_t lo, hi;
+  uint32_t out_n, hist;
+  bool wrapped = false;
+  if constexpr (BATCH) {
+    const InflateSeg R = rows[seg];
+    src = R.src;
+    src_n = R.src_n;
+    lo = R.ix[0];
+    hi = R.ix[1];
+    out_n = R.out_n;
+    hist = R.hist & ~kSegWrapped;
+    wrapped = (R.hist & kSegWrapped) != 0;
+  } else {
+    lo = index[seg];
+    hi = index[seg + 1];
+    const uint64_t obase = (uint64_t)seg * kChunk;
+    out_n = dst_n > obase ? (uint32_t)(dst_n - obase < kChunk ? dst_n - obase : kChunk) : 0u;
+    hist = (seg % sps) * kChunk;
+  }
   const inflate::SegmentResult r = inflate::decode_segment(src, src_n, lo, hi, out_n, tokens + (uint64_t)seg * kChunk,
-                                                           s_tables + threadIdx.x * inflate::LaneLayout::kBytes,
-                                                           (seg % sps) * kChunk);
+                                                           s_tables + threadIdx.x * inflate::LaneLayout::kBytes, hist);
   SegInfo si;
   si.status = r.status;
+  // a wrapped item whose body ENDS short of its output: container.hpp's raw decode succeeds there and its checksum of the
+  // whole output fails -- Error (a raw item keeps the single call's SrcTooSmall)
+  if (BATCH && wrapped && r.status == inflate::kSrcTooSmall && r.ended) si.status = inflate::kError;
   si.ntok = r.ntok;
   si.raw = (r.raw ? kSegRaw : 0u) | kSegSerial;
   si.out_n = out_n;
@@ -453,9 +474,13 @@ __device__ void decode_regions_lockstep(const uint8_t* src, uint64_t src_n, uint
 constexpr uint32_t kSpecLookBack = 512;
 constexpr uint32_t kSpecCheck = 1024;  // the checkpoint of a counting pass: this many bits behind the lane's start
 
+// BATCH: the wave's two segments may belong to different items -- each half reads its own row (stream, index entries,
+// sub-index, size, history) in the prologue
+template <bool BATCH>
 __device__ __forceinline__ void tokens_wave_sub(const uint8_t* __restrict__ src, uint64_t src_n, const uint64_t* __restrict__ index,
                                             const uint32_t* __restrict__ subidx, uint32_t nseg, uint64_t dst_n,
-                                            uint32_t* __restrict__ tokens, SegInfo* __restrict__ info, uint32_t sps) {
+                                            uint32_t* __restrict__ tokens, SegInfo* __restrict__ info, uint32_t sps,
+                                            const InflateSeg* __restrict__ rows) {
   using L = inflate::SharedLayout;
   __shared__ __align__(16) uint8_t s_tab[2][L::kBytes];
   __shared__ __align__(16) RegionLds s_reg;
@@ -464,9 +489,29 @@ __device__ __forceinline__ void tokens_wave_sub(const uint8_t* __restrict__ src,
   const uint32_t lane = threadIdx.x, half = lane >> 5, hl = lane & 31;
   const uint32_t seg = 2 * blockIdx.x + half;
   const bool live = seg < nseg;
-  const uint64_t lo = live ? index[seg] : 0, hi = live ? index[seg + 1] : 0;
-  const uint64_t obase = (uint64_t)seg * kChunk;
-  const uint32_t out_n = (live && dst_n > obase) ? (uint32_t)(dst_n - obase < kChunk ? dst_n - obase : kChunk) : 0u;
+  uint64_t lo, hi;
+  uint32_t out_n, hist = 0;            // (BATCH only: the single call derives both where it needs them)
+  const uint32_t* seg_sub = nullptr;
+  if constexpr (BATCH) {
+    lo = 0;
+    hi = 0;
+    out_n = 0;
+    if (live) {
+      const InflateSeg R = rows[seg];
+      src = R.src;
+      src_n = R.src_n;
+      lo = R.ix[0];
+      hi = R.ix[1];
+      out_n = R.out_n;
+      hist = R.hist & ~kSegWrapped;
+      seg_sub = R.sub;
+    }
+  } else {
+    lo = live ? index[seg] : 0;
+    hi = live ? index[seg + 1] : 0;
+    const uint64_t obase = (uint64_t)seg * kChunk;
+    out_n = (live && dst_n > obase) ? (uint32_t)(dst_n - obase < kChunk ? dst_n - obase : kChunk) : 0u;
+  }
   {
     // RFC 1951 3.2.5 as a table: base | extra bits << 16
     uint32_t base = 0, extra = 0;
@@ -507,7 +552,7 @@ __device__ __forceinline__ void tokens_wave_sub(const uint8_t* __restrict__ src,
   uint32_t bit0 = 0, bit1 = 0, tok1 = 0, ob = 0, oe = 0;
   bool go = false;
   if (decode) {
-    const uint32_t* sub = subidx + (uint64_t)seg * 2 * kSubRegions;
+    const uint32_t* sub = BATCH ? seg_sub : subidx + (uint64_t)seg * 2 * kSubRegions;
     bit0 = sub[2 * hl];
     tok0 = sub[2 * hl + 1];
     bit1 = hl + 1 < kSubRegions ? sub[2 * hl + 2] : 0u;
@@ -521,7 +566,7 @@ __device__ __forceinline__ void tokens_wave_sub(const uint8_t* __restrict__ src,
   {
     RegionOut o;
     decode_regions_lockstep<L, false>(src, src_n, lo, hi, bit0, bit1, hl + 1 == kSubRegions, ob, oe,
-                                      tokens + (uint64_t)seg * kChunk + tok0, s_tab[half], half, (seg % sps) * kChunk, go, lane,
+                                      tokens + (uint64_t)seg * kChunk + tok0, s_tab[half], half, BATCH ? hist : (seg % sps) * kChunk, go, lane,
                                       s_reg, o);
     n = o.ntok;
     if (go) {
@@ -554,7 +599,13 @@ __global__ __launch_bounds__(64, 2) void k_inflate_tokens_sub(const uint8_t* __r
                                                              const uint32_t* __restrict__ subidx, uint32_t nseg,
                                                              uint64_t dst_n, uint32_t* __restrict__ tokens,
                                                              SegInfo* __restrict__ info, uint32_t sps) {
-  tokens_wave_sub(src, src_n, index, subidx, nseg, dst_n, tokens, info, sps);
+  tokens_wave_sub<false>(src, src_n, index, subidx, nseg, dst_n, tokens, info, sps, nullptr);
+}
+// (its own kernel, not a template parameter of the one above: the single call's kernel keeps its signature and figures)
+__attribute__((amdgpu_waves_per_eu(5, 5)))
+__global__ __launch_bounds__(64, 2) void k_inflate_tokens_sub_batch(const InflateSeg* __restrict__ rows, uint32_t nseg,
+                                                                   uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
+  tokens_wave_sub<true>(nullptr, 0, nullptr, nullptr, nseg, 0, tokens, info, 1, rows);
 }
 
 // ---- k_inflate_tokens_spec: the wave, block after block ----
@@ -636,9 +687,11 @@ struct SegState {
 };
 enum : uint32_t { kSegRun = 0, kSegDone = 1, kSegRetry = 2 };
 
+// BATCH: as tokens_wave_sub -- each half's row gives its stream, index entries, size and history
+template <bool BATCH>
 __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src, uint64_t src_n, const uint64_t* __restrict__ index,
                                                  uint32_t nseg, uint64_t dst_n, uint32_t* __restrict__ tokens,
-                                                 SegInfo* __restrict__ info, uint32_t sps) {
+                                                 SegInfo* __restrict__ info, uint32_t sps, const InflateSeg* __restrict__ rows) {
   using L = inflate::SharedLayout;
   __shared__ __align__(16) uint8_t s_tab[2][L::kBytes];
   __shared__ __align__(16) RegionLds s_reg;
@@ -646,6 +699,14 @@ __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src
   __shared__ SegState s_st[2];
   const uint32_t lane = threadIdx.x, half = lane >> 5, hl = lane & 31;
   const uint32_t seg = 2 * blockIdx.x + half;
+  uint32_t hist = 0;  // (BATCH only: the single call derives it where it needs it)
+  if constexpr (BATCH) {
+    if (seg < nseg) {  // (every lane of the half: the stream pointer is the half's own)
+      src = rows[seg].src;
+      src_n = rows[seg].src_n;
+      hist = rows[seg].hist & ~kSegWrapped;
+    }
+  }
   {
     // RFC 1951 3.2.5 as a table: base | extra bits << 16
     uint32_t base = 0, extra = 0;
@@ -655,9 +716,18 @@ __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src
   }
   if (hl == 0) {
     const bool live = seg < nseg;
-    const uint64_t lo = live ? index[seg] : 0, hi = live ? index[seg + 1] : 0;
-    const uint64_t obase = (uint64_t)seg * kChunk;
-    const uint32_t out_n = (live && dst_n > obase) ? (uint32_t)(dst_n - obase < kChunk ? dst_n - obase : kChunk) : 0u;
+    uint64_t lo, hi;
+    uint32_t out_n;
+    if constexpr (BATCH) {
+      lo = live ? rows[seg].ix[0] : 0;
+      hi = live ? rows[seg].ix[1] : 0;
+      out_n = live ? rows[seg].out_n : 0u;
+    } else {
+      lo = live ? index[seg] : 0;
+      hi = live ? index[seg + 1] : 0;
+      const uint64_t obase = (uint64_t)seg * kChunk;
+      out_n = (live && dst_n > obase) ? (uint32_t)(dst_n - obase < kChunk ? dst_n - obase : kChunk) : 0u;
+    }
     const uint32_t seg_bits = (hi > lo && hi - lo < (1ull << 16)) ? 8u * (uint32_t)(hi - lo) : 0u;
     SegState z;
     z.lo = lo;
@@ -861,7 +931,7 @@ __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src
     {
       const uint32_t ob = S.out_base + bsum - nbytes;
       decode_regions_lockstep<L, false>(src, src_n, S.lo, S.hi, entry, exitb, hl == 31, ob, ob + nbytes,
-                                        tokens + (uint64_t)seg * kChunk + S.tok_base + (tsum - cnt), m, half, (seg % sps) * kChunk, go,
+                                        tokens + (uint64_t)seg * kChunk + S.tok_base + (tsum - cnt), m, half, BATCH ? hist : (seg % sps) * kChunk, go,
                                         lane, s_reg, o);
     }
     fresh();
@@ -902,7 +972,12 @@ __global__ __launch_bounds__(64, 2) void k_inflate_tokens_spec(const uint8_t* __
                                                               const uint64_t* __restrict__ index, uint32_t nseg,
                                                               uint64_t dst_n, uint32_t* __restrict__ tokens,
                                                               SegInfo* __restrict__ info, uint32_t sps) {
-  tokens_wave_spec(src, src_n, index, nseg, dst_n, tokens, info, sps);
+  tokens_wave_spec<false>(src, src_n, index, nseg, dst_n, tokens, info, sps, nullptr);
+}
+__attribute__((amdgpu_waves_per_eu(5, 5)))
+__global__ __launch_bounds__(64, 2) void k_inflate_tokens_spec_batch(const InflateSeg* __restrict__ rows, uint32_t nseg,
+                                                                    uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
+  tokens_wave_spec<true>(nullptr, 0, nullptr, nseg, 0, tokens, info, 1, rows);
 }
 
 __device__ __forceinline__ uint32_t load_word_guarded(const uint8_t* base, uint64_t src_n, uint64_t w) {
@@ -927,10 +1002,11 @@ __device__ __forceinline__ uint32_t load_word_guarded(const uint8_t* base, uint6
 // step being produced; byte p of the strip lives at p mod KB_RING.  Every step's bytes go to `dst` as soon as they
 // are final (whole dwords; the odd bytes with the next step), so the ring never has to hold a whole segment.
 // rb: ring position of the segment's first byte; segbase: that byte's position in its strip (bytes of history).
-// Returns false when the segment failed.
+// Returns false when the segment failed.  BATCH: the segment's output starts at rows[seg].dst.
+template <bool BATCH>
 __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t src_n, const uint32_t* __restrict__ tokens,
                                       SegInfo* __restrict__ info, uint8_t* __restrict__ dst, uint32_t seg, uint32_t segbase,
-                                      uint32_t rb, uint8_t* s_dyn) {
+                                      uint32_t rb, uint8_t* s_dyn, const InflateSeg* __restrict__ rows) {
   constexpr uint32_t kRing = KB_RING;
   uint8_t* s_out = s_dyn;                                          // [kRing] output window
   uint16_t* s_ptr = reinterpret_cast<uint16_t*>(s_dyn + kRing);   // [KB_SPAN] step-relative source, or kFinal
@@ -960,7 +1036,9 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
   const SegInfo si = info[seg];
   if (si.status != inflate::kOk) return false;
   const uint32_t out_n = si.out_n;
-  uint8_t* o = dst + (uint64_t)seg * kChunk;  // 16-byte aligned
+  uint8_t* o;  // 16-byte aligned
+  if constexpr (BATCH) o = rows[seg].dst;
+  else o = dst + (uint64_t)seg * kChunk;
 
   if (si.raw & kSegRaw) {
     // stored segment: dword copy from an arbitrarily aligned stream position
@@ -1237,7 +1315,7 @@ __global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes(const uint8_t* __r
   const uint32_t seg0 = blockIdx.x * sps;
   uint32_t rb = 0;  // ring position of the segment's first byte: (k * kChunk) mod KB_RING
   for (uint32_t k = 0; k < sps && seg0 + k < nseg; ++k) {
-    if (!inflate_segment_bytes(src, src_n, tokens, info, dst, seg0 + k, k * kChunk, rb, s_dyn)) {
+    if (!inflate_segment_bytes<false>(src, src_n, tokens, info, dst, seg0 + k, k * kChunk, rb, s_dyn, nullptr)) {
       // the later segments of the strip depend on this one: they fail with it (first failure in stream
       // order is what the caller sees, k_inflate_status)
       for (uint32_t j = k + 1 + threadIdx.x; j < sps && seg0 + j < nseg; j += KB_THREADS)
@@ -1247,6 +1325,28 @@ __global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes(const uint8_t* __r
     rb += kChunk;
     rb = rb >= KB_RING ? rb - KB_RING : rb;
     __syncthreads();  // the segment's window writes precede the next segment's reads
+  }
+}
+
+// sfh_decompress_batch*: one workgroup per row of the strip table (its segments are one item's, in order)
+__global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes_batch(const InflateSeg* __restrict__ rows,
+                                                                    const InflateStrip* __restrict__ strips,
+                                                                    const uint32_t* __restrict__ tokens,
+                                                                    SegInfo* __restrict__ info) {
+  extern __shared__ __align__(16) uint8_t s_dyn[];
+  const InflateStrip S = strips[blockIdx.x];
+  const uint8_t* src = rows[S.seg0].src;
+  const uint64_t src_n = rows[S.seg0].src_n;
+  uint32_t rb = 0;
+  for (uint32_t k = 0; k < S.nseg; ++k) {
+    if (!inflate_segment_bytes<true>(src, src_n, tokens, info, nullptr, S.seg0 + k, k * kChunk, rb, s_dyn, rows)) {
+      for (uint32_t j = k + 1 + threadIdx.x; j < S.nseg; j += KB_THREADS)
+        if (info[S.seg0 + j].status == inflate::kOk) info[S.seg0 + j].status = inflate::kError;
+      return;
+    }
+    rb += kChunk;
+    rb = rb >= KB_RING ? rb - KB_RING : rb;
+    __syncthreads();
   }
 }
 
@@ -1274,8 +1374,14 @@ __global__ __launch_bounds__(KS_THREADS) void k_inflate_status(const SegInfo* __
 }  // namespace
 
 hipError_t init_inflate_kernels() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_tokens),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_tokens<false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)KT_LDS);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_tokens<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)KT_LDS);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes_batch), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)KB_LDS);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)KB_LDS);
@@ -1291,8 +1397,33 @@ hipError_t launch_inflate_tokens(const uint8_t* src, uint64_t src_n, const uint6
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(k_inflate_tokens, dim3((nseg + KT_LANES - 1) / KT_LANES), dim3(KT_LANES), KT_LDS, s, src, src_n, index,
-                     nseg, dst_n, tokens, info, sps, speculate ? 1u : 0u);
+  hipLaunchKernelGGL(k_inflate_tokens<false>, dim3((nseg + KT_LANES - 1) / KT_LANES), dim3(KT_LANES), KT_LDS, s, src, src_n, index,
+                     nseg, dst_n, tokens, info, sps, speculate ? 1u : 0u, (const InflateSeg*)nullptr);
+  return hipGetLastError();
+}
+
+// The batch's segments: the sub-indexed wave kernel, or the speculative one with the lane-serial kernel behind it for what
+// that one leaves (speculate = false: the lane-serial kernel alone)
+hipError_t launch_inflate_tokens_batch(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool sub,
+                                       bool speculate, hipStream_t s) {
+  if (sub) {
+    hipLaunchKernelGGL(k_inflate_tokens_sub_batch, dim3((nseg + 1) / 2), dim3(64), 0, s, rows, nseg, tokens, info);
+    return hipGetLastError();
+  }
+  if (speculate) {
+    hipLaunchKernelGGL(k_inflate_tokens_spec_batch, dim3((nseg + 1) / 2), dim3(64), 0, s, rows, nseg, tokens, info);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_inflate_tokens<true>, dim3((nseg + KT_LANES - 1) / KT_LANES), dim3(KT_LANES), KT_LDS, s,
+                     (const uint8_t*)nullptr, (uint64_t)0, (const uint64_t*)nullptr, nseg, (uint64_t)0, tokens, info, 1u,
+                     speculate ? 1u : 0u, rows);
+  return hipGetLastError();
+}
+
+hipError_t launch_inflate_bytes_batch(const InflateSeg* rows, const InflateStrip* strips, uint32_t nstrips,
+                                      const uint32_t* tokens, SegInfo* info, hipStream_t s) {
+  hipLaunchKernelGGL(k_inflate_bytes_batch, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, rows, strips, tokens, info);
   return hipGetLastError();
 }
 

@@ -64,6 +64,7 @@ struct SegmentResult {
   uint32_t ntok;     // tokens written (raw == 0)
   uint32_t raw;      // 1: the segment is one stored block holding all `out_n` bytes at byte `raw_off`
   uint64_t raw_off;  // of the stream buffer
+  uint32_t ended;    // with status kSrcTooSmall: 1 when the stream ENDED (BFINAL) short of out_n bytes, 0 when it ran out
 };
 
 SF_HD uint16_t ld16(const uint8_t* m, uint32_t off) { return *reinterpret_cast<const uint16_t*>(m + off); }
@@ -427,7 +428,7 @@ SF_HD uint32_t decode_symbols(BitReader& br, const uint8_t* m, Sink& sink, uint3
 // out_n (<= 32768) bytes.  Tokens go to tokens[0..ntok).  `m`: LaneLayout::kBytes of scratch.  hist: see decode_symbols.
 SF_HD SegmentResult decode_segment(const uint8_t* src, uint64_t src_n, uint64_t seg_begin, uint64_t seg_end,
                                    uint32_t out_n, uint32_t* tokens, uint8_t* m, uint32_t hist = 0) {
-  SegmentResult r{kOk, 0, 0, 0};
+  SegmentResult r{kOk, 0, 0, 0, 0};
   if (seg_begin > seg_end || seg_end > src_n) {
     r.status = kSrcTooSmall;
     return r;
@@ -482,7 +483,10 @@ SF_HD SegmentResult decode_segment(const uint8_t* src, uint64_t src_n, uint64_t 
     bool eob;
     status = decode_symbols<LaneLayout>(br, m, sink, out_pos, out_n, ~0u, eob, hist);
   }
-  if (status == kOk && out_pos != out_n) status = kSrcTooSmall;  // the index promised more bytes
+  if (status == kOk && out_pos != out_n) {  // the index promised more bytes
+    status = kSrcTooSmall;
+    r.ended = last ? 1u : 0u;
+  }
   if (status == kOk && r.raw && sink.n != 0) status = kDstTooSmall;
   sink.flush();
   r.status = status;

@@ -2615,6 +2615,24 @@ hipError_t launch_scan(uint32_t nchunks, const Workspace& ws, uint64_t base, boo
                        (BatchItem*)nullptr, 0u);
   return hipGetLastError();
 }
+// sfh_compress_batch*: the call's index, item after item (sfh_copy_batch_index).  Every launch batch's k_scan left its chunks'
+// offsets in the batch's global scan at their call-level places; a chunk's offset in its item's stream is that + its piece's
+// shift, and an item's last entry is the end of its stream before the trailer (total[item], before k_wrap_batch adds it).
+__global__ __launch_bounds__(256) void k_batch_index(const BatchChunk* __restrict__ chunks, const BatchIndexRow* __restrict__ rows,
+                                                     const BatchItem* __restrict__ pieces, const uint64_t* __restrict__ offsets,
+                                                     const uint64_t* __restrict__ total, uint32_t nchunks, uint64_t* __restrict__ index) {
+  const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= nchunks) return;
+  const BatchIndexRow R = rows[c];
+  const uint64_t e = (uint64_t)c + R.item;  // (item i's entries start after the entries of items 0 .. i-1: their chunks + i)
+  index[e] = offsets[c] + pieces[R.piece].shift;
+  if (chunks[c].item & 1u) index[e + 1] = total[R.item];
+}
+hipError_t launch_batch_index(const BatchChunk* chunks, const BatchIndexRow* rows, const BatchItem* pieces, const uint64_t* offsets,
+                              const uint64_t* total, uint32_t nchunks, uint64_t* index, hipStream_t s) {
+  hipLaunchKernelGGL(k_batch_index, dim3((nchunks + 255) / 256), dim3(256), 0, s, chunks, rows, pieces, offsets, total, nchunks, index);
+  return hipGetLastError();
+}
 hipError_t launch_emit(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws,
                        uint8_t* dst, hipStream_t s, const BatchTables* bt) {
   if (bt)
