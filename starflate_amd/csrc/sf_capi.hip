@@ -352,7 +352,7 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
     if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
     SF_HIP(sf::launch_scan(nb, w, sf::wrapper_header_bytes(o.container), !first, d_out_n, s), "launch k_scan");
     if (ev) SF_HIP(hipEventRecord(ev[3], s), "event");
-    SF_HIP(sf::launch_emit(bsrc, bn, nb, w, (uint8_t*)d_dst, s), "launch k_emit");
+    SF_HIP(sf::launch_emit(bsrc, bn, nb, w, bo, (uint8_t*)d_dst, s), "launch k_emit");
     if (ev) SF_HIP(hipEventRecord(ev[4], s), "event");
     if (pipe) {
       if (bi >= 1 && (rc = drain(bi - 1)) != SFH_OK) return rc;  // (its slot is free again before batch bi + kPipe - 1 needs it)
@@ -556,7 +556,7 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
     if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
     SF_HIP(sf::launch_scan(b.nchunks, w, hdr, false, d_out_n, s, &bt), "launch k_scan");
     if (ev) SF_HIP(hipEventRecord(ev[3], s), "event");
-    SF_HIP(sf::launch_emit(nullptr, 0, b.nchunks, w, nullptr, s, &bt), "launch k_emit");
+    SF_HIP(sf::launch_emit(nullptr, 0, b.nchunks, w, ko, nullptr, s, &bt), "launch k_emit");
     if (ev) SF_HIP(hipEventRecord(ev[4], s), "event");
   }
   // (behind the launch batches and ahead of k_wrap_batch: d_out_n is still every stream's end before its trailer)

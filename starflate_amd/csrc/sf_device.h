@@ -253,7 +253,7 @@ hipError_t launch_plan(uint64_t n, uint32_t nchunks, const Workspace& ws, const 
 // (or, carried, at d_total[item.out]) and d_total[item.out] = the end of the item's stream so far
 hipError_t launch_scan(uint32_t nchunks, const Workspace& ws, uint64_t base, bool carry, uint64_t* d_total, hipStream_t s,
                        const BatchTables* bt = nullptr);
-hipError_t launch_emit(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws,
+hipError_t launch_emit(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws, const Options& opt,
                        uint8_t* dst, hipStream_t s, const BatchTables* bt = nullptr);
 // after every launch batch of a batched call: the items' index entries (item-relative offsets, item after item) into `index`
 hipError_t launch_batch_index(const BatchChunk* chunks, const BatchIndexRow* rows, const BatchItem* pieces, const uint64_t* offsets,

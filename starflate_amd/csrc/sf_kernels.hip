@@ -1793,6 +1793,9 @@ __device__ uint32_t rle_parallel(PlanSmem& S, const uint8_t* lens, uint32_t n, u
 }
 
 __constant__ uint8_t c_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+// a stored block's bytes beyond its data: BFINAL/BTYPE byte, LEN, NLEN.  Under strategy 0 plan_chunk codes a chunk only when
+// that is SMALLER than n_raw + kStoredExtra bytes, which bounds k_emit's small stage (K4_STAGE_AUTO)
+constexpr uint32_t kStoredExtra = 5;
 
 // K2 in three launches: MODE 1 (k_plan_sort) loads, folds, decides "stored without a code", SORTS both alphabets and leaves
 // keys and weights in PlanTree; k_plan_merge builds the trees, one chunk per LANE; MODE 2 (k_plan_finish) picks the parents
@@ -1846,7 +1849,7 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
       C0.header[0] = fin ? 1u : 0u;
       ChunkPlan P;
       P.btype = 0;
-      P.out_bytes = n_raw + 5;
+      P.out_bytes = n_raw + kStoredExtra;
       P.header_bits = 3;
       P.body_bits = 0;
       plan[chunk] = P;
@@ -1902,7 +1905,7 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
     const uint32_t fixbits = 3 + wave_sum(fixb) + extra_all + 5 * nmat;
     const uint32_t est_b = fin ? (est_bits + 7) / 8 : (est_bits + 3 + 7) / 8 + 4;
     const uint32_t fix_b = fin ? (fixbits + 7) / 8 : (fixbits + 3 + 7) / 8 + 4;
-    const uint32_t sto_b = n_raw + 5;
+    const uint32_t sto_b = n_raw + kStoredExtra;
     if (fix_b >= sto_b && est_b + kStoreMargin >= sto_b) {
       ChunkCodes& C0 = codes[chunk];
       for (uint32_t s0 = lane; s0 < 320; s0 += 64) C0.lens[s0] = 0;  // (no code was built)
@@ -2042,7 +2045,7 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
   const uint32_t fix_bits = 3 + fix_body;
   const uint32_t dyn_bytes = fin ? (dyn_bits + 7) / 8 : (dyn_bits + 3 + 7) / 8 + 4;
   const uint32_t fix_bytes = fin ? (fix_bits + 7) / 8 : (fix_bits + 3 + 7) / 8 + 4;
-  const uint32_t sto_bytes = n_raw + 5;
+  const uint32_t sto_bytes = n_raw + kStoredExtra;
   uint32_t bt;
   if (strategy == 1) bt = 0;
   else if (strategy == 2) bt = 1;
@@ -2205,11 +2208,40 @@ __global__ __launch_bounds__(K3_THREADS) void k_scan(uint32_t nchunks, const Chu
 constexpr uint32_t K4_THREADS = 512;
 constexpr uint32_t K4_WAVES = K4_THREADS / 64;
 constexpr uint32_t K4_IPT = 8;  // items per thread per batch (one 16-byte load)
-// the image of one chunk's output: sfh_compress_bound's per-chunk share (fixed-Huffman worst case: nine bits per
-// literal, + the largest dynamic header) + alignment and the bit writers' slack; four workgroups fit a CU's LDS
-constexpr uint32_t K4_STAGE_WORDS = 9392;
-static_assert(4 * K4_STAGE_WORDS >= kChunk + kChunk / 8 + 640 + 16 + 8, "k_emit: stage holds the largest chunk");
-static_assert(4 * (4 * K4_STAGE_WORDS + 4 * (288 + 32 + 256 + 2 * 8 + kSubRegions) + 512) <= 160 * 1024, "k_emit: four workgroups per CU");
+// the image of one chunk's output, sized by the strategy (launch_emit picks it):
+// - forced fixed or dynamic (strategy 2, 3): sfh_compress_bound's per-chunk share (fixed-Huffman worst case: nine bits per
+//   literal, + the largest dynamic header) + alignment and the bit writers' slack;
+// - otherwise a coded chunk is smaller than its stored block (plan_chunk's choice under strategy 0): sh (<= 3) leading bytes
+//   + at most n_raw + kStoredExtra - 1 bytes + the same slack
+constexpr uint32_t K4_STAGE_FORCED = 9392;
+constexpr uint32_t K4_STAGE_AUTO = 8200;
+static_assert(4 * K4_STAGE_FORCED >= 3 + kChunk + kChunk / 8 + 640 + 16 + 8, "k_emit: the stage holds the largest chunk");
+static_assert(4 * K4_STAGE_AUTO >= 3 + kChunk + kStoredExtra - 1 + 16 + 8, "k_emit: the small stage holds the largest chunk "
+              "plan_chunk codes under strategy 0");
+static_assert(K4_STAGE_FORCED % 4 == 0 && K4_STAGE_AUTO % 4 == 0, "the stage is zeroed in 16-byte steps");
+// every __shared__ array of k_emit
+template <uint32_t STAGE_WORDS>
+struct EmitLds {
+  alignas(16) uint32_t stage[STAGE_WORDS];
+  uint32_t lcode[288];
+  uint32_t dcode[32];
+  // ONE table for every kind of item (round 6; before: three tables and four reads per item, every item priced as all
+  // three kinds): entry = value (bits 0..19: the code, a length's extra bits appended) | bits of the value << 20 | all
+  // bits of the item << 27 (a distance: + its extra bits, 0..13, taken from the item's own low bits).  [kTabLit + byte], [kTabLen + len-3], and for a
+  // distance - 1 = d: [min(d, 254 + (d >> 7))] -- d itself below 256, one entry per 128 from there on (the symbols from
+  // 16 on cover whole multiples of 128)
+  uint32_t tab[1024];
+  uint32_t wtot[2][K4_WAVES];
+  uint32_t rtok[kSubRegions];
+};
+// 8 waves per SIMD = four 512-thread workgroups per CU (160 KiB of LDS) under strategy 0; the forced stage fits three (6 waves)
+template <uint32_t STAGE_WORDS>
+constexpr uint32_t k4_waves_per_simd() { return STAGE_WORDS == K4_STAGE_AUTO ? 8 : 6; }
+static_assert(k4_waves_per_simd<K4_STAGE_AUTO>() / 2 * sizeof(EmitLds<K4_STAGE_AUTO>) <= 160 * 1024, "k_emit: four workgroups per CU");
+static_assert(k4_waves_per_simd<K4_STAGE_FORCED>() / 2 * sizeof(EmitLds<K4_STAGE_FORCED>) <= 160 * 1024, "k_emit: three workgroups per CU");
+
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+typedef int16_t s16x2 __attribute__((ext_vector_type(2)));
 
 // code bits of one token: literal byte, or match (l3 = len-3, d1 = dist-1)
 __device__ __forceinline__ void literal_bits(uint32_t byte, const uint32_t* lcode, uint64_t& value, uint32_t& nb) {
@@ -2241,8 +2273,10 @@ __device__ __forceinline__ void match_bits(uint32_t l3, uint32_t d1, const uint3
 }
 
 // BATCH (sfh_compress_batch*): the chunk's bytes, its stream and its place there come from the batch's tables
-template <bool BATCH>
-__global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restrict__ src, uint64_t n_total,
+// STAGE_WORDS: K4_STAGE_AUTO or K4_STAGE_FORCED.  (__launch_bounds__'s second argument is the least number of WAVES per
+// SIMD (amdgpu-waves-per-eu), not workgroups per CU: 8 holds the VGPRs at 64.)
+template <bool BATCH, uint32_t STAGE_WORDS>
+__global__ __launch_bounds__(K4_THREADS, k4_waves_per_simd<STAGE_WORDS>()) void k_emit(const uint8_t* __restrict__ src, uint64_t n_total,
                                                      uint32_t /*nchunks*/, uint16_t* items,
                                                      const uint32_t* __restrict__ nitems_in,
                                                      const uint32_t* __restrict__ ntok_in,
@@ -2255,17 +2289,13 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
                                                      const BatchChunk* __restrict__ bchunks,
                                                      const BatchItem* __restrict__ bitems) {
   // @phase k4.setup trips=0 note=per chunk: tables, header
-  __shared__ __attribute__((aligned(16))) uint32_t s_stage[K4_STAGE_WORDS];
-  __shared__ uint32_t s_lcode[288];
-  __shared__ uint32_t s_dcode[32];
-  // ONE table for every kind of item (round 6; before: three tables and four reads per item, every item priced as all
-  // three kinds): entry = value (bits 0..19: the code, a length's extra bits appended) | bits of the value << 20 | extra
-  // bits to take from the item's own low bits << 25 (a distance: 0..13).  [kTabLit + byte], [kTabLen + len-3], and for a
-  // distance - 1 = d: [min(d, 254 + (d >> 7))] -- d itself below 256, one entry per 128 from there on (the symbols from
-  // 16 on cover whole multiples of 128)
-  __shared__ uint32_t s_tab[1024];
-  __shared__ uint32_t s_wtot[2][K4_WAVES];
-  __shared__ uint32_t s_rtok[kSubRegions];
+  __shared__ EmitLds<STAGE_WORDS> L;
+  uint32_t(&s_stage)[STAGE_WORDS] = L.stage;
+  uint32_t(&s_lcode)[288] = L.lcode;
+  uint32_t(&s_dcode)[32] = L.dcode;
+  uint32_t(&s_tab)[1024] = L.tab;
+  uint32_t(&s_wtot)[2][K4_WAVES] = L.wtot;
+  uint32_t(&s_rtok)[kSubRegions] = L.rtok;
   static_assert(K4_THREADS == 512, "one table entry per thread and kind");
   constexpr uint32_t kTabLit = 512, kTabLen = 768, kTabDistN = 510;
 
@@ -2373,7 +2403,7 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
   const uint32_t nwords = (sh + P.out_bytes + 3) / 4;
   {
     uint4* z = reinterpret_cast<uint4*>(s_stage);
-    for (uint32_t k = t; k < (nwords + 2 + 3) / 4 && k < K4_STAGE_WORDS / 4; k += K4_THREADS) z[k] = make_uint4(0, 0, 0, 0);
+    for (uint32_t k = t; k < (nwords + 2 + 3) / 4 && k < STAGE_WORDS / 4; k += K4_THREADS) z[k] = make_uint4(0, 0, 0, 0);
   }
   if (t < 288) s_lcode[t] = pre_code;  // code | bits << 16
   else if (t < 320) s_dcode[t - 288] = pre_code;
@@ -2384,13 +2414,13 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
   __syncthreads();
   if (t < 256) {
     const uint32_t le = lenlut_entry(t, s_lcode);  // value | bits << 24
-    s_tab[kTabLen + t] = (le & 0xFFFFFu) | ((le >> 24) << 20);
-    s_tab[kTabLit + t] = (pre_code & 0xFFFFu) | ((pre_code >> 16) << 20);
+    s_tab[kTabLen + t] = (le & 0xFFFFFu) | (le >> 24) * (1u << 20 | 1u << 27);
+    s_tab[kTabLit + t] = (pre_code & 0xFFFFu) | (pre_code >> 16) * (1u << 20 | 1u << 27);
   }
   if (t < kTabDistN) {
     const uint32_t sym = dist_symbol_of(t < 256 ? t : (t - 254) << 7);
     const uint32_t dc = s_dcode[sym];  // code | length << 16
-    s_tab[t] = (dc & 0xFFFFu) | ((dc >> 16) << 20) | (dist_extra_of_sym(sym) << 25);
+    s_tab[t] = (dc & 0xFFFFu) | ((dc >> 16) << 20) | (((dc >> 16) + dist_extra_of_sym(sym)) << 27);
   } else {
     s_tab[t] = 0;  // (510, 511: where the distance index of a non-distance item may land; never used)
   }
@@ -2429,7 +2459,7 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
     const uint4 q = q_next;
     const bool full = b0 + K4_THREADS * K4_IPT <= nit;  // (uniform) every item of the batch exists
     if (b0 + K4_THREADS * K4_IPT < nit) q_next = *reinterpret_cast<const uint4*>(it + i0 + K4_THREADS * K4_IPT);
-    const uint32_t e[K4_IPT] = {q.x & 0xFFFFu, q.x >> 16, q.y & 0xFFFFu, q.y >> 16, q.z & 0xFFFFu, q.z >> 16, q.w & 0xFFFFu, q.w >> 16};
+    const uint32_t qd[K4_IPT / 2] = {q.x, q.y, q.z, q.w};  // item 2j in the low half of qd[j], item 2j+1 in the high half
     // Every item is ONE unit of at most 28 bits: a literal its code; a match head its length code + extra bits; a
     // distance its code + extra bits.  (A match is not priced as one 48-bit unit: that needs 64-bit shifts and a
     // two-part flush, and the head's thread would have to look at the next thread's item.)  An item says what it is
@@ -2439,42 +2469,63 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
     // @phase k4.lookup trips=1
     uint32_t ent[K4_IPT];
 #pragma unroll
-    for (uint32_t k = 0; k < K4_IPT; ++k) {
-      const uint32_t cur = e[k];
-      // a token's first item: byte or len-3 with kItemHead right above it -- its place among the literal and length entries;
-      // a distance - 1 (the item itself: bit 15 clear): itself below 256, 254 + (d >> 7) from there on
+    for (uint32_t j = 0; j < K4_IPT / 2; ++j) {
+      // both items of a dword at once, in packed 16-bit arithmetic.  A token's first item: byte or len-3 with kItemHead
+      // right above it -- its place among the literal and length entries; a distance - 1 (the item itself: bit 15 clear):
+      // itself below 256, 254 + (d >> 7) from there on
       static_assert(kItemHead == 0x100 && kTabLen == kTabLit + 0x100 && kTabLit == 0x200, "a token's low nine bits are its table index");
-      uint32_t itok = (cur & 0x1FFu) | kTabLit, idist = min(cur, 254u + (cur >> 7));
-      asm volatile("" : "+v"(itok), "+v"(idist));  // (both are there: the choice is ONE select -- left alone, the compiler branches around each)
-      ent[k] = s_tab[cur >= kItemTok ? itok : idist];
+      static_assert(kItemTok == 0x8000, "bit 15 tells a token's first item from a distance");
+      const u16x2 w = __builtin_bit_cast(u16x2, qd[j]);
+      const uint32_t itok = (qd[j] & 0x01FF01FFu) | (kTabLit * 0x10001u);
+      const u16x2 idist = __builtin_elementwise_min(w, (u16x2)(w >> (uint16_t)7) + (uint16_t)254);
+      uint32_t tok = __builtin_bit_cast(uint32_t, __builtin_bit_cast(s16x2, w) >> (int16_t)15);  // 0xFFFF: a token's first item
+      asm volatile("" : "+v"(tok));  // (opaque: ONE bit select for both halves -- left alone, the compiler compares and selects each)
+      const uint32_t idx = (tok & itok) | (~tok & __builtin_bit_cast(uint32_t, idist));
+      const uint32_t by = __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, idx) << (uint16_t)2));  // byte offsets
+      ent[2 * j] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(s_tab) + (by & 0xFFFFu));
+      ent[2 * j + 1] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(s_tab) + (by >> 16));
     }
     asm volatile("" : "+v"(ent[0]), "+v"(ent[1]), "+v"(ent[2]), "+v"(ent[3]), "+v"(ent[4]), "+v"(ent[5]), "+v"(ent[6]), "+v"(ent[7]));
-    // items that start a token AND carry the region flag (bits 15 and 14), two to a dword: rare (one in ~500)
+    // items that start a token AND carry the region flag (bits 15 and 14): rare (one in ~500).  Item k's bit in `starts`
+    // is sbit(k): the low halves' items at bits 0, 2, 4, 6, the high halves' at 16, 18, 20, 22
     auto both = [](uint32_t w) { return w & (w << 1) & 0x80008000u; };
-    uint32_t flagged = both(q.x) | both(q.y) | both(q.z) | both(q.w);
+    auto sbit = [](uint32_t k) { return (k & 1) ? 15 + k : k; };
+    uint32_t starts = (both(q.x) >> 15) | (both(q.y) >> 13) | (both(q.z) >> 11) | (both(q.w) >> 9);
+    // @phase k4.last trips=0.24 note=a chunk's last, partial batch: ~17K items per chunk on text, 4096 per batch
     if (!full) {  // (uniform) a chunk's last batch: what lies behind the last item is no item -- an empty entry is no bits
       uint32_t left = nit - i0;  // (wraps to something huge for a thread wholly inside: every k is below it)
       left = i0 < nit ? left : 0u;
 #pragma unroll
-      for (uint32_t k = 0; k < K4_IPT; ++k) ent[k] = k < left ? ent[k] : 0u;
-      flagged = 1;  // ... and the flags are looked at item by item
+      for (uint32_t k = 0; k < K4_IPT; ++k) {
+        ent[k] = k < left ? ent[k] : 0u;
+        starts &= k < left ? ~0u : ~(1u << sbit(k));
+      }
     }
+    // @phase k4.price trips=1
+    // the first region start's item (none: 32, which is no sbit) and the bits in front of it, taken in the price loop; a
+    // lane with two starts would leave them to the walk below
+    const uint32_t s0 = starts ? (uint32_t)__builtin_ctz(starts) : 32u;
+    const bool walk = __ballot((starts & (starts - 1)) != 0) != 0;  // (uniform)
+    uint32_t off0 = 0;
 #pragma unroll
     for (uint32_t k = 0; k < K4_IPT; ++k) {
-      // @phase k4.price trips=1
       const uint32_t en = ent[k];
-      const uint32_t dl = __builtin_amdgcn_ubfe(en, 20, 5), de = en >> 25;  // bits of the code, extra bits from the item (a distance's)
-      val[k] = (__builtin_amdgcn_ubfe(e[k], 0, de) << dl) | (en & 0xFFFFFu);
-      nb[k] = dl + de;
+      // the bits of the value and of the whole item; the extra bits (a distance's) are their difference.  Only the low five
+      // bits of a shift or field width count, so neither field needs a mask
+      const uint32_t dl = en >> 20, n = en >> 27;
+      val[k] = (__builtin_amdgcn_ubfe(qd[k / 2], 16 * (k & 1), (n - dl) & 31u) << (dl & 31u)) | (en & 0xFFFFFu);
+      nb[k] = n;
+      // (an item's value and bit count together: left alone, the compiler computes every count first, for the scan, and
+      // holds eight entries' fields until the values -- more than 64 VGPRs)
+      asm volatile("" : "+v"(val[k]), "+v"(nb[k]));
+      off0 = s0 == sbit(k) ? mine : off0;
       mine += nb[k];
     }
-    uint32_t starts = 0;  // bit k: item k starts a token and carries the region flag
-    if (flagged) {
-      uint32_t i_now = i0;
-      asm volatile("" : "+v"(i_now));  // (opaque: the eight compares belong to this rare path, not in front of the loop)
-#pragma unroll
-      for (uint32_t k = 0; k < K4_IPT; ++k)
-        starts |= ((e[k] & (kItemTok | kItemRegion)) == (kItemTok | kItemRegion) && i_now + k < nit) ? 1u << k : 0u;
+    uint32_t region0;  // the start's region: its sub-index entry
+    {
+      const uint32_t j = (s0 >> 1) & 3u;
+      const uint32_t w = j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w;
+      region0 = (w >> ((s0 & 16u) + kItemRegionShift)) & 31u;
     }
     // @phase k4.scan trips=1
     const uint32_t incl = wave_incl_add(mine);
@@ -2491,15 +2542,26 @@ __global__ __launch_bounds__(K4_THREADS, 4) void k_emit(const uint8_t* __restric
     // and OR whole words, instead of one to three atomics per token
     const uint32_t pos = running + pre + incl - mine;
     // @phase k4.subindex trips=1
-    if (starts) {
-      // k_lz77 flags the first token of every 1024-byte parse region (32 per chunk): its bit offset is the
-      // sub-index entry
+    // k_lz77 flags the first token of every 1024-byte parse region (32 per chunk): its bit offset is the sub-index entry
+    if (walk) {
+      // @phase k4.subindex_walk trips=0 note=not reached by k_lz77's items
+      // the thread's items again (the batch's, not in registers any more), item by item.  k_lz77 never gives a lane two
+      // starts: every kSubBytes-th position starts a token and a token is at most 258 bytes in two items, so two region
+      // starts are at least 8 items apart and a lane's eight items begin at a multiple of 8.  The walk keeps k_emit right
+      // for any item stream, at the cost of one ballot per round.
+      const uint4 r = *reinterpret_cast<const uint4*>(it + i0);
+      const uint32_t rd[K4_IPT / 2] = {r.x, r.y, r.z, r.w};
       uint32_t pk = pos;
 #pragma unroll
       for (uint32_t k = 0; k < K4_IPT; ++k) {
-        if ((starts >> k) & 1) sub[2 * ((e[k] >> kItemRegionShift) & 31u)] = pk - 8 * sh;
+        const uint32_t e = (rd[k / 2] >> (16 * (k & 1))) & 0xFFFFu;
+        if ((e & (kItemTok | kItemRegion)) == (kItemTok | kItemRegion) && i0 + k < nit)
+          sub[2 * ((e >> kItemRegionShift) & 31u)] = pk - 8 * sh;
         pk += nb[k];
       }
+    } else if (starts) {
+      // @phase k4.subindex trips=1
+      sub[2 * region0] = pos + off0 - 8 * sh;
     }
     // @phase k4.pack trips=1
     uint32_t wi = pos >> 5, ab = pos & 31;
@@ -2633,15 +2695,17 @@ hipError_t launch_batch_index(const BatchChunk* chunks, const BatchIndexRow* row
   hipLaunchKernelGGL(k_batch_index, dim3((nchunks + 255) / 256), dim3(256), 0, s, chunks, rows, pieces, offsets, total, nchunks, index);
   return hipGetLastError();
 }
-hipError_t launch_emit(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws,
+hipError_t launch_emit(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws, const Options& opt,
                        uint8_t* dst, hipStream_t s, const BatchTables* bt) {
-  if (bt)
-    hipLaunchKernelGGL(k_emit<true>, dim3(nchunks), dim3(K4_THREADS), 0, s, src, n, nchunks, ws.items, ws.nitems, ws.ntok,
-                       ws.plan, ws.codes, ws.offsets, ws.rtok, ws.subidx, dst, bt->chunks, (const BatchItem*)bt->items);
-  else
-    hipLaunchKernelGGL(k_emit<false>, dim3(nchunks), dim3(K4_THREADS), 0, s, src, n, nchunks, ws.items, ws.nitems, ws.ntok,
-                       ws.plan, ws.codes, ws.offsets, ws.rtok, ws.subidx, dst, (const BatchChunk*)nullptr,
-                       (const BatchItem*)nullptr);
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(nchunks), dim3(K4_THREADS), 0, s, src, n, nchunks, ws.items, ws.nitems, ws.ntok, ws.plan,
+                       ws.codes, ws.offsets, ws.rtok, ws.subidx, dst, bt ? bt->chunks : (const BatchChunk*)nullptr,
+                       bt ? (const BatchItem*)bt->items : (const BatchItem*)nullptr);
+  };
+  // the big stage only where plan_chunk may code a chunk larger than its stored block: forced fixed or dynamic
+  const bool forced = opt.strategy == 2 || opt.strategy == 3;
+  if (bt) forced ? launch(k_emit<true, K4_STAGE_FORCED>) : launch(k_emit<true, K4_STAGE_AUTO>);
+  else forced ? launch(k_emit<false, K4_STAGE_FORCED>) : launch(k_emit<false, K4_STAGE_AUTO>);
   return hipGetLastError();
 }
 
