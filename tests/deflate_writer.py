@@ -1,7 +1,8 @@
 """A plain RFC 1951 writer and reader for tests: dynamic blocks from a token list and code lengths chosen freely by
 the caller, so that tests can reach the edges of the format that the compressor's own inputs never reach (15-bit
 literal/length and distance codes, 7-bit code-length codes, repeats at their maximum, runs across the HLIT/HDIST
-boundary, HLIT = 257 / 286, HDIST = 1 / 30, trimmed HCLEN).
+boundary, HLIT = 257 / 286, HDIST = 1 / 30, trimmed HCLEN), and strips whose matches reach back across segments and
+into stored segments at any stream alignment.
 
 TEST INFRASTRUCTURE ONLY.  Pure Python and numpy.  Tokens are the oracle's format (uint32: bit 31 match, bits 16..23
 length - 3, bits 0..14 distance - 1; else a literal byte).  Every writer returns a report of the code lengths it
@@ -53,6 +54,7 @@ def token_symbols(tokens):
 
 
 def expand(tokens, history=b""):
+    """the bytes tokens stand for after `history` (the bytes a match may reach back into)"""
     out = bytearray(history)
     for t in np.asarray(tokens, np.uint32).tolist():
         if t & MATCH:
@@ -147,22 +149,33 @@ def canonical(lens):
 # ---- bits ----
 
 class BitWriter:
+    """LSB-first bit packer.  Whole bytes leave the accumulator as they fill, so a put costs the same at any stream size."""
+
     def __init__(self):
-        self.acc, self.n = 0, 0
+        self.buf, self.acc, self.nacc = bytearray(), 0, 0
+
+    @property
+    def n(self):  # bits written
+        return 8 * len(self.buf) + self.nacc
 
     def put(self, v, n):
         assert 0 <= v < (1 << n) or n == 0
-        self.acc |= v << self.n
-        self.n += n
+        self.acc |= v << self.nacc
+        self.nacc += n
+        if self.nacc >= 64:
+            k = self.nacc >> 3
+            self.buf += (self.acc & ((1 << 8 * k) - 1)).to_bytes(k, "little")
+            self.acc >>= 8 * k
+            self.nacc -= 8 * k
 
     def put_code(self, code, length):  # Huffman codes go MSB first
         self.put(int(f"{code:0{length}b}"[::-1], 2), length)
 
     def align(self):
-        self.n += -self.n % 8
+        self.nacc += -self.nacc % 8  # (buf holds whole bytes)
 
     def bytes(self):
-        return np.frombuffer(self.acc.to_bytes((self.n + 7) // 8, "little"), np.uint8).copy()
+        return np.frombuffer(bytes(self.buf) + self.acc.to_bytes((self.nacc + 7) // 8, "little"), np.uint8).copy()
 
 
 class BitReader:
@@ -240,6 +253,36 @@ def write_stored_empty(bw, final=False):
     bw.align()
     bw.put(0, 16)
     bw.put(0xFFFF, 16)
+
+
+def write_stored(bw, data, final=False):
+    """A stored block that carries data (at most 65535 bytes).  -> the stream byte offset of its first data byte"""
+    data = bytes(data)
+    assert len(data) <= 0xFFFF
+    bw.put(int(final), 1)
+    bw.put(0, 2)
+    bw.align()
+    bw.put(len(data), 16)
+    bw.put(len(data) ^ 0xFFFF, 16)
+    at = bw.n // 8
+    if data:
+        bw.put(int.from_bytes(data, "little"), 8 * len(data))
+    return at
+
+
+class RawSegment:
+    """A segment of one stored block that carries all its bytes, behind as many empty stored blocks as it takes to put
+    the first data byte at a stream offset of raw_mod (mod 4); raw_mod None: no empty block in front."""
+
+    def __init__(self, data, raw_mod=None):
+        self.data, self.raw_mod = bytes(data), raw_mod
+
+
+def huffman_block(tokens, **opt):
+    """(tokens, ll lengths, d lengths, options): a dynamic block whose codes are package-merge's at 15 bits"""
+    tokens = np.asarray(tokens, np.uint32)
+    ll, d = token_symbols(tokens)
+    return tokens, package_merge(ll, 15), package_merge(d, 15), opt
 
 
 def write_dynamic(bw, tokens, ll_lens, d_lens, final=False, hlit=None, hdist=None, max_repeats=True, avoid_repeats=False,
@@ -331,12 +374,13 @@ def write_dynamic(bw, tokens, ll_lens, d_lens, final=False, hlit=None, hdist=Non
     return rep
 
 
-def segment_tokens_ok(tokens, sub):
-    """no match crosses a 1024-byte region (the sub-index's condition) and none reaches before the segment"""
+def segment_tokens_ok(tokens, sub, hist=0):
+    """no match crosses a 1024-byte region (the sub-index's condition) and none reaches before the segment's `hist`
+    bytes of history (the earlier segments of its strip)"""
     pos = 0
     for t in np.asarray(tokens, np.uint32).tolist():
         n = ((t >> 16) & 0xFF) + 3 if t & MATCH else 1
-        if t & MATCH and (t & 0x7FFF) + 1 > pos:
+        if t & MATCH and (t & 0x7FFF) + 1 > pos + hist:
             return False
         if sub and pos // REGION != (pos + n - 1) // REGION:
             return False
@@ -344,27 +388,42 @@ def segment_tokens_ok(tokens, sub):
     return True
 
 
-def write_stream(segments, final=True, subindex=False):
-    """A block-indexed stream: each segment (at most 32768 bytes of output, independent of the others) is a list of
-    blocks, each (tokens, ll_lens, d_lens, options dict for write_dynamic); every segment but the last (or every one,
-    final=False) ends with an empty stored block, so that the next one starts on a byte.  subindex: one block per
-    segment, no match across a 1024-byte region: also the 32 x {bit offset, tokens before} entries per segment.
-    -> (stream uint8, index uint64[nseg + 1], subindex uint32[nseg, 32, 2] or None, output bytes, reports per block)"""
+def write_stream(segments, final=True, subindex=False, strip_segments=1):
+    """A block-indexed stream: each segment (at most 32768 bytes of output) is a list of blocks, each (tokens, ll_lens,
+    d_lens, options dict for write_dynamic) or a bytes-like object (a stored block that carries it; empty: an empty stored
+    block), or the segment is a RawSegment; every segment but the last (or every one, final=False) ends with an empty
+    stored block, so that the next one starts on a byte.  strip_segments: segments per strip (block_bytes / 32768): a
+    segment's matches may reach back into the earlier segments of its strip, never before the strip.  subindex: one
+    dynamic block per segment, no match across a 1024-byte region: also the 32 x {bit offset, tokens before} entries per
+    segment.  -> (stream uint8, index uint64[nseg + 1], subindex uint32[nseg, 32, 2] or None, output bytes, reports per
+    block: write_dynamic's, or {"type": 0, "data_byte": stream offset of its first byte, "len": bytes} for a stored one)"""
     bw = BitWriter()
     idx, subs, reps, out = [0], [], [], bytearray()
+    strip = b""
     for si, blocks in enumerate(segments):
         seg_start = bw.n
         assert seg_start % 8 == 0
+        if si % strip_segments == 0:
+            strip = b""
         seg_out = b""
         last_seg = final and si == len(segments) - 1
-        for bi, (tokens, ll, dl, opt) in enumerate(blocks):
-            opt = dict(opt or {})
+        if isinstance(blocks, RawSegment):
+            j = 0 if blocks.raw_mod is None else (blocks.raw_mod - (seg_start // 8 + 5)) % 4  # an empty stored block is 5 bytes
+            blocks = [b""] * j + [blocks.data]
+        for bi, blk in enumerate(blocks):
             fin = last_seg and bi == len(blocks) - 1
+            if isinstance(blk, (bytes, bytearray)):
+                assert not subindex
+                reps.append({"type": 0, "data_byte": write_stored(bw, blk, final=fin), "len": len(blk)})
+                seg_out += bytes(blk)
+                continue
+            tokens, ll, dl, opt = blk
+            opt = dict(opt or {})
             if subindex:
-                assert len(blocks) == 1 and segment_tokens_ok(tokens, True)
+                assert len(blocks) == 1 and segment_tokens_ok(tokens, True, len(strip))
                 opt["region_starts"] = [r * REGION for r in range(32)]
             reps.append(write_dynamic(bw, tokens, ll, dl, final=fin, **opt))
-            seg_out += expand(tokens, seg_out)
+            seg_out += expand(tokens, strip + seg_out)
         assert len(seg_out) == SEGMENT or (len(seg_out) <= SEGMENT and si == len(segments) - 1), "only the last segment may be short"
         if subindex:  # the one block starts at the segment's first bit: its bit offsets are the segment's
             subs.append(np.array([reps[-1]["marks"][r * REGION] for r in range(32)], np.uint32))
@@ -373,6 +432,7 @@ def write_stream(segments, final=True, subindex=False):
         bw.align()
         idx.append(bw.n // 8)
         out += seg_out
+        strip += seg_out
     stream = bw.bytes()
     return (stream, np.array(idx, np.uint64), np.stack(subs) if subindex else None, bytes(out), reps)
 
@@ -420,11 +480,12 @@ def _decode(br, dec):
     raise ValueError("no code matches")
 
 
-def inflate(data, bit=0, stop_at_segment_end=False):
+def inflate(data, bit=0, stop_at_segment_end=False, matches=None):
     """A plain decoder of raw DEFLATE from `bit` on, for what the tests need to see: -> (bytes, blocks), each block a
     dict with its type, header (dynamic) and the (code length, extra bits, extra value) of every length and distance
     item and the code length of every literal / end-of-block.  Stops after BFINAL (or, stop_at_segment_end, after
-    the first empty stored block)."""
+    the first empty stored block).  matches: a list that gets (output position, distance, length) of every match.
+    Slow (a Python call per bit of a code): meant for streams of a MiB or so."""
     br = BitReader(data, bit)
     out, blocks = bytearray(), []
     while True:
@@ -446,8 +507,8 @@ def inflate(data, bit=0, stop_at_segment_end=False):
             blk["header"] = h
             ll, dl = h["ll_lens"], h["d_lens"]
         else:
-            ll = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 6
-            dl = [5] * 30
+            ll = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8  # all 288: 286 and 287 move the 9-bit codes
+            dl = [5] * 32
         dl_ = _decoder(dl, 15)
         lld = _decoder(ll, 15)
         while True:
@@ -465,6 +526,9 @@ def inflate(data, bit=0, stop_at_segment_end=False):
                 ds = _decode(br, dl_)
                 dist = DIST_BASE[ds] + br.get(DIST_EXTRA[ds])
                 blk["dist_items"].add((dl[ds], DIST_EXTRA[ds], dist - DIST_BASE[ds]))
+                assert dist <= len(out), "distance too far back"
+                if matches is not None:
+                    matches.append((len(out), dist, length))
                 for _ in range(length):
                     out.append(out[-dist])
         if fin:
