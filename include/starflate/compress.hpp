@@ -26,6 +26,7 @@ enum class CompressStatus : std::uint8_t {
   OutOfMemory,
   CommError,    // RCCL not loadable, or an RCCL call failed (gather_streams)
   Unsupported,  // the effort rests on LDS behaviour this device does not show (sfh_lds_order_check)
+  NotIndexable, // recover_index: the stream is not block-flushed every 32 KiB of output
 };
 
 enum class BlockStrategy : std::uint8_t { Auto, Stored, Fixed, Dynamic };
@@ -101,6 +102,7 @@ inline auto to_status(int rc) -> CompressStatus {
     case SFH_E_NOMEM: return CompressStatus::OutOfMemory;
     case SFH_E_COMM: return CompressStatus::CommError;
     case SFH_E_UNSUPPORTED: return CompressStatus::Unsupported;
+    case SFH_E_NOT_INDEXABLE: return CompressStatus::NotIndexable;
     default: return CompressStatus::InvalidArgument;
   }
 }
@@ -254,6 +256,33 @@ class compressor {
                                   ix.segments(), dst.data(), dst.size(), ix.block_bytes, &st);
     if (rc != SFH_OK || st > 7) return DecompressStatus::Error;
     return static_cast<DecompressStatus>(st);
+  }
+  /// The index of a stream given alone, recovered on the GPU from its flush markers: offsets of its
+  /// max(1, ceil(dst_size / 32768)) segments + 1; block_bytes 0 (unknown), no regions.  A stream that is not block-flushed
+  /// every 32 KiB is CompressStatus::NotIndexable.
+  auto recover_index(std::span<const std::byte> src, std::size_t dst_size, Container container)
+      -> compat::expected<stream_index, CompressStatus> {
+    if (!ctx_) return compat::unexpected{init_};
+    stream_index ix;
+    const std::size_t nseg = dst_size ? (dst_size + SFH_SEGMENT_BYTES - 1) / SFH_SEGMENT_BYTES : 1;
+    ix.offsets.resize(nseg + 1);
+    ix.block_bytes = 0;
+    const int rc = sfh_recover_index(ctx_, src.data(), src.size(), static_cast<std::uint32_t>(container), dst_size,
+                                     ix.offsets.data(), nseg, nullptr);
+    if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+    return ix;
+  }
+  /// decompress(src, dst) for a stream given alone: on the GPU when its segment index can be recovered
+  /// (sfh_decompress_any), else -- and whenever the GPU reports anything but Success -- container.hpp's serial
+  /// decompress(src, dst, container), whose status is returned: the caller always gets the reference's answer.
+  auto decompress(std::span<const std::byte> src, std::span<std::byte> dst, Container container) -> DecompressStatus {
+    if (ctx_) {
+      std::uint32_t st = 0;
+      const int rc = sfh_decompress_any(ctx_, src.data(), src.size(), static_cast<std::uint32_t>(container), dst.data(), dst.size(),
+                                        dst.size(), nullptr, &st);
+      if (rc == SFH_OK && st == 0) return DecompressStatus::Success;
+    }
+    return starflate::decompress(src, dst, container);
   }
   /// device pointers (src 16-byte aligned), optional hipStream_t
   auto compress_device(const void* d_src, std::size_t n, void* d_dst, std::size_t cap, const compress_options& opt = {},

@@ -38,7 +38,9 @@ enum sfh_status {
   SFH_E_HIP = -4,           /* a HIP runtime call failed; see sfh_last_error() */
   SFH_E_NOMEM = -5,         /* device scratch allocation failed */
   SFH_E_COMM = -6,          /* RCCL not loadable, or an RCCL call failed; see sfh_last_error() */
-  SFH_E_UNSUPPORTED = -7    /* the effort asked for rests on LDS behaviour this device does not show (sfh_lds_order_check) */
+  SFH_E_UNSUPPORTED = -7,   /* the effort asked for rests on LDS behaviour this device does not show (sfh_lds_order_check) */
+  SFH_E_NOT_INDEXABLE = -8  /* sfh_recover_index* / sfh_decompress_any*: the stream is not block-flushed every 32 KiB of
+                               output (the walk of DESIGN.md 3a ends before it found every segment); nothing was decoded */
 };
 
 /* block strategy (inverse of src/decompress.cpp:416-458 dispatch) */
@@ -345,6 +347,41 @@ int sfh_decompress_batch_device_async(sfh_ctx* ctx, size_t count, const void* co
 int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n,
                          const uint64_t* index, const uint32_t* subindex, void* const* dsts, const uint64_t* dst_n,
                          const uint32_t* block_bytes, uint32_t container, uint32_t* status);
+
+/* ---- decoding without side information ----
+ * The segment index of a stream that is flushed every 32 KiB of output -- every stream sfh_compress* writes, and zlib's with
+ * Z_SYNC_FLUSH / Z_FULL_FLUSH every 32768 input bytes -- recovered from the stream itself: a coded segment ends with the empty
+ * stored block of a flush (bytes 00 00 FF FF), a stored segment is one block of LEN 32768.  One pass over the body finds both
+ * patterns, pointer jumping walks them from the body's first byte.  container: enum sfh_container (the wrapper is read as
+ * sfh_decompress_batch reads it).  Alignment as sfh_decompress_device (d_src 4, d_index 8, d_dst 16).
+ *
+ * sfh_recover_index_device: index[0..nseg] (nseg = max(1, ceil(dst_n / 32768)), offsets into the stream, wrapper header
+ * included, as sfh_copy_index); d_depends (uint8 per segment, device, may be NULL): 1 when a match of the segment reaches
+ * before its first byte (the token stage runs for it).  SFH_E_NOT_INDEXABLE when the walk ends short; a wrapper header that does
+ * not parse is SFH_E_NOT_INDEXABLE as well.  Synchronises `stream` (NULL = the ctx's own).
+ *
+ * sfh_decompress_any_device: recovers the index and decodes with it: *status is the reference's DecompressStatus, and for a
+ * wrapped stream container.hpp's decompress(src, dst, container) (header, ISIZE, the Adler-32 / CRC-32 computed on the GPU:
+ * a mismatch is Error).  Every segment but the last must end exactly on its last byte with a non-final block, so Success means
+ * the bytes the serial decoder writes; a false marker only ever ends in an error status.  No block_bytes: a match may reach
+ * back as far as bytes were written, and segments are copied in rows of dependent segments found by the token stage.
+ * dst_n = SFH_SIZE_FROM_TRAILER with a gzip stream: the output size is ISIZE (members of 4 GiB and more need an explicit size).
+ * The token scratch is 4 bytes per output byte of the whole call.  Synchronises `stream`.
+ * sfh_decompress_any: host buffers (H2D, the same, D2H of dst when *status is 0); dst holds dst_cap bytes (dst_n above it, or an
+ * ISIZE above it, is SFH_E_DST_TOO_SMALL); *dst_n_out (may be NULL) = the output size decoded to. */
+#define SFH_SIZE_FROM_TRAILER UINT64_MAX
+int sfh_recover_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint32_t container, uint64_t dst_n, uint64_t* d_index,
+                             size_t nseg, uint8_t* d_depends, void* stream);
+/* host buffers: index[0..nseg], depends (uint8 per segment, may be NULL) */
+int sfh_recover_index(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, uint64_t dst_n, uint64_t* index, size_t nseg,
+                      uint8_t* depends);
+int sfh_decompress_any_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint32_t container, void* d_dst, uint64_t dst_n,
+                              uint32_t* status, void* stream);
+int sfh_decompress_any(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, void* dst, uint64_t dst_cap,
+                       uint64_t dst_n, uint64_t* dst_n_out, uint32_t* status);
+/* the last sfh_recover_index* / sfh_decompress_any* call: ms[0] candidate scan, ms[1] walk (with profiling on, else zeros);
+ * counts[0] nodes (b0, markers, stored headers), counts[1] rows of dependent segments (0 when no decode ran) */
+int sfh_last_recover_stats(sfh_ctx* ctx, float ms[2], uint64_t counts[2]);
 
 /* bytes of decoder token scratch the last sfh_decompress* call on this ctx used (0 before the first) */
 size_t sfh_last_decode_scratch_bytes(const sfh_ctx* ctx);

@@ -13,6 +13,8 @@ INFLATE_NSTAGES = 2
 SEGMENT_BYTES = 32768
 STRATEGY = {"auto": 0, "stored": 1, "fixed": 2, "dynamic": 3}
 CONTAINER = {"raw": 0, "zlib": 1, "gzip": 2}
+E_NOT_INDEXABLE = -8  # SFH_E_NOT_INDEXABLE
+SIZE_FROM_TRAILER = (1 << 64) - 1  # SFH_SIZE_FROM_TRAILER
 DBG_NTOK, DBG_TOKENS, DBG_HIST, DBG_PLAN, DBG_LENS, DBG_OFFSETS, DBG_STAMPS = range(7)
 DBG_SUBINDEX = 7
 DBG_ITEMS, DBG_NITEMS = 8, 9
@@ -28,6 +30,7 @@ EXPORTS = [
     "sfh_compress_bound", "sfh_compress", "sfh_compress_multi", "sfh_compress_device", "sfh_compress_device_async",
     "sfh_compress_batch_device_async", "sfh_compress_batch", "sfh_batch_index_size", "sfh_copy_batch_index",
     "sfh_decompress_batch_device_async", "sfh_decompress_batch",
+    "sfh_recover_index_device", "sfh_recover_index", "sfh_decompress_any_device", "sfh_decompress_any", "sfh_last_recover_stats",
     "sfh_last_block_bytes", "sfh_index_entries", "sfh_copy_index", "sfh_copy_subindex", "sfh_decompress_device", "sfh_decompress", "sfh_last_inflate_ms", "sfh_last_decode_scratch_bytes",
     "sfh_inflate_stage_name", "sfh_checksum_device", "sfh_crc32_combine", "sfh_adler32_combine",
     "sfh_set_profiling", "sfh_last_stage_ms", "sfh_stage_name", "sfh_debug_read",
@@ -105,6 +108,17 @@ def lib():
     L.sfh_decompress_batch_device_async.restype = C.c_int
     L.sfh_decompress_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, vp, vp, C.POINTER(vp), u64p, vp, C.c_uint32, vp]
     L.sfh_decompress_batch.restype = C.c_int
+    L.sfh_recover_index_device.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint64, vp, sz, vp, vp]
+    L.sfh_recover_index_device.restype = C.c_int
+    L.sfh_recover_index.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint64, vp, sz, vp]
+    L.sfh_recover_index.restype = C.c_int
+    L.sfh_decompress_any_device.argtypes = [vp, vp, sz, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint32), vp]
+    L.sfh_decompress_any_device.restype = C.c_int
+    L.sfh_decompress_any.argtypes = [vp, vp, sz, C.c_uint32, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint32)]
+    L.sfh_decompress_any.restype = C.c_int
+    L.sfh_last_recover_stats.argtypes = [vp, C.POINTER(C.c_float * 2), C.POINTER(C.c_uint64 * 2)]
+    L.sfh_last_recover_stats.restype = C.c_int
     L.sfh_gather_offsets.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     L.sfh_gather_offsets.restype = C.c_int
     L.sfh_comm_ranks.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -252,6 +252,62 @@ class Compressor:
                                              dst.ctypes.data if out_n else None, int(out_n), int(block_bytes), C.byref(st)))
         return (dst[:out_n].tobytes() if st.value == 0 else b""), st.value
 
+    # ---- one stream given alone: the segment index recovered on the GPU ----
+    def recover_index(self, stream, out_n, container="raw", hip_stream=None):
+        """stream: 1-D uint8 CUDA tensor (exactly the compressed bytes), out_n: its decoded size -> (index int64 CUDA tensor of
+        segments + 1 offsets, depends uint8 CUDA tensor: 1 where a match of the segment reaches before its first byte).
+        A stream that is not block-flushed every 32 KiB raises StarflateError with code -8 (SFH_E_NOT_INDEXABLE)."""
+        import torch
+
+        self._check_tensor(stream)
+        nseg = max(1, -(-int(out_n) // CHUNK_BYTES))
+        index = torch.empty(nseg + 1, dtype=torch.int64, device=stream.device)
+        depends = torch.empty(nseg, dtype=torch.uint8, device=stream.device)
+        s = torch.cuda.current_stream(stream.device).cuda_stream if hip_stream is None else hip_stream
+        self._check(self._lib.sfh_recover_index_device(self._h, stream.data_ptr(), stream.numel(), _container(container),
+                                                       int(out_n), index.data_ptr(), nseg, depends.data_ptr(), C.c_void_p(s)))
+        return index, depends
+
+    def decompress_any_tensor(self, stream, out_n=None, container="raw", out=None, hip_stream=None):
+        """stream: 1-D uint8 CUDA tensor; out_n: decoded size (None: gzip's ISIZE) -> (out tensor, DecompressStatus int).
+        No index, no block_bytes: the stream's own flush markers give the segments.  Not block-flushed: StarflateError -8."""
+        import torch
+
+        self._check_tensor(stream)
+        kind = _container(container)
+        if out_n is None:
+            out_n = _isize(stream[-4:].cpu().numpy().tobytes() if stream.numel() >= 4 else b"", kind)
+        if out is None:
+            out = torch.empty(max(int(out_n), 1), dtype=torch.uint8, device=stream.device)
+        self._check_tensor(out)
+        if out.numel() < out_n:
+            raise ValueError("out is smaller than out_n")
+        st = C.c_uint32(0)
+        s = torch.cuda.current_stream(stream.device).cuda_stream if hip_stream is None else hip_stream
+        self._check(self._lib.sfh_decompress_any_device(self._h, stream.data_ptr(), stream.numel(), kind,
+                                                        out.data_ptr() if out_n else None, int(out_n), C.byref(st),
+                                                        C.c_void_p(s)))
+        return out[:out_n], st.value
+
+    def decompress_any(self, data, out_n=None, container="raw"):
+        """Host buffers: a bytes-like raw / zlib / gzip stream -> (bytes, DecompressStatus int), on the GPU without an index;
+        out_n None: gzip's ISIZE.  Not block-flushed every 32 KiB: StarflateError -8 (decompress() falls back instead)."""
+        src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        kind = _container(container)
+        n = _isize(src[-4:].tobytes(), kind) if out_n is None else int(out_n)
+        dst = np.empty(max(n, 1), dtype=np.uint8)
+        st = C.c_uint32(0)
+        self._check(self._lib.sfh_decompress_any(self._h, src.ctypes.data if src.size else None, src.size, kind, dst.ctypes.data,
+                                                 n, n, None, C.byref(st)))
+        return (dst[:n].tobytes() if st.value == 0 else b""), st.value
+
+    def last_recover_stats(self):
+        """The last recover / decompress_any call: {"scan_ms", "walk_ms"} (with profiling on), {"nodes", "rows"}."""
+        ms = (C.c_float * 2)()
+        cnt = (C.c_uint64 * 2)()
+        self._check(self._lib.sfh_last_recover_stats(self._h, C.byref(ms), C.byref(cnt)))
+        return {"scan_ms": ms[0], "walk_ms": ms[1], "nodes": cnt[0], "rows": cnt[1]}
+
     # ---- many independent streams, each decoded into its own buffer, in one call (sfh_decompress_batch*) ----
     def decompress_batch(self, streams, sizes, index=None, subindex=None, block_bytes=None, container="raw"):
         """Host buffers: bytes-like streams and their decoded sizes -> (list of bytes, list of DecompressStatus ints).  index /
@@ -481,6 +537,33 @@ def compress_batch(items, device=0, **kw):
     if c is None:
         c = _DEFAULT[device] = Compressor(device)
     return c.compress_batch(items, **kw)
+
+
+def _container(container):
+    kind = _capi.CONTAINER[container] if isinstance(container, str) else int(container)
+    if kind not in (0, 1, 2):
+        raise ValueError("container: raw, zlib or gzip")
+    return kind
+
+
+def _isize(tail, kind):
+    """out_n=None: gzip's ISIZE (little-endian, the last 4 bytes); other containers carry no size"""
+    if kind != 2:
+        raise ValueError("out_n is required unless container='gzip' (whose trailer carries ISIZE)")
+    return int.from_bytes(tail, "little") if len(tail) == 4 else 0
+
+
+def decompress(data, out_n=None, container="raw", device=0):
+    """One stream given alone -> bytes, on the GPU (Compressor.decompress_any): the segment index is recovered from the
+    stream's flush markers.  A status other than Success raises StarflateError; so does a stream that is not block-flushed
+    every 32 KiB (code -8): such a stream is the serial decoder's."""
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    out, st = c.decompress_any(data, out_n, container)
+    if st:
+        raise StarflateError(st, f"DecompressStatus {st}")
+    return out
 
 
 def decompress_batch(streams, sizes, device=0, **kw):

@@ -220,6 +220,8 @@ struct InflateSeg {      // per segment of a launch batch (k_inflate_tokens*, k_
   uint32_t hist;         // bytes of its strip before it (how far back a match may reach beyond it) | kSegWrapped
 };
 constexpr uint32_t kSegWrapped = 0x80000000u;  // InflateSeg.hist: a zlib / gzip item's segment (a body that ends short is Error)
+constexpr uint32_t kSegExact = 0x40000000u;    // InflateSeg.hist, recovered index only (launch_inflate_tokens_exact): not the
+                                               // stream's last segment, so its blocks must end on its last byte
 struct InflateStrip {    // per strip of a launch batch (k_inflate_bytes: one workgroup each)
   uint32_t seg0, nseg;   // its first segment in the launch batch, its segments
 };
@@ -285,6 +287,28 @@ hipError_t launch_inflate_status(const SegInfo* info, uint32_t nseg, uint32_t* d
 // batched: the launch batch's segment rows stand in for src / index / dst_n / sps (info and tokens: the batch's own)
 hipError_t launch_inflate_tokens_batch(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool sub,
                                        bool speculate, hipStream_t s);
+// ---- sf_unindexed.hip: the segment index recovered from the stream ----
+uint32_t any_scan_waves(uint64_t src_n);  // waves (per-wave counts) of k_any_scan over a buffer of src_n bytes
+size_t any_scan_tmp_words(uint32_t n);    // words of `tmp` launch_scan_u32 needs for n elements
+// exclusive scan of n uint32 (in-place allowed); *total: their sum (device)
+hipError_t launch_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* tmp, uint32_t* total, hipStream_t s);
+// head[0..1]: the body [b0, e).  count: nodes and M nodes per wave; nodes: write them (offsets = exclusive scans of the counts)
+hipError_t launch_any_count(const uint8_t* src, uint64_t src_n, const uint64_t* head, uint32_t* cnt_nodes, uint32_t* cnt_m,
+                            hipStream_t s);
+hipError_t launch_any_nodes(const uint8_t* src, uint64_t src_n, const uint64_t* head, uint32_t* node_off, uint32_t* m_off,
+                            uint64_t* pos, uint8_t* flg, uint32_t* minc, uint32_t* midx, hipStream_t s);
+// n >= 1 nodes, nm of them M: index[0..nseg] and res[0] = segment starts on the chain from b0
+hipError_t launch_any_walk(const uint8_t* src, const uint64_t* head, const uint64_t* pos, const uint8_t* flg, const uint32_t* minc,
+                           const uint32_t* midx, uint32_t n, uint32_t nm, uint32_t* nxt_a, uint32_t* nxt_b, uint8_t* lab,
+                           uint8_t* mark, uint32_t* lbl, uint32_t* rank, uint32_t* tmp, uint32_t* total, uint64_t* index,
+                           uint32_t nseg, uint32_t* res, hipStream_t s);
+hipError_t launch_any_single(const uint64_t* head, uint64_t* index, uint32_t* res, hipStream_t s);
+// behind the token stage: depends[seg], and the rows of k_inflate_bytes_batch (nseg slots, the unused ones empty)
+hipError_t launch_any_rows(const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends, uint32_t* starts,
+                           uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows, hipStream_t s);
+// recovered index (sfh_decompress_any*): the batch kernels with the EXACT end rule for rows flagged kSegExact
+hipError_t launch_inflate_tokens_exact(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool speculate,
+                                       hipStream_t s);
 hipError_t launch_inflate_bytes_batch(const InflateSeg* rows, const InflateStrip* strips, uint32_t nstrips,
                                       const uint32_t* tokens, SegInfo* info, hipStream_t s);
 // per item of the call: the wrapper (before the token kernels), then the status fold (behind every launch batch)

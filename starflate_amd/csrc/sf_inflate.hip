@@ -49,7 +49,8 @@ static_assert(KB_SPAN <= KB_RING - kWindow && KB_RING % 16 == 0 && kChunk % 4 ==
 
 // BATCH (sfh_decompress_batch*): segment `seg` of the launch batch is rows[seg] -- its stream, index entries, size and
 // history -- instead of what the single call derives from seg; the rows are read here, in the prologue, only.
-template <bool BATCH>
+// EXACT (BATCH only): a row flagged kSegExact decodes with decode_segment<true> (the recovered index's end rule).
+template <bool BATCH, bool EXACT = false>
 __global__ __launch_bounds__(KT_LANES) void k_inflate_tokens(const uint8_t* __restrict__ src, uint64_t src_n,
                                                             const uint64_t* __restrict__ index, uint32_t nseg,
                                                             uint64_t dst_n, uint32_t* __restrict__ tokens,
@@ -71,6 +72,7 @@ __global__ __launch_bounds__(KT_LANES) void k_inflate_tokens(const uint8_t* __re
     out_n = R.out_n;
     hist = R.hist & ~kSegWrapped;
     wrapped = (R.hist & kSegWrapped) != 0;
+    if constexpr (EXACT) hist &= ~kSegExact;
   } else {
     lo = index[seg];
     hi = index[seg + 1];
@@ -78,8 +80,15 @@ __global__ __launch_bounds__(KT_LANES) void k_inflate_tokens(const uint8_t* __re
     out_n = dst_n > obase ? (uint32_t)(dst_n - obase < kChunk ? dst_n - obase : kChunk) : 0u;
     hist = (seg % sps) * kChunk;
   }
-  const inflate::SegmentResult r = inflate::decode_segment(src, src_n, lo, hi, out_n, tokens + (uint64_t)seg * kChunk,
-                                                           s_tables + threadIdx.x * inflate::LaneLayout::kBytes, hist);
+  uint32_t* const seg_tokens = tokens + (uint64_t)seg * kChunk;
+  uint8_t* const lane_m = s_tables + threadIdx.x * inflate::LaneLayout::kBytes;
+  inflate::SegmentResult r;
+  if constexpr (EXACT) {
+    if (rows[seg].hist & kSegExact) r = inflate::decode_segment<true>(src, src_n, lo, hi, out_n, seg_tokens, lane_m, hist);
+    else r = inflate::decode_segment(src, src_n, lo, hi, out_n, seg_tokens, lane_m, hist);
+  } else {
+    r = inflate::decode_segment(src, src_n, lo, hi, out_n, seg_tokens, lane_m, hist);
+  }
   SegInfo si;
   si.status = r.status;
   // a wrapped item whose body ENDS short of its output: container.hpp's raw decode succeeds there and its checksum of the
@@ -688,7 +697,9 @@ struct SegState {
 enum : uint32_t { kSegRun = 0, kSegDone = 1, kSegRetry = 2 };
 
 // BATCH: as tokens_wave_sub -- each half's row gives its stream, index entries, size and history
-template <bool BATCH>
+// EXACT (BATCH only): a row flagged kSegExact counts as done only when its blocks end on its last bit, none of them final;
+// anything else goes to k_inflate_tokens<true, true>, which says what is wrong (decode_segment<true>)
+template <bool BATCH, bool EXACT = false>
 __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src, uint64_t src_n, const uint64_t* __restrict__ index,
                                                  uint32_t nseg, uint64_t dst_n, uint32_t* __restrict__ tokens,
                                                  SegInfo* __restrict__ info, uint32_t sps, const InflateSeg* __restrict__ rows) {
@@ -700,11 +711,16 @@ __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src
   const uint32_t lane = threadIdx.x, half = lane >> 5, hl = lane & 31;
   const uint32_t seg = 2 * blockIdx.x + half;
   uint32_t hist = 0;  // (BATCH only: the single call derives it where it needs it)
+  bool exact = false;
   if constexpr (BATCH) {
     if (seg < nseg) {  // (every lane of the half: the stream pointer is the half's own)
       src = rows[seg].src;
       src_n = rows[seg].src_n;
       hist = rows[seg].hist & ~kSegWrapped;
+      if constexpr (EXACT) {
+        exact = (hist & kSegExact) != 0;
+        hist &= ~kSegExact;
+      }
     }
   }
   {
@@ -769,6 +785,9 @@ __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src
       fin = (b3 & 1u) != 0;
     }
     // BFINAL seen, or no header bits left: the segment is complete if it has all its bytes (else the serial decoder says what is wrong)
+    if constexpr (EXACT) {
+      if (exact && (fin || at + 3 > seg_bits)) return (!fin && at == seg_bits && out_base == S.out_n) ? (uint32_t)kSegDone : (uint32_t)kSegRetry;
+    }
     if (fin || at + 3 > seg_bits) return out_base == S.out_n ? (uint32_t)kSegDone : (uint32_t)kSegRetry;
     return kSegRun;
   };
@@ -791,7 +810,7 @@ __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src
       uint64_t raw_off = S.raw_off;
       const uint32_t out_n = S.out_n;
       if (b.st != inflate::kOk) state = kSegRetry;
-      else if (b.kind == kBlkEnd) state = out_base == out_n ? (uint32_t)kSegDone : (uint32_t)kSegRetry;
+      else if (b.kind == kBlkEnd) state = (out_base == out_n && (!EXACT || !exact || at == S.seg_bits)) ? (uint32_t)kSegDone : (uint32_t)kSegRetry;
       else if (b.kind == kBlkStored) {
         if (b.len > out_n - out_base) state = kSegRetry;
         else {
@@ -978,6 +997,12 @@ __attribute__((amdgpu_waves_per_eu(5, 5)))
 __global__ __launch_bounds__(64, 2) void k_inflate_tokens_spec_batch(const InflateSeg* __restrict__ rows, uint32_t nseg,
                                                                     uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
   tokens_wave_spec<true>(nullptr, 0, nullptr, nseg, 0, tokens, info, 1, rows);
+}
+
+__attribute__((amdgpu_waves_per_eu(5, 5)))
+__global__ __launch_bounds__(64, 2) void k_inflate_tokens_spec_exact(const InflateSeg* __restrict__ rows, uint32_t nseg,
+                                                                    uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
+  tokens_wave_spec<true, true>(nullptr, 0, nullptr, nseg, 0, tokens, info, 1, rows);
 }
 
 __device__ __forceinline__ uint32_t load_word_guarded(const uint8_t* base, uint64_t src_n, uint64_t w) {
@@ -1380,6 +1405,9 @@ hipError_t init_inflate_kernels() {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_tokens<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)KT_LDS);
   if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_tokens<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)KT_LDS);
+  if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes_batch), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)KB_LDS);
   if (e != hipSuccess) return e;
@@ -1416,6 +1444,19 @@ hipError_t launch_inflate_tokens_batch(const InflateSeg* rows, uint32_t nseg, ui
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(k_inflate_tokens<true>, dim3((nseg + KT_LANES - 1) / KT_LANES), dim3(KT_LANES), KT_LDS, s,
+                     (const uint8_t*)nullptr, (uint64_t)0, (const uint64_t*)nullptr, nseg, (uint64_t)0, tokens, info, 1u,
+                     speculate ? 1u : 0u, rows);
+  return hipGetLastError();
+}
+
+hipError_t launch_inflate_tokens_exact(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool speculate,
+                                       hipStream_t s) {
+  if (speculate) {
+    hipLaunchKernelGGL(k_inflate_tokens_spec_exact, dim3((nseg + 1) / 2), dim3(64), 0, s, rows, nseg, tokens, info);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((k_inflate_tokens<true, true>), dim3((nseg + KT_LANES - 1) / KT_LANES), dim3(KT_LANES), KT_LDS, s,
                      (const uint8_t*)nullptr, (uint64_t)0, (const uint64_t*)nullptr, nseg, (uint64_t)0, tokens, info, 1u,
                      speculate ? 1u : 0u, rows);
   return hipGetLastError();

@@ -426,6 +426,9 @@ SF_HD uint32_t decode_symbols(BitReader& br, const uint8_t* m, Sink& sink, uint3
 
 // Decodes the blocks of one segment: stream bytes [seg_begin, seg_end) of `src`, which must produce exactly
 // out_n (<= 32768) bytes.  Tokens go to tokens[0..ntok).  `m`: LaneLayout::kBytes of scratch.  hist: see decode_symbols.
+// EXACT (a recovered index): the segment is not the stream's last, so its blocks must end ON seg_end, none of
+// them final -- fewer than 3 bits left over, or BFINAL, is kError there, not the end of the segment.
+template <bool EXACT = false>
 SF_HD SegmentResult decode_segment(const uint8_t* src, uint64_t src_n, uint64_t seg_begin, uint64_t seg_end,
                                    uint32_t out_n, uint32_t* tokens, uint8_t* m, uint32_t hist = 0) {
   SegmentResult r{kOk, 0, 0, 0, 0};
@@ -488,6 +491,7 @@ SF_HD SegmentResult decode_segment(const uint8_t* src, uint64_t src_n, uint64_t 
     r.ended = last ? 1u : 0u;
   }
   if (status == kOk && r.raw && sink.n != 0) status = kDstTooSmall;
+  if (EXACT && status == kOk && (last || br.bitpos != br.nbits)) status = kError;
   sink.flush();
   r.status = status;
   r.ntok = sink.n;

@@ -1,0 +1,364 @@
+// sf_unindexed.hip -- the segment index of a block-flushed DEFLATE stream, recovered from the stream alone,
+// and the two device passes the decoder needs on such an index (sfh_recover_index_device, sfh_decompress_any*).
+//
+//   k_any_scan<WRITE>  one pass over the body (the stream without its wrapper): every position p with [p-4, p) = 00 00 FF FF
+//                      (M, the end of a flush) and every h with [h, h+5) = 00|01 00 80 FF 7F (H, the header of a stored block of
+//                      32 KiB), plus the body's first byte b0.  One wave per 8 KiB of stream; a wave-round with no hit costs
+//                      one ballot.  WRITE = 0 counts the wave's nodes, WRITE = 1 writes them in stream order at the wave's
+//                      offset (an exclusive scan of the counts): no atomics, the node list comes out sorted.
+//   k_any_succ         every node's successor on the walk (the walk rule) and how many segments the edge covers.
+//   k_any_jump         one round of pointer jumping that also spreads the mark "on the chain from b0": after round r every
+//                      node at most 2^(r+1) - 1 steps behind b0 is marked.  Nodes off the chain (flush markers and fake
+//                      headers inside stored payloads) are never marked, and a run of stored segments costs no serial steps.
+//   k_any_scatter      marked node of rank k (an exclusive scan of the edge labels) -> index[k] (and index[k+1] for the coded
+//                      segment a stored jump lands on).
+//   k_any_depends      after the token stage: per segment, does a match reach before its first byte?
+//   k_any_rows_*       rows for k_inflate_bytes_batch: an independent segment and the dependent ones behind it.
+#include "sf_device.h"
+
+#include "sf_inflate_core.h"
+
+namespace sf {
+
+namespace {
+
+constexpr uint32_t KA_THREADS = 256;
+constexpr uint32_t KA_WAVE_BYTES = 8192;  // stream bytes per wave of k_any_scan (32 rounds of 64 lanes x 4 bytes)
+constexpr uint32_t KA_ROUNDS = KA_WAVE_BYTES / 256;
+constexpr uint8_t kNodeM = 1, kNodeH = 2;
+constexpr uint32_t kStoredSeg = kChunk + 5;  // a stored segment: header byte, LEN, NLEN, 32 KiB
+
+__device__ __forceinline__ uint32_t dword_at(const uint8_t* src, uint64_t src_n, int64_t k) {
+  // dword k of the buffer (readable up to the next multiple of 4 bytes); zero outside it
+  if (k < 0 || (uint64_t)k * 4 >= src_n) return 0u;
+  return reinterpret_cast<const uint32_t*>(src)[k];
+}
+
+// the hits of the four positions 4k .. 4k+3: bits 0..3 M, 4..7 H, 8..11 the body's first byte
+__device__ __forceinline__ uint32_t hits_at(const uint8_t* src, uint64_t src_n, uint64_t b0, uint64_t e, int64_t k) {
+  const uint64_t prev = dword_at(src, src_n, k - 1), cur = dword_at(src, src_n, k), next = dword_at(src, src_n, k + 1);
+  const uint64_t lo = (cur << 32) | prev, hi = (next << 32) | cur;
+  uint32_t m = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 4; ++j) {
+    const uint64_t p = 4 * (uint64_t)k + j;
+    if (p < b0 || p >= e) continue;
+    if (p >= b0 + 4 && (uint32_t)(lo >> (8 * j)) == 0xFFFF0000u) m |= 1u << j;
+    const uint64_t h = hi >> (8 * j);
+    if (p + 5 <= e && (h & 0xFEu) == 0 && (uint32_t)(h >> 8) == 0x7FFF8000u) m |= 16u << j;
+    if (p == b0) m |= 256u << j;
+  }
+  return m;
+}
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+  const uint32_t lane = threadIdx.x & 63;
+#pragma unroll
+  for (uint32_t o = 1; o < 64; o <<= 1) {
+    const uint32_t u = (uint32_t)__shfl_up((int)v, o, 64);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+
+// head[0], head[1]: the body [b0, e) (k_inflate_head's implied entries).  counts: per wave {nodes, M nodes}
+// (WRITE: their exclusive scans, node_off / m_off)
+template <bool WRITE>
+__global__ __launch_bounds__(KA_THREADS) void k_any_scan(const uint8_t* __restrict__ src, uint64_t src_n,
+                                                        const uint64_t* __restrict__ head, uint32_t nwaves,
+                                                        uint32_t* __restrict__ cnt_nodes, uint32_t* __restrict__ cnt_m,
+                                                        uint64_t* __restrict__ pos, uint8_t* __restrict__ flg,
+                                                        uint32_t* __restrict__ minc, uint32_t* __restrict__ midx) {
+  const uint32_t wave = blockIdx.x * (KA_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (wave >= nwaves) return;
+  const uint64_t b0 = head[0], e = head[1];
+  uint32_t nodes = WRITE ? cnt_nodes[wave] : 0u, ms = WRITE ? cnt_m[wave] : 0u;
+  const int64_t k0 = (int64_t)wave * (KA_WAVE_BYTES / 4);
+  for (uint32_t r = 0; r < KA_ROUNDS; ++r) {
+    const int64_t k = k0 + r * 64 + lane;
+    const uint32_t h = hits_at(src, src_n, b0, e, k);
+    if (__ballot(h != 0) == 0) continue;
+    const uint32_t pm = h & 15u, any = (h | (h >> 4) | (h >> 8)) & 15u;
+    const uint32_t n_incl = wave_incl_scan(__popc(any)), m_incl = wave_incl_scan(__popc(pm));
+    if constexpr (WRITE) {
+      uint32_t at = nodes + n_incl - __popc(any), mat = ms + m_incl - __popc(pm);
+      for (uint32_t j = 0; j < 4; ++j) {
+        if (!((any >> j) & 1u)) continue;
+        const bool is_m = (pm >> j) & 1u;
+        pos[at] = 4 * (uint64_t)k + j;
+        flg[at] = (is_m ? kNodeM : 0) | (((h >> (4 + j)) & 1u) ? kNodeH : 0);
+        if (is_m) midx[mat++] = at;
+        minc[at] = mat;  // M nodes at or before this one
+        ++at;
+      }
+    }
+    nodes += (uint32_t)__shfl((int)n_incl, 63, 64);
+    ms += (uint32_t)__shfl((int)m_incl, 63, 64);
+  }
+  if (!WRITE && lane == 0) {
+    cnt_nodes[wave] = nodes;
+    cnt_m[wave] = ms;
+  }
+}
+
+// where the segment after a stored segment at p starts: behind its 32 KiB, and behind the empty stored blocks a flush writes
+__device__ __forceinline__ uint64_t landing(const uint8_t* src, uint64_t p, uint64_t e) {
+  uint64_t t = p + kStoredSeg;
+  while (t + 5 <= e && src[t] == 0 && src[t + 1] == 0 && src[t + 2] == 0 && src[t + 3] == 0xFF && src[t + 4] == 0xFF) t += 5;
+  return t;
+}
+
+// first node at or after position t (binary search over the sorted positions)
+__device__ __forceinline__ uint32_t lower_bound(const uint64_t* pos, uint32_t n, uint64_t t) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (pos[mid] < t) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// The walk rule: from a start s in H the next start is landing(s); from any other start, the first M after s.  A landing
+// that is no node is a coded segment's start whose own successor is the first M after it: that edge covers two segments.
+__global__ __launch_bounds__(KA_THREADS) void k_any_succ(const uint8_t* __restrict__ src, const uint64_t* __restrict__ head,
+                                                        const uint64_t* __restrict__ pos, const uint8_t* __restrict__ flg,
+                                                        const uint32_t* __restrict__ minc, const uint32_t* __restrict__ midx,
+                                                        uint32_t n, uint32_t nm, uint32_t* __restrict__ nxt,
+                                                        uint8_t* __restrict__ lab, uint8_t* __restrict__ mark) {
+  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (i > n) return;
+  if (i == n) {
+    nxt[n] = n;  // the end of the body
+    return;
+  }
+  const uint64_t e = head[1];
+  uint32_t s = n, l = 1;
+  if (flg[i] & kNodeH) {
+    const uint64_t t = landing(src, pos[i], e);
+    if (t < e) {
+      const uint32_t j = lower_bound(pos, n, t);
+      if (j < n && pos[j] == t) {
+        s = j;
+      } else {
+        const uint32_t mi = j < n ? minc[j] - (flg[j] & kNodeM) : nm;  // M nodes before j
+        s = mi < nm ? midx[mi] : n;
+        l = 2;
+      }
+    }
+  } else {
+    const uint32_t mi = minc[i];
+    s = mi < nm ? midx[mi] : n;
+  }
+  nxt[i] = s;
+  lab[i] = (uint8_t)l;
+  mark[i] = i == 0;
+}
+
+__global__ __launch_bounds__(KA_THREADS) void k_any_jump(const uint32_t* __restrict__ nxt, uint32_t* __restrict__ nxt2,
+                                                        uint8_t* mark, uint32_t n) {
+  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (i > n) return;
+  const uint32_t j = nxt[i];
+  // (a node marked by another lane of this round is on the chain as well: marks only ever spread along it)
+  if (i < n && j < n && mark[i]) mark[j] = 1;
+  nxt2[i] = nxt[j];
+}
+
+__global__ __launch_bounds__(KA_THREADS) void k_any_labels(const uint8_t* __restrict__ lab, const uint8_t* __restrict__ mark,
+                                                          uint32_t n, uint32_t* __restrict__ c) {
+  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (i < n) c[i] = mark[i] ? lab[i] : 0u;
+}
+
+// res[0]: segment starts on the chain (>= nseg: indexable)
+__global__ __launch_bounds__(KA_THREADS) void k_any_scatter(const uint8_t* __restrict__ src, const uint64_t* __restrict__ head,
+                                                           const uint64_t* __restrict__ pos, const uint8_t* __restrict__ lab,
+                                                           const uint8_t* __restrict__ mark, const uint32_t* __restrict__ rank,
+                                                           const uint32_t* __restrict__ total, uint32_t n, uint64_t* __restrict__ index,
+                                                           uint32_t nseg, uint32_t* __restrict__ res) {
+  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (i == 0) {
+    index[nseg] = head[1];
+    res[0] = *total;
+  }
+  if (i >= n || !mark[i]) return;
+  const uint32_t k = rank[i];
+  if (k < nseg) index[k] = pos[i];
+  if (lab[i] == 2 && k + 1 < nseg) index[k + 1] = landing(src, pos[i], head[1]);
+}
+
+// one segment: index [b0, e], res[0] = 1 (an empty body included: the decoder says what is wrong with it)
+__global__ void k_any_single(const uint64_t* __restrict__ head, uint64_t* __restrict__ index, uint32_t* __restrict__ res) {
+  index[0] = head[0];
+  index[1] = head[1];
+  res[0] = 1;
+}
+
+// ---- exclusive scan of uint32 (1024 per block, then the block sums in one workgroup, then the add) ----
+constexpr uint32_t KS_T = 256, KS_PER = 4, KS_TILE = KS_T * KS_PER;
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, uint32_t& total) {
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint32_t incl = wave_incl_scan(v);
+  if (lane == 63) s_w[w] = incl;
+  __syncthreads();
+  uint32_t before = 0;
+  total = 0;
+  for (uint32_t k = 0; k < KS_T / 64; ++k) {
+    before += k < w ? s_w[k] : 0u;
+    total += s_w[k];
+  }
+  __syncthreads();
+  return before + incl - v;
+}
+__global__ __launch_bounds__(KS_T) void k_scan_tiles(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n,
+                                                     uint32_t* __restrict__ sums) {
+  __shared__ uint32_t s_w[KS_T / 64];
+  const uint64_t base = (uint64_t)blockIdx.x * KS_TILE + threadIdx.x * KS_PER;
+  uint32_t v[KS_PER], t = 0;
+  for (uint32_t j = 0; j < KS_PER; ++j) {
+    v[j] = base + j < n ? in[base + j] : 0u;
+    t += v[j];
+  }
+  uint32_t total;
+  uint32_t run = block_excl_scan(t, s_w, total);
+  for (uint32_t j = 0; j < KS_PER; ++j) {
+    if (base + j < n) out[base + j] = run;
+    run += v[j];
+  }
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(KS_T) void k_scan_top(uint32_t* __restrict__ sums, uint32_t nt, uint32_t* __restrict__ total) {
+  __shared__ uint32_t s_w[KS_T / 64];
+  uint32_t carry = 0;
+  for (uint32_t b = 0; b < nt; b += KS_T) {
+    const uint32_t i = b + threadIdx.x;
+    const uint32_t v = i < nt ? sums[i] : 0u;
+    uint32_t t;
+    const uint32_t x = block_excl_scan(v, s_w, t);
+    if (i < nt) sums[i] = carry + x;
+    carry += t;
+  }
+  if (threadIdx.x == 0) *total = carry;
+}
+__global__ __launch_bounds__(KS_T) void k_scan_add(uint32_t* __restrict__ out, uint32_t n, const uint32_t* __restrict__ sums) {
+  const uint64_t base = (uint64_t)blockIdx.x * KS_TILE + threadIdx.x * KS_PER;
+  const uint32_t add = sums[blockIdx.x];
+  for (uint32_t j = 0; j < KS_PER; ++j)
+    if (base + j < n) out[base + j] += add;
+}
+
+// ---- behind the token stage ----
+
+// one wave per segment: 1 when a match of it reaches before its first byte (segment 0 and failed or stored segments: 0)
+__global__ __launch_bounds__(64) void k_any_depends(const SegInfo* __restrict__ info, const uint32_t* __restrict__ tokens,
+                                                   uint8_t* __restrict__ depends, uint32_t* __restrict__ starts) {
+  const uint32_t seg = blockIdx.x, lane = threadIdx.x;
+  const SegInfo I = info[seg];
+  bool dep = false;
+  if (seg != 0 && I.status == inflate::kOk && !(I.raw & kSegRaw)) {
+    const uint32_t* tk = tokens + (uint64_t)seg * kChunk;
+    uint32_t out = 0;
+    for (uint32_t t0 = 0; t0 < I.ntok && !dep; t0 += 64) {
+      const uint32_t t = t0 + lane;
+      uint32_t len = 0, dist = 0;
+      if (t < I.ntok) {
+        const uint32_t tok = tk[t];
+        const bool m = (tok & inflate::kTokMatchBit) != 0;
+        len = m ? ((tok >> 16) & 0x7FFFu) + 3u : 1u;
+        dist = m ? (tok & 0xFFFFu) + 1u : 0u;
+      }
+      const uint32_t incl = wave_incl_scan(len);
+      dep = __ballot(dist > out + incl - len) != 0;  // (a literal has dist 0)
+      out += (uint32_t)__shfl((int)incl, 63, 64);
+    }
+  }
+  if (lane == 0) {
+    depends[seg] = dep ? 1 : 0;
+    starts[seg] = dep ? 0u : 1u;
+  }
+}
+
+// rows: row r starts at the r-th independent segment; slots past the last row are {0, 0} (the byte kernel's grid is nseg)
+__global__ __launch_bounds__(KA_THREADS) void k_any_rows_a(const uint32_t* __restrict__ starts, const uint32_t* __restrict__ excl,
+                                                          const uint32_t* __restrict__ nrows, uint32_t nseg,
+                                                          InflateStrip* __restrict__ rows) {
+  const uint32_t k = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (k >= nseg) return;
+  if (k >= *nrows) rows[k] = InflateStrip{0, 0};
+  if (starts[k]) rows[excl[k]].seg0 = k;
+}
+__global__ __launch_bounds__(KA_THREADS) void k_any_rows_b(const uint32_t* __restrict__ starts, const uint32_t* __restrict__ excl,
+                                                          uint32_t nseg, InflateStrip* __restrict__ rows) {
+  const uint32_t k = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (k >= nseg || !(k + 1 == nseg || starts[k + 1])) return;
+  const uint32_t r = excl[k] + starts[k] - 1;  // the row segment k belongs to
+  rows[r].nseg = k + 1 - rows[r].seg0;
+}
+
+inline uint32_t grid(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
+
+}  // namespace
+
+uint32_t any_scan_waves(uint64_t src_n) { return (uint32_t)((src_n + KA_WAVE_BYTES - 1) / KA_WAVE_BYTES); }
+size_t any_scan_tmp_words(uint32_t n) { return grid(n, KS_TILE) + 1; }
+
+hipError_t launch_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* tmp, uint32_t* total, hipStream_t s) {
+  const uint32_t nt = grid(n, KS_TILE);
+  if (nt) hipLaunchKernelGGL(k_scan_tiles, dim3(nt), dim3(KS_T), 0, s, in, out, n, tmp);
+  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(KS_T), 0, s, tmp, nt, total);
+  if (nt) hipLaunchKernelGGL(k_scan_add, dim3(nt), dim3(KS_T), 0, s, out, n, tmp);
+  return hipGetLastError();
+}
+
+hipError_t launch_any_count(const uint8_t* src, uint64_t src_n, const uint64_t* head, uint32_t* cnt_nodes, uint32_t* cnt_m,
+                            hipStream_t s) {
+  const uint32_t nw = any_scan_waves(src_n);
+  hipLaunchKernelGGL(k_any_scan<false>, dim3(grid(nw, KA_THREADS / 64)), dim3(KA_THREADS), 0, s, src, src_n, head, nw, cnt_nodes,
+                     cnt_m, (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_any_nodes(const uint8_t* src, uint64_t src_n, const uint64_t* head, uint32_t* node_off, uint32_t* m_off,
+                            uint64_t* pos, uint8_t* flg, uint32_t* minc, uint32_t* midx, hipStream_t s) {
+  const uint32_t nw = any_scan_waves(src_n);
+  hipLaunchKernelGGL(k_any_scan<true>, dim3(grid(nw, KA_THREADS / 64)), dim3(KA_THREADS), 0, s, src, src_n, head, nw, node_off,
+                     m_off, pos, flg, minc, midx);
+  return hipGetLastError();
+}
+
+hipError_t launch_any_walk(const uint8_t* src, const uint64_t* head, const uint64_t* pos, const uint8_t* flg, const uint32_t* minc,
+                           const uint32_t* midx, uint32_t n, uint32_t nm, uint32_t* nxt_a, uint32_t* nxt_b, uint8_t* lab,
+                           uint8_t* mark, uint32_t* lbl, uint32_t* rank, uint32_t* tmp, uint32_t* total, uint64_t* index,
+                           uint32_t nseg, uint32_t* res, hipStream_t s) {
+  hipLaunchKernelGGL(k_any_succ, dim3(grid((uint64_t)n + 1, KA_THREADS)), dim3(KA_THREADS), 0, s, src, head, pos, flg, minc, midx, n,
+                     nm, nxt_a, lab, mark);
+  // after round r the nodes up to 2^(r+1) - 1 steps behind b0 are marked; the chain has at most n nodes
+  for (uint64_t reach = 1; reach < n; reach <<= 1) {
+    hipLaunchKernelGGL(k_any_jump, dim3(grid((uint64_t)n + 1, KA_THREADS)), dim3(KA_THREADS), 0, s, nxt_a, nxt_b, mark, n);
+    std::swap(nxt_a, nxt_b);
+  }
+  hipLaunchKernelGGL(k_any_labels, dim3(grid(n, KA_THREADS)), dim3(KA_THREADS), 0, s, lab, mark, n, lbl);
+  hipError_t e = launch_scan_u32(lbl, rank, n, tmp, total, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_any_scatter, dim3(grid(n ? n : 1, KA_THREADS)), dim3(KA_THREADS), 0, s, src, head, pos, lab, mark, rank, total,
+                     n, index, nseg, res);
+  return hipGetLastError();
+}
+
+hipError_t launch_any_single(const uint64_t* head, uint64_t* index, uint32_t* res, hipStream_t s) {
+  hipLaunchKernelGGL(k_any_single, dim3(1), dim3(1), 0, s, head, index, res);
+  return hipGetLastError();
+}
+
+hipError_t launch_any_rows(const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends, uint32_t* starts,
+                           uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows, hipStream_t s) {
+  hipLaunchKernelGGL(k_any_depends, dim3(nseg), dim3(64), 0, s, info, tokens, depends, starts);
+  hipError_t e = launch_scan_u32(starts, excl, nseg, tmp, nrows, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_any_rows_a, dim3(grid(nseg, KA_THREADS)), dim3(KA_THREADS), 0, s, starts, excl, nrows, nseg, rows);
+  hipLaunchKernelGGL(k_any_rows_b, dim3(grid(nseg, KA_THREADS)), dim3(KA_THREADS), 0, s, starts, excl, nseg, rows);
+  return hipGetLastError();
+}
+
+}  // namespace sf
