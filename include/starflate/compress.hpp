@@ -284,6 +284,25 @@ class compressor {
     }
     return starflate::decompress(src, dst, container);
   }
+  /// decompress(src, dst, produced) for a raw, zlib or gzip stream (one member) with no index and no flush points, on the GPU
+  /// from block discovery to the last byte (sfh_inflate_stream): the status and, on Success, the bytes are container.hpp's
+  /// decompress(src, dst, container)'s, except that a zlib dst may be larger than the output (the Adler-32 covers the bytes
+  /// produced; container.hpp checks it over all of dst); *produced (may be null) = the bytes the body produced.  A problem on the device side
+  /// (no device, allocation) is DecompressStatus::Error; there is no host fallback.
+  auto decompress_stream(std::span<const std::byte> src, std::span<std::byte> dst, Container container, std::size_t* produced = nullptr)
+      -> DecompressStatus {
+    if (produced) *produced = 0;
+    if (!ctx_) return DecompressStatus::Error;
+    std::uint32_t st = 0;
+    std::uint64_t n = 0;
+    // (an empty dst still decodes: the size query is the C interface's, with a null dst)
+    std::byte dummy{};
+    void* d = dst.empty() ? static_cast<void*>(&dummy) : static_cast<void*>(dst.data());
+    const int rc = sfh_inflate_stream(ctx_, src.data(), src.size(), static_cast<std::uint32_t>(container), d, dst.size(), &n, &st);
+    if (rc != SFH_OK || st > 7) return DecompressStatus::Error;
+    if (produced) *produced = static_cast<std::size_t>(n);
+    return static_cast<DecompressStatus>(st);
+  }
   /// device pointers (src 16-byte aligned), optional hipStream_t
   auto compress_device(const void* d_src, std::size_t n, void* d_dst, std::size_t cap, const compress_options& opt = {},
                        void* stream = nullptr) -> compat::expected<std::size_t, CompressStatus> {

@@ -383,6 +383,34 @@ int sfh_decompress_any(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t con
  * counts[0] nodes (b0, markers, stored headers), counts[1] rows of dependent segments (0 when no decode ran) */
 int sfh_last_recover_stats(sfh_ctx* ctx, float ms[2], uint64_t counts[2]);
 
+/* One raw, zlib or gzip stream (one member) with no side information and no flush points, decoded on the GPU (DESIGN.md 3a,
+ * "Streams without flush points").  The body is cut at speculative dynamic-block starts every SFH_STREAM_CHUNK bytes (default
+ * 16384; the environment at sfh_create), the chunks are decoded lane-serially and chained: a chunk counts only when the chunk
+ * before it ends, without BFINAL, exactly on its start, so a wrong guess costs time and never changes a byte or a status.
+ * *status is what container.hpp's decompress(src, dst, container) returns for a dst of dst_cap bytes (raw: decompress(src,
+ * dst)), the first problem in stream order; *dst_n_out the bytes the body produced (on Success: dst[0, *dst_n_out) is the
+ * output).  One difference, on purpose: container.hpp takes a zlib dst to be exactly the output size and checks the Adler-32
+ * over all of it, so a larger dst is Error there; here the output size need not be known, and the Adler-32 is checked over the
+ * bytes produced (zlib's own rule) -- with dst_cap equal to the output size both agree.  A stream with no candidate block
+ * start (a Z_FIXED or level-0 stream) is decoded by one lane: slow, but correct.
+ * Size query: d_dst == NULL and dst_cap == 0 runs the candidate, count and chain steps only: *dst_n_out = the output size, and
+ * *status the wrapper's or the first structural problem of the body (the checks that need output positions -- distance <=
+ * bytes written, the capacity, the checksum -- are the decode call's).
+ * d_src 4-byte aligned, d_dst 16-byte aligned.  Host synchronisations of `stream` (NULL = the ctx's own): the wrapper, the
+ * candidates, each chain round, the write pass's statuses, the checksum.  Scratch: 2 bytes per output byte (the symbol plane),
+ * 64 KiB per group of about sqrt(chunks) chunks, 60 bytes per nominal chunk (sfh_last_decode_scratch_bytes).
+ * sfh_inflate_stream: host buffers (H2D, the same, D2H of dst when *status is 0); dst == NULL with dst_cap == 0 is the size query. */
+int sfh_inflate_stream_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint32_t container, void* d_dst, uint64_t dst_cap,
+                              uint64_t* dst_n_out, uint32_t* status, void* stream);
+int sfh_inflate_stream(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, void* dst, uint64_t dst_cap,
+                       uint64_t* dst_n_out, uint32_t* status);
+/* the last sfh_inflate_stream* call.  ms (profiling on, else zeros): SFH_STREAM_NSTAGES stages -- find, count (the first count
+ * pass and every repair round), write, resolve, checksum.  counts: [0] nominal chunks, [1] candidates (chunk 0 included), [2]
+ * confirmed chunks, [3] repair rounds, [4] the longest confirmed chunk's output bytes, [5] scratch bytes */
+#define SFH_STREAM_NSTAGES 5
+#define SFH_STREAM_NCOUNTS 6
+int sfh_last_stream_stats(sfh_ctx* ctx, float ms[SFH_STREAM_NSTAGES], uint64_t counts[SFH_STREAM_NCOUNTS]);
+
 /* bytes of decoder token scratch the last sfh_decompress* call on this ctx used (0 before the first) */
 size_t sfh_last_decode_scratch_bytes(const sfh_ctx* ctx);
 

@@ -308,6 +308,61 @@ class Compressor:
         self._check(self._lib.sfh_last_recover_stats(self._h, C.byref(ms), C.byref(cnt)))
         return {"scan_ms": ms[0], "walk_ms": ms[1], "nodes": cnt[0], "rows": cnt[1]}
 
+    # ---- one stream without side information or flush points (sfh_inflate_stream*) ----
+    def decompress_stream_tensor(self, stream, out_n=None, container="raw", out=None, hip_stream=None):
+        """stream: 1-D uint8 CUDA tensor -> (out tensor of the decoded bytes, DecompressStatus int), decoded on the GPU from
+        speculative block starts (no index, no flush points needed).  out_n: the output capacity (None: a size query first,
+        then exactly the output size); out: a uint8 CUDA tensor of at least out_n bytes.  Synchronises the stream."""
+        import torch
+
+        self._check_tensor(stream)
+        kind = _container(container)
+        s = torch.cuda.current_stream(stream.device).cuda_stream if hip_stream is None else hip_stream
+        st, n = C.c_uint32(0), C.c_uint64(0)
+        src = stream.data_ptr() if stream.numel() else None
+        if out_n is None:
+            self._check(self._lib.sfh_inflate_stream_device(self._h, src, stream.numel(), kind, None, 0, C.byref(n), C.byref(st),
+                                                            C.c_void_p(s)))
+            if st.value:
+                return stream[:0], st.value
+            out_n = n.value
+        out_n = int(out_n)
+        if out is None:
+            out = torch.empty(max(out_n, 1), dtype=torch.uint8, device=stream.device)
+        self._check_tensor(out)
+        if out.numel() < out_n or out.numel() == 0:
+            raise ValueError("out is smaller than out_n (or empty)")
+        # (always a real pointer: a null dst with a capacity of 0 is the C interface's size query, which checks no trailer)
+        self._check(self._lib.sfh_inflate_stream_device(self._h, src, stream.numel(), kind, out.data_ptr(), out_n, C.byref(n),
+                                                        C.byref(st), C.c_void_p(s)))
+        return (out[: n.value] if st.value == 0 else out[:0]), st.value
+
+    def decompress_stream(self, data, out_n=None, container="raw"):
+        """Host buffers: a bytes-like raw / zlib / gzip stream (one member) -> (bytes, DecompressStatus int), on the GPU with no
+        index and no flush points.  out_n: the output capacity (None: a size query first).  b"" unless the status is 0."""
+        src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        kind = _container(container)
+        st, n = C.c_uint32(0), C.c_uint64(0)
+        sp = src.ctypes.data if src.size else None
+        if out_n is None:
+            self._check(self._lib.sfh_inflate_stream(self._h, sp, src.size, kind, None, 0, C.byref(n), C.byref(st)))
+            if st.value:
+                return b"", st.value
+            out_n = n.value
+        out_n = int(out_n)
+        dst = np.empty(max(out_n, 1), dtype=np.uint8)
+        self._check(self._lib.sfh_inflate_stream(self._h, sp, src.size, kind, dst.ctypes.data, out_n, C.byref(n), C.byref(st)))
+        return (dst[: n.value].tobytes() if st.value == 0 else b""), st.value
+
+    def last_stream_stats(self):
+        """The last decompress_stream* call: per-stage ms (with profiling on, else zeros) and the chunk counts."""
+        ms = (C.c_float * 5)()
+        cnt = (C.c_uint64 * 6)()
+        self._check(self._lib.sfh_last_stream_stats(self._h, C.byref(ms), C.byref(cnt)))
+        names = ("find_ms", "count_ms", "write_ms", "resolve_ms", "checksum_ms")
+        keys = ("chunks", "candidates", "confirmed", "repair_rounds", "longest_chunk", "scratch_bytes")
+        return {**{k: ms[i] for i, k in enumerate(names)}, **{k: cnt[i] for i, k in enumerate(keys)}}
+
     # ---- many independent streams, each decoded into its own buffer, in one call (sfh_decompress_batch*) ----
     def decompress_batch(self, streams, sizes, index=None, subindex=None, block_bytes=None, container="raw"):
         """Host buffers: bytes-like streams and their decoded sizes -> (list of bytes, list of DecompressStatus ints).  index /
@@ -561,6 +616,18 @@ def decompress(data, out_n=None, container="raw", device=0):
     if c is None:
         c = _DEFAULT[device] = Compressor(device)
     out, st = c.decompress_any(data, out_n, container)
+    if st:
+        raise StarflateError(st, f"DecompressStatus {st}")
+    return out
+
+
+def decompress_stream(data, container="raw", out_n=None, device=0):
+    """One raw / zlib / gzip stream with no index and no flush points -> bytes, on the GPU (Compressor.decompress_stream).
+    A status other than Success raises StarflateError."""
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    out, st = c.decompress_stream(data, out_n, container)
     if st:
         raise StarflateError(st, f"DecompressStatus {st}")
     return out

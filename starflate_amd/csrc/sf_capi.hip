@@ -2,6 +2,7 @@
 // No torch types, no exceptions across the boundary; a ctx owns its device scratch.
 #include "../../include/starflate_hip.h"
 #include "sf_device.h"
+#include "sf_inflate_core.h"
 
 #include <dlfcn.h>
 #include <stdio.h>
@@ -98,6 +99,16 @@ struct sfh_ctx {
   hipEvent_t ev_any[5] = {};
   float any_ms[2] = {0, 0};
   uint64_t any_counts[2] = {0, 0};
+  // streams without flush points (sfh_inflate_stream*): candidates | chunk records | the redo list; the symbol plane; the
+  // composed windows of the resolve
+  uint64_t stream_chunk = 16384;  // SFH_STREAM_CHUNK=<bytes>: nominal chunk size S
+  uint8_t* d_stm = nullptr;
+  uint16_t* d_plane = nullptr;
+  uint16_t* d_wins = nullptr;
+  size_t d_stm_cap = 0, d_plane_cap = 0, d_wins_cap = 0;
+  hipEvent_t ev_stm[6] = {};
+  float stm_ms[SFH_STREAM_NSTAGES] = {};
+  uint64_t stm_counts[SFH_STREAM_NCOUNTS] = {};
   char err[256] = {0};
 };
 
@@ -770,7 +781,7 @@ inline size_t al16(size_t b) { return (b + 15) / 16 * 16; }
 // The wrapper, read by k_inflate_head as the batch decoder reads it: *wst its status, *isize gzip's ISIZE; the body [b0, e) lands
 // in any_head.  dst_n: the size the caller asks for (SFH_SIZE_FROM_TRAILER: ISIZE is taken).  Synchronises s.
 int any_wrapper(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t container, uint64_t dst_n, hipStream_t s, uint32_t* wst,
-                uint32_t* isize) {
+                uint32_t* isize, uint32_t* want = nullptr, uint64_t* body = nullptr) {
   if (!ctx->d_anysm) SF_HIP(hipMalloc(&ctx->d_anysm, kAnySmall), "hipMalloc");
   for (hipEvent_t& e : ctx->ev_any)
     if (!e) SF_HIP(hipEventCreate(&e), "event");
@@ -779,9 +790,11 @@ int any_wrapper(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t contain
   SF_HIP(hipMemcpyAsync(ctx->d_anysm, &it, sizeof it, hipMemcpyHostToDevice, s), "H2D wrapper row");
   SF_HIP(sf::launch_inflate_head((sf::InflateItem*)ctx->d_anysm, 1, container, nullptr, nullptr, s), "launch k_inflate_head");
   SF_HIP(hipMemcpyAsync(&it, ctx->d_anysm, sizeof it, hipMemcpyDeviceToHost, s), "D2H wrapper row");
+  if (body) SF_HIP(hipMemcpyAsync(body, any_head(ctx), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "D2H body");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
   *wst = it.wst;
   *isize = it.isize;
+  if (want) *want = it.want;
   return mark_call_end(ctx, s);
 }
 
@@ -934,6 +947,150 @@ int enqueue_any_decode(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t 
   return mark_call_end(ctx, s);
 }
 
+// ---- streams without flush points (sfh_inflate_stream*; sf_stream.hip) ----
+// query: steps A to C only.  stage: decode into ctx->d_out, grown to the output size (the host-buffer entry point).
+int stream_run(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t container, uint8_t* d_dst, uint64_t dst_cap, bool query,
+               bool stage, uint64_t* dst_n_out, uint32_t* status, hipStream_t s) {
+  const bool prof = ctx->profiling != 0;
+  for (float& m : ctx->stm_ms) m = 0;
+  for (uint64_t& c : ctx->stm_counts) c = 0;
+  *dst_n_out = 0;
+  *status = 0;
+  if (container == SFH_RAW && src_n == 0) {  // no header bits at all
+    *status = sf::inflate::kInvalidBlockHeader;
+    return SFH_OK;
+  }
+  for (hipEvent_t& e : ctx->ev_stm)
+    if (!e) SF_HIP(hipEventCreate(&e), "event");
+  uint32_t wst = 0, isize = 0, want = 0;
+  uint64_t body[2] = {0, 0};
+  // (container.hpp: a gzip dst below ISIZE is DstTooSmall; the size query has no dst yet)
+  int rc = any_wrapper(ctx, src, src_n, container, query ? ((uint64_t)1 << 44) : dst_cap, s, &wst, &isize, &want, body);
+  if (rc) return rc;
+  if (wst) {
+    *status = wst;
+    return SFH_OK;
+  }
+  const uint64_t b0 = body[0], body_n = body[1] - body[0], S = ctx->stream_chunk;
+  const uint64_t nc64 = body_n ? (body_n + S - 1) / S : 1;
+  if (nc64 >= ((uint64_t)1 << 31)) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 nominal chunks (SFH_STREAM_CHUNK)", hipSuccess);
+  const uint32_t nc = (uint32_t)nc64;
+  // cand u64[nc] | recs StreamChunk[nc] | list u32[nc]
+  const size_t o_rec = al16(8 * (size_t)nc), o_list = o_rec + al16(sizeof(sf::StreamChunk) * (size_t)nc);
+  if ((rc = grow(ctx, &ctx->d_stm, &ctx->d_stm_cap, o_list + al16(4 * (size_t)nc), "stream chunk records"))) return rc;
+  uint64_t* d_cand = (uint64_t*)ctx->d_stm;
+  sf::StreamChunk* d_rec = (sf::StreamChunk*)(ctx->d_stm + o_rec);
+  uint32_t* d_list = (uint32_t*)(ctx->d_stm + o_list);
+  std::vector<uint64_t> cand;
+  std::vector<sf::StreamChunk> rec;
+  try {
+    cand.resize(nc);
+    rec.reserve(nc);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory for the chunk records", hipSuccess);
+  }
+  // A: candidates
+  if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[0], s), "event");
+  SF_HIP(sf::launch_stream_find(src, src_n, b0, body_n, S, nc, d_cand, s), "launch k_stream_find");
+  if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[1], s), "event");
+  SF_HIP(hipMemcpyAsync(cand.data(), d_cand, 8 * (size_t)nc, hipMemcpyDeviceToHost, s), "D2H candidates");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  for (uint32_t c = 0; c < nc; ++c)
+    if (cand[c] != sf::kNoCandidate && (rec.empty() || cand[c] > rec.back().start))
+      rec.push_back(sf::StreamChunk{cand[c], 0, 0, 0, 0, 0, 0});
+  const uint32_t m = (uint32_t)rec.size();
+  for (uint32_t i = 0; i < m; ++i) rec[i].limit = i + 1 < m ? rec[i + 1].start : ~0ull;
+  // B and C: the count pass, then rounds of repairs until the chain from chunk 0 reaches its end
+  const size_t rec_bytes = sizeof(sf::StreamChunk) * (size_t)m;
+  SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
+  SF_HIP(sf::launch_stream_decode(false, src, src_n, b0, body_n, d_rec, nullptr, m, m, false, nullptr, 0, s), "launch k_stream_decode");
+  SF_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s), "D2H chunk records");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  uint32_t chain = 0, rounds = 0;
+  for (;;) {
+    const std::vector<uint32_t> redo = sf::stream_chain_round(rec, &chain);
+    if (redo.empty()) break;
+    ++rounds;
+    SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
+    SF_HIP(hipMemcpyAsync(d_list, redo.data(), 4 * redo.size(), hipMemcpyHostToDevice, s), "H2D repair list");
+    SF_HIP(sf::launch_stream_decode(false, src, src_n, b0, body_n, d_rec, d_list, (uint32_t)redo.size(), m, false, nullptr, 0, s),
+           "launch k_stream_decode");
+    // the first of them is behind the confirmed chain: it goes on through the run of broken links after it
+    SF_HIP(sf::launch_stream_decode(false, src, src_n, b0, body_n, d_rec, d_list, 1, m, true, nullptr, 0, s), "launch k_stream_decode");
+    SF_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s), "D2H chunk records");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+  }
+  if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[2], s), "event");
+  uint64_t total = 0, longest = 0;
+  for (uint32_t i = 0; i < chain; ++i) {
+    rec[i].base = total;
+    total += rec[i].out;
+    longest = std::max(longest, rec[i].out);
+  }
+  const uint32_t G = sf::stream_group(chain), ng = (chain + G - 1) / G;
+  const size_t wins = (size_t)(ng - 1) * 32768 * sizeof(uint16_t);
+  ctx->stm_counts[0] = nc;
+  ctx->stm_counts[1] = m;
+  ctx->stm_counts[2] = chain;
+  ctx->stm_counts[3] = rounds;
+  ctx->stm_counts[4] = longest;
+  ctx->stm_counts[5] = o_list + al16(4 * (size_t)nc) + (query ? 0 : 2 * total + wins);
+  ctx->last_dtok_bytes = ctx->stm_counts[5];
+  *dst_n_out = total;
+  if (query) {
+    *status = rec[chain - 1].status;
+    if (prof) SF_HIP(hipEventElapsedTime(&ctx->stm_ms[0], ctx->ev_stm[0], ctx->ev_stm[1]), "elapsed");
+    if (prof) SF_HIP(hipEventElapsedTime(&ctx->stm_ms[1], ctx->ev_stm[1], ctx->ev_stm[2]), "elapsed");
+    return mark_call_end(ctx, s);
+  }
+  // D: the exact pass into the symbol plane
+  const uint64_t cap = container == SFH_GZIP ? isize : dst_cap;  // (container.hpp decodes a gzip body into dst.first(ISIZE))
+  if ((rc = grow(ctx, &ctx->d_plane, &ctx->d_plane_cap, std::max<size_t>(16, 2 * total), "symbol plane"))) return rc;
+  if (wins && (rc = grow(ctx, &ctx->d_wins, &ctx->d_wins_cap, wins, "stream windows"))) return rc;
+  if (stage) {
+    if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, std::max<size_t>(16, total), "output staging"))) return rc;
+    d_dst = ctx->d_out;
+  }
+  SF_HIP(hipMemcpyAsync(d_rec, rec.data(), sizeof(sf::StreamChunk) * (size_t)chain, hipMemcpyHostToDevice, s), "H2D chunk records");
+  SF_HIP(sf::launch_stream_decode(true, src, src_n, b0, body_n, d_rec, nullptr, chain, chain, false, ctx->d_plane, cap, s), "launch k_stream_decode");
+  if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[3], s), "event");
+  SF_HIP(hipMemcpyAsync(rec.data(), d_rec, sizeof(sf::StreamChunk) * (size_t)chain, hipMemcpyDeviceToHost, s), "D2H chunk records");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  uint32_t st = 0;
+  for (uint32_t i = 0; i < chain && !st; ++i) st = rec[i].status;
+  if (!st && container == SFH_GZIP && total != isize) st = sf::inflate::kError;
+  if (!st) {
+    // E / F: the windows, and the bytes
+    SF_HIP(sf::launch_stream_resolve(ctx->d_plane, d_rec, chain, ctx->d_wins, d_dst, s), "launch k_stream_resolve");
+    if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[4], s), "event");
+    if (container) {
+      const uint32_t nch = chunks_of((size_t)total);
+      if ((rc = ensure_sums(ctx, nch))) return rc;
+      const uint8_t* sum_src = total ? d_dst : ctx->d_anysm;
+      SF_HIP(sf::launch_checksum(sum_src, total, nch, container, ctx->ws.sums, s), "launch k_checksum");
+      SF_HIP(sf::launch_wrap(ctx->ws.sums, nch, total, container, nullptr, nullptr, ctx->d_value, s), "launch k_wrap");
+      uint32_t got = 0;
+      SF_HIP(hipMemcpyAsync(&got, ctx->d_value, sizeof got, hipMemcpyDeviceToHost, s), "D2H checksum");
+      SF_HIP(hipStreamSynchronize(s), "stream sync");
+      if (got != want) st = sf::inflate::kError;
+    }
+    if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[5], s), "event");
+    if (prof) SF_HIP(hipEventSynchronize(ctx->ev_stm[5]), "event sync");
+  }
+  *status = st;
+  if (st) snprintf(ctx->err, sizeof ctx->err, "DecompressStatus %u", st);
+  if (prof) {
+    SF_HIP(hipEventElapsedTime(&ctx->stm_ms[0], ctx->ev_stm[0], ctx->ev_stm[1]), "elapsed");
+    SF_HIP(hipEventElapsedTime(&ctx->stm_ms[1], ctx->ev_stm[1], ctx->ev_stm[2]), "elapsed");
+    SF_HIP(hipEventElapsedTime(&ctx->stm_ms[2], ctx->ev_stm[2], ctx->ev_stm[3]), "elapsed");
+    if (!st) {
+      SF_HIP(hipEventElapsedTime(&ctx->stm_ms[3], ctx->ev_stm[3], ctx->ev_stm[4]), "elapsed");
+      SF_HIP(hipEventElapsedTime(&ctx->stm_ms[4], ctx->ev_stm[4], ctx->ev_stm[5]), "elapsed");
+    }
+  }
+  return mark_call_end(ctx, s);
+}
+
 int check_any(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, uint64_t dst_n, bool dev) {
   if (!ctx) return SFH_E_INVALID_ARG;
   if ((!src && src_n) || container > SFH_GZIP) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
@@ -1051,6 +1208,8 @@ int sfh_create(sfh_ctx** out, int device) {
     ctx->force_order_fail = (f && f[0] == '1');
     const char* q = getenv("SFH_INFLATE_SERIAL");
     ctx->inflate_serial = (q && q[0] == '1');
+    const char* sc = getenv("SFH_STREAM_CHUNK");
+    if (sc && atoll(sc) > 0) ctx->stream_chunk = (uint64_t)atoll(sc);
   }
   hipError_t e;
   if ((e = hipSetDevice(device)) != hipSuccess || (e = hipStreamCreate(&ctx->stream)) != hipSuccess ||
@@ -1119,6 +1278,11 @@ void sfh_destroy(sfh_ctx* ctx) {
   (void)hipFree(ctx->d_anyseg);
   (void)hipFree(ctx->d_anyix);
   for (hipEvent_t e : ctx->ev_any)
+    if (e) (void)hipEventDestroy(e);
+  (void)hipFree(ctx->d_stm);
+  (void)hipFree(ctx->d_plane);
+  (void)hipFree(ctx->d_wins);
+  for (hipEvent_t e : ctx->ev_stm)
     if (e) (void)hipEventDestroy(e);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -1667,6 +1831,46 @@ int sfh_last_recover_stats(sfh_ctx* ctx, float ms[2], uint64_t counts[2]) {
   ms[1] = ctx->any_ms[1];
   counts[0] = ctx->any_counts[0];
   counts[1] = ctx->any_counts[1];
+  return SFH_OK;
+}
+
+int sfh_inflate_stream_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint32_t container, void* d_dst, uint64_t dst_cap,
+                              uint64_t* dst_n_out, uint32_t* status, void* stream) {
+  if (!ctx) return SFH_E_INVALID_ARG;
+  if ((!d_src && src_n) || container > SFH_GZIP || !dst_n_out || !status || (!d_dst && dst_cap))
+    return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  if (((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & 15))
+    return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, dst 16)", hipSuccess);
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();  // see enqueue()
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  return stream_run(ctx, (const uint8_t*)d_src, src_n, container, (uint8_t*)d_dst, dst_cap, !d_dst, false, dst_n_out, status, s);
+}
+
+int sfh_inflate_stream(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, void* dst, uint64_t dst_cap,
+                       uint64_t* dst_n_out, uint32_t* status) {
+  if (!ctx) return SFH_E_INVALID_ARG;
+  if ((!src && src_n) || container > SFH_GZIP || !dst_n_out || !status || (!dst && dst_cap))
+    return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, src_n ? src_n : 16, "input staging");
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
+  if (src_n) SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, s), "H2D");
+  const bool query = !dst;
+  if ((rc = stream_run(ctx, ctx->d_in, src_n, container, nullptr, dst_cap, query, !query, dst_n_out, status, s))) return rc;
+  if (!query && *status == 0 && *dst_n_out) {
+    SF_HIP(hipMemcpyAsync(dst, ctx->d_out, *dst_n_out, hipMemcpyDeviceToHost, s), "D2H");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+  }
+  return SFH_OK;
+}
+
+int sfh_last_stream_stats(sfh_ctx* ctx, float ms[SFH_STREAM_NSTAGES], uint64_t counts[SFH_STREAM_NCOUNTS]) {
+  if (!ctx || !ms || !counts) return SFH_E_INVALID_ARG;
+  for (int k = 0; k < SFH_STREAM_NSTAGES; ++k) ms[k] = ctx->stm_ms[k];
+  for (int k = 0; k < SFH_STREAM_NCOUNTS; ++k) counts[k] = ctx->stm_counts[k];
   return SFH_OK;
 }
 

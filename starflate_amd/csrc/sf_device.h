@@ -28,6 +28,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
+#include "sf_stream_chain.h"
+
 namespace sf {
 
 constexpr uint32_t kChunk = 32768;      // bytes per DEFLATE block (byte-aligned in the stream)
@@ -317,6 +321,19 @@ hipError_t launch_inflate_head(InflateItem* items, uint32_t nitems, uint32_t con
                                hipStream_t s);
 hipError_t launch_inflate_fold(const InflateItem* items, uint32_t nitems, const SegInfo* info, const uint32_t* sums,
                                uint32_t container, uint32_t* status, hipStream_t s);
+
+// sf_stream.hip: a stream without flush points (sfh_inflate_stream*); StreamChunk and the chain round: sf_stream_chain.h
+constexpr uint64_t kNoCandidate = ~0ull;
+hipError_t launch_stream_find(const uint8_t* src, uint64_t src_n, uint64_t b0, uint64_t body_n, uint64_t step_bytes, uint32_t nc,
+                              uint64_t* cand, hipStream_t s);
+// list (nullable: 0..n-1): the records to decode.  follow: list[0] goes on into the records after it while their links break
+// (m: the record count; see k_stream_decode).  write: the exact pass into plane (cap: the output capacity)
+hipError_t launch_stream_decode(bool write, const uint8_t* src, uint64_t src_n, uint64_t b0, uint64_t body_n, StreamChunk* recs,
+                                const uint32_t* list, uint32_t n, uint32_t m, bool follow, uint16_t* plane, uint64_t cap,
+                                hipStream_t s);
+uint32_t stream_group(uint32_t n);  // chunks per group of the resolve; tables: (groups - 1) * 32768 u16
+hipError_t launch_stream_resolve(const uint16_t* plane, const StreamChunk* recs, uint32_t n, uint16_t* tables, uint8_t* dst,
+                                 hipStream_t s);
 
 // sf_guard.hip: does the LDS execute a returning atomic's lanes in ascending order (op 0: ds_wrxchg_rtn_b32, 1: ds_mskor_rtn_b32)?
 // d_result[0] = mismatches against the sequential model, [1] = positions checked

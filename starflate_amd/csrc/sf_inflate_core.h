@@ -368,6 +368,97 @@ SF_HD uint32_t read_lengths(BitReader& br, uint8_t* m, uint32_t type) {
   return kOk;
 }
 
+// The code-length code of a dynamic header, shared by dynamic_header_candidate and the stream decoder's serial_dynamic
+// (sf_stream.hip): HCLEN 3-bit lengths in the RFC 1951 order (the caller has checked that the bits are there) -> 19 x 3 bits;
+// its Kraft sum in units of 2^-7; and its 7-bit lookup table, (symbol << 3) | code bits, 0 = no code.
+SF_HD uint64_t read_cl_lengths(BitReader& br, uint32_t hclen) {
+  uint64_t clp = 0;
+  _Pragma("nounroll") for (uint32_t k = 0; k < hclen; ++k) {
+    br.refill();
+    const uint32_t order = k < 3 ? 16 + k : k == 3 ? 0 : (k & 1) ? 8 - ((k - 3) >> 1) : 8 + ((k - 4) >> 1);
+    clp |= (uint64_t)br.get(3) << (3 * order);
+  }
+  return clp;
+}
+SF_HD uint32_t cl_kraft(uint64_t clp) {
+  uint32_t kraft = 0;
+  _Pragma("nounroll") for (uint32_t s = 0; s < 19; ++s) {
+    const uint32_t l = (uint32_t)(clp >> (3 * s)) & 7u;
+    kraft += l ? 128u >> l : 0u;
+  }
+  return kraft;
+}
+SF_HD void build_cl_lut(uint64_t clp, uint8_t* lut) {
+  _Pragma("nounroll") for (uint32_t e = 0; e < 128; ++e) lut[e] = 0;
+  uint32_t code = 0;
+  _Pragma("nounroll") for (uint32_t l = 1; l <= 7; ++l) {
+    _Pragma("nounroll") for (uint32_t s = 0; s < 19; ++s)
+      if (((clp >> (3 * s)) & 7u) == l) {
+        const uint32_t rev = bit_reverse(code & ((1u << l) - 1u), l);
+        _Pragma("nounroll") for (uint32_t e = rev; e < 128; e += 1u << l) lut[e] = (uint8_t)((s << 3) | l);
+        ++code;
+      }
+    code <<= 1;
+  }
+}
+
+// Block-start candidate (sf_stream.hip, DESIGN.md 3a "Streams without flush points"): does a strict dynamic-block header
+// parse at the reader's position?  BFINAL = 0 and BTYPE = 2; HLIT <= 286 and HDIST <= 30; a complete code-length code; the
+// literal/length and the distance lengths decode as two sequences, as the serial decoder reads them (no repeat at index 0 of
+// either, no run past the end of either); a complete literal/length code in which 256 has a code; a complete distance code
+// or exactly one distance code, of length 1.  `lut`: 128 bytes of scratch.  True only means "may be a block start": the
+// chain of sf_stream.hip decides; a missed start only makes a chunk longer.
+SF_HD bool dynamic_header_candidate(BitReader& br, uint8_t* lut) {
+  br.refill();
+  if (br.bitpos + 17 > br.nbits) return false;
+  if (br.get(3) != 4u) return false;  // BFINAL 0, BTYPE 2
+  const uint32_t hlit = br.get(5), hdist = br.get(5), hclen = br.get(4) + 4;
+  if (hlit > 29 || hdist > 29) return false;
+  if (br.bitpos + 3 * hclen > br.nbits) return false;
+  const uint64_t clp = read_cl_lengths(br, hclen);
+  if (cl_kraft(clp) != 128u) return false;
+  build_cl_lut(clp, lut);
+  uint32_t kl = 0, kd = 0, nd = 0;
+  bool has_eob = false;
+  _Pragma("nounroll") for (uint32_t seq = 0; seq < 2; ++seq) {
+    const uint32_t n = seq ? hdist + 1 : hlit + 257;
+    uint32_t i = 0, prev = 0;
+    while (i < n) {
+      br.refill();
+      if (br.overrun()) return false;
+      const uint32_t e = lut[br.peek(7)];  // never 0: the code is complete
+      br.drop(e & 7u);
+      const uint32_t sym = e >> 3;
+      uint32_t val = sym, rep = 1;
+      if (sym == 16) {
+        if (i == 0) return false;
+        val = prev;
+        rep = 3 + br.get(2);
+      } else if (sym == 17) {
+        val = 0;
+        rep = 3 + br.get(3);
+      } else if (sym == 18) {
+        val = 0;
+        rep = 11 + br.get(7);
+      }
+      if (i + rep > n) return false;
+      if (val) {
+        if (seq == 0) {
+          kl += (32768u >> val) * rep;
+          if (i <= 256 && 256 < i + rep) has_eob = true;
+        } else {
+          kd += (32768u >> val) * rep;
+          nd += rep;
+        }
+      }
+      prev = val;
+      i += rep;
+    }
+  }
+  if (br.overrun()) return false;
+  return kl == 32768u && has_eob && (kd == 32768u || (nd == 1 && kd == 16384u));
+}
+
 template <class L>
 SF_HD uint32_t read_tables(BitReader& br, uint8_t* m, uint32_t type) {
   const uint32_t st = read_lengths<L>(br, m, type);
