@@ -9,13 +9,17 @@ byte-aligned streams are concatenated on rank 0 over RCCL.  For N > 1 the shardi
 rounds (global piece g = k*N + rank), so the gather of round k (sizes all_gather + one point-to-point send per
 rank, straight to the final offset) overlaps the compression of round k+1 (starflate_amd/multigpu.py).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--bytes B] [--workload text|random|mixed] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--bytes B] [--workload text|random|mixed] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (k_lz77), its launch time measured live
-with HIP events on the launch stream; `cpu_baseline` times the oracle's restatement of the reference
-decompress() on this host; `e2e` is the same call from pinned host buffers (H2D + kernels + D2H); `workloads`
-carries the other two BASELINE workloads at a smaller size (N = 1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the
+headline: MiB/s, ms_per_step, the stream's size and ratio, and (N = 1) the per-kernel times of the timed steps.
+
+--full adds everything else, each leg after the timed steps: the zlib round trip of the streams, the ratio against
+zlib -6, `roofline` for the dominant kernel (k_lz77, its launch time measured live with HIP events on the launch stream),
+`cpu_baseline` (the oracle's restatement of the reference decompress() on this host), `e2e` (the same call from pinned
+host buffers: H2D + kernels + D2H), the GPU `decompress` leg, the other BASELINE workloads and the real-bytes workloads at
+a smaller size (N = 1 only), `multi_gpu` (N > 1), and --sweep.
 """
 import argparse
 import json
@@ -394,6 +398,37 @@ def assemble_line(head, kernel_ms, roofline, cpu, e2e, decomp, real_bytes, multi
     return line
 
 
+def headline(args, corpus, wl, n, world, K, multi, bb, value, ms_per_step, ratio, total_out, checks=None):
+    """The head of the line, plain or --full: the contract's keys, the run's configuration, the stream's size and ratio;
+    `checks` (--full): ratio_zlib6, ratio_vs_zlib6, roundtrip_ok."""
+    metric = "compress MiB/s + ratio vs zlib -6, 1 GiB synthetic; 1/2/4/8 GPU"
+    if corpus:  # not BASELINE.json's workload any more: the line says so where a reader looks first
+        tiled = os.path.getsize(corpus) < n
+        metric = (f"compress MiB/s + ratio vs zlib -6 on {n / 2**30:g} GiB of FILE {os.path.basename(corpus)}"
+                  + (" (shorter than that: repeated; the ratio is taken on the first 64 MiB at most)" if tiled else ""))
+    head = {
+        "metric": metric,
+        "value": round(value, 1), "unit": "MiB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u8", "data": f"file:{os.path.basename(corpus)}" if corpus else "synthetic",
+        "config": {"workload": wl, "effort": args.effort, "block_bytes": bb, "deflate_block_bytes": SEG, "window_bytes": 32768, "strategy": "auto",
+                   "container": args.container,
+                   "parallelism": f"shard{world}" + (f" block-cyclic x{K}, gather overlapped" if multi else "")},
+        "ratio": round(ratio, 4), "compressed_bytes": total_out,
+    }
+    head.update(checks or {})
+    return head
+
+
+def rehearsal_headline(args, world, K, wl, value, ms_per_step, compressor, total_out):
+    """The head of a --backend gloo line: says it is no measurement."""
+    return {"metric": "REHEARSAL of the N > 1 path on CPU (gloo, stand-in compressor) -- not a measurement",
+            "value": round(value, 1), "unit": "MiB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 3), "rehearsal": True, "backend": "gloo", "compressor": compressor,
+            "config": {"workload": wl, "parallelism": f"shard{world} block-cyclic x{K}"},
+            "compressed_bytes": total_out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -403,6 +438,9 @@ def main():
     ap.add_argument("--workload", default="text", choices=["text", "random", "mixed", "runs"])
     ap.add_argument("--effort", default="default", choices=["default", "fast", "fastest", "thorough", "max", "best", "ultra", "extreme", "recent", "recent_all"], help="sfh_options.effort of the timed steps")
     ap.add_argument("--block-bytes", type=int, default=0, help="sfh_options.block_bytes (0 = the library's default: 512 KiB at 1 GiB, 1 MiB with the chain efforts)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also verify, compare and measure everything else (see the module's docstring); "
+                         "the --no-* options, --sweep, --cpu-sample-bytes and --secondary-bytes shape this")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the e2e leg, the other BASELINE workloads and the real-bytes workloads")
@@ -429,15 +467,17 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.sweep and not args.full:
+        ap.error("--sweep is part of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
 
-    # what ties this run to kernel sources (commit + SHA-256): taken ONCE, here -- before torch or anything else has touched
-    # the GPU, so the `git` children it starts are not children of a GPU process (nor of a profiler's preloaded library)
+    # what ties this run to kernel sources (commit + SHA-256), for --full's roofline: taken ONCE, here -- before torch or anything
+    # else has touched the GPU, so the `git` children it starts are not children of a GPU process (nor of a profiler's preloaded library)
     from starflate_amd.build import source_stamp
 
-    stamp = source_stamp()
+    stamp = source_stamp() if args.full else None
 
     import numpy as np
     import torch
@@ -562,6 +602,29 @@ def main():
         dump_outputs(args.dump_outputs, result["out"], result["total"])
 
     ms_per_step = dt / args.steps * 1e3
+    total_in = n * world
+    value = total_in * args.steps / dt / 2**20
+    total_out = int(result["total"])
+    local_n = int(result["local_n"])
+    ratio = n / max(local_n, 1)
+
+    if not args.full:
+        # a plain run: the headline and what the timed steps recorded themselves (the async N > 1 path keeps no per-kernel times)
+        if rank == 0:
+            if rehearsal:
+                line = rehearsal_headline(args, world, K, wl, value, ms_per_step, comp.name, total_out)
+            else:
+                line = headline(args, corpus, wl, n, world, K, multi, bb, value, ms_per_step, ratio, total_out)
+                if stage_acc:
+                    kernel_ms = {k: sum(v) / len(v) for k, v in stage_acc.items()}
+                    line["kernel_ms"] = {k: round(v, 4) for k, v in kernel_ms.items()}
+                    line["kernels_total_ms"] = round(sum(kernel_ms.values()), 4)
+            print(json.dumps(line), flush=True)
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # ---- N > 1: what the record needs to be read without DESIGN.md -- who took part, what the gather cost, what was expected ----
     multi_info = None
     if multi:
@@ -581,10 +644,6 @@ def main():
         fence()
         multi_info = {"ranks_seen": dist.get_world_size(), "distinct_devices": len(set(seen)), "devices": seen,
                       "gather_ms_per_round": timing.get("gather_ms"), "rounds": K}
-    total_in = n * world
-    value = total_in * args.steps / dt / 2**20
-    total_out = int(result["total"])
-    local_n = int(result["local_n"])
 
     # ---- verification (untimed): every rank inflates its own piece streams with zlib ----
     ok = None
@@ -606,13 +665,11 @@ def main():
         dist.destroy_process_group()
         return
     if rehearsal:
-        print(json.dumps({"metric": "REHEARSAL of the N > 1 path on CPU (gloo, stand-in compressor) -- not a measurement",
-                          "value": round(value, 1), "unit": "MiB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                          "ms_per_step": round(ms_per_step, 3), "rehearsal": True, "backend": "gloo", "compressor": comp.name,
-                          "config": {"workload": wl, "parallelism": f"shard{world} block-cyclic x{K}"},
-                          "compressed_bytes": total_out, "roundtrip_ok": ok,
-                          "multi_gpu": dict(multi_info, gather_ms_per_step=round(sum(multi_info["gather_ms_per_round"] or [0.0]), 4),
-                                            prediction=predict_scaling(world, K, ms_per_step, local_n))}), flush=True)
+        line = rehearsal_headline(args, world, K, wl, value, ms_per_step, comp.name, total_out)
+        line["roundtrip_ok"] = ok
+        line["multi_gpu"] = dict(multi_info, gather_ms_per_step=round(sum(multi_info["gather_ms_per_round"] or [0.0]), 4),
+                                 prediction=predict_scaling(world, K, ms_per_step, local_n))
+        print(json.dumps(line), flush=True)
         dist.barrier()
         dist.destroy_process_group()
         return
@@ -633,7 +690,6 @@ def main():
     nchunks = (last.numel() + SEG - 1) // SEG
     offs = comp.debug(_capi.DBG_OFFSETS, nchunks)  # chunk offsets of the last call (no extra launch)
     ours_sample = int(offs[zs // SEG]) if zs < last.numel() else last_n
-    ratio = n / max(local_n, 1)
     ratio_zlib6 = zs / zlen
     ratio_ours_sample = zs / ours_sample
 
@@ -820,23 +876,8 @@ def main():
                                                       "ratio": round(zs / zpar, 4)}
         ok = good if ok is None else (ok and good)
 
-    metric = "compress MiB/s + ratio vs zlib -6, 1 GiB synthetic; 1/2/4/8 GPU"
-    if corpus:  # not BASELINE.json's workload any more: the line says so where a reader looks first
-        tiled = os.path.getsize(corpus) < n
-        metric = (f"compress MiB/s + ratio vs zlib -6 on {n / 2**30:g} GiB of FILE {os.path.basename(corpus)}"
-                  + (" (shorter than that: repeated; the ratio is taken on the first 64 MiB at most)" if tiled else ""))
-    head = {
-        "metric": metric,
-        "value": round(value, 1), "unit": "MiB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u8", "data": f"file:{os.path.basename(corpus)}" if corpus else "synthetic",
-        "config": {"workload": wl, "effort": args.effort, "block_bytes": bb, "deflate_block_bytes": SEG, "window_bytes": 32768, "strategy": "auto",
-                   "container": args.container,
-                   "parallelism": f"shard{world}" + (f" block-cyclic x{K}, gather overlapped" if multi else "")},
-        "ratio": round(ratio, 4), "ratio_zlib6": round(ratio_zlib6, 4),
-        "ratio_vs_zlib6": round(ratio_ours_sample / ratio_zlib6, 4),
-        "compressed_bytes": total_out, "roundtrip_ok": ok,
-    }
+    head = headline(args, corpus, wl, n, world, K, multi, bb, value, ms_per_step, ratio, total_out,
+                    checks={"ratio_zlib6": round(ratio_zlib6, 4), "ratio_vs_zlib6": round(ratio_ours_sample / ratio_zlib6, 4), "roundtrip_ok": ok})
     mg = None
     if multi_info is not None:
         # RCCL saw these devices; the gather of one step as measured (events around each round's transfers on rank 0) beside

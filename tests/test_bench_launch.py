@@ -25,7 +25,7 @@ def _run(*extra, env=None):
 @pytest.mark.parametrize("gpus,container", [(2, "raw"), (3, "gzip")])
 def test_bench_self_launch_gloo(gpus, container):
     r = _run("--gpus", str(gpus), "--backend", "gloo", "--bytes", str(1 << 20), "--rounds", "2", "--steps", "2", "--warmup", "1",
-             "--container", container)
+             "--container", container, "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout  # ONE JSON line, from rank 0 only
@@ -39,6 +39,25 @@ def test_bench_self_launch_gloo(gpus, container):
     pr = m["prediction"]
     assert {"model", "T_c_ms", "T_x_ms", "predicted_step_ms", "predicted_efficiency", "bound"} <= set(pr)
     assert 0 < pr["predicted_efficiency"] <= 1 and pr["T_x_ms"] > 0
+
+
+# what only --full measures or checks: a plain run's line carries none of it
+FULL_ONLY = ("roundtrip_ok", "ratio_zlib6", "ratio_vs_zlib6", "roofline", "cpu_baseline", "e2e", "decompress", "real_bytes", "runs",
+             "multi_gpu", "configs", "sweep_file")
+
+
+def test_bench_plain_run_is_lean():
+    """Without --full the line is the headline of the timed steps alone; --sweep belongs to --full."""
+    r = _run("--gpus", "2", "--backend", "gloo", "--bytes", str(1 << 20), "--rounds", "2", "--steps", "2", "--warmup", "1")
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["rehearsal"] is True and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["compressed_bytes"] > 0 and d["unit"] == "MiB/s"
+    assert not set(FULL_ONLY) & set(d), sorted(set(FULL_ONLY) & set(d))
+    r = _run("--gpus", "2", "--backend", "gloo", "--bytes", str(1 << 20), "--sweep", "x.json")
+    assert r.returncode != 0 and "--full" in r.stderr
 
 
 def _check_dump(d, dump):
@@ -89,7 +108,7 @@ def test_bench_input_file(tmp_path):
     # a "corpus" shorter than --bytes is tiled; found through $STARFLATE_CORPUS_DIR
     p = tmp_path / "alice29.txt"
     p.write_bytes(b"Alice was beginning to get very tired of sitting by her sister on the bank. " * 700)
-    r = _run("--gpus", "2", "--backend", "gloo", "--bytes", str(1 << 18), "--rounds", "1", "--steps", "1", "--warmup", "0",
+    r = _run("--gpus", "2", "--backend", "gloo", "--bytes", str(1 << 18), "--rounds", "1", "--steps", "1", "--warmup", "0", "--full",
              env={"STARFLATE_CORPUS_DIR": str(tmp_path)})
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip())
@@ -200,6 +219,32 @@ def test_bench_line_layout_and_size():
 
 
 @pytest.mark.gpu
+def test_bench_plain_line_on_the_gpu(tmp_path, compressor):
+    """The plain command at a reduced size: the contract's keys and the timed steps' per-kernel times, none of --full's legs, and
+    --dump-outputs writes what the same input compressed gives."""
+    import numpy as np
+
+    from starflate_amd import synth
+
+    dump = tmp_path / "dump"
+    r = _run("--gpus", "1", "--bytes", str(64 << 20), "--steps", "2", "--warmup", "1", "--dump-outputs", str(dump))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("compress MiB/s") and d["unit"] == "MiB/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 2 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert abs(d["value"] - (64 << 20) / (d["ms_per_step"] * 1e-3) / 2**20) <= 0.01 * d["value"]
+    assert "k_lz77" in d["kernel_ms"] and d["kernels_total_ms"] > 0 and d["ratio"] > 1
+    assert not set(FULL_ONLY) & set(d), sorted(set(FULL_ONLY) & set(d))
+    files = _check_dump(d, dump)
+    out, n = compressor.compress_tensor(synth.gen_text_torch(64 << 20, seed=3, device="cuda"), block_bytes=d["config"]["block_bytes"])
+    assert n == d["compressed_bytes"]
+    pos = files["stream_positions.npy"].astype(np.int64)
+    assert np.array_equal(out[:n].cpu().numpy()[pos], files["stream.npy"].astype(np.uint8))
+
+
+@pytest.mark.gpu
 def test_bench_line_on_the_gpu_is_compact(tmp_path, compressor):
     """The real command at a reduced size: one line under the driver's 8 KB, `configs` last with config[3]'s bytes and config[4], and --sweep
     writes its table to a file instead of the line.  --dump-outputs samples the timed step's stream: the bytes a compress of the same
@@ -210,7 +255,7 @@ def test_bench_line_on_the_gpu_is_compact(tmp_path, compressor):
 
     sweep, dump = tmp_path / "sweep.json", tmp_path / "dump"
     r = _run("--bytes", str(64 << 20), "--secondary-bytes", str(32 << 20), "--cpu-sample-bytes", str(16 << 20), "--steps", "2", "--warmup", "1",
-             "--dump-outputs", str(dump))
+             "--dump-outputs", str(dump), "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and len(lines[0]) < 8192, len(lines[0])
@@ -225,7 +270,8 @@ def test_bench_line_on_the_gpu_is_compact(tmp_path, compressor):
     assert d["roofline"]["frac"] > 0 and d["cpu_baseline"]["value"] > 0 and d["decompress"]["sub_indexed"]["equal_to_input"]
     assert d["configs"]["config4_random"]["roofline"]["frac"] > 0.05 and d["configs"]["config4_random"]["ratio"] < 1.001
     assert "real_source" in d["real_bytes"] and "real_binary_effort_recent_all" in d["real_bytes"]
-    r = _run("--bytes", str(32 << 20), "--secondary-bytes", str(32 << 20), "--no-cpu-baseline", "--no-decompress", "--steps", "1", "--warmup", "1", "--sweep", str(sweep))
+    r = _run("--bytes", str(32 << 20), "--secondary-bytes", str(32 << 20), "--no-cpu-baseline", "--no-decompress", "--steps", "1", "--warmup", "1", "--sweep", str(sweep),
+             "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip())
     assert len(r.stdout.strip()) < 8192 and d["sweep_file"] == str(sweep) and list(d)[-1] == "configs"

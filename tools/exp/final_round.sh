@@ -4,7 +4,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $out/pytest.log 2>&1; ec
 tail -3 $out/pytest.log
 bash tools/prof_round.sh ${2:-r06} > $out/prof.log 2>&1; echo "prof rc $?"; tail -12 $out/prof.log
 cp gpurun_out/prof_${2:-r06}/pmc_traffic.json profiles/pmc_traffic.json
-timeout -k 10 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc $?"; python - $out/bench.json <<'PY'
+timeout -k 10 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc $?"; python - $out/bench.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print({k: d[k] for k in ("value", "ms_per_step", "ratio_vs_zlib6", "kernel_ms", "roundtrip_ok")})

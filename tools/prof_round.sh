@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 tag=${1:-r01}
 out=gpurun_out/prof_$tag
 rm -rf $out; mkdir -p $out
-CMD="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-secondary"
+CMD="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-secondary --full"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- $CMD > $out/kt.log 2>&1
 bash tools/pmc_run.sh $out/pmc_fetch 400 "FETCH_SIZE" -- $CMD > $out/pmc_fetch.log 2>&1
 bash tools/pmc_run.sh $out/pmc_write 400 "WRITE_SIZE" -- $CMD > $out/pmc_write.log 2>&1
