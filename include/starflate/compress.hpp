@@ -303,6 +303,40 @@ class compressor {
     if (produced) *produced = static_cast<std::size_t>(n);
     return static_cast<DecompressStatus>(st);
   }
+  /// decompress_stream() on many streams in one call (sfh_inflate_stream_batch): srcs[i] into dsts[i], its status into
+  /// statuses[i] and, when `produced` is not empty, the bytes its body produced into produced[i] -- for every item exactly what
+  /// decompress_stream(srcs[i], dsts[i], container) gives on it alone.  dsts[i] is written only where statuses[i] is Success
+  /// (or the checksum did not match).  A refused call (arguments) is the return value, the statuses then not written; a
+  /// problem on the device side (no device, allocation) is returned as well and makes every status Error.  No host fallback.
+  auto decompress_stream_batch(std::span<const std::span<const std::byte>> srcs, std::span<const std::span<std::byte>> dsts,
+                               Container container, std::span<DecompressStatus> statuses, std::span<std::size_t> produced = {})
+      -> CompressStatus {
+    const std::size_t k = srcs.size();
+    if (dsts.size() != k || statuses.size() != k || (!produced.empty() && produced.size() != k)) return CompressStatus::InvalidArgument;
+    if (!ctx_) {
+      for (auto& st : statuses) st = DecompressStatus::Error;
+      return init_;
+    }
+    std::vector<const void*> sp(k);
+    std::vector<void*> dp(k);
+    std::vector<std::uint64_t> n(k), cap(k), out(k);
+    std::vector<std::uint32_t> st(k);
+    static std::byte dummy{};  // (an empty dst still decodes: a null one is the C interface's size query)
+    for (std::size_t i = 0; i < k; ++i) {
+      sp[i] = srcs[i].data();
+      n[i] = srcs[i].size();
+      dp[i] = dsts[i].empty() ? static_cast<void*>(&dummy) : static_cast<void*>(dsts[i].data());
+      cap[i] = dsts[i].size();
+    }
+    const int rc = sfh_inflate_stream_batch(ctx_, k, sp.data(), n.data(), static_cast<std::uint32_t>(container), dp.data(), cap.data(),
+                                            out.data(), st.data());
+    if (rc == SFH_E_INVALID_ARG) return CompressStatus::InvalidArgument;
+    for (std::size_t i = 0; i < k; ++i) {
+      statuses[i] = (rc != SFH_OK || st[i] > 7) ? DecompressStatus::Error : static_cast<DecompressStatus>(st[i]);
+      if (!produced.empty()) produced[i] = rc == SFH_OK ? static_cast<std::size_t>(out[i]) : 0;
+    }
+    return rc == SFH_OK ? CompressStatus::Success : detail::to_status(rc);
+  }
   /// device pointers (src 16-byte aligned), optional hipStream_t
   auto compress_device(const void* d_src, std::size_t n, void* d_dst, std::size_t cap, const compress_options& opt = {},
                        void* stream = nullptr) -> compat::expected<std::size_t, CompressStatus> {

@@ -404,7 +404,31 @@ int sfh_inflate_stream_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uin
                               uint64_t* dst_n_out, uint32_t* status, void* stream);
 int sfh_inflate_stream(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, void* dst, uint64_t dst_cap,
                        uint64_t* dst_n_out, uint32_t* status);
-/* the last sfh_inflate_stream* call.  ms (profiling on, else zeros): SFH_STREAM_NSTAGES stages -- find, count (the first count
+/* Many such streams in one call, each decoded into its own buffer.  For every item i, status[i], dst_n_out[i] and, on status 0,
+ * the bytes dsts[i][0, dst_n_out[i]) are exactly what sfh_inflate_stream_device returns for that item alone with dst_cap[i]
+ * (container: the same for every item).  One item's failure changes no other item's bytes or status; nothing is written
+ * outside [dsts[i], dsts[i] + dst_cap[i]), and an item's destination only on its status 0 (or after a checksum mismatch).
+ * dst_n_out and status are host arrays; the call synchronises `stream` (NULL = the ctx's own).  Size query: d_dsts == NULL
+ * (dst_cap may then be NULL) runs the candidate, count and chain steps for every item; an item whose dsts[i] is NULL is a size
+ * query of its own.  Refused with SFH_E_INVALID_ARG before anything is enqueued: a null ctx or an unknown container (also with
+ * count == 0); a null array with count > 0, or a null source with src_n > 0 (a null destination with dst_cap > 0); a device
+ * source not 4-byte or destination not 16-byte aligned; dst_cap above 2^44; overlapping destination ranges (an empty one
+ * overlaps nothing); more than 2^31 - 1 nominal chunks (ceil(src_n / SFH_STREAM_CHUNK), at least 1 per item) in the call.
+ * count == 0 is SFH_OK.  The candidate, count and chain steps run over the whole call; the write pass, the windows and the
+ * checksums in launch batches of whole items of at most SFH_BATCH_CHUNKS * 32 KiB of output (1 GiB by default; a larger item
+ * alone).  Host synchronisations: the wrapper, the candidates, each chain round (the most any item needs), and per launch batch
+ * the statuses and the checksums -- not more with more items.  Scratch: 60 bytes per nominal chunk of the call, and per launch
+ * batch 2 bytes per output byte and 64 KiB per group (sfh_last_decode_scratch_bytes: the peak).  sfh_last_stream_stats: counts
+ * [0] to [2] summed over the items, [3] and [4] their maxima, [5] the peak scratch; stage times summed.
+ * sfh_inflate_stream_batch: host buffers, packed through pinned staging (one copy per direction per 64 MiB); only items whose
+ * status is 0 are copied back. */
+int sfh_inflate_stream_batch_device(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n,
+                                    uint32_t container, void* const* d_dsts, const uint64_t* dst_cap,
+                                    uint64_t* dst_n_out, uint32_t* status, void* stream);
+int sfh_inflate_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n,
+                             uint32_t container, void* const* dsts, const uint64_t* dst_cap,
+                             uint64_t* dst_n_out, uint32_t* status);
+/* the last sfh_inflate_stream* call (a batch call: see above).  ms (profiling on, else zeros): SFH_STREAM_NSTAGES stages -- find, count (the first count
  * pass and every repair round), write, resolve, checksum.  counts: [0] nominal chunks, [1] candidates (chunk 0 included), [2]
  * confirmed chunks, [3] repair rounds, [4] the longest confirmed chunk's output bytes, [5] scratch bytes */
 #define SFH_STREAM_NSTAGES 5

@@ -31,7 +31,8 @@ EXPORTS = [
     "sfh_compress_batch_device_async", "sfh_compress_batch", "sfh_batch_index_size", "sfh_copy_batch_index",
     "sfh_decompress_batch_device_async", "sfh_decompress_batch",
     "sfh_recover_index_device", "sfh_recover_index", "sfh_decompress_any_device", "sfh_decompress_any", "sfh_last_recover_stats",
-    "sfh_inflate_stream_device", "sfh_inflate_stream", "sfh_last_stream_stats",
+    "sfh_inflate_stream_device", "sfh_inflate_stream", "sfh_inflate_stream_batch_device", "sfh_inflate_stream_batch",
+    "sfh_last_stream_stats",
     "sfh_last_block_bytes", "sfh_index_entries", "sfh_copy_index", "sfh_copy_subindex", "sfh_decompress_device", "sfh_decompress", "sfh_last_inflate_ms", "sfh_last_decode_scratch_bytes",
     "sfh_inflate_stage_name", "sfh_checksum_device", "sfh_crc32_combine", "sfh_adler32_combine",
     "sfh_set_profiling", "sfh_last_stage_ms", "sfh_stage_name", "sfh_debug_read",
@@ -124,6 +125,11 @@ def lib():
     L.sfh_inflate_stream_device.restype = C.c_int
     L.sfh_inflate_stream.argtypes = [vp, vp, sz, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.sfh_inflate_stream.restype = C.c_int
+    L.sfh_inflate_stream_batch_device.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, C.POINTER(vp), u64p, u64p,
+                                                  C.POINTER(C.c_uint32), vp]
+    L.sfh_inflate_stream_batch_device.restype = C.c_int
+    L.sfh_inflate_stream_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, C.POINTER(vp), u64p, u64p, C.POINTER(C.c_uint32)]
+    L.sfh_inflate_stream_batch.restype = C.c_int
     L.sfh_last_stream_stats.argtypes = [vp, C.POINTER(C.c_float * 5), C.POINTER(C.c_uint64 * 6)]
     L.sfh_last_stream_stats.restype = C.c_int
     L.sfh_gather_offsets.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]

@@ -363,6 +363,73 @@ class Compressor:
         keys = ("chunks", "candidates", "confirmed", "repair_rounds", "longest_chunk", "scratch_bytes")
         return {**{k: ms[i] for i, k in enumerate(names)}, **{k: cnt[i] for i, k in enumerate(keys)}}
 
+    # ---- many streams without side information or flush points in one call (sfh_inflate_stream_batch*) ----
+    def decompress_stream_batch(self, streams, sizes=None, container="raw"):
+        """Host buffers: bytes-like raw / zlib / gzip streams (one member each) -> (list of bytes, list of DecompressStatus ints),
+        every item exactly what decompress_stream gives for it alone.  sizes: the output capacities (None: a size-query call
+        first, then exactly the output sizes).  An item whose status is not 0 comes back as b""."""
+        srcs, n, caps, kind = _stream_batch_args(streams, sizes, container)
+        k = len(srcs)
+        sp = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a in srcs])
+        out_n = (C.c_uint64 * k)()
+        st = (C.c_uint32 * k)()
+        if caps is None:
+            self._check(self._lib.sfh_inflate_stream_batch(self._h, k, sp, n, kind, None, None, out_n, st))
+            caps = [int(out_n[i]) if st[i] == 0 else 0 for i in range(k)]
+            live = [st[i] == 0 for i in range(k)]
+            first = [int(st[i]) for i in range(k)]
+        else:
+            live, first = [True] * k, [0] * k
+        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in caps]
+        # (an item that failed its size query is asked again as a query of its own: a null destination)
+        dp = (C.c_void_p * k)(*[d.ctypes.data if ok else None for d, ok in zip(dsts, live)])
+        if k:
+            self._check(self._lib.sfh_inflate_stream_batch(self._h, k, sp, n, kind, dp, (C.c_uint64 * k)(*caps), out_n, st))
+        stats = [int(st[i]) if live[i] else first[i] for i in range(k)]
+        return [dsts[i][: out_n[i]].tobytes() if stats[i] == 0 else b"" for i in range(k)], stats
+
+    def decompress_stream_batch_tensors(self, streams, sizes=None, container="raw", outs=None, hip_stream=None):
+        """Device buffers: 1-D uint8 CUDA tensors -> (list of output tensors, list of DecompressStatus ints); each output is
+        exactly the item's decoded bytes (empty unless its status is 0).  sizes: the output capacities (None: a size-query
+        call first); outs: one uint8 CUDA tensor of at least sizes[i] bytes per item (default: new ones).  Synchronises the
+        stream."""
+        import torch
+
+        streams = list(streams)
+        for t in streams:
+            self._check_tensor(t)
+        kind = _container(container)
+        k = len(streams)
+        dev = torch.device("cuda", self.device)
+        s = torch.cuda.current_stream(dev).cuda_stream if hip_stream is None else hip_stream
+        sp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in streams])
+        n = (C.c_uint64 * k)(*[t.numel() for t in streams])
+        out_n = (C.c_uint64 * k)()
+        st = (C.c_uint32 * k)()
+        live, first = [True] * k, [0] * k
+        if sizes is None:
+            self._check(self._lib.sfh_inflate_stream_batch_device(self._h, k, sp, n, kind, None, None, out_n, st, C.c_void_p(s)))
+            sizes = [int(out_n[i]) if st[i] == 0 else 0 for i in range(k)]
+            live = [st[i] == 0 for i in range(k)]
+            first = [int(st[i]) for i in range(k)]
+        caps = [int(m) for m in sizes]
+        if len(caps) != k or any(m < 0 for m in caps):
+            raise ValueError("sizes must hold one non-negative capacity per stream")
+        if outs is None:
+            outs = [torch.empty(max(m, 1), dtype=torch.uint8, device=dev) for m in caps]
+        outs = list(outs)
+        if len(outs) != k or any(o.numel() < m for o, m in zip(outs, caps)):
+            raise ValueError("outs must hold one tensor of at least sizes[i] bytes per item")
+        for t in outs:
+            self._check_tensor(t)
+        dp = (C.c_void_p * k)(*[o.data_ptr() if ok else None for o, ok in zip(outs, live)])
+        if k:
+            self._check(self._lib.sfh_inflate_stream_batch_device(self._h, k, sp, n, kind, dp,
+                                                                  (C.c_uint64 * k)(*[m if ok else 0 for m, ok in zip(caps, live)]),
+                                                                  out_n, st, C.c_void_p(s)))
+        stats = [int(st[i]) if live[i] else first[i] for i in range(k)]
+        return [outs[i][: out_n[i]] if stats[i] == 0 else outs[i][:0] for i in range(k)], stats
+
     # ---- many independent streams, each decoded into its own buffer, in one call (sfh_decompress_batch*) ----
     def decompress_batch(self, streams, sizes, index=None, subindex=None, block_bytes=None, container="raw"):
         """Host buffers: bytes-like streams and their decoded sizes -> (list of bytes, list of DecompressStatus ints).  index /
@@ -575,6 +642,25 @@ def _batch_inflate_args(streams, sizes, index, subindex, block_bytes, container)
     return srcs, (C.c_uint64 * len(srcs))(*[a.size for a in srcs]), dst_n, idx, sub, bb, kind
 
 
+def _stream_batch_args(streams, sizes, container):
+    """decompress_stream_batch's host arguments, checked before anything reaches the device: (sources, src_n, capacities or
+    None, container code)."""
+    if isinstance(streams, (bytes, bytearray, memoryview, np.ndarray)):
+        raise ValueError("streams: a sequence of bytes-like streams")
+    srcs = [np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else np.ascontiguousarray(d, dtype=np.uint8).ravel()
+            for d in streams]
+    if not isinstance(container, str) or container not in _capi.CONTAINER:
+        raise ValueError(f"container must be one of {sorted(_capi.CONTAINER)}")
+    caps = None
+    if sizes is not None:
+        caps = [int(m) for m in sizes]
+        if len(caps) != len(srcs):
+            raise ValueError(f"{len(srcs)} streams but {len(caps)} sizes")
+        if any(m < 0 or m > (1 << 44) for m in caps):
+            raise ValueError("sizes must lie in [0, 2^44]")
+    return srcs, (C.c_uint64 * len(srcs))(*[a.size for a in srcs]), caps, _capi.CONTAINER[container]
+
+
 _DEFAULT = {}
 
 
@@ -641,3 +727,13 @@ def decompress_batch(streams, sizes, device=0, **kw):
     if c is None:
         c = _DEFAULT[device] = Compressor(device)
     return c.decompress_batch(streams, sizes, **kw)
+
+
+def decompress_stream_batch(streams, sizes=None, container="raw", device=0):
+    """Raw / zlib / gzip streams with no index and no flush points -> (list of bytes, list of statuses), all in one call
+    (Compressor.decompress_stream_batch).  The arguments are checked before a device is touched."""
+    _stream_batch_args(streams, sizes, container)
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    return c.decompress_stream_batch(streams, sizes, container)

@@ -109,6 +109,11 @@ struct sfh_ctx {
   hipEvent_t ev_stm[6] = {};
   float stm_ms[SFH_STREAM_NSTAGES] = {};
   uint64_t stm_counts[SFH_STREAM_NCOUNTS] = {};
+  // batches of them (sfh_inflate_stream_batch*): the wrapper rows and bodies | the item rows; a launch batch's group, checksum
+  // and fold rows and its statuses
+  uint8_t* d_sbt = nullptr;
+  uint8_t* d_sbr = nullptr;
+  size_t d_sbt_cap = 0, d_sbr_cap = 0;
   char err[256] = {0};
 };
 
@@ -1091,6 +1096,368 @@ int stream_run(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t containe
   return mark_call_end(ctx, s);
 }
 
+// ---- batches of streams without flush points (sfh_inflate_stream_batch*; sf_stream_batch.hip) ----
+// Everything the call checks before it enqueues anything (`dev`: device buffers, the single call's alignment rules).
+int check_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
+                       void* const* dsts, const uint64_t* dst_cap, const uint64_t* dst_n_out, const uint32_t* status, bool dev) {
+  if (!ctx || container > SFH_GZIP) return fail(ctx, SFH_E_INVALID_ARG, "argument (container)", hipSuccess);
+  if (count == 0) return SFH_OK;
+  if (!srcs || !src_n || !dst_n_out || !status || (dsts && !dst_cap)) return fail(ctx, SFH_E_INVALID_ARG, "null array", hipSuccess);
+  const uint64_t S = ctx->stream_chunk;
+  uint64_t nc = 0;
+  for (size_t i = 0; i < count; ++i) {
+    if ((!srcs[i] && src_n[i]) || (dsts && !dsts[i] && dst_cap[i])) return fail(ctx, SFH_E_INVALID_ARG, "null item pointer", hipSuccess);
+    if (dev && (((uintptr_t)srcs[i] & 3) || (dsts && ((uintptr_t)dsts[i] & 15))))
+      return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, dst 16)", hipSuccess);
+    if (dsts && dst_cap[i] > ((uint64_t)1 << 44)) return fail(ctx, SFH_E_INVALID_ARG, "dst_cap: at most 2^44", hipSuccess);
+    nc += src_n[i] ? (src_n[i] + S - 1) / S : 1;  // (at least the body's nominal chunks)
+  }
+  if (nc > ((uint64_t)1 << 31) - 1)
+    return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 nominal chunks in one call (SFH_STREAM_CHUNK)", hipSuccess);
+  if (!dsts) return SFH_OK;
+  std::vector<size_t> ord;
+  try {
+    ord.reserve(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (size_t i = 0; i < count; ++i)  // (an empty range is written nothing and overlaps nothing)
+    if (dst_cap[i]) ord.push_back(i);
+  std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return (uintptr_t)dsts[a] < (uintptr_t)dsts[b]; });
+  for (size_t k = 1; k < ord.size(); ++k)
+    if ((uintptr_t)dsts[ord[k - 1]] + dst_cap[ord[k - 1]] > (uintptr_t)dsts[ord[k]])
+      return fail(ctx, SFH_E_INVALID_ARG, "destination ranges overlap", hipSuccess);
+  return SFH_OK;
+}
+
+// Arguments checked, count > 0.  Item i is decoded when dsts && dsts[i] (else it is a size query, as the single call with no
+// dst); stage: into ctx->d_out at (*out_off)[i] instead (the host-buffer entry point).  The steps of stream_run over the whole
+// call -- A to C for every item at once, the chain rounds until the last item's chain is complete -- then D to F and the
+// checksums in launch batches of whole items of at most batch_chunks * 32 KiB of output each.  Host synchronisations: the
+// wrapper, the candidates, the count pass and each chain round, and per launch batch the statuses and the checksums.
+int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
+                     void* const* dsts, const uint64_t* dst_cap, bool stage, std::vector<uint64_t>* out_off, uint64_t* dst_n_out,
+                     uint32_t* status, hipStream_t s) {
+  const bool prof = ctx->profiling != 0;
+  for (float& m : ctx->stm_ms) m = 0;
+  for (uint64_t& c : ctx->stm_counts) c = 0;
+  ctx->last_dtok_bytes = 0;
+  for (size_t i = 0; i < count; ++i) dst_n_out[i] = status[i] = 0;
+  if (stage) {
+    try {
+      out_off->assign(count + 1, 0);
+    } catch (...) {
+      return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+    }
+  }
+  for (hipEvent_t& e : ctx->ev_stm)
+    if (!e) SF_HIP(hipEventCreate(&e), "event");
+  auto lap = [&](int a, int b, int stage_ix) -> int {
+    float ms = 0;
+    SF_HIP(hipEventElapsedTime(&ms, ctx->ev_stm[a], ctx->ev_stm[b]), "elapsed");
+    ctx->stm_ms[stage_ix] += ms;
+    return SFH_OK;
+  };
+  const uint64_t S = ctx->stream_chunk, kBig = (uint64_t)1 << 44;
+  const auto decodes = [&](size_t i) { return dsts && dsts[i]; };
+  std::vector<sf::InflateItem> head;
+  std::vector<uint64_t> body;
+  std::vector<uint32_t> live;  // the items whose body is decoded, in call order: their rows in `items`
+  std::vector<sf::StreamItem> items;
+  try {
+    head.resize(count);
+    body.resize(2 * count);
+    live.reserve(count);
+    items.reserve(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory for the item rows", hipSuccess);
+  }
+  int rc = order_behind_last_call(ctx, s);
+  if (rc) return rc;
+  // the wrappers: k_inflate_head over every item, as any_wrapper reads one (a raw body is the whole item: no launch)
+  const size_t o_body = al16(sizeof(sf::InflateItem) * count), o_items = o_body + al16(16 * count);
+  if ((rc = grow(ctx, &ctx->d_sbt, &ctx->d_sbt_cap, o_items + sizeof(sf::StreamItem) * count, "stream batch rows"))) return rc;
+  uint64_t* d_body = (uint64_t*)(ctx->d_sbt + o_body);
+  sf::StreamItem* d_items = (sf::StreamItem*)(ctx->d_sbt + o_items);
+  if (container != SFH_RAW) {
+    for (size_t i = 0; i < count; ++i)
+      head[i] = sf::InflateItem{(const uint8_t*)srcs[i], src_n[i], decodes(i) ? dst_cap[i] : kBig, d_body + 2 * i, nullptr, 0, 0,
+                                0, 0, 0, 0};
+    SF_HIP(hipMemcpyAsync(ctx->d_sbt, head.data(), sizeof(sf::InflateItem) * count, hipMemcpyHostToDevice, s), "H2D wrapper rows");
+    SF_HIP(sf::launch_inflate_head((sf::InflateItem*)ctx->d_sbt, (uint32_t)count, container, nullptr, nullptr, s), "launch k_inflate_head");
+    SF_HIP(hipMemcpyAsync(head.data(), ctx->d_sbt, sizeof(sf::InflateItem) * count, hipMemcpyDeviceToHost, s), "D2H wrapper rows");
+    SF_HIP(hipMemcpyAsync(body.data(), d_body, 16 * count, hipMemcpyDeviceToHost, s), "D2H bodies");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+  }
+  uint64_t nc64 = 0;
+  for (size_t i = 0; i < count; ++i) {
+    if (container == SFH_RAW) {
+      if (src_n[i] == 0) {  // no header bits at all
+        status[i] = sf::inflate::kInvalidBlockHeader;
+        continue;
+      }
+      body[2 * i] = 0;
+      body[2 * i + 1] = src_n[i];
+    } else if (head[i].wst) {
+      status[i] = head[i].wst;
+      continue;
+    }
+    const uint64_t bn = body[2 * i + 1] - body[2 * i];
+    sf::StreamItem it{};
+    it.src = (const uint8_t*)srcs[i];
+    it.src_n = src_n[i];
+    it.b0 = body[2 * i];
+    it.body_n = bn;
+    it.c0 = (uint32_t)nc64;
+    nc64 += bn ? (bn + S - 1) / S : 1;
+    live.push_back((uint32_t)i);
+    items.push_back(it);
+  }
+  const uint32_t nl = (uint32_t)live.size();
+  if (nl == 0) return mark_call_end(ctx, s);
+  const uint32_t nc = (uint32_t)nc64;  // (<= the bound check_stream_batch checked)
+  // cand u64[nc] (then: the records' items u32[nc] | the follow list u32[nc]) | recs StreamChunk[nc] | list u32[nc]
+  const size_t o_rec = al16(8 * (size_t)nc), o_list = o_rec + al16(sizeof(sf::StreamChunk) * (size_t)nc);
+  const size_t stm_bytes = o_list + al16(4 * (size_t)nc);
+  if ((rc = grow(ctx, &ctx->d_stm, &ctx->d_stm_cap, stm_bytes, "stream chunk records"))) return rc;
+  uint64_t* d_cand = (uint64_t*)ctx->d_stm;
+  uint32_t* d_rec_item = (uint32_t*)ctx->d_stm;
+  uint32_t* d_follow = d_rec_item + nc;
+  sf::StreamChunk* d_rec = (sf::StreamChunk*)(ctx->d_stm + o_rec);
+  uint32_t* d_list = (uint32_t*)(ctx->d_stm + o_list);
+  std::vector<uint64_t> cand;
+  std::vector<sf::StreamChunk> rec;
+  std::vector<uint32_t> rec_item, chain(nl, 0);
+  try {
+    cand.resize(nc);
+    rec.reserve(nc);
+    rec_item.reserve(nc);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory for the chunk records", hipSuccess);
+  }
+  // A: candidates, every item's nominal chunks at once
+  SF_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(sf::StreamItem) * nl, hipMemcpyHostToDevice, s), "H2D item rows");
+  if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[0], s), "event");
+  SF_HIP(sf::launch_stream_find_batch(d_items, nl, nc, S, d_cand, s), "launch k_stream_find_batch");
+  if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[1], s), "event");
+  SF_HIP(hipMemcpyAsync(cand.data(), d_cand, 8 * (size_t)nc, hipMemcpyDeviceToHost, s), "D2H candidates");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  for (uint32_t k = 0; k < nl; ++k) {
+    sf::StreamItem& it = items[k];
+    const uint32_t c1 = k + 1 < nl ? items[k + 1].c0 : nc;
+    it.r0 = (uint32_t)rec.size();
+    for (uint32_t c = it.c0; c < c1; ++c)
+      if (cand[c] != sf::kNoCandidate && (rec.size() == it.r0 || cand[c] > rec.back().start)) {
+        rec.push_back(sf::StreamChunk{cand[c], 0, 0, 0, 0, 0, 0});
+        rec_item.push_back(k);
+      }
+    it.m = (uint32_t)rec.size() - it.r0;
+    for (uint32_t i = it.r0; i < it.r0 + it.m; ++i) rec[i].limit = i + 1 < it.r0 + it.m ? rec[i + 1].start : ~0ull;
+  }
+  const uint32_t M = (uint32_t)rec.size();
+  // B and C: the count pass over every record, then rounds of repairs until every item's chain reaches its end
+  const size_t rec_bytes = sizeof(sf::StreamChunk) * (size_t)M;
+  SF_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(sf::StreamItem) * nl, hipMemcpyHostToDevice, s), "H2D item rows");
+  SF_HIP(hipMemcpyAsync(d_rec_item, rec_item.data(), 4 * (size_t)M, hipMemcpyHostToDevice, s), "H2D record items");
+  SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
+  SF_HIP(sf::launch_stream_decode_batch(false, d_items, d_rec_item, d_rec, nullptr, M, false, nullptr, s), "launch k_stream_decode_batch");
+  SF_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s), "D2H chunk records");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  std::vector<char> done(nl, 0);
+  std::vector<uint32_t> redo, follow;
+  uint32_t rounds = 0;
+  for (;;) {
+    redo.clear();
+    follow.clear();
+    for (uint32_t k = 0; k < nl; ++k) {
+      if (done[k]) continue;
+      const size_t before = redo.size();
+      sf::stream_chain_round(rec.data(), items[k].r0, items[k].m, redo, &chain[k]);
+      if (redo.size() == before) {
+        done[k] = 1;
+      } else {
+        follow.push_back(redo[before]);  // behind the item's confirmed chain: it goes on through the broken links after it
+      }
+    }
+    if (redo.empty()) break;
+    ++rounds;
+    SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
+    SF_HIP(hipMemcpyAsync(d_list, redo.data(), 4 * redo.size(), hipMemcpyHostToDevice, s), "H2D repair list");
+    SF_HIP(hipMemcpyAsync(d_follow, follow.data(), 4 * follow.size(), hipMemcpyHostToDevice, s), "H2D follow list");
+    SF_HIP(sf::launch_stream_decode_batch(false, d_items, d_rec_item, d_rec, d_list, (uint32_t)redo.size(), false, nullptr, s),
+           "launch k_stream_decode_batch");
+    SF_HIP(sf::launch_stream_decode_batch(false, d_items, d_rec_item, d_rec, d_follow, (uint32_t)follow.size(), true, nullptr, s),
+           "launch k_stream_decode_batch");
+    SF_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s), "D2H chunk records");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+  }
+  if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[2], s), "event");
+  std::vector<uint64_t> total(nl, 0);
+  uint64_t longest = 0, confirmed = 0;
+  for (uint32_t k = 0; k < nl; ++k) {
+    sf::StreamItem& it = items[k];
+    for (uint32_t i = it.r0; i < it.r0 + chain[k]; ++i) {
+      rec[i].base = total[k];
+      total[k] += rec[i].out;
+      longest = std::max(longest, rec[i].out);
+    }
+    it.chain = chain[k];
+    it.G = sf::stream_group(chain[k]);
+    confirmed += chain[k];
+    dst_n_out[live[k]] = total[k];
+    if (!decodes(live[k])) status[live[k]] = rec[it.r0 + chain[k] - 1].status;
+  }
+  ctx->stm_counts[0] = nc;
+  ctx->stm_counts[1] = M;
+  ctx->stm_counts[2] = confirmed;
+  ctx->stm_counts[3] = rounds;
+  ctx->stm_counts[4] = longest;
+  ctx->stm_counts[5] = stm_bytes;
+  ctx->last_dtok_bytes = stm_bytes;
+  if (prof) {
+    SF_HIP(hipEventSynchronize(ctx->ev_stm[2]), "event sync");
+    if ((rc = lap(0, 1, 0)) || (rc = lap(1, 2, 1))) return rc;
+  }
+  // D to F in launch batches of whole items: each item's plane and windows at its place in its batch's
+  const uint64_t budget = (uint64_t)ctx->batch_chunks * sf::kChunk;
+  std::vector<uint32_t> dec;  // the decoded items' rows, and where each launch batch starts among them
+  std::vector<size_t> lb;
+  if (stage) {
+    uint64_t o = 0;
+    for (size_t i = 0, k = 0; i < count; ++i) {
+      (*out_off)[i] = o;
+      if (k < nl && live[k] == i) {
+        if (decodes(i)) o += al16(std::min(total[k], container == SFH_GZIP ? (uint64_t)head[i].isize : dst_cap[i]));
+        ++k;
+      }
+    }
+    (*out_off)[count] = o;
+    if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, std::max<uint64_t>(16, o), "output staging"))) return rc;
+  }
+  uint64_t cur = 0, peak = 0;
+  for (uint32_t k = 0; k < nl; ++k) {
+    const size_t i = live[k];
+    if (!decodes(i)) continue;
+    if (dec.empty() || (cur && cur + total[k] > budget)) {
+      lb.push_back(dec.size());
+      cur = 0;
+    }
+    dec.push_back(k);
+    cur += total[k];
+  }
+  lb.push_back(dec.size());
+  std::vector<uint64_t> plane_n(lb.size(), 0), wins_n(lb.size(), 0);
+  for (size_t b = 0; b + 1 < lb.size(); ++b)
+    for (size_t q = lb[b]; q < lb[b + 1]; ++q) {
+      sf::StreamItem& it = items[dec[q]];
+      const size_t i = live[dec[q]];
+      it.plane = plane_n[b];
+      it.win = wins_n[b];
+      it.cap = container == SFH_GZIP ? (uint64_t)head[i].isize : dst_cap[i];  // (container.hpp: a gzip body into dst.first(ISIZE))
+      it.dst = stage ? ctx->d_out + (*out_off)[i] : (uint8_t*)dsts[i];
+      plane_n[b] += al16(total[dec[q]]);  // (entries; 16-entry aligned)
+      wins_n[b] += (uint64_t)((it.chain + it.G - 1) / it.G - 1) * 32768;
+    }
+  if (!dec.empty()) {
+    SF_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(sf::StreamItem) * nl, hipMemcpyHostToDevice, s), "H2D item rows");
+    SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
+  }
+  std::vector<uint32_t> wlist, link, bst;
+  std::vector<sf::StreamGroup> compose, resolve;
+  std::vector<sf::BatchChunk> sums;
+  std::vector<sf::InflateItem> fold;
+  std::vector<uint32_t> fold_item;
+  for (size_t b = 0; b + 1 < lb.size(); ++b) {
+    const size_t q0 = lb[b], q1 = lb[b + 1];
+    const size_t wins_bytes = 2 * wins_n[b], plane_bytes = std::max<size_t>(16, 2 * plane_n[b]);
+    peak = std::max<uint64_t>(peak, plane_bytes + wins_bytes);
+    if ((rc = grow(ctx, &ctx->d_plane, &ctx->d_plane_cap, plane_bytes, "symbol plane"))) return rc;
+    if (wins_bytes && (rc = grow(ctx, &ctx->d_wins, &ctx->d_wins_cap, wins_bytes, "stream windows"))) return rc;
+    // D: the confirmed records of the batch's items
+    wlist.clear();
+    for (size_t q = q0; q < q1; ++q) {
+      const sf::StreamItem& it = items[dec[q]];
+      for (uint32_t i = it.r0; i < it.r0 + it.chain; ++i) wlist.push_back(i);
+    }
+    const uint32_t ra = items[dec[q0]].r0, rb = items[dec[q1 - 1]].r0 + items[dec[q1 - 1]].m;
+    if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[2], s), "event");
+    SF_HIP(hipMemcpyAsync(d_list, wlist.data(), 4 * wlist.size(), hipMemcpyHostToDevice, s), "H2D write list");
+    SF_HIP(sf::launch_stream_decode_batch(true, d_items, d_rec_item, d_rec, d_list, (uint32_t)wlist.size(), false, ctx->d_plane, s),
+           "launch k_stream_decode_batch");
+    if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[3], s), "event");
+    SF_HIP(hipMemcpyAsync(rec.data() + ra, d_rec + ra, sizeof(sf::StreamChunk) * (size_t)(rb - ra), hipMemcpyDeviceToHost, s),
+           "D2H chunk records");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+    if (prof && (rc = lap(2, 3, 2))) return rc;
+    // the statuses; E / F for the items that decoded, then their checksums
+    compose.clear();
+    resolve.clear();
+    link.clear();
+    sums.clear();
+    fold.clear();
+    fold_item.clear();
+    for (size_t q = q0; q < q1; ++q) {
+      const uint32_t k = dec[q];
+      const sf::StreamItem& it = items[k];
+      const size_t i = live[k];
+      uint32_t st = 0;
+      for (uint32_t r = it.r0; r < it.r0 + it.chain && !st; ++r) st = rec[r].status;
+      if (!st && container == SFH_GZIP && total[k] != head[i].isize) st = sf::inflate::kError;
+      status[i] = st;
+      if (st) continue;
+      const uint32_t ng = (it.chain + it.G - 1) / it.G;
+      for (uint32_t g = 0; g < ng; ++g) {
+        if (g + 1 < ng) compose.push_back(sf::StreamGroup{k, g});
+        resolve.push_back(sf::StreamGroup{k, g});
+      }
+      if (ng > 1) link.push_back(k);
+      if (container) {
+        const uint32_t nch = chunks_of((size_t)total[k]);
+        fold.push_back(sf::InflateItem{it.src, it.src_n, total[k], nullptr, nullptr, (uint32_t)sums.size(), 0, 0, head[i].want,
+                                       (uint32_t)total[k], 0});
+        fold_item.push_back((uint32_t)i);
+        for (uint32_t c = 0; c < nch; ++c) {
+          const uint64_t ob = (uint64_t)c * sf::kChunk;
+          // (an empty output: one empty row, at a real address)
+          sums.push_back(sf::BatchChunk{total[k] ? it.dst + ob : (const uint8_t*)ctx->d_plane, (uint32_t)std::min<uint64_t>(sf::kChunk, total[k] - ob), 0u});
+        }
+      }
+    }
+    if (resolve.empty()) continue;
+    // compose | resolve | link | checksum rows | fold rows | fold statuses
+    const size_t o_res = al16(8 * compose.size()), o_link = o_res + al16(8 * resolve.size());
+    const size_t o_sums = o_link + al16(4 * link.size()), o_fold = o_sums + al16(sizeof(sf::BatchChunk) * sums.size());
+    const size_t o_fst = o_fold + al16(sizeof(sf::InflateItem) * fold.size()), rows_bytes = o_fst + al16(4 * fold.size());
+    if ((rc = grow(ctx, &ctx->d_sbr, &ctx->d_sbr_cap, rows_bytes, "stream batch group rows"))) return rc;
+    uint8_t* R = ctx->d_sbr;
+    SF_HIP(hipMemcpyAsync(R, compose.data(), 8 * compose.size(), hipMemcpyHostToDevice, s), "H2D group rows");
+    SF_HIP(hipMemcpyAsync(R + o_res, resolve.data(), 8 * resolve.size(), hipMemcpyHostToDevice, s), "H2D group rows");
+    if (!link.empty()) SF_HIP(hipMemcpyAsync(R + o_link, link.data(), 4 * link.size(), hipMemcpyHostToDevice, s), "H2D link rows");
+    SF_HIP(sf::launch_stream_resolve_batch(ctx->d_plane, d_rec, d_items, (const sf::StreamGroup*)R, (uint32_t)compose.size(),
+                                           (const uint32_t*)(R + o_link), (uint32_t)link.size(), (const sf::StreamGroup*)(R + o_res),
+                                           (uint32_t)resolve.size(), ctx->d_wins, s), "launch k_stream_resolve_batch");
+    if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[4], s), "event");
+    if (!fold.empty()) {
+      if ((rc = ensure_sums(ctx, (uint32_t)sums.size()))) return rc;
+      SF_HIP(hipMemcpyAsync(R + o_sums, sums.data(), sizeof(sf::BatchChunk) * sums.size(), hipMemcpyHostToDevice, s), "H2D checksum rows");
+      SF_HIP(hipMemcpyAsync(R + o_fold, fold.data(), sizeof(sf::InflateItem) * fold.size(), hipMemcpyHostToDevice, s), "H2D fold rows");
+      SF_HIP(sf::launch_checksum_batch((const sf::BatchChunk*)(R + o_sums), (uint32_t)sums.size(), container, ctx->ws.sums, s),
+             "launch k_checksum_batch");
+      SF_HIP(sf::launch_inflate_fold((const sf::InflateItem*)(R + o_fold), (uint32_t)fold.size(), nullptr, ctx->ws.sums, container,
+                                     (uint32_t*)(R + o_fst), s), "launch k_inflate_fold");
+      bst.resize(fold.size());
+      SF_HIP(hipMemcpyAsync(bst.data(), R + o_fst, 4 * fold.size(), hipMemcpyDeviceToHost, s), "D2H checksums");
+    }
+    if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[5], s), "event");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+    for (size_t f = 0; f < fold.size(); ++f) status[fold_item[f]] = bst[f];
+    if (prof && ((rc = lap(3, 4, 3)) || (rc = lap(4, 5, 4)))) return rc;
+  }
+  ctx->stm_counts[5] = stm_bytes + peak;
+  ctx->last_dtok_bytes = ctx->stm_counts[5];
+  return mark_call_end(ctx, s);
+}
+
 int check_any(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, uint64_t dst_n, bool dev) {
   if (!ctx) return SFH_E_INVALID_ARG;
   if ((!src && src_n) || container > SFH_GZIP) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
@@ -1282,6 +1649,8 @@ void sfh_destroy(sfh_ctx* ctx) {
   (void)hipFree(ctx->d_stm);
   (void)hipFree(ctx->d_plane);
   (void)hipFree(ctx->d_wins);
+  (void)hipFree(ctx->d_sbt);
+  (void)hipFree(ctx->d_sbr);
   for (hipEvent_t e : ctx->ev_stm)
     if (e) (void)hipEventDestroy(e);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1863,6 +2232,79 @@ int sfh_inflate_stream(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t con
   if (!query && *status == 0 && *dst_n_out) {
     SF_HIP(hipMemcpyAsync(dst, ctx->d_out, *dst_n_out, hipMemcpyDeviceToHost, s), "D2H");
     SF_HIP(hipStreamSynchronize(s), "stream sync");
+  }
+  return SFH_OK;
+}
+
+int sfh_inflate_stream_batch_device(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n,
+                                    uint32_t container, void* const* d_dsts, const uint64_t* dst_cap, uint64_t* dst_n_out,
+                                    uint32_t* status, void* stream) {
+  int rc = check_stream_batch(ctx, count, d_srcs, src_n, container, d_dsts, dst_cap, dst_n_out, status, true);
+  if (rc || count == 0) return rc;
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();  // see enqueue()
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  return stream_batch_run(ctx, count, d_srcs, src_n, container, d_dsts, dst_cap, false, nullptr, dst_n_out, status, s);
+}
+
+int sfh_inflate_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
+                             void* const* dsts, const uint64_t* dst_cap, uint64_t* dst_n_out, uint32_t* status) {
+  int rc = check_stream_batch(ctx, count, srcs, src_n, container, dsts, dst_cap, dst_n_out, status, false);
+  if (rc || count == 0) return rc;
+  // As sfh_decompress_batch: the items packed into the device staging (16-byte aligned) through one pinned buffer, one copy per
+  // kStageBytes each way; only the items whose status is 0 are copied out (their output packed by size in ctx->d_out).
+  constexpr size_t kStageBytes = (size_t)kPipeBatchChunks * sf::kChunk;
+  std::vector<uint64_t> in_off, out_off;
+  std::vector<const void*> d_srcs;
+  try {
+    in_off.resize(count + 1);
+    d_srcs.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (size_t i = 0; i < count; ++i) in_off[i + 1] = (in_off[i] + src_n[i] + 15) / 16 * 16;
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t s = ctx->stream;
+  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
+  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
+    ctx->h_stage = nullptr;
+    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
+  }
+  if (rc) return rc;
+  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
+  size_t item = 0;
+  for (uint64_t p0 = 0; p0 < in_off[count]; p0 += kStageBytes) {
+    const uint64_t p1 = std::min<uint64_t>(in_off[count], p0 + kStageBytes);
+    while (item < count && in_off[item] + src_n[item] <= p0) ++item;
+    for (size_t i = item; i < count && in_off[i] < p1; ++i) {
+      const uint64_t a = std::max(p0, in_off[i]), b = std::min(p1, in_off[i] + src_n[i]);
+      if (a < b) memcpy(ctx->h_stage + (a - p0), (const uint8_t*)srcs[i] + (a - in_off[i]), b - a);
+    }
+    SF_HIP(hipMemcpyAsync(ctx->d_in + p0, ctx->h_stage, p1 - p0, hipMemcpyHostToDevice, s), "H2D");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");  // (the next piece refills h_stage)
+  }
+  for (size_t i = 0; i < count; ++i) d_srcs[i] = ctx->d_in + in_off[i];
+  if ((rc = stream_batch_run(ctx, count, d_srcs.data(), src_n, container, dsts, dst_cap, true, &out_off, dst_n_out, status, s))) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  if (!dsts) return SFH_OK;
+  // down: the packed output in pieces, each item with status 0 out of the pieces it lies in
+  const uint64_t end = out_off[count];
+  auto out_n = [&](size_t i) { return (dsts[i] && status[i] == 0) ? dst_n_out[i] : 0; };
+  item = 0;
+  for (uint64_t p0 = 0; p0 < end; p0 += kStageBytes) {
+    const uint64_t p1 = std::min<uint64_t>(end, p0 + kStageBytes);
+    while (item < count && out_off[item] + out_n(item) <= p0) ++item;
+    bool any = false;
+    for (size_t i = item; i < count && out_off[i] < p1 && !any; ++i) any = out_n(i) && out_off[i] + out_n(i) > p0;
+    if (!any) continue;
+    SF_HIP(hipMemcpyAsync(ctx->h_stage, ctx->d_out + p0, p1 - p0, hipMemcpyDeviceToHost, s), "D2H");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+    for (size_t i = item; i < count && out_off[i] < p1; ++i) {
+      const uint64_t a = std::max(p0, out_off[i]), b = std::min(p1, out_off[i] + out_n(i));
+      if (a < b) memcpy((uint8_t*)dsts[i] + (a - out_off[i]), ctx->h_stage + (a - p0), b - a);
+    }
   }
   return SFH_OK;
 }

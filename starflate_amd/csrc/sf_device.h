@@ -334,6 +334,35 @@ hipError_t launch_stream_decode(bool write, const uint8_t* src, uint64_t src_n, 
 uint32_t stream_group(uint32_t n);  // chunks per group of the resolve; tables: (groups - 1) * 32768 u16
 hipError_t launch_stream_resolve(const uint16_t* plane, const StreamChunk* recs, uint32_t n, uint16_t* tables, uint8_t* dst,
                                  hipStream_t s);
+// Batches of such streams (sfh_inflate_stream_batch*): the same passes over the call's items, each read from a row.  The
+// records of all items lie in one array, item after item; a record's item is a separate u32 (StreamChunk keeps its layout).
+struct StreamItem {      // per item whose body is decoded (a wrapper that failed: no row)
+  const uint8_t* src;
+  uint64_t src_n;
+  uint64_t b0, body_n;   // its body: bytes [b0, b0 + body_n) of src
+  uint64_t plane;        // write pass: its first symbol-plane entry in its launch batch's plane
+  uint64_t cap;          // write pass: its output capacity (gzip: ISIZE)
+  uint8_t* dst;          // resolve: its output
+  uint64_t win;          // compose / link / resolve: its first window entry in its launch batch's tables
+  uint32_t c0;           // find: its first nominal chunk in the call (rows ascending by item)
+  uint32_t r0, m;        // its records in the call's
+  uint32_t chain, G;     // its confirmed records, and the chunks per group (stream_group(chain))
+  uint32_t pad;
+};
+struct StreamGroup {     // compose / resolve: one workgroup per (item, group)
+  uint32_t item, g;
+};
+static_assert(sizeof(StreamItem) == 88 && sizeof(StreamGroup) == 8, "stream batch rows");
+// one wave per nominal chunk of the call (nc), its item found by a search over items[].c0
+hipError_t launch_stream_find_batch(const StreamItem* items, uint32_t nitems, uint32_t nc, uint64_t step_bytes, uint64_t* cand,
+                                    hipStream_t s);
+// as launch_stream_decode; rec_item[r]: record r's row in items.  follow: one lane per list entry, each within its item's records
+hipError_t launch_stream_decode_batch(bool write, const StreamItem* items, const uint32_t* rec_item, StreamChunk* recs,
+                                      const uint32_t* list, uint32_t n, bool follow, uint16_t* plane, hipStream_t s);
+// compose rows (every group but an item's last), link (one workgroup per item of more than one group), resolve rows (all)
+hipError_t launch_stream_resolve_batch(const uint16_t* plane, const StreamChunk* recs, const StreamItem* items,
+                                       const StreamGroup* compose, uint32_t ncompose, const uint32_t* link, uint32_t nlink,
+                                       const StreamGroup* resolve, uint32_t nresolve, uint16_t* tables, hipStream_t s);
 
 // sf_guard.hip: does the LDS execute a returning atomic's lanes in ascending order (op 0: ds_wrxchg_rtn_b32, 1: ds_mskor_rtn_b32)?
 // d_result[0] = mismatches against the sequential model, [1] = positions checked

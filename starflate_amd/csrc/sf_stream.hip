@@ -24,185 +24,13 @@
 // including where the input runs out.  A stream with no candidates (Z_FIXED, level 0, ...) is decoded by one lane: slow, but
 // correct.  Bit positions and output counts are 64-bit; the 32-bit BitReader is re-opened before its position passes 2^30.
 // Scratch: 2 bytes per output byte (the plane), 64 KiB per group, 60 bytes per nominal chunk.
-#include "sf_device.h"
-
-#include "sf_inflate_core.h"
+#include "sf_stream_core.h"
 
 namespace sf {
 
 namespace {
 
 using namespace inflate;
-
-constexpr uint32_t KF_THREADS = 256;                 // k_stream_find: 4 waves, one nominal chunk each
-constexpr uint32_t KS_LANES = 4;                     // k_stream_decode: lanes per workgroup (as k_inflate_tokens)
-constexpr uint32_t KS_LDS = KS_LANES * LaneLayout::kBytes;
-constexpr uint32_t KR_THREADS = 1024;                // compose / link / resolve: one 32 KiB window in LDS
-constexpr uint32_t kWin = 32768;
-constexpr uint32_t kPerThread = kWin / KR_THREADS;
-constexpr uint32_t kRebase = 1u << 30;
-
-// The reader at body bit `at`: bitpos counts from the byte holding it (rb = that byte's first bit).
-struct StreamReader {
-  BitReader br;
-  uint64_t rb;
-  __device__ void open(const uint8_t* src, uint64_t src_n, uint64_t b0, uint64_t body_n, uint64_t at) {
-    const uint64_t byte = at >> 3;
-    br.open(src, src_n, b0 + byte, b0 + body_n);
-    rb = byte * 8;
-    br.refill();
-    br.drop((uint32_t)(at & 7));
-  }
-  __device__ uint64_t abs() const { return rb + br.bitpos; }
-  __device__ uint32_t rem() const { return br.nbits - br.bitpos; }  // exact while bitpos <= 2^30 + 2^20 (see the header)
-};
-
-// The dynamic header as the serial decoder reads it (decompress.hpp: HLIT, HDIST, HCLEN, the code-length code, the literal /
-// length lengths and then the distance lengths as two sequences, each checked for over-subscription), tables into m.
-__device__ uint32_t serial_dynamic(BitReader& br, uint8_t* m) {
-  if (br.nbits - br.bitpos < 14) return kError;
-  br.refill();
-  const uint32_t hlit = br.get(5), hdist = br.get(5), hclen = br.get(4) + 4;
-  if (br.nbits - br.bitpos < 3 * hclen) return kError;
-  const uint64_t clp = read_cl_lengths(br, hclen);
-  if (cl_kraft(clp) > 128u) return kError;
-  uint8_t* lut = m + LaneLayout::kOffFastL + kOffClLut;
-  build_cl_lut(clp, lut);
-  uint8_t* lens = m + LaneLayout::kOffLens;
-  for (uint32_t seq = 0; seq < 2; ++seq) {
-    const uint32_t n = seq ? hdist + 1 : hlit + 257;
-    uint8_t* out = lens + (seq ? 288 : 0);
-    uint32_t i = 0, kr = 0;
-    while (i < n) {
-      br.refill();
-      const uint32_t e = lut[br.peek(7)];
-      if (e == 0 || (e & 7u) > br.nbits - br.bitpos) return kInvalidLitOrLen;
-      br.drop(e & 7u);
-      const uint32_t sym = e >> 3;
-      if (sym < 16) {
-        out[i++] = (uint8_t)sym;
-        kr += sym ? 32768u >> sym : 0u;
-        continue;
-      }
-      const uint32_t xb = sym == 16 ? 2 : sym == 17 ? 3 : 7;
-      if (br.nbits - br.bitpos < xb) return kError;
-      const uint32_t rep = br.get(xb) + (sym == 18 ? 11 : 3);
-      if ((sym == 16 && i == 0) || i + rep > n) return kError;
-      const uint32_t v = sym == 16 ? out[i - 1] : 0u;
-      for (uint32_t k = 0; k < rep; ++k) out[i++] = (uint8_t)v;
-      kr += v ? rep * (32768u >> v) : 0u;
-    }
-    if (kr > 32768u) return kError;
-    for (uint32_t s = n; s < (seq ? 32u : 288u); ++s) out[s] = 0;
-  }
-  build_tables<LaneLayout, true>(m);
-  build_tables<LaneLayout, false>(m);
-  return kOk;
-}
-
-// Blocks of one chunk (see the header).  WRITE: the exact rules, and the symbol plane from plane[c.base].
-template <bool WRITE>
-__device__ void stream_decode(const uint8_t* src, uint64_t src_n, uint64_t b0, uint64_t body_n, StreamChunk& c, uint8_t* m,
-                              uint16_t* __restrict__ plane, uint64_t cap) {
-  StreamReader rd;
-  rd.open(src, src_n, b0, body_n, c.start);
-  BitReader& br = rd.br;
-  const uint64_t base = c.base;
-  uint64_t pos = 0;
-  uint32_t st = kOk, fin = 0;
-  while (!fin && rd.abs() < c.limit) {
-    if (br.bitpos > kRebase) rd.open(src, src_n, b0, body_n, rd.abs());
-    if (rd.rem() < 3) { st = kInvalidBlockHeader; break; }
-    br.refill();
-    fin = br.get(1);
-    const uint32_t type = br.get(2);
-    if (type == 3) { st = kInvalidBlockHeader; break; }
-    if (type == 0) {
-      br.drop((8 - (br.bitpos & 7)) & 7);
-      if (rd.rem() < 32) { st = kError; break; }
-      br.refill();
-      const uint32_t len = br.get(16);
-      br.refill();
-      const uint32_t nlen = br.get(16);
-      if ((len ^ nlen) != 0xFFFFu) { st = kNoCompressionLenMismatch; break; }
-      if (rd.rem() < 8 * len) { st = kSrcTooSmall; break; }
-      const uint32_t rel = br.bitpos >> 3;
-      if (WRITE) {
-        if (cap - (base + pos) < len) { st = kDstTooSmall; break; }
-        if (pos + len > c.out) { st = kError; break; }  // (the count pass saw fewer bytes: never)
-        const uint8_t* from = src + b0 + (rd.rb >> 3) + rel;
-        for (uint32_t k = 0; k < len; ++k) plane[base + pos + k] = from[k];
-      }
-      pos += len;
-      br.bitpos += 8 * len;
-      br.seek(rel + len);
-      continue;
-    }
-    if (type == 1) {
-      read_lengths<LaneLayout>(br, m, 1);
-      build_tables<LaneLayout, true>(m);
-      build_tables<LaneLayout, false>(m);
-    } else if ((st = serial_dynamic(br, m)) != kOk) {
-      break;
-    }
-    for (;;) {
-      if (br.bitpos > kRebase) rd.open(src, src_n, b0, body_n, rd.abs());
-      br.refill();
-      uint32_t sym;
-      const uint32_t l = decode_symbol<LaneLayout, true>(m, br, sym);
-      if (l == 0 || l > rd.rem()) { st = kInvalidLitOrLen; break; }
-      br.drop(l);
-      if (sym < 256) {
-        if (WRITE) {
-          if (base + pos >= cap) { st = kDstTooSmall; break; }
-          if (pos >= c.out) { st = kError; break; }
-          plane[base + pos] = (uint16_t)sym;
-        }
-        ++pos;
-        continue;
-      }
-      if (sym == 256) break;
-      if (sym > 285) { st = kInvalidLitOrLen; break; }
-      uint32_t lbase, lextra;
-      length_info(sym, lbase, lextra);
-      if (rd.rem() < lextra) { st = kError; break; }
-      const uint32_t len = lbase + br.get(lextra);
-      br.refill();
-      uint32_t dsym;
-      const uint32_t dl = decode_symbol<LaneLayout, false>(m, br, dsym);
-      if (dl == 0 || dl > rd.rem()) { st = kInvalidDistance; break; }
-      br.drop(dl);
-      if (dsym > 29) { st = kInvalidLitOrLen; break; }
-      uint32_t dbase, dextra;
-      distance_info(dsym, dbase, dextra);
-      if (rd.rem() < dextra) { st = kError; break; }
-      const uint32_t dist = dbase + br.get(dextra);
-      if (WRITE) {
-        if (dist > base + pos) { st = kInvalidDistance; break; }
-        if (cap - (base + pos) < len) { st = kDstTooSmall; break; }
-        if (pos + len > c.out) { st = kError; break; }
-        uint16_t* to = plane + base + pos;
-        if (dist <= pos) {
-          const uint16_t* from = to - dist;
-          for (uint32_t k = 0; k < len; ++k) to[k] = from[k];
-        } else {
-          // window bytes first (marker k: byte k of the 32 KiB before O_i), then the chunk's own
-          const int64_t q = (int64_t)pos - (int64_t)dist;
-          for (uint32_t k = 0; k < len; ++k) {
-            const int64_t p = q + k;
-            to[k] = p < 0 ? (uint16_t)(0x8000u | (uint32_t)(kWin + p)) : plane[base + (uint64_t)p];
-          }
-        }
-      }
-      pos += len;
-    }
-    if (st != kOk) break;
-  }
-  c.end = rd.abs();
-  c.status = st;
-  c.final_ = fin;
-  if (!WRITE) c.out = pos;
-}
 
 __global__ __launch_bounds__(KF_THREADS) void k_stream_find(const uint8_t* __restrict__ src, uint64_t src_n, uint64_t b0,
                                                             uint64_t body_n, uint64_t step_bits, uint32_t nc,
@@ -263,25 +91,6 @@ __global__ __launch_bounds__(KS_LANES) void k_stream_decode(const uint8_t* __res
     b.start = a.end;
     stream_decode<false>(src, src_n, b0, body_n, b, tab, plane, cap);  // (b.start >= b.limit: an empty chunk)
   }
-}
-
-// T <- the window after chunk c, from T = the window before it (entries: literal bytes, or 0x8000 | k, entry k of a base window)
-__device__ __forceinline__ void window_step(uint16_t* T, const uint16_t* __restrict__ plane, const StreamChunk& c) {
-  uint16_t v[kPerThread];
-#pragma unroll
-  for (uint32_t r = 0; r < kPerThread; ++r) {
-    const uint32_t j = r * KR_THREADS + threadIdx.x;
-    if (c.out + j < kWin) {
-      v[r] = T[c.out + j];
-    } else {
-      const uint16_t x = plane[c.base + c.out + j - kWin];
-      v[r] = x < 256 ? x : T[x & 0x7FFFu];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (uint32_t r = 0; r < kPerThread; ++r) T[r * KR_THREADS + threadIdx.x] = v[r];
-  __syncthreads();
 }
 
 // group g (all but the last): the composite map of its chunks over the window before its first chunk (group 0: the window

@@ -15,22 +15,21 @@ struct StreamChunk {
 };
 static_assert(sizeof(StreamChunk) == 48, "stream chunk record");
 
-// C on the host: one round over the chunk records (rec[i].start / .limit are the chunks as decoded; an empty chunk is settled
-// here).  Returns the chunks to decode again; *chain: the confirmed chunks so far (the last one ends the stream or failed)
-// when the list is empty.
-inline std::vector<uint32_t> stream_chain_round(std::vector<StreamChunk>& rec, uint32_t* chain) {
-  std::vector<uint32_t> redo;
-  const uint32_t m = (uint32_t)rec.size();
+// C on the host: one round over the chunk records rec[r0, r0 + m) of one stream (rec[i].start / .limit are the chunks as
+// decoded; an empty chunk is settled here).  Appends the chunks to decode again to redo (indices into rec); *chain: the
+// confirmed chunks so far (the last one ends the stream or failed) when none was appended.  A batched call keeps every
+// item's records in one array and runs this over each item's slice.
+inline void stream_chain_round(StreamChunk* rec, uint32_t r0, uint32_t m, std::vector<uint32_t>& redo, uint32_t* chain) {
   uint32_t confirmed = 1;
   bool broken = false;
   for (uint32_t i = 0; i + 1 < m; ++i) {
-    StreamChunk& a = rec[i];
+    StreamChunk& a = rec[r0 + i];
     if (a.status != 0 || a.final_) {
       if (!broken) break;  // the chain ends here
       continue;
     }
-    if (a.end != rec[i + 1].start) {
-      StreamChunk& b = rec[i + 1];
+    if (a.end != rec[r0 + i + 1].start) {
+      StreamChunk& b = rec[r0 + i + 1];
       b.start = a.end;
       a.limit = a.end;  // (a stopped at its first block end at or beyond it: the same decode)
       if (b.start >= b.limit) {  // nothing of b's range is left: an empty chunk, settled here
@@ -39,7 +38,7 @@ inline std::vector<uint32_t> stream_chain_round(std::vector<StreamChunk>& rec, u
         b.status = 0;
         b.final_ = 0;
       } else {
-        redo.push_back(i + 1);
+        redo.push_back(r0 + i + 1);
         broken = true;
         ++i;  // b's record is stale until it is decoded again
         continue;
@@ -48,6 +47,12 @@ inline std::vector<uint32_t> stream_chain_round(std::vector<StreamChunk>& rec, u
     if (!broken) ++confirmed;
   }
   *chain = confirmed;
+}
+
+// The same over all of rec (one stream).  Returns the chunks to decode again.
+inline std::vector<uint32_t> stream_chain_round(std::vector<StreamChunk>& rec, uint32_t* chain) {
+  std::vector<uint32_t> redo;
+  stream_chain_round(rec.data(), 0, (uint32_t)rec.size(), redo, chain);
   return redo;
 }
 
