@@ -78,6 +78,8 @@ struct stream_index {
   std::vector<std::uint64_t> offsets;  // segments + 1
   std::vector<std::uint32_t> regions;  // segments * 64, or empty
   std::uint32_t block_bytes{SFH_SEGMENT_BYTES};  // strip size the stream was written with
+  std::uint64_t total_bytes{0};        // the stream's whole output size: filled by compressor::index() and recover_index(),
+                                       // read by decompress_range[s] (segments() == max(1, ceil(total_bytes / 32768)))
   [[nodiscard]] auto segments() const -> std::size_t { return offsets.empty() ? 0 : offsets.size() - 1; }
 };
 
@@ -126,18 +128,20 @@ class compressor {
   sfh_ctx* ctx_{nullptr};
   CompressStatus init_{CompressStatus::Success};
   std::vector<std::uint64_t> batch_n_;  // the items' sizes of the last compress_batch() (what batch_index() cuts the index by)
+  std::uint64_t last_n_{0};             // the input size of the last single compress call (index().total_bytes)
 
  public:
   explicit compressor(int device = 0) { init_ = detail::to_status(sfh_create(&ctx_, device)); }
   compressor(const compressor&) = delete;
   auto operator=(const compressor&) -> compressor& = delete;
-  compressor(compressor&& o) noexcept : ctx_{std::exchange(o.ctx_, nullptr)}, init_{o.init_}, batch_n_{std::move(o.batch_n_)} {}
+  compressor(compressor&& o) noexcept : ctx_{std::exchange(o.ctx_, nullptr)}, init_{o.init_}, batch_n_{std::move(o.batch_n_)}, last_n_{o.last_n_} {}
   auto operator=(compressor&& o) noexcept -> compressor& {
     if (this != &o) {
       sfh_destroy(ctx_);
       ctx_ = std::exchange(o.ctx_, nullptr);
       init_ = o.init_;
       batch_n_ = std::move(o.batch_n_);
+      last_n_ = o.last_n_;
     }
     return *this;
   }
@@ -153,6 +157,7 @@ class compressor {
     std::size_t n = 0;
     const int rc = sfh_compress(ctx_, src.data(), src.size(), dst.data(), dst.size(), &n, &c);
     if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+    last_n_ = src.size();
     return n;
   }
   /// host spans, many independent items in one call: item i's stream goes to dsts[i] (dsts[i].size() >=
@@ -237,6 +242,7 @@ class compressor {
     if (n == 0) return compat::unexpected{CompressStatus::InvalidArgument};
     ix.offsets.resize(n);
     ix.block_bytes = sfh_last_block_bytes(ctx_);
+    ix.total_bytes = last_n_;
     int rc = sfh_copy_index(ctx_, ix.offsets.data(), n, 0, nullptr);
     if (rc == SFH_OK && with_regions) {
       ix.regions.resize((n - 1) * SFH_SUBINDEX_WORDS);
@@ -257,6 +263,43 @@ class compressor {
     if (rc != SFH_OK || st > 7) return DecompressStatus::Error;
     return static_cast<DecompressStatus>(st);
   }
+  /// Random access: output bytes [offset, offset + dst.size()) of an indexed stream whose whole output is ix.total_bytes
+  /// bytes (index() fills it in; an index from elsewhere sets it), for roughly what they hold: only the range's decode span -- from the
+  /// start of the strip (ix.block_bytes) that holds its first byte to the segment that holds its last -- is uploaded and
+  /// decoded (sfh_decompress_ranges).  The status is that of the span's first failing segment; dst is written only on
+  /// Success.  A refused call (arguments) or a problem on the device side is DecompressStatus::Error, as in decompress().
+  auto decompress_range(std::span<const std::byte> src, std::span<std::byte> dst, const stream_index& ix, std::uint64_t offset)
+      -> DecompressStatus {
+    const std::span<std::byte> d[1] = {dst};
+    DecompressStatus st = DecompressStatus::Error;
+    if (decompress_ranges(src, ix, std::span<const std::uint64_t>{&offset, 1}, d, std::span<DecompressStatus>{&st, 1}) !=
+        CompressStatus::Success)
+      return DecompressStatus::Error;
+    return st;
+  }
+  /// Many ranges of one stream in one call: bytes [offsets[r], offsets[r] + dsts[r].size()) into dsts[r] (any addresses, not
+  /// overlapping; ranges may overlap each other), range r's status into statuses[r]; one range's failure changes no other.
+  /// A refused call (arguments, no device) is the return value, as with decompress_batch(); the statuses are then not written.
+  auto decompress_ranges(std::span<const std::byte> src, const stream_index& ix, std::span<const std::uint64_t> offsets,
+                         std::span<const std::span<std::byte>> dsts, std::span<DecompressStatus> statuses) -> CompressStatus {
+    if (!ctx_) return init_;
+    const std::size_t k = offsets.size();
+    if (dsts.size() != k || statuses.size() != k || ix.offsets.size() < 2 ||
+        (!ix.regions.empty() && ix.regions.size() != ix.segments() * SFH_SUBINDEX_WORDS))
+      return CompressStatus::InvalidArgument;
+    std::vector<void*> dp(k);
+    std::vector<std::uint64_t> len(k);
+    std::vector<std::uint32_t> st(k);
+    for (std::size_t i = 0; i < k; ++i) {
+      dp[i] = dsts[i].data();
+      len[i] = dsts[i].size();
+    }
+    const int rc = sfh_decompress_ranges(ctx_, src.data(), src.size(), ix.offsets.data(), ix.regions.empty() ? nullptr : ix.regions.data(),
+                                         ix.segments(), ix.total_bytes, ix.block_bytes, k, offsets.data(), len.data(), dp.data(), st.data());
+    if (rc != SFH_OK) return detail::to_status(rc);
+    for (std::size_t i = 0; i < k; ++i) statuses[i] = st[i] > 7 ? DecompressStatus::Error : static_cast<DecompressStatus>(st[i]);
+    return CompressStatus::Success;
+  }
   /// The index of a stream given alone, recovered on the GPU from its flush markers: offsets of its
   /// max(1, ceil(dst_size / 32768)) segments + 1; block_bytes 0 (unknown), no regions.  A stream that is not block-flushed
   /// every 32 KiB is CompressStatus::NotIndexable.
@@ -267,6 +310,7 @@ class compressor {
     const std::size_t nseg = dst_size ? (dst_size + SFH_SEGMENT_BYTES - 1) / SFH_SEGMENT_BYTES : 1;
     ix.offsets.resize(nseg + 1);
     ix.block_bytes = 0;
+    ix.total_bytes = dst_size;
     const int rc = sfh_recover_index(ctx_, src.data(), src.size(), static_cast<std::uint32_t>(container), dst_size,
                                      ix.offsets.data(), nseg, nullptr);
     if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
@@ -345,6 +389,7 @@ class compressor {
     std::size_t out = 0;
     const int rc = sfh_compress_device(ctx_, d_src, n, d_dst, cap, &out, &c, stream);
     if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+    last_n_ = n;
     return out;
   }
   /// enqueue only: the stream size is left in *d_out_n, a device word (what gather_streams reads)
@@ -352,7 +397,9 @@ class compressor {
                              const compress_options& opt = {}, void* stream = nullptr) -> CompressStatus {
     if (!ctx_) return init_;
     const auto c = detail::to_c(opt);
-    return detail::to_status(sfh_compress_device_async(ctx_, d_src, n, d_dst, cap, d_out_n, &c, stream));
+    const int rc = sfh_compress_device_async(ctx_, d_src, n, d_dst, cap, d_out_n, &c, stream);
+    if (rc == SFH_OK) last_n_ = n;
+    return detail::to_status(rc);
   }
 
   /// One process per GPU: what every rank of an RCCL communicator calls after compressing its shard (whole strips,

@@ -348,6 +348,52 @@ int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, co
                          const uint64_t* index, const uint32_t* subindex, void* const* dsts, const uint64_t* dst_n,
                          const uint32_t* block_bytes, uint32_t container, uint32_t* status);
 
+/* ---- random access: byte ranges of one indexed stream's output, decoded for roughly what they hold ----
+ * The stream, its index, sub-index (or NULL) and block_bytes are sfh_decompress_device's; total_n is the stream's whole
+ * output size and nseg == max(1, ceil(total_n / 32768)).  Range r is output bytes [offsets[r], offsets[r] + lengths[r]); with
+ * status[r] == 0, dsts[r][0, lengths[r]) holds exactly those bytes of what sfh_decompress_device writes for the whole
+ * stream.  Offsets, lengths and destination addresses need no alignment (ranges can be gathered into a packed buffer); source
+ * ranges may overlap each other, destination ranges [dsts[r], dsts[r] + lengths[r]) may not.  A range of no bytes is status 0
+ * and writes nothing.
+ * Work: the DECODE SPAN of a range is the segments from the first one of the strip (block_bytes of output) that holds its
+ * first byte to the one that holds its last byte.  Only the spans' segments get tokens and are walked by the byte stage; those
+ * in front of the range's first byte are resolved in LDS only (a match may reach back to the strip's start), and nothing of
+ * them reaches global memory but their tokens.  With block_bytes = 32768 a range inside one segment costs that segment.  Every
+ * range is decoded by itself: ranges that share a strip each pay for their span.  The spans run in launch batches of whole
+ * strips, at most SFH_BATCH_CHUNKS segments each (a larger strip is a batch of its own): the token scratch is one batch's
+ * (sfh_last_decode_scratch_bytes); sfh_last_inflate_ms sums both stages over the batches.
+ * status[r]: the DecompressStatus of the first failing segment of r's decode span in stream order, 0 when none fails; a
+ * segment must produce exactly its 32768 bytes (the stream's last one its remainder), and a wrong sub-index is an error, never
+ * wrong bytes.  Damage outside a range's decode span changes neither its bytes nor its status; one range's failure changes no
+ * other range.  No checksum is verified (a range cannot verify one).  The stream may be wrapped: the index's offsets include
+ * the header, and the trailer is never read.  Nothing is written outside [dsts[r], dsts[r] + lengths[r]).
+ * Refused before anything is enqueued (SFH_E_INVALID_ARG): a null context; with count > 0 a null stream, index or array, or a
+ * null destination with a non-zero length; offsets[r] + lengths[r] above total_n (or overflowing); total_n above 2^44; nseg
+ * not matching total_n; a bad block_bytes; a device pointer out of alignment (d_src 4, d_index 8, d_subindex 4, d_status 4);
+ * overlapping destinations; decode spans of more than 2^31 - 1 segments altogether.  count == 0: SFH_OK.  Afterwards the
+ * context has no index, as after sfh_decompress*.
+ *
+ * Device buffers, enqueued on `stream` (NULL: the context's), no host synchronisation; the host arrays (offsets, lengths,
+ * d_dsts) are read before the call returns; d_status: device uint32[count]. */
+int sfh_decompress_ranges_device_async(sfh_ctx* ctx, const void* d_src, size_t src_n, const uint64_t* d_index,
+                                       const uint32_t* d_subindex, size_t nseg, uint64_t total_n, uint32_t block_bytes,
+                                       size_t count, const uint64_t* offsets, const uint64_t* lengths, void* const* d_dsts,
+                                       uint32_t* d_status, void* stream);
+/* One range; synchronises `stream`, *status on the host. */
+int sfh_decompress_range_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const uint64_t* d_index,
+                                const uint32_t* d_subindex, size_t nseg, uint64_t total_n, uint32_t block_bytes,
+                                uint64_t offset, uint64_t length, void* d_dst, uint32_t* status, void* stream);
+/* Host buffers, synchronous: the stream, index, sub-index and destinations on the host, status[count] on the host; dsts[r] is
+ * written only when status[r] == 0.  The whole stream is NOT uploaded: for every decode span only its stream bytes go up --
+ * from the smallest to the largest of its index entries (in a sound index: [index[first], index[last + 1])), clipped to
+ * src_n and rounded out to 16 bytes -- packed, piece after piece, through the pinned staging, with the span's index entries
+ * and sub-index words.  The index offsets stay offsets into the stream: every row of a span carries a stream base that
+ * points as far in front of the span's piece as the piece's first byte lies in the stream (a per-span InflateSeg.src), and
+ * a stream size that ends with the piece, so what the kernels read at base + offset is the uploaded copy. */
+int sfh_decompress_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uint64_t* index, const uint32_t* subindex,
+                          size_t nseg, uint64_t total_n, uint32_t block_bytes, size_t count, const uint64_t* offsets,
+                          const uint64_t* lengths, void* const* dsts, uint32_t* status);
+
 /* ---- decoding without side information ----
  * The segment index of a stream that is flushed every 32 KiB of output -- every stream sfh_compress* writes, and zlib's with
  * Z_SYNC_FLUSH / Z_FULL_FLUSH every 32768 input bytes -- recovered from the stream itself: a coded segment ends with the empty

@@ -5,8 +5,8 @@ torch plumbing for device buffers, the multi-GPU shard/concat helper and the
 synthetic corpora used by tests and bench.py.
 """
 from .compressor import (CHUNK_BYTES, Compressor, StarflateError, checksum_combine, compress, compress_batch,  # noqa: F401
-                         compress_multi, decompress, decompress_batch, decompress_stream, decompress_stream_batch,
-                         wrapper_bytes)
+                         compress_multi, decompress, decompress_batch, decompress_range, decompress_ranges,
+                         decompress_stream, decompress_stream_batch, wrapper_bytes)
 
-__all__ = ["Compressor", "StarflateError", "compress", "CHUNK_BYTES", "checksum_combine", "wrapper_bytes", "compress_multi", "compress_batch", "decompress", "decompress_batch", "decompress_stream",
+__all__ = ["Compressor", "StarflateError", "compress", "CHUNK_BYTES", "checksum_combine", "wrapper_bytes", "compress_multi", "compress_batch", "decompress", "decompress_batch", "decompress_range", "decompress_ranges", "decompress_stream",
            "decompress_stream_batch"]

@@ -30,6 +30,7 @@ EXPORTS = [
     "sfh_compress_bound", "sfh_compress", "sfh_compress_multi", "sfh_compress_device", "sfh_compress_device_async",
     "sfh_compress_batch_device_async", "sfh_compress_batch", "sfh_batch_index_size", "sfh_copy_batch_index",
     "sfh_decompress_batch_device_async", "sfh_decompress_batch",
+    "sfh_decompress_ranges_device_async", "sfh_decompress_range_device", "sfh_decompress_ranges",
     "sfh_recover_index_device", "sfh_recover_index", "sfh_decompress_any_device", "sfh_decompress_any", "sfh_last_recover_stats",
     "sfh_inflate_stream_device", "sfh_inflate_stream", "sfh_inflate_stream_batch_device", "sfh_inflate_stream_batch",
     "sfh_last_stream_stats",
@@ -110,6 +111,13 @@ def lib():
     L.sfh_decompress_batch_device_async.restype = C.c_int
     L.sfh_decompress_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, vp, vp, C.POINTER(vp), u64p, vp, C.c_uint32, vp]
     L.sfh_decompress_batch.restype = C.c_int
+    L.sfh_decompress_ranges_device_async.argtypes = [vp, vp, sz, vp, vp, sz, C.c_uint64, C.c_uint32, sz, u64p, u64p, C.POINTER(vp), vp, vp]
+    L.sfh_decompress_ranges_device_async.restype = C.c_int
+    L.sfh_decompress_range_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, vp,
+                                              C.POINTER(C.c_uint32), vp]
+    L.sfh_decompress_range_device.restype = C.c_int
+    L.sfh_decompress_ranges.argtypes = [vp, vp, sz, vp, vp, sz, C.c_uint64, C.c_uint32, sz, u64p, u64p, C.POINTER(vp), vp]
+    L.sfh_decompress_ranges.restype = C.c_int
     L.sfh_recover_index_device.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint64, vp, sz, vp, vp]
     L.sfh_recover_index_device.restype = C.c_int
     L.sfh_recover_index.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint64, vp, sz, vp]

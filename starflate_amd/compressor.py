@@ -481,6 +481,66 @@ class Compressor:
             bb.ctypes.data if bb is not None else None, kind, C.c_void_p(status.data_ptr()), C.c_void_p(s)))
         return outs, status[:k]
 
+    # ---- random access: byte ranges of one indexed stream's output (sfh_decompress_range*) ----
+    def decompress_range(self, data, index, total_n, offset, length, subindex=None, *, block_bytes):
+        """Host buffers: output bytes [offset, offset + length) of an indexed stream -> (bytes, DecompressStatus int); b"" when
+        the status is not 0.  Only the range's decode span is uploaded and decoded (decompress_ranges)."""
+        outs, st = self.decompress_ranges(data, index, total_n, [offset], [length], subindex, block_bytes=block_bytes)
+        return (outs[0] if outs[0] is not None else b""), int(st[0])
+
+    def decompress_ranges(self, data, index, total_n, offsets, lengths, subindex=None, *, block_bytes):
+        """Host buffers: bytes-like stream, numpy uint64 index of segments + 1 entries [+ uint32 sub-index], the stream's whole
+        output size and the ranges -> (list of bytes, None where a range's status is not 0; uint32 status array).  Of the
+        stream only the ranges' decode spans travel to the device: from the start of the strip (block_bytes, required as in
+        decompress) holding a range's first byte to the segment holding its last."""
+        src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).ravel()
+        idx = np.ascontiguousarray(index, dtype=np.uint64).ravel()
+        sub = None if subindex is None else np.ascontiguousarray(subindex, dtype=np.uint32).ravel()
+        total_n, offs, lens, nseg = _range_lengths(total_n, offsets, lengths, idx.size, None if sub is None else sub.size, block_bytes)
+        k = len(offs)
+        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in lens]
+        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
+        st = np.zeros(max(k, 1), dtype=np.uint32)
+        self._check(self._lib.sfh_decompress_ranges(
+            self._h, src.ctypes.data if src.size else None, src.size, idx.ctypes.data, sub.ctypes.data if sub is not None else None,
+            nseg, total_n, int(block_bytes), k, (C.c_uint64 * k)(*offs), (C.c_uint64 * k)(*lens), dp, st.ctypes.data))
+        return [dsts[i][: lens[i]].tobytes() if st[i] == 0 else None for i in range(k)], st[:k]
+
+    def decompress_ranges_tensors(self, stream, index, total_n, offsets, lengths, outs=None, subindex=None, hip_stream=None, *,
+                                  block_bytes):
+        """Device buffers: stream (1-D uint8 CUDA tensor), index (int64 CUDA tensor of segments + 1 offsets), optional
+        subindex (int32 CUDA tensor of segments * 64 words) -> (outs, status).  Enqueued on hip_stream (default: the current
+        one) without a host synchronisation.  outs: one uint8 tensor (or view, any alignment: slices of one packed buffer will
+        do) of at least lengths[i] bytes per range, not overlapping (default: new ones); range i's bytes are
+        outs[i][:lengths[i]]; status: an int32 tensor on the device, one DecompressStatus per range."""
+        import torch
+
+        self._check_tensor(stream)
+        for t, dt in ((index, torch.int64), (subindex, torch.int32)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+                raise ValueError("index / subindex must be contiguous int64 / int32 CUDA tensors")
+        if index is None:
+            raise ValueError("an index is required")
+        total_n, offs, lens, nseg = _range_lengths(total_n, offsets, lengths, index.numel(),
+                                                   None if subindex is None else subindex.numel(), block_bytes)
+        k = len(offs)
+        dev = torch.device("cuda", self.device)
+        if outs is None:
+            outs = [torch.empty(max(m, 1), dtype=torch.uint8, device=dev) for m in lens]
+        outs = list(outs)
+        if len(outs) != k or any(o.numel() < m for o, m in zip(outs, lens)):
+            raise ValueError("outs must hold one tensor of at least lengths[i] bytes per range")
+        for t in outs:
+            self._check_tensor(t)
+        status = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+        dp = (C.c_void_p * k)(*[o.data_ptr() for o in outs])
+        s = torch.cuda.current_stream(dev).cuda_stream if hip_stream is None else hip_stream
+        self._check(self._lib.sfh_decompress_ranges_device_async(
+            self._h, stream.data_ptr(), stream.numel(), index.data_ptr(), subindex.data_ptr() if subindex is not None else None,
+            nseg, total_n, int(block_bytes), k, (C.c_uint64 * k)(*offs), (C.c_uint64 * k)(*lens), dp,
+            C.c_void_p(status.data_ptr()), C.c_void_p(s)))
+        return outs, status[:k]
+
     def inflate_ms(self):
         ms = (C.c_float * _capi.INFLATE_NSTAGES)()
         self._check(self._lib.sfh_last_inflate_ms(self._h, C.byref(ms)))
@@ -630,6 +690,35 @@ def _batch_lengths(k, sizes, index_n, subindex_n, block_bytes, container):
     return dst_n, bb, _capi.CONTAINER[container]
 
 
+def _range_lengths(total_n, offsets, lengths, index_n, subindex_n, block_bytes):
+    """decompress_ranges' lengths, checked before anything reaches the device: the stream's output size, the ranges, the
+    entries of the index and the words of the sub-index (None: not given) -> (total_n, offsets list, lengths list, segments)."""
+    total_n = int(total_n)
+    if total_n < 0 or total_n > (1 << 44):
+        raise ValueError("total_n must lie in [0, 2^44]")
+    offs, lens = [int(v) for v in offsets], [int(v) for v in lengths]
+    if len(offs) != len(lens):
+        raise ValueError(f"{len(offs)} offsets but {len(lens)} lengths")
+    for o, m in zip(offs, lens):
+        if o < 0 or m < 0 or o + m > total_n:
+            raise ValueError(f"range [{o}, {o} + {m}) does not lie inside the stream's {total_n} bytes of output")
+    nseg = max(1, -(-total_n // CHUNK_BYTES))
+    if index_n != nseg + 1:
+        raise ValueError(f"index must hold segments + 1 = {nseg + 1} entries, not {index_n}")
+    if subindex_n is not None and subindex_n != nseg * _capi.SUBINDEX_WORDS:
+        raise ValueError(f"subindex must hold {nseg * _capi.SUBINDEX_WORDS} words, not {subindex_n}")
+    bb = int(block_bytes)
+    if bb < 0 or bb % CHUNK_BYTES or bb > (1 << 24):
+        raise ValueError("block_bytes: a multiple of 32768 up to 16 MiB (0 = 32768)")
+    return total_n, offs, lens, nseg
+
+
+def _range_args(index, total_n, offsets, lengths, subindex, block_bytes):
+    idx = np.ascontiguousarray(index, dtype=np.uint64).ravel()
+    sub = None if subindex is None else np.ascontiguousarray(subindex, dtype=np.uint32).ravel()
+    return _range_lengths(total_n, offsets, lengths, idx.size, None if sub is None else sub.size, block_bytes)
+
+
 def _batch_inflate_args(streams, sizes, index, subindex, block_bytes, container):
     """decompress_batch's host arguments, checked (_batch_lengths): (sources, src_n, dst_n, index, subindex, block_bytes,
     container) as the C-ABI takes them."""
@@ -737,3 +826,26 @@ def decompress_stream_batch(streams, sizes=None, container="raw", device=0):
     if c is None:
         c = _DEFAULT[device] = Compressor(device)
     return c.decompress_stream_batch(streams, sizes, container)
+
+
+def decompress_range(data, index, total_n, offset, length, subindex=None, *, block_bytes, device=0):
+    """Output bytes [offset, offset + length) of an indexed stream -> bytes (Compressor.decompress_range).  The arguments are
+    checked before a device is touched; a status other than Success raises StarflateError."""
+    _range_args(index, total_n, [offset], [length], subindex, block_bytes)
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    out, st = c.decompress_range(data, index, total_n, offset, length, subindex, block_bytes=block_bytes)
+    if st:
+        raise StarflateError(st, f"DecompressStatus {st}")
+    return out
+
+
+def decompress_ranges(data, index, total_n, offsets, lengths, subindex=None, *, block_bytes, device=0):
+    """Many ranges of one indexed stream -> (list of bytes or None, status array), all in one call
+    (Compressor.decompress_ranges).  The arguments are checked before a device is touched."""
+    _range_args(index, total_n, offsets, lengths, subindex, block_bytes)
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    return c.decompress_ranges(data, index, total_n, offsets, lengths, subindex, block_bytes=block_bytes)

@@ -3,6 +3,7 @@
 #include "../../include/starflate_hip.h"
 #include "sf_device.h"
 #include "sf_inflate_core.h"
+#include "sf_range_plan.h"
 
 #include <dlfcn.h>
 #include <stdio.h>
@@ -774,6 +775,150 @@ int enqueue_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs,
   if (container) SF_HIP(sf::launch_checksum_batch(t_sums, nseg, container, ctx->ws.sums, s), "launch k_checksum");
   SF_HIP(sf::launch_inflate_fold(t_items, (uint32_t)count, ctx->ws.seginfo, ctx->ws.sums, container, d_status, s), "launch k_inflate_fold");
   return mark_call_end(ctx, s);
+}
+
+// ---- random access (sfh_decompress_range*) ----
+// Everything the call checks before it plans or enqueues anything (`dev`: device buffers, the decoder's alignment rules; dsts
+// are free of them).
+int check_ranges(sfh_ctx* ctx, const void* src, const uint64_t* index, const uint32_t* subindex, size_t nseg, uint64_t total_n,
+                 uint32_t block_bytes, size_t count, const uint64_t* offsets, const uint64_t* lengths, void* const* dsts,
+                 const uint32_t* status, bool dev) {
+  if (!ctx) return fail(ctx, SFH_E_INVALID_ARG, "argument (context)", hipSuccess);
+  if (count == 0) return SFH_OK;
+  if (!src || !index || !offsets || !lengths || !dsts || !status) return fail(ctx, SFH_E_INVALID_ARG, "null array", hipSuccess);
+  if (count > ((size_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "too many ranges", hipSuccess);
+  if (total_n > sf::range::kMaxTotal || nseg != (size_t)sf::range::segments_of(total_n))
+    return fail(ctx, SFH_E_INVALID_ARG, "nseg != max(1, ceil(total_n / 32768))", hipSuccess);
+  if (block_bytes % sf::kChunk || block_bytes > sf::kMaxStrip)
+    return fail(ctx, SFH_E_INVALID_ARG, "block_bytes: a multiple of 32768 up to 16 MiB (0 = 32768)", hipSuccess);
+  if (dev && (((uintptr_t)src & 3) || ((uintptr_t)index & 7) || ((uintptr_t)subindex & 3) || ((uintptr_t)status & 3)))
+    return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, index 8, sub-index 4, status 4)", hipSuccess);
+  for (size_t r = 0; r < count; ++r) {
+    if (!dsts[r] && lengths[r]) return fail(ctx, SFH_E_INVALID_ARG, "null destination", hipSuccess);
+    if (offsets[r] > total_n || lengths[r] > total_n - offsets[r])
+      return fail(ctx, SFH_E_INVALID_ARG, "a range ends behind total_n", hipSuccess);
+  }
+  std::vector<size_t> ord;
+  try {
+    ord.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  // (a destination of no bytes is written nothing and overlaps nothing: it is left out)
+  size_t m = 0;
+  for (size_t r = 0; r < count; ++r)
+    if (lengths[r]) ord[m++] = r;
+  std::sort(ord.begin(), ord.begin() + (std::ptrdiff_t)m, [&](size_t a, size_t b) { return (uintptr_t)dsts[a] < (uintptr_t)dsts[b]; });
+  for (size_t k = 1; k < m; ++k)
+    if ((uintptr_t)dsts[ord[k - 1]] + lengths[ord[k - 1]] > (uintptr_t)dsts[ord[k]])
+      return fail(ctx, SFH_E_INVALID_ARG, "destination ranges overlap", hipSuccess);
+  return SFH_OK;
+}
+
+int plan_ranges_checked(sfh_ctx* ctx, uint64_t total_n, uint32_t block_bytes, size_t count, const uint64_t* offsets,
+                        const uint64_t* lengths, sf::range::Plan& P) {
+  try {
+    const int pr = sf::range::plan_ranges(total_n, block_bytes, count, offsets, lengths, ctx->batch_chunks, P);
+    if (pr == sf::range::kPlanTooMany)
+      return fail(ctx, SFH_E_INVALID_ARG, "decode spans of more than 2^31 - 1 segments in one call", hipSuccess);
+    if (pr) return fail(ctx, SFH_E_INVALID_ARG, "argument (ranges)", hipSuccess);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory for the range plan", hipSuccess);
+  }
+  return SFH_OK;
+}
+
+// What the rows of one range's decode span read: the stream base its index entries are offsets into and the bytes readable
+// from it, the index entry and (or null) the sub-index words of the span's FIRST segment -- the later rows' follow.
+struct RangeSource {
+  const uint8_t* src;
+  uint64_t src_n;
+  const uint64_t* ix;
+  const uint32_t* sub;
+};
+
+// Device buffers, arguments checked, the plan made.  The host builds the tables -- per row its InflateSeg and its write
+// window, per strip, per range its span -- and uploads them in one copy; then the token kernels (as they are, over the rows)
+// and the clipped byte stage batch after batch, and the fold of every range's status.
+int enqueue_ranges(sfh_ctx* ctx, const sf::range::Plan& P, const RangeSource* from, void* const* d_dsts, size_t count, bool sub,
+                   uint32_t* d_status, hipStream_t s) {
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();  // see enqueue()
+  const size_t nrows = P.rows.size(), nstrips = P.strips.size();
+  const size_t b_segs = nrows * sizeof(sf::InflateSeg), b_clips = nrows * sizeof(sf::InflateClip);
+  const size_t b_strips = nstrips * sizeof(sf::InflateStrip), b_spans = count * sizeof(sf::InflateSpan);
+  const size_t bytes = b_segs + b_clips + b_strips + b_spans;
+  int rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, nrows * sizeof(sf::SegInfo), "segment records");
+  if (!rc) rc = ensure_dtok(ctx, P.widest);
+  if (!rc) rc = stage_tables(ctx, bytes);
+  if (rc) return rc;
+  sf::InflateSeg* h_segs = (sf::InflateSeg*)ctx->h_tab;
+  sf::InflateClip* h_clips = (sf::InflateClip*)(ctx->h_tab + b_segs);
+  sf::InflateStrip* h_strips = (sf::InflateStrip*)(ctx->h_tab + b_segs + b_clips);
+  sf::InflateSpan* h_spans = (sf::InflateSpan*)(ctx->h_tab + b_segs + b_clips + b_strips);
+  for (size_t g = 0; g < nrows; ++g) {
+    const sf::range::Row& w = P.rows[g];
+    const RangeSource& f = from[w.range];
+    const size_t k = g - P.spans[w.range].row0;
+    h_segs[g] = sf::InflateSeg{f.src, f.ix + k, sub ? f.sub + k * SFH_SUBINDEX_WORDS : nullptr, nullptr, f.src_n, w.out_n, w.hist};
+    h_clips[g] = sf::InflateClip{(uint8_t*)d_dsts[w.range] + w.dst_off, w.lo, w.hi};
+  }
+  for (size_t k = 0; k < nstrips; ++k) h_strips[k] = sf::InflateStrip{P.strips[k].row0, P.strips[k].nrows};
+  for (size_t r = 0; r < count; ++r) h_spans[r] = sf::InflateSpan{P.spans[r].row0, P.spans[r].nrows};
+  const sf::InflateSeg* t_segs = (const sf::InflateSeg*)ctx->d_tab;
+  const sf::InflateClip* t_clips = (const sf::InflateClip*)(ctx->d_tab + b_segs);
+  const sf::InflateStrip* t_strips = (const sf::InflateStrip*)(ctx->d_tab + b_segs + b_clips);
+  const sf::InflateSpan* t_spans = (const sf::InflateSpan*)(ctx->d_tab + b_segs + b_clips + b_strips);
+
+  ctx->index_valid = false;
+  ctx->bix_valid = false;
+  ctx->last_chunks = (uint32_t)nrows;
+  ctx->last_dtok_bytes = (size_t)P.widest * sf::kChunk * sizeof(uint32_t);
+  const bool prof = ctx->profiling != 0;
+  if ((rc = order_behind_last_call(ctx, s)) != SFH_OK) return rc;
+  SF_HIP(hipMemcpyAsync(ctx->d_tab, ctx->h_tab, bytes, hipMemcpyHostToDevice, s), "descriptor tables");
+  SF_HIP(hipEventRecord(ctx->ev_tab, s), "event");
+  ctx->tab_pending = true;
+  const uint32_t nbatches = (uint32_t)P.batches.size();
+  ctx->ev_inf_valid = false;
+  if (prof) {
+    const size_t need = (size_t)nbatches * (SFH_INFLATE_NSTAGES + 1);
+    while (ctx->ev_inf.size() < need) {
+      hipEvent_t e = nullptr;
+      SF_HIP(hipEventCreate(&e), "event");
+      ctx->ev_inf.push_back(e);
+    }
+  }
+  for (uint32_t bi = 0; bi < nbatches; ++bi) {
+    const sf::range::Batch& b = P.batches[bi];
+    sf::SegInfo* binfo = ctx->ws.seginfo + b.row0;
+    hipEvent_t* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
+    if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
+    SF_HIP(sf::launch_inflate_tokens_batch(t_segs + b.row0, b.nrows, ctx->ws.tokens, binfo, sub, !ctx->inflate_serial, s),
+           "launch k_inflate_tokens");
+    if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
+    SF_HIP(sf::launch_inflate_bytes_clip(t_segs + b.row0, t_clips + b.row0, t_strips + b.strip0, b.nstrips, ctx->ws.tokens, binfo, s),
+           "launch k_inflate_bytes_clip");
+    if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
+  }
+  ctx->ev_inf_batches = nbatches;
+  ctx->ev_inf_valid = prof;
+  SF_HIP(sf::launch_inflate_fold_spans(t_spans, (uint32_t)count, ctx->ws.seginfo, d_status, s), "launch k_inflate_fold_spans");
+  return mark_call_end(ctx, s);
+}
+
+// d_bstatus / h_bstatus hold `count` statuses
+int ensure_bstatus(sfh_ctx* ctx, size_t count) {
+  if (ctx->bstatus_cap >= count) return SFH_OK;
+  (void)hipFree(ctx->d_bstatus);
+  if (ctx->h_bstatus) (void)hipHostFree(ctx->h_bstatus);
+  ctx->d_bstatus = ctx->h_bstatus = nullptr;
+  ctx->bstatus_cap = 0;
+  if (hipMalloc(&ctx->d_bstatus, count * sizeof(uint32_t)) != hipSuccess ||
+      hipHostMalloc((void**)&ctx->h_bstatus, count * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+    return fail(ctx, SFH_E_NOMEM, "range statuses", hipSuccess);
+  ctx->bstatus_cap = count;
+  return SFH_OK;
 }
 
 // ---- decoding without side information (sfh_recover_index_device, sfh_decompress_any*) ----
@@ -1955,6 +2100,187 @@ int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, co
       if (status[i] != 0) continue;
       const uint64_t a = std::max(p0, out_off[i]), b = std::min(p1, out_off[i] + dst_n[i]);
       if (a < b) memcpy((uint8_t*)dsts[i] + (a - out_off[i]), ctx->h_stage + (a - p0), b - a);
+    }
+  }
+  return SFH_OK;
+}
+
+int sfh_decompress_ranges_device_async(sfh_ctx* ctx, const void* d_src, size_t src_n, const uint64_t* d_index,
+                                       const uint32_t* d_subindex, size_t nseg, uint64_t total_n, uint32_t block_bytes,
+                                       size_t count, const uint64_t* offsets, const uint64_t* lengths, void* const* d_dsts,
+                                       uint32_t* d_status, void* stream) {
+  int rc = check_ranges(ctx, d_src, d_index, d_subindex, nseg, total_n, block_bytes, count, offsets, lengths, d_dsts, d_status, true);
+  if (rc || count == 0) return rc;
+  sf::range::Plan P;
+  if ((rc = plan_ranges_checked(ctx, total_n, block_bytes, count, offsets, lengths, P)) != SFH_OK) return rc;
+  std::vector<RangeSource> from;
+  try {
+    from.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (size_t r = 0; r < count; ++r) {
+    const uint64_t g = P.spans[r].first_seg;
+    from[r] = RangeSource{(const uint8_t*)d_src, src_n, d_index + g, d_subindex ? d_subindex + g * SFH_SUBINDEX_WORDS : nullptr};
+  }
+  return enqueue_ranges(ctx, P, from.data(), d_dsts, count, d_subindex != nullptr, d_status, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int sfh_decompress_range_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const uint64_t* d_index,
+                                const uint32_t* d_subindex, size_t nseg, uint64_t total_n, uint32_t block_bytes,
+                                uint64_t offset, uint64_t length, void* d_dst, uint32_t* status, void* stream) {
+  if (!ctx || !status) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  void* dsts[1] = {d_dst};
+  uint32_t aligned_status = 0;  // (stands in for the device status word in the argument check)
+  int rc = check_ranges(ctx, d_src, d_index, d_subindex, nseg, total_n, block_bytes, 1, &offset, &length, dsts, &aligned_status, true);
+  if (rc) return rc;
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  if ((rc = ensure_bstatus(ctx, 1)) != SFH_OK) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  rc = sfh_decompress_ranges_device_async(ctx, d_src, src_n, d_index, d_subindex, nseg, total_n, block_bytes, 1, &offset, &length,
+                                          dsts, ctx->d_bstatus, s);
+  if (rc) return rc;
+  SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy status");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  *status = ctx->h_bstatus[0];
+  if (*status) snprintf(ctx->err, sizeof ctx->err, "range [%llu, +%llu): DecompressStatus %u", (unsigned long long)offset,
+                        (unsigned long long)length, *status);
+  return SFH_OK;
+}
+
+int sfh_decompress_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uint64_t* index, const uint32_t* subindex,
+                          size_t nseg, uint64_t total_n, uint32_t block_bytes, size_t count, const uint64_t* offsets,
+                          const uint64_t* lengths, void* const* dsts, uint32_t* status) {
+  int rc = check_ranges(ctx, src, index, subindex, nseg, total_n, block_bytes, count, offsets, lengths, dsts, status, false);
+  if (rc || count == 0) return rc;
+  sf::range::Plan P;
+  if ((rc = plan_ranges_checked(ctx, total_n, block_bytes, count, offsets, lengths, P)) != SFH_OK) return rc;
+  // Per decode span: its piece of the stream -- from the smallest to the largest of its index entries, clipped to src_n and
+  // rounded out to 16 bytes (a damaged index cannot send a row outside its piece: a row reads from its first entry on, and
+  // only when its second entry is not above the bytes readable) --, its index entries and its sub-index words, each packed span
+  // after span.  The destinations are packed as well, 16 bytes apart at least.
+  constexpr size_t kStageBytes = (size_t)kPipeBatchChunks * sf::kChunk;
+  std::vector<uint64_t> p_lo, p_n, in_off, out_off, ix_off;
+  std::vector<RangeSource> from;
+  std::vector<void*> d_dsts;
+  try {
+    p_lo.resize(count);
+    p_n.resize(count);
+    in_off.resize(count + 1);
+    out_off.resize(count + 1);
+    ix_off.resize(count + 1);
+    from.resize(count);
+    d_dsts.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (size_t r = 0; r < count; ++r) {
+    const sf::range::Span& S = P.spans[r];
+    uint64_t lo = 0, hi = 0;
+    if (S.nrows) {
+      lo = hi = index[S.first_seg];
+      for (uint32_t k = 1; k <= S.nrows; ++k) {
+        lo = std::min(lo, index[S.first_seg + k]);
+        hi = std::max(hi, index[S.first_seg + k]);
+      }
+    }
+    lo = std::min<uint64_t>(lo, src_n) / 16 * 16;
+    hi = std::min<uint64_t>(src_n, (std::min<uint64_t>(hi, src_n) + 15) / 16 * 16);
+    p_lo[r] = lo;
+    p_n[r] = hi - lo;
+    in_off[r + 1] = (in_off[r] + p_n[r] + 15) / 16 * 16;
+    out_off[r + 1] = (out_off[r] + lengths[r] + 15) / 16 * 16;
+    ix_off[r + 1] = ix_off[r] + (S.nrows ? S.nrows + 1 : 0);
+  }
+  const size_t nrows = P.rows.size(), entries = (size_t)ix_off[count];
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t s = ctx->stream;
+  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
+  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_off[count] ? out_off[count] : 16, "output staging");
+  if (!rc) rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, (entries ? entries : 1) * sizeof(uint64_t), "index staging");
+  if (!rc && subindex)
+    rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, (nrows ? nrows : 1) * SFH_SUBINDEX_WORDS * sizeof(uint32_t), "sub-index staging");
+  if (!rc) rc = ensure_bstatus(ctx, count);
+  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
+    ctx->h_stage = nullptr;
+    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
+  }
+  if (rc) return rc;
+  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
+  // up: the packed pieces, one copy per kStageBytes
+  size_t item = 0;
+  for (uint64_t p0 = 0; p0 < in_off[count]; p0 += kStageBytes) {
+    const uint64_t p1 = std::min<uint64_t>(in_off[count], p0 + kStageBytes);
+    while (item < count && in_off[item] + p_n[item] <= p0) ++item;
+    for (size_t r = item; r < count && in_off[r] < p1; ++r) {
+      const uint64_t a = std::max(p0, in_off[r]), b = std::min(p1, in_off[r] + p_n[r]);
+      if (a < b) memcpy(ctx->h_stage + (a - p0), (const uint8_t*)src + p_lo[r] + (a - in_off[r]), b - a);
+    }
+    SF_HIP(hipMemcpyAsync(ctx->d_in + p0, ctx->h_stage, p1 - p0, hipMemcpyHostToDevice, s), "H2D");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");  // (the next piece refills h_stage)
+  }
+  // the spans' index entries and sub-index words through the same staging
+  {
+    const size_t per = kStageBytes / sizeof(uint64_t);
+    uint64_t* h = (uint64_t*)ctx->h_stage;
+    size_t filled = 0, base = 0;  // entries in the staging, entries already on the device
+    auto flush = [&]() -> int {
+      if (!filled) return SFH_OK;
+      SF_HIP(hipMemcpyAsync(ctx->d_index + base, h, filled * sizeof(uint64_t), hipMemcpyHostToDevice, s), "H2D index");
+      SF_HIP(hipStreamSynchronize(s), "stream sync");
+      base += filled;
+      filled = 0;
+      return SFH_OK;
+    };
+    for (size_t r = 0; r < count; ++r) {
+      const sf::range::Span& S = P.spans[r];
+      for (size_t k = 0; S.nrows && k <= S.nrows; ++k) {
+        h[filled++] = index[S.first_seg + k];
+        if (filled == per && (rc = flush()) != SFH_OK) return rc;
+      }
+    }
+    if ((rc = flush()) != SFH_OK) return rc;
+  }
+  if (subindex) {
+    const size_t per = kStageBytes / (SFH_SUBINDEX_WORDS * sizeof(uint32_t));
+    uint32_t* h = (uint32_t*)ctx->h_stage;
+    for (size_t g0 = 0; g0 < nrows; g0 += per) {
+      const size_t g1 = std::min(nrows, g0 + per);
+      for (size_t g = g0; g < g1; ++g)
+        memcpy(h + (g - g0) * SFH_SUBINDEX_WORDS, subindex + P.rows[g].seg * SFH_SUBINDEX_WORDS, SFH_SUBINDEX_WORDS * sizeof(uint32_t));
+      SF_HIP(hipMemcpyAsync(ctx->d_sub + g0 * SFH_SUBINDEX_WORDS, h, (g1 - g0) * SFH_SUBINDEX_WORDS * sizeof(uint32_t),
+                            hipMemcpyHostToDevice, s), "H2D sub-index");
+      SF_HIP(hipStreamSynchronize(s), "stream sync");
+    }
+  }
+  for (size_t r = 0; r < count; ++r) {
+    // (the base points p_lo[r] bytes in front of the piece: base + an index entry of the span is the uploaded byte)
+    const uint8_t* base = (const uint8_t*)((uintptr_t)(ctx->d_in + in_off[r]) - (uintptr_t)p_lo[r]);
+    from[r] = RangeSource{base, p_lo[r] + p_n[r], ctx->d_index + ix_off[r], subindex ? ctx->d_sub + (size_t)P.spans[r].row0 * SFH_SUBINDEX_WORDS : nullptr};
+    d_dsts[r] = ctx->d_out + out_off[r];
+  }
+  if ((rc = enqueue_ranges(ctx, P, from.data(), d_dsts.data(), count, subindex != nullptr, ctx->d_bstatus, s)) != SFH_OK) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy statuses");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  for (size_t r = 0; r < count; ++r) status[r] = ctx->h_bstatus[r];
+  // down: the packed output in pieces, each range with status 0 out of the pieces it lies in
+  const uint64_t end = out_off[count];
+  item = 0;
+  for (uint64_t p0 = 0; p0 < end; p0 += kStageBytes) {
+    const uint64_t p1 = std::min<uint64_t>(end, p0 + kStageBytes);
+    while (item < count && out_off[item] + lengths[item] <= p0) ++item;
+    bool any = false;
+    for (size_t r = item; r < count && out_off[r] < p1 && !any; ++r) any = status[r] == 0 && lengths[r] && out_off[r] + lengths[r] > p0;
+    if (!any) continue;
+    SF_HIP(hipMemcpyAsync(ctx->h_stage, ctx->d_out + p0, p1 - p0, hipMemcpyDeviceToHost, s), "D2H");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+    for (size_t r = item; r < count && out_off[r] < p1; ++r) {
+      if (status[r] != 0) continue;
+      const uint64_t a = std::max(p0, out_off[r]), b = std::min(p1, out_off[r] + lengths[r]);
+      if (a < b) memcpy((uint8_t*)dsts[r] + (a - out_off[r]), ctx->h_stage + (a - p0), b - a);
     }
   }
   return SFH_OK;

@@ -242,6 +242,16 @@ struct InflateItem {     // per item of the call (k_inflate_head, k_inflate_fold
   uint32_t pad;
 };
 static_assert(sizeof(InflateSeg) == 48 && sizeof(InflateStrip) == 8 && sizeof(InflateItem) == 64, "decoder descriptor rows");
+// Random access (sfh_decompress_range*; sf_range_plan.h): the rows of a launch batch are the segments of the ranges' decode
+// spans, and beside every InflateSeg stands its write window -- the part of the segment that belongs to the range.
+struct InflateClip {     // per segment of a launch batch (k_inflate_bytes_clip)
+  uint8_t* dst;          // where its byte `lo` goes (any alignment)
+  uint32_t lo, hi;       // [lo, hi) of its out_n bytes are written; lo == hi: it is resolved in LDS only
+};
+struct InflateSpan {     // per range of the call (k_inflate_fold_spans)
+  uint32_t row0, nrows;  // its rows in the call's segment records
+};
+static_assert(sizeof(InflateClip) == 16 && sizeof(InflateSpan) == 8, "range descriptor rows");
 struct BatchTables {  // the device tables of one launch batch (null: the single call's implicit geometry)
   const BatchStrip* strips;
   uint32_t nstrips;
@@ -321,6 +331,10 @@ hipError_t launch_inflate_head(InflateItem* items, uint32_t nitems, uint32_t con
                                hipStream_t s);
 hipError_t launch_inflate_fold(const InflateItem* items, uint32_t nitems, const SegInfo* info, const uint32_t* sums,
                                uint32_t container, uint32_t* status, hipStream_t s);
+// random access: the byte stage with a write window per row, and every range's status (its span's first failing segment)
+hipError_t launch_inflate_bytes_clip(const InflateSeg* rows, const InflateClip* clips, const InflateStrip* strips, uint32_t nstrips,
+                                     const uint32_t* tokens, SegInfo* info, hipStream_t s);
+hipError_t launch_inflate_fold_spans(const InflateSpan* spans, uint32_t nspans, const SegInfo* info, uint32_t* status, hipStream_t s);
 
 // sf_stream.hip: a stream without flush points (sfh_inflate_stream*); StreamChunk and the chain round: sf_stream_chain.h
 constexpr uint64_t kNoCandidate = ~0ull;

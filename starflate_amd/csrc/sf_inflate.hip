@@ -22,6 +22,8 @@
 //                     inside it become 16-bit pointers that pointer jumping resolves in a few barrier-
 //                     separated rounds, whatever the nesting or overlap.  A segment that is one stored block
 //                     is copied straight from the stream.
+//   k_inflate_bytes_clip  the same walk for random access (sfh_decompress_range*): every segment with a write window, the
+//                     part of it a requested byte range covers; the rest of it only passes through the LDS ring.
 //   k_inflate_status  first non-zero segment status in stream order = what the serial decoder would report.
 #include "sf_device.h"
 
@@ -1028,10 +1030,14 @@ __device__ __forceinline__ uint32_t load_word_guarded(const uint8_t* base, uint6
 // are final (whole dwords; the odd bytes with the next step), so the ring never has to hold a whole segment.
 // rb: ring position of the segment's first byte; segbase: that byte's position in its strip (bytes of history).
 // Returns false when the segment failed.  BATCH: the segment's output starts at rows[seg].dst.
-template <bool BATCH>
+// CLIP (k_inflate_bytes_clip, with BATCH): of the segment's bytes only [clips[seg].lo, clips[seg].hi) are written, byte lo at
+// clips[seg].dst, which has any alignment; an empty window: the segment is resolved into the ring for the ones behind it and
+// nothing of it reaches global memory.
+template <bool BATCH, bool CLIP = false>
 __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t src_n, const uint32_t* __restrict__ tokens,
                                       SegInfo* __restrict__ info, uint8_t* __restrict__ dst, uint32_t seg, uint32_t segbase,
-                                      uint32_t rb, uint8_t* s_dyn, const InflateSeg* __restrict__ rows) {
+                                      uint32_t rb, uint8_t* s_dyn, const InflateSeg* __restrict__ rows,
+                                      const InflateClip* __restrict__ clips = nullptr) {
   constexpr uint32_t kRing = KB_RING;
   uint8_t* s_out = s_dyn;                                          // [kRing] output window
   uint16_t* s_ptr = reinterpret_cast<uint16_t*>(s_dyn + kRing);   // [KB_SPAN] step-relative source, or kFinal
@@ -1061,8 +1067,15 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
   const SegInfo si = info[seg];
   if (si.status != inflate::kOk) return false;
   const uint32_t out_n = si.out_n;
-  uint8_t* o;  // 16-byte aligned
-  if constexpr (BATCH) o = rows[seg].dst;
+  uint8_t* o;  // 16-byte aligned (CLIP: where byte c_lo goes, any alignment)
+  uint32_t c_lo = 0, c_hi = 0;  // CLIP: the write window
+  if constexpr (CLIP) {
+    const InflateClip C = clips[seg];
+    o = C.dst;
+    c_lo = C.lo < out_n ? C.lo : out_n;
+    c_hi = C.hi < out_n ? C.hi : out_n;
+    c_hi = c_hi > c_lo ? c_hi : c_lo;
+  } else if constexpr (BATCH) o = rows[seg].dst;
   else o = dst + (uint64_t)seg * kChunk;
 
   if (si.raw & kSegRaw) {
@@ -1070,14 +1083,33 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
     const uint32_t mis = (uint32_t)(si.raw_off & 3);
     const uint64_t w0 = si.raw_off >> 2;
     const uint32_t nd = out_n / 4;
+    const uint32_t done = 4 * nd;
+    if constexpr (CLIP) {
+      // the window's bytes to a destination of any alignment: single bytes up to its first dword boundary, dwords funnel-
+      // shifted from the stream, single bytes behind the last whole dword
+      const uint32_t n = c_hi - c_lo;
+      const uint64_t s0 = si.raw_off + c_lo;
+      const uint32_t head = min((uint32_t)(0u - (uint32_t)(uintptr_t)o) & 3u, n);
+      const uint32_t cnd = (n - head) / 4, cdone = head + 4 * cnd;
+      const uint32_t cmis = (uint32_t)((s0 + head) & 3);
+      const uint64_t cw0 = (s0 + head) >> 2;
+      uint32_t* o32 = reinterpret_cast<uint32_t*>(o + head);
+      if (t < head) o[t] = src[s0 + t];
+      for (uint32_t k = t; k < cnd; k += KB_THREADS) {
+        const uint32_t lo = load_word_guarded(src, src_n, cw0 + k);
+        const uint32_t hi = cmis ? load_word_guarded(src, src_n, cw0 + k + 1) : 0u;
+        o32[k] = __builtin_amdgcn_alignbyte(hi, lo, cmis);
+      }
+      if (t < n - cdone) o[cdone + t] = src[s0 + cdone + t];
+    } else {
     uint32_t* o32 = reinterpret_cast<uint32_t*>(o);
     for (uint32_t k = t; k < nd; k += KB_THREADS) {
       const uint32_t lo = load_word_guarded(src, src_n, w0 + k);
       const uint32_t hi = mis ? load_word_guarded(src, src_n, w0 + k + 1) : 0u;
       o32[k] = __builtin_amdgcn_alignbyte(hi, lo, mis);
     }
-    const uint32_t done = 4 * nd;
     if (t < out_n - done) o[done + t] = src[si.raw_off + done + t];
+    }
     {
       // later segments of the strip may copy from these bytes: their last kWindow go into the ring as well
       __syncthreads();  // (the previous segment's last window reads are done)
@@ -1311,7 +1343,35 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
     if (t < kWords) s_mark[t] = 0;
     __syncthreads();
     // the step's bytes are final: whole dwords go out now (ring and dst are dword-aligned alike)
-    {
+    if constexpr (CLIP) {
+      // ... those of them inside the window, to whole dwords of the DESTINATION: single bytes up to its first dword boundary,
+      // then dwords funnel-shifted out of the ring (two aligned reads; the ring's length is a multiple of 4, so neither wraps),
+      // up to its last dword boundary; what lies behind that waits for the next step, or, at the window's end, goes out in
+      // single bytes.  `flushed`: the segment's bytes up to here are dealt with.
+      const uint32_t a = flushed > c_lo ? flushed : c_lo;
+      uint32_t e = next_pos < c_hi ? next_pos : c_hi;
+      if (a < e) {
+        if (e < c_hi) {
+          const uint32_t odd = (uint32_t)(uintptr_t)(o + (e - c_lo)) & 3u;
+          e = e - a > odd ? e - odd : a;
+        }
+        uint8_t* p = o + (a - c_lo);
+        const uint32_t n = e - a;
+        const uint32_t head = min((0u - (uint32_t)(uintptr_t)p) & 3u, n);
+        const uint32_t cnd = (n - head) / 4, cdone = head + 4 * cnd;
+        const uint32_t fbase = ring(a);  // (uniform; n < kRing)
+        uint32_t* p32 = reinterpret_cast<uint32_t*>(p + head);
+        if (t < head) p[t] = s_out[wrap1(fbase + t)];
+        for (uint32_t k = t; k < cnd; k += KB_THREADS) {
+          const uint32_t r = wrap1(fbase + head + 4 * k), r4 = r & ~3u;
+          const uint32_t w0 = *reinterpret_cast<const uint32_t*>(s_out + r4);
+          const uint32_t w1 = *reinterpret_cast<const uint32_t*>(s_out + wrap1(r4 + 4));
+          p32[k] = __builtin_amdgcn_alignbyte(w1, w0, r & 3u);
+        }
+        if (t < n - cdone) p[cdone + t] = s_out[wrap1(fbase + cdone + t)];
+        flushed = e;
+      }
+    } else {
       const uint32_t end4 = next_pos & ~3u;
       uint32_t* o32 = reinterpret_cast<uint32_t*>(o);
       const uint32_t fbase = ring(flushed);  // (uniform; the bytes to flush span less than kRing)
@@ -1326,7 +1386,8 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
     if (t == 0) info[seg].status = inflate::kError;
     return false;
   }
-  if (t < out_n - flushed) o[flushed + t] = s_out[ring(flushed + t)];  // the last odd bytes
+  if constexpr (!CLIP)
+    if (t < out_n - flushed) o[flushed + t] = s_out[ring(flushed + t)];  // the last odd bytes
   return true;
 }
 
@@ -1375,6 +1436,46 @@ __global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes_batch(const Inflat
   }
 }
 
+// sfh_decompress_range*: as k_inflate_bytes_batch, every row with its write window.  The rows of a strip are the segments
+// of one range's decode span inside one strip of the stream: those in front of the range's first byte have an empty
+// window and are only resolved into the ring.
+__global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes_clip(const InflateSeg* __restrict__ rows,
+                                                                   const InflateClip* __restrict__ clips,
+                                                                   const InflateStrip* __restrict__ strips,
+                                                                   const uint32_t* __restrict__ tokens,
+                                                                   SegInfo* __restrict__ info) {
+  extern __shared__ __align__(16) uint8_t s_dyn[];
+  const InflateStrip S = strips[blockIdx.x];
+  const uint8_t* src = rows[S.seg0].src;
+  const uint64_t src_n = rows[S.seg0].src_n;
+  uint32_t rb = 0;
+  for (uint32_t k = 0; k < S.nseg; ++k) {
+    if (!inflate_segment_bytes<true, true>(src, src_n, tokens, info, nullptr, S.seg0 + k, k * kChunk, rb, s_dyn, rows, clips)) {
+      for (uint32_t j = k + 1 + threadIdx.x; j < S.nseg; j += KB_THREADS)
+        if (info[S.seg0 + j].status == inflate::kOk) info[S.seg0 + j].status = inflate::kError;
+      return;
+    }
+    rb += kChunk;
+    rb = rb >= KB_RING ? rb - KB_RING : rb;
+    __syncthreads();
+  }
+}
+
+// Every range's status: the first failing segment of its decode span in stream order (k_inflate_fold's idea, over the spans'
+// rows in the call's segment records).  One wave per range.
+__global__ __launch_bounds__(64) void k_inflate_fold_spans(const InflateSpan* __restrict__ spans, uint32_t nspans,
+                                                           const SegInfo* __restrict__ info, uint32_t* __restrict__ status) {
+  const uint32_t r = blockIdx.x, lane = threadIdx.x;
+  if (r >= nspans) return;
+  const InflateSpan S = spans[r];
+  uint32_t first = 0xFFFFFFFFu;
+  for (uint32_t k = lane; k < S.nrows && first == 0xFFFFFFFFu; k += 64)
+    if (info[S.row0 + k].status != inflate::kOk) first = k;
+#pragma unroll
+  for (uint32_t d = 32; d; d >>= 1) first = min(first, (uint32_t)__shfl_xor((int)first, (int)d));
+  if (lane == 0) status[r] = first == 0xFFFFFFFFu ? (uint32_t)inflate::kOk : info[S.row0 + first].status;
+}
+
 constexpr uint32_t KS_THREADS = 1024;
 __global__ __launch_bounds__(KS_THREADS) void k_inflate_status(const SegInfo* __restrict__ info, uint32_t nseg,
                                                                uint32_t* __restrict__ result /* [status, segment] */) {
@@ -1409,6 +1510,9 @@ hipError_t init_inflate_kernels() {
                             (int)KT_LDS);
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes_batch), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)KB_LDS);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes_clip), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)KB_LDS);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1465,6 +1569,17 @@ hipError_t launch_inflate_tokens_exact(const InflateSeg* rows, uint32_t nseg, ui
 hipError_t launch_inflate_bytes_batch(const InflateSeg* rows, const InflateStrip* strips, uint32_t nstrips,
                                       const uint32_t* tokens, SegInfo* info, hipStream_t s) {
   hipLaunchKernelGGL(k_inflate_bytes_batch, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, rows, strips, tokens, info);
+  return hipGetLastError();
+}
+
+hipError_t launch_inflate_bytes_clip(const InflateSeg* rows, const InflateClip* clips, const InflateStrip* strips, uint32_t nstrips,
+                                     const uint32_t* tokens, SegInfo* info, hipStream_t s) {
+  hipLaunchKernelGGL(k_inflate_bytes_clip, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, rows, clips, strips, tokens, info);
+  return hipGetLastError();
+}
+
+hipError_t launch_inflate_fold_spans(const InflateSpan* spans, uint32_t nspans, const SegInfo* info, uint32_t* status, hipStream_t s) {
+  hipLaunchKernelGGL(k_inflate_fold_spans, dim3(nspans), dim3(64), 0, s, spans, nspans, info, status);
   return hipGetLastError();
 }
 
