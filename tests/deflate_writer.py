@@ -482,15 +482,15 @@ def _decode(br, dec):
 
 def inflate(data, bit=0, stop_at_segment_end=False, matches=None):
     """A plain decoder of raw DEFLATE from `bit` on, for what the tests need to see: -> (bytes, blocks), each block a
-    dict with its type, header (dynamic) and the (code length, extra bits, extra value) of every length and distance
-    item and the code length of every literal / end-of-block.  Stops after BFINAL (or, stop_at_segment_end, after
-    the first empty stored block).  matches: a list that gets (output position, distance, length) of every match.
+    dict with its type, start bit ("start") and output offset ("out"), header (dynamic) and the (code length, extra bits,
+    extra value) of every length and distance item and the code length of every literal / end-of-block.  Stops after
+    BFINAL (or, stop_at_segment_end, after the first empty stored block).  matches: a list that gets (output position, distance, length) of every match.
     Slow (a Python call per bit of a code): meant for streams of a MiB or so."""
     br = BitReader(data, bit)
     out, blocks = bytearray(), []
     while True:
         fin, typ = br.get(1), br.get(2)
-        blk = {"type": typ, "ll": set(), "len_items": set(), "dist_items": set(), "start": br.pos - 3}
+        blk = {"type": typ, "ll": set(), "len_items": set(), "dist_items": set(), "start": br.pos - 3, "out": len(out)}
         blocks.append(blk)
         if typ == 0:
             br.pos += -br.pos % 8

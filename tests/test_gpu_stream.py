@@ -14,6 +14,7 @@ import deflate_writer as W
 import starflate_amd
 import stream_host as H
 from starflate_amd import Compressor, StarflateError, synth
+from stream_cases import write_fixed
 
 pytestmark = pytest.mark.gpu
 
@@ -170,22 +171,7 @@ def _writer_stream(kind, seed):
             for _ in range(ln):
                 out.append(out[-d])
         if kind == "fixed" and b % 2:
-            bw.put(int(final), 1)
-            bw.put(1, 2)
-            ll = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8
-            llc, dc = W.canonical(ll), W.canonical([5] * 32)
-            for t in toks:
-                if t & W.MATCH:
-                    ln, d = ((t >> 16) & 0xFF) + 3, (t & 0x7FFF) + 1
-                    s, eb, ev = W.len_symbol(ln)
-                    bw.put_code(llc[s], ll[s])
-                    bw.put(ev, eb)
-                    ds, deb, dev = W.dist_symbol(d)
-                    bw.put_code(dc[ds], 5)
-                    bw.put(dev, deb)
-                else:
-                    bw.put_code(llc[t], ll[t])
-            bw.put_code(llc[256], ll[256])
+            write_fixed(bw, toks, final)
             continue
         ll_f, d_f = W.token_symbols(np.asarray(toks, np.uint32))
         if kind == "incomplete":
