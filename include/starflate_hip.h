@@ -442,9 +442,14 @@ int sfh_last_recover_stats(sfh_ctx* ctx, float ms[2], uint64_t counts[2]);
  * Size query: d_dst == NULL and dst_cap == 0 runs the candidate, count and chain steps only: *dst_n_out = the output size, and
  * *status the wrapper's or the first structural problem of the body (the checks that need output positions -- distance <=
  * bytes written, the capacity, the checksum -- are the decode call's).
- * d_src 4-byte aligned, d_dst 16-byte aligned.  Host synchronisations of `stream` (NULL = the ctx's own): the wrapper, the
- * candidates, each chain round, the write pass's statuses, the checksum.  Scratch: 2 bytes per output byte (the symbol plane),
- * 64 KiB per group of about sqrt(chunks) chunks, 60 bytes per nominal chunk (sfh_last_decode_scratch_bytes).
+ * The call is the batched call below with one item: one decoder runs both.  d_src 4-byte aligned, d_dst 16-byte aligned.  A
+ * call on another stream than the ctx's previous call first waits, on the device, for that call (raw streams included: the
+ * calls share the ctx's scratch).  Host synchronisations of `stream` (NULL = the ctx's own): the wrapper (zlib and gzip; a raw
+ * stream has none), the candidates, the count pass and each chain round, the write pass's statuses, and one at the end of the
+ * decode (with a wrapper: behind the checksum).  Scratch: 60 bytes per nominal chunk, 2 bytes per output byte (the symbol
+ * plane, rounded up to 16 entries, 16 bytes at least) and 64 KiB per group of about sqrt(chunks) chunks beyond the first
+ * (sfh_last_decode_scratch_bytes; the size query: the first term only).  After a non-zero *status sfh_last_error reads
+ * "DecompressStatus N".
  * sfh_inflate_stream: host buffers (H2D, the same, D2H of dst when *status is 0); dst == NULL with dst_cap == 0 is the size query. */
 int sfh_inflate_stream_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint32_t container, void* d_dst, uint64_t dst_cap,
                               uint64_t* dst_n_out, uint32_t* status, void* stream);

@@ -4,6 +4,7 @@
 #include "sf_device.h"
 #include "sf_inflate_core.h"
 #include "sf_range_plan.h"
+#include "sf_stage_plan.h"
 
 #include <dlfcn.h>
 #include <stdio.h>
@@ -100,8 +101,8 @@ struct sfh_ctx {
   hipEvent_t ev_any[5] = {};
   float any_ms[2] = {0, 0};
   uint64_t any_counts[2] = {0, 0};
-  // streams without flush points (sfh_inflate_stream*): candidates | chunk records | the redo list; the symbol plane; the
-  // composed windows of the resolve
+  // streams without flush points (sfh_inflate_stream*, one item or a batch): candidates (then: the records' items | the follow
+  // list) | chunk records | the redo list; the symbol plane; the composed windows of the resolve
   uint64_t stream_chunk = 16384;  // SFH_STREAM_CHUNK=<bytes>: nominal chunk size S
   uint8_t* d_stm = nullptr;
   uint16_t* d_plane = nullptr;
@@ -110,8 +111,7 @@ struct sfh_ctx {
   hipEvent_t ev_stm[6] = {};
   float stm_ms[SFH_STREAM_NSTAGES] = {};
   uint64_t stm_counts[SFH_STREAM_NCOUNTS] = {};
-  // batches of them (sfh_inflate_stream_batch*): the wrapper rows and bodies | the item rows; a launch batch's group, checksum
-  // and fold rows and its statuses
+  // the wrapper rows and bodies | the item rows; a launch batch's group, checksum and fold rows and its statuses
   uint8_t* d_sbt = nullptr;
   uint8_t* d_sbr = nullptr;
   size_t d_sbt_cap = 0, d_sbr_cap = 0;
@@ -291,6 +291,7 @@ struct HostPipe {
   bool overflow = false;
 };
 constexpr uint32_t kPipeBatchChunks = 2048;  // 64 MiB of input per batch on the host-buffer path
+constexpr size_t kStageBytes = (size_t)kPipeBatchChunks * sf::kChunk;  // the pinned staging (h_stage) of the batched host calls
 
 // effort -> what the match kernel does: {both levels, near candidate, even positions only, second table, chain depth, exact recency}
 sf::Options kernel_options(const sfh_options& o, uint32_t strip_bytes) {
@@ -907,6 +908,26 @@ int enqueue_ranges(sfh_ctx* ctx, const sf::range::Plan& P, const RangeSource* fr
   return mark_call_end(ctx, s);
 }
 
+// The batched host-buffer calls' staging (sf_stage_plan.h): piece i lies at [off[i], off[i] + len[i]) of a packed layout of
+// `total` bytes in ctx->d_in (up) or ctx->d_out (down), and moves through the pinned h_stage, one copy and one wait per
+// kStageBytes.  Down, len[i] == 0 skips piece i, and a stretch of kStageBytes that holds no other piece's bytes is not copied.
+int stage_up(sfh_ctx* ctx, const void* const* srcs, const uint64_t* len, const uint64_t* off, size_t count, uint64_t total,
+             hipStream_t s) {
+  return sf::stage::pack_up(ctx->h_stage, kStageBytes, srcs, len, off, count, total, [&](uint64_t p0, uint64_t n) -> int {
+    SF_HIP(hipMemcpyAsync(ctx->d_in + p0, ctx->h_stage, n, hipMemcpyHostToDevice, s), "H2D");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");  // (the next piece refills h_stage)
+    return SFH_OK;
+  });
+}
+int stage_down(sfh_ctx* ctx, void* const* dsts, const uint64_t* len, const uint64_t* off, size_t count, uint64_t total,
+               hipStream_t s) {
+  return sf::stage::unpack_down(ctx->h_stage, kStageBytes, dsts, len, off, count, total, [&](uint64_t p0, uint64_t n) -> int {
+    SF_HIP(hipMemcpyAsync(ctx->h_stage, ctx->d_out + p0, n, hipMemcpyDeviceToHost, s), "D2H");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+    return SFH_OK;
+  });
+}
+
 // d_bstatus / h_bstatus hold `count` statuses
 int ensure_bstatus(sfh_ctx* ctx, size_t count) {
   if (ctx->bstatus_cap >= count) return SFH_OK;
@@ -916,7 +937,7 @@ int ensure_bstatus(sfh_ctx* ctx, size_t count) {
   ctx->bstatus_cap = 0;
   if (hipMalloc(&ctx->d_bstatus, count * sizeof(uint32_t)) != hipSuccess ||
       hipHostMalloc((void**)&ctx->h_bstatus, count * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-    return fail(ctx, SFH_E_NOMEM, "range statuses", hipSuccess);
+    return fail(ctx, SFH_E_NOMEM, "batch statuses", hipSuccess);
   ctx->bstatus_cap = count;
   return SFH_OK;
 }
@@ -931,7 +952,7 @@ inline size_t al16(size_t b) { return (b + 15) / 16 * 16; }
 // The wrapper, read by k_inflate_head as the batch decoder reads it: *wst its status, *isize gzip's ISIZE; the body [b0, e) lands
 // in any_head.  dst_n: the size the caller asks for (SFH_SIZE_FROM_TRAILER: ISIZE is taken).  Synchronises s.
 int any_wrapper(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t container, uint64_t dst_n, hipStream_t s, uint32_t* wst,
-                uint32_t* isize, uint32_t* want = nullptr, uint64_t* body = nullptr) {
+                uint32_t* isize) {
   if (!ctx->d_anysm) SF_HIP(hipMalloc(&ctx->d_anysm, kAnySmall), "hipMalloc");
   for (hipEvent_t& e : ctx->ev_any)
     if (!e) SF_HIP(hipEventCreate(&e), "event");
@@ -940,11 +961,9 @@ int any_wrapper(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t contain
   SF_HIP(hipMemcpyAsync(ctx->d_anysm, &it, sizeof it, hipMemcpyHostToDevice, s), "H2D wrapper row");
   SF_HIP(sf::launch_inflate_head((sf::InflateItem*)ctx->d_anysm, 1, container, nullptr, nullptr, s), "launch k_inflate_head");
   SF_HIP(hipMemcpyAsync(&it, ctx->d_anysm, sizeof it, hipMemcpyDeviceToHost, s), "D2H wrapper row");
-  if (body) SF_HIP(hipMemcpyAsync(body, any_head(ctx), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "D2H body");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
   *wst = it.wst;
   *isize = it.isize;
-  if (want) *want = it.want;
   return mark_call_end(ctx, s);
 }
 
@@ -1097,152 +1116,8 @@ int enqueue_any_decode(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t 
   return mark_call_end(ctx, s);
 }
 
-// ---- streams without flush points (sfh_inflate_stream*; sf_stream.hip) ----
-// query: steps A to C only.  stage: decode into ctx->d_out, grown to the output size (the host-buffer entry point).
-int stream_run(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t container, uint8_t* d_dst, uint64_t dst_cap, bool query,
-               bool stage, uint64_t* dst_n_out, uint32_t* status, hipStream_t s) {
-  const bool prof = ctx->profiling != 0;
-  for (float& m : ctx->stm_ms) m = 0;
-  for (uint64_t& c : ctx->stm_counts) c = 0;
-  *dst_n_out = 0;
-  *status = 0;
-  if (container == SFH_RAW && src_n == 0) {  // no header bits at all
-    *status = sf::inflate::kInvalidBlockHeader;
-    return SFH_OK;
-  }
-  for (hipEvent_t& e : ctx->ev_stm)
-    if (!e) SF_HIP(hipEventCreate(&e), "event");
-  uint32_t wst = 0, isize = 0, want = 0;
-  uint64_t body[2] = {0, 0};
-  // (container.hpp: a gzip dst below ISIZE is DstTooSmall; the size query has no dst yet)
-  int rc = any_wrapper(ctx, src, src_n, container, query ? ((uint64_t)1 << 44) : dst_cap, s, &wst, &isize, &want, body);
-  if (rc) return rc;
-  if (wst) {
-    *status = wst;
-    return SFH_OK;
-  }
-  const uint64_t b0 = body[0], body_n = body[1] - body[0], S = ctx->stream_chunk;
-  const uint64_t nc64 = body_n ? (body_n + S - 1) / S : 1;
-  if (nc64 >= ((uint64_t)1 << 31)) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 nominal chunks (SFH_STREAM_CHUNK)", hipSuccess);
-  const uint32_t nc = (uint32_t)nc64;
-  // cand u64[nc] | recs StreamChunk[nc] | list u32[nc]
-  const size_t o_rec = al16(8 * (size_t)nc), o_list = o_rec + al16(sizeof(sf::StreamChunk) * (size_t)nc);
-  if ((rc = grow(ctx, &ctx->d_stm, &ctx->d_stm_cap, o_list + al16(4 * (size_t)nc), "stream chunk records"))) return rc;
-  uint64_t* d_cand = (uint64_t*)ctx->d_stm;
-  sf::StreamChunk* d_rec = (sf::StreamChunk*)(ctx->d_stm + o_rec);
-  uint32_t* d_list = (uint32_t*)(ctx->d_stm + o_list);
-  std::vector<uint64_t> cand;
-  std::vector<sf::StreamChunk> rec;
-  try {
-    cand.resize(nc);
-    rec.reserve(nc);
-  } catch (...) {
-    return fail(ctx, SFH_E_NOMEM, "host memory for the chunk records", hipSuccess);
-  }
-  // A: candidates
-  if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[0], s), "event");
-  SF_HIP(sf::launch_stream_find(src, src_n, b0, body_n, S, nc, d_cand, s), "launch k_stream_find");
-  if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[1], s), "event");
-  SF_HIP(hipMemcpyAsync(cand.data(), d_cand, 8 * (size_t)nc, hipMemcpyDeviceToHost, s), "D2H candidates");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  for (uint32_t c = 0; c < nc; ++c)
-    if (cand[c] != sf::kNoCandidate && (rec.empty() || cand[c] > rec.back().start))
-      rec.push_back(sf::StreamChunk{cand[c], 0, 0, 0, 0, 0, 0});
-  const uint32_t m = (uint32_t)rec.size();
-  for (uint32_t i = 0; i < m; ++i) rec[i].limit = i + 1 < m ? rec[i + 1].start : ~0ull;
-  // B and C: the count pass, then rounds of repairs until the chain from chunk 0 reaches its end
-  const size_t rec_bytes = sizeof(sf::StreamChunk) * (size_t)m;
-  SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
-  SF_HIP(sf::launch_stream_decode(false, src, src_n, b0, body_n, d_rec, nullptr, m, m, false, nullptr, 0, s), "launch k_stream_decode");
-  SF_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s), "D2H chunk records");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  uint32_t chain = 0, rounds = 0;
-  for (;;) {
-    const std::vector<uint32_t> redo = sf::stream_chain_round(rec, &chain);
-    if (redo.empty()) break;
-    ++rounds;
-    SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
-    SF_HIP(hipMemcpyAsync(d_list, redo.data(), 4 * redo.size(), hipMemcpyHostToDevice, s), "H2D repair list");
-    SF_HIP(sf::launch_stream_decode(false, src, src_n, b0, body_n, d_rec, d_list, (uint32_t)redo.size(), m, false, nullptr, 0, s),
-           "launch k_stream_decode");
-    // the first of them is behind the confirmed chain: it goes on through the run of broken links after it
-    SF_HIP(sf::launch_stream_decode(false, src, src_n, b0, body_n, d_rec, d_list, 1, m, true, nullptr, 0, s), "launch k_stream_decode");
-    SF_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s), "D2H chunk records");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");
-  }
-  if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[2], s), "event");
-  uint64_t total = 0, longest = 0;
-  for (uint32_t i = 0; i < chain; ++i) {
-    rec[i].base = total;
-    total += rec[i].out;
-    longest = std::max(longest, rec[i].out);
-  }
-  const uint32_t G = sf::stream_group(chain), ng = (chain + G - 1) / G;
-  const size_t wins = (size_t)(ng - 1) * 32768 * sizeof(uint16_t);
-  ctx->stm_counts[0] = nc;
-  ctx->stm_counts[1] = m;
-  ctx->stm_counts[2] = chain;
-  ctx->stm_counts[3] = rounds;
-  ctx->stm_counts[4] = longest;
-  ctx->stm_counts[5] = o_list + al16(4 * (size_t)nc) + (query ? 0 : 2 * total + wins);
-  ctx->last_dtok_bytes = ctx->stm_counts[5];
-  *dst_n_out = total;
-  if (query) {
-    *status = rec[chain - 1].status;
-    if (prof) SF_HIP(hipEventElapsedTime(&ctx->stm_ms[0], ctx->ev_stm[0], ctx->ev_stm[1]), "elapsed");
-    if (prof) SF_HIP(hipEventElapsedTime(&ctx->stm_ms[1], ctx->ev_stm[1], ctx->ev_stm[2]), "elapsed");
-    return mark_call_end(ctx, s);
-  }
-  // D: the exact pass into the symbol plane
-  const uint64_t cap = container == SFH_GZIP ? isize : dst_cap;  // (container.hpp decodes a gzip body into dst.first(ISIZE))
-  if ((rc = grow(ctx, &ctx->d_plane, &ctx->d_plane_cap, std::max<size_t>(16, 2 * total), "symbol plane"))) return rc;
-  if (wins && (rc = grow(ctx, &ctx->d_wins, &ctx->d_wins_cap, wins, "stream windows"))) return rc;
-  if (stage) {
-    if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, std::max<size_t>(16, total), "output staging"))) return rc;
-    d_dst = ctx->d_out;
-  }
-  SF_HIP(hipMemcpyAsync(d_rec, rec.data(), sizeof(sf::StreamChunk) * (size_t)chain, hipMemcpyHostToDevice, s), "H2D chunk records");
-  SF_HIP(sf::launch_stream_decode(true, src, src_n, b0, body_n, d_rec, nullptr, chain, chain, false, ctx->d_plane, cap, s), "launch k_stream_decode");
-  if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[3], s), "event");
-  SF_HIP(hipMemcpyAsync(rec.data(), d_rec, sizeof(sf::StreamChunk) * (size_t)chain, hipMemcpyDeviceToHost, s), "D2H chunk records");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  uint32_t st = 0;
-  for (uint32_t i = 0; i < chain && !st; ++i) st = rec[i].status;
-  if (!st && container == SFH_GZIP && total != isize) st = sf::inflate::kError;
-  if (!st) {
-    // E / F: the windows, and the bytes
-    SF_HIP(sf::launch_stream_resolve(ctx->d_plane, d_rec, chain, ctx->d_wins, d_dst, s), "launch k_stream_resolve");
-    if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[4], s), "event");
-    if (container) {
-      const uint32_t nch = chunks_of((size_t)total);
-      if ((rc = ensure_sums(ctx, nch))) return rc;
-      const uint8_t* sum_src = total ? d_dst : ctx->d_anysm;
-      SF_HIP(sf::launch_checksum(sum_src, total, nch, container, ctx->ws.sums, s), "launch k_checksum");
-      SF_HIP(sf::launch_wrap(ctx->ws.sums, nch, total, container, nullptr, nullptr, ctx->d_value, s), "launch k_wrap");
-      uint32_t got = 0;
-      SF_HIP(hipMemcpyAsync(&got, ctx->d_value, sizeof got, hipMemcpyDeviceToHost, s), "D2H checksum");
-      SF_HIP(hipStreamSynchronize(s), "stream sync");
-      if (got != want) st = sf::inflate::kError;
-    }
-    if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[5], s), "event");
-    if (prof) SF_HIP(hipEventSynchronize(ctx->ev_stm[5]), "event sync");
-  }
-  *status = st;
-  if (st) snprintf(ctx->err, sizeof ctx->err, "DecompressStatus %u", st);
-  if (prof) {
-    SF_HIP(hipEventElapsedTime(&ctx->stm_ms[0], ctx->ev_stm[0], ctx->ev_stm[1]), "elapsed");
-    SF_HIP(hipEventElapsedTime(&ctx->stm_ms[1], ctx->ev_stm[1], ctx->ev_stm[2]), "elapsed");
-    SF_HIP(hipEventElapsedTime(&ctx->stm_ms[2], ctx->ev_stm[2], ctx->ev_stm[3]), "elapsed");
-    if (!st) {
-      SF_HIP(hipEventElapsedTime(&ctx->stm_ms[3], ctx->ev_stm[3], ctx->ev_stm[4]), "elapsed");
-      SF_HIP(hipEventElapsedTime(&ctx->stm_ms[4], ctx->ev_stm[4], ctx->ev_stm[5]), "elapsed");
-    }
-  }
-  return mark_call_end(ctx, s);
-}
-
-// ---- batches of streams without flush points (sfh_inflate_stream_batch*; sf_stream_batch.hip) ----
-// Everything the call checks before it enqueues anything (`dev`: device buffers, the single call's alignment rules).
+// ---- streams without flush points (sfh_inflate_stream*, sfh_inflate_stream_batch*; sf_stream.hip) ----
+// Everything a batched call checks before it enqueues anything (`dev`: device buffers, the single call's alignment rules).
 int check_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
                        void* const* dsts, const uint64_t* dst_cap, const uint64_t* dst_n_out, const uint32_t* status, bool dev) {
   if (!ctx || container > SFH_GZIP) return fail(ctx, SFH_E_INVALID_ARG, "argument (container)", hipSuccess);
@@ -1275,11 +1150,13 @@ int check_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, cons
   return SFH_OK;
 }
 
-// Arguments checked, count > 0.  Item i is decoded when dsts && dsts[i] (else it is a size query, as the single call with no
-// dst); stage: into ctx->d_out at (*out_off)[i] instead (the host-buffer entry point).  The steps of stream_run over the whole
-// call -- A to C for every item at once, the chain rounds until the last item's chain is complete -- then D to F and the
-// checksums in launch batches of whole items of at most batch_chunks * 32 KiB of output each.  Host synchronisations: the
-// wrapper, the candidates, the count pass and each chain round, and per launch batch the statuses and the checksums.
+// The one driver: a single stream is a call of one item.  Arguments checked, count > 0.  Item i is decoded when dsts && dsts[i]
+// (else it is a size query: steps A to C only); stage: into ctx->d_out at (*out_off)[i] instead (the host-buffer entry points).
+// The wrappers (k_inflate_head), then A to C for every item at once -- the candidate filter, the count pass, the chain rounds
+// with a follow launch until the last item's chain is complete, the scan of the counts -- then D to F (write pass, resolve) and
+// the checksums in launch batches of whole items of at most batch_chunks * 32 KiB of output each.  Host synchronisations: the
+// wrapper (not for raw items), the candidates, the count pass and each chain round, and per launch batch the statuses and the
+// checksums.
 int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
                      void* const* dsts, const uint64_t* dst_cap, bool stage, std::vector<uint64_t>* out_off, uint64_t* dst_n_out,
                      uint32_t* status, hipStream_t s) {
@@ -1319,9 +1196,9 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   }
   int rc = order_behind_last_call(ctx, s);
   if (rc) return rc;
-  // the wrappers: k_inflate_head over every item, as any_wrapper reads one (a raw body is the whole item: no launch)
+  // the wrappers: k_inflate_head over every item, as any_wrapper reads one (a raw body is the whole item: no launch, no wait)
   const size_t o_body = al16(sizeof(sf::InflateItem) * count), o_items = o_body + al16(16 * count);
-  if ((rc = grow(ctx, &ctx->d_sbt, &ctx->d_sbt_cap, o_items + sizeof(sf::StreamItem) * count, "stream batch rows"))) return rc;
+  if ((rc = grow(ctx, &ctx->d_sbt, &ctx->d_sbt_cap, o_items + sizeof(sf::StreamItem) * count, "stream item rows"))) return rc;
   uint64_t* d_body = (uint64_t*)(ctx->d_sbt + o_body);
   sf::StreamItem* d_items = (sf::StreamItem*)(ctx->d_sbt + o_items);
   if (container != SFH_RAW) {
@@ -1360,7 +1237,8 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   }
   const uint32_t nl = (uint32_t)live.size();
   if (nl == 0) return mark_call_end(ctx, s);
-  const uint32_t nc = (uint32_t)nc64;  // (<= the bound check_stream_batch checked)
+  if (nc64 >= ((uint64_t)1 << 31)) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 nominal chunks (SFH_STREAM_CHUNK)", hipSuccess);
+  const uint32_t nc = (uint32_t)nc64;
   // cand u64[nc] (then: the records' items u32[nc] | the follow list u32[nc]) | recs StreamChunk[nc] | list u32[nc]
   const size_t o_rec = al16(8 * (size_t)nc), o_list = o_rec + al16(sizeof(sf::StreamChunk) * (size_t)nc);
   const size_t stm_bytes = o_list + al16(4 * (size_t)nc);
@@ -1383,7 +1261,7 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   // A: candidates, every item's nominal chunks at once
   SF_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(sf::StreamItem) * nl, hipMemcpyHostToDevice, s), "H2D item rows");
   if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[0], s), "event");
-  SF_HIP(sf::launch_stream_find_batch(d_items, nl, nc, S, d_cand, s), "launch k_stream_find_batch");
+  SF_HIP(sf::launch_stream_find(d_items, nl, nc, S, d_cand, s), "launch k_stream_find");
   if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[1], s), "event");
   SF_HIP(hipMemcpyAsync(cand.data(), d_cand, 8 * (size_t)nc, hipMemcpyDeviceToHost, s), "D2H candidates");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
@@ -1405,7 +1283,7 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   SF_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(sf::StreamItem) * nl, hipMemcpyHostToDevice, s), "H2D item rows");
   SF_HIP(hipMemcpyAsync(d_rec_item, rec_item.data(), 4 * (size_t)M, hipMemcpyHostToDevice, s), "H2D record items");
   SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
-  SF_HIP(sf::launch_stream_decode_batch(false, d_items, d_rec_item, d_rec, nullptr, M, false, nullptr, s), "launch k_stream_decode_batch");
+  SF_HIP(sf::launch_stream_decode(false, d_items, d_rec_item, d_rec, nullptr, M, false, nullptr, s), "launch k_stream_decode");
   SF_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s), "D2H chunk records");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
   std::vector<char> done(nl, 0);
@@ -1429,10 +1307,10 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
     SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
     SF_HIP(hipMemcpyAsync(d_list, redo.data(), 4 * redo.size(), hipMemcpyHostToDevice, s), "H2D repair list");
     SF_HIP(hipMemcpyAsync(d_follow, follow.data(), 4 * follow.size(), hipMemcpyHostToDevice, s), "H2D follow list");
-    SF_HIP(sf::launch_stream_decode_batch(false, d_items, d_rec_item, d_rec, d_list, (uint32_t)redo.size(), false, nullptr, s),
-           "launch k_stream_decode_batch");
-    SF_HIP(sf::launch_stream_decode_batch(false, d_items, d_rec_item, d_rec, d_follow, (uint32_t)follow.size(), true, nullptr, s),
-           "launch k_stream_decode_batch");
+    SF_HIP(sf::launch_stream_decode(false, d_items, d_rec_item, d_rec, d_list, (uint32_t)redo.size(), false, nullptr, s),
+           "launch k_stream_decode");
+    SF_HIP(sf::launch_stream_decode(false, d_items, d_rec_item, d_rec, d_follow, (uint32_t)follow.size(), true, nullptr, s),
+           "launch k_stream_decode");
     SF_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s), "D2H chunk records");
     SF_HIP(hipStreamSynchronize(s), "stream sync");
   }
@@ -1527,8 +1405,8 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
     const uint32_t ra = items[dec[q0]].r0, rb = items[dec[q1 - 1]].r0 + items[dec[q1 - 1]].m;
     if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[2], s), "event");
     SF_HIP(hipMemcpyAsync(d_list, wlist.data(), 4 * wlist.size(), hipMemcpyHostToDevice, s), "H2D write list");
-    SF_HIP(sf::launch_stream_decode_batch(true, d_items, d_rec_item, d_rec, d_list, (uint32_t)wlist.size(), false, ctx->d_plane, s),
-           "launch k_stream_decode_batch");
+    SF_HIP(sf::launch_stream_decode(true, d_items, d_rec_item, d_rec, d_list, (uint32_t)wlist.size(), false, ctx->d_plane, s),
+           "launch k_stream_decode");
     if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[3], s), "event");
     SF_HIP(hipMemcpyAsync(rec.data() + ra, d_rec + ra, sizeof(sf::StreamChunk) * (size_t)(rb - ra), hipMemcpyDeviceToHost, s),
            "D2H chunk records");
@@ -1573,14 +1451,14 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
     const size_t o_res = al16(8 * compose.size()), o_link = o_res + al16(8 * resolve.size());
     const size_t o_sums = o_link + al16(4 * link.size()), o_fold = o_sums + al16(sizeof(sf::BatchChunk) * sums.size());
     const size_t o_fst = o_fold + al16(sizeof(sf::InflateItem) * fold.size()), rows_bytes = o_fst + al16(4 * fold.size());
-    if ((rc = grow(ctx, &ctx->d_sbr, &ctx->d_sbr_cap, rows_bytes, "stream batch group rows"))) return rc;
+    if ((rc = grow(ctx, &ctx->d_sbr, &ctx->d_sbr_cap, rows_bytes, "stream group rows"))) return rc;
     uint8_t* R = ctx->d_sbr;
     SF_HIP(hipMemcpyAsync(R, compose.data(), 8 * compose.size(), hipMemcpyHostToDevice, s), "H2D group rows");
     SF_HIP(hipMemcpyAsync(R + o_res, resolve.data(), 8 * resolve.size(), hipMemcpyHostToDevice, s), "H2D group rows");
     if (!link.empty()) SF_HIP(hipMemcpyAsync(R + o_link, link.data(), 4 * link.size(), hipMemcpyHostToDevice, s), "H2D link rows");
-    SF_HIP(sf::launch_stream_resolve_batch(ctx->d_plane, d_rec, d_items, (const sf::StreamGroup*)R, (uint32_t)compose.size(),
-                                           (const uint32_t*)(R + o_link), (uint32_t)link.size(), (const sf::StreamGroup*)(R + o_res),
-                                           (uint32_t)resolve.size(), ctx->d_wins, s), "launch k_stream_resolve_batch");
+    SF_HIP(sf::launch_stream_resolve(ctx->d_plane, d_rec, d_items, (const sf::StreamGroup*)R, (uint32_t)compose.size(),
+                                     (const uint32_t*)(R + o_link), (uint32_t)link.size(), (const sf::StreamGroup*)(R + o_res),
+                                     (uint32_t)resolve.size(), ctx->d_wins, s), "launch k_stream_resolve");
     if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[4], s), "event");
     if (!fold.empty()) {
       if ((rc = ensure_sums(ctx, (uint32_t)sums.size()))) return rc;
@@ -1601,6 +1479,17 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   ctx->stm_counts[5] = stm_bytes + peak;
   ctx->last_dtok_bytes = ctx->stm_counts[5];
   return mark_call_end(ctx, s);
+}
+
+// A single stream: the driver with count == 1 (dst null: the size query; stage: dst is a host buffer, the bytes land at
+// ctx->d_out).  The single calls' own argument checks stand in for check_stream_batch.
+int stream_one(sfh_ctx* ctx, const void* d_src, uint64_t src_n, uint32_t container, void* dst, uint64_t dst_cap, bool stage,
+               uint64_t* dst_n_out, uint32_t* status, hipStream_t s) {
+  std::vector<uint64_t> out_off;
+  const int rc = stream_batch_run(ctx, 1, &d_src, &src_n, container, dst ? &dst : nullptr, &dst_cap, stage, &out_off, dst_n_out,
+                                  status, s);
+  if (!rc && *status) snprintf(ctx->err, sizeof ctx->err, "DecompressStatus %u", *status);
+  return rc;
 }
 
 int check_any(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, uint64_t dst_n, bool dev) {
@@ -1898,9 +1787,8 @@ int sfh_compress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, cons
                        const uint64_t* dst_cap, uint64_t* out_n, const sfh_options* opt) {
   int rc = check_batch(ctx, count, srcs, src_n, dsts, dst_cap, out_n, opt, false);
   if (rc || count == 0) return rc;
-  // The items are packed into the device staging (sources 16-byte aligned, destinations a bound apart) through one pinned
-  // buffer: one copy per kStageBytes each way, then the device path over the staged items.
-  constexpr size_t kStageBytes = (size_t)kPipeBatchChunks * sf::kChunk;
+  // The items are packed into the device staging (sources 16-byte aligned, destinations a bound apart) and moved through the
+  // pinned buffer (stage_up, stage_down), with the device path over the staged items in between.
   std::vector<uint64_t> in_off, out_off;
   std::vector<const void*> d_srcs;
   std::vector<void*> d_dsts;
@@ -1937,18 +1825,7 @@ int sfh_compress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, cons
   }
   if (rc) return rc;
   if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  // up: the packed layout [0, in_off[count]) in pieces of kStageBytes (an item may straddle two pieces)
-  size_t item = 0;
-  for (uint64_t p0 = 0; p0 < in_off[count]; p0 += kStageBytes) {
-    const uint64_t p1 = std::min<uint64_t>(in_off[count], p0 + kStageBytes);
-    while (item < count && in_off[item] + src_n[item] <= p0) ++item;
-    for (size_t i = item; i < count && in_off[i] < p1; ++i) {
-      const uint64_t a = std::max(p0, in_off[i]), b = std::min(p1, in_off[i] + src_n[i]);
-      if (a < b) memcpy(ctx->h_stage + (a - p0), (const uint8_t*)srcs[i] + (a - in_off[i]), b - a);
-    }
-    SF_HIP(hipMemcpyAsync(ctx->d_in + p0, ctx->h_stage, p1 - p0, hipMemcpyHostToDevice, s), "H2D");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");  // (the next piece refills h_stage)
-  }
+  if ((rc = stage_up(ctx, srcs, src_n, in_off.data(), count, in_off[count], s))) return rc;
   for (size_t i = 0; i < count; ++i) {
     d_srcs[i] = ctx->d_in + in_off[i];
     d_dsts[i] = ctx->d_out + out_off[i];
@@ -1960,20 +1837,8 @@ int sfh_compress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, cons
   SF_HIP(hipMemcpyAsync(ctx->h_bn, ctx->d_bn, count * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "copy sizes");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
   for (size_t i = 0; i < count; ++i) out_n[i] = ctx->h_bn[i];
-  // down: [0, end of the last stream) of the output staging in pieces, each item's stream out of the pieces it lies in
-  const uint64_t end = out_off[count - 1] + out_n[count - 1];
-  item = 0;
-  for (uint64_t p0 = 0; p0 < end; p0 += kStageBytes) {
-    const uint64_t p1 = std::min<uint64_t>(end, p0 + kStageBytes);
-    SF_HIP(hipMemcpyAsync(ctx->h_stage, ctx->d_out + p0, p1 - p0, hipMemcpyDeviceToHost, s), "D2H");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");
-    while (item < count && out_off[item] + out_n[item] <= p0) ++item;
-    for (size_t i = item; i < count && out_off[i] < p1; ++i) {
-      const uint64_t a = std::max(p0, out_off[i]), b = std::min(p1, out_off[i] + out_n[i]);
-      if (a < b) memcpy((uint8_t*)dsts[i] + (a - out_off[i]), ctx->h_stage + (a - p0), b - a);
-    }
-  }
-  return SFH_OK;
+  // down: [0, end of the last stream) of the output staging, each item's stream
+  return stage_down(ctx, dsts, out_n, out_off.data(), count, out_off[count - 1] + out_n[count - 1], s);
 }
 
 int sfh_batch_index_size(const sfh_ctx* ctx, size_t* items, size_t* entries) {
@@ -2015,16 +1880,16 @@ int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, co
                          uint32_t container, uint32_t* status) {
   int rc = check_inflate_batch(ctx, count, srcs, src_n, index, subindex, dsts, dst_n, block_bytes, container, status, false);
   if (rc || count == 0) return rc;
-  // As sfh_compress_batch: the items packed into the device staging (16-byte aligned) through one pinned buffer, one copy per
-  // kStageBytes each way; only the items whose status is 0 are copied out of it.
-  constexpr size_t kStageBytes = (size_t)kPipeBatchChunks * sf::kChunk;
-  std::vector<uint64_t> in_off, out_off;
+  // The items packed into the device staging (16-byte aligned) and moved through the pinned buffer (stage_up, stage_down);
+  // only the items whose status is 0 are copied out of it.
+  std::vector<uint64_t> in_off, out_off, got;
   std::vector<const void*> d_srcs;
   std::vector<void*> d_dsts;
   size_t entries = 0, segs = 0;
   try {
     in_off.resize(count + 1);
     out_off.resize(count + 1);
+    got.resize(count);
     d_srcs.resize(count);
     d_dsts.resize(count);
   } catch (...) {
@@ -2042,34 +1907,14 @@ int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, co
   if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_off[count] ? out_off[count] : 16, "output staging");
   if (!rc && index) rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, entries * sizeof(uint64_t), "index staging");
   if (!rc && subindex) rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, segs * SFH_SUBINDEX_WORDS * sizeof(uint32_t), "sub-index staging");
-  if (!rc && ctx->bstatus_cap < count) {
-    (void)hipFree(ctx->d_bstatus);
-    if (ctx->h_bstatus) (void)hipHostFree(ctx->h_bstatus);
-    ctx->d_bstatus = ctx->h_bstatus = nullptr;
-    ctx->bstatus_cap = 0;
-    if (hipMalloc(&ctx->d_bstatus, count * sizeof(uint32_t)) != hipSuccess ||
-        hipHostMalloc((void**)&ctx->h_bstatus, count * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-      rc = fail(ctx, SFH_E_NOMEM, "batch statuses", hipSuccess);
-    else
-      ctx->bstatus_cap = count;
-  }
+  if (!rc) rc = ensure_bstatus(ctx, count);
   if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
     ctx->h_stage = nullptr;
     rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
   }
   if (rc) return rc;
   if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  size_t item = 0;
-  for (uint64_t p0 = 0; p0 < in_off[count]; p0 += kStageBytes) {
-    const uint64_t p1 = std::min<uint64_t>(in_off[count], p0 + kStageBytes);
-    while (item < count && in_off[item] + src_n[item] <= p0) ++item;
-    for (size_t i = item; i < count && in_off[i] < p1; ++i) {
-      const uint64_t a = std::max(p0, in_off[i]), b = std::min(p1, in_off[i] + src_n[i]);
-      if (a < b) memcpy(ctx->h_stage + (a - p0), (const uint8_t*)srcs[i] + (a - in_off[i]), b - a);
-    }
-    SF_HIP(hipMemcpyAsync(ctx->d_in + p0, ctx->h_stage, p1 - p0, hipMemcpyHostToDevice, s), "H2D");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");  // (the next piece refills h_stage)
-  }
+  if ((rc = stage_up(ctx, srcs, src_n, in_off.data(), count, in_off[count], s))) return rc;
   if (index) SF_HIP(hipMemcpyAsync(ctx->d_index, index, entries * sizeof(uint64_t), hipMemcpyHostToDevice, s), "H2D index");
   if (subindex)
     SF_HIP(hipMemcpyAsync(ctx->d_sub, subindex, segs * SFH_SUBINDEX_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, s), "H2D sub-index");
@@ -2084,25 +1929,12 @@ int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, co
   }
   SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy statuses");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
-  for (size_t i = 0; i < count; ++i) status[i] = ctx->h_bstatus[i];
-  // down: the packed output in pieces, each item with status 0 out of the pieces it lies in
-  const uint64_t end = out_off[count];
-  item = 0;
-  for (uint64_t p0 = 0; p0 < end; p0 += kStageBytes) {
-    const uint64_t p1 = std::min<uint64_t>(end, p0 + kStageBytes);
-    while (item < count && out_off[item] + dst_n[item] <= p0) ++item;
-    bool any = false;
-    for (size_t i = item; i < count && out_off[i] < p1 && !any; ++i) any = status[i] == 0 && dst_n[i] && out_off[i] + dst_n[i] > p0;
-    if (!any) continue;
-    SF_HIP(hipMemcpyAsync(ctx->h_stage, ctx->d_out + p0, p1 - p0, hipMemcpyDeviceToHost, s), "D2H");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");
-    for (size_t i = item; i < count && out_off[i] < p1; ++i) {
-      if (status[i] != 0) continue;
-      const uint64_t a = std::max(p0, out_off[i]), b = std::min(p1, out_off[i] + dst_n[i]);
-      if (a < b) memcpy((uint8_t*)dsts[i] + (a - out_off[i]), ctx->h_stage + (a - p0), b - a);
-    }
+  for (size_t i = 0; i < count; ++i) {
+    status[i] = ctx->h_bstatus[i];
+    got[i] = status[i] == 0 ? dst_n[i] : 0;
   }
-  return SFH_OK;
+  // down: the packed output, each item with status 0
+  return stage_down(ctx, dsts, got.data(), out_off.data(), count, out_off[count], s);
 }
 
 int sfh_decompress_ranges_device_async(sfh_ctx* ctx, const void* d_src, size_t src_n, const uint64_t* d_index,
@@ -2159,8 +1991,8 @@ int sfh_decompress_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uin
   // rounded out to 16 bytes (a damaged index cannot send a row outside its piece: a row reads from its first entry on, and
   // only when its second entry is not above the bytes readable) --, its index entries and its sub-index words, each packed span
   // after span.  The destinations are packed as well, 16 bytes apart at least.
-  constexpr size_t kStageBytes = (size_t)kPipeBatchChunks * sf::kChunk;
-  std::vector<uint64_t> p_lo, p_n, in_off, out_off, ix_off;
+  std::vector<uint64_t> p_lo, p_n, in_off, out_off, ix_off, got;
+  std::vector<const void*> p_src;
   std::vector<RangeSource> from;
   std::vector<void*> d_dsts;
   try {
@@ -2169,6 +2001,8 @@ int sfh_decompress_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uin
     in_off.resize(count + 1);
     out_off.resize(count + 1);
     ix_off.resize(count + 1);
+    got.resize(count);
+    p_src.resize(count);
     from.resize(count);
     d_dsts.resize(count);
   } catch (...) {
@@ -2188,6 +2022,7 @@ int sfh_decompress_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uin
     hi = std::min<uint64_t>(src_n, (std::min<uint64_t>(hi, src_n) + 15) / 16 * 16);
     p_lo[r] = lo;
     p_n[r] = hi - lo;
+    p_src[r] = (const uint8_t*)src + lo;
     in_off[r + 1] = (in_off[r] + p_n[r] + 15) / 16 * 16;
     out_off[r + 1] = (out_off[r] + lengths[r] + 15) / 16 * 16;
     ix_off[r + 1] = ix_off[r] + (S.nrows ? S.nrows + 1 : 0);
@@ -2207,18 +2042,7 @@ int sfh_decompress_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uin
   }
   if (rc) return rc;
   if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  // up: the packed pieces, one copy per kStageBytes
-  size_t item = 0;
-  for (uint64_t p0 = 0; p0 < in_off[count]; p0 += kStageBytes) {
-    const uint64_t p1 = std::min<uint64_t>(in_off[count], p0 + kStageBytes);
-    while (item < count && in_off[item] + p_n[item] <= p0) ++item;
-    for (size_t r = item; r < count && in_off[r] < p1; ++r) {
-      const uint64_t a = std::max(p0, in_off[r]), b = std::min(p1, in_off[r] + p_n[r]);
-      if (a < b) memcpy(ctx->h_stage + (a - p0), (const uint8_t*)src + p_lo[r] + (a - in_off[r]), b - a);
-    }
-    SF_HIP(hipMemcpyAsync(ctx->d_in + p0, ctx->h_stage, p1 - p0, hipMemcpyHostToDevice, s), "H2D");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");  // (the next piece refills h_stage)
-  }
+  if ((rc = stage_up(ctx, p_src.data(), p_n.data(), in_off.data(), count, in_off[count], s))) return rc;
   // the spans' index entries and sub-index words through the same staging
   {
     const size_t per = kStageBytes / sizeof(uint64_t);
@@ -2265,25 +2089,12 @@ int sfh_decompress_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uin
   }
   SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy statuses");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
-  for (size_t r = 0; r < count; ++r) status[r] = ctx->h_bstatus[r];
-  // down: the packed output in pieces, each range with status 0 out of the pieces it lies in
-  const uint64_t end = out_off[count];
-  item = 0;
-  for (uint64_t p0 = 0; p0 < end; p0 += kStageBytes) {
-    const uint64_t p1 = std::min<uint64_t>(end, p0 + kStageBytes);
-    while (item < count && out_off[item] + lengths[item] <= p0) ++item;
-    bool any = false;
-    for (size_t r = item; r < count && out_off[r] < p1 && !any; ++r) any = status[r] == 0 && lengths[r] && out_off[r] + lengths[r] > p0;
-    if (!any) continue;
-    SF_HIP(hipMemcpyAsync(ctx->h_stage, ctx->d_out + p0, p1 - p0, hipMemcpyDeviceToHost, s), "D2H");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");
-    for (size_t r = item; r < count && out_off[r] < p1; ++r) {
-      if (status[r] != 0) continue;
-      const uint64_t a = std::max(p0, out_off[r]), b = std::min(p1, out_off[r] + lengths[r]);
-      if (a < b) memcpy((uint8_t*)dsts[r] + (a - out_off[r]), ctx->h_stage + (a - p0), b - a);
-    }
+  for (size_t r = 0; r < count; ++r) {
+    status[r] = ctx->h_bstatus[r];
+    got[r] = status[r] == 0 ? lengths[r] : 0;
   }
-  return SFH_OK;
+  // down: the packed output, each range with status 0
+  return stage_down(ctx, dsts, got.data(), out_off.data(), count, out_off[count], s);
 }
 
 uint32_t sfh_last_block_bytes(const sfh_ctx* ctx) { return (ctx && ctx->index_valid) ? ctx->last_block_bytes : 0u; }
@@ -2539,7 +2350,7 @@ int sfh_inflate_stream_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uin
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
   (void)hipGetLastError();  // see enqueue()
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  return stream_run(ctx, (const uint8_t*)d_src, src_n, container, (uint8_t*)d_dst, dst_cap, !d_dst, false, dst_n_out, status, s);
+  return stream_one(ctx, d_src, src_n, container, d_dst, dst_cap, false, dst_n_out, status, s);
 }
 
 int sfh_inflate_stream(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, void* dst, uint64_t dst_cap,
@@ -2553,9 +2364,8 @@ int sfh_inflate_stream(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t con
   hipStream_t s = ctx->stream;
   if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
   if (src_n) SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, s), "H2D");
-  const bool query = !dst;
-  if ((rc = stream_run(ctx, ctx->d_in, src_n, container, nullptr, dst_cap, query, !query, dst_n_out, status, s))) return rc;
-  if (!query && *status == 0 && *dst_n_out) {
+  if ((rc = stream_one(ctx, ctx->d_in, src_n, container, dst, dst_cap, dst != nullptr, dst_n_out, status, s))) return rc;
+  if (dst && *status == 0 && *dst_n_out) {  // (staged: the one item lies at ctx->d_out)
     SF_HIP(hipMemcpyAsync(dst, ctx->d_out, *dst_n_out, hipMemcpyDeviceToHost, s), "D2H");
     SF_HIP(hipStreamSynchronize(s), "stream sync");
   }
@@ -2577,13 +2387,13 @@ int sfh_inflate_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs
                              void* const* dsts, const uint64_t* dst_cap, uint64_t* dst_n_out, uint32_t* status) {
   int rc = check_stream_batch(ctx, count, srcs, src_n, container, dsts, dst_cap, dst_n_out, status, false);
   if (rc || count == 0) return rc;
-  // As sfh_decompress_batch: the items packed into the device staging (16-byte aligned) through one pinned buffer, one copy per
-  // kStageBytes each way; only the items whose status is 0 are copied out (their output packed by size in ctx->d_out).
-  constexpr size_t kStageBytes = (size_t)kPipeBatchChunks * sf::kChunk;
-  std::vector<uint64_t> in_off, out_off;
+  // The items packed into the device staging (16-byte aligned) and moved through the pinned buffer (stage_up, stage_down);
+  // only the items whose status is 0 are copied out (their output packed by size in ctx->d_out).
+  std::vector<uint64_t> in_off, out_off, got;
   std::vector<const void*> d_srcs;
   try {
     in_off.resize(count + 1);
+    got.resize(count);
     d_srcs.resize(count);
   } catch (...) {
     return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
@@ -2598,41 +2408,16 @@ int sfh_inflate_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs
   }
   if (rc) return rc;
   if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  size_t item = 0;
-  for (uint64_t p0 = 0; p0 < in_off[count]; p0 += kStageBytes) {
-    const uint64_t p1 = std::min<uint64_t>(in_off[count], p0 + kStageBytes);
-    while (item < count && in_off[item] + src_n[item] <= p0) ++item;
-    for (size_t i = item; i < count && in_off[i] < p1; ++i) {
-      const uint64_t a = std::max(p0, in_off[i]), b = std::min(p1, in_off[i] + src_n[i]);
-      if (a < b) memcpy(ctx->h_stage + (a - p0), (const uint8_t*)srcs[i] + (a - in_off[i]), b - a);
-    }
-    SF_HIP(hipMemcpyAsync(ctx->d_in + p0, ctx->h_stage, p1 - p0, hipMemcpyHostToDevice, s), "H2D");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");  // (the next piece refills h_stage)
-  }
+  if ((rc = stage_up(ctx, srcs, src_n, in_off.data(), count, in_off[count], s))) return rc;
   for (size_t i = 0; i < count; ++i) d_srcs[i] = ctx->d_in + in_off[i];
   if ((rc = stream_batch_run(ctx, count, d_srcs.data(), src_n, container, dsts, dst_cap, true, &out_off, dst_n_out, status, s))) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
   if (!dsts) return SFH_OK;
-  // down: the packed output in pieces, each item with status 0 out of the pieces it lies in
-  const uint64_t end = out_off[count];
-  auto out_n = [&](size_t i) { return (dsts[i] && status[i] == 0) ? dst_n_out[i] : 0; };
-  item = 0;
-  for (uint64_t p0 = 0; p0 < end; p0 += kStageBytes) {
-    const uint64_t p1 = std::min<uint64_t>(end, p0 + kStageBytes);
-    while (item < count && out_off[item] + out_n(item) <= p0) ++item;
-    bool any = false;
-    for (size_t i = item; i < count && out_off[i] < p1 && !any; ++i) any = out_n(i) && out_off[i] + out_n(i) > p0;
-    if (!any) continue;
-    SF_HIP(hipMemcpyAsync(ctx->h_stage, ctx->d_out + p0, p1 - p0, hipMemcpyDeviceToHost, s), "D2H");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");
-    for (size_t i = item; i < count && out_off[i] < p1; ++i) {
-      const uint64_t a = std::max(p0, out_off[i]), b = std::min(p1, out_off[i] + out_n(i));
-      if (a < b) memcpy((uint8_t*)dsts[i] + (a - out_off[i]), ctx->h_stage + (a - p0), b - a);
-    }
-  }
-  return SFH_OK;
+  // down: the packed output, each decoded item with status 0
+  for (size_t i = 0; i < count; ++i) got[i] = (dsts[i] && status[i] == 0) ? dst_n_out[i] : 0;
+  return stage_down(ctx, dsts, got.data(), out_off.data(), count, out_off[count], s);
 }
 
 int sfh_last_stream_stats(sfh_ctx* ctx, float ms[SFH_STREAM_NSTAGES], uint64_t counts[SFH_STREAM_NCOUNTS]) {

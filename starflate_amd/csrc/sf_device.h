@@ -336,20 +336,10 @@ hipError_t launch_inflate_bytes_clip(const InflateSeg* rows, const InflateClip* 
                                      const uint32_t* tokens, SegInfo* info, hipStream_t s);
 hipError_t launch_inflate_fold_spans(const InflateSpan* spans, uint32_t nspans, const SegInfo* info, uint32_t* status, hipStream_t s);
 
-// sf_stream.hip: a stream without flush points (sfh_inflate_stream*); StreamChunk and the chain round: sf_stream_chain.h
-constexpr uint64_t kNoCandidate = ~0ull;
-hipError_t launch_stream_find(const uint8_t* src, uint64_t src_n, uint64_t b0, uint64_t body_n, uint64_t step_bytes, uint32_t nc,
-                              uint64_t* cand, hipStream_t s);
-// list (nullable: 0..n-1): the records to decode.  follow: list[0] goes on into the records after it while their links break
-// (m: the record count; see k_stream_decode).  write: the exact pass into plane (cap: the output capacity)
-hipError_t launch_stream_decode(bool write, const uint8_t* src, uint64_t src_n, uint64_t b0, uint64_t body_n, StreamChunk* recs,
-                                const uint32_t* list, uint32_t n, uint32_t m, bool follow, uint16_t* plane, uint64_t cap,
-                                hipStream_t s);
-uint32_t stream_group(uint32_t n);  // chunks per group of the resolve; tables: (groups - 1) * 32768 u16
-hipError_t launch_stream_resolve(const uint16_t* plane, const StreamChunk* recs, uint32_t n, uint16_t* tables, uint8_t* dst,
-                                 hipStream_t s);
-// Batches of such streams (sfh_inflate_stream_batch*): the same passes over the call's items, each read from a row.  The
+// sf_stream.hip: streams without flush points (sfh_inflate_stream*, sfh_inflate_stream_batch*; a single stream is a call of one
+// item); StreamChunk and the chain round: sf_stream_chain.h.  Every pass runs over the call's items, each read from a row.  The
 // records of all items lie in one array, item after item; a record's item is a separate u32 (StreamChunk keeps its layout).
+constexpr uint64_t kNoCandidate = ~0ull;
 struct StreamItem {      // per item whose body is decoded (a wrapper that failed: no row)
   const uint8_t* src;
   uint64_t src_n;
@@ -366,17 +356,20 @@ struct StreamItem {      // per item whose body is decoded (a wrapper that faile
 struct StreamGroup {     // compose / resolve: one workgroup per (item, group)
   uint32_t item, g;
 };
-static_assert(sizeof(StreamItem) == 88 && sizeof(StreamGroup) == 8, "stream batch rows");
+static_assert(sizeof(StreamItem) == 88 && sizeof(StreamGroup) == 8, "stream item rows");
 // one wave per nominal chunk of the call (nc), its item found by a search over items[].c0
-hipError_t launch_stream_find_batch(const StreamItem* items, uint32_t nitems, uint32_t nc, uint64_t step_bytes, uint64_t* cand,
-                                    hipStream_t s);
-// as launch_stream_decode; rec_item[r]: record r's row in items.  follow: one lane per list entry, each within its item's records
-hipError_t launch_stream_decode_batch(bool write, const StreamItem* items, const uint32_t* rec_item, StreamChunk* recs,
-                                      const uint32_t* list, uint32_t n, bool follow, uint16_t* plane, hipStream_t s);
+hipError_t launch_stream_find(const StreamItem* items, uint32_t nitems, uint32_t nc, uint64_t step_bytes, uint64_t* cand,
+                              hipStream_t s);
+// list (nullable: 0..n-1): the records to decode; rec_item[r]: record r's row in items.  follow: one lane per list entry goes on
+// into the records after it while their links break, within its item's records (see k_stream_decode).  write: the exact pass
+// into plane + the item's offset
+hipError_t launch_stream_decode(bool write, const StreamItem* items, const uint32_t* rec_item, StreamChunk* recs,
+                                const uint32_t* list, uint32_t n, bool follow, uint16_t* plane, hipStream_t s);
+uint32_t stream_group(uint32_t n);  // chunks per group of the resolve; an item's tables: (groups - 1) * 32768 u16
 // compose rows (every group but an item's last), link (one workgroup per item of more than one group), resolve rows (all)
-hipError_t launch_stream_resolve_batch(const uint16_t* plane, const StreamChunk* recs, const StreamItem* items,
-                                       const StreamGroup* compose, uint32_t ncompose, const uint32_t* link, uint32_t nlink,
-                                       const StreamGroup* resolve, uint32_t nresolve, uint16_t* tables, hipStream_t s);
+hipError_t launch_stream_resolve(const uint16_t* plane, const StreamChunk* recs, const StreamItem* items,
+                                 const StreamGroup* compose, uint32_t ncompose, const uint32_t* link, uint32_t nlink,
+                                 const StreamGroup* resolve, uint32_t nresolve, uint16_t* tables, hipStream_t s);
 
 // sf_guard.hip: does the LDS execute a returning atomic's lanes in ascending order (op 0: ds_wrxchg_rtn_b32, 1: ds_mskor_rtn_b32)?
 // d_result[0] = mismatches against the sequential model, [1] = positions checked

@@ -1,24 +1,29 @@
-// sf_stream.hip -- one raw, zlib or gzip stream (one member) decoded on the GPU with no side information and no flush points
-// (sfh_inflate_stream*, DESIGN.md 3a "Streams without flush points").  The body (the stream without its wrapper) is cut into
-// chunks at speculative block starts, the chunks are decoded lane-serially, and a chain rule keeps exactly the serial decoder's
-// block sequence:
+// sf_stream.hip -- raw, zlib or gzip streams (one member each) decoded on the GPU with no side information and no flush points
+// (sfh_inflate_stream*, sfh_inflate_stream_batch*; DESIGN.md 3a "Streams without flush points").  A call holds one item or
+// many; a single stream is a call of one item.  Each kernel reads its item's stream, body (the stream without its wrapper),
+// plane, capacity and output from a StreamItem row (sf_device.h).  The body is cut into chunks at speculative block starts, the
+// chunks are decoded lane-serially, and a chain rule keeps exactly the serial decoder's block sequence.  The records of all
+// items lie in one array, item after item (a record's item: rec_item):
 //
-//   k_stream_find        A. one wave per nominal chunk start (every S body bytes, S = SFH_STREAM_CHUNK): the first bit offset
-//                           before the next nominal start where dynamic_header_candidate (sf_inflate_core.h) holds.  Chunk 0
-//                           starts at the body's first bit whatever its block type.
-//   k_stream_decode<0>   B. one lane per chunk: whole blocks from the chunk's start until the first block end at or beyond the
-//                           next chunk's start (the last chunk: until BFINAL or an error).  Records the end bit, the output
-//                           bytes, BFINAL and the first structural problem.  The checks that need the absolute output position
-//                           (distance <= bytes written, dst capacity) wait for the write pass.
-//                        C. on the host (sf_stream_chain.h): chunk i+1 is confirmed when chunk i is and ended, without BFINAL,
-//                           exactly on i+1's start.  Every broken link is redecoded from the end before it, all of a round in
-//                           parallel; then one lane follows the first of them through the run of broken links behind it.
-//   k_stream_decode<1>   D. the confirmed chain again, with the exact rules now that each chunk's output offset O_i (an
-//                           exclusive scan of the counts) and the capacity are known.  Every output byte becomes a u16 in the
-//                           symbol plane: a literal byte (< 256), or 0x8000 | k, byte k of the 32 KiB window before O_i.
-//   k_stream_compose     F. the window of chunk i+1 is a map of chunk i's tail over chunk i's window.  Groups of G ~ sqrt(N)
-//   k_stream_link           chunks compose their maps in parallel (compose), one workgroup carries the window across the
-//   k_stream_resolve        groups (link, N/G steps), and every group then writes its chunks' final bytes (resolve).
+//   k_stream_find        A. one wave per nominal chunk start of the call (every S body bytes of an item, S = SFH_STREAM_CHUNK):
+//                           the first bit offset before the next nominal start where dynamic_header_candidate
+//                           (sf_inflate_core.h) holds.  An item's chunk 0 starts at its body's first bit whatever its block type.
+//   k_stream_decode<0>   B. one lane per record: whole blocks from the chunk's start until the first block end at or beyond the
+//                           next chunk's start (an item's last chunk: until BFINAL or an error).  Records the end bit, the
+//                           output bytes, BFINAL and the first structural problem.  The checks that need the absolute output
+//                           position (distance <= bytes written, dst capacity) wait for the write pass.
+//                        C. on the host (sf_stream_chain.h), over each item's slice of the records: chunk i+1 is confirmed when
+//                           chunk i is and ended, without BFINAL, exactly on i+1's start.  Every broken link is redecoded from
+//                           the end before it, all of a round in parallel; then one lane per item with a broken link follows
+//                           the first of them through the run of broken links behind it, and stops at its item's last record.
+//   k_stream_decode<1>   D. the confirmed records of a launch batch's items again, with the exact rules now that each chunk's
+//                           output offset O_i (an exclusive scan of its item's counts) and the capacity are known.  Every
+//                           output byte becomes a u16 in the symbol plane (plane + the item's offset, so a record's base stays
+//                           item-relative): a literal byte (< 256), or 0x8000 | k, byte k of the 32 KiB window before O_i.
+//   k_stream_compose     F. the window of chunk i+1 is a map of chunk i's tail over chunk i's window.  Per item, groups of
+//   k_stream_link           G ~ sqrt(N) chunks compose their maps in parallel (compose, one workgroup per (item, group)), one
+//   k_stream_resolve        workgroup per item of more than one group carries the window across its groups (link, N/G steps),
+//                           and every group then writes its chunks' final bytes into the item's dst (resolve).
 //
 // The statuses are the serial decoder's (include/starflate/decompress.hpp): stream_decode follows its checks in its order,
 // including where the input runs out.  A stream with no candidates (Z_FIXED, level 0, ...) is decoded by one lane: slow, but
@@ -30,91 +35,108 @@ namespace sf {
 
 namespace {
 
-using namespace inflate;
-
-__global__ __launch_bounds__(KF_THREADS) void k_stream_find(const uint8_t* __restrict__ src, uint64_t src_n, uint64_t b0,
-                                                            uint64_t body_n, uint64_t step_bits, uint32_t nc,
-                                                            uint64_t* __restrict__ cand) {
+// one wave per nominal chunk row of the call; the row's item is the last whose first row c0 is at or before it
+__global__ __launch_bounds__(KF_THREADS) void k_stream_find(const StreamItem* __restrict__ items, uint32_t nitems, uint32_t nc,
+                                                            uint64_t step_bits, uint64_t* __restrict__ cand) {
   __shared__ uint8_t s_lut[KF_THREADS][128];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t c = blockIdx.x * (KF_THREADS / 64) + wave;
-  if (c >= nc) return;
+  const uint32_t r = blockIdx.x * (KF_THREADS / 64) + wave;
+  if (r >= nc) return;
+  uint32_t lo = 0, hi = nitems;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (items[mid].c0 <= r) lo = mid;
+    else hi = mid;
+  }
+  const StreamItem& I = items[lo];
+  const uint32_t c = r - I.c0;
   if (c == 0) {
-    if (lane == 0) cand[0] = 0;
+    if (lane == 0) cand[r] = 0;
     return;
   }
-  const uint64_t bits = 8 * body_n, lo = (uint64_t)c * step_bits;
-  const uint64_t hi = lo + step_bits < bits ? lo + step_bits : bits;
-  for (uint64_t at = lo; at < hi; at += 64) {
+  const uint64_t bits = 8 * I.body_n, lo_bit = (uint64_t)c * step_bits;
+  const uint64_t hi_bit = lo_bit + step_bits < bits ? lo_bit + step_bits : bits;
+  for (uint64_t at = lo_bit; at < hi_bit; at += 64) {
     const uint64_t p = at + lane;
     bool hit = false;
-    if (p < hi) {
+    if (p < hi_bit) {
       StreamReader rd;
-      rd.open(src, src_n, b0, body_n, p);
+      rd.open(I.src, I.src_n, I.b0, I.body_n, p);
       hit = dynamic_header_candidate(rd.br, s_lut[threadIdx.x]);
     }
     const uint64_t b = __ballot(hit);
     if (b) {
-      if (lane == 0) cand[c] = at + (uint64_t)(__ffsll((unsigned long long)b) - 1);
+      if (lane == 0) cand[r] = at + (uint64_t)(__ffsll((unsigned long long)b) - 1);
       return;
     }
   }
-  if (lane == 0) cand[c] = kNoCandidate;
+  if (lane == 0) cand[r] = kNoCandidate;
 }
 
-// list: the records to decode (a repair round: the chunks to decode again).  follow (count pass; one lane, list[0]: the first
-// broken link behind the confirmed chain, already decoded again): the lane goes on into the chunks after it while their links
-// break -- each next chunk starts where the one before ended, as the host's chain round would set it -- until a link holds or
-// the records end.  A run of false candidates (stored blocks full of DEFLATE data put one in nearly every nominal chunk) is
-// then mended in one round instead of one link per round; the other lanes' speculative repairs of the round have finished (an
-// earlier launch), so no record is written by two lanes.
+// list: the records to decode (nullable: 0..n-1; a repair round: the records to decode again), each against its item's stream,
+// plane (write: plane + I.plane) and capacity.  follow (count pass; one lane per list entry: an item's first broken link behind
+// its confirmed chain, already decoded again): the lane goes on into the records after it while their links break -- each next
+// chunk starts where the one before ended, as the host's chain round would set it -- until a link holds or its item's records
+// end, so a repair never runs into the next item.  A run of false candidates (stored blocks full of DEFLATE data put one in
+// nearly every nominal chunk) is then mended in one round instead of one link per round; the other lanes' speculative repairs
+// of the round have finished (an earlier launch), so no record is written by two lanes.
 template <bool WRITE>
-__global__ __launch_bounds__(KS_LANES) void k_stream_decode(const uint8_t* __restrict__ src, uint64_t src_n, uint64_t b0,
-                                                            uint64_t body_n, StreamChunk* __restrict__ recs,
-                                                            const uint32_t* __restrict__ list, uint32_t n, uint32_t m,
-                                                            bool follow, uint16_t* __restrict__ plane, uint64_t cap) {
+__global__ __launch_bounds__(KS_LANES) void k_stream_decode(const StreamItem* __restrict__ items,
+                                                            const uint32_t* __restrict__ rec_item, StreamChunk* __restrict__ recs,
+                                                            const uint32_t* __restrict__ list, uint32_t n, bool follow,
+                                                            uint16_t* __restrict__ plane) {
   extern __shared__ __align__(16) uint8_t s_tables[];
   const uint32_t k = blockIdx.x * KS_LANES + threadIdx.x;
   if (k >= n) return;
   uint8_t* tab = s_tables + threadIdx.x * LaneLayout::kBytes;
+  if (WRITE && follow) return;
   uint32_t i = list ? list[k] : k;
-  if (!follow) {
-    stream_decode<WRITE>(src, src_n, b0, body_n, recs[i], tab, plane, cap);
-    return;
-  }
-  if (WRITE || k != 0) return;
-  for (uint32_t j = i + 1; j < m; i = j++) {
-    StreamChunk& a = recs[i];
-    StreamChunk& b = recs[j];
-    if (a.status != 0 || a.final_ || a.end == b.start) break;
-    a.limit = a.end;  // (as stream_chain_round: the same decode)
-    b.start = a.end;
-    stream_decode<false>(src, src_n, b0, body_n, b, tab, plane, cap);  // (b.start >= b.limit: an empty chunk)
+  const StreamItem& I = items[rec_item[i]];
+  const uint32_t m = I.r0 + I.m;
+  for (uint32_t j = follow ? i + 1 : i; j < m; i = j++) {
+    if (follow) {
+      StreamChunk& a = recs[i];
+      StreamChunk& b = recs[j];
+      if (a.status != 0 || a.final_ || a.end == b.start) break;
+      a.limit = a.end;  // (as stream_chain_round: the same decode)
+      b.start = a.end;
+    }
+    stream_decode<WRITE>(I.src, I.src_n, I.b0, I.body_n, recs[j], tab, WRITE ? plane + I.plane : plane, I.cap);
+    if (!follow) break;  // (follow: b.start >= b.limit is an empty chunk)
   }
 }
 
-// group g (all but the last): the composite map of its chunks over the window before its first chunk (group 0: the window
-// itself, whose bytes before the stream are never read)
+// row (item, group), every group but an item's last: the composite map of the group's chunks over the window before its first
+// chunk (group 0: the window itself, whose bytes before the stream are never read)
 __global__ __launch_bounds__(KR_THREADS) void k_stream_compose(const uint16_t* __restrict__ plane,
-                                                               const StreamChunk* __restrict__ recs, uint32_t n, uint32_t G,
+                                                               const StreamChunk* __restrict__ recs,
+                                                               const StreamItem* __restrict__ items,
+                                                               const StreamGroup* __restrict__ rows,
                                                                uint16_t* __restrict__ tables) {
   __shared__ uint16_t T[kWin];
-  const uint32_t g = blockIdx.x;
+  const StreamGroup R = rows[blockIdx.x];
+  const StreamItem& I = items[R.item];
+  const uint32_t g = R.g, G = I.G, n = I.chain;
   for (uint32_t j = threadIdx.x; j < kWin; j += KR_THREADS) T[j] = g ? (uint16_t)(0x8000u | j) : 0;
   __syncthreads();
   const uint32_t i1 = (g + 1) * G < n ? (g + 1) * G : n;
-  for (uint32_t i = g * G; i < i1; ++i) window_step(T, plane, recs[i]);
-  for (uint32_t j = threadIdx.x; j < kWin; j += KR_THREADS) tables[(size_t)g * kWin + j] = T[j];
+  for (uint32_t i = g * G; i < i1; ++i) window_step(T, plane + I.plane, recs[I.r0 + i]);
+  for (uint32_t j = threadIdx.x; j < kWin; j += KR_THREADS) tables[I.win + (size_t)g * kWin + j] = T[j];
 }
 
-// one workgroup: tables[g] <- the window after group g, in bytes (tables[0] is that already)
-__global__ __launch_bounds__(KR_THREADS) void k_stream_link(uint16_t* __restrict__ tables, uint32_t ng) {
+// one workgroup per listed item (those of more than one group), all of them at once: the item's tables[g] <- the window after
+// its group g, in bytes (tables[0] is that already)
+__global__ __launch_bounds__(KR_THREADS) void k_stream_link(const StreamItem* __restrict__ items,
+                                                            const uint32_t* __restrict__ link, uint16_t* __restrict__ tables) {
   __shared__ uint16_t W[kWin];
-  for (uint32_t j = threadIdx.x; j < kWin; j += KR_THREADS) W[j] = tables[j];
+  const StreamItem& I = items[link[blockIdx.x]];
+  const uint32_t ng = (I.chain + I.G - 1) / I.G;
+  uint16_t* t = tables + I.win;
+  for (uint32_t j = threadIdx.x; j < kWin; j += KR_THREADS) W[j] = t[j];
   __syncthreads();
   for (uint32_t g = 1; g + 1 < ng; ++g) {
     uint16_t v[kPerThread];
-    uint16_t* C = tables + (size_t)g * kWin;
+    uint16_t* C = t + (size_t)g * kWin;
 #pragma unroll
     for (uint32_t r = 0; r < kPerThread; ++r) {
       const uint16_t x = C[r * KR_THREADS + threadIdx.x];
@@ -130,44 +152,50 @@ __global__ __launch_bounds__(KR_THREADS) void k_stream_link(uint16_t* __restrict
   }
 }
 
-// group g: its chunks' bytes into dst, each from its window, then the window carried to the next chunk
+// row (item, group): the group's chunks' bytes into the item's dst, each from its window, then the window carried to the next
+// chunk
 __global__ __launch_bounds__(KR_THREADS) void k_stream_resolve(const uint16_t* __restrict__ plane,
-                                                               const StreamChunk* __restrict__ recs, uint32_t n, uint32_t G,
-                                                               const uint16_t* __restrict__ tables, uint8_t* __restrict__ dst) {
+                                                               const StreamChunk* __restrict__ recs,
+                                                               const StreamItem* __restrict__ items,
+                                                               const StreamGroup* __restrict__ rows,
+                                                               const uint16_t* __restrict__ tables) {
   __shared__ uint16_t T[kWin];
-  const uint32_t g = blockIdx.x;
-  for (uint32_t j = threadIdx.x; j < kWin; j += KR_THREADS) T[j] = g ? tables[(size_t)(g - 1) * kWin + j] : 0;
+  const StreamGroup R = rows[blockIdx.x];
+  const StreamItem& I = items[R.item];
+  const uint32_t g = R.g, G = I.G, n = I.chain;
+  const uint16_t* p = plane + I.plane;
+  uint8_t* dst = I.dst;
+  for (uint32_t j = threadIdx.x; j < kWin; j += KR_THREADS) T[j] = g ? tables[I.win + (size_t)(g - 1) * kWin + j] : 0;
   __syncthreads();
   const uint32_t i1 = (g + 1) * G < n ? (g + 1) * G : n;
   for (uint32_t i = g * G; i < i1; ++i) {
-    const StreamChunk c = recs[i];
-    for (uint64_t p = threadIdx.x; p < c.out; p += KR_THREADS) {
-      const uint16_t x = plane[c.base + p];
-      dst[c.base + p] = (uint8_t)(x < 256 ? x : T[x & 0x7FFFu]);
+    const StreamChunk c = recs[I.r0 + i];
+    for (uint64_t q = threadIdx.x; q < c.out; q += KR_THREADS) {
+      const uint16_t x = p[c.base + q];
+      dst[c.base + q] = (uint8_t)(x < 256 ? x : T[x & 0x7FFFu]);
     }
-    if (i + 1 < i1) window_step(T, plane, c);
+    if (i + 1 < i1) window_step(T, p, c);
   }
 }
 
 }  // namespace
 
-hipError_t launch_stream_find(const uint8_t* src, uint64_t src_n, uint64_t b0, uint64_t body_n, uint64_t step_bytes, uint32_t nc,
-                              uint64_t* cand, hipStream_t s) {
+hipError_t launch_stream_find(const StreamItem* items, uint32_t nitems, uint32_t nc, uint64_t step_bytes, uint64_t* cand,
+                              hipStream_t s) {
+  if (nc == 0) return hipSuccess;
   const uint32_t per = KF_THREADS / 64;
-  hipLaunchKernelGGL(k_stream_find, dim3((nc + per - 1) / per), dim3(KF_THREADS), 0, s, src, src_n, b0, body_n, 8 * step_bytes,
-                     nc, cand);
+  hipLaunchKernelGGL(k_stream_find, dim3((nc + per - 1) / per), dim3(KF_THREADS), 0, s, items, nitems, nc, 8 * step_bytes, cand);
   return hipGetLastError();
 }
 
-hipError_t launch_stream_decode(bool write, const uint8_t* src, uint64_t src_n, uint64_t b0, uint64_t body_n, StreamChunk* recs,
-                                const uint32_t* list, uint32_t n, uint32_t m, bool follow, uint16_t* plane, uint64_t cap,
-                                hipStream_t s) {
+hipError_t launch_stream_decode(bool write, const StreamItem* items, const uint32_t* rec_item, StreamChunk* recs,
+                                const uint32_t* list, uint32_t n, bool follow, uint16_t* plane, hipStream_t s) {
   if (n == 0) return hipSuccess;
   const dim3 grid((n + KS_LANES - 1) / KS_LANES), block(KS_LANES);
   if (write)
-    hipLaunchKernelGGL(k_stream_decode<true>, grid, block, KS_LDS, s, src, src_n, b0, body_n, recs, list, n, m, follow, plane, cap);
+    hipLaunchKernelGGL(k_stream_decode<true>, grid, block, KS_LDS, s, items, rec_item, recs, list, n, follow, plane);
   else
-    hipLaunchKernelGGL(k_stream_decode<false>, grid, block, KS_LDS, s, src, src_n, b0, body_n, recs, list, n, m, follow, plane, cap);
+    hipLaunchKernelGGL(k_stream_decode<false>, grid, block, KS_LDS, s, items, rec_item, recs, list, n, follow, plane);
   return hipGetLastError();
 }
 
@@ -177,17 +205,18 @@ uint32_t stream_group(uint32_t n) {
   return g;
 }
 
-hipError_t launch_stream_resolve(const uint16_t* plane, const StreamChunk* recs, uint32_t n, uint16_t* tables, uint8_t* dst,
-                                 hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  const uint32_t G = stream_group(n), ng = (n + G - 1) / G;
-  if (ng > 1) {
-    hipLaunchKernelGGL(k_stream_compose, dim3(ng - 1), dim3(KR_THREADS), 0, s, plane, recs, n, G, tables);
-    if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(k_stream_link, dim3(1), dim3(KR_THREADS), 0, s, tables, ng);
+hipError_t launch_stream_resolve(const uint16_t* plane, const StreamChunk* recs, const StreamItem* items,
+                                 const StreamGroup* compose, uint32_t ncompose, const uint32_t* link, uint32_t nlink,
+                                 const StreamGroup* resolve, uint32_t nresolve, uint16_t* tables, hipStream_t s) {
+  if (ncompose) {
+    hipLaunchKernelGGL(k_stream_compose, dim3(ncompose), dim3(KR_THREADS), 0, s, plane, recs, items, compose, tables);
     if (hipError_t e = hipGetLastError()) return e;
   }
-  hipLaunchKernelGGL(k_stream_resolve, dim3(ng), dim3(KR_THREADS), 0, s, plane, recs, n, G, tables, dst);
+  if (nlink) {
+    hipLaunchKernelGGL(k_stream_link, dim3(nlink), dim3(KR_THREADS), 0, s, items, link, tables);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  if (nresolve) hipLaunchKernelGGL(k_stream_resolve, dim3(nresolve), dim3(KR_THREADS), 0, s, plane, recs, items, resolve, tables);
   return hipGetLastError();
 }
 

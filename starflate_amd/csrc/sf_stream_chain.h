@@ -17,8 +17,8 @@ static_assert(sizeof(StreamChunk) == 48, "stream chunk record");
 
 // C on the host: one round over the chunk records rec[r0, r0 + m) of one stream (rec[i].start / .limit are the chunks as
 // decoded; an empty chunk is settled here).  Appends the chunks to decode again to redo (indices into rec); *chain: the
-// confirmed chunks so far (the last one ends the stream or failed) when none was appended.  A batched call keeps every
-// item's records in one array and runs this over each item's slice.
+// confirmed chunks so far (the last one ends the stream or failed) when none was appended.  A call keeps every item's records
+// in one array and runs this over each item's slice (one stream: r0 = 0).
 inline void stream_chain_round(StreamChunk* rec, uint32_t r0, uint32_t m, std::vector<uint32_t>& redo, uint32_t* chain) {
   uint32_t confirmed = 1;
   bool broken = false;
@@ -49,7 +49,8 @@ inline void stream_chain_round(StreamChunk* rec, uint32_t r0, uint32_t m, std::v
   *chain = confirmed;
 }
 
-// The same over all of rec (one stream).  Returns the chunks to decode again.
+// The same over all of rec (one stream).  Returns the chunks to decode again.  The library runs the slice form only; this one
+// is for host-side callers that hold one stream's records in a vector.
 inline std::vector<uint32_t> stream_chain_round(std::vector<StreamChunk>& rec, uint32_t* chain) {
   std::vector<uint32_t> redo;
   stream_chain_round(rec.data(), 0, (uint32_t)rec.size(), redo, chain);

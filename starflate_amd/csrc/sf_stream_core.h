@@ -1,6 +1,5 @@
-// sf_stream_core.h -- the device code the stream decoder's kernels share: the single stream's (sf_stream.hip) and the batched
-// ones (sf_stream_batch.hip).  Each includes it into its own translation unit, so that the single kernels' code does not depend
-// on how often the batched kernels call these functions (the inliner's choices are per unit).
+// sf_stream_core.h -- the device code under the stream decoder's kernels (sf_stream.hip): the reader over an item's body, the
+// lane-serial block decoder of the count and write passes (stream_decode) and the window step of compose and resolve.
 #pragma once
 #include "sf_device.h"
 

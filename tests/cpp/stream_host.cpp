@@ -47,9 +47,8 @@ uint32_t sfs_serial(const uint8_t* src, uint64_t n, uint32_t container, uint8_t*
 
 // sf::stream_chain_round over rec[0, m) (updated in place) -> the chunks to decode again in redo[0, return); *chain
 uint32_t sfs_chain_round(sf::StreamChunk* rec, uint32_t m, uint32_t* redo, uint32_t* chain) {
-  std::vector<sf::StreamChunk> v(rec, rec + m);
-  const std::vector<uint32_t> r = sf::stream_chain_round(v, chain);
-  for (uint32_t i = 0; i < m; ++i) rec[i] = v[i];
+  std::vector<uint32_t> r;
+  sf::stream_chain_round(rec, 0, m, r, chain);
   for (size_t i = 0; i < r.size(); ++i) redo[i] = r[i];
   return static_cast<uint32_t>(r.size());
 }

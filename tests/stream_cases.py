@@ -268,7 +268,7 @@ def edges(seed, nblocks=30):
 
 def predict(case, S):
     """The chunk partition of the stream decoder with nominal chunks of S stream bytes: chunk 0 at bit 0, then the first
-    candidate of the strict predicate in every nominal chunk (as stream_run picks them).  -> dict: picks (bits), false (the
+    candidate of the strict predicate in every nominal chunk (as the library's driver picks them).  -> dict: picks (bits), false (the
     picks that are no block start), bases (O_i of the picks that are block starts), outs (their chunks' output bytes)"""
     raw = case.raw
     starts = dict(case.blocks)

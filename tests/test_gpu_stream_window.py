@@ -1,5 +1,5 @@
-"""Far distances and the carried window in the stream decoders (decompress_stream, decompress_stream_batch; sf_stream.hip,
-sf_stream_batch.hip, sf_stream_core.h), on the streams of tests/stream_cases.py (their CPU side: tests/test_stream_window.py).
+"""Far distances and the carried window in the stream decoders (decompress_stream, decompress_stream_batch: one decoder, a
+single stream being a call of one item; sf_stream.hip, sf_stream_core.h), on the streams of tests/stream_cases.py (their CPU side: tests/test_stream_window.py).
 
 zlib never emits a distance above 32506, so its streams do not reach window entry 0, nor a marker that survives many chunks
 and groups.  These do: generations of 32 KiB copied through matches at 32768, 32767 and 32768 - 257 (47 chunks in 7 groups
