@@ -437,8 +437,11 @@ int sfh_last_recover_stats(sfh_ctx* ctx, float ms[2], uint64_t counts[2]);
  * dst)), the first problem in stream order; *dst_n_out the bytes the body produced (on Success: dst[0, *dst_n_out) is the
  * output).  One difference, on purpose: container.hpp takes a zlib dst to be exactly the output size and checks the Adler-32
  * over all of it, so a larger dst is Error there; here the output size need not be known, and the Adler-32 is checked over the
- * bytes produced (zlib's own rule) -- with dst_cap equal to the output size both agree.  A stream with no candidate block
- * start (a Z_FIXED or level-0 stream) is decoded by one lane: slow, but correct.
+ * bytes produced (zlib's own rule) -- with dst_cap equal to the output size both agree.  Candidate block starts are
+ * dynamic-Huffman headers and, inside a run of stored blocks, non-final stored-block headers with zero padding bits, so a
+ * stream of stored blocks (level 0, or data zlib could not compress) is cut at its blocks; the last block of a run is not a
+ * cut.  Fixed-Huffman blocks are no candidates: a Z_FIXED stream is decoded
+ * by one lane: slow, but correct.
  * Size query: d_dst == NULL and dst_cap == 0 runs the candidate, count and chain steps only: *dst_n_out = the output size, and
  * *status the wrapper's or the first structural problem of the body (the checks that need output positions -- distance <=
  * bytes written, the capacity, the checksum -- are the decode call's).

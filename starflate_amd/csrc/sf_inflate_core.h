@@ -459,6 +459,35 @@ SF_HD bool dynamic_header_candidate(BitReader& br, uint8_t* lut) {
   return kl == 32768u && has_eob && (kd == 32768u || (nd == 1 && kd == 16384u));
 }
 
+// Block-start candidate for stored blocks (DESIGN.md 3a "Stored block starts"), at body bit p = 8 * byte + k.  With B the
+// first byte boundary at or after the three header bits, where LEN lies: (1) bits p .. 8B - 1 are zero (BFINAL 0, BTYPE 0 and
+// the zero padding zlib writes); (2) p is the lowest such bit of byte B - 1, so a LEN byte has at most one candidate, the bit
+// length of the byte before it: exact after a stored block and after a code whose last bit is 1; (3) B + 4 <= body_n and
+// LEN ^ NLEN == 0xFFFF; (4) B + 4 + LEN <= body_n.  k of 6 or 7 would put LEN two bytes on: never a candidate.
+// `br`: opened on the body at `byte` and refilled, nothing dropped -- 40 bits or more are buffered, byte B - 1 and the four
+// of LEN and NLEN; what the reader repeats past the stream's last dword lies behind the test of (3).
+SF_HD bool stored_header_candidate(const BitReader& br, uint32_t k, uint64_t byte, uint64_t body_n) {
+  const uint32_t v = (uint32_t)br.buf & 0xFFu;
+  if (k > 5 || (v >> k) != 0 || ((((v << 1) | 1u) >> k) & 1u) == 0) return false;  // nearly every position ends here
+  if (byte + 5 > body_n) return false;
+  const uint32_t w = (uint32_t)(br.buf >> 8);
+  const uint32_t len = w & 0xFFFFu;
+  return (len ^ (w >> 16)) == 0xFFFFu && byte + 5 + len <= body_n;
+}
+
+// LEN of the stored header a reader opened as above holds (meaningful where stored_header_candidate holds)
+SF_HD uint32_t stored_header_len(const BitReader& br) { return (uint32_t)(br.buf >> 8) & 0xFFFFu; }
+
+// The look-ahead behind a stored candidate's payload (k_stream_find; DESIGN.md 3a "Stored block starts"): is the header at
+// byte `e` = B + 4 + LEN <= body_n, where the next block must start, a stored one again (final or not, any padding bits)
+// whose LEN and NLEN fit the body and agree?  Then the candidate lies inside a run of stored blocks, where no other kind of
+// candidate can be.
+SF_HD bool stored_run_follows(const uint8_t* body, uint64_t body_n, uint64_t e) {
+  if (e + 5 > body_n || (body[e] & 6u) != 0) return false;
+  const uint32_t len = body[e + 1] | (uint32_t)body[e + 2] << 8, nlen = body[e + 3] | (uint32_t)body[e + 4] << 8;
+  return (len ^ nlen) == 0xFFFFu;
+}
+
 template <class L>
 SF_HD uint32_t read_tables(BitReader& br, uint8_t* m, uint32_t type) {
   const uint32_t st = read_lengths<L>(br, m, type);

@@ -6,8 +6,12 @@
 // items lie in one array, item after item (a record's item: rec_item):
 //
 //   k_stream_find        A. one wave per nominal chunk start of the call (every S body bytes of an item, S = SFH_STREAM_CHUNK):
-//                           the first bit offset before the next nominal start where dynamic_header_candidate
-//                           (sf_inflate_core.h) holds.  An item's chunk 0 starts at its body's first bit whatever its block type.
+//                           the first bit offset before the next nominal start where dynamic_header_candidate or
+//                           stored_header_candidate (sf_inflate_core.h) holds, the latter only where the block behind its
+//                           payload is a stored one too (stored_run_follows): inside a run of stored blocks.  The last
+//                           block of a run is left to the lane that comes through; the Huffman block behind it has its
+//                           own candidate if it is a dynamic one.  An item's chunk 0 starts at its body's first bit
+//                           whatever its block type.
 //   k_stream_decode<0>   B. one lane per record: whole blocks from the chunk's start until the first block end at or beyond the
 //                           next chunk's start (an item's last chunk: until BFINAL or an error).  Records the end bit, the
 //                           output bytes, BFINAL and the first structural problem.  The checks that need the absolute output
@@ -26,8 +30,9 @@
 //                           and every group then writes its chunks' final bytes into the item's dst (resolve).
 //
 // The statuses are the serial decoder's (include/starflate/decompress.hpp): stream_decode follows its checks in its order,
-// including where the input runs out.  A stream with no candidates (Z_FIXED, level 0, ...) is decoded by one lane: slow, but
-// correct.  Bit positions and output counts are 64-bit; the 32-bit BitReader is re-opened before its position passes 2^30.
+// including where the input runs out.  Dynamic blocks and non-final stored blocks in front of another stored block are candidates
+// (a stored block with non-zero padding is not); fixed blocks are not, three header bits being no evidence, so a Z_FIXED
+// stream is decoded by one lane: slow, but correct.  A stored block's payload goes into the plane 16 bytes per step (copy_stored).  Bit positions and output counts are 64-bit; the 32-bit BitReader is re-opened before its position passes 2^30.
 // Scratch: 2 bytes per output byte (the plane), 64 KiB per group, 60 bytes per nominal chunk.
 #include "sf_stream_core.h"
 
@@ -61,8 +66,13 @@ __global__ __launch_bounds__(KF_THREADS) void k_stream_find(const StreamItem* __
     bool hit = false;
     if (p < hi_bit) {
       StreamReader rd;
-      rd.open(I.src, I.src_n, I.b0, I.body_n, p);
-      hit = dynamic_header_candidate(rd.br, s_lut[threadIdx.x]);
+      rd.open(I.src, I.src_n, I.b0, I.body_n, p & ~7ull);
+      hit = stored_header_candidate(rd.br, (uint32_t)(p & 7), p >> 3, I.body_n) &&
+            stored_run_follows(I.src + I.b0, I.body_n, (p >> 3) + 5 + stored_header_len(rd.br));
+      if (!hit) {
+        rd.br.drop((uint32_t)(p & 7));
+        hit = dynamic_header_candidate(rd.br, s_lut[threadIdx.x]);
+      }
     }
     const uint64_t b = __ballot(hit);
     if (b) {

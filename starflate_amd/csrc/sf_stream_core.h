@@ -77,6 +77,41 @@ __device__ uint32_t serial_dynamic(BitReader& br, uint8_t* m) {
   return kOk;
 }
 
+// A stored block's payload into the plane: `len` bytes at `from` (any address inside the stream) become `len` u16 entries at
+// `to` (2-byte aligned).  A head of single entries brings `to` to a 16-byte boundary; then 16 bytes per step: the source as
+// aligned dwords, one carried from step to step and funnelled to the source's byte offset, widened to 16 entries and written
+// by two 16-byte stores; a tail of single entries.  No dword past the one holding the payload's last byte is loaded (a step
+// whose source is dword-aligned repeats its last one instead), so nothing beyond the stream's last dword is read.  The stream's first byte is 4-byte aligned, as BitReader needs it (host
+// sources are staged that way, device ones are checked), so that an aligned dword never straddles the end of what d_src promises.
+typedef uint32_t Store16 __attribute__((ext_vector_type(4), may_alias));  // (the plane is read back as u16)
+__device__ __forceinline__ void copy_stored(uint16_t* __restrict__ to, const uint8_t* __restrict__ from, uint32_t len) {
+  uint32_t k = (uint32_t)((0 - reinterpret_cast<uintptr_t>(to)) & 15u) >> 1;
+  k = k < len ? k : len;
+  for (uint32_t j = 0; j < k; ++j) to[j] = from[j];
+  if (len - k >= 16) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(from + k);
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+    const uint32_t sh = 8 * (uint32_t)(a & 3);
+    const uint32_t lastw = (uint32_t)((reinterpret_cast<uintptr_t>(from + len - 1) >> 2) - (a >> 2));
+    uint32_t carry = w[0], i = 1;
+    for (; k + 16 <= len; k += 16) {
+      uint32_t d[4];
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j, ++i) {
+        const uint32_t nx = w[i < lastw ? i : lastw];
+        d[j] = (uint32_t)((((uint64_t)nx << 32) | carry) >> sh);
+        carry = nx;
+      }
+      Store16* o = reinterpret_cast<Store16*>(to + k);
+      o[0] = Store16{(d[0] & 0xFFu) | ((d[0] & 0xFF00u) << 8), ((d[0] >> 16) & 0xFFu) | ((d[0] >> 8) & 0xFF0000u),
+                        (d[1] & 0xFFu) | ((d[1] & 0xFF00u) << 8), ((d[1] >> 16) & 0xFFu) | ((d[1] >> 8) & 0xFF0000u)};
+      o[1] = Store16{(d[2] & 0xFFu) | ((d[2] & 0xFF00u) << 8), ((d[2] >> 16) & 0xFFu) | ((d[2] >> 8) & 0xFF0000u),
+                        (d[3] & 0xFFu) | ((d[3] & 0xFF00u) << 8), ((d[3] >> 16) & 0xFFu) | ((d[3] >> 8) & 0xFF0000u)};
+    }
+  }
+  for (; k < len; ++k) to[k] = from[k];
+}
+
 // Blocks of one chunk (see the header).  WRITE: the exact rules, and the symbol plane from plane[c.base].
 template <bool WRITE>
 __device__ void stream_decode(const uint8_t* src, uint64_t src_n, uint64_t b0, uint64_t body_n, StreamChunk& c, uint8_t* m,
@@ -107,8 +142,7 @@ __device__ void stream_decode(const uint8_t* src, uint64_t src_n, uint64_t b0, u
       if (WRITE) {
         if (cap - (base + pos) < len) { st = kDstTooSmall; break; }
         if (pos + len > c.out) { st = kError; break; }  // (the count pass saw fewer bytes: never)
-        const uint8_t* from = src + b0 + (rd.rb >> 3) + rel;
-        for (uint32_t k = 0; k < len; ++k) plane[base + pos + k] = from[k];
+        copy_stored(plane + base + pos, src + b0 + (rd.rb >> 3) + rel, len);
       }
       pos += len;
       br.bitpos += 8 * len;

@@ -3,9 +3,13 @@
 warm-up, the per-stage ms (HIP events, profiling on), chunks / candidates / confirmed / repair rounds / scratch; and for
 comparison the serial decoder on one core (the oracle's sfo_decompress, zlib's inflate and container.hpp's decompress(), sampled
 on a --sample byte prefix stream) and decompress_any on a Z_SYNC_FLUSH-every-32-KiB stream of the same data; and the repair
-worst case, stored blocks full of DEFLATE data (--stored-bytes of the text as zlib -6 streams, packed again by zlib -6).
+worst case, stored blocks full of DEFLATE data (--stored-bytes of the text as zlib -6 streams, packed again by zlib -6); and
+three legs of --stored-leg-bytes each whose streams are made of stored blocks: level0_noise (zlib -0 of noise, blocks of 65535
+bytes), level6_noise (zlib -6 of noise, which stores it in blocks of about 16 KiB) and mixed6 (zlib -6 of alternating 1 MiB
+pieces of text and noise), each with its stage ms.  All inputs are seeded.
 
-usage: python tools/stream_inflate_rate.py OUT.json [--bytes N] [--repeats N] [--sample N] [--stored-bytes N]"""
+usage: python tools/stream_inflate_rate.py OUT.json [--bytes N] [--repeats N] [--sample N] [--stored-bytes N]
+                                                    [--stored-leg-bytes N]"""
 import argparse
 import json
 import os
@@ -46,6 +50,27 @@ def zlib_flushed(data, every=32768):
     return b"".join(out) + c.flush()
 
 
+def stored_leg(comp, plain, level, repeats):
+    """zlib -`level` of `plain`, decoded: bytes, median ms and MiB/s, the chunk counts, and the stage ms of a profiled pass"""
+    m = len(plain)
+    st = torch.from_numpy(np.frombuffer(zlib.compress(plain, level), np.uint8).copy()).cuda()
+    out = torch.empty(m, dtype=torch.uint8, device="cuda")
+    ms = timed(lambda: comp.decompress_stream_tensor(st, m, "zlib", out=out), repeats)
+    _, status = comp.decompress_stream_tensor(st, m, "zlib", out=out)
+    assert status == 0 and out.cpu().numpy().tobytes() == plain
+    s = comp.last_stream_stats()
+    leg = {"bytes": m, "stream_bytes": st.numel(), "ms": ms, "mib_s": m / MiB / (ms / 1e3),
+           **{q: s[q] for q in ("chunks", "candidates", "confirmed", "repair_rounds", "longest_chunk")}}
+    comp.set_profiling(True)
+    stages = []
+    for _ in range(repeats):
+        comp.decompress_stream_tensor(st, m, "zlib", out=out)
+        stages.append(comp.last_stream_stats())
+    comp.set_profiling(False)
+    leg.update({q: statistics.median(x[q] for x in stages) for q in stages[0] if q.endswith("_ms")})
+    return leg
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out")
@@ -53,6 +78,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sample", type=int, default=32 << 20)
     ap.add_argument("--stored-bytes", type=int, default=256 << 20)
+    ap.add_argument("--stored-leg-bytes", type=int, default=256 << 20)
     a = ap.parse_args()
     build.build()
     comp = Compressor(0)
@@ -135,6 +161,15 @@ def main():
     s = comp.last_stream_stats()
     res["stored_deflate"] = {"bytes": len(inner), "ms": ms, "mib_s": len(inner) / MiB / (ms / 1e3),
                              **{q: s[q] for q in ("chunks", "candidates", "confirmed", "repair_rounds", "longest_chunk")}}
+    del pt, pout
+    # streams made of stored blocks (DESIGN 3a "Stored block starts")
+    m = a.stored_leg_bytes
+    noise = np.random.default_rng(17).integers(0, 256, m, dtype=np.uint8).tobytes()
+    piece = 1 << 20
+    text = synth.gen_text((m + 1) // 2 + piece, seed=2).tobytes()  # (this leg's own: whatever --bytes is)
+    mixed = b"".join(noise[j:j + piece] if (j // piece) & 1 else text[j // 2:j // 2 + piece] for j in range(0, m, piece))[:m]
+    for name, plain, level in (("level0_noise", noise, 0), ("level6_noise", noise, 6), ("mixed6", mixed, 6)):
+        res[name] = stored_leg(comp, plain, level, a.repeats)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
