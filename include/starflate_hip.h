@@ -303,7 +303,15 @@ int sfh_copy_subindex(sfh_ctx* ctx, uint32_t* dst, size_t words, int dst_on_devi
  * Scratch: the decoder keeps 4 bytes of tokens per output byte -- of ONE batch of whole strips, at most 1 GiB of output (round
  * 6; before: of the whole call): 4 GiB at most whatever dst_n is (sfh_last_decode_scratch_bytes), the two kernels alternating
  * batch after batch on the stream; bytes and status are those of one pass over everything
- * (/root/reference/src/decompress.cpp:197-242 semantics: the first failing block in stream order). */
+ * (/root/reference/src/decompress.cpp:197-242 semantics: the first failing block in stream order).
+ * The call is an sfh_decompress_batch_device_async call of one raw item followed by one synchronisation: one set of kernels
+ * and one geometry serve both.  What that means for a single stream, against the implicit-geometry kernels it ran before:
+ *   - the call builds and uploads a descriptor table, 48 bytes per segment plus 8 per strip (about 0.15 % of the output), in
+ *     pinned host memory and on the device -- so it can fail with SFH_E_NOMEM for that table;
+ *   - before it fills the pinned table it waits, on the host, for the previous call's table copy to have read it;
+ *   - it launches k_inflate_head (for a raw item: nothing but a cleared wrapper status) in front of the token kernels and
+ *     k_inflate_fold behind the byte kernels, where it launched k_inflate_status.
+ * Bytes, statuses, the first failing segment sfh_last_error names and the scratch are unchanged. */
 int sfh_decompress_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const uint64_t* d_index,
                           const uint32_t* d_subindex, size_t nseg, void* d_dst, size_t dst_n, uint32_t block_bytes,
                           uint32_t* status, void* stream);
@@ -332,7 +340,8 @@ int sfh_decompress(sfh_ctx* ctx, const void* src, size_t src_n, const uint64_t* 
  * (a destination of no bytes overlaps nothing),
  * no index while some dst_n[i] > 32768, a sub-index without an index, more than 2^31 - 1 segments.  count == 0: SFH_OK.
  * The items run in launch batches of whole items (at most SFH_BATCH_CHUNKS segments; a larger item in batches of its own, cut
- * at its strips, as sfh_decompress_device cuts a call), so the token scratch is that of one batch
+ * at its strips: max(sps, SFH_BATCH_CHUNKS / sps * sps) segments each, sps = block_bytes / 32768), so the token scratch is
+ * that of one batch
  * (sfh_last_decode_scratch_bytes, at most 4 GiB).  Afterwards the context has no index, as after sfh_decompress*;
  * sfh_last_inflate_ms sums both stages over the launch batches.
  *

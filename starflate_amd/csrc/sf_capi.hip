@@ -3,6 +3,7 @@
 #include "../../include/starflate_hip.h"
 #include "sf_device.h"
 #include "sf_inflate_core.h"
+#include "sf_inflate_plan.h"
 #include "sf_range_plan.h"
 #include "sf_stage_plan.h"
 
@@ -422,6 +423,44 @@ int stage_tables(sfh_ctx* ctx, size_t bytes) {
   if (ctx->d_tab_cap < bytes && ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (its kernels read d_tab)
   return grow(ctx, &ctx->d_tab, &ctx->d_tab_cap, bytes, "descriptor tables");
 }
+// ... and once h_tab is filled: the call takes its place behind the previous one and the tables go up
+int upload_tables(sfh_ctx* ctx, size_t bytes, hipStream_t s) {
+  if (int rc = order_behind_last_call(ctx, s)) return rc;
+  SF_HIP(hipMemcpyAsync(ctx->d_tab, ctx->h_tab, bytes, hipMemcpyHostToDevice, s), "descriptor tables");
+  SF_HIP(hipEventRecord(ctx->ev_tab, s), "event");
+  ctx->tab_pending = true;
+  return SFH_OK;
+}
+
+// Destinations must not overlap: sorted by address, each ends before the next begins.  (A destination of no bytes is written
+// nothing and overlaps nothing: it is left out.)
+int check_disjoint(sfh_ctx* ctx, void* const* dsts, const uint64_t* lens, size_t count) {
+  std::vector<size_t> ord;
+  try {
+    ord.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  size_t m = 0;
+  for (size_t i = 0; i < count; ++i)
+    if (lens[i]) ord[m++] = i;
+  std::sort(ord.begin(), ord.begin() + (std::ptrdiff_t)m, [&](size_t a, size_t b) { return (uintptr_t)dsts[a] < (uintptr_t)dsts[b]; });
+  for (size_t k = 1; k < m; ++k)
+    if ((uintptr_t)dsts[ord[k - 1]] + lens[ord[k - 1]] > (uintptr_t)dsts[ord[k]])
+      return fail(ctx, SFH_E_INVALID_ARG, "destination ranges overlap", hipSuccess);
+  return SFH_OK;
+}
+
+// the per-stage events of a profiled decode call: SFH_INFLATE_NSTAGES + 1 per launch batch
+int ensure_inflate_events(sfh_ctx* ctx, uint32_t nbatches) {
+  const size_t need = (size_t)nbatches * (SFH_INFLATE_NSTAGES + 1);
+  while (ctx->ev_inf.size() < need) {
+    hipEvent_t e = nullptr;
+    SF_HIP(hipEventCreate(&e), "event");
+    ctx->ev_inf.push_back(e);
+  }
+  return SFH_OK;
+}
 
 // ---- batched compression (sfh_compress_batch*) ----
 // Everything a batch call checks before it enqueues anything (`dev`: device buffers, the single call's alignment rules).
@@ -441,19 +480,7 @@ int check_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint6
     chunks += chunks_of((size_t)src_n[i]);
   }
   if (chunks > ((uint64_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 chunks in one call", hipSuccess);
-  // destinations must not overlap: sorted by address, each ends before the next begins
-  std::vector<size_t> ord;
-  try {
-    ord.resize(count);
-  } catch (...) {
-    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
-  }
-  for (size_t i = 0; i < count; ++i) ord[i] = i;
-  std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return (uintptr_t)dsts[a] < (uintptr_t)dsts[b]; });
-  for (size_t k = 1; k < count; ++k)
-    if ((uintptr_t)dsts[ord[k - 1]] + dst_cap[ord[k - 1]] > (uintptr_t)dsts[ord[k]])
-      return fail(ctx, SFH_E_INVALID_ARG, "destination ranges overlap", hipSuccess);
-  return SFH_OK;
+  return check_disjoint(ctx, dsts, dst_cap, count);  // (no capacity is 0: sfh_compress_bound > 0)
 }
 
 // One launch batch: its rows in the call's tables (chunk rows are the call's, in item order; strip and item rows per batch).
@@ -557,10 +584,7 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
   ctx->index_valid = false;  // a batch has no single index: the index functions refuse until the next single call
   ctx->last_chunks = lbs.back().nchunks;
   const bool prof = ctx->profiling != 0;
-  if ((rc = order_behind_last_call(ctx, s)) != SFH_OK) return rc;
-  SF_HIP(hipMemcpyAsync(ctx->d_tab, ctx->h_tab, bytes, hipMemcpyHostToDevice, s), "descriptor tables");
-  SF_HIP(hipEventRecord(ctx->ev_tab, s), "event");
-  ctx->tab_pending = true;
+  if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
   const uint32_t nbatches = (uint32_t)lbs.size();
   ctx->ev_valid = false;
   if (prof) {
@@ -631,150 +655,101 @@ int check_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, con
     segs += chunks_of((size_t)dst_n[i]);
   }
   if (segs > ((uint64_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 segments in one call", hipSuccess);
-  std::vector<size_t> ord;
-  try {
-    ord.resize(count);
-  } catch (...) {
-    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
-  }
-  // (a destination of no bytes is written nothing and overlaps nothing: it is left out)
-  size_t m = 0;
-  for (size_t i = 0; i < count; ++i)
-    if (dst_n[i]) ord[m++] = i;
-  std::sort(ord.begin(), ord.begin() + (std::ptrdiff_t)m, [&](size_t a, size_t b) { return (uintptr_t)dsts[a] < (uintptr_t)dsts[b]; });
-  for (size_t k = 1; k < m; ++k)
-    if ((uintptr_t)dsts[ord[k - 1]] + dst_n[ord[k - 1]] > (uintptr_t)dsts[ord[k]])
-      return fail(ctx, SFH_E_INVALID_ARG, "destination ranges overlap", hipSuccess);
-  return SFH_OK;
+  return check_disjoint(ctx, dsts, dst_n, count);
 }
 
-struct InflateBatch {
-  uint32_t r0 = 0, nseg = 0, s0 = 0, nstrips = 0;  // its rows in the call's segment and strip tables
-};
-
-// Device buffers, arguments checked.  The host builds the tables -- per segment, per strip (both cut into launch batches of
-// whole items, an item larger than a batch into batches of its own at its strips, as sfh_decompress_device cuts a call),
-// per item, and with a container per checksum chunk -- uploads them in one copy, and then: k_inflate_head (wrappers,
-// implied index entries), the token and byte kernels batch after batch, k_checksum_batch over the decoded bytes and
-// k_inflate_fold (every item's status).
+// Device buffers, arguments checked.  The launch batches are planned (sf_inflate_plan.h: whole items, an item larger than a
+// batch in batches of its own at its strips), which also says how large the tables are; the host then writes them straight into
+// the pinned block -- per segment, per strip, per item, and with a container per checksum chunk -- uploads them in one copy,
+// and then: k_inflate_head (wrappers, implied index entries), the token and byte kernels batch after batch,
+// k_checksum_batch over the decoded bytes and k_inflate_fold (every item's status; d_first, nullable: its first failing segment).
 int enqueue_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, const uint64_t* d_index,
                           const uint32_t* d_subindex, void* const* d_dsts, const uint64_t* dst_n, const uint32_t* block_bytes,
-                          uint32_t container, uint32_t* d_status, hipStream_t s) {
+                          uint32_t container, uint32_t* d_status, uint32_t* d_first, hipStream_t s) {
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
   (void)hipGetLastError();  // see enqueue()
   const uint64_t trailer = container == SFH_ZLIB ? 4 : container == SFH_GZIP ? 8 : 0;
-  std::vector<sf::InflateSeg> segs;
-  std::vector<sf::InflateStrip> strips;
-  std::vector<sf::InflateItem> items;
-  std::vector<sf::BatchChunk> sums;
-  std::vector<InflateBatch> lbs;
-  const uint32_t cap = ctx->batch_chunks;
   int rc = SFH_OK;
   if (!d_index && (rc = grow(ctx, &ctx->d_implied, &ctx->d_implied_cap, 2 * count * sizeof(uint64_t), "implied index")))
     return rc;
+  sf::iplan::Plan P;
   try {
-    items.resize(count);
-    InflateBatch cur;
-    auto close = [&] {
-      if (cur.nseg) lbs.push_back(cur);
-      cur = InflateBatch{};
-      cur.r0 = (uint32_t)segs.size();
-      cur.s0 = (uint32_t)strips.size();
-    };
-    close();
-    uint64_t entry = 0;  // the item's first index entry (items before: their segments + 1 each)
-    for (size_t i = 0; i < count; ++i) {
-      const uint32_t nseg = chunks_of((size_t)dst_n[i]);
-      const uint32_t sps = (block_bytes && block_bytes[i]) ? block_bytes[i] / sf::kChunk : 1u;
-      const uint8_t* src = (const uint8_t*)d_srcs[i];
-      uint8_t* dst = (uint8_t*)d_dsts[i];
-      const uint64_t* ix = d_index ? d_index + entry : ctx->d_implied + 2 * i;
-      const uint64_t body_n = container ? (src_n[i] > trailer ? src_n[i] - trailer : 0) : src_n[i];
-      items[i] = sf::InflateItem{src, src_n[i], dst_n[i], d_index ? nullptr : ctx->d_implied + 2 * i, d_index ? ix : nullptr,
-                                 (uint32_t)segs.size(), nseg, 0, 0, 0, 0};
-      // whole, in the current launch batch or the next; an item larger than a batch: batches of its own, of whole strips
-      const uint32_t piece = nseg <= cap ? nseg : std::max(sps, cap / sps * sps);
-      if (nseg > cap || cur.nseg + nseg > cap) close();
-      for (uint32_t k0 = 0; k0 < nseg; k0 += piece) {
-        if (k0) close();
-        const uint32_t k1 = std::min(nseg, k0 + piece);
-        for (uint32_t k = k0; k < k1; k += sps) {
-          strips.push_back(sf::InflateStrip{cur.nseg + (k - k0), std::min(sps, k1 - k)});
-          ++cur.nstrips;
-        }
-        for (uint32_t k = k0; k < k1; ++k) {
-          const uint64_t ob = (uint64_t)k * sf::kChunk;
-          const uint32_t on = (uint32_t)std::min<uint64_t>(sf::kChunk, dst_n[i] - ob);
-          // (the segments are the call's in item order: the flattened sub-index holds segment g at g * SFH_SUBINDEX_WORDS)
-          segs.push_back(sf::InflateSeg{src, ix + k, d_subindex ? d_subindex + segs.size() * SFH_SUBINDEX_WORDS : nullptr,
-                                        dst + ob, body_n, on, (k % sps) * sf::kChunk | (container ? sf::kSegWrapped : 0u)});
-          if (container) sums.push_back(sf::BatchChunk{dst + ob, on, 0u});
-        }
-        cur.nseg += k1 - k0;
-      }
-      if (nseg > cap) close();
-      entry += nseg + 1;
-    }
-    close();
+    sf::iplan::plan_batches(count, dst_n, block_bytes, ctx->batch_chunks, P);
   } catch (...) {
-    return fail(ctx, SFH_E_NOMEM, "host memory for the descriptor tables", hipSuccess);
+    return fail(ctx, SFH_E_NOMEM, "host memory for the launch batches", hipSuccess);
   }
-  const uint32_t nseg = (uint32_t)segs.size();
-  uint32_t widest = 0;
-  for (const InflateBatch& b : lbs) widest = std::max(widest, b.nseg);
+  const uint32_t nseg = P.nseg;
   rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, (size_t)nseg * sizeof(sf::SegInfo), "segment records");
-  if (!rc) rc = ensure_dtok(ctx, widest);
+  if (!rc) rc = ensure_dtok(ctx, P.widest);
   if (!rc && container) rc = ensure_sums(ctx, nseg);
   if (rc) return rc;
   // the tables, in one pinned block: segments | items | strips | checksum chunks (rows of 48, 64, 8 and 16 bytes)
-  const size_t b_segs = segs.size() * sizeof(sf::InflateSeg), b_items = items.size() * sizeof(sf::InflateItem);
-  const size_t b_strips = strips.size() * sizeof(sf::InflateStrip), b_sums = sums.size() * sizeof(sf::BatchChunk);
+  const size_t b_segs = (size_t)nseg * sizeof(sf::InflateSeg), b_items = count * sizeof(sf::InflateItem);
+  const size_t b_strips = (size_t)P.nstrips * sizeof(sf::InflateStrip), b_sums = container ? (size_t)nseg * sizeof(sf::BatchChunk) : 0;
   const size_t o_sums = (b_segs + b_items + b_strips + 15) / 16 * 16, bytes = o_sums + b_sums;
   if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
-  memcpy(ctx->h_tab, segs.data(), b_segs);
-  memcpy(ctx->h_tab + b_segs, items.data(), b_items);
-  memcpy(ctx->h_tab + b_segs + b_items, strips.data(), b_strips);
-  memcpy(ctx->h_tab + o_sums, sums.data(), b_sums);
+  sf::InflateSeg* h_segs = (sf::InflateSeg*)ctx->h_tab;
+  sf::InflateItem* h_items = (sf::InflateItem*)(ctx->h_tab + b_segs);
+  sf::InflateStrip* h_strips = (sf::InflateStrip*)(ctx->h_tab + b_segs + b_items);
+  sf::BatchChunk* h_sums = (sf::BatchChunk*)(ctx->h_tab + o_sums);
+  uint32_t seg0 = 0;  // the item's first segment in the call; its first index entry: the items before have one more each
+  for (size_t i = 0; i < count; ++i) {
+    const uint32_t n = sf::iplan::segments_of(dst_n[i]);
+    h_items[i] = sf::InflateItem{(const uint8_t*)d_srcs[i], src_n[i], dst_n[i], d_index ? nullptr : ctx->d_implied + 2 * i,
+                                 d_index ? d_index + seg0 + i : nullptr, seg0, n, 0, 0, 0, 0};
+    seg0 += n;
+  }
+  uint32_t g = 0, t = 0;  // the next segment and strip row (the batches follow each other in both tables)
+  for (const sf::iplan::Batch& b : P.batches)
+    sf::iplan::for_rows(
+        b, dst_n, block_bytes, [&](uint32_t first, uint32_t n) { h_strips[t++] = sf::InflateStrip{first, n}; },
+        [&](size_t i, uint32_t k) {
+          // (segment g of the call is entry g + i of the flattened index: every item before this one has an entry more than segments)
+          const uint64_t* ix = d_index ? d_index + (g + i) : ctx->d_implied + 2 * i;
+          uint8_t* out = (uint8_t*)d_dsts[i] + (uint64_t)k * sf::kChunk;
+          const uint32_t on = sf::iplan::seg_out_n(dst_n[i], k);
+          const uint64_t body_n = container ? (src_n[i] > trailer ? src_n[i] - trailer : 0) : src_n[i];
+          // (the segments are the call's in item order: the flattened sub-index holds segment g at g * SFH_SUBINDEX_WORDS)
+          h_segs[g] = sf::InflateSeg{(const uint8_t*)d_srcs[i], ix, d_subindex ? d_subindex + (size_t)g * SFH_SUBINDEX_WORDS : nullptr,
+                                     out, body_n, on,
+                                     sf::iplan::seg_hist(k, sf::iplan::sps_of(block_bytes, i)) | (container ? sf::kSegWrapped : 0u)};
+          if (container) h_sums[g] = sf::BatchChunk{out, on, 0u};
+          ++g;
+        });
   sf::InflateSeg* t_segs = (sf::InflateSeg*)ctx->d_tab;
   sf::InflateItem* t_items = (sf::InflateItem*)(ctx->d_tab + b_segs);
   const sf::InflateStrip* t_strips = (const sf::InflateStrip*)(ctx->d_tab + b_segs + b_items);
   sf::BatchChunk* t_sums = (sf::BatchChunk*)(ctx->d_tab + o_sums);
 
-  ctx->index_valid = false;
+  ctx->index_valid = false;  // the last call is now this one: what sfh_debug_read returns belongs to it
   ctx->bix_valid = false;
   ctx->last_chunks = nseg;
-  ctx->last_dtok_bytes = (size_t)widest * sf::kChunk * sizeof(uint32_t);
+  ctx->last_dtok_bytes = (size_t)P.widest * sf::kChunk * sizeof(uint32_t);
   const bool prof = ctx->profiling != 0;
-  if ((rc = order_behind_last_call(ctx, s)) != SFH_OK) return rc;
-  SF_HIP(hipMemcpyAsync(ctx->d_tab, ctx->h_tab, bytes, hipMemcpyHostToDevice, s), "descriptor tables");
-  SF_HIP(hipEventRecord(ctx->ev_tab, s), "event");
-  ctx->tab_pending = true;
-  const uint32_t nbatches = (uint32_t)lbs.size();
+  if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
+  const uint32_t nbatches = (uint32_t)P.batches.size();
   ctx->ev_inf_valid = false;
-  if (prof) {
-    const size_t need = (size_t)nbatches * (SFH_INFLATE_NSTAGES + 1);
-    while (ctx->ev_inf.size() < need) {
-      hipEvent_t e = nullptr;
-      SF_HIP(hipEventCreate(&e), "event");
-      ctx->ev_inf.push_back(e);
-    }
-  }
+  if (prof && (rc = ensure_inflate_events(ctx, nbatches)) != SFH_OK) return rc;
   SF_HIP(sf::launch_inflate_head(t_items, (uint32_t)count, container, t_segs, container ? t_sums : nullptr, s), "launch k_inflate_head");
+  // The token scratch (4 bytes per output byte) holds ONE batch -- 4 GiB for any size of call -- and the two stages alternate
+  // on the stream, batch after batch.  Strips decode independently, the segment records and the statuses cover the whole call,
+  // so the result -- bytes, first failing segment, its status -- is that of one pass over everything.
   for (uint32_t bi = 0; bi < nbatches; ++bi) {
-    const InflateBatch& b = lbs[bi];
-    sf::SegInfo* binfo = ctx->ws.seginfo + b.r0;
+    const sf::iplan::Batch& b = P.batches[bi];
+    sf::SegInfo* binfo = ctx->ws.seginfo + b.row0;
     hipEvent_t* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
     if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
-    SF_HIP(sf::launch_inflate_tokens_batch(t_segs + b.r0, b.nseg, ctx->ws.tokens, binfo, d_subindex != nullptr,
-                                           !ctx->inflate_serial, s), "launch k_inflate_tokens");
+    SF_HIP(sf::launch_inflate_tokens(t_segs + b.row0, b.nseg, ctx->ws.tokens, binfo, d_subindex != nullptr, !ctx->inflate_serial, s),
+           "launch k_inflate_tokens");
     if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
-    SF_HIP(sf::launch_inflate_bytes_batch(t_segs + b.r0, t_strips + b.s0, b.nstrips, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes");
+    SF_HIP(sf::launch_inflate_bytes(t_segs + b.row0, t_strips + b.strip0, b.nstrips, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes");
     if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
   }
   ctx->ev_inf_batches = nbatches;
   ctx->ev_inf_valid = prof;
   if (container) SF_HIP(sf::launch_checksum_batch(t_sums, nseg, container, ctx->ws.sums, s), "launch k_checksum");
-  SF_HIP(sf::launch_inflate_fold(t_items, (uint32_t)count, ctx->ws.seginfo, ctx->ws.sums, container, d_status, s), "launch k_inflate_fold");
+  SF_HIP(sf::launch_inflate_fold(t_items, (uint32_t)count, ctx->ws.seginfo, ctx->ws.sums, container, d_status, d_first, s),
+         "launch k_inflate_fold");
   return mark_call_end(ctx, s);
 }
 
@@ -799,21 +774,7 @@ int check_ranges(sfh_ctx* ctx, const void* src, const uint64_t* index, const uin
     if (offsets[r] > total_n || lengths[r] > total_n - offsets[r])
       return fail(ctx, SFH_E_INVALID_ARG, "a range ends behind total_n", hipSuccess);
   }
-  std::vector<size_t> ord;
-  try {
-    ord.resize(count);
-  } catch (...) {
-    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
-  }
-  // (a destination of no bytes is written nothing and overlaps nothing: it is left out)
-  size_t m = 0;
-  for (size_t r = 0; r < count; ++r)
-    if (lengths[r]) ord[m++] = r;
-  std::sort(ord.begin(), ord.begin() + (std::ptrdiff_t)m, [&](size_t a, size_t b) { return (uintptr_t)dsts[a] < (uintptr_t)dsts[b]; });
-  for (size_t k = 1; k < m; ++k)
-    if ((uintptr_t)dsts[ord[k - 1]] + lengths[ord[k - 1]] > (uintptr_t)dsts[ord[k]])
-      return fail(ctx, SFH_E_INVALID_ARG, "destination ranges overlap", hipSuccess);
-  return SFH_OK;
+  return check_disjoint(ctx, dsts, lengths, count);
 }
 
 int plan_ranges_checked(sfh_ctx* ctx, uint64_t total_n, uint32_t block_bytes, size_t count, const uint64_t* offsets,
@@ -876,26 +837,16 @@ int enqueue_ranges(sfh_ctx* ctx, const sf::range::Plan& P, const RangeSource* fr
   ctx->last_chunks = (uint32_t)nrows;
   ctx->last_dtok_bytes = (size_t)P.widest * sf::kChunk * sizeof(uint32_t);
   const bool prof = ctx->profiling != 0;
-  if ((rc = order_behind_last_call(ctx, s)) != SFH_OK) return rc;
-  SF_HIP(hipMemcpyAsync(ctx->d_tab, ctx->h_tab, bytes, hipMemcpyHostToDevice, s), "descriptor tables");
-  SF_HIP(hipEventRecord(ctx->ev_tab, s), "event");
-  ctx->tab_pending = true;
+  if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
   const uint32_t nbatches = (uint32_t)P.batches.size();
   ctx->ev_inf_valid = false;
-  if (prof) {
-    const size_t need = (size_t)nbatches * (SFH_INFLATE_NSTAGES + 1);
-    while (ctx->ev_inf.size() < need) {
-      hipEvent_t e = nullptr;
-      SF_HIP(hipEventCreate(&e), "event");
-      ctx->ev_inf.push_back(e);
-    }
-  }
+  if (prof && (rc = ensure_inflate_events(ctx, nbatches)) != SFH_OK) return rc;
   for (uint32_t bi = 0; bi < nbatches; ++bi) {
     const sf::range::Batch& b = P.batches[bi];
     sf::SegInfo* binfo = ctx->ws.seginfo + b.row0;
     hipEvent_t* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
     if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
-    SF_HIP(sf::launch_inflate_tokens_batch(t_segs + b.row0, b.nrows, ctx->ws.tokens, binfo, sub, !ctx->inflate_serial, s),
+    SF_HIP(sf::launch_inflate_tokens(t_segs + b.row0, b.nrows, ctx->ws.tokens, binfo, sub, !ctx->inflate_serial, s),
            "launch k_inflate_tokens");
     if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
     SF_HIP(sf::launch_inflate_bytes_clip(t_segs + b.row0, t_clips + b.row0, t_strips + b.strip0, b.nstrips, ctx->ws.tokens, binfo, s),
@@ -1084,16 +1035,9 @@ int enqueue_any_decode(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t 
   ctx->last_chunks = nseg;
   ctx->last_dtok_bytes = (size_t)nseg * sf::kChunk * sizeof(uint32_t);
   const bool prof = ctx->profiling != 0;
-  if ((rc = order_behind_last_call(ctx, s)) != SFH_OK) return rc;
-  SF_HIP(hipMemcpyAsync(ctx->d_tab, ctx->h_tab, tab, hipMemcpyHostToDevice, s), "descriptor tables");
-  SF_HIP(hipEventRecord(ctx->ev_tab, s), "event");
-  ctx->tab_pending = true;
+  if ((rc = upload_tables(ctx, tab, s)) != SFH_OK) return rc;
   ctx->ev_inf_valid = false;
-  while (prof && ctx->ev_inf.size() < SFH_INFLATE_NSTAGES + 1) {
-    hipEvent_t e = nullptr;
-    SF_HIP(hipEventCreate(&e), "event");
-    ctx->ev_inf.push_back(e);
-  }
+  if (prof && (rc = ensure_inflate_events(ctx, 1)) != SFH_OK) return rc;
   hipEvent_t* ev = prof ? ctx->ev_inf.data() : nullptr;
   SF_HIP(sf::launch_inflate_head(t_item, 1, container, t_segs, sums.empty() ? nullptr : t_sums, s), "launch k_inflate_head");
   if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
@@ -1104,10 +1048,10 @@ int enqueue_any_decode(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t 
   if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
   if (depends_out) *depends_out = sb;
   if (bytes) {
-    SF_HIP(sf::launch_inflate_bytes_batch(t_segs, rows, nseg, ctx->ws.tokens, ctx->ws.seginfo, s), "launch k_inflate_bytes");
+    SF_HIP(sf::launch_inflate_bytes(t_segs, rows, nseg, ctx->ws.tokens, ctx->ws.seginfo, s), "launch k_inflate_bytes");
     if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
     if (container) SF_HIP(sf::launch_checksum_batch(t_sums, nseg, container, ctx->ws.sums, s), "launch k_checksum");
-    SF_HIP(sf::launch_inflate_fold(t_item, 1, ctx->ws.seginfo, ctx->ws.sums, container, d_status, s), "launch k_inflate_fold");
+    SF_HIP(sf::launch_inflate_fold(t_item, 1, ctx->ws.seginfo, ctx->ws.sums, container, d_status, nullptr, s), "launch k_inflate_fold");
   } else if (ev) {
     SF_HIP(hipEventRecord(ev[2], s), "event");
   }
@@ -1467,7 +1411,7 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
       SF_HIP(sf::launch_checksum_batch((const sf::BatchChunk*)(R + o_sums), (uint32_t)sums.size(), container, ctx->ws.sums, s),
              "launch k_checksum_batch");
       SF_HIP(sf::launch_inflate_fold((const sf::InflateItem*)(R + o_fold), (uint32_t)fold.size(), nullptr, ctx->ws.sums, container,
-                                     (uint32_t*)(R + o_fst), s), "launch k_inflate_fold");
+                                     (uint32_t*)(R + o_fst), nullptr, s), "launch k_inflate_fold");
       bst.resize(fold.size());
       SF_HIP(hipMemcpyAsync(bst.data(), R + o_fst, 4 * fold.size(), hipMemcpyDeviceToHost, s), "D2H checksums");
     }
@@ -1872,7 +1816,7 @@ int sfh_decompress_batch_device_async(sfh_ctx* ctx, size_t count, const void* co
   int rc = check_inflate_batch(ctx, count, d_srcs, src_n, d_index, d_subindex, d_dsts, dst_n, block_bytes, container, d_status, true);
   if (rc || count == 0) return rc;
   return enqueue_inflate_batch(ctx, count, d_srcs, src_n, d_index, d_subindex, d_dsts, dst_n, block_bytes, container, d_status,
-                               stream ? (hipStream_t)stream : ctx->stream);
+                               nullptr, stream ? (hipStream_t)stream : ctx->stream);
 }
 
 int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, const uint64_t* index,
@@ -1923,7 +1867,7 @@ int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, co
     d_dsts[i] = ctx->d_out + out_off[i];
   }
   if ((rc = enqueue_inflate_batch(ctx, count, d_srcs.data(), src_n, index ? ctx->d_index : nullptr, subindex ? ctx->d_sub : nullptr,
-                                  d_dsts.data(), dst_n, block_bytes, container, ctx->d_bstatus, s)) != SFH_OK) {
+                                  d_dsts.data(), dst_n, block_bytes, container, ctx->d_bstatus, nullptr, s)) != SFH_OK) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
@@ -2135,57 +2079,14 @@ int sfh_decompress_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const u
     return fail(ctx, SFH_E_INVALID_ARG, "nseg != ceil(dst_n / 32768)", hipSuccess);
   if (block_bytes % sf::kChunk || block_bytes > sf::kMaxStrip)
     return fail(ctx, SFH_E_INVALID_ARG, "block_bytes: a multiple of 32768 up to 16 MiB (0 = 32768)", hipSuccess);
-  const uint32_t sps = block_bytes ? block_bytes / sf::kChunk : 1u;  // segments per strip
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  (void)hipGetLastError();  // see enqueue()
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-  // Batches of whole strips, like the compressor: the token scratch (4 bytes per output byte) holds ONE batch of at most
-  // kBatchChunks segments -- 4 GiB for any size of call -- and the two kernels alternate on the stream, batch after batch.
-  // Strips decode independently (a match never reaches before its strip, /root/reference/src/decompress.cpp:178 within one), the
-  // segment records and the statuses cover the whole call, so the result -- bytes, first failing segment, its status -- is
-  // that of one pass over everything.
-  const uint32_t batch = std::max(sps, ctx->batch_chunks / sps * sps);  // (a strip larger than a batch is its own batch)
-  const uint32_t nbatches = (uint32_t)((nseg + batch - 1) / batch);
-  int rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, nseg * sizeof(sf::SegInfo), "segment records");
-  if (!rc) rc = ensure_dtok(ctx, (uint32_t)std::min<size_t>(nseg, batch));
-  if (rc) return rc;
-  ctx->last_dtok_bytes = std::min<size_t>(nseg, batch) * sf::kChunk * sizeof(uint32_t);
-  ctx->index_valid = false;  // the last call is now this one: what sfh_debug_read returns belongs to it
-  ctx->bix_valid = false;
-  ctx->last_chunks = (uint32_t)nseg;
-  const bool prof = ctx->profiling != 0;
-  if ((rc = order_behind_last_call(ctx, s)) != SFH_OK) return rc;
-  ctx->ev_inf_valid = false;
-  if (prof) {
-    const size_t need = (size_t)nbatches * (SFH_INFLATE_NSTAGES + 1);
-    while (ctx->ev_inf.size() < need) {
-      hipEvent_t e = nullptr;
-      SF_HIP(hipEventCreate(&e), "event");
-      ctx->ev_inf.push_back(e);
-    }
-  }
-  uint32_t bi = 0;
-  for (size_t g0 = 0; g0 < nseg; g0 += batch, ++bi) {
-    const uint32_t nb = (uint32_t)std::min<size_t>(batch, nseg - g0);
-    const uint64_t bdst_n = std::min<uint64_t>((uint64_t)nb * sf::kChunk, dst_n - (uint64_t)g0 * sf::kChunk);  // this batch's output bytes
-    const uint64_t* bindex = d_index + g0;           // (stream offsets are absolute: src stays what it is)
-    sf::SegInfo* binfo = ctx->ws.seginfo + g0;
-    uint8_t* bdst = (uint8_t*)d_dst + g0 * sf::kChunk;
-    hipEvent_t* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
-    if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
-    if (d_subindex)
-      SF_HIP(sf::launch_inflate_tokens_sub((const uint8_t*)d_src, src_n, bindex, d_subindex + g0 * SFH_SUBINDEX_WORDS, nb, bdst_n,
-                                           ctx->ws.tokens, binfo, sps, s), "launch k_inflate_tokens_sub");
-    else
-      SF_HIP(sf::launch_inflate_tokens((const uint8_t*)d_src, src_n, bindex, nb, bdst_n, ctx->ws.tokens,
-                                       binfo, sps, !ctx->inflate_serial, s), "launch k_inflate_tokens");
-    if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
-    SF_HIP(sf::launch_inflate_bytes((const uint8_t*)d_src, src_n, nb, ctx->ws.tokens, binfo, bdst, sps, s), "launch k_inflate_bytes");
-    if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
-  }
-  ctx->ev_inf_batches = nbatches;
-  ctx->ev_inf_valid = prof;
-  SF_HIP(sf::launch_inflate_status(ctx->ws.seginfo, (uint32_t)nseg, ctx->d_value, s), "launch k_inflate_status");
+  // a batch of one raw item: its status and first failing segment land in d_value[0..1]
+  const void* const srcs[1] = {d_src};
+  void* const dsts[1] = {d_dst};
+  const uint64_t src_ns[1] = {src_n}, dst_ns[1] = {dst_n};
+  if (int rc = enqueue_inflate_batch(ctx, 1, srcs, src_ns, d_index, d_subindex, dsts, dst_ns, &block_bytes, 0, ctx->d_value,
+                                     ctx->d_value + 1, s))
+    return rc;
   uint32_t res[2] = {0, 0};
   SF_HIP(hipMemcpyAsync(res, ctx->d_value, sizeof res, hipMemcpyDeviceToHost, s), "copy status");
   SF_HIP(hipStreamSynchronize(s), "stream sync");

@@ -347,12 +347,15 @@ __global__ __launch_bounds__(256) void k_inflate_head(InflateItem* __restrict__ 
   I.isize = isize;
 }
 
-// One workgroup per item, behind every launch batch: the first failing segment in the item's stream order (what
-// k_inflate_status is to the single call) after the wrapper's status; with a container and a clean body the checksum of the
-// decoded bytes, folded from k_checksum_batch's partials by wrap_stream -- the compressor's fold -- against the trailer's.
+// One workgroup per item, behind every launch batch: the first failing segment in the item's stream order (what the serial
+// decoder would report) after the wrapper's status; with a container and a clean body the checksum of the decoded bytes,
+// folded from k_checksum_batch's partials by wrap_stream -- the compressor's fold -- against the trailer's.
+// first (nullable): per item the number of that segment in the item, 0xFFFFFFFF when none failed (sfh_decompress_device's
+// message names it).
 __global__ __launch_bounds__(KW_THREADS) void k_inflate_fold(const InflateItem* __restrict__ items, const SegInfo* __restrict__ info,
                                                              const uint32_t* __restrict__ sums, uint32_t kind,
-                                                             uint32_t* __restrict__ status, uint32_t chunk_op) {
+                                                             uint32_t* __restrict__ status, uint32_t* __restrict__ first,
+                                                             uint32_t chunk_op) {
   __shared__ uint32_t s_first, s_sum;
   const uint32_t t = threadIdx.x;
   const InflateItem I = items[blockIdx.x];
@@ -374,7 +377,10 @@ __global__ __launch_bounds__(KW_THREADS) void k_inflate_fold(const InflateItem* 
     __syncthreads();
     if (s_sum != I.want) st = kStError;
   }
-  if (t == 0) status[blockIdx.x] = st;
+  if (t == 0) {
+    status[blockIdx.x] = st;
+    if (first) first[blockIdx.x] = f;
+  }
 }
 
 }  // namespace
@@ -386,8 +392,8 @@ hipError_t launch_inflate_head(InflateItem* items, uint32_t nitems, uint32_t con
 }
 
 hipError_t launch_inflate_fold(const InflateItem* items, uint32_t nitems, const SegInfo* info, const uint32_t* sums,
-                               uint32_t container, uint32_t* status, hipStream_t s) {
-  hipLaunchKernelGGL(k_inflate_fold, dim3(nitems), dim3(KW_THREADS), 0, s, items, info, sums, container, status, kChunkOp);
+                               uint32_t container, uint32_t* status, uint32_t* first, hipStream_t s) {
+  hipLaunchKernelGGL(k_inflate_fold, dim3(nitems), dim3(KW_THREADS), 0, s, items, info, sums, container, status, first, kChunkOp);
   return hipGetLastError();
 }
 

@@ -22,8 +22,9 @@
 // A call on more than kBatchChunks chunks runs K1..K4 batch after batch (bounded scratch); the host-buffer entry
 // point pipelines smaller batches with their copies.  A batched call (sfh_compress_batch*: many items, each its own
 // stream) runs the same kernels over descriptor tables (BatchStrip / BatchChunk / BatchItem below).
-// The decoder (sf_inflate.hip, sf_inflate_core.h) runs the other way: k_inflate_tokens[_sub] (Huffman codes ->
-// tokens, all segments at once), k_inflate_bytes (tokens -> bytes, strip by strip), k_inflate_status.
+// The decoder (sf_inflate.hip, sf_inflate_core.h) runs the other way, over descriptor rows (InflateSeg / InflateStrip / InflateItem
+// below): k_inflate_tokens[_sub / _spec] (Huffman codes -> tokens, all segments at once), k_inflate_bytes (tokens -> bytes,
+// strip by strip), k_inflate_fold (every item's status).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -131,7 +132,7 @@ struct PlanTree {
 };
 static_assert(sizeof(PlanTree) % 16 == 0, "PlanTree rows");
 
-// per-segment record of the decoder (sf_inflate.hip): written by k_inflate_tokens, read by k_inflate_bytes
+// per-segment record of the decoder (sf_inflate.hip): written by k_inflate_tokens*, read by k_inflate_bytes and k_inflate_fold
 constexpr uint32_t kSegRaw = 1u, kSegSerial = 2u;
 struct SegInfo {
   uint32_t status;   // DecompressStatus of the reference (src/decompress.hpp:13-23), 0 = Success
@@ -212,8 +213,9 @@ struct BatchIndexRow { // per chunk of the call (k_batch_index: the batch's inde
 };
 static_assert(sizeof(BatchStrip) == 16 && sizeof(BatchChunk) == 16 && sizeof(BatchItem) == 32 && sizeof(WrapItem) == 32,
               "descriptor rows (the host packs them into one upload)");
-// Batched decompression (sfh_decompress_batch*): the decoder's kernels with a compile-time BATCH parameter read these rows
-// where the single call derives a segment's stream, index entries, output and history from its number.
+// The indexed decoder (sfh_decompress*, sfh_decompress_batch*, _range*, _any*): its kernels read a segment's stream, index
+// entries, output and history from these rows (a single stream is a call of one item; the cut into launch batches:
+// sf_inflate_plan.h).
 struct InflateSeg {      // per segment of a launch batch (k_inflate_tokens*, k_inflate_bytes)
   const uint8_t* src;    // its item's stream (index entries are offsets into it)
   const uint64_t* ix;    // its two index entries: [ix[0], ix[1]) are its stream bytes
@@ -289,18 +291,12 @@ hipError_t launch_wrap_batch(const uint32_t* sums, const WrapItem* items, uint32
                              uint64_t* d_total, hipStream_t s);
 // sf_inflate.hip
 hipError_t init_inflate_kernels();
-// sps: segments per strip (1: every segment independent); a segment's matches may reach its strip's earlier segments
-hipError_t launch_inflate_tokens(const uint8_t* src, uint64_t src_n, const uint64_t* index, uint32_t nseg, uint64_t dst_n,
-                                 uint32_t* tokens, SegInfo* info, uint32_t sps, bool speculate, hipStream_t s);
-hipError_t launch_inflate_tokens_sub(const uint8_t* src, uint64_t src_n, const uint64_t* index, const uint32_t* subidx,
-                                     uint32_t nseg, uint64_t dst_n, uint32_t* tokens, SegInfo* info, uint32_t sps,
-                                     hipStream_t s);
-hipError_t launch_inflate_bytes(const uint8_t* src, uint64_t src_n, uint32_t nseg, const uint32_t* tokens, SegInfo* info,
-                                uint8_t* dst, uint32_t sps, hipStream_t s);
-hipError_t launch_inflate_status(const SegInfo* info, uint32_t nseg, uint32_t* d_result, hipStream_t s);
-// batched: the launch batch's segment rows stand in for src / index / dst_n / sps (info and tokens: the batch's own)
-hipError_t launch_inflate_tokens_batch(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool sub,
-                                       bool speculate, hipStream_t s);
+// one launch batch: its segment rows (info and tokens: the batch's own), then its strips (a segment's matches may reach its
+// strip's earlier segments).  sub: the rows carry sub-index words; else speculate, or the lane-serial kernel alone
+hipError_t launch_inflate_tokens(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool sub, bool speculate,
+                                 hipStream_t s);
+hipError_t launch_inflate_bytes(const InflateSeg* rows, const InflateStrip* strips, uint32_t nstrips, const uint32_t* tokens,
+                                SegInfo* info, hipStream_t s);
 // ---- sf_unindexed.hip: the segment index recovered from the stream ----
 uint32_t any_scan_waves(uint64_t src_n);  // waves (per-wave counts) of k_any_scan over a buffer of src_n bytes
 size_t any_scan_tmp_words(uint32_t n);    // words of `tmp` launch_scan_u32 needs for n elements
@@ -317,20 +313,19 @@ hipError_t launch_any_walk(const uint8_t* src, const uint64_t* head, const uint6
                            uint8_t* mark, uint32_t* lbl, uint32_t* rank, uint32_t* tmp, uint32_t* total, uint64_t* index,
                            uint32_t nseg, uint32_t* res, hipStream_t s);
 hipError_t launch_any_single(const uint64_t* head, uint64_t* index, uint32_t* res, hipStream_t s);
-// behind the token stage: depends[seg], and the rows of k_inflate_bytes_batch (nseg slots, the unused ones empty)
+// behind the token stage: depends[seg], and the strip rows of k_inflate_bytes (nseg slots, the unused ones empty)
 hipError_t launch_any_rows(const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends, uint32_t* starts,
                            uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows, hipStream_t s);
-// recovered index (sfh_decompress_any*): the batch kernels with the EXACT end rule for rows flagged kSegExact
+// recovered index (sfh_decompress_any*): the token kernels with the EXACT end rule for rows flagged kSegExact
 hipError_t launch_inflate_tokens_exact(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool speculate,
                                        hipStream_t s);
-hipError_t launch_inflate_bytes_batch(const InflateSeg* rows, const InflateStrip* strips, uint32_t nstrips,
-                                      const uint32_t* tokens, SegInfo* info, hipStream_t s);
 // per item of the call: the wrapper (before the token kernels), then the status fold (behind every launch batch)
 // (segs, sums: the call's segment and checksum rows, which a gzip item with ISIZE below its output size cuts down to ISIZE)
 hipError_t launch_inflate_head(InflateItem* items, uint32_t nitems, uint32_t container, InflateSeg* segs, BatchChunk* sums,
                                hipStream_t s);
+// first (nullable): per item, its first failing segment (0xFFFFFFFF: none)
 hipError_t launch_inflate_fold(const InflateItem* items, uint32_t nitems, const SegInfo* info, const uint32_t* sums,
-                               uint32_t container, uint32_t* status, hipStream_t s);
+                               uint32_t container, uint32_t* status, uint32_t* first, hipStream_t s);
 // random access: the byte stage with a write window per row, and every range's status (its span's first failing segment)
 hipError_t launch_inflate_bytes_clip(const InflateSeg* rows, const InflateClip* clips, const InflateStrip* strips, uint32_t nstrips,
                                      const uint32_t* tokens, SegInfo* info, hipStream_t s);

@@ -24,7 +24,10 @@
 //                     is copied straight from the stream.
 //   k_inflate_bytes_clip  the same walk for random access (sfh_decompress_range*): every segment with a write window, the
 //                     part of it a requested byte range covers; the rest of it only passes through the LDS ring.
-//   k_inflate_status  first non-zero segment status in stream order = what the serial decoder would report.
+// Every kernel reads a segment from its row (InflateSeg: stream, the two index entries, sub-index words, output, size,
+// history; the byte stage a strip from its InflateStrip) in its prologue, and only there: a single stream is a call of one
+// item (sfh_decompress_device), so there is one geometry.  The first non-zero segment status in stream order -- what the
+// serial decoder would report -- is k_inflate_fold's (sf_checksum.hip).
 #include "sf_device.h"
 
 #include <stdlib.h>
@@ -49,39 +52,32 @@ constexpr uint32_t KB_LDS = KB_RING + KB_AUX;            // 52,000 B: three work
 static_assert(3 * KB_LDS <= 160 * 1024, "k_inflate_bytes: three workgroups per CU");
 static_assert(KB_SPAN <= KB_RING - kWindow && KB_RING % 16 == 0 && kChunk % 4 == 0, "ring geometry");
 
-// BATCH (sfh_decompress_batch*): segment `seg` of the launch batch is rows[seg] -- its stream, index entries, size and
-// history -- instead of what the single call derives from seg; the rows are read here, in the prologue, only.
-// EXACT (BATCH only): a row flagged kSegExact decodes with decode_segment<true> (the recovered index's end rule).
-template <bool BATCH, bool EXACT = false>
-__global__ __launch_bounds__(KT_LANES) void k_inflate_tokens(const uint8_t* __restrict__ src, uint64_t src_n,
-                                                            const uint64_t* __restrict__ index, uint32_t nseg,
-                                                            uint64_t dst_n, uint32_t* __restrict__ tokens,
-                                                            SegInfo* __restrict__ info, uint32_t sps,
-                                                            uint32_t only_retry, const InflateSeg* __restrict__ rows) {
+// A pointer read from a row is a generic one to the compiler, and a load through it a FLAT load, which counts on lgkmcnt as
+// well as on vmcnt: the token loops' waits for their LDS reads then also wait for the window loads in flight (token stage of
+// a 1 GiB stream, sub-indexed: 3.24 ms against 2.97 with the stream pointer a kernel argument).  Rows point to device
+// memory; said here, where a kernel takes a pointer out of its row, the accesses are global ones.
+template <class T>
+__device__ __forceinline__ T* row_ptr(T* p) {
+  return (T*)(__attribute__((address_space(1))) T*)(uintptr_t)p;
+}
+
+// Segment `seg` of the launch batch is rows[seg]: its stream, index entries, size and history.
+// EXACT: a row flagged kSegExact decodes with decode_segment<true> (the recovered index's end rule).
+template <bool EXACT = false>
+__global__ __launch_bounds__(KT_LANES) void k_inflate_tokens(const InflateSeg* __restrict__ rows, uint32_t nseg,
+                                                            uint32_t* __restrict__ tokens, SegInfo* __restrict__ info,
+                                                            uint32_t only_retry) {
   extern __shared__ __align__(16) uint8_t s_tables[];
   const uint32_t seg = blockIdx.x * KT_LANES + threadIdx.x;
   if (seg >= nseg) return;
   if (only_retry && info[seg].status != kRetrySerial) return;  // behind k_inflate_tokens_spec: what that one left
-  uint64_t lo, hi;
-  uint32_t out_n, hist;
-  bool wrapped = false;
-  if constexpr (BATCH) {
-    const InflateSeg R = rows[seg];
-    src = R.src;
-    src_n = R.src_n;
-    lo = R.ix[0];
-    hi = R.ix[1];
-    out_n = R.out_n;
-    hist = R.hist & ~kSegWrapped;
-    wrapped = (R.hist & kSegWrapped) != 0;
-    if constexpr (EXACT) hist &= ~kSegExact;
-  } else {
-    lo = index[seg];
-    hi = index[seg + 1];
-    const uint64_t obase = (uint64_t)seg * kChunk;
-    out_n = dst_n > obase ? (uint32_t)(dst_n - obase < kChunk ? dst_n - obase : kChunk) : 0u;
-    hist = (seg % sps) * kChunk;
-  }
+  const InflateSeg R = rows[seg];
+  const uint8_t* const src = row_ptr(R.src);
+  const uint64_t src_n = R.src_n, lo = row_ptr(R.ix)[0], hi = row_ptr(R.ix)[1];
+  const uint32_t out_n = R.out_n;
+  uint32_t hist = R.hist & ~kSegWrapped;
+  const bool wrapped = (R.hist & kSegWrapped) != 0;
+  if constexpr (EXACT) hist &= ~kSegExact;
   uint32_t* const seg_tokens = tokens + (uint64_t)seg * kChunk;
   uint8_t* const lane_m = s_tables + threadIdx.x * inflate::LaneLayout::kBytes;
   inflate::SegmentResult r;
@@ -94,8 +90,8 @@ __global__ __launch_bounds__(KT_LANES) void k_inflate_tokens(const uint8_t* __re
   SegInfo si;
   si.status = r.status;
   // a wrapped item whose body ENDS short of its output: container.hpp's raw decode succeeds there and its checksum of the
-  // whole output fails -- Error (a raw item keeps the single call's SrcTooSmall)
-  if (BATCH && wrapped && r.status == inflate::kSrcTooSmall && r.ended) si.status = inflate::kError;
+  // whole output fails -- Error (a raw item keeps the serial decoder's SrcTooSmall)
+  if (wrapped && r.status == inflate::kSrcTooSmall && r.ended) si.status = inflate::kError;
   si.ntok = r.ntok;
   si.raw = (r.raw ? kSegRaw : 0u) | kSegSerial;
   si.out_n = out_n;
@@ -485,13 +481,11 @@ __device__ void decode_regions_lockstep(const uint8_t* src, uint64_t src_n, uint
 constexpr uint32_t kSpecLookBack = 512;
 constexpr uint32_t kSpecCheck = 1024;  // the checkpoint of a counting pass: this many bits behind the lane's start
 
-// BATCH: the wave's two segments may belong to different items -- each half reads its own row (stream, index entries,
-// sub-index, size, history) in the prologue
-template <bool BATCH>
-__device__ __forceinline__ void tokens_wave_sub(const uint8_t* __restrict__ src, uint64_t src_n, const uint64_t* __restrict__ index,
-                                            const uint32_t* __restrict__ subidx, uint32_t nseg, uint64_t dst_n,
-                                            uint32_t* __restrict__ tokens, SegInfo* __restrict__ info, uint32_t sps,
-                                            const InflateSeg* __restrict__ rows) {
+// The wave's two segments may belong to different items: each half reads its own row (stream, index entries, sub-index,
+// size, history) in the prologue.
+__attribute__((amdgpu_waves_per_eu(5, 5)))  // 96 VGPRs: what the workgroup's LDS allows per SIMD
+__global__ __launch_bounds__(64, 2) void k_inflate_tokens_sub(const InflateSeg* __restrict__ rows, uint32_t nseg,
+                                                             uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
   using L = inflate::SharedLayout;
   __shared__ __align__(16) uint8_t s_tab[2][L::kBytes];
   __shared__ __align__(16) RegionLds s_reg;
@@ -500,28 +494,19 @@ __device__ __forceinline__ void tokens_wave_sub(const uint8_t* __restrict__ src,
   const uint32_t lane = threadIdx.x, half = lane >> 5, hl = lane & 31;
   const uint32_t seg = 2 * blockIdx.x + half;
   const bool live = seg < nseg;
-  uint64_t lo, hi;
-  uint32_t out_n, hist = 0;            // (BATCH only: the single call derives both where it needs them)
+  const uint8_t* src = nullptr;
+  uint64_t src_n = 0, lo = 0, hi = 0;
+  uint32_t out_n = 0, hist = 0;
   const uint32_t* seg_sub = nullptr;
-  if constexpr (BATCH) {
-    lo = 0;
-    hi = 0;
-    out_n = 0;
-    if (live) {
-      const InflateSeg R = rows[seg];
-      src = R.src;
-      src_n = R.src_n;
-      lo = R.ix[0];
-      hi = R.ix[1];
-      out_n = R.out_n;
-      hist = R.hist & ~kSegWrapped;
-      seg_sub = R.sub;
-    }
-  } else {
-    lo = live ? index[seg] : 0;
-    hi = live ? index[seg + 1] : 0;
-    const uint64_t obase = (uint64_t)seg * kChunk;
-    out_n = (live && dst_n > obase) ? (uint32_t)(dst_n - obase < kChunk ? dst_n - obase : kChunk) : 0u;
+  if (live) {
+    const InflateSeg R = rows[seg];
+    src = row_ptr(R.src);
+    src_n = R.src_n;
+    lo = row_ptr(R.ix)[0];
+    hi = row_ptr(R.ix)[1];
+    out_n = R.out_n;
+    hist = R.hist & ~kSegWrapped;
+    seg_sub = row_ptr(R.sub);
   }
   {
     // RFC 1951 3.2.5 as a table: base | extra bits << 16
@@ -563,7 +548,7 @@ __device__ __forceinline__ void tokens_wave_sub(const uint8_t* __restrict__ src,
   uint32_t bit0 = 0, bit1 = 0, tok1 = 0, ob = 0, oe = 0;
   bool go = false;
   if (decode) {
-    const uint32_t* sub = BATCH ? seg_sub : subidx + (uint64_t)seg * 2 * kSubRegions;
+    const uint32_t* sub = seg_sub;
     bit0 = sub[2 * hl];
     tok0 = sub[2 * hl + 1];
     bit1 = hl + 1 < kSubRegions ? sub[2 * hl + 2] : 0u;
@@ -577,7 +562,7 @@ __device__ __forceinline__ void tokens_wave_sub(const uint8_t* __restrict__ src,
   {
     RegionOut o;
     decode_regions_lockstep<L, false>(src, src_n, lo, hi, bit0, bit1, hl + 1 == kSubRegions, ob, oe,
-                                      tokens + (uint64_t)seg * kChunk + tok0, s_tab[half], half, BATCH ? hist : (seg % sps) * kChunk, go, lane,
+                                      tokens + (uint64_t)seg * kChunk + tok0, s_tab[half], half, hist, go, lane,
                                       s_reg, o);
     n = o.ntok;
     if (go) {
@@ -602,21 +587,6 @@ __device__ __forceinline__ void tokens_wave_sub(const uint8_t* __restrict__ src,
       info[seg] = si;
     }
   }
-}
-
-__attribute__((amdgpu_waves_per_eu(5, 5)))  // 96 VGPRs: what the workgroup's LDS allows per SIMD
-__global__ __launch_bounds__(64, 2) void k_inflate_tokens_sub(const uint8_t* __restrict__ src, uint64_t src_n,
-                                                             const uint64_t* __restrict__ index,
-                                                             const uint32_t* __restrict__ subidx, uint32_t nseg,
-                                                             uint64_t dst_n, uint32_t* __restrict__ tokens,
-                                                             SegInfo* __restrict__ info, uint32_t sps) {
-  tokens_wave_sub<false>(src, src_n, index, subidx, nseg, dst_n, tokens, info, sps, nullptr);
-}
-// (its own kernel, not a template parameter of the one above: the single call's kernel keeps its signature and figures)
-__attribute__((amdgpu_waves_per_eu(5, 5)))
-__global__ __launch_bounds__(64, 2) void k_inflate_tokens_sub_batch(const InflateSeg* __restrict__ rows, uint32_t nseg,
-                                                                   uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
-  tokens_wave_sub<true>(nullptr, 0, nullptr, nullptr, nseg, 0, tokens, info, 1, rows);
 }
 
 // ---- k_inflate_tokens_spec: the wave, block after block ----
@@ -698,13 +668,12 @@ struct SegState {
 };
 enum : uint32_t { kSegRun = 0, kSegDone = 1, kSegRetry = 2 };
 
-// BATCH: as tokens_wave_sub -- each half's row gives its stream, index entries, size and history
-// EXACT (BATCH only): a row flagged kSegExact counts as done only when its blocks end on its last bit, none of them final;
-// anything else goes to k_inflate_tokens<true, true>, which says what is wrong (decode_segment<true>)
-template <bool BATCH, bool EXACT = false>
-__device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src, uint64_t src_n, const uint64_t* __restrict__ index,
-                                                 uint32_t nseg, uint64_t dst_n, uint32_t* __restrict__ tokens,
-                                                 SegInfo* __restrict__ info, uint32_t sps, const InflateSeg* __restrict__ rows) {
+// As k_inflate_tokens_sub: each half's row gives its stream, index entries, size and history.
+// EXACT: a row flagged kSegExact counts as done only when its blocks end on its last bit, none of them final; anything else
+// goes to k_inflate_tokens<true>, which says what is wrong (decode_segment<true>)
+template <bool EXACT>
+__device__ __forceinline__ void tokens_wave_spec(const InflateSeg* __restrict__ rows, uint32_t nseg, uint32_t* __restrict__ tokens,
+                                                 SegInfo* __restrict__ info) {
   using L = inflate::SharedLayout;
   __shared__ __align__(16) uint8_t s_tab[2][L::kBytes];
   __shared__ __align__(16) RegionLds s_reg;
@@ -712,17 +681,17 @@ __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src
   __shared__ SegState s_st[2];
   const uint32_t lane = threadIdx.x, half = lane >> 5, hl = lane & 31;
   const uint32_t seg = 2 * blockIdx.x + half;
-  uint32_t hist = 0;  // (BATCH only: the single call derives it where it needs it)
+  const uint8_t* src = nullptr;
+  uint64_t src_n = 0;
+  uint32_t hist = 0;
   bool exact = false;
-  if constexpr (BATCH) {
-    if (seg < nseg) {  // (every lane of the half: the stream pointer is the half's own)
-      src = rows[seg].src;
-      src_n = rows[seg].src_n;
-      hist = rows[seg].hist & ~kSegWrapped;
-      if constexpr (EXACT) {
-        exact = (hist & kSegExact) != 0;
-        hist &= ~kSegExact;
-      }
+  if (seg < nseg) {  // (every lane of the half: the stream pointer is the half's own)
+    src = row_ptr(rows[seg].src);
+    src_n = rows[seg].src_n;
+    hist = rows[seg].hist & ~kSegWrapped;
+    if constexpr (EXACT) {
+      exact = (hist & kSegExact) != 0;
+      hist &= ~kSegExact;
     }
   }
   {
@@ -734,18 +703,8 @@ __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src
   }
   if (hl == 0) {
     const bool live = seg < nseg;
-    uint64_t lo, hi;
-    uint32_t out_n;
-    if constexpr (BATCH) {
-      lo = live ? rows[seg].ix[0] : 0;
-      hi = live ? rows[seg].ix[1] : 0;
-      out_n = live ? rows[seg].out_n : 0u;
-    } else {
-      lo = live ? index[seg] : 0;
-      hi = live ? index[seg + 1] : 0;
-      const uint64_t obase = (uint64_t)seg * kChunk;
-      out_n = (live && dst_n > obase) ? (uint32_t)(dst_n - obase < kChunk ? dst_n - obase : kChunk) : 0u;
-    }
+    const uint64_t lo = live ? row_ptr(rows[seg].ix)[0] : 0, hi = live ? row_ptr(rows[seg].ix)[1] : 0;
+    const uint32_t out_n = live ? rows[seg].out_n : 0u;
     const uint32_t seg_bits = (hi > lo && hi - lo < (1ull << 16)) ? 8u * (uint32_t)(hi - lo) : 0u;
     SegState z;
     z.lo = lo;
@@ -952,7 +911,7 @@ __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src
     {
       const uint32_t ob = S.out_base + bsum - nbytes;
       decode_regions_lockstep<L, false>(src, src_n, S.lo, S.hi, entry, exitb, hl == 31, ob, ob + nbytes,
-                                        tokens + (uint64_t)seg * kChunk + S.tok_base + (tsum - cnt), m, half, BATCH ? hist : (seg % sps) * kChunk, go,
+                                        tokens + (uint64_t)seg * kChunk + S.tok_base + (tsum - cnt), m, half, hist, go,
                                         lane, s_reg, o);
     }
     fresh();
@@ -989,22 +948,15 @@ __device__ __forceinline__ void tokens_wave_spec(const uint8_t* __restrict__ src
 }
 
 __attribute__((amdgpu_waves_per_eu(5, 5)))
-__global__ __launch_bounds__(64, 2) void k_inflate_tokens_spec(const uint8_t* __restrict__ src, uint64_t src_n,
-                                                              const uint64_t* __restrict__ index, uint32_t nseg,
-                                                              uint64_t dst_n, uint32_t* __restrict__ tokens,
-                                                              SegInfo* __restrict__ info, uint32_t sps) {
-  tokens_wave_spec<false>(src, src_n, index, nseg, dst_n, tokens, info, sps, nullptr);
-}
-__attribute__((amdgpu_waves_per_eu(5, 5)))
-__global__ __launch_bounds__(64, 2) void k_inflate_tokens_spec_batch(const InflateSeg* __restrict__ rows, uint32_t nseg,
-                                                                    uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
-  tokens_wave_spec<true>(nullptr, 0, nullptr, nseg, 0, tokens, info, 1, rows);
+__global__ __launch_bounds__(64, 2) void k_inflate_tokens_spec(const InflateSeg* __restrict__ rows, uint32_t nseg,
+                                                              uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
+  tokens_wave_spec<false>(rows, nseg, tokens, info);
 }
 
 __attribute__((amdgpu_waves_per_eu(5, 5)))
 __global__ __launch_bounds__(64, 2) void k_inflate_tokens_spec_exact(const InflateSeg* __restrict__ rows, uint32_t nseg,
                                                                     uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
-  tokens_wave_spec<true, true>(nullptr, 0, nullptr, nseg, 0, tokens, info, 1, rows);
+  tokens_wave_spec<true>(rows, nseg, tokens, info);
 }
 
 __device__ __forceinline__ uint32_t load_word_guarded(const uint8_t* base, uint64_t src_n, uint64_t w) {
@@ -1029,15 +981,14 @@ __device__ __forceinline__ uint32_t load_word_guarded(const uint8_t* base, uint6
 // step being produced; byte p of the strip lives at p mod KB_RING.  Every step's bytes go to `dst` as soon as they
 // are final (whole dwords; the odd bytes with the next step), so the ring never has to hold a whole segment.
 // rb: ring position of the segment's first byte; segbase: that byte's position in its strip (bytes of history).
-// Returns false when the segment failed.  BATCH: the segment's output starts at rows[seg].dst.
-// CLIP (k_inflate_bytes_clip, with BATCH): of the segment's bytes only [clips[seg].lo, clips[seg].hi) are written, byte lo at
+// Returns false when the segment failed.  The segment's output starts at rows[seg].dst.
+// CLIP (k_inflate_bytes_clip): of the segment's bytes only [clips[seg].lo, clips[seg].hi) are written, byte lo at
 // clips[seg].dst, which has any alignment; an empty window: the segment is resolved into the ring for the ones behind it and
 // nothing of it reaches global memory.
-template <bool BATCH, bool CLIP = false>
+template <bool CLIP>
 __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t src_n, const uint32_t* __restrict__ tokens,
-                                      SegInfo* __restrict__ info, uint8_t* __restrict__ dst, uint32_t seg, uint32_t segbase,
-                                      uint32_t rb, uint8_t* s_dyn, const InflateSeg* __restrict__ rows,
-                                      const InflateClip* __restrict__ clips = nullptr) {
+                                      SegInfo* __restrict__ info, uint32_t seg, uint32_t segbase, uint32_t rb, uint8_t* s_dyn,
+                                      const InflateSeg* __restrict__ rows, const InflateClip* __restrict__ clips) {
   constexpr uint32_t kRing = KB_RING;
   uint8_t* s_out = s_dyn;                                          // [kRing] output window
   uint16_t* s_ptr = reinterpret_cast<uint16_t*>(s_dyn + kRing);   // [KB_SPAN] step-relative source, or kFinal
@@ -1075,8 +1026,9 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
     c_lo = C.lo < out_n ? C.lo : out_n;
     c_hi = C.hi < out_n ? C.hi : out_n;
     c_hi = c_hi > c_lo ? c_hi : c_lo;
-  } else if constexpr (BATCH) o = rows[seg].dst;
-  else o = dst + (uint64_t)seg * kChunk;
+  } else {
+    o = rows[seg].dst;
+  }
 
   if (si.raw & kSegRaw) {
     // stored segment: dword copy from an arbitrarily aligned stream position
@@ -1391,21 +1343,22 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
   return true;
 }
 
-// The byte-copy kernel: one workgroup per strip of `sps` segments (sps = 1: independent segments), the
-// segments in order, the window carried in LDS from one to the next.
-__global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes(const uint8_t* __restrict__ src, uint64_t src_n,
-                                                              const uint32_t* __restrict__ tokens,
-                                                              SegInfo* __restrict__ info, uint8_t* __restrict__ dst,
-                                                              uint32_t nseg, uint32_t sps) {
+// The byte-copy kernel: one workgroup per row of the strip table (its segments are one item's, in order; a strip of one:
+// an independent segment), the window carried in LDS from one segment to the next.
+__global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes(const InflateSeg* __restrict__ rows,
+                                                              const InflateStrip* __restrict__ strips,
+                                                              const uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
   extern __shared__ __align__(16) uint8_t s_dyn[];
-  const uint32_t seg0 = blockIdx.x * sps;
-  uint32_t rb = 0;  // ring position of the segment's first byte: (k * kChunk) mod KB_RING
-  for (uint32_t k = 0; k < sps && seg0 + k < nseg; ++k) {
-    if (!inflate_segment_bytes<false>(src, src_n, tokens, info, dst, seg0 + k, k * kChunk, rb, s_dyn, nullptr)) {
-      // the later segments of the strip depend on this one: they fail with it (first failure in stream
-      // order is what the caller sees, k_inflate_status)
-      for (uint32_t j = k + 1 + threadIdx.x; j < sps && seg0 + j < nseg; j += KB_THREADS)
-        if (info[seg0 + j].status == inflate::kOk) info[seg0 + j].status = inflate::kError;
+  const InflateStrip S = strips[blockIdx.x];
+  const uint8_t* src = rows[S.seg0].src;
+  const uint64_t src_n = rows[S.seg0].src_n;
+  uint32_t rb = 0;
+  for (uint32_t k = 0; k < S.nseg; ++k) {
+    if (!inflate_segment_bytes<false>(src, src_n, tokens, info, S.seg0 + k, k * kChunk, rb, s_dyn, rows, nullptr)) {
+      // the later segments of the strip depend on this one: they fail with it (first failure in stream order is what
+      // the caller sees, k_inflate_fold)
+      for (uint32_t j = k + 1 + threadIdx.x; j < S.nseg; j += KB_THREADS)
+        if (info[S.seg0 + j].status == inflate::kOk) info[S.seg0 + j].status = inflate::kError;
       return;
     }
     rb += kChunk;
@@ -1414,29 +1367,7 @@ __global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes(const uint8_t* __r
   }
 }
 
-// sfh_decompress_batch*: one workgroup per row of the strip table (its segments are one item's, in order)
-__global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes_batch(const InflateSeg* __restrict__ rows,
-                                                                    const InflateStrip* __restrict__ strips,
-                                                                    const uint32_t* __restrict__ tokens,
-                                                                    SegInfo* __restrict__ info) {
-  extern __shared__ __align__(16) uint8_t s_dyn[];
-  const InflateStrip S = strips[blockIdx.x];
-  const uint8_t* src = rows[S.seg0].src;
-  const uint64_t src_n = rows[S.seg0].src_n;
-  uint32_t rb = 0;
-  for (uint32_t k = 0; k < S.nseg; ++k) {
-    if (!inflate_segment_bytes<true>(src, src_n, tokens, info, nullptr, S.seg0 + k, k * kChunk, rb, s_dyn, rows)) {
-      for (uint32_t j = k + 1 + threadIdx.x; j < S.nseg; j += KB_THREADS)
-        if (info[S.seg0 + j].status == inflate::kOk) info[S.seg0 + j].status = inflate::kError;
-      return;
-    }
-    rb += kChunk;
-    rb = rb >= KB_RING ? rb - KB_RING : rb;
-    __syncthreads();
-  }
-}
-
-// sfh_decompress_range*: as k_inflate_bytes_batch, every row with its write window.  The rows of a strip are the segments
+// sfh_decompress_range*: as k_inflate_bytes, every row with its write window.  The rows of a strip are the segments
 // of one range's decode span inside one strip of the stream: those in front of the range's first byte have an empty
 // window and are only resolved into the ring.
 __global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes_clip(const InflateSeg* __restrict__ rows,
@@ -1450,7 +1381,7 @@ __global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes_clip(const Inflate
   const uint64_t src_n = rows[S.seg0].src_n;
   uint32_t rb = 0;
   for (uint32_t k = 0; k < S.nseg; ++k) {
-    if (!inflate_segment_bytes<true, true>(src, src_n, tokens, info, nullptr, S.seg0 + k, k * kChunk, rb, s_dyn, rows, clips)) {
+    if (!inflate_segment_bytes<true>(src, src_n, tokens, info, S.seg0 + k, k * kChunk, rb, s_dyn, rows, clips)) {
       for (uint32_t j = k + 1 + threadIdx.x; j < S.nseg; j += KB_THREADS)
         if (info[S.seg0 + j].status == inflate::kOk) info[S.seg0 + j].status = inflate::kError;
       return;
@@ -1476,27 +1407,6 @@ __global__ __launch_bounds__(64) void k_inflate_fold_spans(const InflateSpan* __
   if (lane == 0) status[r] = first == 0xFFFFFFFFu ? (uint32_t)inflate::kOk : info[S.row0 + first].status;
 }
 
-constexpr uint32_t KS_THREADS = 1024;
-__global__ __launch_bounds__(KS_THREADS) void k_inflate_status(const SegInfo* __restrict__ info, uint32_t nseg,
-                                                               uint32_t* __restrict__ result /* [status, segment] */) {
-  __shared__ uint32_t s_first[KS_THREADS];
-  const uint32_t t = threadIdx.x;
-  uint32_t first = 0xFFFFFFFFu;
-  for (uint32_t s = t; s < nseg; s += KS_THREADS)
-    if (info[s].status != inflate::kOk && s < first) first = s;
-  s_first[t] = first;
-  __syncthreads();
-  for (uint32_t o = KS_THREADS / 2; o; o >>= 1) {
-    if (t < o && s_first[t + o] < s_first[t]) s_first[t] = s_first[t + o];
-    __syncthreads();
-  }
-  if (t == 0) {
-    const uint32_t f = s_first[0];
-    result[0] = f == 0xFFFFFFFFu ? (uint32_t)inflate::kOk : info[f].status;
-    result[1] = f;
-  }
-}
-
 }  // namespace
 
 hipError_t init_inflate_kernels() {
@@ -1506,50 +1416,28 @@ hipError_t init_inflate_kernels() {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_tokens<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)KT_LDS);
   if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_tokens<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)KT_LDS);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes_batch), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)KB_LDS);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes_clip), hipFuncAttributeMaxDynamicSharedMemorySize,
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)KB_LDS);
   if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes), hipFuncAttributeMaxDynamicSharedMemorySize,
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes_clip), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)KB_LDS);
 }
 
-// Index-only streams: the speculative wave kernel, then the lane-serial one for the segments that one left (speculate =
-// false: the lane-serial kernel for every segment, the path of rounds 2-4; SFH_INFLATE_SERIAL=1).
-hipError_t launch_inflate_tokens(const uint8_t* src, uint64_t src_n, const uint64_t* index, uint32_t nseg, uint64_t dst_n,
-                                 uint32_t* tokens, SegInfo* info, uint32_t sps, bool speculate, hipStream_t s) {
-  if (speculate) {
-    hipLaunchKernelGGL(k_inflate_tokens_spec, dim3((nseg + 1) / 2), dim3(64), 0, s, src, src_n, index, nseg, dst_n, tokens,
-                       info, sps);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k_inflate_tokens<false>, dim3((nseg + KT_LANES - 1) / KT_LANES), dim3(KT_LANES), KT_LDS, s, src, src_n, index,
-                     nseg, dst_n, tokens, info, sps, speculate ? 1u : 0u, (const InflateSeg*)nullptr);
-  return hipGetLastError();
-}
-
-// The batch's segments: the sub-indexed wave kernel, or the speculative one with the lane-serial kernel behind it for what
-// that one leaves (speculate = false: the lane-serial kernel alone)
-hipError_t launch_inflate_tokens_batch(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool sub,
-                                       bool speculate, hipStream_t s) {
+// A launch batch's segments: the sub-indexed wave kernel, or -- index only -- the speculative one with the lane-serial kernel
+// behind it for what that one leaves (speculate = false: the lane-serial kernel for every segment; SFH_INFLATE_SERIAL=1).
+hipError_t launch_inflate_tokens(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool sub, bool speculate,
+                                 hipStream_t s) {
   if (sub) {
-    hipLaunchKernelGGL(k_inflate_tokens_sub_batch, dim3((nseg + 1) / 2), dim3(64), 0, s, rows, nseg, tokens, info);
+    hipLaunchKernelGGL(k_inflate_tokens_sub, dim3((nseg + 1) / 2), dim3(64), 0, s, rows, nseg, tokens, info);
     return hipGetLastError();
   }
   if (speculate) {
-    hipLaunchKernelGGL(k_inflate_tokens_spec_batch, dim3((nseg + 1) / 2), dim3(64), 0, s, rows, nseg, tokens, info);
+    hipLaunchKernelGGL(k_inflate_tokens_spec, dim3((nseg + 1) / 2), dim3(64), 0, s, rows, nseg, tokens, info);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(k_inflate_tokens<true>, dim3((nseg + KT_LANES - 1) / KT_LANES), dim3(KT_LANES), KT_LDS, s,
-                     (const uint8_t*)nullptr, (uint64_t)0, (const uint64_t*)nullptr, nseg, (uint64_t)0, tokens, info, 1u,
-                     speculate ? 1u : 0u, rows);
+  hipLaunchKernelGGL(k_inflate_tokens<false>, dim3((nseg + KT_LANES - 1) / KT_LANES), dim3(KT_LANES), KT_LDS, s, rows, nseg,
+                     tokens, info, speculate ? 1u : 0u);
   return hipGetLastError();
 }
 
@@ -1560,15 +1448,14 @@ hipError_t launch_inflate_tokens_exact(const InflateSeg* rows, uint32_t nseg, ui
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((k_inflate_tokens<true, true>), dim3((nseg + KT_LANES - 1) / KT_LANES), dim3(KT_LANES), KT_LDS, s,
-                     (const uint8_t*)nullptr, (uint64_t)0, (const uint64_t*)nullptr, nseg, (uint64_t)0, tokens, info, 1u,
-                     speculate ? 1u : 0u, rows);
+  hipLaunchKernelGGL(k_inflate_tokens<true>, dim3((nseg + KT_LANES - 1) / KT_LANES), dim3(KT_LANES), KT_LDS, s, rows, nseg,
+                     tokens, info, speculate ? 1u : 0u);
   return hipGetLastError();
 }
 
-hipError_t launch_inflate_bytes_batch(const InflateSeg* rows, const InflateStrip* strips, uint32_t nstrips,
-                                      const uint32_t* tokens, SegInfo* info, hipStream_t s) {
-  hipLaunchKernelGGL(k_inflate_bytes_batch, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, rows, strips, tokens, info);
+hipError_t launch_inflate_bytes(const InflateSeg* rows, const InflateStrip* strips, uint32_t nstrips, const uint32_t* tokens,
+                                SegInfo* info, hipStream_t s) {
+  hipLaunchKernelGGL(k_inflate_bytes, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, rows, strips, tokens, info);
   return hipGetLastError();
 }
 
@@ -1580,26 +1467,6 @@ hipError_t launch_inflate_bytes_clip(const InflateSeg* rows, const InflateClip* 
 
 hipError_t launch_inflate_fold_spans(const InflateSpan* spans, uint32_t nspans, const SegInfo* info, uint32_t* status, hipStream_t s) {
   hipLaunchKernelGGL(k_inflate_fold_spans, dim3(nspans), dim3(64), 0, s, spans, nspans, info, status);
-  return hipGetLastError();
-}
-
-hipError_t launch_inflate_tokens_sub(const uint8_t* src, uint64_t src_n, const uint64_t* index, const uint32_t* subidx,
-                                     uint32_t nseg, uint64_t dst_n, uint32_t* tokens, SegInfo* info, uint32_t sps,
-                                     hipStream_t s) {
-  hipLaunchKernelGGL(k_inflate_tokens_sub, dim3((nseg + 1) / 2), dim3(64), 0, s, src, src_n, index, subidx, nseg, dst_n,
-                     tokens, info, sps);
-  return hipGetLastError();
-}
-
-hipError_t launch_inflate_bytes(const uint8_t* src, uint64_t src_n, uint32_t nseg, const uint32_t* tokens, SegInfo* info,
-                                uint8_t* dst, uint32_t sps, hipStream_t s) {
-  const uint32_t nstrips = (nseg + sps - 1) / sps;
-  hipLaunchKernelGGL(k_inflate_bytes, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, src, src_n, tokens, info, dst, nseg, sps);
-  return hipGetLastError();
-}
-
-hipError_t launch_inflate_status(const SegInfo* info, uint32_t nseg, uint32_t* d_result, hipStream_t s) {
-  hipLaunchKernelGGL(k_inflate_status, dim3(1), dim3(KS_THREADS), 0, s, info, nseg, d_result);
   return hipGetLastError();
 }
 

@@ -13,7 +13,7 @@
 //   k_any_scatter      marked node of rank k (an exclusive scan of the edge labels) -> index[k] (and index[k+1] for the coded
 //                      segment a stored jump lands on).
 //   k_any_depends      after the token stage: per segment, does a match reach before its first byte?
-//   k_any_rows_*       rows for k_inflate_bytes_batch: an independent segment and the dependent ones behind it.
+//   k_any_rows_*       strip rows for k_inflate_bytes: an independent segment and the dependent ones behind it.
 #include "sf_device.h"
 
 #include "sf_inflate_core.h"

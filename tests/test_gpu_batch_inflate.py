@@ -15,6 +15,7 @@ import torch
 
 from conftest import ROOT
 from starflate_amd import Compressor, synth
+from single_decode_cases import context_under, damaged_batch, first_entry_batch, parent_record
 
 pytestmark = pytest.mark.gpu
 
@@ -45,17 +46,6 @@ def _items(sizes, seed=0):
 
 def _nseg(n):
     return max(1, -(-n // CHUNK))
-
-
-def _split(idx, sub, sizes):
-    """the flattened batch index -> per item (index, subindex)"""
-    out, e, g = [], 0, 0
-    for n in sizes:
-        k = _nseg(n)
-        out.append((idx[e: e + k + 1], sub[g * 64: (g + k) * 64]))
-        e += k + 1
-        g += k
-    return out
 
 
 def _dev(arrays):
@@ -111,17 +101,10 @@ def _single(comp, stream, ix, sb, n, bb):
 
 
 def test_raw_items_equal_the_single_call_damaged_ones_included(comp):
-    sizes = (70000, 200000, 100000, 50000, 300000, 1000)
-    items = [synth.gen_text(n, seed=30 + i) for i, n in enumerate(sizes)]
-    streams = [bytearray(s) for s in comp.compress_batch(items, block_bytes=262144)]
-    idx, sub, bb = comp.last_batch_index()
-    idx, sub, bb = idx.copy(), sub.copy(), bb.copy()
-    per = _split(idx, sub, sizes)
-    streams[1][len(streams[1]) // 2] ^= 0x5A          # a flipped body byte
-    per[2][0][1] += 3                                  # a wrong index entry
-    per[3][1][2 * 5] += 7                              # a wrong sub-index word
-    bb[4] = 32768                                      # too small a block_bytes: InvalidDistance
-    streams = [bytes(s) for s in streams]
+    """(The single call is a batch of one item: beside it stand the statuses the implicit-geometry single call of the commit
+    before that gave for these items, tests/golden/single_decode_parent.json.)"""
+    sizes, items, streams, idx, sub, bb, per = damaged_batch(comp)
+    recorded = parent_record()["batch_want_st"]["damaged"]
     for use_sub in (False, True):
         s_arg = sub if use_sub else None
         touts, tst = comp.decompress_batch_tensors(_dev([np.frombuffer(s, np.uint8) for s in streams]), sizes,
@@ -135,6 +118,7 @@ def test_raw_items_equal_the_single_call_damaged_ones_included(comp):
             want_b, want_st = _single(comp, streams[i], per[i][0], per[i][1] if use_sub else None, n, int(bb[i]))
             assert st[i] == want_st, (i, use_sub)
             assert touts[i][:n].cpu().numpy().tobytes() == want_b, (i, use_sub)
+        assert st == recorded[str(use_sub).lower()], use_sub
         assert st[0] == 0 and st[5] == 0 and st[2] != 0 and (st[3] != 0) == use_sub
         assert st[1] != 0 or touts[1].cpu().numpy().tobytes() != items[1].tobytes()  # (a flipped byte may still decode)
         assert st[4] == INVALID_DISTANCE
@@ -142,15 +126,10 @@ def test_raw_items_equal_the_single_call_damaged_ones_included(comp):
 
 def test_raw_items_with_a_first_entry_past_0(comp):
     """A wrapped stream decoded as a raw body through its index (entry 0 = the header's end), and a damaged entry 0: a raw
-    item's status is the single call's, which does not look at where entry 0 lies."""
-    sizes = (5000, 70000, 40000)
-    items = [synth.gen_text(n, seed=50 + i) for i, n in enumerate(sizes)]
-    streams = comp.compress_batch(items, container="gzip")
-    idx, sub, bb = comp.last_batch_index()
-    idx = idx.copy()
-    per = _split(idx, sub, sizes)
-    assert all(int(p[0][0]) == 10 for p in per)
-    per[2][0][0] += 1  # a damaged entry 0
+    item's status is the single call's, which does not look at where entry 0 lies.  (Beside the single call, a batch of one
+    item, stand the statuses recorded from the commit before it became one.)"""
+    sizes, items, streams, idx, sub, bb, per = first_entry_batch(comp)
+    recorded = parent_record()["batch_want_st"]["first_entry"]
     for use_sub in (False, True):
         outs, st = comp.decompress_batch(streams, sizes, index=idx, subindex=sub if use_sub else None, block_bytes=bb)
         for i, n in enumerate(sizes):
@@ -158,6 +137,7 @@ def test_raw_items_with_a_first_entry_past_0(comp):
             assert st[i] == want_st, (i, use_sub)
             if want_st == 0:
                 assert outs[i] == want_b
+        assert st == recorded[str(use_sub).lower()], use_sub
         assert st[0] == 0 and st[1] == 0 and outs[0] == items[0].tobytes()
 
 
@@ -314,6 +294,28 @@ def test_launch_batches_match_the_default():
         assert p.returncode == 0, p.stderr[-2000:]
         return p.stdout.strip()
     assert run({"SFH_BATCH_CHUNKS": "4"}) == run({})
+
+
+def test_an_item_is_cut_where_its_strips_do_not_divide_the_cap():
+    """Strips of three segments under a cap of eight: an item is cut at max(sps, cap / sps * sps) = 6 segments, the single
+    call's rule (sf_inflate_plan.h), so the item of seven, which would fit the cap whole, is a batch of six and a batch of one,
+    and no batch of this call is wider than six (the token scratch says so).  Around it: an item in front, which shares no
+    batch with it, a short last strip, and items that do not fit the batch open before them."""
+    bb = 3 * CHUNK
+    sizes = (1000, 7 * CHUNK - 5, 2 * CHUNK + 1, 6 * CHUNK, 4 * CHUNK)
+    items = [synth.gen_text(n, seed=70 + i) for i, n in enumerate(sizes)]
+    c = context_under(SFH_BATCH_CHUNKS="8")
+    try:
+        streams = c.compress_batch(items, block_bytes=bb)
+        idx, sub, bbs = c.last_batch_index()
+        assert bbs.tolist() == [bb] * len(sizes)
+        for s in (None, sub):
+            outs, st = c.decompress_batch(streams, sizes, index=idx, subindex=s, block_bytes=bbs)
+            assert st == [0] * len(sizes)
+            assert outs == [a.tobytes() for a in items]
+            assert c.last_decode_scratch_bytes() == 6 * CHUNK * 4
+    finally:
+        c.close()
 
 
 def test_async_ordering_and_index_state(comp):
