@@ -328,6 +328,64 @@ class compressor {
     }
     return starflate::decompress(src, dst, container);
   }
+  /// Many streams given alone, decoded in one call (sfh_decompress_any_batch): srcs[i] into exactly dsts[i].size() bytes at
+  /// dsts[i] -- what compress_batch() wrote, read back with nothing but the streams.  As decompress(src, dst, container) does
+  /// for one stream, every item the GPU did not report Success for (not block-flushed, damaged, a refused call) goes through
+  /// container.hpp's serial decompress(srcs[i], dsts[i], container): statuses[i] is always the reference's answer.
+  auto decompress_batch(std::span<const std::span<const std::byte>> srcs, std::span<const std::span<std::byte>> dsts,
+                        Container container, std::span<DecompressStatus> statuses) -> CompressStatus {
+    const std::size_t k = srcs.size();
+    if (dsts.size() != k || statuses.size() != k) return CompressStatus::InvalidArgument;
+    std::vector<std::uint32_t> st(k, 1U);
+    if (ctx_ && k) {
+      std::vector<const void*> sp(k);
+      std::vector<void*> dp(k);
+      std::vector<std::uint64_t> n(k), dn(k);
+      for (std::size_t i = 0; i < k; ++i) {
+        sp[i] = srcs[i].data();
+        n[i] = srcs[i].size();
+        dp[i] = dsts[i].data();
+        dn[i] = dsts[i].size();
+      }
+      if (sfh_decompress_any_batch(ctx_, k, sp.data(), n.data(), static_cast<std::uint32_t>(container), dp.data(), dn.data(), dn.data(),
+                                   nullptr, st.data()) != SFH_OK)
+        st.assign(k, 1U);
+    }
+    for (std::size_t i = 0; i < k; ++i)
+      statuses[i] = st[i] == 0 ? DecompressStatus::Success : starflate::decompress(srcs[i], dsts[i], container);
+    return CompressStatus::Success;
+  }
+  /// The indexes of many streams given alone, recovered on the GPU in one call (sfh_recover_index_batch): batch_index()'s
+  /// layout with block_bytes 0 (unknown) and no regions.  indexable[i] (may be empty: not wanted) is false for an item that is
+  /// not block-flushed every 32 KiB, whose entries are 0.
+  auto recover_index_batch(std::span<const std::span<const std::byte>> srcs, std::span<const std::size_t> dst_sizes,
+                           Container container, std::vector<bool>* indexable = nullptr)
+      -> compat::expected<batch_stream_index, CompressStatus> {
+    if (!ctx_) return compat::unexpected{init_};
+    const std::size_t k = srcs.size();
+    if (dst_sizes.size() != k) return compat::unexpected{CompressStatus::InvalidArgument};
+    batch_stream_index ix;
+    ix.block_bytes.assign(k, 0U);
+    ix.first.resize(k + 1);
+    std::vector<const void*> sp(k);
+    std::vector<std::uint64_t> n(k), dn(k);
+    std::vector<std::uint32_t> st(k);
+    for (std::size_t i = 0; i < k; ++i) {
+      sp[i] = srcs[i].data();
+      n[i] = srcs[i].size();
+      dn[i] = dst_sizes[i];
+      ix.first[i + 1] = ix.first[i] + (dst_sizes[i] ? (dst_sizes[i] + SFH_SEGMENT_BYTES - 1) / SFH_SEGMENT_BYTES : 1) + 1;
+    }
+    ix.offsets.resize(ix.first[k]);
+    const int rc = sfh_recover_index_batch(ctx_, k, sp.data(), n.data(), static_cast<std::uint32_t>(container), dn.data(),
+                                           ix.offsets.data(), st.data());
+    if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+    if (indexable != nullptr) {
+      indexable->resize(k);
+      for (std::size_t i = 0; i < k; ++i) (*indexable)[i] = st[i] == 0;
+    }
+    return ix;
+  }
   /// decompress(src, dst, produced) for a raw, zlib or gzip stream (one member) with no index and no flush points, on the GPU
   /// from block discovery to the last byte (sfh_inflate_stream): the status and, on Success, the bytes are container.hpp's
   /// decompress(src, dst, container)'s, except that a zlib dst may be larger than the output (the Adler-32 covers the bytes

@@ -434,6 +434,43 @@ int sfh_decompress_any_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uin
                               uint32_t* status, void* stream);
 int sfh_decompress_any(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, void* dst, uint64_t dst_cap,
                        uint64_t dst_n, uint64_t* dst_n_out, uint32_t* status);
+/* Many block-flushed streams in one call, each with no side information and each decoded into its own buffer: what
+ * sfh_compress_batch writes, read back with nothing but the streams.  For every item i, status[i], dst_n_out[i] and, on status
+ * 0, the bytes are exactly what sfh_decompress_any_device gives for that item alone (container: the same for every item).  An
+ * item for which the single call returns SFH_E_NOT_INDEXABLE gets status[i] = SFH_ITEM_NOT_INDEXABLE -- a per-item status,
+ * never a DecompressStatus -- and its destination is not written; the call still returns SFH_OK (sfh_inflate_stream_batch*
+ * decodes such items).  A wrapper that does not parse gives the item container.hpp's status, as in the single call.  One item's
+ * failure or unindexability changes no other item's bytes or status, and nothing is written outside [dsts[i], dsts[i] +
+ * dst_cap[i]).  dst_n[i]: the item's output size, or SFH_SIZE_FROM_TRAILER (gzip: ISIZE); a size or an ISIZE above dst_cap[i]
+ * is DecompressStatus DstTooSmall (4) for that item, not a failure of the call.  dst_n_out (may be NULL) and status are host
+ * arrays.
+ * Refused with SFH_E_INVALID_ARG before anything is enqueued: a null ctx or an unknown container (also with count == 0); a null
+ * array with count > 0, a null source with src_n > 0 or a null destination with dst_cap > 0; a device source not 4-byte, a
+ * destination not 16-byte or the index not 8-byte aligned; a size above 2^44; SFH_SIZE_FROM_TRAILER with a container other
+ * than gzip (or in a recover call); overlapping destination ranges; more than 2^31 - 1 segments or scan waves (8 KiB of an
+ * item's stream each; an item of one segment has none) in the call.  count == 0 is SFH_OK.
+ * Host synchronisations of `stream` (NULL = the ctx's own), per call and not per item: one after the wrappers (only when some
+ * item's size is SFH_SIZE_FROM_TRAILER), one after the node count, one after the walk, one at the end of the decode.  The
+ * recovery runs over the whole call (one scan, one walk over the items' node lists, each with its own end sentinel); the decode
+ * in launch batches of whole items of at most SFH_BATCH_CHUNKS segments (a larger item alone and whole), so the token scratch is
+ * that of the widest launch batch (sfh_last_decode_scratch_bytes).  sfh_last_recover_stats sums over the call,
+ * sfh_last_inflate_ms over the launch batches.  Afterwards the ctx holds no index of either kind.
+ * sfh_recover_index_batch_device: the walk alone.  d_index: flat, sfh_copy_batch_index's layout -- item i's max(1, ceil(dst_n[i]
+ * / 32768)) + 1 entries behind those of the items before it; status[i] is 0 or SFH_ITEM_NOT_INDEXABLE (then the item's entries
+ * are 0).
+ * sfh_recover_index_batch, sfh_decompress_any_batch: host buffers, packed through the pinned staging; only items whose status
+ * is 0 are copied back. */
+#define SFH_ITEM_NOT_INDEXABLE 0xFFFFFFF8u /* (uint32_t)SFH_E_NOT_INDEXABLE */
+int sfh_recover_index_batch_device(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, uint32_t container,
+                                   const uint64_t* dst_n, uint64_t* d_index, uint32_t* status, void* stream);
+int sfh_decompress_any_batch_device(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, uint32_t container,
+                                    void* const* d_dsts, const uint64_t* dst_cap, const uint64_t* dst_n, uint64_t* dst_n_out,
+                                    uint32_t* status, void* stream);
+int sfh_recover_index_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
+                            const uint64_t* dst_n, uint64_t* index, uint32_t* status);
+int sfh_decompress_any_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
+                             void* const* dsts, const uint64_t* dst_cap, const uint64_t* dst_n, uint64_t* dst_n_out,
+                             uint32_t* status);
 /* the last sfh_recover_index* / sfh_decompress_any* call: ms[0] candidate scan, ms[1] walk (with profiling on, else zeros);
  * counts[0] nodes (b0, markers, stored headers), counts[1] rows of dependent segments (0 when no decode ran) */
 int sfh_last_recover_stats(sfh_ctx* ctx, float ms[2], uint64_t counts[2]);

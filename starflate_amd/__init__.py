@@ -4,9 +4,9 @@ Only what the hot path needs: csrc/ (HIP kernels + C-ABI), the ctypes binding,
 torch plumbing for device buffers, the multi-GPU shard/concat helper and the
 synthetic corpora used by tests and bench.py.
 """
-from .compressor import (CHUNK_BYTES, Compressor, StarflateError, checksum_combine, compress, compress_batch,  # noqa: F401
-                         compress_multi, decompress, decompress_batch, decompress_range, decompress_ranges,
+from .compressor import (CHUNK_BYTES, ITEM_NOT_INDEXABLE, Compressor, StarflateError, checksum_combine, compress, compress_batch,  # noqa: F401
+                         compress_multi, decompress, decompress_any_batch, decompress_batch, decompress_range, decompress_ranges,
                          decompress_stream, decompress_stream_batch, wrapper_bytes)
 
 __all__ = ["Compressor", "StarflateError", "compress", "CHUNK_BYTES", "checksum_combine", "wrapper_bytes", "compress_multi", "compress_batch", "decompress", "decompress_batch", "decompress_range", "decompress_ranges", "decompress_stream",
-           "decompress_stream_batch"]
+           "decompress_stream_batch", "decompress_any_batch", "ITEM_NOT_INDEXABLE"]

@@ -15,6 +15,7 @@ STRATEGY = {"auto": 0, "stored": 1, "fixed": 2, "dynamic": 3}
 CONTAINER = {"raw": 0, "zlib": 1, "gzip": 2}
 E_NOT_INDEXABLE = -8  # SFH_E_NOT_INDEXABLE
 SIZE_FROM_TRAILER = (1 << 64) - 1  # SFH_SIZE_FROM_TRAILER
+ITEM_NOT_INDEXABLE = 0xFFFFFFF8  # SFH_ITEM_NOT_INDEXABLE: a per-item status of the sfh_*_any_batch* calls
 DBG_NTOK, DBG_TOKENS, DBG_HIST, DBG_PLAN, DBG_LENS, DBG_OFFSETS, DBG_STAMPS = range(7)
 DBG_SUBINDEX = 7
 DBG_ITEMS, DBG_NITEMS = 8, 9
@@ -32,6 +33,7 @@ EXPORTS = [
     "sfh_decompress_batch_device_async", "sfh_decompress_batch",
     "sfh_decompress_ranges_device_async", "sfh_decompress_range_device", "sfh_decompress_ranges",
     "sfh_recover_index_device", "sfh_recover_index", "sfh_decompress_any_device", "sfh_decompress_any", "sfh_last_recover_stats",
+    "sfh_recover_index_batch_device", "sfh_recover_index_batch", "sfh_decompress_any_batch_device", "sfh_decompress_any_batch",
     "sfh_inflate_stream_device", "sfh_inflate_stream", "sfh_inflate_stream_batch_device", "sfh_inflate_stream_batch",
     "sfh_last_stream_stats",
     "sfh_last_block_bytes", "sfh_index_entries", "sfh_copy_index", "sfh_copy_subindex", "sfh_decompress_device", "sfh_decompress", "sfh_last_inflate_ms", "sfh_last_decode_scratch_bytes",
@@ -127,6 +129,15 @@ def lib():
     L.sfh_decompress_any.argtypes = [vp, vp, sz, C.c_uint32, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint32)]
     L.sfh_decompress_any.restype = C.c_int
+    u32p = C.POINTER(C.c_uint32)
+    L.sfh_recover_index_batch_device.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, u64p, vp, u32p, vp]
+    L.sfh_recover_index_batch_device.restype = C.c_int
+    L.sfh_recover_index_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, u64p, vp, u32p]
+    L.sfh_recover_index_batch.restype = C.c_int
+    L.sfh_decompress_any_batch_device.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, C.POINTER(vp), u64p, u64p, u64p, u32p, vp]
+    L.sfh_decompress_any_batch_device.restype = C.c_int
+    L.sfh_decompress_any_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, C.POINTER(vp), u64p, u64p, u64p, u32p]
+    L.sfh_decompress_any_batch.restype = C.c_int
     L.sfh_last_recover_stats.argtypes = [vp, C.POINTER(C.c_float * 2), C.POINTER(C.c_uint64 * 2)]
     L.sfh_last_recover_stats.restype = C.c_int
     L.sfh_inflate_stream_device.argtypes = [vp, vp, sz, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), vp]

@@ -14,6 +14,7 @@ import numpy as np
 from . import _capi
 
 CHUNK_BYTES = 32768
+ITEM_NOT_INDEXABLE = _capi.ITEM_NOT_INDEXABLE  # a per-item status of decompress_any_batch: not block-flushed every 32 KiB
 
 
 class StarflateError(RuntimeError):
@@ -430,6 +431,93 @@ class Compressor:
         stats = [int(st[i]) if live[i] else first[i] for i in range(k)]
         return [outs[i][: out_n[i]] if stats[i] == 0 else outs[i][:0] for i in range(k)], stats
 
+    # ---- many block-flushed streams with no side information in one call (sfh_decompress_any_batch*) ----
+    def decompress_any_batch(self, streams, sizes=None, container="raw"):
+        """Host buffers: bytes-like raw / zlib / gzip streams, each block-flushed every 32 KiB (what compress_batch writes) ->
+        (list of bytes, list of statuses), every item exactly what decompress_any gives for it alone.  sizes: the decoded
+        sizes (None: gzip's ISIZE).  A status is a DecompressStatus, or ITEM_NOT_INDEXABLE for an item that is not
+        block-flushed (decompress_stream_batch decodes those).  An item whose status is not 0 comes back as b""."""
+        srcs, n, want, caps, kind = _any_batch_args(streams, sizes, container)
+        k = len(srcs)
+        if k == 0:
+            return [], []
+        sp = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a in srcs])
+        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in caps]
+        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
+        out_n = (C.c_uint64 * k)()
+        st = (C.c_uint32 * k)()
+        self._check(self._lib.sfh_decompress_any_batch(self._h, k, sp, n, kind, dp, (C.c_uint64 * k)(*caps), want, out_n, st))
+        return [dsts[i][: out_n[i]].tobytes() if st[i] == 0 else b"" for i in range(k)], [int(v) for v in st]
+
+    def decompress_any_batch_tensors(self, streams, sizes=None, container="raw", outs=None, hip_stream=None):
+        """Device buffers: 1-D uint8 CUDA tensors -> (list of output tensors, list of statuses); each output is the item's
+        decoded bytes (empty unless its status is 0).  sizes: the decoded sizes (None: gzip's ISIZE, read on the device; outs
+        is then required and gives the capacities); outs: one uint8 CUDA tensor (16-byte aligned) of at least sizes[i] bytes
+        per item (default: new ones).  Synchronises the stream."""
+        import torch
+
+        streams = list(streams)
+        kind = _container(container)
+        k = len(streams)
+        if sizes is None:
+            if kind != 2:
+                raise ValueError("sizes is required unless container='gzip' (whose trailer carries ISIZE)")
+            if outs is None:
+                raise ValueError("sizes=None on device tensors needs outs (the capacities)")
+            want = [_capi.SIZE_FROM_TRAILER] * k
+        else:
+            want = [int(m) for m in sizes]
+            if len(want) != k or any(m < 0 or m > (1 << 44) for m in want):
+                raise ValueError("sizes must hold one size in [0, 2^44] per stream")
+        for t in streams:
+            self._check_tensor(t)
+        dev = torch.device("cuda", self.device)
+        s = torch.cuda.current_stream(dev).cuda_stream if hip_stream is None else hip_stream
+        if outs is None:
+            outs = [torch.empty(max(m, 1), dtype=torch.uint8, device=dev) for m in want]
+        outs = list(outs)
+        if len(outs) != k or (sizes is not None and any(o.numel() < m for o, m in zip(outs, want))):
+            raise ValueError("outs must hold one tensor of at least sizes[i] bytes per item")
+        for t in outs:
+            self._check_tensor(t)
+        if k == 0:
+            return [], []
+        sp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in streams])
+        n = (C.c_uint64 * k)(*[t.numel() for t in streams])
+        dp = (C.c_void_p * k)(*[o.data_ptr() for o in outs])
+        caps = (C.c_uint64 * k)(*[o.numel() for o in outs])
+        out_n = (C.c_uint64 * k)()
+        st = (C.c_uint32 * k)()
+        self._check(self._lib.sfh_decompress_any_batch_device(self._h, k, sp, n, kind, dp, caps, (C.c_uint64 * k)(*want), out_n, st,
+                                                              C.c_void_p(s)))
+        return [outs[i][: out_n[i]] if st[i] == 0 else outs[i][:0] for i in range(k)], [int(v) for v in st]
+
+    def recover_index_batch(self, streams, sizes, container="raw", hip_stream=None):
+        """streams: 1-D uint8 CUDA tensors, sizes: their decoded sizes -> (index: one int64 CUDA tensor, last_batch_index()'s
+        flat layout -- item i's segments + 1 offsets behind those of the items before it -- and a list of statuses: 0, or
+        ITEM_NOT_INDEXABLE for an item that is not block-flushed every 32 KiB, whose entries are 0)."""
+        import torch
+
+        streams = list(streams)
+        kind = _container(container)
+        want = [int(m) for m in sizes]
+        k = len(streams)
+        if len(want) != k or any(m < 0 or m > (1 << 44) for m in want):
+            raise ValueError("sizes must hold one size in [0, 2^44] per stream")
+        for t in streams:
+            self._check_tensor(t)
+        dev = torch.device("cuda", self.device)
+        s = torch.cuda.current_stream(dev).cuda_stream if hip_stream is None else hip_stream
+        entries = sum(max(1, -(-m // CHUNK_BYTES)) + 1 for m in want)
+        index = torch.zeros(max(entries, 1), dtype=torch.int64, device=dev)
+        st = (C.c_uint32 * max(k, 1))()
+        if k:
+            sp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in streams])
+            n = (C.c_uint64 * k)(*[t.numel() for t in streams])
+            self._check(self._lib.sfh_recover_index_batch_device(self._h, k, sp, n, kind, (C.c_uint64 * k)(*want), index.data_ptr(),
+                                                                 st, C.c_void_p(s)))
+        return index[:entries], [int(st[i]) for i in range(k)]
+
     # ---- many independent streams, each decoded into its own buffer, in one call (sfh_decompress_batch*) ----
     def decompress_batch(self, streams, sizes, index=None, subindex=None, block_bytes=None, container="raw"):
         """Host buffers: bytes-like streams and their decoded sizes -> (list of bytes, list of DecompressStatus ints).  index /
@@ -750,6 +838,32 @@ def _stream_batch_args(streams, sizes, container):
     return srcs, (C.c_uint64 * len(srcs))(*[a.size for a in srcs]), caps, _capi.CONTAINER[container]
 
 
+def _any_batch_args(streams, sizes, container):
+    """decompress_any_batch's host arguments, checked before anything reaches the device: (sources, src_n, dst_n as the C-ABI
+    takes it, capacities, container code).  sizes=None: gzip's ISIZE, which also gives the capacities here."""
+    if isinstance(streams, (bytes, bytearray, memoryview, np.ndarray)):
+        raise ValueError("streams: a sequence of bytes-like streams")
+    srcs = [np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else np.ascontiguousarray(d, dtype=np.uint8).ravel()
+            for d in streams]
+    if not isinstance(container, str) or container not in _capi.CONTAINER:
+        raise ValueError(f"container must be one of {sorted(_capi.CONTAINER)}")
+    kind = _capi.CONTAINER[container]
+    k = len(srcs)
+    if sizes is None:
+        if kind != 2:
+            raise ValueError("sizes is required unless container='gzip' (whose trailer carries ISIZE)")
+        caps = [int.from_bytes(a[-4:].tobytes(), "little") if a.size >= 18 else 0 for a in srcs]
+        want = [_capi.SIZE_FROM_TRAILER] * k
+    else:
+        caps = [int(m) for m in sizes]
+        if len(caps) != k:
+            raise ValueError(f"{k} streams but {len(caps)} sizes")
+        if any(m < 0 or m > (1 << 44) for m in caps):
+            raise ValueError("sizes must lie in [0, 2^44]")
+        want = caps
+    return srcs, (C.c_uint64 * k)(*[a.size for a in srcs]), (C.c_uint64 * k)(*want), caps, kind
+
+
 _DEFAULT = {}
 
 
@@ -826,6 +940,26 @@ def decompress_stream_batch(streams, sizes=None, container="raw", device=0):
     if c is None:
         c = _DEFAULT[device] = Compressor(device)
     return c.decompress_stream_batch(streams, sizes, container)
+
+
+def decompress_any_batch(streams, sizes=None, container="raw", device=0, fallback=True):
+    """Raw / zlib / gzip streams given alone -> (list of bytes, list of statuses), all in one call on the GPU
+    (Compressor.decompress_any_batch): what compress_batch wrote, read back with nothing but the streams.  sizes=None: gzip's
+    ISIZE.  fallback=True: the items that are not block-flushed every 32 KiB (status ITEM_NOT_INDEXABLE) are decoded by one
+    decompress_stream_batch call, on the GPU as well; fallback=False reports that status.  The arguments are checked before a
+    device is touched."""
+    _, _, _, caps, _ = _any_batch_args(streams, sizes, container)
+    streams = list(streams)
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    outs, sts = c.decompress_any_batch(streams, sizes, container)
+    rest = [i for i, st in enumerate(sts) if st == ITEM_NOT_INDEXABLE] if fallback else []
+    if rest:
+        o2, s2 = c.decompress_stream_batch([streams[i] for i in rest], [caps[i] for i in rest], container)
+        for i, o, st in zip(rest, o2, s2):
+            outs[i], sts[i] = o, st
+    return outs, sts
 
 
 def decompress_range(data, index, total_n, offset, length, subindex=None, *, block_bytes, device=0):

@@ -1,6 +1,7 @@
 // sf_capi.hip -- the C-ABI of include/starflate_hip.h over the kernels of sf_kernels.hip.
 // No torch types, no exceptions across the boundary; a ctx owns its device scratch.
 #include "../../include/starflate_hip.h"
+#include "sf_any_plan.h"
 #include "sf_device.h"
 #include "sf_inflate_core.h"
 #include "sf_inflate_plan.h"
@@ -99,6 +100,8 @@ struct sfh_ctx {
   uint8_t* d_anyseg = nullptr;
   uint64_t* d_anyix = nullptr;
   size_t d_anycnt_cap = 0, d_any_cap = 0, d_anyseg_cap = 0, d_anyix_cap = 0;
+  uint8_t* d_anyb = nullptr;     // the batched calls: every item's body, node ranges and indexable flag; the totals
+  size_t d_anyb_cap = 0;
   hipEvent_t ev_any[5] = {};
   float any_ms[2] = {0, 0};
   uint64_t any_counts[2] = {0, 0};
@@ -1060,6 +1063,304 @@ int enqueue_any_decode(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t 
   return mark_call_end(ctx, s);
 }
 
+// ---- many block-flushed streams in one call (sfh_recover_index_batch*, sfh_decompress_any_batch*) ----
+constexpr uint32_t kStDstTooSmall = 4;  // the reference's DecompressStatus::DstTooSmall
+
+// Everything a call checks before it enqueues anything (`dev`: device buffers, the single call's alignment rules).  dsts /
+// dst_cap null: sfh_recover_index_batch* (dst_n are sizes, d_index the flat index).
+int check_any_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
+                    void* const* dsts, const uint64_t* dst_cap, const uint64_t* dst_n, const uint64_t* index, bool recover,
+                    const uint32_t* status, bool dev) {
+  if (!ctx) return SFH_E_INVALID_ARG;
+  if (container > SFH_GZIP) return fail(ctx, SFH_E_INVALID_ARG, "argument (container)", hipSuccess);
+  if (count == 0) return SFH_OK;
+  if (!srcs || !src_n || !dst_n || !status || (recover ? !index : (!dsts || !dst_cap)))
+    return fail(ctx, SFH_E_INVALID_ARG, "null array", hipSuccess);
+  if (count > ((size_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "too many items", hipSuccess);
+  if (dev && recover && ((uintptr_t)index & 7)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (index 8)", hipSuccess);
+  uint64_t segs = 0, waves = 0;
+  for (size_t i = 0; i < count; ++i) {
+    if ((!srcs[i] && src_n[i]) || (!recover && !dsts[i] && dst_cap[i])) return fail(ctx, SFH_E_INVALID_ARG, "null item pointer", hipSuccess);
+    if (dev && (((uintptr_t)srcs[i] & 3) || (!recover && ((uintptr_t)dsts[i] & 15))))
+      return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, dst 16)", hipSuccess);
+    const bool trailer = dst_n[i] == SFH_SIZE_FROM_TRAILER;
+    if (trailer && (container != SFH_GZIP || recover))
+      return fail(ctx, SFH_E_INVALID_ARG, "SFH_SIZE_FROM_TRAILER: a gzip stream of a decode call only", hipSuccess);
+    if (src_n[i] > ((uint64_t)1 << 44) || (!trailer && dst_n[i] > ((uint64_t)1 << 44)) || (!recover && dst_cap[i] > ((uint64_t)1 << 44)))
+      return fail(ctx, SFH_E_INVALID_ARG, "item too large (sizes up to 2^44)", hipSuccess);
+    // (ISIZE is 32 bits wide, and one above the capacity is refused for the item)
+    const uint64_t n = trailer ? std::min<uint64_t>(dst_cap[i], 0xFFFFFFFFu) : (!recover && dst_n[i] > dst_cap[i]) ? 0 : dst_n[i];
+    const uint32_t ns = chunks_of((size_t)n);
+    segs += ns;
+    if (ns > 1) waves += (src_n[i] + 8191) / 8192;
+  }
+  if (segs > ((uint64_t)1 << 31) - 1 || waves > ((uint64_t)1 << 31) - 1)
+    return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 segments or scan waves in one call", hipSuccess);
+  return recover ? SFH_OK : check_disjoint(ctx, dsts, dst_cap, count);
+}
+
+// what the recovery leaves on the host, per item of the call
+struct AnyBatch {
+  std::vector<uint64_t> out_n;  // the size the item decodes to (SFH_SIZE_FROM_TRAILER resolved; 0 where the wrapper failed)
+  std::vector<uint64_t> ix0;    // its first entry in the flat index
+  std::vector<uint32_t> st;     // 0: indexable; the wrapper's status, DstTooSmall, or SFH_ITEM_NOT_INDEXABLE
+  std::vector<uint8_t> take;    // st == 0
+  uint64_t entries = 0;         // of the flat index
+};
+
+// d_anyb: heads u64[2 count] | ranges AnyRange[count] | ok u32[count] | totals u32[8] (nodes, M nodes, labels, -, -, largest)
+// The recovery of a whole call: the wrappers (k_inflate_head over every item), one scan over every item that has more than one
+// segment, one walk over the concatenated node lists.  d_index: the flat index (zeroed first: the entries of an item that is
+// not indexable stay 0).  Synchronises s: after the wrappers only where ISIZE sizes the work, after the node count, after the
+// walk.  Arguments checked (check_any_batch).
+int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, uint32_t container,
+                      const uint64_t* dst_cap, const uint64_t* dst_n, uint64_t* d_index, hipStream_t s, AnyBatch& R) {
+  const bool prof = ctx->profiling != 0;
+  ctx->any_ms[0] = ctx->any_ms[1] = 0;
+  ctx->any_counts[0] = ctx->any_counts[1] = 0;
+  std::vector<sf::InflateItem> rows;
+  std::vector<sf::AnyItem> items;
+  std::vector<uint32_t> okv;
+  bool trailer = false;
+  try {
+    R.out_n.assign(count, 0);
+    R.ix0.assign(count, 0);
+    R.st.assign(count, 0);
+    R.take.assign(count, 0);
+    rows.resize(count);
+    items.resize(count);
+    okv.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (hipEvent_t& e : ctx->ev_any)
+    if (!e) SF_HIP(hipEventCreate(&e), "event");
+  const size_t o_rng = 16 * count, o_ok = o_rng + sizeof(sf::AnyRange) * count, o_tot = al16(o_ok + 4 * count);
+  int rc = grow(ctx, &ctx->d_anyb, &ctx->d_anyb_cap, o_tot + 32, "recovery tables");
+  if (rc) return rc;
+  uint64_t* heads = (uint64_t*)ctx->d_anyb;
+  sf::AnyRange* range = (sf::AnyRange*)(ctx->d_anyb + o_rng);
+  uint32_t* ok = (uint32_t*)(ctx->d_anyb + o_ok);
+  uint32_t* tot = (uint32_t*)(ctx->d_anyb + o_tot);
+  for (size_t i = 0; i < count; ++i) {
+    const bool tr = dst_n[i] == SFH_SIZE_FROM_TRAILER;
+    trailer |= tr;
+    // an explicit size above the capacity: the item takes no part (an empty row: the wrapper check reads nothing of it)
+    if (!tr && dst_cap && dst_n[i] > dst_cap[i]) R.st[i] = kStDstTooSmall;
+    // (a size from the trailer: k_inflate_head's own ISIZE check, against the capacity)
+    rows[i] = sf::InflateItem{(const uint8_t*)d_srcs[i], src_n[i], tr ? dst_cap[i] : dst_n[i], heads + 2 * i, nullptr, 0, 0, 0, 0, 0, 0};
+    R.out_n[i] = tr ? 0 : dst_n[i];
+  }
+  // the item rows, the scan's item rows and its wave map: one pinned block, uploaded at once -- or, where ISIZE sizes the work,
+  // the item rows first and the rest once the wrappers are read
+  uint64_t segs = 0, nw = 0;
+  auto geometry = [&] {
+    segs = nw = 0;
+    for (size_t i = 0; i < count; ++i) {
+      const uint32_t ns = R.st[i] ? 1u : chunks_of((size_t)R.out_n[i]);
+      const uint32_t w = (ns > 1 && !R.st[i]) ? sf::any_scan_waves(src_n[i]) : 0u;
+      R.ix0[i] = segs + i;
+      items[i] = sf::AnyItem{(const uint8_t*)d_srcs[i], src_n[i], R.ix0[i], ns, (uint32_t)nw, w, 0};
+      segs += ns;
+      nw += w;
+    }
+    R.entries = segs + count;
+  };
+  auto fill_scan_rows = [&](uint8_t* at) {
+    memcpy(at, items.data(), count * sizeof(sf::AnyItem));
+    sf::AnyWave* wv = (sf::AnyWave*)(at + count * sizeof(sf::AnyItem));
+    for (size_t i = 0; i < count; ++i)
+      for (uint32_t p = 0; p < items[i].nwaves; ++p) wv[items[i].wave0 + p] = sf::AnyWave{(uint32_t)i, p};
+  };
+  const size_t b_rows = count * sizeof(sf::InflateItem);
+  size_t o_items = b_rows;
+  if (!trailer) {
+    geometry();
+    const size_t bytes = b_rows + count * sizeof(sf::AnyItem) + (size_t)nw * sizeof(sf::AnyWave);
+    if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
+    memcpy(ctx->h_tab, rows.data(), b_rows);
+    fill_scan_rows(ctx->h_tab + b_rows);
+    if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
+    SF_HIP(sf::launch_inflate_head((sf::InflateItem*)ctx->d_tab, (uint32_t)count, container, nullptr, nullptr, s), "launch k_inflate_head");
+  } else {
+    if ((rc = stage_tables(ctx, b_rows)) != SFH_OK) return rc;
+    memcpy(ctx->h_tab, rows.data(), b_rows);
+    if ((rc = upload_tables(ctx, b_rows, s)) != SFH_OK) return rc;
+    SF_HIP(sf::launch_inflate_head((sf::InflateItem*)ctx->d_tab, (uint32_t)count, container, nullptr, nullptr, s), "launch k_inflate_head");
+    SF_HIP(hipMemcpyAsync(rows.data(), ctx->d_tab, b_rows, hipMemcpyDeviceToHost, s), "D2H wrapper rows");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+    for (size_t i = 0; i < count; ++i) {
+      if (!R.st[i] && rows[i].wst) R.st[i] = rows[i].wst;
+      if (dst_n[i] == SFH_SIZE_FROM_TRAILER) R.out_n[i] = rows[i].wst ? 0 : rows[i].isize;
+    }
+    geometry();
+    if (segs > ((uint64_t)1 << 31) - 1 || nw > ((uint64_t)1 << 31) - 1)
+      return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 segments or scan waves in one call", hipSuccess);
+    const size_t bytes = count * sizeof(sf::AnyItem) + (size_t)nw * sizeof(sf::AnyWave);
+    if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
+    fill_scan_rows(ctx->h_tab);
+    if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
+    o_items = 0;
+  }
+  const sf::AnyItem* t_items = (const sf::AnyItem*)(ctx->d_tab + o_items);
+  const sf::AnyWave* t_waves = (const sf::AnyWave*)(ctx->d_tab + o_items + count * sizeof(sf::AnyItem));
+  if (!d_index) {
+    if ((rc = grow(ctx, &ctx->d_anyix, &ctx->d_anyix_cap, R.entries * sizeof(uint64_t), "recovered index"))) return rc;
+    d_index = ctx->d_anyix;
+  }
+  SF_HIP(hipMemsetAsync(d_index, 0, R.entries * sizeof(uint64_t), s), "clear the index");
+  SF_HIP(hipMemsetAsync(ok, 0, (o_tot + 32) - o_ok, s), "clear the flags");
+  SF_HIP(sf::launch_any_single_batch(t_items, (uint32_t)count, heads, d_index, ok, s), "launch k_any_single");
+  const uint32_t nwaves = (uint32_t)nw;
+  if (nwaves) {
+    const size_t tw = sf::any_scan_tmp_words(nwaves);
+    if ((rc = grow(ctx, &ctx->d_anycnt, &ctx->d_anycnt_cap, (2 * (size_t)nwaves + tw) * sizeof(uint32_t), "candidate counts"))) return rc;
+    uint32_t* cn = (uint32_t*)ctx->d_anycnt;
+    uint32_t* cm = cn + nwaves;
+    uint32_t* tmp = cm + nwaves;
+    if (prof) SF_HIP(hipEventRecord(ctx->ev_any[0], s), "event");
+    SF_HIP(sf::launch_any_count_batch(t_items, t_waves, heads, nwaves, cn, cm, s), "launch k_any_scan");
+    SF_HIP(sf::launch_scan_u32(cn, cn, nwaves, tmp, tot + 0, s), "launch scan");
+    SF_HIP(sf::launch_scan_u32(cm, cm, nwaves, tmp, tot + 1, s), "launch scan");
+    SF_HIP(sf::launch_any_ranges(t_items, (uint32_t)count, cn, cm, nwaves, tot, range, tot + 5, s), "launch k_any_ranges");
+    if (prof) SF_HIP(hipEventRecord(ctx->ev_any[1], s), "event");
+    uint32_t h[6] = {0, 0, 0, 0, 0, 0};
+    SF_HIP(hipMemcpyAsync(h, tot, sizeof h, hipMemcpyDeviceToHost, s), "D2H node count");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+    const uint32_t n = h[0], nm = h[1], largest = h[5];  // n: sentinels included, one per item that was scanned
+    uint32_t scanned = 0;
+    for (size_t i = 0; i < count; ++i) scanned += items[i].nwaves ? 1u : 0u;
+    ctx->any_counts[0] = n - scanned;
+    // pos u64[n] | nxt_a, nxt_b, minc, lbl, rank, item u32[n] | midx u32[nm+1] | tmp | flg, lab, mark u8[n]
+    const size_t ntw = sf::any_scan_tmp_words(n), w4 = al16(4 * (size_t)n), w1 = al16(n);
+    const size_t o_nxa = al16(8 * (size_t)n), o_nxb = o_nxa + w4, o_minc = o_nxb + w4, o_lbl = o_minc + w4, o_rank = o_lbl + w4;
+    const size_t o_item = o_rank + w4, o_midx = o_item + w4, o_tmp = o_midx + al16(4 * ((size_t)nm + 1)), o_flg = o_tmp + al16(4 * ntw);
+    const size_t o_lab = o_flg + w1, o_mark = o_lab + w1;
+    if ((rc = grow(ctx, &ctx->d_any, &ctx->d_any_cap, o_mark + w1, "walk nodes"))) return rc;
+    uint8_t* b = ctx->d_any;
+    if (prof) SF_HIP(hipEventRecord(ctx->ev_any[2], s), "event");
+    SF_HIP(sf::launch_any_nodes_batch(t_items, t_waves, heads, nwaves, cn, cm, (uint64_t*)b, b + o_flg, (uint32_t*)(b + o_minc),
+                                      (uint32_t*)(b + o_midx), (uint32_t*)(b + o_item), s), "launch k_any_scan");
+    if (prof) SF_HIP(hipEventRecord(ctx->ev_any[3], s), "event");
+    SF_HIP(sf::launch_any_walk_batch(t_items, heads, range, (uint32_t*)(b + o_item), (uint64_t*)b, b + o_flg, (uint32_t*)(b + o_minc),
+                                     (uint32_t*)(b + o_midx), n, largest, (uint32_t*)(b + o_nxa), (uint32_t*)(b + o_nxb), b + o_lab,
+                                     b + o_mark, (uint32_t*)(b + o_lbl), (uint32_t*)(b + o_rank), (uint32_t*)(b + o_tmp), tot + 2,
+                                     d_index, ok, s), "launch k_any_walk");
+    if (prof) SF_HIP(hipEventRecord(ctx->ev_any[4], s), "event");
+  }
+  SF_HIP(hipMemcpyAsync(okv.data(), ok, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "D2H walk");
+  if (!trailer && container) SF_HIP(hipMemcpyAsync(rows.data(), ctx->d_tab, b_rows, hipMemcpyDeviceToHost, s), "D2H wrapper rows");
+  if ((rc = mark_call_end(ctx, s)) != SFH_OK) return rc;
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  if (prof && nwaves) {
+    float a = 0, c = 0, w = 0;
+    SF_HIP(hipEventElapsedTime(&a, ctx->ev_any[0], ctx->ev_any[1]), "elapsed");
+    SF_HIP(hipEventElapsedTime(&c, ctx->ev_any[2], ctx->ev_any[3]), "elapsed");
+    SF_HIP(hipEventElapsedTime(&w, ctx->ev_any[3], ctx->ev_any[4]), "elapsed");
+    ctx->any_ms[0] = a + c;
+    ctx->any_ms[1] = w;
+  }
+  for (size_t i = 0; i < count; ++i) {
+    if (!R.st[i] && rows[i].wst) R.st[i] = rows[i].wst;  // container.hpp's answer for the wrapper
+    if (!R.st[i] && !okv[i]) R.st[i] = SFH_ITEM_NOT_INDEXABLE;
+    R.take[i] = R.st[i] == 0;
+  }
+  ctx->index_valid = false;
+  ctx->bix_valid = false;
+  return SFH_OK;
+}
+
+// The decoder on the flat recovered index, over the items the recovery kept (R.take): the batch decoder's tables and kernels,
+// launch batch after launch batch of whole items (sf_any_plan.h) -- the token stage with the exact end rule and the
+// reference's distance rule, the rows of dependent segments built on the device over the batch's segment table, the byte
+// stage -- then the checksums and the fold.  The statuses land in R.st.  Synchronises s at the end.
+int any_batch_decode(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, uint32_t container,
+                     void* const* d_dsts, const uint64_t* d_index, hipStream_t s, AnyBatch& R) {
+  const uint64_t trailer = container == SFH_ZLIB ? 4 : container == SFH_GZIP ? 8 : 0;
+  sf::aplan::Plan P;
+  try {
+    sf::aplan::plan_batches(count, R.out_n.data(), R.take.data(), ctx->batch_chunks, P);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory for the launch batches", hipSuccess);
+  }
+  ctx->last_chunks = P.nseg;
+  ctx->last_dtok_bytes = (size_t)P.widest * sf::kChunk * sizeof(uint32_t);
+  ctx->ev_inf_valid = false;
+  if (P.nseg == 0) return SFH_OK;
+  const uint32_t nseg = P.nseg, nitems = P.nitems, nb = (uint32_t)P.batches.size(), wd = P.widest;
+  int rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, (size_t)nseg * sizeof(sf::SegInfo), "segment records");
+  if (!rc) rc = ensure_dtok(ctx, wd);
+  if (!rc && container) rc = ensure_sums(ctx, nseg);
+  if (!rc) rc = ensure_bstatus(ctx, (size_t)nitems + nb);
+  // rows per batch u32[nb] | depends u8[wd] | starts, excl u32[wd] | tmp | rows InflateStrip[wd]
+  const size_t tw = sf::any_scan_tmp_words(wd);
+  const size_t o_dep = al16(4 * (size_t)nb), o_st = o_dep + al16(wd), o_ex = o_st + al16(4 * (size_t)wd), o_tmp = o_ex + al16(4 * (size_t)wd);
+  const size_t o_rows = o_tmp + al16(4 * tw);
+  if (!rc) rc = grow(ctx, &ctx->d_anyseg, &ctx->d_anyseg_cap, o_rows + sizeof(sf::InflateStrip) * (size_t)wd, "segment rows");
+  if (rc) return rc;
+  // the tables, in one pinned block: segments | items | checksum chunks
+  const size_t b_segs = (size_t)nseg * sizeof(sf::InflateSeg), b_items = (size_t)nitems * sizeof(sf::InflateItem);
+  const size_t o_sums = al16(b_segs + b_items), bytes = o_sums + (container ? (size_t)nseg * sizeof(sf::BatchChunk) : 0);
+  if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
+  sf::InflateSeg* h_segs = (sf::InflateSeg*)ctx->h_tab;
+  sf::InflateItem* h_items = (sf::InflateItem*)(ctx->h_tab + b_segs);
+  sf::BatchChunk* h_sums = (sf::BatchChunk*)(ctx->h_tab + o_sums);
+  uint32_t g = 0, j = 0;
+  for (size_t i = 0; i < count; ++i) {
+    if (!R.take[i]) continue;
+    const uint64_t out_n = R.out_n[i], body_n = container ? (src_n[i] > trailer ? src_n[i] - trailer : 0) : src_n[i];
+    const uint32_t n = sf::aplan::segments_of(out_n);
+    const uint64_t* ix = d_index + R.ix0[i];
+    h_items[j++] = sf::InflateItem{(const uint8_t*)d_srcs[i], src_n[i], out_n, nullptr, ix, g, n, 0, 0, 0, 0};
+    for (uint32_t k = 0; k < n; ++k, ++g) {
+      const uint64_t ob = (uint64_t)k * sf::kChunk;
+      const uint32_t on = (uint32_t)std::min<uint64_t>(sf::kChunk, out_n - std::min(out_n, ob));
+      const uint32_t hist = (k ? sf::kChunk : 0u) | (container ? sf::kSegWrapped : 0u) | (k + 1 < n ? sf::kSegExact : 0u);
+      uint8_t* out = (uint8_t*)d_dsts[i] + ob;
+      h_segs[g] = sf::InflateSeg{(const uint8_t*)d_srcs[i], ix + k, nullptr, out, body_n, on, hist};
+      if (container) h_sums[g] = sf::BatchChunk{out, on, 0u};
+    }
+  }
+  sf::InflateSeg* t_segs = (sf::InflateSeg*)ctx->d_tab;
+  sf::InflateItem* t_items = (sf::InflateItem*)(ctx->d_tab + b_segs);
+  sf::BatchChunk* t_sums = (sf::BatchChunk*)(ctx->d_tab + o_sums);
+  uint8_t* sb = ctx->d_anyseg;
+  uint32_t* d_nrows = (uint32_t*)sb;
+  sf::InflateStrip* strips = (sf::InflateStrip*)(sb + o_rows);
+  const bool prof = ctx->profiling != 0;
+  if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
+  if (prof && (rc = ensure_inflate_events(ctx, nb)) != SFH_OK) return rc;
+  SF_HIP(sf::launch_inflate_head(t_items, nitems, container, t_segs, container ? t_sums : nullptr, s), "launch k_inflate_head");
+  for (uint32_t bi = 0; bi < nb; ++bi) {
+    const sf::aplan::Batch& b = P.batches[bi];
+    sf::SegInfo* binfo = ctx->ws.seginfo + b.row0;
+    hipEvent_t* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
+    if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
+    SF_HIP(sf::launch_inflate_tokens_exact(t_segs + b.row0, b.nseg, ctx->ws.tokens, binfo, !ctx->inflate_serial, s),
+           "launch k_inflate_tokens");
+    SF_HIP(sf::launch_any_rows_batch(t_segs + b.row0, binfo, ctx->ws.tokens, b.nseg, sb + o_dep, (uint32_t*)(sb + o_st),
+                                     (uint32_t*)(sb + o_ex), (uint32_t*)(sb + o_tmp), d_nrows + bi, strips, s), "launch k_any_rows");
+    if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
+    SF_HIP(sf::launch_inflate_bytes(t_segs + b.row0, strips, b.nseg, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes");
+    if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
+  }
+  ctx->ev_inf_batches = nb;
+  ctx->ev_inf_valid = prof;
+  if (container) SF_HIP(sf::launch_checksum_batch(t_sums, nseg, container, ctx->ws.sums, s), "launch k_checksum");
+  SF_HIP(sf::launch_inflate_fold(t_items, nitems, ctx->ws.seginfo, ctx->ws.sums, container, ctx->d_bstatus, nullptr, s),
+         "launch k_inflate_fold");
+  SF_HIP(hipMemcpyAsync(ctx->d_bstatus + nitems, d_nrows, nb * sizeof(uint32_t), hipMemcpyDeviceToDevice, s), "copy rows");
+  SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, ((size_t)nitems + nb) * sizeof(uint32_t), hipMemcpyDeviceToHost, s),
+         "copy statuses");
+  if ((rc = mark_call_end(ctx, s)) != SFH_OK) return rc;
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  j = 0;
+  for (size_t i = 0; i < count; ++i)
+    if (R.take[i]) R.st[i] = ctx->h_bstatus[j++];
+  for (uint32_t bi = 0; bi < nb; ++bi) ctx->any_counts[1] += ctx->h_bstatus[nitems + bi];
+  return SFH_OK;
+}
+
 // ---- streams without flush points (sfh_inflate_stream*, sfh_inflate_stream_batch*; sf_stream.hip) ----
 // Everything a batched call checks before it enqueues anything (`dev`: device buffers, the single call's alignment rules).
 int check_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
@@ -1621,6 +1922,7 @@ void sfh_destroy(sfh_ctx* ctx) {
   (void)hipFree(ctx->d_anycnt);
   (void)hipFree(ctx->d_any);
   (void)hipFree(ctx->d_anyseg);
+  (void)hipFree(ctx->d_anyb);
   (void)hipFree(ctx->d_anyix);
   for (hipEvent_t e : ctx->ev_any)
     if (e) (void)hipEventDestroy(e);
@@ -2230,6 +2532,139 @@ int sfh_decompress_any(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t con
     SF_HIP(hipStreamSynchronize(s), "stream sync");
   }
   return SFH_OK;
+}
+
+int sfh_recover_index_batch_device(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, uint32_t container,
+                                   const uint64_t* dst_n, uint64_t* d_index, uint32_t* status, void* stream) {
+  int rc = check_any_batch(ctx, count, d_srcs, src_n, container, nullptr, nullptr, dst_n, d_index, true, status, true);
+  if (rc || count == 0) return rc;
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();  // see enqueue()
+  AnyBatch R;
+  if ((rc = any_batch_recover(ctx, count, d_srcs, src_n, container, nullptr, dst_n, d_index, stream ? (hipStream_t)stream : ctx->stream, R)))
+    return rc;
+  for (size_t i = 0; i < count; ++i) status[i] = R.st[i] ? SFH_ITEM_NOT_INDEXABLE : 0u;  // (a wrapper that does not parse too)
+  return SFH_OK;
+}
+
+int sfh_decompress_any_batch_device(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, uint32_t container,
+                                    void* const* d_dsts, const uint64_t* dst_cap, const uint64_t* dst_n, uint64_t* dst_n_out,
+                                    uint32_t* status, void* stream) {
+  int rc = check_any_batch(ctx, count, d_srcs, src_n, container, d_dsts, dst_cap, dst_n, nullptr, false, status, true);
+  if (rc || count == 0) return rc;
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();  // see enqueue()
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  AnyBatch R;
+  if ((rc = any_batch_recover(ctx, count, d_srcs, src_n, container, dst_cap, dst_n, nullptr, s, R))) return rc;
+  if ((rc = any_batch_decode(ctx, count, d_srcs, src_n, container, d_dsts, ctx->d_anyix, s, R))) return rc;
+  for (size_t i = 0; i < count; ++i) {
+    status[i] = R.st[i];
+    if (dst_n_out) dst_n_out[i] = R.out_n[i];
+  }
+  return SFH_OK;
+}
+
+int sfh_recover_index_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
+                            const uint64_t* dst_n, uint64_t* index, uint32_t* status) {
+  int rc = check_any_batch(ctx, count, srcs, src_n, container, nullptr, nullptr, dst_n, index, true, status, false);
+  if (rc || count == 0) return rc;
+  std::vector<uint64_t> in_off;
+  std::vector<const void*> d_srcs;
+  size_t entries = count;
+  try {
+    in_off.resize(count + 1);
+    d_srcs.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (size_t i = 0; i < count; ++i) {
+    in_off[i + 1] = (in_off[i] + src_n[i] + 15) / 16 * 16;
+    entries += chunks_of((size_t)dst_n[i]);
+  }
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t s = ctx->stream;
+  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
+  if (!rc) rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, entries * sizeof(uint64_t), "index staging");
+  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
+    ctx->h_stage = nullptr;
+    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
+  }
+  if (rc) return rc;
+  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
+  if ((rc = stage_up(ctx, srcs, src_n, in_off.data(), count, in_off[count], s))) return rc;
+  for (size_t i = 0; i < count; ++i) d_srcs[i] = ctx->d_in + in_off[i];
+  AnyBatch R;
+  if ((rc = any_batch_recover(ctx, count, d_srcs.data(), src_n, container, nullptr, dst_n, ctx->d_index, s, R))) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  SF_HIP(hipMemcpyAsync(index, ctx->d_index, entries * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "D2H index");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  for (size_t i = 0; i < count; ++i) status[i] = R.st[i] ? SFH_ITEM_NOT_INDEXABLE : 0u;  // (a wrapper that does not parse too)
+  return SFH_OK;
+}
+
+int sfh_decompress_any_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
+                             void* const* dsts, const uint64_t* dst_cap, const uint64_t* dst_n, uint64_t* dst_n_out,
+                             uint32_t* status) {
+  int rc = check_any_batch(ctx, count, srcs, src_n, container, dsts, dst_cap, dst_n, nullptr, false, status, false);
+  if (rc || count == 0) return rc;
+  // The items packed into the device staging (16-byte aligned) and moved through the pinned buffer (stage_up, stage_down);
+  // only the items whose status is 0 are copied out of it.  An item's slot is its output size (ISIZE is read here); one
+  // whose size is above its capacity gets no slot, and the device call reports it.
+  std::vector<uint64_t> in_off, out_off, slot, got;
+  std::vector<const void*> d_srcs;
+  std::vector<void*> d_dsts;
+  try {
+    in_off.resize(count + 1);
+    out_off.resize(count + 1);
+    slot.resize(count);
+    got.resize(count);
+    d_srcs.resize(count);
+    d_dsts.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (size_t i = 0; i < count; ++i) {
+    uint64_t n = dst_n[i];
+    if (n == SFH_SIZE_FROM_TRAILER) {
+      const uint8_t* p = (const uint8_t*)srcs[i];
+      const uint64_t sn = src_n[i];
+      n = sn >= 18 ? (uint64_t)(p[sn - 4] | (uint32_t)p[sn - 3] << 8 | (uint32_t)p[sn - 2] << 16 | (uint32_t)p[sn - 1] << 24) : 0;
+    }
+    slot[i] = n <= dst_cap[i] ? n : 0;
+    in_off[i + 1] = (in_off[i] + src_n[i] + 15) / 16 * 16;
+    out_off[i + 1] = (out_off[i] + slot[i] + 15) / 16 * 16;
+  }
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t s = ctx->stream;
+  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
+  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_off[count] ? out_off[count] : 16, "output staging");
+  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
+    ctx->h_stage = nullptr;
+    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
+  }
+  if (rc) return rc;
+  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
+  if ((rc = stage_up(ctx, srcs, src_n, in_off.data(), count, in_off[count], s))) return rc;
+  for (size_t i = 0; i < count; ++i) {
+    d_srcs[i] = ctx->d_in + in_off[i];
+    d_dsts[i] = ctx->d_out + out_off[i];
+  }
+  AnyBatch R;
+  rc = any_batch_recover(ctx, count, d_srcs.data(), src_n, container, slot.data(), dst_n, nullptr, s, R);
+  if (!rc) rc = any_batch_decode(ctx, count, d_srcs.data(), src_n, container, d_dsts.data(), ctx->d_anyix, s, R);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  for (size_t i = 0; i < count; ++i) {
+    status[i] = R.st[i];
+    if (dst_n_out) dst_n_out[i] = R.out_n[i];
+    got[i] = status[i] == 0 ? R.out_n[i] : 0;
+  }
+  return stage_down(ctx, dsts, got.data(), out_off.data(), count, out_off[count], s);
 }
 
 int sfh_last_recover_stats(sfh_ctx* ctx, float ms[2], uint64_t counts[2]) {

@@ -316,6 +316,44 @@ hipError_t launch_any_single(const uint64_t* head, uint64_t* index, uint32_t* re
 // behind the token stage: depends[seg], and the strip rows of k_inflate_bytes (nseg slots, the unused ones empty)
 hipError_t launch_any_rows(const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends, uint32_t* starts,
                            uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows, hipStream_t s);
+// Many bodies in one call (sfh_recover_index_batch*, sfh_decompress_any_batch*): the scan runs one wave per 8 KiB of one item
+// (waves: the wave -> {item, piece} map, built by the host), the node list is the items' lists one after the other, each with
+// its own end sentinel, and the walk stays inside a node's item (range[item], written by launch_any_ranges).  heads: every
+// item's body [b0, e) (k_inflate_head's implied entries); index: flat, item i's nseg + 1 entries from items[i].ix0.
+struct AnyItem {
+  const uint8_t* src;
+  uint64_t src_n;
+  uint64_t ix0;            // its first entry in the flat index
+  uint32_t nseg;
+  uint32_t wave0, nwaves;  // its waves in the call (none: an item of one segment, which needs no walk)
+  uint32_t pad;
+};
+struct AnyWave {
+  uint32_t item, piece;    // the wave scans bytes [piece * 8192, +8192) of the item's stream
+};
+struct AnyRange {
+  uint32_t n0, n1, m0, m1; // the item's nodes [n0, n1) and its sentinel n1; its M nodes [m0, m1) of the M list
+};
+static_assert(sizeof(AnyItem) == 40 && sizeof(AnyWave) == 8 && sizeof(AnyRange) == 16, "recovery descriptor rows");
+hipError_t launch_any_count_batch(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves,
+                                  uint32_t* cnt_nodes, uint32_t* cnt_m, hipStream_t s);
+// after the scans of the counts (tot[0], tot[1]: their totals): range[], and *largest = the largest item's nodes (zeroed before)
+hipError_t launch_any_ranges(const AnyItem* items, uint32_t nitems, const uint32_t* node_off, const uint32_t* m_off, uint32_t nwaves,
+                             const uint32_t* tot, AnyRange* range, uint32_t* largest, hipStream_t s);
+hipError_t launch_any_nodes_batch(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves,
+                                  uint32_t* node_off, uint32_t* m_off, uint64_t* pos, uint8_t* flg, uint32_t* minc, uint32_t* midx,
+                                  uint32_t* item, hipStream_t s);
+// ntot >= 1 nodes, sentinels included: the flat index and ok[item] = the item's chain holds its nseg segments
+hipError_t launch_any_walk_batch(const AnyItem* items, const uint64_t* heads, const AnyRange* range, const uint32_t* item,
+                                 const uint64_t* pos, const uint8_t* flg, const uint32_t* minc, const uint32_t* midx, uint32_t ntot,
+                                 uint32_t largest, uint32_t* nxt_a, uint32_t* nxt_b, uint8_t* lab, uint8_t* mark, uint32_t* lbl,
+                                 uint32_t* rank, uint32_t* tmp, uint32_t* total, uint64_t* index, uint32_t* ok, hipStream_t s);
+hipError_t launch_any_single_batch(const AnyItem* items, uint32_t nitems, const uint64_t* heads, uint64_t* index, uint32_t* ok,
+                                   hipStream_t s);
+// launch_any_rows over a launch batch's segment table: an item's first segment (no history) always starts a row
+hipError_t launch_any_rows_batch(const InflateSeg* segs, const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends,
+                                 uint32_t* starts, uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows,
+                                 hipStream_t s);
 // recovered index (sfh_decompress_any*): the token kernels with the EXACT end rule for rows flagged kSegExact
 hipError_t launch_inflate_tokens_exact(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool speculate,
                                        hipStream_t s);

@@ -296,6 +296,199 @@ __global__ __launch_bounds__(KA_THREADS) void k_any_rows_b(const uint32_t* __res
   rows[r].nseg = k + 1 - rows[r].seg0;
 }
 
+// ---- many bodies in one call (sfh_recover_index_batch*, sfh_decompress_any_batch*) ----
+// The node list is the items' lists one after the other, each closed by its own end sentinel (kNodeS, at the body's end e: the
+// last wave of an item writes it); item[at] names a node's item, range[item] its nodes [n0, n1) (n1: the sentinel) and its M
+// nodes [m0, m1) in the concatenated lists.  An item of one segment has no waves and no nodes (k_any_single's rule).
+constexpr uint8_t kNodeS = 4;
+
+// one wave per 8 KiB of ONE item's stream (waves[wave] = {item, piece}): hits are tested against the item's own base and body,
+// so a pattern is never seen across two items that lie back to back
+template <bool WRITE>
+__global__ __launch_bounds__(KA_THREADS) void k_any_scan_batch(const AnyItem* __restrict__ items, const AnyWave* __restrict__ waves,
+                                                              const uint64_t* __restrict__ heads, uint32_t nwaves,
+                                                              uint32_t* __restrict__ cnt_nodes, uint32_t* __restrict__ cnt_m,
+                                                              uint64_t* __restrict__ pos, uint8_t* __restrict__ flg,
+                                                              uint32_t* __restrict__ minc, uint32_t* __restrict__ midx,
+                                                              uint32_t* __restrict__ item) {
+  const uint32_t wave = blockIdx.x * (KA_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (wave >= nwaves) return;
+  const AnyWave W = waves[wave];
+  const AnyItem I = items[W.item];
+  const uint8_t* src = I.src;
+  const uint64_t src_n = I.src_n, b0 = heads[2 * (size_t)W.item], e = heads[2 * (size_t)W.item + 1];
+  uint32_t nodes = WRITE ? cnt_nodes[wave] : 0u, ms = WRITE ? cnt_m[wave] : 0u;
+  const int64_t k0 = (int64_t)W.piece * (KA_WAVE_BYTES / 4);
+  for (uint32_t r = 0; r < KA_ROUNDS; ++r) {
+    const int64_t k = k0 + r * 64 + lane;
+    const uint32_t h = hits_at(src, src_n, b0, e, k);
+    if (__ballot(h != 0) == 0) continue;
+    const uint32_t pm = h & 15u, any = (h | (h >> 4) | (h >> 8)) & 15u;
+    const uint32_t n_incl = wave_incl_scan(__popc(any)), m_incl = wave_incl_scan(__popc(pm));
+    if constexpr (WRITE) {
+      uint32_t at = nodes + n_incl - __popc(any), mat = ms + m_incl - __popc(pm);
+      for (uint32_t j = 0; j < 4; ++j) {
+        if (!((any >> j) & 1u)) continue;
+        const bool is_m = (pm >> j) & 1u;
+        pos[at] = 4 * (uint64_t)k + j;
+        flg[at] = (is_m ? kNodeM : 0) | (((h >> (4 + j)) & 1u) ? kNodeH : 0);
+        item[at] = W.item;
+        if (is_m) midx[mat++] = at;
+        minc[at] = mat;  // M nodes (of the call) at or before this one
+        ++at;
+      }
+    }
+    nodes += (uint32_t)__shfl((int)n_incl, 63, 64);
+    ms += (uint32_t)__shfl((int)m_incl, 63, 64);
+  }
+  const bool last = W.piece + 1 == I.nwaves;  // the item's sentinel stands behind its last node
+  if (lane == 0) {
+    if constexpr (WRITE) {
+      if (last) {
+        pos[nodes] = e;
+        flg[nodes] = kNodeS;
+        item[nodes] = W.item;
+        minc[nodes] = ms;
+      }
+    } else {
+      cnt_nodes[wave] = nodes + (last ? 1u : 0u);
+      cnt_m[wave] = ms;
+    }
+  }
+}
+
+// per item, from the scanned counts: its node and M ranges; tot[5]: the largest item's nodes (the rounds of the jump)
+__global__ __launch_bounds__(KA_THREADS) void k_any_ranges(const AnyItem* __restrict__ items, uint32_t nitems,
+                                                          const uint32_t* __restrict__ node_off, const uint32_t* __restrict__ m_off,
+                                                          uint32_t nwaves, const uint32_t* __restrict__ tot,
+                                                          AnyRange* __restrict__ range, uint32_t* __restrict__ largest) {
+  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (i >= nitems) return;
+  const AnyItem I = items[i];
+  AnyRange R{0, 0, 0, 0};
+  if (I.nwaves) {
+    const uint32_t w1 = I.wave0 + I.nwaves;
+    R.n0 = node_off[I.wave0];
+    R.n1 = (w1 < nwaves ? node_off[w1] : tot[0]) - 1;
+    R.m0 = m_off[I.wave0];
+    R.m1 = w1 < nwaves ? m_off[w1] : tot[1];
+    atomicMax(largest, R.n1 - R.n0);
+  }
+  range[i] = R;
+}
+
+// k_any_succ over the concatenated list: the search and the M lists are confined to the node's item, its sentinel is a
+// self-loop and the mark starts at the item's first node
+__global__ __launch_bounds__(KA_THREADS) void k_any_succ_batch(const AnyItem* __restrict__ items, const uint64_t* __restrict__ heads,
+                                                              const AnyRange* __restrict__ range, const uint32_t* __restrict__ item,
+                                                              const uint64_t* __restrict__ pos, const uint8_t* __restrict__ flg,
+                                                              const uint32_t* __restrict__ minc, const uint32_t* __restrict__ midx,
+                                                              uint32_t ntot, uint32_t* __restrict__ nxt, uint8_t* __restrict__ lab,
+                                                              uint8_t* __restrict__ mark) {
+  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (i >= ntot) return;
+  const uint32_t it = item[i];
+  const AnyRange R = range[it];
+  if (i == R.n1) {
+    nxt[i] = i;  // the end of this item's body
+    lab[i] = 0;
+    mark[i] = 0;
+    return;
+  }
+  const uint8_t* src = items[it].src;
+  const uint64_t e = heads[2 * (size_t)it + 1];
+  const uint64_t* ipos = pos + R.n0;
+  const uint32_t n = R.n1 - R.n0;
+  uint32_t s = R.n1, l = 1;
+  if (flg[i] & kNodeH) {
+    const uint64_t t = landing(src, pos[i], e);
+    if (t < e) {
+      const uint32_t j = lower_bound(ipos, n, t);
+      if (j < n && ipos[j] == t) {
+        s = R.n0 + j;
+      } else {
+        const uint32_t mi = j < n ? minc[R.n0 + j] - (flg[R.n0 + j] & kNodeM) : R.m1;  // M nodes before j
+        s = mi < R.m1 ? midx[mi] : R.n1;
+        l = 2;
+      }
+    }
+  } else {
+    const uint32_t mi = minc[i];
+    s = mi < R.m1 ? midx[mi] : R.n1;
+  }
+  nxt[i] = s;
+  lab[i] = (uint8_t)l;
+  mark[i] = i == R.n0;
+}
+
+// rank: the exclusive scan of the labels over the whole list; a node's segment is its rank minus the rank of its item's first
+// node, and the rank at the sentinel closes the item's chain total: ok[item] = the chain holds the item's nseg segments.
+// index: flat, every item's nseg + 1 entries from its ix0 (sfh_copy_batch_index's layout)
+__global__ __launch_bounds__(KA_THREADS) void k_any_scatter_batch(const AnyItem* __restrict__ items, const uint64_t* __restrict__ heads,
+                                                                 const AnyRange* __restrict__ range, const uint32_t* __restrict__ item,
+                                                                 const uint64_t* __restrict__ pos, const uint8_t* __restrict__ lab,
+                                                                 const uint8_t* __restrict__ mark, const uint32_t* __restrict__ rank,
+                                                                 uint32_t ntot, uint64_t* __restrict__ index, uint32_t* __restrict__ ok) {
+  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (i >= ntot) return;
+  const uint32_t it = item[i];
+  const AnyRange R = range[it];
+  const AnyItem I = items[it];
+  const uint64_t e = heads[2 * (size_t)it + 1];
+  uint64_t* ix = index + I.ix0;
+  const uint32_t k = rank[i] - rank[R.n0];
+  if (i == R.n1) {
+    ix[I.nseg] = e;
+    ok[it] = k >= I.nseg ? 1u : 0u;
+    return;
+  }
+  if (!mark[i]) return;
+  if (k < I.nseg) ix[k] = pos[i];
+  if (lab[i] == 2 && k + 1 < I.nseg) ix[k + 1] = landing(I.src, pos[i], e);
+}
+
+// the items of one segment: index [b0, e], indexable (k_any_single's rule)
+__global__ __launch_bounds__(KA_THREADS) void k_any_single_batch(const AnyItem* __restrict__ items, uint32_t nitems,
+                                                                const uint64_t* __restrict__ heads, uint64_t* __restrict__ index,
+                                                                uint32_t* __restrict__ ok) {
+  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (i >= nitems || items[i].nwaves) return;
+  index[items[i].ix0] = heads[2 * (size_t)i];
+  index[items[i].ix0 + 1] = heads[2 * (size_t)i + 1];
+  ok[i] = 1;
+}
+
+// k_any_depends over a launch batch's segment table: an item's first segment (no history) always starts a row
+__global__ __launch_bounds__(64) void k_any_depends_batch(const InflateSeg* __restrict__ rows, const SegInfo* __restrict__ info,
+                                                         const uint32_t* __restrict__ tokens, uint8_t* __restrict__ depends,
+                                                         uint32_t* __restrict__ starts) {
+  const uint32_t seg = blockIdx.x, lane = threadIdx.x;
+  const SegInfo I = info[seg];
+  const bool first = (rows[seg].hist & ~(kSegWrapped | kSegExact)) == 0;
+  bool dep = false;
+  if (!first && I.status == inflate::kOk && !(I.raw & kSegRaw)) {
+    const uint32_t* tk = tokens + (uint64_t)seg * kChunk;
+    uint32_t out = 0;
+    for (uint32_t t0 = 0; t0 < I.ntok && !dep; t0 += 64) {
+      const uint32_t t = t0 + lane;
+      uint32_t len = 0, dist = 0;
+      if (t < I.ntok) {
+        const uint32_t tok = tk[t];
+        const bool m = (tok & inflate::kTokMatchBit) != 0;
+        len = m ? ((tok >> 16) & 0x7FFFu) + 3u : 1u;
+        dist = m ? (tok & 0xFFFFu) + 1u : 0u;
+      }
+      const uint32_t incl = wave_incl_scan(len);
+      dep = __ballot(dist > out + incl - len) != 0;  // (a literal has dist 0)
+      out += (uint32_t)__shfl((int)incl, 63, 64);
+    }
+  }
+  if (lane == 0) {
+    depends[seg] = dep ? 1 : 0;
+    starts[seg] = dep ? 0u : 1u;
+  }
+}
+
 inline uint32_t grid(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
 
 }  // namespace
@@ -354,6 +547,67 @@ hipError_t launch_any_single(const uint64_t* head, uint64_t* index, uint32_t* re
 hipError_t launch_any_rows(const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends, uint32_t* starts,
                            uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows, hipStream_t s) {
   hipLaunchKernelGGL(k_any_depends, dim3(nseg), dim3(64), 0, s, info, tokens, depends, starts);
+  hipError_t e = launch_scan_u32(starts, excl, nseg, tmp, nrows, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_any_rows_a, dim3(grid(nseg, KA_THREADS)), dim3(KA_THREADS), 0, s, starts, excl, nrows, nseg, rows);
+  hipLaunchKernelGGL(k_any_rows_b, dim3(grid(nseg, KA_THREADS)), dim3(KA_THREADS), 0, s, starts, excl, nseg, rows);
+  return hipGetLastError();
+}
+
+// ---- many bodies in one call ----
+
+hipError_t launch_any_count_batch(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves,
+                                  uint32_t* cnt_nodes, uint32_t* cnt_m, hipStream_t s) {
+  hipLaunchKernelGGL(k_any_scan_batch<false>, dim3(grid(nwaves, KA_THREADS / 64)), dim3(KA_THREADS), 0, s, items, waves, heads, nwaves,
+                     cnt_nodes, cnt_m, (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                     (uint32_t*)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_any_ranges(const AnyItem* items, uint32_t nitems, const uint32_t* node_off, const uint32_t* m_off, uint32_t nwaves,
+                             const uint32_t* tot, AnyRange* range, uint32_t* largest, hipStream_t s) {
+  hipLaunchKernelGGL(k_any_ranges, dim3(grid(nitems, KA_THREADS)), dim3(KA_THREADS), 0, s, items, nitems, node_off, m_off, nwaves, tot,
+                     range, largest);
+  return hipGetLastError();
+}
+
+hipError_t launch_any_nodes_batch(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves,
+                                  uint32_t* node_off, uint32_t* m_off, uint64_t* pos, uint8_t* flg, uint32_t* minc, uint32_t* midx,
+                                  uint32_t* item, hipStream_t s) {
+  hipLaunchKernelGGL(k_any_scan_batch<true>, dim3(grid(nwaves, KA_THREADS / 64)), dim3(KA_THREADS), 0, s, items, waves, heads, nwaves,
+                     node_off, m_off, pos, flg, minc, midx, item);
+  return hipGetLastError();
+}
+
+hipError_t launch_any_walk_batch(const AnyItem* items, const uint64_t* heads, const AnyRange* range, const uint32_t* item,
+                                 const uint64_t* pos, const uint8_t* flg, const uint32_t* minc, const uint32_t* midx, uint32_t ntot,
+                                 uint32_t largest, uint32_t* nxt_a, uint32_t* nxt_b, uint8_t* lab, uint8_t* mark, uint32_t* lbl,
+                                 uint32_t* rank, uint32_t* tmp, uint32_t* total, uint64_t* index, uint32_t* ok, hipStream_t s) {
+  hipLaunchKernelGGL(k_any_succ_batch, dim3(grid(ntot, KA_THREADS)), dim3(KA_THREADS), 0, s, items, heads, range, item, pos, flg, minc,
+                     midx, ntot, nxt_a, lab, mark);
+  // (the list's last node is a sentinel: k_any_jump's n.  A sentinel it marks carries the label 0.)
+  for (uint64_t reach = 1; reach < largest; reach <<= 1) {
+    hipLaunchKernelGGL(k_any_jump, dim3(grid(ntot, KA_THREADS)), dim3(KA_THREADS), 0, s, nxt_a, nxt_b, mark, ntot - 1);
+    std::swap(nxt_a, nxt_b);
+  }
+  hipLaunchKernelGGL(k_any_labels, dim3(grid(ntot, KA_THREADS)), dim3(KA_THREADS), 0, s, lab, mark, ntot, lbl);
+  hipError_t e = launch_scan_u32(lbl, rank, ntot, tmp, total, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_any_scatter_batch, dim3(grid(ntot, KA_THREADS)), dim3(KA_THREADS), 0, s, items, heads, range, item, pos, lab,
+                     mark, rank, ntot, index, ok);
+  return hipGetLastError();
+}
+
+hipError_t launch_any_single_batch(const AnyItem* items, uint32_t nitems, const uint64_t* heads, uint64_t* index, uint32_t* ok,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(k_any_single_batch, dim3(grid(nitems, KA_THREADS)), dim3(KA_THREADS), 0, s, items, nitems, heads, index, ok);
+  return hipGetLastError();
+}
+
+hipError_t launch_any_rows_batch(const InflateSeg* segs, const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends,
+                                 uint32_t* starts, uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows,
+                                 hipStream_t s) {
+  hipLaunchKernelGGL(k_any_depends_batch, dim3(nseg), dim3(64), 0, s, segs, info, tokens, depends, starts);
   hipError_t e = launch_scan_u32(starts, excl, nseg, tmp, nrows, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_any_rows_a, dim3(grid(nseg, KA_THREADS)), dim3(KA_THREADS), 0, s, starts, excl, nrows, nseg, rows);
