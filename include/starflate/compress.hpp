@@ -60,7 +60,9 @@ struct compress_options {
   bool final_stream{true};  // false: byte-aligned, non-final stream (a shard that is not the last)
   std::uint8_t lazy{3};     // 0..3 positions of look-ahead of the lazy match rule (sfh_options.lazy)
   bool stored_fast_path{true};  // skip the search of a chunk whose first 8 KiB are (almost) all literals
-  Container container{Container::Raw};  // Zlib / Gzip: wrapper + GPU-computed Adler-32 / CRC-32 (needs final_stream)
+  Container container{Container::Raw};  // Zlib / Gzip: wrapper + GPU-computed Adler-32 / CRC-32 (needs final_stream);
+                                        // Dictzip: Gzip with the random-access table in its header (block_bytes 0 or 32768,
+                                        // at most SFH_DZ_MAX_CHUNKS * 32768 bytes; compressor::compress and compress_device* only)
   int device{0};
   Effort effort{Effort::Default};  // sfh_options.effort
   std::uint8_t chain_depth{0};     // sfh_options.chain_depth: with Best / Ultra / Extreme, candidates per position (0: 8 / 16 / 32)
@@ -69,6 +71,10 @@ struct compress_options {
 };
 
 inline auto compress_bound(std::size_t n, std::uint32_t block_bytes = 0) -> std::size_t { return sfh_compress_bound(n, block_bytes); }
+/// ... for a container: Container::Dictzip's header carries two bytes per 32 KiB of input (0: what the call would refuse)
+inline auto compress_bound(std::size_t n, std::uint32_t block_bytes, Container container) -> std::size_t {
+  return sfh_compress_bound_container(n, block_bytes, static_cast<std::uint32_t>(container));
+}
 
 /// What makes a stream of this library decodable in parallel (on the GPU): the first stream byte of every
 /// 32 KiB segment plus the end of the last one, the strip size (no match reaches before its strip), and
@@ -108,6 +114,8 @@ inline auto to_status(int rc) -> CompressStatus {
     default: return CompressStatus::InvalidArgument;
   }
 }
+/// what the decoders' `container` argument takes: to them a dictzip file is a gzip stream
+inline auto to_c(Container c) -> std::uint32_t { return c == Container::Dictzip ? SFH_GZIP : static_cast<std::uint32_t>(c); }
 inline auto to_c(const compress_options& o) -> sfh_options {
   sfh_options c;
   sfh_default_options(&c);
@@ -122,6 +130,22 @@ inline auto to_c(const compress_options& o) -> sfh_options {
   return c;
 }
 }  // namespace detail
+
+/// The index a dictzip file of 32 KiB chunks carries in its own header (sfh_dz_read_index: host arithmetic, no device):
+/// offsets, block_bytes 32768 and total_bytes (ISIZE), what compressor::decompress_range[s] and decompress() take.  A gzip file
+/// without such a table is CompressStatus::NotIndexable, a header that does not parse InvalidArgument.
+inline auto dz_read_index(std::span<const std::byte> src) -> compat::expected<stream_index, CompressStatus> {
+  stream_index ix;
+  ix.offsets.resize(static_cast<std::size_t>(SFH_DZ_MAX_CHUNKS) + 1);
+  sfh_dz_info info{};
+  const int rc = sfh_dz_read_index(src.data(), src.size(), &info, ix.offsets.data(), ix.offsets.size());
+  if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+  if (info.status != 0) return compat::unexpected{CompressStatus::InvalidArgument};
+  ix.offsets.resize(static_cast<std::size_t>(info.nseg) + 1);
+  ix.block_bytes = SFH_SEGMENT_BYTES;
+  ix.total_bytes = info.total_n;
+  return ix;
+}
 
 /// One GPU context (device scratch, stream).  Not thread-safe; distinct objects are independent.
 class compressor {
@@ -229,7 +253,7 @@ class compressor {
     }
     const int rc = sfh_decompress_batch(ctx_, k, sp.data(), n.data(), ix ? ix->offsets.data() : nullptr,
                                         (ix && !ix->regions.empty()) ? ix->regions.data() : nullptr, dp.data(), dn.data(),
-                                        ix ? ix->block_bytes.data() : nullptr, static_cast<std::uint32_t>(container), st.data());
+                                        ix ? ix->block_bytes.data() : nullptr, detail::to_c(container), st.data());
     if (rc != SFH_OK) return detail::to_status(rc);
     for (std::size_t i = 0; i < k; ++i) statuses[i] = st[i] > 7 ? DecompressStatus::Error : static_cast<DecompressStatus>(st[i]);
     return CompressStatus::Success;
@@ -300,6 +324,39 @@ class compressor {
     for (std::size_t i = 0; i < k; ++i) statuses[i] = st[i] > 7 ? DecompressStatus::Error : static_cast<DecompressStatus>(st[i]);
     return CompressStatus::Success;
   }
+  /// A file written with Container::Dictzip (or any dictzip file of 32 KiB chunks) decoded with the index its own header
+  /// carries (sfh_decompress_dz): the header, ISIZE and the CRC-32 are verified.  dst.size() >= ISIZE; *produced (nullable) =
+  /// ISIZE on Success.  A file without such a table is decoded by decompress(src, dst, Container::Gzip), and so is whatever
+  /// the GPU does not report Success for: the caller always gets the reference's answer.
+  auto decompress_dz(std::span<const std::byte> src, std::span<std::byte> dst, std::size_t* produced = nullptr) -> DecompressStatus {
+    if (ctx_) {
+      std::uint32_t st = 0;
+      std::uint64_t n = 0;
+      const int rc = sfh_decompress_dz(ctx_, src.data(), src.size(), dst.data(), dst.size(), &n, &st);
+      if (rc == SFH_OK && st == 0) {
+        if (produced != nullptr) *produced = static_cast<std::size_t>(n);
+        return DecompressStatus::Success;
+      }
+    }
+    const auto st = decompress(src, dst, Container::Gzip);
+    if (st == DecompressStatus::Success && produced != nullptr && src.size() >= 18) {
+      const auto tr = src.last(4);
+      *produced = detail::u8(tr[0]) | (detail::u8(tr[1]) << 8U) | (detail::u8(tr[2]) << 16U) | (detail::u8(tr[3]) << 24U);
+    }
+    return st;
+  }
+  /// Random access into such a file, given nothing but its bytes: output bytes [offset, offset + part.size()) into `part`
+  /// (sfh_decompress_dz_ranges: the header is read on the host, only the chunks holding the range are uploaded and decoded;
+  /// no checksum is verified).  A file without a table of 32 KiB chunks, a refused call or a device problem is Error.
+  auto decompress_dz_range(std::span<const std::byte> src, std::span<std::byte> part, std::uint64_t offset) -> DecompressStatus {
+    if (!ctx_) return DecompressStatus::Error;
+    void* dp[1] = {part.data()};
+    const std::uint64_t len = part.size();
+    std::uint32_t st = 0;
+    const int rc = sfh_decompress_dz_ranges(ctx_, src.data(), src.size(), 1, &offset, &len, dp, &st);
+    if (rc != SFH_OK || st > 7) return DecompressStatus::Error;
+    return static_cast<DecompressStatus>(st);
+  }
   /// The index of a stream given alone, recovered on the GPU from its flush markers: offsets of its
   /// max(1, ceil(dst_size / 32768)) segments + 1; block_bytes 0 (unknown), no regions.  A stream that is not block-flushed
   /// every 32 KiB is CompressStatus::NotIndexable.
@@ -311,7 +368,7 @@ class compressor {
     ix.offsets.resize(nseg + 1);
     ix.block_bytes = 0;
     ix.total_bytes = dst_size;
-    const int rc = sfh_recover_index(ctx_, src.data(), src.size(), static_cast<std::uint32_t>(container), dst_size,
+    const int rc = sfh_recover_index(ctx_, src.data(), src.size(), detail::to_c(container), dst_size,
                                      ix.offsets.data(), nseg, nullptr);
     if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
     return ix;
@@ -322,7 +379,7 @@ class compressor {
   auto decompress(std::span<const std::byte> src, std::span<std::byte> dst, Container container) -> DecompressStatus {
     if (ctx_) {
       std::uint32_t st = 0;
-      const int rc = sfh_decompress_any(ctx_, src.data(), src.size(), static_cast<std::uint32_t>(container), dst.data(), dst.size(),
+      const int rc = sfh_decompress_any(ctx_, src.data(), src.size(), detail::to_c(container), dst.data(), dst.size(),
                                         dst.size(), nullptr, &st);
       if (rc == SFH_OK && st == 0) return DecompressStatus::Success;
     }
@@ -347,7 +404,7 @@ class compressor {
         dp[i] = dsts[i].data();
         dn[i] = dsts[i].size();
       }
-      if (sfh_decompress_any_batch(ctx_, k, sp.data(), n.data(), static_cast<std::uint32_t>(container), dp.data(), dn.data(), dn.data(),
+      if (sfh_decompress_any_batch(ctx_, k, sp.data(), n.data(), detail::to_c(container), dp.data(), dn.data(), dn.data(),
                                    nullptr, st.data()) != SFH_OK)
         st.assign(k, 1U);
     }
@@ -377,7 +434,7 @@ class compressor {
       ix.first[i + 1] = ix.first[i] + (dst_sizes[i] ? (dst_sizes[i] + SFH_SEGMENT_BYTES - 1) / SFH_SEGMENT_BYTES : 1) + 1;
     }
     ix.offsets.resize(ix.first[k]);
-    const int rc = sfh_recover_index_batch(ctx_, k, sp.data(), n.data(), static_cast<std::uint32_t>(container), dn.data(),
+    const int rc = sfh_recover_index_batch(ctx_, k, sp.data(), n.data(), detail::to_c(container), dn.data(),
                                            ix.offsets.data(), st.data());
     if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
     if (indexable != nullptr) {
@@ -400,7 +457,7 @@ class compressor {
     // (an empty dst still decodes: the size query is the C interface's, with a null dst)
     std::byte dummy{};
     void* d = dst.empty() ? static_cast<void*>(&dummy) : static_cast<void*>(dst.data());
-    const int rc = sfh_inflate_stream(ctx_, src.data(), src.size(), static_cast<std::uint32_t>(container), d, dst.size(), &n, &st);
+    const int rc = sfh_inflate_stream(ctx_, src.data(), src.size(), detail::to_c(container), d, dst.size(), &n, &st);
     if (rc != SFH_OK || st > 7) return DecompressStatus::Error;
     if (produced) *produced = static_cast<std::size_t>(n);
     return static_cast<DecompressStatus>(st);
@@ -430,7 +487,7 @@ class compressor {
       dp[i] = dsts[i].empty() ? static_cast<void*>(&dummy) : static_cast<void*>(dsts[i].data());
       cap[i] = dsts[i].size();
     }
-    const int rc = sfh_inflate_stream_batch(ctx_, k, sp.data(), n.data(), static_cast<std::uint32_t>(container), dp.data(), cap.data(),
+    const int rc = sfh_inflate_stream_batch(ctx_, k, sp.data(), n.data(), detail::to_c(container), dp.data(), cap.data(),
                                             out.data(), st.data());
     if (rc == SFH_E_INVALID_ARG) return CompressStatus::InvalidArgument;
     for (std::size_t i = 0; i < k; ++i) {

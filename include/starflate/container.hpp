@@ -17,6 +17,8 @@ enum class Container : std::uint8_t {
   Raw,   // RFC 1951 only (what the reference reads)
   Zlib,  // 78 9C .. Adler-32 (big-endian)
   Gzip,  // 1F 8B 08 .. CRC-32, ISIZE (little-endian)
+  Dictzip,  // Gzip at block_bytes 32768 whose FEXTRA field carries dictzip's table of chunk sizes (SFH_DICTZIP): what
+            // compress() writes on request; to every decoder it is the Gzip case
 };
 
 namespace detail {
@@ -75,7 +77,8 @@ inline auto decompress(std::span<const std::byte> src, std::span<std::byte> dst,
       const std::uint32_t want = (u8(tr[0]) << 24U) | (u8(tr[1]) << 16U) | (u8(tr[2]) << 8U) | u8(tr[3]);
       return adler32(dst) == want ? DecompressStatus::Success : DecompressStatus::Error;
     }
-    case Container::Gzip: {
+    case Container::Gzip:
+    case Container::Dictzip: {
       if (src.size() < 18) return DecompressStatus::SrcTooSmall;
       if (u8(src[0]) != 0x1F || u8(src[1]) != 0x8B || u8(src[2]) != 8) return DecompressStatus::Error;
       const std::uint32_t flg = u8(src[3]);

@@ -40,7 +40,8 @@ enum sfh_status {
   SFH_E_COMM = -6,          /* RCCL not loadable, or an RCCL call failed; see sfh_last_error() */
   SFH_E_UNSUPPORTED = -7,   /* the effort asked for rests on LDS behaviour this device does not show (sfh_lds_order_check) */
   SFH_E_NOT_INDEXABLE = -8  /* sfh_recover_index* / sfh_decompress_any*: the stream is not block-flushed every 32 KiB of
-                               output (the walk of DESIGN.md 3a ends before it found every segment); nothing was decoded */
+                               output (the walk of DESIGN.md 3a ends before it found every segment); nothing was decoded.
+                               sfh_dz_read_index* / sfh_decompress_dz*: the gzip header carries no dictzip table of 32 KiB chunks */
 };
 
 /* block strategy (inverse of src/decompress.cpp:416-458 dispatch) */
@@ -55,7 +56,13 @@ enum sfh_strategy {
 enum sfh_container {
   SFH_RAW = 0,  /* RFC 1951 only: what the reference's decompress() reads */
   SFH_ZLIB = 1, /* RFC 1950: 78 9C, stream, Adler-32 big-endian */
-  SFH_GZIP = 2  /* RFC 1952: 1F 8B 08 00, MTIME 0, XFL 0, OS 255, stream, CRC-32, ISIZE (both little-endian) */
+  SFH_GZIP = 2, /* RFC 1952: 1F 8B 08 00, MTIME 0, XFL 0, OS 255, stream, CRC-32, ISIZE (both little-endian) */
+  SFH_DICTZIP = 3 /* SFH_GZIP at block_bytes = 32768 whose header carries dictzip(1)'s random-access table (FLG = FEXTRA, an
+                     'RA' subfield: VER 1, CHLEN 32768, CHCNT, the compressed bytes of every 32 KiB chunk; "Seekable gzip" below).
+                     In sfh_options.container of sfh_compress, sfh_compress_device and sfh_compress_device_async ONLY: the
+                     batched calls, sfh_compress_multi and the gathered multi-process path refuse it (SFH_E_INVALID_ARG; out of
+                     scope so far), and so does every decoder's `container` argument -- to a decoder such a file is an SFH_GZIP
+                     stream (FEXTRA is skipped); sfh_dz_read_index* / sfh_decompress_dz* read the table */
 };
 
 typedef struct sfh_options {
@@ -72,8 +79,10 @@ typedef struct sfh_options {
                             entropy within 64 bytes of 8 KiB) is stored outright, its other 24 KiB never fetched by the
                             match kernel (round 6);
                             1: always search the whole chunk */
-  uint32_t container;    /* enum sfh_container; SFH_ZLIB / SFH_GZIP need final_stream = 1.  The checksum is
-                            computed on the GPU from the same device buffer (two more launches) */
+  uint32_t container;    /* enum sfh_container; SFH_ZLIB / SFH_GZIP / SFH_DICTZIP need final_stream = 1.  The checksum is
+                            computed on the GPU from the same device buffer (two more launches).  SFH_DICTZIP: block_bytes
+                            must be 0 or 32768 (0 is 32768 then, whatever n is: the table promises independent chunks) and
+                            n <= SFH_DZ_MAX_CHUNKS * 32768, else SFH_E_INVALID_ARG before anything is enqueued */
   uint32_t block_bytes;  /* bytes of input coded independently of what precedes them (a "strip"): a multiple of
                             32768 up to 16 MiB; 0 (default) = SFH_DEFAULT_BLOCK_BYTES, more (SFH_LARGE_BLOCK_BYTES,
                             SFH_CHAIN_BLOCK_BYTES with the chain efforts) for inputs of half a GiB and up, less for inputs
@@ -165,6 +174,24 @@ const char* sfh_last_error(const sfh_ctx* ctx);
  * valid block_bytes gives the same figure; a block_bytes the compress calls reject (not a multiple of 32768, or above
  * 16 MiB) returns 0. */
 size_t sfh_compress_bound(size_t n, uint32_t block_bytes);
+
+/* ---- Seekable gzip: the dictzip random-access table (SFH_DICTZIP) ----
+ *   1F 8B 08 04  00 00 00 00  00 FF        the gzip header SFH_GZIP writes, FLG = FEXTRA
+ *   XLEN (u16) = 10 + 2 * nseg | 'R' 'A' | LEN (u16) = 6 + 2 * nseg | VER (u16) = 1 | CHLEN (u16) = 32768 | CHCNT (u16) = nseg
+ *   nseg x u16: compressed bytes of segment i (= index[i + 1] - index[i]; the last one reaches to the trailer and holds BFINAL)
+ *   the raw DEFLATE body, CRC-32, ISIZE: byte for byte what SFH_GZIP writes at block_bytes = 32768 with the same options
+ * (all little-endian; nseg = max(1, ceil(n / 32768))).  Every gzip reader inflates the file, dictzip readers seek in it, and
+ * sfh_dz_read_index* turns the table back into the segment index of sfh_decompress_ranges*.  XLEN is 16 bits wide, so nseg <=
+ * SFH_DZ_MAX_CHUNKS and n <= SFH_DZ_MAX_CHUNKS * 32768 = 1,073,545,216 bytes: the format's limit.  After such a compress call
+ * the index, the sub-index and sfh_last_block_bytes() (32768) are as after any other; index[0] is this header's end.
+ *
+ * sfh_dz_header_bytes: 22 + 2 * nseg for n input bytes, 0 above the limit.
+ * sfh_compress_bound_container: the capacity a compress call with `container` needs: for SFH_DICTZIP sfh_compress_bound(n, 32768)
+ * + sfh_dz_header_bytes(n) - 10 (the bound counts the gzip header), and 0 for a block_bytes the call would refuse (anything but 0
+ * and 32768) or an n above the limit; for the other containers sfh_compress_bound(n, block_bytes); 0 for an unknown container. */
+#define SFH_DZ_MAX_CHUNKS 32762u
+size_t sfh_dz_header_bytes(size_t n);
+size_t sfh_compress_bound_container(size_t n, uint32_t block_bytes, uint32_t container);
 
 /* Host buffers, synchronous.  *out_n = stream bytes.  Inside the call the input goes up, through the kernels and the
  * stream comes down in 64 MiB batches on three streams, so with pinned buffers the call takes about as long as the
@@ -402,6 +429,45 @@ int sfh_decompress_range_device(sfh_ctx* ctx, const void* d_src, size_t src_n, c
 int sfh_decompress_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uint64_t* index, const uint32_t* subindex,
                           size_t nseg, uint64_t total_n, uint32_t block_bytes, size_t count, const uint64_t* offsets,
                           const uint64_t* lengths, void* const* dsts, uint32_t* status);
+
+/* ---- reading a dictzip table: the index from the file's own header, no side information and no scan ----
+ * The gzip header of `src` is parsed (magic, CM; the FEXTRA subfields up to 'RA', others may stand before and behind it; FNAME,
+ * FCOMMENT and FHCRC skipped; no read beyond src_n) and the table's sizes are summed into the index: index[0] = the header's
+ * end, index[i + 1] = index[i] + size[i], index[nseg] = src_n - 8, the trailer's first byte -- so the last segment takes in
+ * what lies between the table's end and the trailer (dictzip(1) leaves its empty final block there).  info->total_n = ISIZE,
+ * info->nseg = max(1, CHCNT), info->header_bytes = index[0].
+ * SFH_E_NOT_INDEXABLE, nothing written: no FEXTRA, no 'RA' subfield, VER != 1, or CHLEN != 32768 (the indexed decoder's segments
+ *   are 32 KiB: files of dictzip's own default chunk length go to sfh_inflate_stream*).
+ * SFH_OK with info->status = 5 (SrcTooSmall): a stream too short for its header and trailer (below 18 bytes, or a file name,
+ *   comment or header CRC that does not end in front of the trailer).
+ * SFH_OK with info->status = 1 (Error): bad magic or CM, XLEN or a subfield overrunning, LEN != 6 + 2 * CHCNT, CHCNT != max(1,
+ *   ceil(ISIZE / 32768)) (CHCNT == 0 with ISIZE == 0 reads as one empty segment), the sizes' sum reaching past src_n - 8.
+ *   With a non-zero status the other fields are 0 and the index is not written.
+ * SFH_E_DST_TOO_SMALL: index_cap < nseg + 1 (SFH_DZ_MAX_CHUNKS + 1 entries always suffice); SFH_E_INVALID_ARG: a null pointer.
+ * sfh_dz_read_index: host bytes, no context, no device: arithmetic on the header.
+ * sfh_dz_read_index_device: device bytes (d_src 4-byte, d_index 8-byte aligned), one workgroup (k_dz_index), then one read-back
+ *   of the info: one synchronisation of `stream` (NULL = the ctx's own). */
+typedef struct sfh_dz_info {
+  uint64_t total_n;
+  uint32_t nseg, header_bytes, status, reserved;
+} sfh_dz_info;
+int sfh_dz_read_index(const void* src, size_t src_n, sfh_dz_info* info, uint64_t* index, size_t index_cap);
+int sfh_dz_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sfh_dz_info* info, uint64_t* d_index,
+                             size_t index_cap, void* stream);
+/* A dictzip file decoded with its own table: the index is read (as above), then the file runs as one SFH_GZIP item of
+ * sfh_decompress_batch* with that index and block_bytes = 32768 -- the wrapper, ISIZE and the CRC-32 are verified exactly as
+ * there.  *dst_n_out = ISIZE; ISIZE > dst_cap is SFH_E_DST_TOO_SMALL; a table that does not parse gives its status (1 or 5) in
+ * *status with nothing decoded; SFH_E_NOT_INDEXABLE as above, nothing decoded.  d_src 4-byte, d_dst 16-byte aligned;
+ * synchronises `stream`.  sfh_decompress_dz: host buffers (H2D, the same, D2H of dst when *status is 0).
+ * sfh_decompress_dz_ranges: host buffers; the header is read on the host, then sfh_decompress_ranges runs with that index: only
+ * the decode spans' bytes are uploaded.  A table that does not parse gives every range its status.  For a file on the device:
+ * sfh_dz_read_index_device, then sfh_decompress_ranges_device_async. */
+int sfh_decompress_dz_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                             uint32_t* status, void* stream);
+int sfh_decompress_dz(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                      uint32_t* status);
+int sfh_decompress_dz_ranges(sfh_ctx* ctx, const void* src, size_t src_n, size_t count, const uint64_t* offsets,
+                             const uint64_t* lengths, void* const* dsts, uint32_t* status);
 
 /* ---- decoding without side information ----
  * The segment index of a stream that is flushed every 32 KiB of output -- every stream sfh_compress* writes, and zlib's with

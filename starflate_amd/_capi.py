@@ -12,7 +12,9 @@ NSTAGES = 5
 INFLATE_NSTAGES = 2
 SEGMENT_BYTES = 32768
 STRATEGY = {"auto": 0, "stored": 1, "fixed": 2, "dynamic": 3}
-CONTAINER = {"raw": 0, "zlib": 1, "gzip": 2}
+CONTAINER = {"raw": 0, "zlib": 1, "gzip": 2}  # what the decoders take (to them a dictzip file is a gzip stream)
+COMPRESS_CONTAINER = dict(CONTAINER, dictzip=3)  # ... and the single-stream compress calls: SFH_DICTZIP
+DZ_MAX_CHUNKS = 32762  # SFH_DZ_MAX_CHUNKS
 E_NOT_INDEXABLE = -8  # SFH_E_NOT_INDEXABLE
 SIZE_FROM_TRAILER = (1 << 64) - 1  # SFH_SIZE_FROM_TRAILER
 ITEM_NOT_INDEXABLE = 0xFFFFFFF8  # SFH_ITEM_NOT_INDEXABLE: a per-item status of the sfh_*_any_batch* calls
@@ -28,10 +30,11 @@ SUBINDEX_WORDS = 64
 # every symbol include/starflate_hip.h declares
 EXPORTS = [
     "sfh_default_options", "sfh_device_count", "sfh_get_device_props", "sfh_create", "sfh_destroy", "sfh_last_error",
-    "sfh_compress_bound", "sfh_compress", "sfh_compress_multi", "sfh_compress_device", "sfh_compress_device_async",
+    "sfh_compress_bound", "sfh_compress_bound_container", "sfh_dz_header_bytes", "sfh_compress", "sfh_compress_multi", "sfh_compress_device", "sfh_compress_device_async",
     "sfh_compress_batch_device_async", "sfh_compress_batch", "sfh_batch_index_size", "sfh_copy_batch_index",
     "sfh_decompress_batch_device_async", "sfh_decompress_batch",
     "sfh_decompress_ranges_device_async", "sfh_decompress_range_device", "sfh_decompress_ranges",
+    "sfh_dz_read_index", "sfh_dz_read_index_device", "sfh_decompress_dz_device", "sfh_decompress_dz", "sfh_decompress_dz_ranges",
     "sfh_recover_index_device", "sfh_recover_index", "sfh_decompress_any_device", "sfh_decompress_any", "sfh_last_recover_stats",
     "sfh_recover_index_batch_device", "sfh_recover_index_batch", "sfh_decompress_any_batch_device", "sfh_decompress_any_batch",
     "sfh_inflate_stream_device", "sfh_inflate_stream", "sfh_inflate_stream_batch_device", "sfh_inflate_stream_batch",
@@ -47,6 +50,11 @@ class Options(C.Structure):
     _fields_ = [("strategy", C.c_uint32), ("final_stream", C.c_uint32), ("lazy", C.c_uint32),
                 ("no_stored_fast_path", C.c_uint32), ("container", C.c_uint32), ("block_bytes", C.c_uint32),
                 ("effort", C.c_uint32), ("chain_depth", C.c_uint32)]
+
+
+class DzInfo(C.Structure):  # sfh_dz_info
+    _fields_ = [("total_n", C.c_uint64), ("nseg", C.c_uint32), ("header_bytes", C.c_uint32), ("status", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class DeviceProps(C.Structure):
@@ -92,6 +100,20 @@ def lib():
     L.sfh_last_error.restype = C.c_char_p
     L.sfh_compress_bound.argtypes = [sz, C.c_uint32]
     L.sfh_compress_bound.restype = sz
+    L.sfh_compress_bound_container.argtypes = [sz, C.c_uint32, C.c_uint32]
+    L.sfh_compress_bound_container.restype = sz
+    L.sfh_dz_header_bytes.argtypes = [sz]
+    L.sfh_dz_header_bytes.restype = sz
+    L.sfh_dz_read_index.argtypes = [vp, sz, C.POINTER(DzInfo), vp, sz]
+    L.sfh_dz_read_index.restype = C.c_int
+    L.sfh_dz_read_index_device.argtypes = [vp, vp, sz, C.POINTER(DzInfo), vp, sz, vp]
+    L.sfh_dz_read_index_device.restype = C.c_int
+    L.sfh_decompress_dz_device.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), vp]
+    L.sfh_decompress_dz_device.restype = C.c_int
+    L.sfh_decompress_dz.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    L.sfh_decompress_dz.restype = C.c_int
+    L.sfh_decompress_dz_ranges.argtypes = [vp, vp, sz, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(vp), vp]
+    L.sfh_decompress_dz_ranges.restype = C.c_int
     L.sfh_compress.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]
     L.sfh_compress.restype = C.c_int
     L.sfh_compress_multi.argtypes = [C.POINTER(vp), C.c_int, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]
@@ -214,7 +236,7 @@ def make_options(strategy="auto", final_stream=True, lazy=True, stored_fast_path
     o.final_stream = int(bool(final_stream))
     o.lazy = 3 if lazy is True else int(lazy)
     o.no_stored_fast_path = int(not stored_fast_path)
-    o.container = CONTAINER[container] if isinstance(container, str) else int(container)
+    o.container = COMPRESS_CONTAINER[container] if isinstance(container, str) else int(container)
     o.block_bytes = int(block_bytes)
     if isinstance(effort, str) and effort.startswith("chain"):  # "chain4": exact hash chains of that depth
         o.effort, o.chain_depth = EFFORT["best"], int(effort[5:].lstrip(":") or 8)

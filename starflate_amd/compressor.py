@@ -53,11 +53,22 @@ class Compressor:
     def compress_bound(n):
         return _capi.lib().sfh_compress_bound(int(n), 0)
 
+    @staticmethod
+    def _bound(n, container, block_bytes):
+        """capacity of a single-stream compress call: container="dictzip" carries its table on top of compress_bound(n)
+        (ValueError for what that container refuses: a block_bytes other than 0 and 32768, an input above 32762 * 32768 bytes)"""
+        if container not in ("dictzip", _capi.COMPRESS_CONTAINER["dictzip"]):
+            return Compressor.compress_bound(n)
+        cap = _capi.lib().sfh_compress_bound_container(int(n), int(block_bytes), _capi.COMPRESS_CONTAINER["dictzip"])
+        if not cap:
+            raise ValueError('container="dictzip": block_bytes must be 0 or 32768 and the input at most 32762 * 32768 bytes')
+        return cap
+
     # ---- host buffers (PCIe inclusive) ----
     def compress(self, data, strategy="auto", final_stream=True, lazy=True, stored_fast_path=True, container="raw",
                  block_bytes=0, effort="default"):
         src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
-        cap = self.compress_bound(src.size)
+        cap = self._bound(src.size, container, block_bytes)
         dst = np.empty(cap, dtype=np.uint8)
         out_n = C.c_size_t(0)
         opt = _capi.make_options(strategy, final_stream, lazy, stored_fast_path, container, block_bytes, effort)
@@ -73,7 +84,7 @@ class Compressor:
 
         self._check_tensor(src)
         n = src.numel()
-        cap = self.compress_bound(n)
+        cap = self._bound(n, container, block_bytes)
         if out is None:
             out = torch.empty(cap, dtype=torch.uint8, device=src.device)
         self._check_tensor(out)
@@ -629,6 +640,39 @@ class Compressor:
             C.c_void_p(status.data_ptr()), C.c_void_p(s)))
         return outs, status[:k]
 
+    # ---- seekable gzip: files written with container="dictzip", read with nothing but their bytes (sfh_decompress_dz*) ----
+    def decompress_dictzip(self, data):
+        """Host buffers: a dictzip file of 32 KiB chunks -> (bytes, DecompressStatus int), decoded with the index its own header
+        carries; header, ISIZE and CRC-32 are verified.  b"" when the status is not 0.  A gzip file without such a table raises
+        StarflateError with code -8 (SFH_E_NOT_INDEXABLE)."""
+        src = _as_bytes(data)
+        try:
+            _, cap = dictzip_index(src)  # the header first: the output is sized from an ISIZE that agrees with the table
+        except StarflateError as e:
+            if e.code < 0:
+                raise
+            return b"", e.code
+        dst = np.empty(max(cap, 1), dtype=np.uint8)
+        got, st = C.c_uint64(0), C.c_uint32(0)
+        self._check(self._lib.sfh_decompress_dz(self._h, src.ctypes.data, src.size, dst.ctypes.data, cap, C.byref(got), C.byref(st)))
+        return (dst[: got.value].tobytes() if st.value == 0 else b""), int(st.value)
+
+    def read_ranges(self, data, offsets, lengths):
+        """Host buffers: byte ranges of what a dictzip file of 32 KiB chunks holds, given nothing but the file -> (list of bytes,
+        None where a range's status is not 0; uint32 status array).  The header is read on the host; of the file only the
+        chunks that hold the ranges travel to the device (decompress_ranges).  No checksum is verified (a range cannot
+        verify one)."""
+        return self._read_ranges(*_dz_range_args(data, offsets, lengths))
+
+    def _read_ranges(self, src, offs, lens):
+        k = len(offs)
+        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in lens]
+        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
+        st = np.zeros(max(k, 1), dtype=np.uint32)
+        self._check(self._lib.sfh_decompress_dz_ranges(self._h, src.ctypes.data, src.size, k, (C.c_uint64 * k)(*offs),
+                                                       (C.c_uint64 * k)(*lens), dp, st.ctypes.data))
+        return [dsts[i][: lens[i]].tobytes() if st[i] == 0 else None for i in range(k)], st[:k]
+
     def inflate_ms(self):
         ms = (C.c_float * _capi.INFLATE_NSTAGES)()
         self._check(self._lib.sfh_last_inflate_ms(self._h, C.byref(ms)))
@@ -983,3 +1027,60 @@ def decompress_ranges(data, index, total_n, offsets, lengths, subindex=None, *, 
     if c is None:
         c = _DEFAULT[device] = Compressor(device)
     return c.decompress_ranges(data, index, total_n, offsets, lengths, subindex, block_bytes=block_bytes)
+
+
+def dictzip_index(data):
+    """The segment index a dictzip file of 32 KiB chunks carries in its own gzip header -> (uint64 array of segments + 1
+    offsets into the file, total_n): what decompress_ranges takes, with block_bytes=32768.  Host arithmetic on the header, no
+    device.  A gzip file without such a table raises StarflateError with code -8 (SFH_E_NOT_INDEXABLE), a header that does not
+    parse with its DecompressStatus (1 Error, 5 SrcTooSmall)."""
+    src = _as_bytes(data)
+    index = np.zeros(_capi.DZ_MAX_CHUNKS + 1, dtype=np.uint64)
+    info = _capi.DzInfo()
+    rc = _capi.lib().sfh_dz_read_index(src.ctypes.data if src.size else None, src.size, C.byref(info), index.ctypes.data, index.size)
+    if rc:
+        raise StarflateError(rc, "no dictzip table of 32 KiB chunks in the gzip header")
+    if info.status:
+        raise StarflateError(info.status, f"dictzip header: DecompressStatus {info.status}")
+    return index[: info.nseg + 1].copy(), int(info.total_n)
+
+
+def decompress_dictzip(data, device=0):
+    """A dictzip file -> bytes, on the GPU, decoded with the index its header carries (Compressor.decompress_dictzip).  A file
+    whose table the indexed decoder cannot use (dictzip's own default chunk length, or no table at all) is decoded by
+    decompress_stream(data, container="gzip") instead, as decompress_any_batch(fallback=True) does for its items.  A status
+    other than Success raises StarflateError."""
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    try:
+        out, st = c.decompress_dictzip(data)
+    except StarflateError as e:
+        if e.code != _capi.E_NOT_INDEXABLE:
+            raise
+        return decompress_stream(data, container="gzip", device=device)
+    if st:
+        raise StarflateError(st, f"DecompressStatus {st}")
+    return out
+
+
+def _as_bytes(data):
+    return np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).ravel()
+
+
+def _dz_range_args(data, offsets, lengths):
+    """read_ranges' arguments, checked on the host: the file's header (dictzip_index) and the ranges against its ISIZE"""
+    src = _as_bytes(data)
+    _, total_n = dictzip_index(src)
+    _, offs, lens, _ = _range_lengths(total_n, offsets, lengths, max(1, -(-total_n // CHUNK_BYTES)) + 1, None, CHUNK_BYTES)
+    return src, offs, lens
+
+
+def read_ranges(data, offsets, lengths, device=0):
+    """Byte ranges of what a dictzip file holds, given nothing but its bytes -> (list of bytes or None, status array)
+    (Compressor.read_ranges).  The header and the ranges are checked before a device is touched."""
+    args = _dz_range_args(data, offsets, lengths)
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    return c._read_ranges(*args)

@@ -3,6 +3,7 @@
 #include "../../include/starflate_hip.h"
 #include "sf_any_plan.h"
 #include "sf_device.h"
+#include "sf_dz_plan.h"
 #include "sf_inflate_core.h"
 #include "sf_inflate_plan.h"
 #include "sf_range_plan.h"
@@ -33,6 +34,7 @@ struct sfh_ctx {
   uint64_t* d_total = nullptr;   // own result slot for the synchronous entry points
   uint64_t* h_total = nullptr;   // ... and the pinned word it is copied to (a pageable target is staged by the runtime)
   uint32_t* d_value = nullptr;   // result slot of sfh_checksum_device; [2] for the decoder's status
+  sf::DzInfo* d_dzinfo = nullptr; // result slot of sfh_dz_read_index_device (on first use)
   uint64_t* d_index = nullptr;   // staging for the host-buffer decoder
   size_t d_index_cap = 0;
   uint32_t* d_sub = nullptr;
@@ -245,10 +247,11 @@ int mark_call_end(sfh_ctx* ctx, hipStream_t s) {
   return SFH_OK;
 }
 
-int check_opt(const sfh_options* o) {
+// dictzip: the caller writes SFH_DICTZIP (the single-stream calls; enqueue() checks what that container asks beyond this)
+int check_opt(const sfh_options* o, bool dictzip = false) {
   if (!o) return 0;
   if (o->strategy > SFH_DYNAMIC || o->final_stream > 1 || o->lazy > 3 || o->no_stored_fast_path > 1) return -1;
-  if (o->container > SFH_GZIP || (o->container && !o->final_stream)) return -1;  // a non-final shard has no trailer
+  if (o->container > (dictzip ? SFH_DICTZIP : SFH_GZIP) || (o->container && !o->final_stream)) return -1;  // a non-final shard has no trailer
   if (o->block_bytes % sf::kChunk || o->block_bytes > sf::kMaxStrip) return -1;
   if (o->effort > SFH_EFFORT_RECENT_ALL || o->chain_depth > 255) return -1;
   if (o->chain_depth && (o->effort < SFH_EFFORT_BEST || o->effort > SFH_EFFORT_EXTREME)) return -1;
@@ -314,12 +317,22 @@ sf::Options kernel_options(const sfh_options& o, uint32_t strip_bytes) {
 
 int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, uint64_t* d_out_n,
             const sfh_options* opt, hipStream_t s, HostPipe* pipe = nullptr) {
-  if (!ctx || (!d_src && n) || !d_dst || !d_out_n || check_opt(opt)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  if (!ctx || (!d_src && n) || !d_dst || !d_out_n || check_opt(opt, true)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   if (((uintptr_t)d_src & 15) || ((uintptr_t)d_dst & 3)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 16, dst 4)", hipSuccess);
-  if (cap < sfh_compress_bound(n, 0)) return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < sfh_compress_bound(n)", hipSuccess);
-  if (n > ((size_t)1 << 44)) return fail(ctx, SFH_E_INVALID_ARG, "input too large", hipSuccess);
   sfh_options o;
   if (opt) o = *opt; else sfh_default_options(&o);
+  // SFH_DICTZIP: the gzip stream at block_bytes = 32768 (the table promises independent chunks), its header with the table
+  const bool dictzip = o.container == SFH_DICTZIP;
+  if (dictzip) {
+    if ((o.block_bytes && o.block_bytes != sf::kChunk) || n > sf::dz::kMaxInput)
+      return fail(ctx, SFH_E_INVALID_ARG, "SFH_DICTZIP: block_bytes 0 or 32768, n <= SFH_DZ_MAX_CHUNKS * 32768", hipSuccess);
+    o.block_bytes = sf::kChunk;
+    o.container = SFH_GZIP;
+    if (cap < sfh_compress_bound_container(n, sf::kChunk, SFH_DICTZIP))
+      return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < sfh_compress_bound_container(n)", hipSuccess);
+  }
+  if (cap < sfh_compress_bound(n, 0)) return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < sfh_compress_bound(n)", hipSuccess);
+  if (n > ((size_t)1 << 44)) return fail(ctx, SFH_E_INVALID_ARG, "input too large", hipSuccess);
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
   (void)hipGetLastError();  // launches are checked with hipGetLastError(): drop whatever an earlier caller on this thread left
   const uint32_t nchunks = chunks_of(n);
@@ -348,7 +361,7 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
       ctx->ev.push_back(e);
     }
   }
-  const size_t hdr = sf::wrapper_header_bytes(o.container);
+  const size_t hdr = sf::wrapper_header_bytes(o.container, dictzip ? nchunks : 0u);
   if (pipe) pipe->copied = hdr;  // the wrapper header is written last (k_wrap) and copied last
   // the stream bytes of batch `b` (its end is in h_tot once ev_batch fires) go down while later batches run
   auto drain = [&](uint32_t b) -> int {
@@ -384,7 +397,7 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
     if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
     SF_HIP(sf::launch_plan(bn, nb, w, bo, s), "launch k_plan");
     if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
-    SF_HIP(sf::launch_scan(nb, w, sf::wrapper_header_bytes(o.container), !first, d_out_n, s), "launch k_scan");
+    SF_HIP(sf::launch_scan(nb, w, hdr, !first, d_out_n, s), "launch k_scan");
     if (ev) SF_HIP(hipEventRecord(ev[3], s), "event");
     SF_HIP(sf::launch_emit(bsrc, bn, nb, w, bo, (uint8_t*)d_dst, s), "launch k_emit");
     if (ev) SF_HIP(hipEventRecord(ev[4], s), "event");
@@ -397,7 +410,9 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
   if (pipe && (rc = drain(bi - 1)) != SFH_OK) return rc;
   if (o.container) {
     SF_HIP(sf::launch_checksum((const uint8_t*)d_src, n, nchunks, o.container, ctx->ws.sums, s), "launch k_checksum");
-    SF_HIP(sf::launch_wrap(ctx->ws.sums, nchunks, n, o.container, (uint8_t*)d_dst, d_out_n, nullptr, s), "launch k_wrap");
+    // (dictzip: the table is the differences of the call's index, complete behind the last batch's k_scan)
+    SF_HIP(sf::launch_wrap(ctx->ws.sums, nchunks, n, o.container, (uint8_t*)d_dst, d_out_n, nullptr, s, dictzip ? ctx->ws.offsets : nullptr),
+           "launch k_wrap");
   }
   if (prof) {
     SF_HIP(hipEventRecord(ctx->ev[(size_t)nbatches * sfh_ctx::kEvPerBatch], s), "event");
@@ -1891,6 +1906,7 @@ void sfh_destroy(sfh_ctx* ctx) {
   (void)hipFree(ctx->d_total);
   if (ctx->h_total) (void)hipHostFree(ctx->h_total);
   (void)hipFree(ctx->d_value);
+  (void)hipFree(ctx->d_dzinfo);
   (void)hipFree(ctx->d_index);
   (void)hipFree(ctx->d_sub);
   for (hipEvent_t e : ctx->ev_inf) (void)hipEventDestroy(e);
@@ -1958,6 +1974,16 @@ size_t sfh_compress_bound(size_t n, uint32_t block_bytes) {
   return nchunks * (size_t)(sf::kChunk + sf::kChunk / 8 + 640);
 }
 
+size_t sfh_dz_header_bytes(size_t n) { return (size_t)sf::dz::header_bytes(n); }
+
+size_t sfh_compress_bound_container(size_t n, uint32_t block_bytes, uint32_t container) {
+  if (container > SFH_DICTZIP) return 0;
+  if (container != SFH_DICTZIP) return sfh_compress_bound(n, block_bytes);
+  if ((block_bytes && block_bytes != sf::kChunk) || n > sf::dz::kMaxInput) return 0;
+  // (sfh_compress_bound covers the gzip header's 10 bytes: what comes on top is the extra field)
+  return sfh_compress_bound(n, sf::kChunk) + (size_t)sf::dz::header_bytes(n) - 10;
+}
+
 int sfh_compress_device_async(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap,
                               uint64_t* d_out_n, const sfh_options* opt, void* stream) {
   if (!ctx) return SFH_E_INVALID_ARG;
@@ -1979,7 +2005,12 @@ int sfh_compress_device(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, 
 int sfh_compress(sfh_ctx* ctx, const void* src, size_t n, void* dst, size_t cap, size_t* out_n,
                  const sfh_options* opt) {
   if (!ctx || (!src && n) || !dst || !out_n) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
-  const size_t bound = sfh_compress_bound(n, 0);
+  // (SFH_DICTZIP: the larger header needs the larger bound -- of the staging, and of the caller's buffer as well)
+  const bool dictzip = opt && opt->container == SFH_DICTZIP;
+  const size_t bound = dictzip ? sfh_compress_bound_container(n, opt->block_bytes, SFH_DICTZIP) : sfh_compress_bound(n, 0);
+  if (dictzip && !bound) return fail(ctx, SFH_E_INVALID_ARG, "SFH_DICTZIP: block_bytes 0 or 32768, n <= SFH_DZ_MAX_CHUNKS * 32768", hipSuccess);
+  if (dictzip && check_opt(opt, true)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  if (dictzip && cap < bound) return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < sfh_compress_bound_container(n)", hipSuccess);
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
   int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, n ? n : 16, "input staging");
   if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, bound, "output staging");
@@ -2012,7 +2043,7 @@ int sfh_compress(sfh_ctx* ctx, const void* src, size_t n, void* dst, size_t cap,
   }
   // a wrapped stream: the header in front and the trailer behind the raw bytes came last (k_wrap)
   const sfh_options* o = opt;
-  const size_t hdr = (o && o->container) ? sf::wrapper_header_bytes(o->container) : 0;
+  const size_t hdr = dictzip ? sf::dz::header_bytes(n) : (o && o->container) ? sf::wrapper_header_bytes(o->container) : 0;
   if (hdr) SF_HIP(hipMemcpyAsync(dst, ctx->d_out, hdr, hipMemcpyDeviceToHost, ctx->s_out), "D2H header");
   if (total > pipe.copied)
     SF_HIP(hipMemcpyAsync((uint8_t*)dst + pipe.copied, ctx->d_out + pipe.copied, total - pipe.copied, hipMemcpyDeviceToHost, ctx->s_out), "D2H trailer");
@@ -2419,6 +2450,128 @@ int sfh_decompress(sfh_ctx* ctx, const void* src, size_t src_n, const uint64_t* 
     SF_HIP(hipStreamSynchronize(s), "stream sync");
   }
   return SFH_OK;
+}
+
+// ---- the dictzip table read back (sf_dz_plan.h) ----
+int sfh_dz_read_index(const void* src, size_t src_n, sfh_dz_info* info, uint64_t* index, size_t index_cap) {
+  if (!info || (!src && src_n) || (!index && index_cap)) return SFH_E_INVALID_ARG;
+  sf::dz::Head H;
+  const int rc = sf::dz::read_index((const uint8_t*)src, src_n, H, index, index_cap);
+  if (rc != sf::dz::kOk) return rc;  // SFH_E_NOT_INDEXABLE, SFH_E_DST_TOO_SMALL: nothing written
+  const bool ok = H.status == sf::dz::kStOk;
+  *info = sfh_dz_info{ok ? H.total_n : 0, ok ? H.nseg : 0u, ok ? H.header_bytes : 0u, H.status, 0u};
+  return SFH_OK;
+}
+
+int sfh_dz_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sfh_dz_info* info, uint64_t* d_index, size_t index_cap,
+                             void* stream) {
+  if (!ctx || !info || (!d_src && src_n) || (!d_index && index_cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  if (((uintptr_t)d_src & 3) || ((uintptr_t)d_index & 7)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, index 8)", hipSuccess);
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();  // see enqueue()
+  if (!ctx->d_dzinfo) {
+    const hipError_t e = hipMalloc(&ctx->d_dzinfo, sizeof(sf::DzInfo));
+    if (e != hipSuccess) return fail(ctx, SFH_E_NOMEM, "dictzip info slot", e);
+  }
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  if (int rc = order_behind_last_call(ctx, s)) return rc;  // (the info slot is the context's)
+  SF_HIP(sf::launch_dz_index((const uint8_t*)d_src, src_n, d_index, index_cap, ctx->d_dzinfo, s), "launch k_dz_index");
+  sf::DzInfo r{};
+  SF_HIP(hipMemcpyAsync(&r, ctx->d_dzinfo, sizeof r, hipMemcpyDeviceToHost, s), "copy dictzip info");
+  if (int rc = mark_call_end(ctx, s)) return rc;
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  if (r.rc == SFH_E_NOT_INDEXABLE) return fail(ctx, SFH_E_NOT_INDEXABLE, "no dictzip table of 32 KiB chunks in the gzip header", hipSuccess);
+  if (r.rc == SFH_E_DST_TOO_SMALL) return fail(ctx, SFH_E_DST_TOO_SMALL, "index_cap < nseg + 1", hipSuccess);
+  *info = sfh_dz_info{r.total_n, r.nseg, r.header_bytes, r.status, 0u};
+  return SFH_OK;
+}
+
+int sfh_decompress_dz_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                             uint32_t* status, void* stream) {
+  if (!ctx || (!d_src && src_n) || !dst_n_out || !status || (!d_dst && dst_cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  if (((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & 15)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, dst 16)", hipSuccess);
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  const size_t entries = (size_t)SFH_DZ_MAX_CHUNKS + 1;
+  if (int rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, entries * sizeof(uint64_t), "index staging")) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  sfh_dz_info info{};
+  if (int rc = sfh_dz_read_index_device(ctx, d_src, src_n, &info, ctx->d_index, entries, s)) return rc;
+  *dst_n_out = 0;
+  *status = info.status;
+  if (info.status) {
+    snprintf(ctx->err, sizeof ctx->err, "dictzip header: DecompressStatus %u", info.status);
+    return SFH_OK;
+  }
+  if (info.total_n > dst_cap) return fail(ctx, SFH_E_DST_TOO_SMALL, "ISIZE above dst_cap", hipSuccess);
+  // one gzip item with that index: the wrapper, ISIZE and the CRC-32 are sfh_decompress_batch's
+  const void* const srcs[1] = {d_src};
+  void* const dsts[1] = {d_dst};
+  const uint64_t src_ns[1] = {src_n}, dst_ns[1] = {info.total_n};
+  const uint32_t bb = sf::kChunk;
+  if (int rc = enqueue_inflate_batch(ctx, 1, srcs, src_ns, ctx->d_index, nullptr, dsts, dst_ns, &bb, SFH_GZIP, ctx->d_value,
+                                     ctx->d_value + 1, s))
+    return rc;
+  uint32_t res[2] = {0, 0};
+  SF_HIP(hipMemcpyAsync(res, ctx->d_value, sizeof res, hipMemcpyDeviceToHost, s), "copy status");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  *status = res[0];
+  if (res[0] == 0) *dst_n_out = info.total_n;
+  else snprintf(ctx->err, sizeof ctx->err, "segment %u: DecompressStatus %u", res[1], res[0]);
+  return SFH_OK;
+}
+
+int sfh_decompress_dz(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                      uint32_t* status) {
+  if (!ctx || (!src && src_n) || !dst_n_out || !status || (!dst && dst_cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  // the header on the host first: what to refuse, and how much output staging the call needs.  (parse_head is everything
+  // but the sizes' sum: that check -- Error when they reach past the trailer -- is k_dz_index's, in the device call below)
+  sf::dz::Head H;
+  if (sf::dz::parse_head((const uint8_t*)src, src_n, H) != sf::dz::kOk)
+    return fail(ctx, SFH_E_NOT_INDEXABLE, "no dictzip table of 32 KiB chunks in the gzip header", hipSuccess);
+  if (H.status != sf::dz::kStOk) {  // a header that does not parse: nothing goes up
+    *status = H.status;
+    *dst_n_out = 0;
+    snprintf(ctx->err, sizeof ctx->err, "dictzip header: DecompressStatus %u", H.status);
+    return SFH_OK;
+  }
+  if (H.total_n > dst_cap) return fail(ctx, SFH_E_DST_TOO_SMALL, "ISIZE above dst_cap", hipSuccess);
+  const uint64_t out_n = H.total_n;
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, src_n ? src_n : 16, "input staging");
+  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_n ? out_n : 16, "output staging");
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  if (src_n) SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, s), "H2D");
+  if ((rc = sfh_decompress_dz_device(ctx, ctx->d_in, src_n, ctx->d_out, out_n, dst_n_out, status, s))) return rc;
+  if (*status == 0 && out_n) {
+    SF_HIP(hipMemcpyAsync(dst, ctx->d_out, out_n, hipMemcpyDeviceToHost, s), "D2H");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+  }
+  return SFH_OK;
+}
+
+int sfh_decompress_dz_ranges(sfh_ctx* ctx, const void* src, size_t src_n, size_t count, const uint64_t* offsets,
+                             const uint64_t* lengths, void* const* dsts, uint32_t* status) {
+  if (!ctx || (!src && src_n) || (count && !status)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  sf::dz::Head H;
+  if (sf::dz::parse_head((const uint8_t*)src, src_n, H) != sf::dz::kOk)
+    return fail(ctx, SFH_E_NOT_INDEXABLE, "no dictzip table of 32 KiB chunks in the gzip header", hipSuccess);
+  std::vector<uint64_t> index;
+  if (H.status == sf::dz::kStOk) {
+    try {
+      index.resize((size_t)H.nseg + 1);
+    } catch (...) {
+      return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+    }
+    (void)sf::dz::read_index((const uint8_t*)src, src_n, H, index.data(), index.size());  // (H.status: the sizes' sum as well)
+  }
+  if (H.status != sf::dz::kStOk) {  // a table that does not parse: every range's status
+    for (size_t r = 0; r < count; ++r) status[r] = H.status;
+    snprintf(ctx->err, sizeof ctx->err, "dictzip header: DecompressStatus %u", H.status);
+    return SFH_OK;
+  }
+  return sfh_decompress_ranges(ctx, src, src_n, index.data(), nullptr, H.nseg, H.total_n, sf::kChunk, count, offsets, lengths, dsts,
+                               status);
 }
 
 int sfh_recover_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint32_t container, uint64_t dst_n, uint64_t* d_index,

@@ -13,10 +13,14 @@
 //   k_wrap            one workgroup (k_wrap_batch: one per item of a batch): folds the per-chunk values in order (CRC: a tree of multiplications
 //                     by x^(8*length) mod P, then the right padding is divided out with x^-1 and the
 //                     0xFFFFFFFF preset / final inversion are applied; Adler: plain modular sums),
-//                     writes the wrapper header and trailer, bumps the stream size.
+//                     writes the wrapper header and trailer, bumps the stream size.  With the call's index (SFH_DICTZIP) the
+//                     gzip header carries the dictzip 'RA' table: the chunks' sizes, stored by all lanes.
+//   k_dz_index        one workgroup: reads such a table back into a segment index (sf_dz_plan.h): one lane parses the
+//                     header, all lanes load the sizes, a workgroup prefix sum, the index stored by all lanes.
 //
 // All arithmetic is integer; results are bit-exact with zlib's crc32()/adler32().
 #include "sf_device.h"
+#include "sf_dz_plan.h"
 
 namespace sf {
 
@@ -178,9 +182,12 @@ __global__ __launch_bounds__(KC_THREADS) void k_checksum_batch(const BatchChunk*
 
 // One workgroup.  total: in = header bytes + raw stream bytes (k_scan ran with that base), out += trailer.
 // dst == nullptr: only *value is written (the checksum of the n input bytes).
+// offsets (gzip only; null: the plain header): the call's index, nchunks + 1 entries -- the header is dictzip's, its table
+// the differences of the entries (dst 4-byte aligned, so the table, at byte 22, takes 16-bit stores).
 __device__ __forceinline__ void wrap_stream(const uint32_t* __restrict__ sums, uint32_t nchunks, uint64_t n, uint32_t kind,
                                             uint8_t* __restrict__ dst, uint64_t* __restrict__ total,
-                                            uint32_t* __restrict__ value, uint32_t chunk_op) {
+                                            uint32_t* __restrict__ value, uint32_t chunk_op,
+                                            const uint64_t* __restrict__ offsets = nullptr) {
   __shared__ uint32_t s_v[KW_THREADS];
   __shared__ uint32_t s_w[KW_THREADS];
   const uint32_t t = threadIdx.x;
@@ -235,6 +242,11 @@ __device__ __forceinline__ void wrap_stream(const uint32_t* __restrict__ sums, u
       result = (b << 16) | a;
     }
   }
+  if (dst && offsets) {
+    // a chunk's size always fits 16 bits: sfh_compress_bound allows a 32 KiB block 32768 + 4096 + 640 = 37504 bytes
+    uint16_t* tab = reinterpret_cast<uint16_t*>(dst + dz::kFixedHeader);
+    for (uint32_t k = t; k < nchunks; k += KW_THREADS) tab[k] = (uint16_t)(offsets[k + 1] - offsets[k]);
+  }
   if (t != 0) return;
   if (value) *value = result;
   if (!dst) return;
@@ -249,8 +261,14 @@ __device__ __forceinline__ void wrap_stream(const uint32_t* __restrict__ sums, u
     tr[3] = (uint8_t)result;
     *total = end + 4;
   } else {
-    const uint8_t h[10] = {0x1F, 0x8B, 8, 0, 0, 0, 0, 0, 0, 0xFF};  // no flags, MTIME 0, XFL 0, OS unknown
+    const uint8_t h[10] = {0x1F, 0x8B, 8, (uint8_t)(offsets ? 4 : 0), 0, 0, 0, 0, 0, 0xFF};  // FEXTRA or no flags, MTIME 0, XFL 0, OS unknown
     for (int k = 0; k < 10; ++k) dst[k] = h[k];
+    if (offsets) {  // XLEN | 'R' 'A' LEN | VER 1, CHLEN 32768, CHCNT (nchunks <= dz::kMaxChunks: the host checked)
+      const uint32_t xlen = 10 + 2 * nchunks, len = 6 + 2 * nchunks;
+      const uint8_t x[12] = {(uint8_t)xlen, (uint8_t)(xlen >> 8), 'R', 'A', (uint8_t)len, (uint8_t)(len >> 8), 1, 0,
+                             (uint8_t)dz::kChunkLen, (uint8_t)(dz::kChunkLen >> 8), (uint8_t)nchunks, (uint8_t)(nchunks >> 8)};
+      for (int k = 0; k < 12; ++k) dst[10 + k] = x[k];
+    }
     const uint32_t isize = (uint32_t)n;
     for (int k = 0; k < 4; ++k) {
       tr[k] = (uint8_t)(result >> (8 * k));
@@ -263,8 +281,59 @@ __device__ __forceinline__ void wrap_stream(const uint32_t* __restrict__ sums, u
 __global__ __launch_bounds__(KW_THREADS) void k_wrap(const uint32_t* __restrict__ sums, uint32_t nchunks, uint64_t n,
                                                      uint32_t kind, uint8_t* __restrict__ dst,
                                                      uint64_t* __restrict__ total, uint32_t* __restrict__ value,
-                                                     uint32_t chunk_op) {
-  wrap_stream(sums, nchunks, n, kind, dst, total, value, chunk_op);
+                                                     uint32_t chunk_op, const uint64_t* __restrict__ offsets) {
+  wrap_stream(sums, nchunks, n, kind, dst, total, value, chunk_op, offsets);
+}
+
+// sfh_dz_read_index_device: one workgroup.  Lane 0 parses the variable part of the header (sf_dz_plan.h); then every lane
+// takes a run of consecutive sizes (at most 32: 32762 entries over 1024 lanes; byte loads, the table lies at any byte
+// offset), the runs' sums are scanned over the wave (DPP) and the waves' totals through LDS, and every lane stores its run's
+// index entries.  *out: the info, its last word the call's return code; the index is written only when both are 0.
+__global__ __launch_bounds__(KW_THREADS) void k_dz_index(const uint8_t* __restrict__ src, uint64_t n, uint64_t* __restrict__ index,
+                                                         uint64_t index_cap, DzInfo* __restrict__ out) {
+  __shared__ dz::Head s_head;
+  __shared__ int s_rc;
+  __shared__ uint32_t s_wave[KW_THREADS / 64];
+  const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (t == 0) s_rc = dz::parse_head(src, n, s_head);
+  __syncthreads();
+  const dz::Head H = s_head;
+  int rc = s_rc;
+  uint32_t st = H.status;
+  if (rc == dz::kOk && st == dz::kStOk) {  // (uniform)
+    const uint32_t per = (H.chcnt + KW_THREADS - 1) / KW_THREADS;
+    const uint32_t i0 = min(t * per, H.chcnt), i1 = min(i0 + per, H.chcnt);
+    uint32_t mine = 0;  // (all sizes together stay below 2^32: 32762 * 65535)
+    for (uint32_t i = i0; i < i1; ++i) mine += dz::size_at(src, H, i);
+    const uint32_t incl = wave_incl_add(mine);
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (uint32_t w = 0; w < KW_THREADS / 64; ++w) {
+      const uint32_t v = s_wave[w];
+      before += w < wave ? v : 0u;
+      total += v;
+    }
+    if ((uint64_t)H.header_bytes + total > H.end) {
+      st = dz::kStError;  // the sizes reach past the trailer
+    } else if (index_cap < (uint64_t)H.nseg + 1) {
+      rc = dz::kDstTooSmall;
+    } else {
+      uint64_t o = (uint64_t)H.header_bytes + before + (incl - mine);
+      for (uint32_t i = i0; i < i1; ++i) {
+        o += dz::size_at(src, H, i);
+        if (i + 1 < H.nseg) index[i + 1] = o;  // (the last entry is the trailer's first byte, not the table's sum)
+      }
+      if (t == 0) {
+        index[0] = H.header_bytes;
+        index[H.nseg] = H.end;
+      }
+    }
+  }
+  if (t == 0) {
+    const bool ok = rc == dz::kOk && st == dz::kStOk;
+    *out = DzInfo{ok ? H.total_n : 0, ok ? H.nseg : 0u, ok ? H.header_bytes : 0u, st, rc};
+  }
 }
 
 // sfh_compress_batch*: one workgroup per item, its own partials, header and trailer
@@ -397,7 +466,10 @@ hipError_t launch_inflate_fold(const InflateItem* items, uint32_t nitems, const 
   return hipGetLastError();
 }
 
-uint32_t wrapper_header_bytes(uint32_t kind) { return kind == kChecksumAdler32 ? 2u : kind == kChecksumCrc32 ? 10u : 0u; }
+// nseg: the call's segments, or 0 for the plain gzip header (the dictzip header carries a size per segment)
+uint32_t wrapper_header_bytes(uint32_t kind, uint32_t nseg) {
+  return kind == kChecksumAdler32 ? 2u : kind != kChecksumCrc32 ? 0u : nseg ? dz::kFixedHeader + 2 * nseg : 10u;
+}
 
 hipError_t launch_checksum(const uint8_t* src, uint64_t n, uint32_t nchunks, uint32_t kind, uint32_t* sums,
                            hipStream_t s) {
@@ -409,9 +481,14 @@ hipError_t launch_checksum(const uint8_t* src, uint64_t n, uint32_t nchunks, uin
 }
 
 hipError_t launch_wrap(const uint32_t* sums, uint32_t nchunks, uint64_t n, uint32_t kind, uint8_t* dst,
-                       uint64_t* d_total, uint32_t* d_value, hipStream_t s) {
+                       uint64_t* d_total, uint32_t* d_value, hipStream_t s, const uint64_t* dz_offsets) {
   hipLaunchKernelGGL(k_wrap, dim3(1), dim3(KW_THREADS), 0, s, sums, nchunks, n, kind, dst, d_total, d_value,
-                     kChunkOp);
+                     kChunkOp, dz_offsets);
+  return hipGetLastError();
+}
+
+hipError_t launch_dz_index(const uint8_t* src, uint64_t src_n, uint64_t* index, uint64_t index_cap, DzInfo* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_dz_index, dim3(1), dim3(KW_THREADS), 0, s, src, src_n, index, index_cap, out);
   return hipGetLastError();
 }
 

@@ -279,12 +279,21 @@ hipError_t launch_batch_index(const BatchChunk* chunks, const BatchIndexRow* row
 hipError_t init_kernels();
 
 // sf_checksum.hip
-uint32_t wrapper_header_bytes(uint32_t kind);
+// bytes in front of the raw stream; nseg != 0 (gzip only): the dictzip header with its table of nseg chunk sizes
+uint32_t wrapper_header_bytes(uint32_t kind, uint32_t nseg = 0);
 hipError_t launch_checksum(const uint8_t* src, uint64_t n, uint32_t nchunks, uint32_t kind, uint32_t* sums,
                            hipStream_t s);
 // dst != null: header at dst[0..), trailer at dst[*d_total..), *d_total += trailer bytes; d_value (nullable) = checksum
+// dz_offsets (gzip, dst 4-byte aligned; null: the plain header): the call's index -- the header is dictzip's (sf_dz_plan.h)
 hipError_t launch_wrap(const uint32_t* sums, uint32_t nchunks, uint64_t n, uint32_t kind, uint8_t* dst,
-                       uint64_t* d_total, uint32_t* d_value, hipStream_t s);
+                       uint64_t* d_total, uint32_t* d_value, hipStream_t s, const uint64_t* dz_offsets = nullptr);
+// the dictzip table of a gzip stream read into index[0 .. nseg] (k_dz_index); *out: sfh_dz_info's fields, then the return code
+struct DzInfo {
+  uint64_t total_n;
+  uint32_t nseg, header_bytes, status;
+  int32_t rc;
+};
+hipError_t launch_dz_index(const uint8_t* src, uint64_t src_n, uint64_t* index, uint64_t index_cap, DzInfo* out, hipStream_t s);
 // batched: sums[c] for the call's chunk table; one k_wrap workgroup per item (header at dst, trailer at d_total[out])
 hipError_t launch_checksum_batch(const BatchChunk* chunks, uint32_t nchunks, uint32_t kind, uint32_t* sums, hipStream_t s);
 hipError_t launch_wrap_batch(const uint32_t* sums, const WrapItem* items, uint32_t nitems, uint32_t kind,
