@@ -147,6 +147,34 @@ inline auto dz_read_index(std::span<const std::byte> src) -> compat::expected<st
   return ix;
 }
 
+/// BGZF, the blocked gzip of bgzip / htslib (sfh_compress_bgzf*, sfh_bgzf_read_index*, sfh_decompress_bgzf*): the capacity
+/// compressor::compress_bgzf needs for n input bytes ...
+inline auto bgzf_bound(std::size_t n) -> std::size_t { return sfh_bgzf_bound(n); }
+/// ... and the members of such a file, found on the host (no device): every member's first byte and the file's size, the prefix
+/// sums of the members' ISIZE, and what sfh_bgzf_info says.  A file that does not parse is InvalidArgument.
+struct bgzf_index {
+  std::vector<std::uint64_t> member_off;  // members + 1
+  std::vector<std::uint64_t> out_off;     // members + 1; out_off.back() == total_bytes
+  std::uint64_t total_bytes{0};
+  std::uint32_t max_isize{0};
+  bool has_eof{false};
+  [[nodiscard]] auto members() const -> std::size_t { return member_off.empty() ? 0 : member_off.size() - 1; }
+};
+inline auto bgzf_read_index(std::span<const std::byte> src) -> compat::expected<bgzf_index, CompressStatus> {
+  sfh_bgzf_info info{};
+  (void)sfh_bgzf_read_index(src.data(), src.size(), &info, nullptr, nullptr, 0);  // the count (SFH_E_DST_TOO_SMALL: it is there)
+  if (info.status != 0) return compat::unexpected{CompressStatus::InvalidArgument};
+  bgzf_index ix;
+  ix.member_off.resize(static_cast<std::size_t>(info.members) + 1);
+  ix.out_off.resize(static_cast<std::size_t>(info.members) + 1);
+  const int rc = sfh_bgzf_read_index(src.data(), src.size(), &info, ix.member_off.data(), ix.out_off.data(), ix.member_off.size());
+  if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+  ix.total_bytes = info.total_n;
+  ix.max_isize = info.max_isize;
+  ix.has_eof = info.has_eof != 0;
+  return ix;
+}
+
 /// One GPU context (device scratch, stream).  Not thread-safe; distinct objects are independent.
 class compressor {
   sfh_ctx* ctx_{nullptr};
@@ -183,6 +211,31 @@ class compressor {
     if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
     last_n_ = src.size();
     return n;
+  }
+  /// host spans: a BGZF file -- one gzip member per 32768 input bytes, then the EOF member -- that bgzip -d and htslib read
+  /// (sfh_compress_bgzf).  dst.size() >= bgzf_bound(src.size()); opt.container must be Raw (the call is the wrapper),
+  /// final_stream true, block_bytes 0 or 32768.  The context holds no index afterwards.
+  auto compress_bgzf(std::span<const std::byte> src, std::span<std::byte> dst, const compress_options& opt = {})
+      -> compat::expected<std::size_t, CompressStatus> {
+    if (!ctx_) return compat::unexpected{init_};
+    const auto c = detail::to_c(opt);
+    std::size_t n = 0;
+    const int rc = sfh_compress_bgzf(ctx_, src.data(), src.size(), dst.data(), dst.size(), &n, &c);
+    if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+    return n;
+  }
+  /// A BGZF file decoded (sfh_decompress_bgzf: members of any size; every member's header, ISIZE and CRC-32 verified).
+  /// dst.size() >= the members' ISIZEs together (bgzf_read_index); *produced (nullable) = that sum on Success.  A refused call
+  /// or a device problem is Error.
+  auto decompress_bgzf(std::span<const std::byte> src, std::span<std::byte> dst, std::size_t* produced = nullptr) -> DecompressStatus {
+    if (!ctx_) return DecompressStatus::Error;
+    std::uint32_t st = 0;
+    std::uint64_t n = 0;
+    const int rc = sfh_decompress_bgzf(ctx_, src.data(), src.size(), dst.data(), dst.size(), &n, &st);
+    if (rc == SFH_E_DST_TOO_SMALL) return DecompressStatus::DstTooSmall;
+    if (rc != SFH_OK || st > 7) return DecompressStatus::Error;
+    if (st == 0 && produced != nullptr) *produced = static_cast<std::size_t>(n);
+    return static_cast<DecompressStatus>(st);
   }
   /// host spans, many independent items in one call: item i's stream goes to dsts[i] (dsts[i].size() >=
   /// compress_bound(srcs[i].size())), its size to sizes[i]; byte-identical to compress(srcs[i], dsts[i], opt).

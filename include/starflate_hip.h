@@ -41,7 +41,10 @@ enum sfh_status {
   SFH_E_UNSUPPORTED = -7,   /* the effort asked for rests on LDS behaviour this device does not show (sfh_lds_order_check) */
   SFH_E_NOT_INDEXABLE = -8  /* sfh_recover_index* / sfh_decompress_any*: the stream is not block-flushed every 32 KiB of
                                output (the walk of DESIGN.md 3a ends before it found every segment); nothing was decoded.
-                               sfh_dz_read_index* / sfh_decompress_dz*: the gzip header carries no dictzip table of 32 KiB chunks */
+                               sfh_dz_read_index* / sfh_decompress_dz*: the gzip header carries no dictzip table of 32 KiB chunks.
+                               sfh_decompress_bgzf_device: a member of the BGZF file holds more than 32768 bytes (ISIZE), so it
+                               is no single segment of the indexed decoder; nothing was decoded (sfh_decompress_bgzf, host
+                               buffers, reads such files) */
 };
 
 /* block strategy (inverse of src/decompress.cpp:416-458 dispatch) */
@@ -468,6 +471,67 @@ int sfh_decompress_dz(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, ui
                       uint32_t* status);
 int sfh_decompress_dz_ranges(sfh_ctx* ctx, const void* src, size_t src_n, size_t count, const uint64_t* offsets,
                              const uint64_t* lengths, void* const* dsts, uint32_t* status);
+
+/* ---- BGZF: the blocked gzip of bgzip / htslib (BAM, BCF, tabix), written and read ----
+ * A series of complete gzip members, each stating its own size, closed by a fixed empty member (all little-endian):
+ *   member: 1F 8B 08 04 | MTIME 0 | XFL 0 | OS FF | XLEN 06 00 | 'B' 'C' 02 00 | BSIZE (u16) = the member's bytes - 1
+ *           raw DEFLATE body, last block BFINAL | CRC-32 of the member's input | ISIZE (u32)
+ *   EOF:    1F 8B 08 04 00 00 00 00 00 FF 06 00 42 43 02 00 1B 00 03 00 00 00 00 00 00 00 00 00  (28 bytes)
+ * THE WRITER puts 32768 input bytes into every member (the last one holds the remainder), one member per chunk of the
+ * compressor -- a stored chunk, 37504 + 26 bytes, still fits BSIZE; two chunks would not -- then the EOF member; an input of 0
+ * bytes gives the EOF member alone, as bgzip writes it.  Defining property: with the input cut into slices of 32768 bytes the
+ * file is, for every slice, the 18-byte header above, bytes [10:] of what sfh_compress(slice, container = SFH_GZIP, the same
+ * options) writes alone (body, CRC-32, ISIZE) with BSIZE to match, and the EOF member behind the last.
+ * Options: container must be SFH_RAW (the call is the wrapper), final_stream 1, block_bytes 0 or 32768 (0 means 32768); every
+ * strategy, effort, lazy and chain_depth of sfh_compress.  Anything else is SFH_E_INVALID_ARG before anything is enqueued;
+ * cap < sfh_bgzf_bound(n) is SFH_E_DST_TOO_SMALL.  sfh_bgzf_bound(n) = max(1, ceil(n / 32768)) * (sfh_compress_bound(32768, 0)
+ * + 26) + 28.  Alignment as sfh_compress_device (d_src 16, d_dst 4).  The file's size is not limited: launch batches carry on
+ * as in the single-stream call.  sfh_compress_bgzf_device_async makes no host synchronisation (*d_out_n: the file's bytes).
+ * After the call the context holds no block index (sfh_index_entries() is 0), as after a batched call.
+ * sfh_compress_bgzf: host buffers, staged and pipelined like sfh_compress. */
+size_t sfh_bgzf_bound(size_t n);
+int sfh_compress_bgzf_device_async(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, uint64_t* d_out_n,
+                                   const sfh_options* opt, void* stream);
+int sfh_compress_bgzf_device(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, size_t* out_n,
+                             const sfh_options* opt, void* stream);
+int sfh_compress_bgzf(sfh_ctx* ctx, const void* src, size_t n, void* dst, size_t cap, size_t* out_n, const sfh_options* opt);
+/* THE READER finds the members from the file alone.  A member starts where bytes 0..2 are 1F 8B 08 and FLG has FEXTRA; its
+ * extra field is walked subfield by subfield for 'B' 'C' with SLEN 2 (others may stand before and behind it); it is BSIZE + 1
+ * bytes long and its ISIZE is its last four bytes.  FNAME, FCOMMENT and FHCRC are the gzip decoder's.
+ * member_off[0 .. members] = the first byte of every member (the EOF member and any other empty member count) and src_n;
+ * out_off[0 .. members] = the prefix sums of ISIZE, so out_off[members] = info->total_n.  info->has_eof: the last member is byte
+ * for byte the EOF member (its absence is no error; htslib only warns).  src_n == 0: no members, status 0.
+ * info->status = 5 (SrcTooSmall): a member's header (12 bytes and its extra field) or its BSIZE + 1 bytes reach past src_n;
+ * 1 (Error): bad magic or CM at a member's start, FEXTRA clear, no 'BC' subfield, a subfield overrunning XLEN, BSIZE + 1 below
+ * the member's header plus 8.  With a non-zero status the counts are 0 and the arrays are not written.
+ * SFH_E_DST_TOO_SMALL: cap < members + 1 (the arrays hold cap entries each; info then carries the counts, nothing else is
+ * written); SFH_E_INVALID_ARG: a null pointer.
+ * sfh_bgzf_read_index: host bytes, no context, no device: member after member.
+ * sfh_bgzf_read_index_device: device bytes (d_src 4-byte, the arrays 8-byte aligned).  No lane chases BSIZE from member to
+ *   member: every byte position that parses as a member's head is a node, pointer jumping from position 0 ranks the nodes the
+ *   chain reaches ("BGZF"), and a head-shaped pattern inside compressed data is a node nobody reaches.  Two
+ *   synchronisations of `stream` (NULL = the ctx's own) whatever the file holds: the node count, then the info. */
+typedef struct sfh_bgzf_info {
+  uint64_t total_n;
+  uint32_t members, max_isize, has_eof, status;
+} sfh_bgzf_info;
+int sfh_bgzf_read_index(const void* src, size_t src_n, sfh_bgzf_info* info, uint64_t* member_off, uint64_t* out_off, size_t cap);
+int sfh_bgzf_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sfh_bgzf_info* info, uint64_t* d_member_off,
+                               uint64_t* d_out_off, size_t cap, void* stream);
+/* A BGZF file decoded.  The index is read (as above); with info.max_isize <= 32768 every member is one segment of the indexed
+ * decoder and one index-free SFH_GZIP item of sfh_decompress_batch*: its wrapper, ISIZE, body and CRC-32 count exactly as
+ * there for that member alone, in launch batches of at most SFH_BATCH_CHUNKS members.  *status = the DecompressStatus of the
+ * first failing member in file order, or 0; a file whose index fails gives that status and nothing is decoded.  *dst_n_out =
+ * total_n; total_n > dst_cap is SFH_E_DST_TOO_SMALL.  d_src 4-byte, d_dst 16-byte aligned; three synchronisations of `stream`.
+ * A member above 32768 bytes (bgzip writes 65280): sfh_decompress_bgzf_device returns SFH_E_NOT_INDEXABLE and decodes nothing.
+ * sfh_decompress_bgzf (host buffers) reads every BGZF file: it walks on the host; members of at most 32768 bytes go up and
+ * through the device call (dst is written only when *status is 0); larger ones run as the items of sfh_inflate_stream_batch
+ * (SFH_GZIP, dsts[i] = dst + out_off[i], dst_cap[i] = ISIZE_i), the first non-zero item status in order being *status
+ * (INTEGRATION.md has the two paths' rates). */
+int sfh_decompress_bgzf_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                               uint32_t* status, void* stream);
+int sfh_decompress_bgzf(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                        uint32_t* status);
 
 /* ---- decoding without side information ----
  * The segment index of a stream that is flushed every 32 KiB of output -- every stream sfh_compress* writes, and zlib's with

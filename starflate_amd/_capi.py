@@ -35,6 +35,8 @@ EXPORTS = [
     "sfh_decompress_batch_device_async", "sfh_decompress_batch",
     "sfh_decompress_ranges_device_async", "sfh_decompress_range_device", "sfh_decompress_ranges",
     "sfh_dz_read_index", "sfh_dz_read_index_device", "sfh_decompress_dz_device", "sfh_decompress_dz", "sfh_decompress_dz_ranges",
+    "sfh_bgzf_bound", "sfh_compress_bgzf_device_async", "sfh_compress_bgzf_device", "sfh_compress_bgzf",
+    "sfh_bgzf_read_index", "sfh_bgzf_read_index_device", "sfh_decompress_bgzf_device", "sfh_decompress_bgzf",
     "sfh_recover_index_device", "sfh_recover_index", "sfh_decompress_any_device", "sfh_decompress_any", "sfh_last_recover_stats",
     "sfh_recover_index_batch_device", "sfh_recover_index_batch", "sfh_decompress_any_batch_device", "sfh_decompress_any_batch",
     "sfh_inflate_stream_device", "sfh_inflate_stream", "sfh_inflate_stream_batch_device", "sfh_inflate_stream_batch",
@@ -55,6 +57,11 @@ class Options(C.Structure):
 class DzInfo(C.Structure):  # sfh_dz_info
     _fields_ = [("total_n", C.c_uint64), ("nseg", C.c_uint32), ("header_bytes", C.c_uint32), ("status", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class BgzfInfo(C.Structure):  # sfh_bgzf_info
+    _fields_ = [("total_n", C.c_uint64), ("members", C.c_uint32), ("max_isize", C.c_uint32), ("has_eof", C.c_uint32),
+                ("status", C.c_uint32)]
 
 
 class DeviceProps(C.Structure):
@@ -114,6 +121,22 @@ def lib():
     L.sfh_decompress_dz.restype = C.c_int
     L.sfh_decompress_dz_ranges.argtypes = [vp, vp, sz, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(vp), vp]
     L.sfh_decompress_dz_ranges.restype = C.c_int
+    L.sfh_bgzf_bound.argtypes = [sz]
+    L.sfh_bgzf_bound.restype = sz
+    L.sfh_compress_bgzf_device_async.argtypes = [vp, vp, sz, vp, sz, vp, C.POINTER(Options), vp]
+    L.sfh_compress_bgzf_device_async.restype = C.c_int
+    L.sfh_compress_bgzf_device.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options), vp]
+    L.sfh_compress_bgzf_device.restype = C.c_int
+    L.sfh_compress_bgzf.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]
+    L.sfh_compress_bgzf.restype = C.c_int
+    L.sfh_bgzf_read_index.argtypes = [vp, sz, C.POINTER(BgzfInfo), vp, vp, sz]
+    L.sfh_bgzf_read_index.restype = C.c_int
+    L.sfh_bgzf_read_index_device.argtypes = [vp, vp, sz, C.POINTER(BgzfInfo), vp, vp, sz, vp]
+    L.sfh_bgzf_read_index_device.restype = C.c_int
+    L.sfh_decompress_bgzf_device.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), vp]
+    L.sfh_decompress_bgzf_device.restype = C.c_int
+    L.sfh_decompress_bgzf.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    L.sfh_decompress_bgzf.restype = C.c_int
     L.sfh_compress.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]
     L.sfh_compress.restype = C.c_int
     L.sfh_compress_multi.argtypes = [C.POINTER(vp), C.c_int, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]

@@ -110,6 +110,111 @@ class Compressor:
         self._check(self._lib.sfh_compress_device_async(self._h, src.data_ptr() if n else None, n, out.data_ptr(),
                                                         out.numel(), size_out.data_ptr(), C.byref(opt), C.c_void_p(s)))
 
+    # ---- BGZF, the blocked gzip of bgzip / htslib: one member per 32 KiB of input, then the EOF member (sfh_compress_bgzf*) ----
+    @staticmethod
+    def bgzf_bound(n):
+        return _capi.lib().sfh_bgzf_bound(int(n))
+
+    def compress_bgzf(self, data, strategy="auto", lazy=True, stored_fast_path=True, effort="default"):
+        """Host buffers: bytes-like -> the BGZF file (bytes) that `bgzip -d`, htslib and gzip.decompress read."""
+        src = _as_bytes(data)
+        cap = self.bgzf_bound(src.size)
+        dst = np.empty(cap, dtype=np.uint8)
+        out_n = C.c_size_t(0)
+        opt = _capi.make_options(strategy, True, lazy, stored_fast_path, "raw", 0, effort)
+        self._check(self._lib.sfh_compress_bgzf(self._h, src.ctypes.data if src.size else None, src.size, dst.ctypes.data, cap,
+                                                C.byref(out_n), C.byref(opt)))
+        return dst[: out_n.value].tobytes()
+
+    def compress_bgzf_tensor(self, src, out=None, strategy="auto", lazy=True, stream=None, stored_fast_path=True, effort="default",
+                             **options):
+        """src: 1-D uint8 tensor on this device.  Returns (out tensor, file byte count).  options: sfh_options fields the
+        call refuses when set otherwise (container, final_stream, block_bytes), passed through for its refusals to be seen."""
+        import torch
+
+        self._check_tensor(src)
+        n = src.numel()
+        if out is None:
+            out = torch.empty(self.bgzf_bound(n), dtype=torch.uint8, device=src.device)
+        self._check_tensor(out)
+        out_n = C.c_size_t(0)
+        opt = _capi.make_options(strategy, options.get("final_stream", True), lazy, stored_fast_path, options.get("container", "raw"),
+                                 options.get("block_bytes", 0), effort)
+        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
+        self._check(self._lib.sfh_compress_bgzf_device(self._h, src.data_ptr() if n else None, n, out.data_ptr(), out.numel(),
+                                                       C.byref(out_n), C.byref(opt), C.c_void_p(s)))
+        return out, out_n.value
+
+    def compress_bgzf_tensor_async(self, src, out, size_out, strategy="auto", lazy=True, stream=None, effort="default"):
+        """Enqueue only, no host synchronisation.  size_out: 1-element int64 CUDA tensor receiving the file's size."""
+        import torch
+
+        self._check_tensor(src)
+        self._check_tensor(out)
+        if size_out.dtype not in (torch.int64, torch.uint64) or not size_out.is_cuda:
+            raise ValueError("size_out must be a 1-element int64 CUDA tensor")
+        opt = _capi.make_options(strategy, True, lazy, effort=effort)
+        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
+        n = src.numel()
+        self._check(self._lib.sfh_compress_bgzf_device_async(self._h, src.data_ptr() if n else None, n, out.data_ptr(), out.numel(),
+                                                             size_out.data_ptr(), C.byref(opt), C.c_void_p(s)))
+
+    def bgzf_index(self, data):
+        """The members of a BGZF file -> (member_off, out_off, info dict): bgzf_index() at module level, on the host."""
+        return bgzf_index(data)
+
+    def bgzf_index_tensor(self, src, stream=None):
+        """src: 1-D uint8 tensor on this device holding a BGZF file -> (member_off, out_off: int64 tensors of members + 1
+        entries on the device, info dict), found on the device by pointer jumping (sfh_bgzf_read_index_device).  A file that
+        does not parse raises StarflateError with its DecompressStatus."""
+        import torch
+
+        self._check_tensor(src)
+        n = src.numel()
+        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
+        info = _capi.BgzfInfo()
+        cap = n // 26 + 2  # (a member is 26 bytes at least)
+        moff = torch.empty(cap, dtype=torch.int64, device=src.device)
+        ooff = torch.empty(cap, dtype=torch.int64, device=src.device)
+        self._check(self._lib.sfh_bgzf_read_index_device(self._h, src.data_ptr() if n else None, n, C.byref(info), moff.data_ptr(),
+                                                         ooff.data_ptr(), cap, C.c_void_p(s)))
+        if info.status:
+            raise StarflateError(info.status, f"BGZF members: DecompressStatus {info.status}")
+        m = info.members + 1
+        return moff[:m].clone(), ooff[:m].clone(), _bgzf_info_dict(info)
+
+    def decompress_bgzf(self, data):
+        """Host buffers: a BGZF file -> (bytes, DecompressStatus int); every member's header, ISIZE and CRC-32 are verified.
+        b"" when the status is not 0.  Members of at most 32 KiB decode as segments of the indexed decoder, larger ones
+        (bgzip's 65280) through the stream decoder (sfh_decompress_bgzf)."""
+        src = _as_bytes(data)
+        try:
+            _, out_off, _ = bgzf_index(src)
+        except StarflateError as e:
+            return b"", e.code
+        cap = int(out_off[-1])
+        dst = np.empty(max(cap, 1), dtype=np.uint8)
+        got, st = C.c_uint64(0), C.c_uint32(0)
+        self._check(self._lib.sfh_decompress_bgzf(self._h, src.ctypes.data if src.size else None, src.size, dst.ctypes.data, cap,
+                                                  C.byref(got), C.byref(st)))
+        return (dst[: got.value].tobytes() if st.value == 0 else b""), int(st.value)
+
+    def decompress_bgzf_tensor(self, src, total_n, out=None, stream=None):
+        """src: 1-D uint8 tensor on this device holding a BGZF file of total_n output bytes (bgzf_index) -> (out tensor,
+        bytes written, DecompressStatus int).  A member above 32 KiB raises StarflateError with code -8."""
+        import torch
+
+        self._check_tensor(src)
+        if out is None:
+            out = torch.empty(max(int(total_n), 16), dtype=torch.uint8, device=src.device)
+        self._check_tensor(out)
+        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
+        got, st = C.c_uint64(0), C.c_uint32(0)
+        n = src.numel()
+        self._check(self._lib.sfh_decompress_bgzf_device(self._h, src.data_ptr() if n else None, n, out.data_ptr(), int(total_n),
+                                                         C.byref(got), C.byref(st), C.c_void_p(s)))
+        return out, int(got.value), int(st.value)
+
     # ---- many independent items, each its own stream, in one call (sfh_compress_batch*) ----
     def compress_batch(self, items, strategy="auto", final_stream=True, lazy=True, stored_fast_path=True, container="raw",
                        block_bytes=0, effort="default"):
@@ -1059,6 +1164,48 @@ def decompress_dictzip(data, device=0):
         if e.code != _capi.E_NOT_INDEXABLE:
             raise
         return decompress_stream(data, container="gzip", device=device)
+    if st:
+        raise StarflateError(st, f"DecompressStatus {st}")
+    return out
+
+
+def _bgzf_info_dict(info):
+    return {"total_n": int(info.total_n), "members": int(info.members), "max_isize": int(info.max_isize), "has_eof": bool(info.has_eof)}
+
+
+def bgzf_index(data):
+    """The members of a BGZF file (bgzip, BAM, BCF) -> (member_off, out_off, info): uint64 arrays of members + 1 entries --
+    every member's first byte and the file's size; the prefix sums of the members' ISIZE -- and a dict with total_n, members,
+    max_isize and has_eof.  Host arithmetic, no device.  A file that does not parse raises StarflateError with its
+    DecompressStatus (1 Error, 5 SrcTooSmall)."""
+    src = _as_bytes(data)
+    info = _capi.BgzfInfo()
+    L = _capi.lib()
+    rc = L.sfh_bgzf_read_index(src.ctypes.data if src.size else None, src.size, C.byref(info), None, None, 0)  # the count
+    if info.status:
+        raise StarflateError(info.status, f"BGZF members: DecompressStatus {info.status}")
+    moff = np.zeros(info.members + 1, dtype=np.uint64)
+    ooff = np.zeros(info.members + 1, dtype=np.uint64)
+    rc = L.sfh_bgzf_read_index(src.ctypes.data if src.size else None, src.size, C.byref(info), moff.ctypes.data, ooff.ctypes.data, moff.size)
+    if rc:
+        raise StarflateError(rc, "sfh_bgzf_read_index")
+    return moff, ooff, _bgzf_info_dict(info)
+
+
+def compress_bgzf(data, device=0, **options):
+    """bytes-like -> a BGZF file on the GPU (Compressor.compress_bgzf)."""
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    return c.compress_bgzf(data, **options)
+
+
+def decompress_bgzf(data, device=0):
+    """A BGZF file -> bytes, on the GPU (Compressor.decompress_bgzf).  A status other than Success raises StarflateError."""
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    out, st = c.decompress_bgzf(data)
     if st:
         raise StarflateError(st, f"DecompressStatus {st}")
     return out

@@ -2,6 +2,7 @@
 // No torch types, no exceptions across the boundary; a ctx owns its device scratch.
 #include "../../include/starflate_hip.h"
 #include "sf_any_plan.h"
+#include "sf_bgzf_plan.h"
 #include "sf_device.h"
 #include "sf_dz_plan.h"
 #include "sf_inflate_core.h"
@@ -35,6 +36,14 @@ struct sfh_ctx {
   uint64_t* h_total = nullptr;   // ... and the pinned word it is copied to (a pageable target is staged by the runtime)
   uint32_t* d_value = nullptr;   // result slot of sfh_checksum_device; [2] for the decoder's status
   sf::DzInfo* d_dzinfo = nullptr; // result slot of sfh_dz_read_index_device (on first use)
+  // BGZF read (sfh_bgzf_read_index_device, sfh_decompress_bgzf_device), all on first use: the info slot; the scan's counts,
+  // their scan and its scratch; the walk's node arrays; the decoder's own index; its rows, implied entries and statuses
+  sf::BgzfInfo* d_bgzfinfo = nullptr;
+  uint8_t* d_bgzfcnt = nullptr;
+  uint8_t* d_bgzfwalk = nullptr;
+  uint64_t* d_bgzfix = nullptr;
+  uint8_t* d_bgzfrows = nullptr;
+  size_t d_bgzfcnt_cap = 0, d_bgzfwalk_cap = 0, d_bgzfix_cap = 0, d_bgzfrows_cap = 0;
   uint64_t* d_index = nullptr;   // staging for the host-buffer decoder
   size_t d_index_cap = 0;
   uint32_t* d_sub = nullptr;
@@ -315,12 +324,21 @@ sf::Options kernel_options(const sfh_options& o, uint32_t strip_bytes) {
                      ef_recent ? 1u : 0u};
 }
 
+// bgzf (sfh_compress_bgzf*): the raw stream at block_bytes = 32768 with every chunk closed (BFINAL) and wrapped as a gzip
+// member of its own -- k_scan leaves 26 bytes around every block, k_bgzf_wrap fills them in behind each launch batch -- and
+// the EOF member behind the last.  Off: nothing below differs from before.
 int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, uint64_t* d_out_n,
-            const sfh_options* opt, hipStream_t s, HostPipe* pipe = nullptr) {
+            const sfh_options* opt, hipStream_t s, HostPipe* pipe = nullptr, bool bgzf = false) {
   if (!ctx || (!d_src && n) || !d_dst || !d_out_n || check_opt(opt, true)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   if (((uintptr_t)d_src & 15) || ((uintptr_t)d_dst & 3)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 16, dst 4)", hipSuccess);
   sfh_options o;
   if (opt) o = *opt; else sfh_default_options(&o);
+  if (bgzf) {
+    if (o.container != SFH_RAW || o.final_stream != 1 || (o.block_bytes && o.block_bytes != sf::kChunk))
+      return fail(ctx, SFH_E_INVALID_ARG, "BGZF: container SFH_RAW, final_stream 1, block_bytes 0 or 32768", hipSuccess);
+    o.block_bytes = sf::kChunk;
+    if (cap < sfh_bgzf_bound(n)) return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < sfh_bgzf_bound(n)", hipSuccess);
+  }
   // SFH_DICTZIP: the gzip stream at block_bytes = 32768 (the table promises independent chunks), its header with the table
   const bool dictzip = o.container == SFH_DICTZIP;
   if (dictzip) {
@@ -337,11 +355,12 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
   (void)hipGetLastError();  // launches are checked with hipGetLastError(): drop whatever an earlier caller on this thread left
   const uint32_t nchunks = chunks_of(n);
   int rc = ensure_compress_ws(ctx, nchunks);
-  if (!rc && o.container) rc = ensure_sums(ctx, nchunks);
+  if (!rc && (o.container || bgzf)) rc = ensure_sums(ctx, nchunks);
   if (rc) return rc;
   ctx->last_chunks = nchunks;
   ctx->bix_valid = false;
-  const sf::Options ko = kernel_options(o, resolve_block_bytes(o.block_bytes, n, o.effort));
+  sf::Options ko = kernel_options(o, resolve_block_bytes(o.block_bytes, n, o.effort));
+  if (bgzf) ko.final_stream = 2;  // every chunk ends its own stream (plan_chunk)
   if ((ko.chain_depth || ko.recent) && (rc = ensure_order(ctx, ko.recent ? 1 : 0)) != SFH_OK) return rc;
   ctx->last_block_bytes = ko.strip_bytes;
   const bool prof = ctx->profiling != 0;
@@ -363,6 +382,12 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
   }
   const size_t hdr = sf::wrapper_header_bytes(o.container, dictzip ? nchunks : 0u);
   if (pipe) pipe->copied = hdr;  // the wrapper header is written last (k_wrap) and copied last
+  if (bgzf && n == 0) {  // the EOF member alone
+    ctx->ev_valid = false;
+    ctx->index_valid = false;
+    SF_HIP(sf::launch_bgzf_wrap(nullptr, nullptr, 0, 0, (uint8_t*)d_dst, d_out_n, 2u, s), "launch k_bgzf_wrap");
+    return mark_call_end(ctx, s);
+  }
   // the stream bytes of batch `b` (its end is in h_tot once ev_batch fires) go down while later batches run
   auto drain = [&](uint32_t b) -> int {
     SF_HIP(hipEventSynchronize(ctx->ev_batch[b % sfh_ctx::kPipe]), "wait for a batch");
@@ -389,7 +414,7 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
     w.offsets += c0;
     w.subidx += (size_t)c0 * 2 * sf::kSubRegions;
     sf::Options bo = ko;
-    bo.final_stream = last ? ko.final_stream : 0u;
+    bo.final_stream = (last || bgzf) ? ko.final_stream : 0u;
     // every batch has its own events (recorded behind the wait for its input, so a kernel's time excludes the copy)
     hipEvent_t* ev = prof ? &ctx->ev[(size_t)bi * sfh_ctx::kEvPerBatch] : nullptr;
     if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
@@ -397,10 +422,15 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
     if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
     SF_HIP(sf::launch_plan(bn, nb, w, bo, s), "launch k_plan");
     if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
-    SF_HIP(sf::launch_scan(nb, w, hdr, !first, d_out_n, s), "launch k_scan");
+    SF_HIP(sf::launch_scan(nb, w, hdr, !first, d_out_n, s, nullptr, bgzf ? sf::bgzf::kHeader : 0u, bgzf ? sf::bgzf::kWrap : 0u),
+           "launch k_scan");
     if (ev) SF_HIP(hipEventRecord(ev[3], s), "event");
     SF_HIP(sf::launch_emit(bsrc, bn, nb, w, bo, (uint8_t*)d_dst, s), "launch k_emit");
     if (ev) SF_HIP(hipEventRecord(ev[4], s), "event");
+    if (bgzf) {  // the batch's members are complete before its bytes are drained; the last batch's lane 0 appends the EOF member
+      SF_HIP(sf::launch_checksum(bsrc, bn, nb, SFH_GZIP, ctx->ws.sums + c0, s), "launch k_checksum");
+      SF_HIP(sf::launch_bgzf_wrap(ctx->ws.sums + c0, w.offsets, nb, bn, (uint8_t*)d_dst, d_out_n, last ? 1u : 0u, s), "launch k_bgzf_wrap");
+    }
     if (pipe) {
       if (bi >= 1 && (rc = drain(bi - 1)) != SFH_OK) return rc;  // (its slot is free again before batch bi + kPipe - 1 needs it)
       SF_HIP(hipMemcpyAsync(&ctx->h_tot[bi % sfh_ctx::kPipe], d_out_n, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "copy size");
@@ -419,7 +449,7 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
     ctx->ev_batches = nbatches;
   }
   ctx->ev_valid = prof;
-  ctx->index_valid = true;
+  ctx->index_valid = !bgzf;  // (BGZF: the offsets are the blocks' inside their members, no index of a stream)
   return mark_call_end(ctx, s);
 }
 
@@ -1907,6 +1937,11 @@ void sfh_destroy(sfh_ctx* ctx) {
   if (ctx->h_total) (void)hipHostFree(ctx->h_total);
   (void)hipFree(ctx->d_value);
   (void)hipFree(ctx->d_dzinfo);
+  (void)hipFree(ctx->d_bgzfinfo);
+  (void)hipFree(ctx->d_bgzfcnt);
+  (void)hipFree(ctx->d_bgzfwalk);
+  (void)hipFree(ctx->d_bgzfix);
+  (void)hipFree(ctx->d_bgzfrows);
   (void)hipFree(ctx->d_index);
   (void)hipFree(ctx->d_sub);
   for (hipEvent_t e : ctx->ev_inf) (void)hipEventDestroy(e);
@@ -2002,12 +2037,16 @@ int sfh_compress_device(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, 
   return SFH_OK;
 }
 
-int sfh_compress(sfh_ctx* ctx, const void* src, size_t n, void* dst, size_t cap, size_t* out_n,
-                 const sfh_options* opt) {
+namespace {
+// sfh_compress and sfh_compress_bgzf: host buffers, the batch loop moving the data as well
+int compress_host(sfh_ctx* ctx, const void* src, size_t n, void* dst, size_t cap, size_t* out_n, const sfh_options* opt, bool bgzf) {
   if (!ctx || (!src && n) || !dst || !out_n) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   // (SFH_DICTZIP: the larger header needs the larger bound -- of the staging, and of the caller's buffer as well)
-  const bool dictzip = opt && opt->container == SFH_DICTZIP;
-  const size_t bound = dictzip ? sfh_compress_bound_container(n, opt->block_bytes, SFH_DICTZIP) : sfh_compress_bound(n, 0);
+  const bool dictzip = !bgzf && opt && opt->container == SFH_DICTZIP;
+  const size_t bound = bgzf ? sfh_bgzf_bound(n) : dictzip ? sfh_compress_bound_container(n, opt->block_bytes, SFH_DICTZIP) : sfh_compress_bound(n, 0);
+  if (bgzf && (check_opt(opt) || (opt && (opt->container != SFH_RAW || opt->final_stream != 1 || (opt->block_bytes && opt->block_bytes != sf::kChunk)))))
+    return fail(ctx, SFH_E_INVALID_ARG, "BGZF: container SFH_RAW, final_stream 1, block_bytes 0 or 32768", hipSuccess);
+  if (bgzf && cap < bound) return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < sfh_bgzf_bound(n)", hipSuccess);
   if (dictzip && !bound) return fail(ctx, SFH_E_INVALID_ARG, "SFH_DICTZIP: block_bytes 0 or 32768, n <= SFH_DZ_MAX_CHUNKS * 32768", hipSuccess);
   if (dictzip && check_opt(opt, true)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   if (dictzip && cap < bound) return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < sfh_compress_bound_container(n)", hipSuccess);
@@ -2027,7 +2066,7 @@ int sfh_compress(sfh_ctx* ctx, const void* src, size_t n, void* dst, size_t cap,
   hipStream_t s = ctx->stream;
   // the staging buffers may still be read by copies of the previous call: they were all waited for below
   HostPipe pipe{(const uint8_t*)src, (uint8_t*)dst, cap};
-  rc = enqueue(ctx, ctx->d_in, n, ctx->d_out, bound, ctx->d_total, opt, s, &pipe);
+  rc = enqueue(ctx, ctx->d_in, n, ctx->d_out, bound, ctx->d_total, opt, s, &pipe, bgzf);
   if (rc) {
     (void)hipStreamSynchronize(ctx->s_in);
     (void)hipStreamSynchronize(s);
@@ -2043,13 +2082,44 @@ int sfh_compress(sfh_ctx* ctx, const void* src, size_t n, void* dst, size_t cap,
   }
   // a wrapped stream: the header in front and the trailer behind the raw bytes came last (k_wrap)
   const sfh_options* o = opt;
-  const size_t hdr = dictzip ? sf::dz::header_bytes(n) : (o && o->container) ? sf::wrapper_header_bytes(o->container) : 0;
+  const size_t hdr = dictzip ? sf::dz::header_bytes(n) : (!bgzf && o && o->container) ? sf::wrapper_header_bytes(o->container) : 0;
   if (hdr) SF_HIP(hipMemcpyAsync(dst, ctx->d_out, hdr, hipMemcpyDeviceToHost, ctx->s_out), "D2H header");
   if (total > pipe.copied)
     SF_HIP(hipMemcpyAsync((uint8_t*)dst + pipe.copied, ctx->d_out + pipe.copied, total - pipe.copied, hipMemcpyDeviceToHost, ctx->s_out), "D2H trailer");
   SF_HIP(hipStreamSynchronize(ctx->s_out), "stream sync");
   *out_n = (size_t)total;
   return SFH_OK;
+}
+}  // namespace
+
+int sfh_compress(sfh_ctx* ctx, const void* src, size_t n, void* dst, size_t cap, size_t* out_n,
+                 const sfh_options* opt) {
+  return compress_host(ctx, src, n, dst, cap, out_n, opt, false);
+}
+
+// ---- BGZF, the writer ----
+size_t sfh_bgzf_bound(size_t n) { return (size_t)sf::bgzf::bound(n); }
+
+int sfh_compress_bgzf_device_async(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, uint64_t* d_out_n,
+                                   const sfh_options* opt, void* stream) {
+  if (!ctx) return SFH_E_INVALID_ARG;
+  return enqueue(ctx, d_src, n, d_dst, cap, d_out_n, opt, stream ? (hipStream_t)stream : ctx->stream, nullptr, true);
+}
+
+int sfh_compress_bgzf_device(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, size_t* out_n,
+                             const sfh_options* opt, void* stream) {
+  if (!ctx || !out_n) return SFH_E_INVALID_ARG;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  int rc = enqueue(ctx, d_src, n, d_dst, cap, ctx->d_total, opt, s, nullptr, true);
+  if (rc) return rc;
+  SF_HIP(hipMemcpyAsync(ctx->h_total, ctx->d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "copy size");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  *out_n = (size_t)*ctx->h_total;
+  return SFH_OK;
+}
+
+int sfh_compress_bgzf(sfh_ctx* ctx, const void* src, size_t n, void* dst, size_t cap, size_t* out_n, const sfh_options* opt) {
+  return compress_host(ctx, src, n, dst, cap, out_n, opt, true);
 }
 
 int sfh_compress_batch_device_async(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n,
@@ -2572,6 +2642,226 @@ int sfh_decompress_dz_ranges(sfh_ctx* ctx, const void* src, size_t src_n, size_t
   }
   return sfh_decompress_ranges(ctx, src, src_n, index.data(), nullptr, H.nseg, H.total_n, sf::kChunk, count, offsets, lengths, dsts,
                                status);
+}
+
+// ---- BGZF, the reader (sf_bgzf_plan.h, sf_bgzf.hip) ----
+int sfh_bgzf_read_index(const void* src, size_t src_n, sfh_bgzf_info* info, uint64_t* member_off, uint64_t* out_off, size_t cap) {
+  if (!info || (!src && src_n) || ((!member_off || !out_off) && cap)) return SFH_E_INVALID_ARG;
+  sf::bgzf::Info I;
+  const int rc = sf::bgzf::read_index((const uint8_t*)src, src_n, I, member_off, out_off, cap);
+  *info = sfh_bgzf_info{I.total_n, I.members, I.max_isize, I.has_eof, I.status};
+  return rc;  // SFH_OK, SFH_E_DST_TOO_SMALL
+}
+
+namespace {
+// the nodes of the file counted (one synchronisation); their per-workgroup offsets stay in ctx->d_bgzfcnt for the walk
+int bgzf_count_nodes(sfh_ctx* ctx, const uint8_t* d_src, size_t src_n, hipStream_t s, uint32_t* nn) {
+  const uint32_t nb = sf::bgzf_scan_blocks(src_n);
+  const size_t words = 2 * (size_t)nb + sf::any_scan_tmp_words(nb) + 1;
+  if (int rc = grow(ctx, &ctx->d_bgzfcnt, &ctx->d_bgzfcnt_cap, words * sizeof(uint32_t), "BGZF scan counts")) return rc;
+  if (!ctx->d_bgzfinfo) {
+    const hipError_t e = hipMalloc(&ctx->d_bgzfinfo, sizeof(sf::BgzfInfo));
+    if (e != hipSuccess) return fail(ctx, SFH_E_NOMEM, "BGZF info slot", e);
+  }
+  uint32_t* cnt = (uint32_t*)ctx->d_bgzfcnt;
+  uint32_t *off = cnt + nb, *tmp = off + nb, *total = tmp + sf::any_scan_tmp_words(nb);
+  if (int rc = order_behind_last_call(ctx, s)) return rc;
+  SF_HIP(sf::launch_bgzf_count(d_src, src_n, cnt, s), "launch k_bgzf_scan");
+  SF_HIP(sf::launch_scan_u32(cnt, off, nb, tmp, total, s), "scan of the node counts");
+  SF_HIP(hipMemcpyAsync(nn, total, sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy node count");
+  if (int rc = mark_call_end(ctx, s)) return rc;
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  return SFH_OK;
+}
+// ... and walked (one synchronisation): *r the info, member_off / out_off written when the file parses and cap holds them
+int bgzf_walk_nodes(sfh_ctx* ctx, const uint8_t* d_src, size_t src_n, uint32_t nn, uint64_t* d_member_off, uint64_t* d_out_off,
+                    size_t cap, hipStream_t s, sf::BgzfInfo* r) {
+  if (int rc = grow(ctx, &ctx->d_bgzfwalk, &ctx->d_bgzfwalk_cap, sf::bgzf_walk_bytes(nn), "BGZF walk scratch")) return rc;
+  const uint32_t* off = (const uint32_t*)ctx->d_bgzfcnt + sf::bgzf_scan_blocks(src_n);
+  SF_HIP(sf::launch_bgzf_walk(d_src, src_n, off, nn, ctx->d_bgzfwalk, d_member_off, d_out_off, cap, ctx->d_bgzfinfo, s), "BGZF walk");
+  SF_HIP(hipMemcpyAsync(r, ctx->d_bgzfinfo, sizeof *r, hipMemcpyDeviceToHost, s), "copy BGZF info");
+  if (int rc = mark_call_end(ctx, s)) return rc;
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  return SFH_OK;
+}
+}  // namespace
+
+int sfh_bgzf_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sfh_bgzf_info* info, uint64_t* d_member_off,
+                               uint64_t* d_out_off, size_t cap, void* stream) {
+  if (!ctx || !info || (!d_src && src_n) || ((!d_member_off || !d_out_off) && cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  if (((uintptr_t)d_src & 3) || ((uintptr_t)d_member_off & 7) || ((uintptr_t)d_out_off & 7))
+    return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, index arrays 8)", hipSuccess);
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();  // see enqueue()
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  *info = sfh_bgzf_info{0, 0, 0, 0, 0};
+  if (src_n == 0) {  // no members
+    if (!cap) return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < members + 1", hipSuccess);
+    const uint64_t zero = 0;
+    SF_HIP(hipMemcpyAsync(d_member_off, &zero, sizeof zero, hipMemcpyHostToDevice, s), "index");
+    SF_HIP(hipMemcpyAsync(d_out_off, &zero, sizeof zero, hipMemcpyHostToDevice, s), "index");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+    return SFH_OK;
+  }
+  uint32_t nn = 0;
+  if (int rc = bgzf_count_nodes(ctx, (const uint8_t*)d_src, src_n, s, &nn)) return rc;
+  sf::BgzfInfo r{};
+  if (int rc = bgzf_walk_nodes(ctx, (const uint8_t*)d_src, src_n, nn, d_member_off, d_out_off, cap, s, &r)) return rc;
+  *info = sfh_bgzf_info{r.total_n, r.members, r.max_isize, r.has_eof, r.status};
+  if (r.rc == SFH_E_DST_TOO_SMALL) return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < members + 1", hipSuccess);
+  return SFH_OK;
+}
+
+int sfh_decompress_bgzf_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                               uint32_t* status, void* stream) {
+  if (!ctx || (!d_src && src_n) || !dst_n_out || !status || (!d_dst && dst_cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  if (((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & 15)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, dst 16)", hipSuccess);
+  *dst_n_out = 0;
+  *status = 0;
+  if (src_n == 0) return SFH_OK;
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();  // see enqueue()
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  // the index, in the context's own arrays: the file has no more members than nodes
+  uint32_t nn = 0;
+  if (int rc = bgzf_count_nodes(ctx, (const uint8_t*)d_src, src_n, s, &nn)) return rc;
+  const size_t cap = (size_t)nn + 1;
+  if (int rc = grow(ctx, &ctx->d_bgzfix, &ctx->d_bgzfix_cap, 2 * cap * sizeof(uint64_t), "BGZF index")) return rc;
+  uint64_t *member_off = ctx->d_bgzfix, *out_off = ctx->d_bgzfix + cap;
+  sf::BgzfInfo r{};
+  if (int rc = bgzf_walk_nodes(ctx, (const uint8_t*)d_src, src_n, nn, member_off, out_off, cap, s, &r)) return rc;
+  if (r.status) {
+    *status = r.status;
+    snprintf(ctx->err, sizeof ctx->err, "BGZF members: DecompressStatus %u", r.status);
+    return SFH_OK;
+  }
+  if (r.max_isize > sf::kChunk)
+    return fail(ctx, SFH_E_NOT_INDEXABLE, "a BGZF member above 32768 bytes (sfh_decompress_bgzf reads such files)", hipSuccess);
+  if (r.total_n > dst_cap) return fail(ctx, SFH_E_DST_TOO_SMALL, "the members' ISIZEs above dst_cap", hipSuccess);
+  // every member one index-free gzip item of one segment; the rows are written on the device, from the device's index
+  const uint32_t m = r.members, per = ctx->batch_chunks;
+  const size_t o_items = (size_t)m * sizeof(sf::InflateSeg), o_clips = o_items + (size_t)m * sizeof(sf::InflateItem);
+  const size_t o_sums = o_clips + (size_t)m * sizeof(sf::InflateClip), o_implied = o_sums + (size_t)m * sizeof(sf::BatchChunk);
+  const size_t o_strips = o_implied + (size_t)m * 2 * sizeof(uint64_t), o_status = o_strips + (size_t)m * sizeof(sf::InflateStrip);
+  int rc = grow(ctx, &ctx->d_bgzfrows, &ctx->d_bgzfrows_cap, o_status + (size_t)m * sizeof(uint32_t), "BGZF decoder rows");
+  if (!rc) rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, (size_t)m * sizeof(sf::SegInfo), "segment records");
+  if (!rc) rc = ensure_dtok(ctx, std::min(m, per));
+  if (!rc) rc = ensure_sums(ctx, m);
+  if (rc) return rc;
+  uint8_t* R = ctx->d_bgzfrows;
+  sf::InflateSeg* segs = (sf::InflateSeg*)R;
+  sf::InflateItem* items = (sf::InflateItem*)(R + o_items);
+  sf::InflateClip* clips = (sf::InflateClip*)(R + o_clips);
+  sf::BatchChunk* sums = (sf::BatchChunk*)(R + o_sums);
+  uint64_t* implied = (uint64_t*)(R + o_implied);
+  sf::InflateStrip* strips = (sf::InflateStrip*)(R + o_strips);
+  uint32_t* d_status = (uint32_t*)(R + o_status);
+  ctx->index_valid = false;
+  ctx->bix_valid = false;
+  ctx->ev_inf_valid = false;
+  ctx->last_chunks = m;
+  ctx->last_dtok_bytes = (size_t)std::min(m, per) * sf::kChunk * sizeof(uint32_t);
+  SF_HIP(sf::launch_bgzf_rows((const uint8_t*)d_src, member_off, out_off, m, per, (uint8_t*)d_dst, segs, items, clips, strips, sums, implied, s),
+         "launch k_bgzf_rows");
+  for (uint32_t b0 = 0; b0 < m; b0 += per) {
+    const uint32_t nb = std::min(per, m - b0);
+    sf::SegInfo* binfo = ctx->ws.seginfo + b0;
+    SF_HIP(sf::launch_inflate_tokens(segs + b0, nb, ctx->ws.tokens, binfo, false, !ctx->inflate_serial, s), "launch k_inflate_tokens");
+    // (a foreign file's ISIZEs may leave a member's output off a 16-byte boundary: the byte stage with a write window)
+    if (r.unaligned) SF_HIP(sf::launch_inflate_bytes_clip(segs + b0, clips + b0, strips + b0, nb, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes_clip");
+    else SF_HIP(sf::launch_inflate_bytes(segs + b0, strips + b0, nb, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes");
+  }
+  if (r.unaligned) SF_HIP(sf::launch_checksum_batch_any(sums, m, ctx->ws.sums, s), "launch k_checksum");
+  else SF_HIP(sf::launch_checksum_batch(sums, m, SFH_GZIP, ctx->ws.sums, s), "launch k_checksum");
+  SF_HIP(sf::launch_inflate_fold(items, m, ctx->ws.seginfo, ctx->ws.sums, SFH_GZIP, d_status, nullptr, s), "launch k_inflate_fold");
+  SF_HIP(sf::launch_bgzf_first(d_status, m, ctx->d_value, s), "launch k_bgzf_first");
+  uint32_t res[2] = {0, 0};
+  SF_HIP(hipMemcpyAsync(res, ctx->d_value, sizeof res, hipMemcpyDeviceToHost, s), "copy status");
+  if ((rc = mark_call_end(ctx, s))) return rc;
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  *status = res[0];
+  if (res[0] == 0) *dst_n_out = r.total_n;
+  else snprintf(ctx->err, sizeof ctx->err, "BGZF member %u: DecompressStatus %u", res[1], res[0]);
+  return SFH_OK;
+}
+
+int sfh_decompress_bgzf(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                        uint32_t* status) {
+  if (!ctx || (!src && src_n) || !dst_n_out || !status || (!dst && dst_cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  *dst_n_out = 0;
+  *status = 0;
+  // the members on the host first: what to refuse, which path, how much staging
+  sf::bgzf::Info I;
+  std::vector<uint64_t> member_off, out_off;
+  if (sf::bgzf::read_index((const uint8_t*)src, src_n, I, nullptr, nullptr, 0) == sf::bgzf::kDstTooSmall) {
+    try {
+      member_off.resize((size_t)I.members + 1);
+      out_off.resize((size_t)I.members + 1);
+    } catch (...) {
+      return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+    }
+    (void)sf::bgzf::read_index((const uint8_t*)src, src_n, I, member_off.data(), out_off.data(), member_off.size());
+  }
+  if (I.status) {
+    *status = I.status;
+    snprintf(ctx->err, sizeof ctx->err, "BGZF members: DecompressStatus %u", I.status);
+    return SFH_OK;
+  }
+  if (I.total_n > dst_cap) return fail(ctx, SFH_E_DST_TOO_SMALL, "the members' ISIZEs above dst_cap", hipSuccess);
+  if (I.members == 0) return SFH_OK;
+  if (I.max_isize <= sf::kChunk) {  // the device path
+    SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+    int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, src_n, "input staging");
+    if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, I.total_n ? I.total_n : 16, "output staging");
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
+    SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, s), "H2D");
+    if ((rc = sfh_decompress_bgzf_device(ctx, ctx->d_in, src_n, ctx->d_out, I.total_n, dst_n_out, status, s))) return rc;
+    if (*status == 0 && I.total_n) {
+      SF_HIP(hipMemcpyAsync(dst, ctx->d_out, I.total_n, hipMemcpyDeviceToHost, s), "D2H");
+      SF_HIP(hipStreamSynchronize(s), "stream sync");
+    }
+    return SFH_OK;
+  }
+  // members above 32 KiB (bgzip's 65280): each one an item of the stream decoder, into a buffer of the call's own so that dst
+  // is written only when every member decoded
+  const size_t m = I.members;
+  std::vector<uint8_t> out;
+  std::vector<const void*> srcs;
+  std::vector<void*> dsts;
+  std::vector<uint64_t> src_ns, caps, got;
+  std::vector<uint32_t> st;
+  try {
+    out.resize(I.total_n ? I.total_n : 1);
+    srcs.resize(m);
+    dsts.resize(m);
+    src_ns.resize(m);
+    caps.resize(m);
+    got.resize(m);
+    st.resize(m);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (size_t i = 0; i < m; ++i) {
+    srcs[i] = (const uint8_t*)src + member_off[i];
+    src_ns[i] = member_off[i + 1] - member_off[i];
+    dsts[i] = out.data() + out_off[i];
+    caps[i] = out_off[i + 1] - out_off[i];
+  }
+  if (int rc = sfh_inflate_stream_batch(ctx, m, srcs.data(), src_ns.data(), SFH_GZIP, dsts.data(), caps.data(), got.data(), st.data()))
+    return rc;
+  for (size_t i = 0; i < m; ++i) {
+    const uint32_t sti = st[i] ? st[i] : (got[i] != caps[i] ? 1u : 0u);
+    if (sti) {
+      *status = sti;
+      snprintf(ctx->err, sizeof ctx->err, "BGZF member %zu: DecompressStatus %u", i, sti);
+      return SFH_OK;
+    }
+  }
+  memcpy(dst, out.data(), I.total_n);
+  *dst_n_out = I.total_n;
+  return SFH_OK;
 }
 
 int sfh_recover_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint32_t container, uint64_t dst_n, uint64_t* d_index,

@@ -18,7 +18,14 @@
 //   k_dz_index        one workgroup: reads such a table back into a segment index (sf_dz_plan.h): one lane parses the
 //                     header, all lanes load the sizes, a workgroup prefix sum, the index stored by all lanes.
 //
+//   k_bgzf_wrap       sfh_compress_bgzf*: one LANE per member (a chunk each): the chunk's CRC-32 finished from its partial,
+//                     the 18-byte header with BSIZE from the offsets' difference, the trailer; the EOF member behind the last.
+//   k_bgzf_rows       sfh_decompress_bgzf_device: one lane per member: k_inflate_head's gzip checks on the member's own bytes,
+//                     and the decoder's rows -- the stream is the FILE (its base is aligned, a member's is not), the implied
+//                     entries absolute.
+//
 // All arithmetic is integer; results are bit-exact with zlib's crc32()/adler32().
+#include "sf_bgzf_plan.h"
 #include "sf_device.h"
 #include "sf_dz_plan.h"
 
@@ -72,8 +79,9 @@ constexpr SegShift make_seg_shift() {
 __constant__ SegShift c_seg = make_seg_shift();
 constexpr uint32_t kChunkOp = gf2_pow(kX8, kChunk);  // x^(8*32768): appends one chunk
 
-// the partial of one chunk: `valid` bytes at cp (16-byte aligned), zero-padded to kChunk, into *out
-template <uint32_t KIND>
+// the partial of one chunk: `valid` bytes at cp (16-byte aligned; ANY: of any alignment, read bytewise), zero-padded to kChunk,
+// into *out
+template <uint32_t KIND, bool ANY = false>
 __device__ __forceinline__ void checksum_chunk(const uint8_t* __restrict__ cp, uint32_t valid, uint32_t* __restrict__ out) {
   __shared__ uint32_t s_data[KC_STAGE];
   __shared__ uint32_t s_tab[KIND == kChecksumCrc32 ? 1024 : 1];
@@ -86,11 +94,11 @@ __device__ __forceinline__ void checksum_chunk(const uint8_t* __restrict__ cp, u
   for (uint32_t i = 0; i < kChunk / 16 / KC_THREADS; ++i) {
     const uint32_t k = t + KC_THREADS * i, byte0 = 16 * k;
     uint4 q = make_uint4(0, 0, 0, 0);
-    if (byte0 + 16 <= valid) {
+    if (!ANY && byte0 + 16 <= valid) {
       q = s16[k];
     } else if (byte0 < valid) {
       uint32_t w[4] = {0, 0, 0, 0};
-      for (uint32_t b = 0; byte0 + b < valid; ++b) w[b >> 2] |= (uint32_t)cp[byte0 + b] << (8 * (b & 3));
+      for (uint32_t b = 0; b < 16 && byte0 + b < valid; ++b) w[b >> 2] |= (uint32_t)cp[byte0 + b] << (8 * (b & 3));
       q = make_uint4(w[0], w[1], w[2], w[3]);
     }
     const uint32_t d = 4 * k, p = d + (d >> 5);
@@ -178,6 +186,51 @@ template <uint32_t KIND>
 __global__ __launch_bounds__(KC_THREADS) void k_checksum_batch(const BatchChunk* __restrict__ chunks, uint32_t* __restrict__ sums) {
   const BatchChunk B = chunks[blockIdx.x];
   checksum_chunk<KIND>(B.src, B.n_raw, sums + blockIdx.x);
+}
+
+// sfh_decompress_bgzf_device on a file whose ISIZEs leave a member's output off a 16-byte boundary
+__global__ __launch_bounds__(KC_THREADS) void k_checksum_batch_any(const BatchChunk* __restrict__ chunks, uint32_t* __restrict__ sums) {
+  const BatchChunk B = chunks[blockIdx.x];
+  checksum_chunk<kChecksumCrc32, true>(B.src, B.n_raw, sums + blockIdx.x);
+}
+
+// sfh_compress_bgzf*: one lane per member of a launch batch, behind its k_emit and k_checksum.  Member c holds chunk c: its
+// block lies at [offsets[c], offsets[c + 1] - 26) (k_scan with lead 18, extra 26), so the header goes 18 bytes in front of it
+// and the trailer behind it.  The CRC-32 is wrap_stream's for a stream of one chunk: the zero padding divided out of the
+// partial, the preset register carried over the chunk's bytes, the inversion -- only the batch's last member can be short,
+// the others share kFullPreset.  n: the batch's input bytes.  eof: lane 0 stores the EOF member at *total and adds it
+// (2: the file is that member alone, an empty input).  The members lie at any byte offset: single-byte stores.
+constexpr uint32_t kFullPreset = gf2_mul(gf2_pow(kX8, kChunk), 0xFFFFFFFFu);
+__global__ __launch_bounds__(256) void k_bgzf_wrap(const uint32_t* __restrict__ sums, const uint64_t* __restrict__ offsets,
+                                                   uint32_t nmembers, uint64_t n, uint8_t* __restrict__ dst,
+                                                   uint64_t* __restrict__ total, uint32_t eof) {
+  const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+  if (c < nmembers) {
+    const uint64_t cbase = (uint64_t)c * kChunk;
+    const uint32_t m = (uint32_t)(n - cbase < kChunk ? n - cbase : kChunk);
+    uint32_t raw = sums[c], preset = kFullPreset;
+    if (m != kChunk) {
+      raw = gf2_mul(raw, gf2_pow(kXinv, 8ull * (kChunk - m)));
+      preset = gf2_mul(gf2_pow(kX8, m), 0xFFFFFFFFu);
+    }
+    const uint32_t crc = ~(raw ^ preset);
+    const uint64_t b0 = offsets[c], b1 = offsets[c + 1];
+    const uint32_t bsize = (uint32_t)(b1 - b0) - 1;  // (37504 + 26 at most: sfh_compress_bound's share of a chunk)
+    uint8_t* h = dst + (b0 - bgzf::kHeader);
+    for (uint32_t k = 0; k < 16; ++k) h[k] = bgzf::eof_byte(k);
+    h[16] = (uint8_t)bsize;
+    h[17] = (uint8_t)(bsize >> 8);
+    uint8_t* tr = dst + (b1 - bgzf::kWrap);
+    for (uint32_t k = 0; k < 4; ++k) {
+      tr[k] = (uint8_t)(crc >> (8 * k));
+      tr[4 + k] = (uint8_t)(m >> (8 * k));
+    }
+  }
+  if (c == 0 && eof) {
+    const uint64_t end = eof > 1 ? 0 : *total;
+    for (uint32_t k = 0; k < bgzf::kEofBytes; ++k) dst[end + k] = bgzf::eof_byte(k);
+    *total = end + bgzf::kEofBytes;
+  }
 }
 
 // One workgroup.  total: in = header bytes + raw stream bytes (k_scan ran with that base), out += trailer.
@@ -347,6 +400,36 @@ __global__ __launch_bounds__(KW_THREADS) void k_wrap_batch(const uint32_t* __res
 // the reference's DecompressStatus values these kernels produce themselves (src/decompress.hpp:13-23)
 constexpr uint32_t kStOk = 0, kStError = 1, kStDstTooSmall = 4, kStSrcTooSmall = 5;
 
+// the gzip wrapper of the n bytes at p (any alignment) whose body decodes into dst_n bytes: container.hpp's checks in its
+// order.  st, hdr, end (= n), want and isize come in cleared
+__device__ __forceinline__ void gzip_head(const uint8_t* __restrict__ p, uint64_t n, uint64_t dst_n, uint32_t& st, uint64_t& hdr,
+                                          uint64_t& end, uint32_t& want, uint32_t& isize) {
+  if (n < 18) {
+    st = kStSrcTooSmall;
+  } else if (p[0] != 0x1F || p[1] != 0x8B || p[2] != 8 || (p[3] & 0xE0u) != 0) {
+    st = kStError;
+  } else {
+    const uint32_t flg = p[3];
+    end = n - 8;
+    uint64_t at = 10;
+    if (flg & 0x04u) {  // FEXTRA
+      if (at + 2 > end) st = kStSrcTooSmall;
+      else at += 2 + (p[at] | (uint32_t)p[at + 1] << 8);
+    }
+    for (uint32_t bit = 0x08u; st == kStOk && bit <= 0x10u; bit <<= 1) {  // FNAME, FCOMMENT: zero-terminated
+      if (!(flg & bit)) continue;
+      while (at < end && p[at] != 0) ++at;
+      ++at;
+    }
+    if (flg & 0x02u) at += 2;  // FHCRC
+    if (st == kStOk && at > end) st = kStSrcTooSmall;
+    hdr = at;
+    want = p[n - 8] | (uint32_t)p[n - 7] << 8 | (uint32_t)p[n - 6] << 16 | (uint32_t)p[n - 5] << 24;
+    isize = p[n - 4] | (uint32_t)p[n - 3] << 8 | (uint32_t)p[n - 2] << 16 | (uint32_t)p[n - 1] << 24;
+    if (st == kStOk && isize > dst_n) st = kStDstTooSmall;
+  }
+}
+
 // One lane per item, before the token kernels: the wrapper checks of include/starflate/container.hpp in its order (the
 // header, the stream long enough for it, gzip's ISIZE against the output), the trailer's checksum, and with an index its
 // first entry against the header's end.  An index-free call gets the item's one segment here: from the header's end to the
@@ -373,30 +456,7 @@ __global__ __launch_bounds__(256) void k_inflate_head(InflateItem* __restrict__ 
       want = (uint32_t)p[n - 4] << 24 | (uint32_t)p[n - 3] << 16 | (uint32_t)p[n - 2] << 8 | p[n - 1];
     }
   } else if (kind == kChecksumCrc32) {
-    if (n < 18) {
-      st = kStSrcTooSmall;
-    } else if (p[0] != 0x1F || p[1] != 0x8B || p[2] != 8 || (p[3] & 0xE0u) != 0) {
-      st = kStError;
-    } else {
-      const uint32_t flg = p[3];
-      end = n - 8;
-      uint64_t at = 10;
-      if (flg & 0x04u) {  // FEXTRA
-        if (at + 2 > end) st = kStSrcTooSmall;
-        else at += 2 + (p[at] | (uint32_t)p[at + 1] << 8);
-      }
-      for (uint32_t bit = 0x08u; st == kStOk && bit <= 0x10u; bit <<= 1) {  // FNAME, FCOMMENT: zero-terminated
-        if (!(flg & bit)) continue;
-        while (at < end && p[at] != 0) ++at;
-        ++at;
-      }
-      if (flg & 0x02u) at += 2;  // FHCRC
-      if (st == kStOk && at > end) st = kStSrcTooSmall;
-      hdr = at;
-      want = p[n - 8] | (uint32_t)p[n - 7] << 8 | (uint32_t)p[n - 6] << 16 | (uint32_t)p[n - 5] << 24;
-      isize = p[n - 4] | (uint32_t)p[n - 3] << 8 | (uint32_t)p[n - 2] << 16 | (uint32_t)p[n - 1] << 24;
-      if (st == kStOk && isize > I.dst_n) st = kStDstTooSmall;
-    }
+    gzip_head(p, n, I.dst_n, st, hdr, end, want, isize);
   }
   // (a raw item's index is the caller's business, as in sfh_decompress_device: its first entry need not be 0)
   if (kind != 0 && st == kStOk && I.ix0 && *I.ix0 != hdr) st = kStError;
@@ -414,6 +474,35 @@ __global__ __launch_bounds__(256) void k_inflate_head(InflateItem* __restrict__ 
   I.wst = st;
   I.want = want;
   I.isize = isize;
+}
+
+// sfh_decompress_bgzf_device: one lane per member (its bytes [member_off[i], member_off[i + 1]) of the file, its output
+// out_off[i] .. out_off[i + 1], at most 32768 bytes: one segment).  The member is an index-free gzip item of
+// sfh_decompress_batch, checked by gzip_head on its own bytes -- but its segment row reads the FILE: the bit reader needs a
+// 4-byte aligned base and takes any offset, so the implied entries (body start, trailer start) and the read limit are
+// absolute.  Beside the segment row its write window (all of it: k_inflate_bytes_clip takes any destination alignment), its
+// strip of one (numbered within its launch batch of `per_batch` rows) and its checksum row.
+__global__ __launch_bounds__(256) void k_bgzf_rows(const uint8_t* __restrict__ src, const uint64_t* __restrict__ member_off,
+                                                   const uint64_t* __restrict__ out_off, uint32_t nmembers, uint32_t per_batch,
+                                                   uint8_t* __restrict__ dst, InflateSeg* __restrict__ segs,
+                                                   InflateItem* __restrict__ items, InflateClip* __restrict__ clips,
+                                                   InflateStrip* __restrict__ strips, BatchChunk* __restrict__ sums,
+                                                   uint64_t* __restrict__ implied) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nmembers) return;
+  const uint64_t a = member_off[i], n = member_off[i + 1] - a, o = out_off[i];
+  const uint32_t on = (uint32_t)(out_off[i + 1] - o);
+  uint32_t st = kStOk, want = 0, isize = 0;
+  uint64_t hdr = 0, end = n;
+  gzip_head(src + a, n, on, st, hdr, end, want, isize);
+  uint64_t* ix = implied + 2 * (uint64_t)i;
+  ix[0] = st == kStOk ? a + hdr : 0;
+  ix[1] = st == kStOk ? a + end : 0;
+  items[i] = InflateItem{src + a, n, on, ix, nullptr, i, 1u, st, want, isize, 0u};
+  segs[i] = InflateSeg{src, ix, nullptr, dst + o, a + (n > 8 ? n - 8 : 0), on, kSegWrapped};
+  clips[i] = InflateClip{dst + o, 0u, on};
+  strips[i] = InflateStrip{i % per_batch, 1u};
+  sums[i] = BatchChunk{dst + o, on, 0u};
 }
 
 // One workgroup per item, behind every launch batch: the first failing segment in the item's stream order (what the serial
@@ -497,6 +586,26 @@ hipError_t launch_checksum_batch(const BatchChunk* chunks, uint32_t nchunks, uin
     hipLaunchKernelGGL(k_checksum_batch<kChecksumCrc32>, dim3(nchunks), dim3(KC_THREADS), 0, s, chunks, sums);
   else
     hipLaunchKernelGGL(k_checksum_batch<kChecksumAdler32>, dim3(nchunks), dim3(KC_THREADS), 0, s, chunks, sums);
+  return hipGetLastError();
+}
+
+hipError_t launch_checksum_batch_any(const BatchChunk* chunks, uint32_t nchunks, uint32_t* sums, hipStream_t s) {
+  hipLaunchKernelGGL(k_checksum_batch_any, dim3(nchunks), dim3(KC_THREADS), 0, s, chunks, sums);
+  return hipGetLastError();
+}
+
+hipError_t launch_bgzf_wrap(const uint32_t* sums, const uint64_t* offsets, uint32_t nmembers, uint64_t n, uint8_t* dst,
+                            uint64_t* d_total, uint32_t eof, hipStream_t s) {
+  hipLaunchKernelGGL(k_bgzf_wrap, dim3(nmembers ? (nmembers + 255) / 256 : 1), dim3(256), 0, s, sums, offsets, nmembers, n, dst, d_total,
+                     eof);
+  return hipGetLastError();
+}
+
+hipError_t launch_bgzf_rows(const uint8_t* src, const uint64_t* member_off, const uint64_t* out_off, uint32_t nmembers,
+                            uint32_t per_batch, uint8_t* dst, InflateSeg* segs, InflateItem* items, InflateClip* clips,
+                            InflateStrip* strips, BatchChunk* sums, uint64_t* implied, hipStream_t s) {
+  hipLaunchKernelGGL(k_bgzf_rows, dim3((nmembers + 255) / 256), dim3(256), 0, s, src, member_off, out_off, nmembers, per_batch, dst, segs,
+                     items, clips, strips, sums, implied);
   return hipGetLastError();
 }
 

@@ -166,7 +166,7 @@ struct Workspace {
 
 struct Options {
   uint32_t strategy;
-  uint32_t final_stream;
+  uint32_t final_stream; // 1: the call's last chunk ends with BFINAL; 2 (BGZF): every chunk does
   uint32_t lazy;
   uint32_t fast_skip;     // 0: off; 1: stored fast path; 2: ... and a chunk may be stored by its probe (strategy 0 only: launch_lz77)
   uint32_t strip_bytes;  // multiple of kChunk
@@ -269,8 +269,10 @@ hipError_t launch_plan(uint64_t n, uint32_t nchunks, const Workspace& ws, const 
 // offsets start at `base` (bytes of wrapper header in front of the stream), or with `carry` at the current *d_total
 // (the end of the previous batch); *d_total = the end of this batch.  With tables: every item's offsets start at `base`
 // (or, carried, at d_total[item.out]) and d_total[item.out] = the end of the item's stream so far
+// lead, extra (BGZF, without tables): every chunk a member of `extra` bytes around its block, the offsets `lead` bytes behind the
+// members' first bytes (see k_scan)
 hipError_t launch_scan(uint32_t nchunks, const Workspace& ws, uint64_t base, bool carry, uint64_t* d_total, hipStream_t s,
-                       const BatchTables* bt = nullptr);
+                       const BatchTables* bt = nullptr, uint32_t lead = 0, uint32_t extra = 0);
 hipError_t launch_emit(const uint8_t* src, uint64_t n, uint32_t nchunks, const Workspace& ws, const Options& opt,
                        uint8_t* dst, hipStream_t s, const BatchTables* bt = nullptr);
 // after every launch batch of a batched call: the items' index entries (item-relative offsets, item after item) into `index`
@@ -294,6 +296,31 @@ struct DzInfo {
   int32_t rc;
 };
 hipError_t launch_dz_index(const uint8_t* src, uint64_t src_n, uint64_t* index, uint64_t index_cap, DzInfo* out, hipStream_t s);
+// BGZF (sf_bgzf_plan.h).  The writer: behind a launch batch's k_emit and k_checksum (k_scan ran with lead 18, extra 26), one lane
+// per member stores its header and trailer; eof: the EOF member at *d_total, which grows by it (2: at 0, the whole file)
+hipError_t launch_bgzf_wrap(const uint32_t* sums, const uint64_t* offsets, uint32_t nmembers, uint64_t n, uint8_t* dst,
+                            uint64_t* d_total, uint32_t eof, hipStream_t s);
+// The reader (sf_bgzf.hip): *out of the walk -- sfh_bgzf_info's fields, the return code, and whether a member's output starts
+// off a 16-byte boundary
+struct BgzfInfo {
+  uint64_t total_n;
+  uint32_t members, max_isize, has_eof, status;
+  int32_t rc;
+  uint32_t unaligned, pad;
+};
+uint32_t bgzf_scan_blocks(uint64_t src_n);  // workgroups (counts) of the node scan
+hipError_t launch_bgzf_count(const uint8_t* src, uint64_t src_n, uint32_t* cnt, hipStream_t s);
+size_t bgzf_walk_bytes(uint32_t nn);        // scratch of the walk over nn nodes
+// node_off: the exclusive scan of the counts, nn their total.  member_off, out_off: cap entries each, written when the file
+// parses and members + 1 <= cap
+hipError_t launch_bgzf_walk(const uint8_t* src, uint64_t src_n, const uint32_t* node_off, uint32_t nn, uint8_t* scratch,
+                            uint64_t* member_off, uint64_t* out_off, uint64_t cap, BgzfInfo* out, hipStream_t s);
+// the decoder's rows for members of one segment each (see k_bgzf_rows); the first failing member: res[0] its status, res[1] it
+hipError_t launch_bgzf_rows(const uint8_t* src, const uint64_t* member_off, const uint64_t* out_off, uint32_t nmembers,
+                            uint32_t per_batch, uint8_t* dst, InflateSeg* segs, InflateItem* items, InflateClip* clips,
+                            InflateStrip* strips, BatchChunk* sums, uint64_t* implied, hipStream_t s);
+hipError_t launch_bgzf_first(const uint32_t* status, uint32_t m, uint32_t* res, hipStream_t s);
+hipError_t launch_checksum_batch_any(const BatchChunk* chunks, uint32_t nchunks, uint32_t* sums, hipStream_t s);  // CRC-32, any alignment
 // batched: sums[c] for the call's chunk table; one k_wrap workgroup per item (header at dst, trailer at d_total[out])
 hipError_t launch_checksum_batch(const BatchChunk* chunks, uint32_t nchunks, uint32_t kind, uint32_t* sums, hipStream_t s);
 hipError_t launch_wrap_batch(const uint32_t* sums, const WrapItem* items, uint32_t nitems, uint32_t kind,

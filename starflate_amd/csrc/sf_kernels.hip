@@ -1833,7 +1833,7 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
   } else {
     const uint64_t cbase = (uint64_t)chunk * kChunk;
     n_raw = (uint32_t)((n_total - cbase) < (uint64_t)kChunk ? (n_total - cbase) : kChunk);
-    fin = (chunk + 1 == nchunks) && final_stream;
+    fin = final_stream > 1 || ((chunk + 1 == nchunks) && final_stream);  // (2: every chunk closes a stream of its own, BGZF)
   }
 
   PlanTree* const T = ptree + chunk;
@@ -2128,7 +2128,7 @@ __global__ __launch_bounds__(64) void k_plan_merge(uint32_t nchunks, PlanTree* _
 constexpr uint32_t K3_THREADS = 1024;
 constexpr uint32_t K3_TILES = kBatchChunks / K3_THREADS;  // a batch in tiles of one chunk per thread
 static_assert(kBatchChunks % K3_THREADS == 0 && K3_TILES == 32 && K3_THREADS / 64 == 16, "k_scan: 32 tiles, a DPP row per tile's wave totals");
-static_assert((uint64_t)kBatchChunks * (kChunk + kChunk / 8 + 656) < (1ull << 32), "a batch's bytes fit 32 bits");
+static_assert((uint64_t)kBatchChunks * (kChunk + kChunk / 8 + 656 + 26) < (1ull << 32), "a batch's bytes fit 32 bits (BGZF: + 26 per chunk)");
 // `carry` (a batch after the first): the offsets continue where *total -- the previous batch's end -- left off.
 // Round 5: every thread takes chunk t of every tile -- coalesced loads, all 32 in flight at once -- instead of 32 consecutive
 // chunks (a 512-byte stride between lanes, one dependent pass for the sums and one for the offsets: 46 us per GiB); the
@@ -2136,11 +2136,14 @@ static_assert((uint64_t)kBatchChunks * (kChunk + kChunk / 8 + 656) < (1ull << 32
 // BATCH (sfh_compress_batch*): the same scan from 0 over the launch batch's chunks, then per item: its stream starts at
 // `base` (the wrapper header) or, carried, at total[item.out]; item.shift turns a chunk's offset in the batch into its
 // offset in the item's stream (k_emit), and total[item.out] = the item's end so far.
+// `extra`, `lead` (BGZF, both 0 otherwise): every chunk is a gzip member of its own, `extra` bytes of header and trailer around
+// its block; the offsets are the blocks' first bytes, `lead` (the header) behind their members' -- the closing entry likewise,
+// so member c is [offsets[c] - lead, offsets[c + 1] - lead) -- and *total is the end of the last member.
 template <bool BATCH>
 __global__ __launch_bounds__(K3_THREADS) void k_scan(uint32_t nchunks, const ChunkPlan* __restrict__ plan,
                                                      uint64_t base, uint32_t carry, uint64_t* __restrict__ offsets,
                                                      uint64_t* __restrict__ total, BatchItem* __restrict__ bitems,
-                                                     uint32_t nitems) {
+                                                     uint32_t nitems, uint32_t lead, uint32_t extra) {
   __shared__ uint32_t s_wt[K3_TILES][16];  // [tile][wave]: the wave's bytes in the tile, then the bytes of the tile's waves before it
   __shared__ uint32_t s_tile[K3_TILES + 1];  // bytes of the tiles before, [K3_TILES]: of all
   const uint64_t hdr = base;
@@ -2151,7 +2154,7 @@ __global__ __launch_bounds__(K3_THREADS) void k_scan(uint32_t nchunks, const Chu
 #pragma unroll
   for (uint32_t k = 0; k < K3_TILES; ++k) {
     const uint32_t c = k * K3_THREADS + t;
-    v[k] = c < nchunks ? plan[c].out_bytes : 0u;
+    v[k] = c < nchunks ? plan[c].out_bytes + extra : 0u;
   }
 #pragma unroll
   for (uint32_t k = 0; k < K3_TILES; ++k) {
@@ -2182,12 +2185,12 @@ __global__ __launch_bounds__(K3_THREADS) void k_scan(uint32_t nchunks, const Chu
 #pragma unroll
   for (uint32_t k = 0; k < K3_TILES; ++k) {
     const uint32_t c = k * K3_THREADS + t;
-    if (c < nchunks) offsets[c] = base + s_tile[k] + s_wt[k][wave] + ex[k];
+    if (c < nchunks) offsets[c] = base + lead + s_tile[k] + s_wt[k][wave] + ex[k];
   }
   if (t == 0) {
     const uint64_t all = base + s_tile[K3_TILES];
     if constexpr (!BATCH) *total = all;
-    offsets[nchunks] = all;  // closes the index: chunk c occupies [offsets[c], offsets[c + 1])
+    offsets[nchunks] = all + lead;  // closes the index: chunk c occupies [offsets[c], offsets[c + 1])
   }
   if constexpr (BATCH) {
     __syncthreads();  // (the offsets above are this workgroup's own stores)
@@ -2667,14 +2670,14 @@ hipError_t launch_plan(uint64_t n, uint32_t nchunks, const Workspace& ws, const 
   return hipGetLastError();
 }
 hipError_t launch_scan(uint32_t nchunks, const Workspace& ws, uint64_t base, bool carry, uint64_t* d_total, hipStream_t s,
-                       const BatchTables* bt) {
+                       const BatchTables* bt, uint32_t lead, uint32_t extra) {
   if (nchunks > kBatchChunks) return hipErrorInvalidValue;  // k_scan covers one batch (K3_TILES tiles, 32-bit sums): more would get no offset
   if (bt)
     hipLaunchKernelGGL(k_scan<true>, dim3(1), dim3(K3_THREADS), 0, s, nchunks, ws.plan, base, 0u, ws.offsets, d_total, bt->items,
-                       bt->nitems);
+                       bt->nitems, 0u, 0u);
   else
     hipLaunchKernelGGL(k_scan<false>, dim3(1), dim3(K3_THREADS), 0, s, nchunks, ws.plan, base, carry ? 1u : 0u, ws.offsets, d_total,
-                       (BatchItem*)nullptr, 0u);
+                       (BatchItem*)nullptr, 0u, lead, extra);
   return hipGetLastError();
 }
 // sfh_compress_batch*: the call's index, item after item (sfh_copy_batch_index).  Every launch batch's k_scan left its chunks'
