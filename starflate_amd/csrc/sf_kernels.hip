@@ -777,6 +777,7 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         const uint32_t pswK = kWindow + (ps & ~3u);   // LDS address of that dword in step 0
         const uint32_t psK1 = kWindow - 1u + ps;      // LDS address of the byte before the position in step 0
         const uint32_t mlen0 = to_rend < kCap ? to_rend : kCap;  // bytes a match may take from the position, the input's end aside
+        // @phase inherit
         auto lds32 = [&](uint32_t at, uint32_t off) { return *reinterpret_cast<const uint32_t*>(smem + at + off); };
         // (uniform) the round's staging slots.  (Addressed as base + the position's offset in the round: with the
         // constant folded into the base -- an odd base below the array, odd offsets -- the same stores cost 1 GiB of
@@ -789,12 +790,13 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         auto bucket_of = [](uint32_t product) { return (product >> (30 - HB)) & (((1u << HB) - 1u) << 2); };
         static_assert(HB <= kHashBits && 30 - HB > 0, "bucket offsets");
         auto tab_at = [&](uint32_t* table, uint32_t off) -> uint32_t& { return *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(table) + off); };
+        // @phase match.setup2 trips=1
         uint32_t f_a0 = 0, f_a1 = 0, f_h = 0, f_m0 = 0, f_m1 = 0, f_q0 = 0, f_q1 = 0, f_maxlen = 0;
-        // @phase match.loop trips=9 depth=2 note=nine intervals for eight steps
-        for (uint32_t it = 0; it <= nsteps; ++it) {
-          uint32_t ins_h = 0, ins_v = 0;
-          [[maybe_unused]] uint32_t ins2_h = 0, ins2_v = 0;  // LONG: the same for the seven-byte table; STRIDE2: for the odd position behind
-          bool has_ins = false;                           // (uniform) this wave inserts in this interval
+        // first part -> insertion: bucket and entry of the position (LONG: and of the seven-byte table; STRIDE2: and of the odd position behind)
+        uint32_t ins_h = 0, ins_v = 0;
+        [[maybe_unused]] uint32_t ins2_h = 0, ins2_v = 0;
+        auto first_part = [&](uint32_t it) {  // it: (uniform) the step, < nsteps
+          // @phase match.first trips=4 depth=2 note=a wave does the first part of every second step
           const uint32_t code_it = (rb / STEP + it - ebase + 1) << SH;  // (uniform) step code of step `it`
           // ... | the position's low bits: ONE v_or (the compiler would derive it from an address it has at hand, in three)
           auto code_of = [&](uint32_t low) {
@@ -802,170 +804,211 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
             asm("v_or_b32 %0, %1, %2" : "=v"(c) : "s"(code_it), "v"(low));
             return c;
           };
-          if ((it & 1) == grp) {
-            if (it < nsteps) {
-              // @phase match.first trips=4 depth=2 note=a wave does the first part of every second step
-              // ---- first part of the search at position ps of step `it` ----
-              const uint32_t sb = it * STEP;            // (uniform) the step's first position, round-relative
-              const uint32_t wb = sb + pswK;
-              const uint32_t d0 = lds32(wb, 0), d1 = lds32(wb, 4), d2 = lds32(wb, 8);
-              const uint32_t a0 = __builtin_amdgcn_alignbyte(d1, d0, sh0), a1 = __builtin_amdgcn_alignbyte(d2, d1, sh0);
-              const uint32_t hmul = a0 * 2654435761u;
-              const uint32_t h = bucket_of(hmul);       // (byte offset of the bucket: see bucket_of)
-              const uint32_t farv = tab_at(s_table, h);
-              if constexpr (STRIDE2) {
-                // the odd position behind this one is only inserted: its four bytes are in the registers already, its
-                // bucket is read beside this one's
-                static_assert(!STRIDE2 || HB == kHashBits, "the odd position's bucket is in the one table");
-                ins2_h = bucket_of(__builtin_amdgcn_alignbyte(a1, a0, 1) * 2654435761u);
-                ins2_v = tab_at(s_table, ins2_h);
-              }
-              [[maybe_unused]] uint32_t h2 = 0, farv2 = 0;
-              if constexpr (LONG) {
-                // bytes 4..6 join the hash (the specification's long hash: two multiplicative hashes xored)
-                h2 = bucket_of(hmul ^ ((a1 & 0xFFFFFFu) * 0x85EBCA6Bu));
-                farv2 = tab_at(s_table2, h2);
-              }
-              const uint32_t f0 = farv >> 16, f1 = farv & 0xFFFFu;
-              const uint32_t m0 = entry_rel<SH>(f0), m1 = entry_rel<SH>(f1);  // coded positions + 1, from the epoch's start
-              const uint32_t c0 = m0 + (K - 1), c1 = m1 + (K - 1);
-              // An empty or outdated entry decodes to some address that is not a candidate: it is still read (kept inside
-              // the LDS allocation by a 16-bit mask that leaves real candidates alone), its rank is dropped.
-              // ad - c <= kWindow  <=>  m >= thr, as signed numbers: thr >= 1 (see ebase), m < 0 for what ageing left of a
-              // position in the step before the epoch
-              static_assert(kWindow + kRound + kLook <= 0x10000 && 0x10000 + 16 <= K1_LDS, "candidate reads stay in LDS");
-              const int32_t thr = (int32_t)((sb - (K - 1)) + ps);
-              const bool ok0 = (int32_t)m0 >= thr, ok1 = DEPTH2 && (int32_t)m1 >= thr;
-              // bytes a match may take from here: inside the round's valid part, the parse region and kCap (0 beyond qn).
-              // (A step is a whole number of regions: the distance to the region's end does not depend on the step.)
-              const uint32_t maxlen = (uint32_t)max(min((int)((qn - sb) - ps), (int)mlen0), 0);
-              // candidates are ranked by their first kRank bytes; only the winner is compared to kCap
-              uint32_t l0, l1 = 0;
-              if constexpr (DEPTH2) rank8x2(s_data, a0, a1, c0, c1, maxlen, l0, l1);
-              else l0 = rank8(s_data, a0, a1, c0, maxlen);
-              f_a0 = a0; f_a1 = a1; f_h = h; f_maxlen = maxlen;
-              if constexpr (LONG) {
-                const uint32_t g0 = farv2 >> 16, g1 = farv2 & 0xFFFFu;
-                const uint32_t m2 = entry_rel<SH>(g0), m3 = entry_rel<SH>(g1);
-                const uint32_t c2 = m2 + (K - 1), c3 = m3 + (K - 1);
-                // a position without kLongBytes bytes left in the strip reads nothing from the seven-byte table
-                const bool lng = rb + sb + ps + kLongBytes <= n;
-                const bool ok2 = lng && (int32_t)m2 >= thr, ok3 = lng && (int32_t)m3 >= thr;
-                uint32_t l2, l3;
-                rank8x2(s_data, a0, a1, c2, c3, maxlen, l2, l3);
-                const uint32_t ad = kWindow + sb + ps;
-                auto key = [&](bool ok, uint32_t l, uint32_t c) { return ok ? (l << 16) | (0xFFFFu - (ad - c)) : 0u; };
-                f_m0 = key(ok0, l0, c0); f_m1 = key(ok1, l1, c1); f_q0 = key(ok2, l2, c2); f_q1 = key(ok3, l3, c3);
-                ins2_h = h2;
-                ins2_v = __builtin_amdgcn_alignbit(code_of(cv), farv2, 16);
-              } else {
-                f_q0 = c0; f_q1 = c1;
-                f_m0 = ok0 ? l0 : 0u;
-                f_m1 = ok1 ? l1 : 0u;
-              }
-              ins_h = h;
-              ins_v = __builtin_amdgcn_alignbit(code_of(cv), farv, 16);
-              if constexpr (STRIDE2) ins2_v = __builtin_amdgcn_alignbit(code_of(cv - 1u), ins2_v, 16);
-              has_ins = true;
-            }
+          // ---- first part of the search at position ps of step `it` ----
+          const uint32_t sb = it * STEP;            // (uniform) the step's first position, round-relative
+          const uint32_t wb = sb + pswK;
+          const uint32_t d0 = lds32(wb, 0), d1 = lds32(wb, 4), d2 = lds32(wb, 8);
+          const uint32_t a0 = __builtin_amdgcn_alignbyte(d1, d0, sh0), a1 = __builtin_amdgcn_alignbyte(d2, d1, sh0);
+          const uint32_t hmul = a0 * 2654435761u;
+          const uint32_t h = bucket_of(hmul);       // (byte offset of the bucket: see bucket_of)
+          const uint32_t farv = tab_at(s_table, h);
+          if constexpr (STRIDE2) {
+            // the odd position behind this one is only inserted: its four bytes are in the registers already, its
+            // bucket is read beside this one's
+            static_assert(!STRIDE2 || HB == kHashBits, "the odd position's bucket is in the one table");
+            ins2_h = bucket_of(__builtin_amdgcn_alignbyte(a1, a0, 1) * 2654435761u);
+            ins2_v = tab_at(s_table, ins2_h);
+          }
+          [[maybe_unused]] uint32_t h2 = 0, farv2 = 0;
+          if constexpr (LONG) {
+            // bytes 4..6 join the hash (the specification's long hash: two multiplicative hashes xored)
+            h2 = bucket_of(hmul ^ ((a1 & 0xFFFFFFu) * 0x85EBCA6Bu));
+            farv2 = tab_at(s_table2, h2);
+          }
+          const uint32_t f0 = farv >> 16, f1 = farv & 0xFFFFu;
+          const uint32_t m0 = entry_rel<SH>(f0), m1 = entry_rel<SH>(f1);  // coded positions + 1, from the epoch's start
+          const uint32_t c0 = m0 + (K - 1), c1 = m1 + (K - 1);
+          // An empty or outdated entry decodes to some address that is not a candidate: it is still read (kept inside
+          // the LDS allocation by a 16-bit mask that leaves real candidates alone), its rank is dropped.
+          // ad - c <= kWindow  <=>  m >= thr, as signed numbers: thr >= 1 (see ebase), m < 0 for what ageing left of a
+          // position in the step before the epoch
+          static_assert(kWindow + kRound + kLook <= 0x10000 && 0x10000 + 16 <= K1_LDS, "candidate reads stay in LDS");
+          const int32_t thr = (int32_t)((sb - (K - 1)) + ps);
+          const bool ok0 = (int32_t)m0 >= thr, ok1 = DEPTH2 && (int32_t)m1 >= thr;
+          // bytes a match may take from here: inside the round's valid part, the parse region and kCap (0 beyond qn).
+          // (A step is a whole number of regions: the distance to the region's end does not depend on the step.)
+          const uint32_t maxlen = (uint32_t)max(min((int)((qn - sb) - ps), (int)mlen0), 0);
+          // candidates are ranked by their first kRank bytes; only the winner is compared to kCap
+          uint32_t l0, l1 = 0;
+          if constexpr (DEPTH2) rank8x2(s_data, a0, a1, c0, c1, maxlen, l0, l1);
+          else l0 = rank8(s_data, a0, a1, c0, maxlen);
+          f_a0 = a0; f_a1 = a1; f_h = h; f_maxlen = maxlen;
+          if constexpr (LONG) {
+            const uint32_t g0 = farv2 >> 16, g1 = farv2 & 0xFFFFu;
+            const uint32_t m2 = entry_rel<SH>(g0), m3 = entry_rel<SH>(g1);
+            const uint32_t c2 = m2 + (K - 1), c3 = m3 + (K - 1);
+            // a position without kLongBytes bytes left in the strip reads nothing from the seven-byte table
+            const bool lng = rb + sb + ps + kLongBytes <= n;
+            const bool ok2 = lng && (int32_t)m2 >= thr, ok3 = lng && (int32_t)m3 >= thr;
+            uint32_t l2, l3;
+            rank8x2(s_data, a0, a1, c2, c3, maxlen, l2, l3);
+            const uint32_t ad = kWindow + sb + ps;
+            auto key = [&](bool ok, uint32_t l, uint32_t c) { return ok ? (l << 16) | (0xFFFFu - (ad - c)) : 0u; };
+            f_m0 = key(ok0, l0, c0); f_m1 = key(ok1, l1, c1); f_q0 = key(ok2, l2, c2); f_q1 = key(ok3, l3, c3);
+            ins2_h = h2;
+            ins2_v = __builtin_amdgcn_alignbit(code_of(cv), farv2, 16);
           } else {
-            if (it >= 1) {
-              // @phase match.second trips=4 depth=2
-              // ---- second part of the search at position ps of step it - 1 ----
-              const uint32_t sb = (it - 1) * STEP;      // (uniform) that step's first position, round-relative
-              const uint32_t ad1 = sb + psK1;           // LDS address of the byte before the position
-              const uint32_t wb = sb + pswK;
-              const uint32_t a0 = f_a0, a1 = f_a1, maxlen = f_maxlen;
-              uint32_t neare = NEAR ? tab_at(s_table, f_h) : 0u;
-              uint32_t pbyte = STRIDE2 ? smem[ad1] : 0u;  // the odd position's byte (used if a match is found)
-              // this position's bytes 8..15 (for the winner's extension, if it comes to that)
-              uint32_t d2 = lds32(wb, 8), d3 = lds32(wb, 12), d4 = lds32(wb, 16);
-              asm volatile("" : "+v"(neare), "+v"(pbyte), "+v"(d2), "+v"(d3), "+v"(d4));  // one round trip for all
-              // longest wins; ties go to the smaller distance: near, then the newer far level
-              uint32_t best = 0, bq = ad1 + 1u;
-              if constexpr (NEAR) {
-                // the step's first position with this hash: this one's own entry at the latest, so the bucket is not empty
-                // (and it is of this very step: only its index in the step has to be decoded)
-                uint32_t nc;
-                const uint32_t nlow = (neare >> 16) & (STEP - 1u);
-                asm("v_sub_u32 %0, %1, %2" : "=v"(nc) : "s"(kWindow + sb + STEP - 1u), "v"(nlow));
-                const bool okn = nlow > cv;  // nc < ad (nc == ad: this position is the first, it has no near candidate)
-                const uint32_t ln = rank8(s_data, a0, a1, nc, maxlen);
-                best = okn ? ln : 0u;
-                bq = nc;
-              }
-              if constexpr (LONG) {
-                // the largest key: the longest rank, the nearest of those
-                const uint32_t ad = ad1 + 1u;
-                const uint32_t kn = best ? (best << 16) | (0xFFFFu - (ad - bq)) : 0u;
-                const uint32_t kb = max(max(max(f_m0, f_m1), max(f_q0, f_q1)), kn);
-                best = kb >> 16;
-                bq = best ? ad - (0xFFFFu - (kb & 0xFFFFu)) : ad;
-              } else {
-                if (f_m0 > best) { best = f_m0; bq = f_q0; }
-                if (f_m1 > best) { best = f_m1; bq = f_q1; }
-              }
-              const uint32_t bd1 = ad1 - bq;  // distance - 1 (what is staged; nothing reads it where there is no match)
-              const uint32_t cbyte = STRIDE2 ? s_bytes[(bq - 1) & 0xFFFFu] : 0u;  // the byte in front of the winner (any bq reads inside LDS)
-              if (best == kRank) {
-                // the winner's next eight bytes, only where its first kRank all matched
-                const uint32_t a2 = __builtin_amdgcn_alignbyte(d3, d2, sh0), a3 = __builtin_amdgcn_alignbyte(d4, d3, sh0);
-                const uint32_t lx = kRank + cmp8<kRank / 4>(s_data, a2, a3, bq);  // maxlen <= kCap does the capping
-                best = lx < maxlen ? lx : maxlen;
-              }
-              // a 4-byte match farther than kFar4 costs more bits than four literals: drop it.  (maxlen <= n - p, so a
-              // position without kMinMatch bytes left cannot reach kMinMatch.)
-              const bool ok = best >= (bd1 >= kFar4 ? kMinMatch + 1 : kMinMatch);
-              const uint32_t len4 = ok ? best - 3 : 0u;
-              if constexpr (STRIDE2) {
-                // the odd position in front: the same match one byte longer if its byte fits too (and the candidate is
-                // not the strip's first byte: the copy would start before the strip)
-                const bool inh = ok && inh_here && pbyte == cbyte && bq != first_ad;
-                const uint32_t len4o = inh ? (best < kCap ? best - 2 : kCap - 3) : 0u;
-                // one staging slot per EVEN position (an odd position that has a match has its successor's distance)
-                *reinterpret_cast<uint16_t*>(gst + (ad1 - (kWindow - 1u))) = (uint16_t)bd1;  // only read where the length says there is a match
-                // 4-bit lengths, SHIFTED by one position: byte j = {position 2j - 1, position 2j} of the round -- the pair
-                // this thread knows
-                smem[L_LEN4 + ((sb >> 1) + tp)] = (uint8_t)(len4o | (len4 << 4));
-              } else {
-                *reinterpret_cast<uint16_t*>(gst + 2u * (ad1 - (kWindow - 1u))) = (uint16_t)bd1;
-                // two lanes' 4-bit lengths -> one byte (the odd lane's value comes over the DPP network), stored by the
-                // even lanes.  All 64 lanes of the wave are active here, so the execution mask is switched and restored by
-                // hand: two scalar moves instead of the save / branch / restore a divergent `if` compiles to (smem sits at
-                // LDS address 0: it is the kernel's only __shared__ object)
-                uint32_t v = len4;
-                v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xF5 /* quad_perm:[1,1,3,3] */, 0xF, 0xF, true) << 4;
-                // (the store is invisible to the compiler's counter tracking: waited for here, ahead of the barrier behind it)
-                asm volatile("s_mov_b64 exec, %2\n\tds_write_b8 %0, %1 offset:%3\n\ts_mov_b64 exec, -1\n\ts_waitcnt lgkmcnt(0)"
-                             :: "v"((sb + tp) >> 1), "v"(v), "s"(0x5555555555555555ull), "n"(L_LEN4) : "memory");
-              }
-            }
+            f_q0 = c0; f_q1 = c1;
+            f_m0 = ok0 ? l0 : 0u;
+            f_m1 = ok1 ? l1 : 0u;
           }
-          // @phase match.barrier trips=8 depth=2
-          if (it == nsteps) break;
-          lds_barrier();  // every read of the table as it stands before step `it` precedes the step's insertions
+          ins_h = h;
+          ins_v = __builtin_amdgcn_alignbit(code_of(cv), farv, 16);
+          if constexpr (STRIDE2) ins2_v = __builtin_amdgcn_alignbit(code_of(cv - 1u), ins2_v, 16);
+        };
+        auto second_part = [&](uint32_t it) {  // it: (uniform) the interval, 1..nsteps: the step is it - 1
+          // @phase match.second trips=4 depth=2
+          // ---- second part of the search at position ps of step it - 1 ----
+          const uint32_t sb = (it - 1) * STEP;      // (uniform) that step's first position, round-relative
+          const uint32_t ad1 = sb + psK1;           // LDS address of the byte before the position
+          const uint32_t wb = sb + pswK;
+          const uint32_t a0 = f_a0, a1 = f_a1, maxlen = f_maxlen;
+          uint32_t neare = NEAR ? tab_at(s_table, f_h) : 0u;
+          uint32_t pbyte = STRIDE2 ? smem[ad1] : 0u;  // the odd position's byte (used if a match is found)
+          // this position's bytes 8..15 (for the winner's extension, if it comes to that)
+          uint32_t d2 = lds32(wb, 8), d3 = lds32(wb, 12), d4 = lds32(wb, 16);
+          asm volatile("" : "+v"(neare), "+v"(pbyte), "+v"(d2), "+v"(d3), "+v"(d4));  // one round trip for all
+          // longest wins; ties go to the smaller distance: near, then the newer far level
+          uint32_t best = 0, bq = ad1 + 1u;
+          if constexpr (NEAR) {
+            // the step's first position with this hash: this one's own entry at the latest, so the bucket is not empty
+            // (and it is of this very step: only its index in the step has to be decoded)
+            uint32_t nc;
+            const uint32_t nlow = (neare >> 16) & (STEP - 1u);
+            asm("v_sub_u32 %0, %1, %2" : "=v"(nc) : "s"(kWindow + sb + STEP - 1u), "v"(nlow));
+            const bool okn = nlow > cv;  // nc < ad (nc == ad: this position is the first, it has no near candidate)
+            const uint32_t ln = rank8(s_data, a0, a1, nc, maxlen);
+            best = okn ? ln : 0u;
+            bq = nc;
+          }
+          if constexpr (LONG) {
+            // the largest key: the longest rank, the nearest of those
+            const uint32_t ad = ad1 + 1u;
+            const uint32_t kn = best ? (best << 16) | (0xFFFFu - (ad - bq)) : 0u;
+            const uint32_t kb = max(max(max(f_m0, f_m1), max(f_q0, f_q1)), kn);
+            best = kb >> 16;
+            bq = best ? ad - (0xFFFFu - (kb & 0xFFFFu)) : ad;
+          } else {
+            if (f_m0 > best) { best = f_m0; bq = f_q0; }
+            if (f_m1 > best) { best = f_m1; bq = f_q1; }
+          }
+          const uint32_t bd1 = ad1 - bq;  // distance - 1 (what is staged; nothing reads it where there is no match)
+          const uint32_t cbyte = STRIDE2 ? s_bytes[(bq - 1) & 0xFFFFu] : 0u;  // the byte in front of the winner (any bq reads inside LDS)
+          if (best == kRank) {
+            // the winner's next eight bytes, only where its first kRank all matched
+            const uint32_t a2 = __builtin_amdgcn_alignbyte(d3, d2, sh0), a3 = __builtin_amdgcn_alignbyte(d4, d3, sh0);
+            const uint32_t lx = kRank + cmp8<kRank / 4>(s_data, a2, a3, bq);  // maxlen <= kCap does the capping
+            best = lx < maxlen ? lx : maxlen;
+          }
+          // a 4-byte match farther than kFar4 costs more bits than four literals: drop it.  (maxlen <= n - p, so a
+          // position without kMinMatch bytes left cannot reach kMinMatch.)
+          const bool ok = best >= (bd1 >= kFar4 ? kMinMatch + 1 : kMinMatch);
+          const uint32_t len4 = ok ? best - 3 : 0u;
+          if constexpr (STRIDE2) {
+            // the odd position in front: the same match one byte longer if its byte fits too (and the candidate is
+            // not the strip's first byte: the copy would start before the strip)
+            const bool inh = ok && inh_here && pbyte == cbyte && bq != first_ad;
+            const uint32_t len4o = inh ? (best < kCap ? best - 2 : kCap - 3) : 0u;
+            // one staging slot per EVEN position (an odd position that has a match has its successor's distance)
+            // (the slot's offset pinned as a 32-bit register: the store is uniform base + offset, not a 64-bit pointer per
+            // thread that the loop carries and advances)
+            uint32_t slot = ad1 - (kWindow - 1u);
+            asm("" : "+v"(slot));
+            *reinterpret_cast<uint16_t*>(gst + slot) = (uint16_t)bd1;  // only read where the length says there is a match
+            // 4-bit lengths, SHIFTED by one position: byte j = {position 2j - 1, position 2j} of the round -- the pair
+            // this thread knows
+            smem[L_LEN4 + ((sb >> 1) + tp)] = (uint8_t)(len4o | (len4 << 4));
+          } else {
+            *reinterpret_cast<uint16_t*>(gst + 2u * (ad1 - (kWindow - 1u))) = (uint16_t)bd1;
+            // two lanes' 4-bit lengths -> one byte (the odd lane's value comes over the DPP network), stored by the
+            // even lanes.  All 64 lanes of the wave are active here, so the execution mask is switched and restored by
+            // hand: two scalar moves instead of the save / branch / restore a divergent `if` compiles to (smem sits at
+            // LDS address 0: it is the kernel's only __shared__ object)
+            uint32_t v = len4;
+            v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xF5 /* quad_perm:[1,1,3,3] */, 0xF, 0xF, true) << 4;
+            // (the store is invisible to the compiler's counter tracking: waited for here, ahead of the barrier behind it)
+            asm volatile("s_mov_b64 exec, %2\n\tds_write_b8 %0, %1 offset:%3\n\ts_mov_b64 exec, -1\n\ts_waitcnt lgkmcnt(0)"
+                         :: "v"((sb + tp) >> 1), "v"(v), "s"(0x5555555555555555ull), "n"(L_LEN4) : "memory");
+          }
+        };
+        auto insert = [&]() {  // (by the half that did the step's first part)
           // @phase match.insert trips=4 depth=2
-          if (has_ins) {  // (the half that did the step's first part)
-            // {code, old newest}: the upper half of code:bucket.  (Positions without kMinMatch bytes left insert like the
-            // rest, which nothing can observe: every position after them in the strip is such a position too and takes no
-            // match, the next strip starts from an empty table.)  A lane whose predecessor in the wave has the same bucket
-            // need not insert: that one's position is lower, its code larger (a run would otherwise serialise the wave's
-            // atomics)
-            const uint32_t hp = (uint32_t)__builtin_amdgcn_update_dpp((int)~ins_h, (int)ins_h, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-            if (hp != ins_h) atomicMax(&tab_at(s_table, ins_h), ins_v);
-            if constexpr (LONG) {
-              const uint32_t hp2 = (uint32_t)__builtin_amdgcn_update_dpp((int)~ins2_h, (int)ins2_h, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-              if (hp2 != ins2_h) atomicMax(&tab_at(s_table2, ins2_h), ins2_v);
-            }
-            if constexpr (STRIDE2) {
-              // the odd position behind: the same, among the wave's odd positions (and its own even position's bucket has
-              // the larger code already)
-              const uint32_t hp2 = (uint32_t)__builtin_amdgcn_update_dpp((int)~ins2_h, (int)ins2_h, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-              if (hp2 != ins2_h && ins2_h != ins_h) atomicMax(&tab_at(s_table, ins2_h), ins2_v);
-            }
+          // {code, old newest}: the upper half of code:bucket.  (Positions without kMinMatch bytes left insert like the
+          // rest, which nothing can observe: every position after them in the strip is such a position too and takes no
+          // match, the next strip starts from an empty table.)  A lane whose predecessor in the wave has the same bucket
+          // need not insert: that one's position is lower, its code larger (a run would otherwise serialise the wave's
+          // atomics)
+          const uint32_t hp = (uint32_t)__builtin_amdgcn_update_dpp((int)~ins_h, (int)ins_h, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+          if (hp != ins_h) atomicMax(&tab_at(s_table, ins_h), ins_v);
+          if constexpr (LONG) {
+            const uint32_t hp2 = (uint32_t)__builtin_amdgcn_update_dpp((int)~ins2_h, (int)ins2_h, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+            if (hp2 != ins2_h) atomicMax(&tab_at(s_table2, ins2_h), ins2_v);
           }
-          // @phase match.barrier2 trips=8 depth=2
-          lds_barrier();  // insertions complete before the near reads
+          if constexpr (STRIDE2) {
+            // the odd position behind: the same, among the wave's odd positions (and its own even position's bucket has
+            // the larger code already)
+            const uint32_t hp2 = (uint32_t)__builtin_amdgcn_update_dpp((int)~ins2_h, (int)ins2_h, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+            if (hp2 != ins2_h && ins2_h != ins_h) atomicMax(&tab_at(s_table, ins2_h), ins2_v);
+          }
+        };
+        // @phase match.loop trips=4 depth=2 note=two intervals per trip: nine intervals for eight steps
+        // A wave's intervals alternate, and which comes first is its half's, fixed for the kernel: ONE branch per round puts the
+        // second half an interval behind (interval 0 has no step before it to finish), then every wave runs the same
+        // straight-line pair -- first part, barrier, insertion, barrier; second part, barrier, barrier -- with no test of
+        // the interval's parity, of "is there a step before" or of "does this wave insert" inside it.  Both halves pass
+        // two barriers per interval, 2 * nsteps in all.
+        // (LONG keeps the loop over single intervals with its tests: the pair costs that instantiation five spilled registers.
+        // The two loops are ONE schedule written twice: whatever changes in one must leave both halves passing the same
+        // 2 * nsteps barriers in the other, or the workgroup hangs.)
+        if constexpr (LONG) {
+          for (uint32_t it = 0; it <= nsteps; ++it) {
+            ins_h = ins_v = ins2_h = ins2_v = 0;
+            bool has_ins = false;  // (uniform) this wave inserts in this interval
+            if ((it & 1) == grp) {
+              if (it < nsteps) {
+                first_part(it);
+                has_ins = true;
+              }
+            } else if (it >= 1) {
+              second_part(it);
+            }
+            if (it == nsteps) break;
+            lds_barrier();
+            if (has_ins) insert();
+            lds_barrier();
+          }
+        } else {
+          uint32_t it = 0;
+          if (grp) {
+            if (nsteps) { lds_barrier(); lds_barrier(); }
+            it = 1;
+          }
+          while (it < nsteps) {
+            first_part(it);
+            // @phase match.barrier trips=4 depth=2 note=every barrier site of the pair runs once per pair
+            lds_barrier();  // every read of the table as it stands before step `it` precedes the step's insertions
+            insert();
+            // @phase match.barrier trips=4 depth=2
+            lds_barrier();  // insertions complete before the near reads
+            // @phase match.loop trips=4 depth=2
+            second_part(it + 1);
+            if (it + 1 == nsteps) break;
+            // @phase match.barrier trips=4 depth=2
+            lds_barrier();  // (the other half's insertion lies between these two)
+            lds_barrier();
+            // @phase match.loop trips=4 depth=2
+            it += 2;
+          }
         }
         // @phase match.tail trips=1
         // STRIDE2: the last position of the last step that ran is odd and has no successor in its step: no match.  Its length

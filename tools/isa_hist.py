@@ -108,8 +108,10 @@ def kernel_body(asm_path, pattern, src_name):
         s = ln.strip()
         if s.startswith(".loc"):
             p = s.split()
-            # a line of another file (a HIP header's min(), a builtin wrapper) says nothing about the phase: 0 = "inherit"
-            lines.append(("loc", int(p[2]) if os.path.basename(src_name) in s else 0))
+            # a line of another file (a HIP header's min(), a builtin wrapper) says nothing about the phase: 0 = "inherit".
+            # (The file is the one named in FRONT of an inlined-at note `@[ sf_kernels.hip:719:51 ]`, which names this source
+            # whatever file the line is of.)
+            lines.append(("loc", int(p[2]) if os.path.basename(src_name) in s.split("@[")[0] else 0))
         elif re.match(r"^\.LBB\d+_\d+:", ln):
             d = re.search(r"Depth=(\d+)", ln)
             lines.append(("label", (s.split(":")[0], int(d.group(1)) if d else 0)))
