@@ -5,7 +5,8 @@ loop takes a wave's intervals in PAIRS: the half of the workgroup that starts an
 nsteps and the pair that does not must all pass the same barriers.  Strip lengths around one round, two rounds and a chunk,
 each plus the look-ahead, give or take up to nine bytes, put the strip's end on every side of a thread's two words and
 of a step's first position; each must give the specification's stream bit for bit, for every kernel class (step tables
-at stride 2, every position, exact recency, hash chains).
+at stride 2 with two levels and with one, every position, the two tables of `max`, whose match loop alone still takes
+its intervals one at a time, exact recency at stride 2 and at every position, hash chains of depth 8, 16 and 32).
 
 (History: a variant that fetched the prefetch with one unguarded 8-byte load behind a uniform test
 rb + 2 * kRound + kLook <= n was measured and left out, profiles/r08_notes.md; the lengths bracket that bound too.)
@@ -25,7 +26,7 @@ CHUNK = 32768   # kChunk: a DEFLATE block, four rounds
 ROUND = 8192    # kRound: positions per round, eight per thread
 LOOK = 32       # kLook: the bytes behind a round that its matches may read
 
-EFFORTS = ("default", "fastest", "thorough", "recent_all", "best")
+EFFORTS = ("default", "fast", "fastest", "thorough", "max", "recent", "recent_all", "best", "ultra", "extreme")
 DELTAS = (-9, -8, -5, -4, -1, 0, 1, 3, 4, 7, 8)
 LENGTHS = sorted({base + d for base in (ROUND + LOOK, 2 * ROUND + LOOK, CHUNK + LOOK) for d in DELTAS}
                  | {ROUND - 1, ROUND, ROUND + 1, LOOK + 8 * 1024 - 4})
@@ -68,6 +69,7 @@ def test_lengths_cover_every_prefetch_boundary():
     look-ahead) lie inside the strip up to n - 4 and n - 8, so the deltas put n on both sides of both for the last thread
     and of a word's middle; the last round is one step of a few positions behind one, two and four full rounds, or all
     eight steps with the last one a position short (kRound - 1)."""
+    assert sorted(EFFORTS) == sorted(EFFORT_PARAMS) and len(set(EFFORTS)) == len(EFFORTS)
     assert ROUND + LOOK in LENGTHS and 2 * ROUND + LOOK in LENGTHS and CHUNK + LOOK in LENGTHS
     assert len(LENGTHS) == 3 * len(DELTAS) + 3  # (kLook + 8 * 1024 - 4 is kRound + kLook - 4 again)
     for data, bb in _cases().values():
