@@ -226,7 +226,10 @@ class compressor {
   }
   /// A BGZF file decoded (sfh_decompress_bgzf: members of any size; every member's header, ISIZE and CRC-32 verified).
   /// dst.size() >= the members' ISIZEs together (bgzf_read_index); *produced (nullable) = that sum on Success.  A refused call
-  /// or a device problem is Error.
+  /// or a device problem is Error.  Every conforming file decodes in the indexed decoder: members of at most 32768 bytes in
+  /// its narrow rows, a file with a member of up to 65536 bytes (bgzip and htslib write 65280) in its wide rows.  For device
+  /// buffers call sfh_decompress_bgzf_wide_device(native(), ...) -- it reads every conforming file -- or, for files of
+  /// 32 KiB members only, sfh_decompress_bgzf_device (starflate_hip.h).
   auto decompress_bgzf(std::span<const std::byte> src, std::span<std::byte> dst, std::size_t* produced = nullptr) -> DecompressStatus {
     if (!ctx_) return DecompressStatus::Error;
     std::uint32_t st = 0;

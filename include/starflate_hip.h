@@ -43,8 +43,9 @@ enum sfh_status {
                                output (the walk of DESIGN.md 3a ends before it found every segment); nothing was decoded.
                                sfh_dz_read_index* / sfh_decompress_dz*: the gzip header carries no dictzip table of 32 KiB chunks.
                                sfh_decompress_bgzf_device: a member of the BGZF file holds more than 32768 bytes (ISIZE), so it
-                               is no single segment of the indexed decoder; nothing was decoded (sfh_decompress_bgzf, host
-                               buffers, reads such files) */
+                               is no narrow row of the indexed decoder; nothing was decoded (sfh_decompress_bgzf_wide_device
+                               and sfh_decompress_bgzf read such files).  sfh_decompress_bgzf_wide_device: a member claims more
+                               than 65536 bytes, which is not BGZF */
 };
 
 /* block strategy (inverse of src/decompress.cpp:416-458 dispatch) */
@@ -523,13 +524,24 @@ int sfh_bgzf_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sf
  * there for that member alone, in launch batches of at most SFH_BATCH_CHUNKS members.  *status = the DecompressStatus of the
  * first failing member in file order, or 0; a file whose index fails gives that status and nothing is decoded.  *dst_n_out =
  * total_n; total_n > dst_cap is SFH_E_DST_TOO_SMALL.  d_src 4-byte, d_dst 16-byte aligned; three synchronisations of `stream`.
- * A member above 32768 bytes (bgzip writes 65280): sfh_decompress_bgzf_device returns SFH_E_NOT_INDEXABLE and decodes nothing.
- * sfh_decompress_bgzf (host buffers) reads every BGZF file: it walks on the host; members of at most 32768 bytes go up and
- * through the device call (dst is written only when *status is 0); larger ones run as the items of sfh_inflate_stream_batch
- * (SFH_GZIP, dsts[i] = dst + out_off[i], dst_cap[i] = ISIZE_i), the first non-zero item status in order being *status
- * (INTEGRATION.md has the two paths' rates). */
+ * A member above 32768 bytes (bgzip and htslib write 65280, the format allows 65536): sfh_decompress_bgzf_device returns
+ * SFH_E_NOT_INDEXABLE and decodes nothing.
+ * sfh_decompress_bgzf_wide_device reads EVERY conforming BGZF file, ISIZE <= 65536 per member: same arguments, alignment,
+ * synchronisations, *status and messages.  A file without a member above 32768 bytes takes the path above, launch for launch.
+ * A file with one is decoded as a whole on the decoder's WIDE ROWS: a member is still one segment of the same kernels, built a
+ * second time for rows of 65536 output bytes and 65536 tokens (the speculative wave follows 8 blocks with output per member
+ * instead of 4; the lane-serial kernel stands behind it as ever), with two checksum partials per member.  A wide member's
+ * tokens take 256 KiB, so a launch batch holds SFH_BATCH_CHUNKS / 2 members and sfh_last_decode_scratch_bytes keeps its bound.
+ * A member claiming more than 65536 bytes is not BGZF: SFH_E_NOT_INDEXABLE, nothing decoded.
+ * sfh_decompress_bgzf (host buffers) walks on the host and sends the file up and through the device call that fits its widest
+ * member -- at most 32768 bytes: sfh_decompress_bgzf_device; up to 65536: sfh_decompress_bgzf_wide_device -- and dst is
+ * written only when *status is 0.  Only gzip members with a 'BC' field that claim more than 65536 bytes (not BGZF) still run as
+ * the items of sfh_inflate_stream_batch (SFH_GZIP, dsts[i] = dst + out_off[i], dst_cap[i] = ISIZE_i), the first non-zero item
+ * status in order being *status (INTEGRATION.md 1.4 has the rates). */
 int sfh_decompress_bgzf_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_dst, uint64_t dst_cap, uint64_t* dst_n_out,
                                uint32_t* status, void* stream);
+int sfh_decompress_bgzf_wide_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                                    uint32_t* status, void* stream);
 int sfh_decompress_bgzf(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, uint64_t dst_cap, uint64_t* dst_n_out,
                         uint32_t* status);
 

@@ -37,6 +37,7 @@ EXPORTS = [
     "sfh_dz_read_index", "sfh_dz_read_index_device", "sfh_decompress_dz_device", "sfh_decompress_dz", "sfh_decompress_dz_ranges",
     "sfh_bgzf_bound", "sfh_compress_bgzf_device_async", "sfh_compress_bgzf_device", "sfh_compress_bgzf",
     "sfh_bgzf_read_index", "sfh_bgzf_read_index_device", "sfh_decompress_bgzf_device", "sfh_decompress_bgzf",
+    "sfh_decompress_bgzf_wide_device",
     "sfh_recover_index_device", "sfh_recover_index", "sfh_decompress_any_device", "sfh_decompress_any", "sfh_last_recover_stats",
     "sfh_recover_index_batch_device", "sfh_recover_index_batch", "sfh_decompress_any_batch_device", "sfh_decompress_any_batch",
     "sfh_inflate_stream_device", "sfh_inflate_stream", "sfh_inflate_stream_batch_device", "sfh_inflate_stream_batch",
@@ -135,6 +136,8 @@ def lib():
     L.sfh_bgzf_read_index_device.restype = C.c_int
     L.sfh_decompress_bgzf_device.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), vp]
     L.sfh_decompress_bgzf_device.restype = C.c_int
+    L.sfh_decompress_bgzf_wide_device.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), vp]
+    L.sfh_decompress_bgzf_wide_device.restype = C.c_int
     L.sfh_decompress_bgzf.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.sfh_decompress_bgzf.restype = C.c_int
     L.sfh_compress.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]

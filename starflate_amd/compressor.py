@@ -185,8 +185,10 @@ class Compressor:
 
     def decompress_bgzf(self, data):
         """Host buffers: a BGZF file -> (bytes, DecompressStatus int); every member's header, ISIZE and CRC-32 are verified.
-        b"" when the status is not 0.  Members of at most 32 KiB decode as segments of the indexed decoder, larger ones
-        (bgzip's 65280) through the stream decoder (sfh_decompress_bgzf)."""
+        b"" when the status is not 0.  Every BGZF member is one segment of the indexed decoder: in its rows of 32 KiB when no
+        member of the file holds more, else -- bgzip's and htslib's 65280 bytes, the format's 65536 -- in its wide rows of
+        64 KiB (sfh_decompress_bgzf).  Only members claiming more than 65536 bytes, which is not BGZF, go through the stream
+        decoder."""
         src = _as_bytes(data)
         try:
             _, out_off, _ = bgzf_index(src)
@@ -213,6 +215,24 @@ class Compressor:
         n = src.numel()
         self._check(self._lib.sfh_decompress_bgzf_device(self._h, src.data_ptr() if n else None, n, out.data_ptr(), int(total_n),
                                                          C.byref(got), C.byref(st), C.c_void_p(s)))
+        return out, int(got.value), int(st.value)
+
+    def decompress_bgzf_wide_tensor(self, src, total_n, out=None, stream=None):
+        """decompress_bgzf_tensor for every conforming BGZF file: members of up to 65536 bytes (bgzip and htslib write 65280)
+        decode on the device, in the indexed decoder's wide rows (sfh_decompress_bgzf_wide_device); a file without a member
+        above 32 KiB takes decompress_bgzf_tensor's path.  A member claiming more than 65536 bytes raises StarflateError with
+        code -8."""
+        import torch
+
+        self._check_tensor(src)
+        if out is None:
+            out = torch.empty(max(int(total_n), 16), dtype=torch.uint8, device=src.device)
+        self._check_tensor(out)
+        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
+        got, st = C.c_uint64(0), C.c_uint32(0)
+        n = src.numel()
+        self._check(self._lib.sfh_decompress_bgzf_wide_device(self._h, src.data_ptr() if n else None, n, out.data_ptr(), int(total_n),
+                                                              C.byref(got), C.byref(st), C.c_void_p(s)))
         return out, int(got.value), int(st.value)
 
     # ---- many independent items, each its own stream, in one call (sfh_compress_batch*) ----

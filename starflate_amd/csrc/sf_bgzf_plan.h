@@ -49,6 +49,12 @@ SF_BGZF_HD uint64_t bound(uint64_t n) {
   return m * (uint64_t)(kMemberInput + kMemberInput / 8 + 640 + kWrap) + kEofBytes;
 }
 
+// The reader's wide rows (a file with a member above kMemberInput bytes of output; kMaxMember at most).  A wide member's tokens
+// take twice a narrow one's scratch, so a launch batch of `batch_chunks` narrow members holds half as many wide ones (one at
+// least); and the checksum partials stay per kMemberInput bytes: two rows per wide member, 2 i and 2 i + 1.
+SF_BGZF_HD uint32_t wide_batch(uint32_t batch_chunks) { return batch_chunks / 2 ? batch_chunks / 2 : 1u; }
+SF_BGZF_HD uint64_t checksum_rows(uint64_t members, bool wide) { return wide ? 2 * members : members; }
+
 SF_BGZF_HD uint32_t le16(const uint8_t* p) { return p[0] | (uint32_t)p[1] << 8; }  // (no alignment assumed)
 SF_BGZF_HD uint32_t le32(const uint8_t* p) { return le16(p) | le16(p + 2) << 16; }
 

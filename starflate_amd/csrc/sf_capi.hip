@@ -2712,8 +2712,13 @@ int sfh_bgzf_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sf
   return SFH_OK;
 }
 
-int sfh_decompress_bgzf_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_dst, uint64_t dst_cap, uint64_t* dst_n_out,
-                               uint32_t* status, void* stream) {
+namespace {
+// sfh_decompress_bgzf_device (widest = kChunk) and sfh_decompress_bgzf_wide_device (kWideRow): a file with a member above
+// `widest` bytes is refused.  A file whose members all fit kChunk takes the narrow rows whichever call it came through; one
+// with a member above that is decoded on wide rows as a whole: tokens kWideRow apart (so a launch batch holds half as many
+// members and the token scratch keeps its bound), two checksum partials per member.
+int bgzf_decode_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                       uint32_t* status, void* stream, uint32_t widest) {
   if (!ctx || (!d_src && src_n) || !dst_n_out || !status || (!d_dst && dst_cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   if (((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & 15)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, dst 16)", hipSuccess);
   *dst_n_out = 0;
@@ -2735,18 +2740,23 @@ int sfh_decompress_bgzf_device(sfh_ctx* ctx, const void* d_src, size_t src_n, vo
     snprintf(ctx->err, sizeof ctx->err, "BGZF members: DecompressStatus %u", r.status);
     return SFH_OK;
   }
-  if (r.max_isize > sf::kChunk)
-    return fail(ctx, SFH_E_NOT_INDEXABLE, "a BGZF member above 32768 bytes (sfh_decompress_bgzf reads such files)", hipSuccess);
+  if (r.max_isize > widest)
+    return fail(ctx, SFH_E_NOT_INDEXABLE,
+                widest == sf::kChunk ? "a BGZF member above 32768 bytes (sfh_decompress_bgzf_wide_device and sfh_decompress_bgzf read such files)"
+                                     : "a member above 65536 bytes: not BGZF", hipSuccess);
+  const bool wide = r.max_isize > sf::kChunk;
   if (r.total_n > dst_cap) return fail(ctx, SFH_E_DST_TOO_SMALL, "the members' ISIZEs above dst_cap", hipSuccess);
   // every member one index-free gzip item of one segment; the rows are written on the device, from the device's index
-  const uint32_t m = r.members, per = ctx->batch_chunks;
+  const uint32_t m = r.members, per = wide ? sf::bgzf::wide_batch(ctx->batch_chunks) : ctx->batch_chunks;
+  if (wide && m > 0x7FFFFFFFu) return fail(ctx, SFH_E_INVALID_ARG, "2^31 members or more", hipSuccess);
+  const uint32_t row = wide ? sf::kWideRow : sf::kChunk, nsums = (uint32_t)sf::bgzf::checksum_rows(m, wide);
   const size_t o_items = (size_t)m * sizeof(sf::InflateSeg), o_clips = o_items + (size_t)m * sizeof(sf::InflateItem);
-  const size_t o_sums = o_clips + (size_t)m * sizeof(sf::InflateClip), o_implied = o_sums + (size_t)m * sizeof(sf::BatchChunk);
+  const size_t o_sums = o_clips + (size_t)m * sizeof(sf::InflateClip), o_implied = o_sums + (size_t)nsums * sizeof(sf::BatchChunk);
   const size_t o_strips = o_implied + (size_t)m * 2 * sizeof(uint64_t), o_status = o_strips + (size_t)m * sizeof(sf::InflateStrip);
   int rc = grow(ctx, &ctx->d_bgzfrows, &ctx->d_bgzfrows_cap, o_status + (size_t)m * sizeof(uint32_t), "BGZF decoder rows");
   if (!rc) rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, (size_t)m * sizeof(sf::SegInfo), "segment records");
-  if (!rc) rc = ensure_dtok(ctx, std::min(m, per));
-  if (!rc) rc = ensure_sums(ctx, m);
+  if (!rc) rc = ensure_dtok(ctx, std::min(m, per) * (row / sf::kChunk));
+  if (!rc) rc = ensure_sums(ctx, nsums);
   if (rc) return rc;
   uint8_t* R = ctx->d_bgzfrows;
   sf::InflateSeg* segs = (sf::InflateSeg*)R;
@@ -2760,20 +2770,31 @@ int sfh_decompress_bgzf_device(sfh_ctx* ctx, const void* d_src, size_t src_n, vo
   ctx->bix_valid = false;
   ctx->ev_inf_valid = false;
   ctx->last_chunks = m;
-  ctx->last_dtok_bytes = (size_t)std::min(m, per) * sf::kChunk * sizeof(uint32_t);
-  SF_HIP(sf::launch_bgzf_rows((const uint8_t*)d_src, member_off, out_off, m, per, (uint8_t*)d_dst, segs, items, clips, strips, sums, implied, s),
-         "launch k_bgzf_rows");
+  ctx->last_dtok_bytes = (size_t)std::min(m, per) * row * sizeof(uint32_t);
+  if (wide)
+    SF_HIP(sf::launch_bgzf_rows_wide((const uint8_t*)d_src, member_off, out_off, m, per, (uint8_t*)d_dst, segs, items, clips, strips, sums, implied, s),
+           "launch k_bgzf_rows");
+  else
+    SF_HIP(sf::launch_bgzf_rows((const uint8_t*)d_src, member_off, out_off, m, per, (uint8_t*)d_dst, segs, items, clips, strips, sums, implied, s),
+           "launch k_bgzf_rows");
   for (uint32_t b0 = 0; b0 < m; b0 += per) {
     const uint32_t nb = std::min(per, m - b0);
     sf::SegInfo* binfo = ctx->ws.seginfo + b0;
+    if (wide) {
+      SF_HIP(sf::launch_inflate_tokens_wide(segs + b0, nb, ctx->ws.tokens, binfo, !ctx->inflate_serial, s), "launch k_inflate_tokens");
+      SF_HIP(sf::launch_inflate_bytes_wide(segs + b0, r.unaligned ? clips + b0 : nullptr, strips + b0, nb, ctx->ws.tokens, binfo, s),
+             "launch k_inflate_bytes");
+      continue;
+    }
     SF_HIP(sf::launch_inflate_tokens(segs + b0, nb, ctx->ws.tokens, binfo, false, !ctx->inflate_serial, s), "launch k_inflate_tokens");
     // (a foreign file's ISIZEs may leave a member's output off a 16-byte boundary: the byte stage with a write window)
     if (r.unaligned) SF_HIP(sf::launch_inflate_bytes_clip(segs + b0, clips + b0, strips + b0, nb, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes_clip");
     else SF_HIP(sf::launch_inflate_bytes(segs + b0, strips + b0, nb, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes");
   }
-  if (r.unaligned) SF_HIP(sf::launch_checksum_batch_any(sums, m, ctx->ws.sums, s), "launch k_checksum");
-  else SF_HIP(sf::launch_checksum_batch(sums, m, SFH_GZIP, ctx->ws.sums, s), "launch k_checksum");
-  SF_HIP(sf::launch_inflate_fold(items, m, ctx->ws.seginfo, ctx->ws.sums, SFH_GZIP, d_status, nullptr, s), "launch k_inflate_fold");
+  if (r.unaligned) SF_HIP(sf::launch_checksum_batch_any(sums, nsums, ctx->ws.sums, s), "launch k_checksum");
+  else SF_HIP(sf::launch_checksum_batch(sums, nsums, SFH_GZIP, ctx->ws.sums, s), "launch k_checksum");
+  if (wide) SF_HIP(sf::launch_inflate_fold_wide(items, m, ctx->ws.seginfo, ctx->ws.sums, SFH_GZIP, d_status, s), "launch k_inflate_fold");
+  else SF_HIP(sf::launch_inflate_fold(items, m, ctx->ws.seginfo, ctx->ws.sums, SFH_GZIP, d_status, nullptr, s), "launch k_inflate_fold");
   SF_HIP(sf::launch_bgzf_first(d_status, m, ctx->d_value, s), "launch k_bgzf_first");
   uint32_t res[2] = {0, 0};
   SF_HIP(hipMemcpyAsync(res, ctx->d_value, sizeof res, hipMemcpyDeviceToHost, s), "copy status");
@@ -2783,6 +2804,17 @@ int sfh_decompress_bgzf_device(sfh_ctx* ctx, const void* d_src, size_t src_n, vo
   if (res[0] == 0) *dst_n_out = r.total_n;
   else snprintf(ctx->err, sizeof ctx->err, "BGZF member %u: DecompressStatus %u", res[1], res[0]);
   return SFH_OK;
+}
+}  // namespace
+
+int sfh_decompress_bgzf_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                               uint32_t* status, void* stream) {
+  return bgzf_decode_device(ctx, d_src, src_n, d_dst, dst_cap, dst_n_out, status, stream, sf::kChunk);
+}
+
+int sfh_decompress_bgzf_wide_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_dst, uint64_t dst_cap, uint64_t* dst_n_out,
+                                    uint32_t* status, void* stream) {
+  return bgzf_decode_device(ctx, d_src, src_n, d_dst, dst_cap, dst_n_out, status, stream, sf::kWideRow);
 }
 
 int sfh_decompress_bgzf(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, uint64_t dst_cap, uint64_t* dst_n_out,
@@ -2809,7 +2841,8 @@ int sfh_decompress_bgzf(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, 
   }
   if (I.total_n > dst_cap) return fail(ctx, SFH_E_DST_TOO_SMALL, "the members' ISIZEs above dst_cap", hipSuccess);
   if (I.members == 0) return SFH_OK;
-  if (I.max_isize <= sf::kChunk) {  // the device path
+  if (I.max_isize <= sf::kWideRow) {  // the device path: narrow rows, or wide ones for a file with a member above 32768 bytes
+    const bool wide = I.max_isize > sf::kChunk;
     SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
     int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, src_n, "input staging");
     if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, I.total_n ? I.total_n : 16, "output staging");
@@ -2817,15 +2850,15 @@ int sfh_decompress_bgzf(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, 
     hipStream_t s = ctx->stream;
     if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
     SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, s), "H2D");
-    if ((rc = sfh_decompress_bgzf_device(ctx, ctx->d_in, src_n, ctx->d_out, I.total_n, dst_n_out, status, s))) return rc;
+    if ((rc = bgzf_decode_device(ctx, ctx->d_in, src_n, ctx->d_out, I.total_n, dst_n_out, status, s, wide ? sf::kWideRow : sf::kChunk))) return rc;
     if (*status == 0 && I.total_n) {
       SF_HIP(hipMemcpyAsync(dst, ctx->d_out, I.total_n, hipMemcpyDeviceToHost, s), "D2H");
       SF_HIP(hipStreamSynchronize(s), "stream sync");
     }
     return SFH_OK;
   }
-  // members above 32 KiB (bgzip's 65280): each one an item of the stream decoder, into a buffer of the call's own so that dst
-  // is written only when every member decoded
+  // a member above 64 KiB (gzip members with BGZF's extra field, but not BGZF): each one an item of the stream decoder, into a
+  // buffer of the call's own so that dst is written only when every member decoded
   const size_t m = I.members;
   std::vector<uint8_t> out;
   std::vector<const void*> srcs;

@@ -477,11 +477,15 @@ __global__ __launch_bounds__(256) void k_inflate_head(InflateItem* __restrict__ 
 }
 
 // sfh_decompress_bgzf_device: one lane per member (its bytes [member_off[i], member_off[i + 1]) of the file, its output
-// out_off[i] .. out_off[i + 1], at most 32768 bytes: one segment).  The member is an index-free gzip item of
+// out_off[i] .. out_off[i + 1], at most 32768 bytes -- WIDE: 65536 --: one segment).  The member is an index-free gzip item of
 // sfh_decompress_batch, checked by gzip_head on its own bytes -- but its segment row reads the FILE: the bit reader needs a
 // 4-byte aligned base and takes any offset, so the implied entries (body start, trailer start) and the read limit are
 // absolute.  Beside the segment row its write window (all of it: k_inflate_bytes_clip takes any destination alignment), its
 // strip of one (numbered within its launch batch of `per_batch` rows) and its checksum row.
+// WIDE (sfh_decompress_bgzf_wide_device): a member holds up to kWideRow bytes -- still one segment, in a wide row of the
+// decoder, but TWO checksum rows, sums[2 i] its first kChunk bytes and sums[2 i + 1] the rest (empty for a member that has no
+// more): the partials are per kChunk, and k_inflate_fold_wide folds the two.
+template <bool WIDE>
 __global__ __launch_bounds__(256) void k_bgzf_rows(const uint8_t* __restrict__ src, const uint64_t* __restrict__ member_off,
                                                    const uint64_t* __restrict__ out_off, uint32_t nmembers, uint32_t per_batch,
                                                    uint8_t* __restrict__ dst, InflateSeg* __restrict__ segs,
@@ -502,7 +506,13 @@ __global__ __launch_bounds__(256) void k_bgzf_rows(const uint8_t* __restrict__ s
   segs[i] = InflateSeg{src, ix, nullptr, dst + o, a + (n > 8 ? n - 8 : 0), on, kSegWrapped};
   clips[i] = InflateClip{dst + o, 0u, on};
   strips[i] = InflateStrip{i % per_batch, 1u};
-  sums[i] = BatchChunk{dst + o, on, 0u};
+  if constexpr (WIDE) {
+    const uint32_t n0 = on < kChunk ? on : kChunk;
+    sums[2 * (uint64_t)i] = BatchChunk{dst + o, n0, 0u};
+    sums[2 * (uint64_t)i + 1] = BatchChunk{dst + o + n0, on - n0, 0u};
+  } else {
+    sums[i] = BatchChunk{dst + o, on, 0u};
+  }
 }
 
 // One workgroup per item, behind every launch batch: the first failing segment in the item's stream order (what the serial
@@ -510,10 +520,12 @@ __global__ __launch_bounds__(256) void k_bgzf_rows(const uint8_t* __restrict__ s
 // folded from k_checksum_batch's partials by wrap_stream -- the compressor's fold -- against the trailer's.
 // first (nullable): per item the number of that segment in the item, 0xFFFFFFFF when none failed (sfh_decompress_device's
 // message names it).
-__global__ __launch_bounds__(KW_THREADS) void k_inflate_fold(const InflateItem* __restrict__ items, const SegInfo* __restrict__ info,
-                                                             const uint32_t* __restrict__ sums, uint32_t kind,
-                                                             uint32_t* __restrict__ status, uint32_t* __restrict__ first,
-                                                             uint32_t chunk_op) {
+// SUMS: checksum partials per segment record (2: wide rows of one segment per item, k_bgzf_rows<true>).
+template <uint32_t SUMS>
+__device__ __forceinline__ void inflate_fold(const InflateItem* __restrict__ items, const SegInfo* __restrict__ info,
+                                             const uint32_t* __restrict__ sums, uint32_t kind,
+                                             uint32_t* __restrict__ status, uint32_t* __restrict__ first,
+                                             uint32_t chunk_op) {
   __shared__ uint32_t s_first, s_sum;
   const uint32_t t = threadIdx.x;
   const InflateItem I = items[blockIdx.x];
@@ -531,7 +543,7 @@ __global__ __launch_bounds__(KW_THREADS) void k_inflate_fold(const InflateItem* 
     // the checksum of what was decoded: gzip's first ISIZE bytes (k_inflate_head cut the rows down to them), else all
     const uint64_t n = (kind == kChecksumCrc32 && I.isize < I.dst_n) ? I.isize : I.dst_n;
     const uint32_t nch = n ? (uint32_t)((n + kChunk - 1) / kChunk) : 1u;
-    wrap_stream(sums + I.seg0, nch, n, kind, nullptr, nullptr, &s_sum, chunk_op);
+    wrap_stream(sums + (uint64_t)SUMS * I.seg0, nch, n, kind, nullptr, nullptr, &s_sum, chunk_op);
     __syncthreads();
     if (s_sum != I.want) st = kStError;
   }
@@ -539,6 +551,19 @@ __global__ __launch_bounds__(KW_THREADS) void k_inflate_fold(const InflateItem* 
     status[blockIdx.x] = st;
     if (first) first[blockIdx.x] = f;
   }
+}
+
+__global__ __launch_bounds__(KW_THREADS) void k_inflate_fold(const InflateItem* __restrict__ items, const SegInfo* __restrict__ info,
+                                                             const uint32_t* __restrict__ sums, uint32_t kind,
+                                                             uint32_t* __restrict__ status, uint32_t* __restrict__ first,
+                                                             uint32_t chunk_op) {
+  inflate_fold<1>(items, info, sums, kind, status, first, chunk_op);
+}
+
+__global__ __launch_bounds__(KW_THREADS) void k_inflate_fold_wide(const InflateItem* __restrict__ items, const SegInfo* __restrict__ info,
+                                                                  const uint32_t* __restrict__ sums, uint32_t kind,
+                                                                  uint32_t* __restrict__ status, uint32_t chunk_op) {
+  inflate_fold<2>(items, info, sums, kind, status, nullptr, chunk_op);
 }
 
 }  // namespace
@@ -552,6 +577,12 @@ hipError_t launch_inflate_head(InflateItem* items, uint32_t nitems, uint32_t con
 hipError_t launch_inflate_fold(const InflateItem* items, uint32_t nitems, const SegInfo* info, const uint32_t* sums,
                                uint32_t container, uint32_t* status, uint32_t* first, hipStream_t s) {
   hipLaunchKernelGGL(k_inflate_fold, dim3(nitems), dim3(KW_THREADS), 0, s, items, info, sums, container, status, first, kChunkOp);
+  return hipGetLastError();
+}
+
+hipError_t launch_inflate_fold_wide(const InflateItem* items, uint32_t nitems, const SegInfo* info, const uint32_t* sums,
+                                    uint32_t container, uint32_t* status, hipStream_t s) {
+  hipLaunchKernelGGL(k_inflate_fold_wide, dim3(nitems), dim3(KW_THREADS), 0, s, items, info, sums, container, status, kChunkOp);
   return hipGetLastError();
 }
 
@@ -604,8 +635,16 @@ hipError_t launch_bgzf_wrap(const uint32_t* sums, const uint64_t* offsets, uint3
 hipError_t launch_bgzf_rows(const uint8_t* src, const uint64_t* member_off, const uint64_t* out_off, uint32_t nmembers,
                             uint32_t per_batch, uint8_t* dst, InflateSeg* segs, InflateItem* items, InflateClip* clips,
                             InflateStrip* strips, BatchChunk* sums, uint64_t* implied, hipStream_t s) {
-  hipLaunchKernelGGL(k_bgzf_rows, dim3((nmembers + 255) / 256), dim3(256), 0, s, src, member_off, out_off, nmembers, per_batch, dst, segs,
+  hipLaunchKernelGGL(k_bgzf_rows<false>, dim3((nmembers + 255) / 256), dim3(256), 0, s, src, member_off, out_off, nmembers, per_batch, dst, segs,
                      items, clips, strips, sums, implied);
+  return hipGetLastError();
+}
+
+hipError_t launch_bgzf_rows_wide(const uint8_t* src, const uint64_t* member_off, const uint64_t* out_off, uint32_t nmembers,
+                                 uint32_t per_batch, uint8_t* dst, InflateSeg* segs, InflateItem* items, InflateClip* clips,
+                                 InflateStrip* strips, BatchChunk* sums, uint64_t* implied, hipStream_t s) {
+  hipLaunchKernelGGL(k_bgzf_rows<true>, dim3((nmembers + 255) / 256), dim3(256), 0, s, src, member_off, out_off, nmembers, per_batch, dst,
+                     segs, items, clips, strips, sums, implied);
   return hipGetLastError();
 }
 

@@ -37,6 +37,7 @@ namespace sf {
 
 constexpr uint32_t kChunk = 32768;      // bytes per DEFLATE block (byte-aligned in the stream)
 constexpr uint32_t kWindow = 32768;     // a match reaches back at most this far, and never before its strip
+constexpr uint32_t kWideRow = 65536;    // the decoder's wide rows: a foreign BGZF member's output (bgzip: 65280), and its tokens
 constexpr uint32_t kStep = 1024;        // positions per hash-insertion step (= K1 threads)
 constexpr uint32_t kHashBits = 13;      // buckets of two 16-bit history levels each (32 KiB of LDS)
 constexpr uint32_t kMaxStrip = 1u << 24;  // largest block_bytes
@@ -319,6 +320,10 @@ hipError_t launch_bgzf_walk(const uint8_t* src, uint64_t src_n, const uint32_t* 
 hipError_t launch_bgzf_rows(const uint8_t* src, const uint64_t* member_off, const uint64_t* out_off, uint32_t nmembers,
                             uint32_t per_batch, uint8_t* dst, InflateSeg* segs, InflateItem* items, InflateClip* clips,
                             InflateStrip* strips, BatchChunk* sums, uint64_t* implied, hipStream_t s);
+// ... for members of up to kWideRow bytes: TWO checksum rows per member (sums[2 i], sums[2 i + 1]: its first 32 KiB, the rest)
+hipError_t launch_bgzf_rows_wide(const uint8_t* src, const uint64_t* member_off, const uint64_t* out_off, uint32_t nmembers,
+                                 uint32_t per_batch, uint8_t* dst, InflateSeg* segs, InflateItem* items, InflateClip* clips,
+                                 InflateStrip* strips, BatchChunk* sums, uint64_t* implied, hipStream_t s);
 hipError_t launch_bgzf_first(const uint32_t* status, uint32_t m, uint32_t* res, hipStream_t s);
 hipError_t launch_checksum_batch_any(const BatchChunk* chunks, uint32_t nchunks, uint32_t* sums, hipStream_t s);  // CRC-32, any alignment
 // batched: sums[c] for the call's chunk table; one k_wrap workgroup per item (header at dst, trailer at d_total[out])
@@ -333,6 +338,12 @@ hipError_t launch_inflate_tokens(const InflateSeg* rows, uint32_t nseg, uint32_t
                                  hipStream_t s);
 hipError_t launch_inflate_bytes(const InflateSeg* rows, const InflateStrip* strips, uint32_t nstrips, const uint32_t* tokens,
                                 SegInfo* info, hipStream_t s);
+// the same two stages on wide rows: segments of up to kWideRow bytes, tokens [nseg][kWideRow], index only; clips: null, or
+// every row's write window
+hipError_t launch_inflate_tokens_wide(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool speculate,
+                                      hipStream_t s);
+hipError_t launch_inflate_bytes_wide(const InflateSeg* rows, const InflateClip* clips, const InflateStrip* strips, uint32_t nstrips,
+                                     const uint32_t* tokens, SegInfo* info, hipStream_t s);
 // ---- sf_unindexed.hip: the segment index recovered from the stream ----
 uint32_t any_scan_waves(uint64_t src_n);  // waves (per-wave counts) of k_any_scan over a buffer of src_n bytes
 size_t any_scan_tmp_words(uint32_t n);    // words of `tmp` launch_scan_u32 needs for n elements
@@ -400,6 +411,9 @@ hipError_t launch_inflate_head(InflateItem* items, uint32_t nitems, uint32_t con
 // first (nullable): per item, its first failing segment (0xFFFFFFFF: none)
 hipError_t launch_inflate_fold(const InflateItem* items, uint32_t nitems, const SegInfo* info, const uint32_t* sums,
                                uint32_t container, uint32_t* status, uint32_t* first, hipStream_t s);
+// items of one wide segment each (launch_bgzf_rows_wide): segment record seg0, checksum partials 2 * seg0 and 2 * seg0 + 1
+hipError_t launch_inflate_fold_wide(const InflateItem* items, uint32_t nitems, const SegInfo* info, const uint32_t* sums,
+                                    uint32_t container, uint32_t* status, hipStream_t s);
 // random access: the byte stage with a write window per row, and every range's status (its span's first failing segment)
 hipError_t launch_inflate_bytes_clip(const InflateSeg* rows, const InflateClip* clips, const InflateStrip* strips, uint32_t nstrips,
                                      const uint32_t* tokens, SegInfo* info, hipStream_t s);

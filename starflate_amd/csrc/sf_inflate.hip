@@ -63,7 +63,8 @@ __device__ __forceinline__ T* row_ptr(T* p) {
 
 // Segment `seg` of the launch batch is rows[seg]: its stream, index entries, size and history.
 // EXACT: a row flagged kSegExact decodes with decode_segment<true> (the recovered index's end rule).
-template <bool EXACT = false>
+// ROW: tokens (and output bytes) a row holds at most -- the stride of the token scratch (kWideRow: BGZF members of up to 64 KiB).
+template <bool EXACT = false, uint32_t ROW = kChunk>
 __global__ __launch_bounds__(KT_LANES) void k_inflate_tokens(const InflateSeg* __restrict__ rows, uint32_t nseg,
                                                             uint32_t* __restrict__ tokens, SegInfo* __restrict__ info,
                                                             uint32_t only_retry) {
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(KT_LANES) void k_inflate_tokens(const InflateSeg* _
   uint32_t hist = R.hist & ~kSegWrapped;
   const bool wrapped = (R.hist & kSegWrapped) != 0;
   if constexpr (EXACT) hist &= ~kSegExact;
-  uint32_t* const seg_tokens = tokens + (uint64_t)seg * kChunk;
+  uint32_t* const seg_tokens = tokens + (uint64_t)seg * ROW;
   uint8_t* const lane_m = s_tables + threadIdx.x * inflate::LaneLayout::kBytes;
   inflate::SegmentResult r;
   if constexpr (EXACT) {
@@ -604,6 +605,9 @@ constexpr uint32_t kBlkNone = 0, kBlkEnd = 1, kBlkStored = 2, kBlkCoded = 3;
 // costs the wave its tables and three passes, so a segment cut into dozens of small blocks (zlib with memLevel 1: a block
 // every 127 symbols) is the lane-serial kernel's, and is handed over after four turns rather than after dozens.
 constexpr uint32_t kSpecMaxBlocks = 4;
+// ... of a wide row (65536 bytes at most): zlib cuts a block every 16383 symbols, so bgzip's 65280-byte member of poorly
+// compressible data has four blocks and more
+constexpr uint32_t kSpecMaxBlocksWide = 8;
 
 template <class L>
 __device__ BlockOpen open_block(const uint8_t* src, uint64_t src_n, uint64_t lo, uint64_t hi, uint32_t at, uint8_t* m) {
@@ -671,7 +675,8 @@ enum : uint32_t { kSegRun = 0, kSegDone = 1, kSegRetry = 2 };
 // As k_inflate_tokens_sub: each half's row gives its stream, index entries, size and history.
 // EXACT: a row flagged kSegExact counts as done only when its blocks end on its last bit, none of them final; anything else
 // goes to k_inflate_tokens<true>, which says what is wrong (decode_segment<true>)
-template <bool EXACT>
+// ROW: see k_inflate_tokens; MAXBLK: blocks with output the wave follows.
+template <bool EXACT, uint32_t ROW = kChunk, uint32_t MAXBLK = kSpecMaxBlocks>
 __device__ __forceinline__ void tokens_wave_spec(const InflateSeg* __restrict__ rows, uint32_t nseg, uint32_t* __restrict__ tokens,
                                                  SegInfo* __restrict__ info) {
   using L = inflate::SharedLayout;
@@ -753,7 +758,7 @@ __device__ __forceinline__ void tokens_wave_spec(const InflateSeg* __restrict__ 
     return kSegRun;
   };
 #pragma nounroll
-  for (uint32_t blk = 0; blk < kSpecMaxBlocks; ++blk) {
+  for (uint32_t blk = 0; blk < MAXBLK; ++blk) {
     __syncthreads();  // (the tables and records of the block before are read, the states are written)
     fresh();
     if (__ballot(S.state == kSegRun) == 0) break;
@@ -783,7 +788,7 @@ __device__ __forceinline__ void tokens_wave_spec(const InflateSeg* __restrict__ 
           } else if (raw) {
             state = b.len ? (uint32_t)kSegRetry : state;  // (cannot happen: a raw segment has no bytes left)
           } else {
-            uint32_t* seg_tokens = tokens + (uint64_t)seg * kChunk + tok_base;
+            uint32_t* seg_tokens = tokens + (uint64_t)seg * ROW + tok_base;
             const uint8_t* from = src + S.lo + b.data_byte;
             for (uint32_t k = hl; k < b.len; k += 32) seg_tokens[k] = from[k];
             tok_base += b.len;
@@ -838,7 +843,7 @@ __device__ __forceinline__ void tokens_wave_spec(const InflateSeg* __restrict__ 
       entry = nom0;
       const uint32_t back = nom0 - hdr < kSpecLookBack ? nom0 - hdr : kSpecLookBack;
       const bool look = take && back != 0;
-      decode_regions_lockstep<L, true>(src, src_n, S.lo, S.hi, nom0 - back, nom0, false, 0u, kChunk, nullptr, m, half, 0x40000000u,
+      decode_regions_lockstep<L, true>(src, src_n, S.lo, S.hi, nom0 - back, nom0, false, 0u, ROW, nullptr, m, half, 0x40000000u,
                                        look, lane, s_reg, o);
       if (look && o.st == inflate::kOk && !o.eob) entry = o.bit;
     }
@@ -911,7 +916,7 @@ __device__ __forceinline__ void tokens_wave_spec(const InflateSeg* __restrict__ 
     {
       const uint32_t ob = S.out_base + bsum - nbytes;
       decode_regions_lockstep<L, false>(src, src_n, S.lo, S.hi, entry, exitb, hl == 31, ob, ob + nbytes,
-                                        tokens + (uint64_t)seg * kChunk + S.tok_base + (tsum - cnt), m, half, hist, go,
+                                        tokens + (uint64_t)seg * ROW + S.tok_base + (tsum - cnt), m, half, hist, go,
                                         lane, s_reg, o);
     }
     fresh();
@@ -959,6 +964,17 @@ __global__ __launch_bounds__(64, 2) void k_inflate_tokens_spec_exact(const Infla
   tokens_wave_spec<true>(rows, nseg, tokens, info);
 }
 
+// Wide rows (sfh_decompress_bgzf_wide_device): a segment of up to kWideRow bytes, its tokens kWideRow apart.  Nothing in the wave
+// depends on the output size -- the lanes split the block's BITS, and a segment's stream stays below 64 KiB (BSIZE is 16 bits).
+// Two segments per wave, as above.  (One segment per wave, 64 lanes to a block's bits, was built and measured on 256 MiB in
+// zlib -6 members of 65280 bytes, whole call: text 3.73 ms against 4.14, real bytes 5.47 ms against 5.32, either beyond the
+// spread of 7 repeats.  Faster on one input, slower on the other: not kept.  INTEGRATION.md 1.4.)
+__attribute__((amdgpu_waves_per_eu(5, 5)))
+__global__ __launch_bounds__(64, 2) void k_inflate_tokens_spec_wide(const InflateSeg* __restrict__ rows, uint32_t nseg,
+                                                                   uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
+  tokens_wave_spec<false, kWideRow, kSpecMaxBlocksWide>(rows, nseg, tokens, info);
+}
+
 __device__ __forceinline__ uint32_t load_word_guarded(const uint8_t* base, uint64_t src_n, uint64_t w) {
   const uint64_t b = 4 * w;
   if (b + 4 <= src_n) return reinterpret_cast<const uint32_t*>(base)[w];
@@ -985,7 +1001,8 @@ __device__ __forceinline__ uint32_t load_word_guarded(const uint8_t* base, uint6
 // CLIP (k_inflate_bytes_clip): of the segment's bytes only [clips[seg].lo, clips[seg].hi) are written, byte lo at
 // clips[seg].dst, which has any alignment; an empty window: the segment is resolved into the ring for the ones behind it and
 // nothing of it reaches global memory.
-template <bool CLIP>
+// ROW: the stride of the token scratch, and the most a segment holds (kWideRow: see ring()).
+template <bool CLIP, uint32_t ROW = kChunk>
 __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t src_n, const uint32_t* __restrict__ tokens,
                                       SegInfo* __restrict__ info, uint32_t seg, uint32_t segbase, uint32_t rb, uint8_t* s_dyn,
                                       const InflateSeg* __restrict__ rows, const InflateClip* __restrict__ clips) {
@@ -1005,7 +1022,8 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
   static_assert(kWords <= 128 && KB_SPAN % 32 == 0, "one wave scans the bitmap, two words per lane");
   const uint32_t t = threadIdx.x, lane = t & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  // ring index of the segment's byte q (q < kChunk + kRing)
+  // ring index of the segment's byte q (q <= ROW: rb + q < 3 * kRing)
+  static_assert(ROW <= 2 * KB_RING, "ring(): two conditional subtractions");
   auto ring = [&](uint32_t q) -> uint32_t {
     uint32_t a = rb + q;
     a = a >= kRing ? a - kRing : a;
@@ -1078,7 +1096,7 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
   }
 
   const uint32_t ntok = si.ntok;
-  const uint32_t* tk = tokens + (uint64_t)seg * kChunk;
+  const uint32_t* tk = tokens + (uint64_t)seg * ROW;
   uint32_t tok_base = 0, pos0 = 0;  // uniform: first token / output byte of the step
   uint32_t flushed = 0;             // uniform: bytes of the segment already in dst (a multiple of 4)
   bool bad = false;
@@ -1345,6 +1363,8 @@ __device__ bool inflate_segment_bytes(const uint8_t* __restrict__ src, uint64_t 
 
 // The byte-copy kernel: one workgroup per row of the strip table (its segments are one item's, in order; a strip of one:
 // an independent segment), the window carried in LDS from one segment to the next.
+// ROW = kWideRow: rows of up to 64 KiB (a strip of them: every segment but the last holds ROW bytes, as with kChunk).
+template <uint32_t ROW = kChunk>
 __global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes(const InflateSeg* __restrict__ rows,
                                                               const InflateStrip* __restrict__ strips,
                                                               const uint32_t* __restrict__ tokens, SegInfo* __restrict__ info) {
@@ -1354,14 +1374,14 @@ __global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes(const InflateSeg* 
   const uint64_t src_n = rows[S.seg0].src_n;
   uint32_t rb = 0;
   for (uint32_t k = 0; k < S.nseg; ++k) {
-    if (!inflate_segment_bytes<false>(src, src_n, tokens, info, S.seg0 + k, k * kChunk, rb, s_dyn, rows, nullptr)) {
+    if (!inflate_segment_bytes<false, ROW>(src, src_n, tokens, info, S.seg0 + k, k * ROW, rb, s_dyn, rows, nullptr)) {
       // the later segments of the strip depend on this one: they fail with it (first failure in stream order is what
       // the caller sees, k_inflate_fold)
       for (uint32_t j = k + 1 + threadIdx.x; j < S.nseg; j += KB_THREADS)
         if (info[S.seg0 + j].status == inflate::kOk) info[S.seg0 + j].status = inflate::kError;
       return;
     }
-    rb += kChunk;
+    rb += ROW % KB_RING;
     rb = rb >= KB_RING ? rb - KB_RING : rb;
     __syncthreads();  // the segment's window writes precede the next segment's reads
   }
@@ -1370,6 +1390,7 @@ __global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes(const InflateSeg* 
 // sfh_decompress_range*: as k_inflate_bytes, every row with its write window.  The rows of a strip are the segments
 // of one range's decode span inside one strip of the stream: those in front of the range's first byte have an empty
 // window and are only resolved into the ring.
+template <uint32_t ROW = kChunk>
 __global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes_clip(const InflateSeg* __restrict__ rows,
                                                                    const InflateClip* __restrict__ clips,
                                                                    const InflateStrip* __restrict__ strips,
@@ -1381,12 +1402,12 @@ __global__ __launch_bounds__(KB_THREADS) void k_inflate_bytes_clip(const Inflate
   const uint64_t src_n = rows[S.seg0].src_n;
   uint32_t rb = 0;
   for (uint32_t k = 0; k < S.nseg; ++k) {
-    if (!inflate_segment_bytes<true>(src, src_n, tokens, info, S.seg0 + k, k * kChunk, rb, s_dyn, rows, clips)) {
+    if (!inflate_segment_bytes<true, ROW>(src, src_n, tokens, info, S.seg0 + k, k * ROW, rb, s_dyn, rows, clips)) {
       for (uint32_t j = k + 1 + threadIdx.x; j < S.nseg; j += KB_THREADS)
         if (info[S.seg0 + j].status == inflate::kOk) info[S.seg0 + j].status = inflate::kError;
       return;
     }
-    rb += kChunk;
+    rb += ROW % KB_RING;
     rb = rb >= KB_RING ? rb - KB_RING : rb;
     __syncthreads();
   }
@@ -1410,17 +1431,21 @@ __global__ __launch_bounds__(64) void k_inflate_fold_spans(const InflateSpan* __
 }  // namespace
 
 hipError_t init_inflate_kernels() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_tokens<false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)KT_LDS);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_tokens<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)KT_LDS);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)KB_LDS);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(k_inflate_bytes_clip), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)KB_LDS);
+  const struct {
+    const void* f;
+    uint32_t lds;
+  } ks[] = {{reinterpret_cast<const void*>(k_inflate_tokens<false>), KT_LDS},
+            {reinterpret_cast<const void*>(k_inflate_tokens<true>), KT_LDS},
+            {reinterpret_cast<const void*>(k_inflate_tokens<false, kWideRow>), KT_LDS},
+            {reinterpret_cast<const void*>(k_inflate_bytes<>), KB_LDS},
+            {reinterpret_cast<const void*>(k_inflate_bytes_clip<>), KB_LDS},
+            {reinterpret_cast<const void*>(k_inflate_bytes<kWideRow>), KB_LDS},
+            {reinterpret_cast<const void*>(k_inflate_bytes_clip<kWideRow>), KB_LDS}};
+  for (const auto& k : ks) {
+    const hipError_t e = hipFuncSetAttribute(k.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 // A launch batch's segments: the sub-indexed wave kernel, or -- index only -- the speculative one with the lane-serial kernel
@@ -1441,6 +1466,19 @@ hipError_t launch_inflate_tokens(const InflateSeg* rows, uint32_t nseg, uint32_t
   return hipGetLastError();
 }
 
+// rows of up to kWideRow bytes, their tokens kWideRow apart: index only
+hipError_t launch_inflate_tokens_wide(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool speculate,
+                                      hipStream_t s) {
+  if (speculate) {
+    hipLaunchKernelGGL(k_inflate_tokens_spec_wide, dim3((nseg + 1) / 2), dim3(64), 0, s, rows, nseg, tokens, info);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((k_inflate_tokens<false, kWideRow>), dim3((nseg + KT_LANES - 1) / KT_LANES), dim3(KT_LANES), KT_LDS, s, rows,
+                     nseg, tokens, info, speculate ? 1u : 0u);
+  return hipGetLastError();
+}
+
 hipError_t launch_inflate_tokens_exact(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool speculate,
                                        hipStream_t s) {
   if (speculate) {
@@ -1455,13 +1493,21 @@ hipError_t launch_inflate_tokens_exact(const InflateSeg* rows, uint32_t nseg, ui
 
 hipError_t launch_inflate_bytes(const InflateSeg* rows, const InflateStrip* strips, uint32_t nstrips, const uint32_t* tokens,
                                 SegInfo* info, hipStream_t s) {
-  hipLaunchKernelGGL(k_inflate_bytes, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, rows, strips, tokens, info);
+  hipLaunchKernelGGL(k_inflate_bytes<>, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, rows, strips, tokens, info);
+  return hipGetLastError();
+}
+
+// clips: null, or every row's write window (k_inflate_bytes_clip)
+hipError_t launch_inflate_bytes_wide(const InflateSeg* rows, const InflateClip* clips, const InflateStrip* strips, uint32_t nstrips,
+                                     const uint32_t* tokens, SegInfo* info, hipStream_t s) {
+  if (clips) hipLaunchKernelGGL(k_inflate_bytes_clip<kWideRow>, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, rows, clips, strips, tokens, info);
+  else hipLaunchKernelGGL(k_inflate_bytes<kWideRow>, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, rows, strips, tokens, info);
   return hipGetLastError();
 }
 
 hipError_t launch_inflate_bytes_clip(const InflateSeg* rows, const InflateClip* clips, const InflateStrip* strips, uint32_t nstrips,
                                      const uint32_t* tokens, SegInfo* info, hipStream_t s) {
-  hipLaunchKernelGGL(k_inflate_bytes_clip, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, rows, clips, strips, tokens, info);
+  hipLaunchKernelGGL(k_inflate_bytes_clip<>, dim3(nstrips), dim3(KB_THREADS), KB_LDS, s, rows, clips, strips, tokens, info);
   return hipGetLastError();
 }
 

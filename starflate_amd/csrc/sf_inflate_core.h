@@ -231,7 +231,7 @@ struct alignas(16) Tok4 {
   uint32_t a, b, c, d;
 };
 struct TokenSink {
-  uint32_t* out;  // 16-byte aligned, room for 32768 tokens
+  uint32_t* out;  // 16-byte aligned, room for a token per output byte of the segment
   uint32_t n;
   uint32_t q0, q1, q2;
   SF_HD void put(uint32_t t) {
@@ -545,7 +545,7 @@ SF_HD uint32_t decode_symbols(BitReader& br, const uint8_t* m, Sink& sink, uint3
 }
 
 // Decodes the blocks of one segment: stream bytes [seg_begin, seg_end) of `src`, which must produce exactly
-// out_n (<= 32768) bytes.  Tokens go to tokens[0..ntok).  `m`: LaneLayout::kBytes of scratch.  hist: see decode_symbols.
+// out_n bytes (at most what the caller's token row holds: 32768, or 65536 in a wide row).  Tokens go to tokens[0..ntok).  `m`: LaneLayout::kBytes of scratch.  hist: see decode_symbols.
 // EXACT (a recovered index): the segment is not the stream's last, so its blocks must end ON seg_end, none of
 // them final -- fewer than 3 bits left over, or BFINAL, is kError there, not the end of the segment.
 template <bool EXACT = false>
