@@ -258,6 +258,14 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
   // kEpS steps whenever a round would reach kEpMax steps past it, entries older than that vanish
   constexpr uint32_t kEpS = (kEpochSteps << 10) >> SH, kEpMax = (kEpochMax << 10) >> SH;
   static_assert(((kEpMax + 1) << SH) <= 65536 && kRound % STEP == 0, "step codes");
+  // the window's shift: 2050 units of 16 bytes move down by 512, three per thread
+  constexpr uint32_t kUnits = (kWindow + kLook) / 16, kOff = kRound / 16;
+  static_assert(kUnits > 2 * K1_THREADS && kUnits <= 3 * K1_THREADS, "shift: three units per thread");
+  // EARLY (the step tables' pair loop): the shift, the prefetched bytes' store and the ageing for round r + 1 are done in
+  // round r, behind the barrier between walk and emit, where no wave reads the window or the table any more (see the counts
+  // phase); the stage of round r + 1 is then the prefetch loads and the closing barrier.  LONG, RECENT (whose hsave leans on the
+  // stage's top barrier) and CHAIN keep the stage as it was.
+  constexpr bool EARLY = !CHAIN && !RECENT && !LONG;
 
   // static LDS (its address is a compile-time constant: no base register, no add per access)
   __shared__ __attribute__((aligned(16))) uint8_t smem[CHAIN ? C_K1_LDS : RECENT ? R_K1_LDS : K1_LDS];
@@ -327,6 +335,33 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
   bool short_probe = false;              // (uniform) the strip's previous chunk took it: only kSkipProbe positions of this one's span are searched
   bool lds_stale = false;                // (uniform) the rounds behind a chunk's probe round were taken in one go: the window in LDS is not the strip's
   uint32_t stale_span = 0;               // ... and the positions of that chunk that were searched and inserted (its probe span)
+  [[maybe_unused]] bool staged = false;  // (uniform, EARLY) the round in hand found its window, its bytes and the table's age in place
+  // age the step codes for the round that begins at strip position `at`, if it is due: all move down by kEpochSteps steps,
+  // saturating at 0 -- ONE packed 16-bit instruction per bucket (v_pk_sub_u16 clamp).  What falls below 1 << 10 (step
+  // field 0) is older than the window: empty.  (Between a round's last table access, in its match phase, and the barrier in
+  // front of the next round's: in that round's stage, or -- EARLY -- behind the barrier between the round before's walk and emit.)
+  // @phase stage.ageing trips=1 depth=2 note=two iterations every second round
+  auto age = [&](uint32_t at) {
+    if (at / STEP - ebase >= kEpMax) {
+      // (behind a chunk whose later rounds were taken in one go the epoch is further back than one move mends: the moves
+      // that were due meanwhile are made up in this one -- at most three, 3 * kEpS << SH < 2^16; what ageing removes is
+      // older than the window either way, so when it happens shows nowhere)
+      const uint32_t moves = (at / STEP - ebase - kEpMax) / kEpS + 1u;
+      static_assert(3 * (kEpS << SH) < 65536 && (kRoundsPerChunk * (kRound / STEP) - 1) / kEpS + 1 <= 3, "ageing: one packed subtract makes up for a skipped chunk");
+      const uint32_t kSub2 = moves * ((kEpS << SH) * 0x00010001u);
+      uint4* t4 = reinterpret_cast<uint4*>(smem + L_TABLE);
+      static_assert((1u << kHashBits) % (4 * K1_THREADS) == 0, "ageing: whole 16-byte units per thread");
+      for (uint32_t idx = t; idx < (1u << kHashBits) / 4; idx += K1_THREADS) {
+        uint4 e = t4[idx];
+        asm("v_pk_sub_u16 %0, %0, %1 clamp" : "+v"(e.x) : "s"(kSub2));
+        asm("v_pk_sub_u16 %0, %0, %1 clamp" : "+v"(e.y) : "s"(kSub2));
+        asm("v_pk_sub_u16 %0, %0, %1 clamp" : "+v"(e.z) : "s"(kSub2));
+        asm("v_pk_sub_u16 %0, %0, %1 clamp" : "+v"(e.w) : "s"(kSub2));
+        t4[idx] = e;
+      }
+      ebase += moves * kEpS;
+    }
+  };
 
   // @phase round.head trips=1 note=round bookkeeping
   for (uint32_t r = 0; r < nrounds; ++r) {
@@ -349,10 +384,10 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
     // ---- stage: shift the window down by one round, append the prefetched 4 KiB ----
     {
       uint4* s4 = reinterpret_cast<uint4*>(smem + L_DATA);
-      constexpr uint32_t kUnits = (kWindow + kLook) / 16, kOff = kRound / 16;  // 2050 units move down by 512
-      static_assert(kUnits > 2 * K1_THREADS && kUnits <= 3 * K1_THREADS, "shift: three units per thread");
       const bool reload = lds_stale;  // (uniform)
-      if (reload) {
+      const bool placed = EARLY && staged;  // (uniform) the previous round has done it all but the prefetch (never ahead of a reload)
+      if (placed) {
+      } else if (reload) {
         // behind a chunk that took the stored fast path (its later rounds never came through here): what the window must hold
         // and this round come from the input again instead of from three shifts per skipped chunk.  Of the window only the
         // skipped chunk's PROBE SPAN was ever inserted into the table (stale_span positions at the window's start, and
@@ -366,14 +401,18 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         const uint8_t* const wp = sp + (rb - kWindow);
         // (... and the window's LAST bytes: the byte in front of the round's first position is looked at whenever a match
         // starts there -- the odd neighbour's byte check of a near candidate, the run test of the wave-wide extension)
+        // (EARLY: from an opaque copy of t -- with the stage this short the addresses of this rare path are hoisted out of the
+        // round loop otherwise, into registers that spill)
+        uint32_t tr = t;
+        if constexpr (EARLY) asm volatile("" : "+v"(tr));
         if (rb + kRound + kLook <= n) {
-          if (t < wunits) s4[t] = reinterpret_cast<const uint4*>(wp)[t];
-          if (t < kRoundUnits) s4[kWindow / 16 + t] = reinterpret_cast<const uint4*>(wp)[kWindow / 16 + t];
-          if (t == K1_THREADS - 1) s4[kWindow / 16 - 1] = reinterpret_cast<const uint4*>(wp)[kWindow / 16 - 1];
+          if (tr < wunits) s4[tr] = reinterpret_cast<const uint4*>(wp)[tr];
+          if (tr < kRoundUnits) s4[kWindow / 16 + tr] = reinterpret_cast<const uint4*>(wp)[kWindow / 16 + tr];
+          if (tr == K1_THREADS - 1) s4[kWindow / 16 - 1] = reinterpret_cast<const uint4*>(wp)[kWindow / 16 - 1];
         } else {  // the strip ends inside: word by word, zeros beyond the end
-          for (uint32_t i = t; i < 4 * wunits; i += K1_THREADS) s_data[i] = load4(rb - kWindow + 4 * i);
-          for (uint32_t i = t; i < 4 * kRoundUnits; i += K1_THREADS) s_data[kWindow / 4 + i] = load4(rb + 4 * i);
-          if (t == K1_THREADS - 1) s_data[kWindow / 4 - 1] = load4(rb - 4);
+          for (uint32_t i = tr; i < 4 * wunits; i += K1_THREADS) s_data[i] = load4(rb - kWindow + 4 * i);
+          for (uint32_t i = tr; i < 4 * kRoundUnits; i += K1_THREADS) s_data[kWindow / 4 + i] = load4(rb + 4 * i);
+          if (tr == K1_THREADS - 1) s_data[kWindow / 4 - 1] = load4(rb - 4);
         }
         lds_stale = false;
       } else {
@@ -385,36 +424,18 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         s4[K1_THREADS + t] = c1;
         if (t < kUnits - 2 * K1_THREADS) s4[2 * K1_THREADS + t] = c2;
       }
-      if (!reload) *reinterpret_cast<uint2*>(&s_data[(kWindow + kLook) / 4 + 2 * t]) = make_uint2(pre_lo, pre_hi);
+      if (!reload && !placed) *reinterpret_cast<uint2*>(&s_data[(kWindow + kLook) / 4 + 2 * t]) = make_uint2(pre_lo, pre_hi);
       // (RECENT asks for them behind the match phase, whose serial pass wants the registers: parse and emit hide the latency)
       if (!RECENT && r + 1 < nrounds) {
         pre_lo = load4(rb + kRound + kLook + 8 * t);
         pre_hi = load4(rb + kRound + kLook + 8 * t + 4);
       }
-      // age the step codes: all move down by kEpochSteps steps, saturating at 0 -- ONE packed 16-bit instruction per
-      // bucket (v_pk_sub_u16 clamp).  What falls below 1 << 10 (step field 0) is older than the window: empty
       // @phase stage.ageing trips=1 depth=2 note=two iterations every second round
-      if (rb / STEP - ebase >= kEpMax) {
-        // (behind a chunk whose later rounds were taken in one go the epoch is further back than one move mends: the moves
-        // that were due meanwhile are made up in this one -- at most three, 3 * kEpS << SH < 2^16; what ageing removes is
-        // older than the window either way, so when it happens shows nowhere)
-        const uint32_t moves = (rb / STEP - ebase - kEpMax) / kEpS + 1u;
-        static_assert(3 * (kEpS << SH) < 65536 && (kRoundsPerChunk * (kRound / STEP) - 1) / kEpS + 1 <= 3, "ageing: one packed subtract makes up for a skipped chunk");
-        const uint32_t kSub2 = moves * ((kEpS << SH) * 0x00010001u);
-        uint4* t4 = reinterpret_cast<uint4*>(smem + L_TABLE);
-        static_assert((1u << kHashBits) % (4 * K1_THREADS) == 0, "ageing: whole 16-byte units per thread");
-        for (uint32_t idx = t; idx < (1u << kHashBits) / 4; idx += K1_THREADS) {
-          uint4 e = t4[idx];
-          asm("v_pk_sub_u16 %0, %0, %1 clamp" : "+v"(e.x) : "s"(kSub2));
-          asm("v_pk_sub_u16 %0, %0, %1 clamp" : "+v"(e.y) : "s"(kSub2));
-          asm("v_pk_sub_u16 %0, %0, %1 clamp" : "+v"(e.z) : "s"(kSub2));
-          asm("v_pk_sub_u16 %0, %0, %1 clamp" : "+v"(e.w) : "s"(kSub2));
-          t4[idx] = e;
-        }
-        ebase += moves * kEpS;
-      }
+      if (!placed) age(rb);
+      if constexpr (EARLY) staged = false;
       // @phase stage.end trips=1 note=closing barrier
-      // (the barrier at the top of the stage follows the previous round's last histogram update)
+      // (the barrier at the top of the stage follows the previous round's last histogram update; behind a round that has
+      // placed this one's window, this barrier follows its shift, its ageing and its emit's histogram updates)
       if constexpr (RECENT) hsave = t < kHistStride ? s_hist[t] : 0u;
       __syncthreads();
     }
@@ -1292,10 +1313,30 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
       stamp(3);
       // @phase parse.counts trips=1
       // tokens (low half) and matches (high half: a match takes two items) before this lane, per wave, per round
+      // EARLY: the lane's pieces of the window's shift, the eight bytes its emit codes among them, asked for here: this wave's
+      // walk is over, the barrier below waits for the slowest wave's, and the round trip passes in that wait.  Behind the
+      // barrier no wave reads the window any more -- but for the stored fast path, which keeps today's order -- so the
+      // shift's writes need no barrier of their own.  (Ten registers, live across this one barrier: pinned in front of
+      // it, so that the loads are neither sunk behind it nor hoisted into the walk.)
+      // The shift in pieces of eight bytes, thread t's at 8 t in each of the window's four rounds and in the look-ahead: the
+      // piece that moves into the window's last round IS the lane's B.
+      static_assert(kWindow == 4 * kRound && 8 * K1_THREADS == kRound && kLook % 8 == 0, "shift: four pieces per thread and the look-ahead");
+      [[maybe_unused]] uint2 sh_0 = make_uint2(0, 0), sh_1 = sh_0, sh_2 = sh_0, B_early = sh_0;
+      if constexpr (EARLY) {
+        asm volatile("" ::: "memory");
+        const uint2* s2 = reinterpret_cast<const uint2*>(smem + L_DATA);
+        sh_0 = s2[kRound / 8 + t];
+        sh_1 = s2[2 * kRound / 8 + t];
+        sh_2 = s2[3 * kRound / 8 + t];
+        B_early = s2[kWindow / 8 + t];
+      }
       const uint32_t cm = marks & T;                   // chain positions that are matches
       const uint32_t mine = (uint32_t)__popc(marks) | ((uint32_t)__popc(cm) << 16);
       const uint32_t incl = wave_incl_add(mine);
       if (lane == 63) s_wtot[wave] = incl;
+      if constexpr (EARLY)
+        asm volatile("" : "+v"(sh_0.x), "+v"(sh_0.y), "+v"(sh_1.x), "+v"(sh_1.y), "+v"(sh_2.x), "+v"(sh_2.y),
+                          "+v"(B_early.x), "+v"(B_early.y));
       __syncthreads();
       uint32_t wbase, rtotal;
       {
@@ -1317,6 +1358,26 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
       stamp(4);
       __builtin_amdgcn_s_setprio(0);  // emit, flush and the next round's stage: nothing waits for them
 
+      if constexpr (EARLY) {
+        // @phase emit.place trips=1 note=the next round's window, bytes and table age
+        // The next round's window, unless this is the strip's last round or the chunk goes the stored way (which counts in
+        // the window and leaves it stale: the next round then loads it again).  Every wave is behind its walk -- the last reader of
+        // the window and, since the match phase, of the table; the emit below takes its bytes from B_early: lanes 0..3's lie
+        // where the look-ahead moves to, everyone else's where the prefetched bytes land.  The next round's
+        // stage is then the prefetch loads and the closing barrier, which also orders these writes before its match phase.
+        if (!skip_now && r + 1 < nrounds) {
+          uint2* s2 = reinterpret_cast<uint2*>(smem + L_DATA);
+          s2[t] = sh_0;
+          s2[kRound / 8 + t] = sh_1;
+          s2[2 * kRound / 8 + t] = sh_2;
+          s2[3 * kRound / 8 + t] = B_early;
+          // (the look-ahead, by the four threads whose prefetched bytes land on it: their own read, then their own write)
+          if (t >= K1_THREADS - kLook / 8) s2[kWindow / 8 + t - (K1_THREADS - kLook / 8)] = s2[(kWindow + kRound) / 8 + t - (K1_THREADS - kLook / 8)];
+          *reinterpret_cast<uint2*>(&s_data[(kWindow + kLook) / 4 + 2 * t]) = make_uint2(pre_lo, pre_hi);
+          age(rb + kRound);  // (the next round's position; K of this round is not used again)
+          staged = true;
+        }
+      }
       // @phase skip_now trips=0
       if (__builtin_expect(skip_now, 0)) {
         // (qn == kRound here: the chunk is longer than the span.)  The REST of the chunk is taken right here, in one go: its
@@ -1327,7 +1388,7 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         // a full chunk whose probe span's BYTES are as good as uniform -- their entropy, the plan's fixed point, within
         // kStoreMargin bytes of the span -- has no tokens at all, which k_plan stores; its other 24 KiB are never fetched.
         const uint32_t clen = (n - cstart) < kChunk ? (n - cstart) : kChunk;  // the chunk's bytes
-        const uint2 B = *reinterpret_cast<const uint2*>(&s_bytes[kWindow + 8 * t]);
+        const uint2 B = EARLY ? B_early : *reinterpret_cast<const uint2*>(&s_bytes[kWindow + 8 * t]);  // (pb = 8 t)
         bool pstore = false;  // (uniform)
         if (clen == kChunk) {
           // The byte counts.  On the histogram itself a wave's 64 random bytes pile up on the LDS banks (one atomic
@@ -1412,7 +1473,7 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         // population count over both masks side by side
         const uint32_t both = marks | (cm << 8);
         auto item_at = [&](uint32_t below) { return ib0 + 2u * (uint32_t)__popc(both & (below | (below << 8))); };
-        const uint2 B = *reinterpret_cast<const uint2*>(&s_bytes[kWindow + pb]);
+        const uint2 B = EARLY ? B_early : *reinterpret_cast<const uint2*>(&s_bytes[kWindow + pb]);  // (EARLY: the window has moved on)
         // first token of a sub-index region: its position is the region's first, which is always a token start,
         // so the flag can only ever go onto the lane's slot 0
         // (from an opaque copy of t: hoisted out of the round loop, the flag's thread-constant part is one more register alive
