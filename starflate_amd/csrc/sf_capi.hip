@@ -53,7 +53,7 @@ struct sfh_ctx {
   uint32_t ev_inf_batches = 0;
   bool ev_inf_valid = false;
   size_t last_dtok_bytes = 0;    // bytes of decoder token scratch the last decode call used (bounded: one batch)
-  uint8_t* d_in = nullptr;       // staging for the host-buffer entry points (capacities in bytes)
+  uint8_t* d_in = nullptr;       // staging for the host-buffer entry points (capacities in bytes): host_up, staged_up
   uint8_t* d_out = nullptr;
   size_t d_in_cap = 0, d_out_cap = 0;
   int profiling = 0;
@@ -86,8 +86,8 @@ struct sfh_ctx {
   size_t h_tab_cap = 0, d_tab_cap = 0;
   hipEvent_t ev_tab = nullptr;
   bool tab_pending = false;
-  uint8_t* h_stage = nullptr;    // sfh_compress_batch: pinned staging of the packed items (kStageBytes)
-  uint64_t* d_bn = nullptr;      // ... the items' sizes on the device and in pinned memory
+  uint8_t* h_stage = nullptr;    // the batched host calls (staged_up, staged_down): pinned staging of the packed items (kStageBytes)
+  uint64_t* d_bn = nullptr;      // sfh_compress_batch: the items' sizes on the device and in pinned memory
   uint64_t* h_bn = nullptr;
   size_t bn_cap = 0;             // items d_bn / h_bn hold
   // the index of the last call when it was a compress batch (sfh_copy_batch_index): every item's entries, item after item, in
@@ -135,6 +135,8 @@ struct sfh_ctx {
 
 namespace {
 
+using sf::stage::al16;
+
 int fail(sfh_ctx* c, int code, const char* what, hipError_t e) {
   if (c) snprintf(c->err, sizeof c->err, "%s: %s", what, e == hipSuccess ? "" : hipGetErrorString(e));
   return code;
@@ -156,6 +158,20 @@ int grow(sfh_ctx* ctx, T** p, size_t* cap_bytes, size_t bytes, const char* what)
   const hipError_t e = hipMalloc(p, bytes);
   if (e != hipSuccess) return fail(ctx, SFH_E_NOMEM, what, e);
   *cap_bytes = bytes;
+  return SFH_OK;
+}
+
+// Grow-only device array with its pinned twin (what a call reads back per item): *d and *h hold `count` elements afterwards.
+template <class T>
+int grow_pair(sfh_ctx* ctx, T** d, T** h, size_t* cap, size_t count, const char* what) {
+  if (*cap >= count) return SFH_OK;
+  (void)hipFree(*d);
+  if (*h) (void)hipHostFree(*h);
+  *d = *h = nullptr;
+  *cap = 0;
+  if (hipMalloc(d, count * sizeof(T)) != hipSuccess || hipHostMalloc((void**)h, count * sizeof(T), hipHostMallocDefault) != hipSuccess)
+    return fail(ctx, SFH_E_NOMEM, what, hipSuccess);
+  *cap = count;
   return SFH_OK;
 }
 
@@ -253,6 +269,23 @@ int mark_call_end(sfh_ctx* ctx, hipStream_t s) {
   SF_HIP(hipEventRecord(ctx->ev_done, s), "event");
   ctx->busy = true;
   ctx->last_stream = s;
+  return SFH_OK;
+}
+// What opens a device entry point: the context's device is current, whatever launch error an earlier caller on this thread
+// left is dropped (launches are checked with hipGetLastError()), and *s is the caller's stream, or the context's for none.
+int begin_call(sfh_ctx* ctx, void* stream, hipStream_t* s) {
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();
+  *s = stream ? (hipStream_t)stream : ctx->stream;
+  return SFH_OK;
+}
+// A host-buffer call begins on an idle context: EVERY one of them waits here, on the host, for the last call's device work.
+// It fills the context's staging (d_in, d_index, d_sub; h_stage) with copies on the context's stream that are issued before
+// its device path takes its place behind the last call (order_behind_last_call), and that call -- on a caller's stream, or
+// one that returned an error with work in flight -- may still use the staging (sfh_decompress_dz_device on a caller's stream
+// decodes from d_index).  After a call that ended synchronised the event has fired and this returns at once.
+int wait_idle(sfh_ctx* ctx) {
+  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");
   return SFH_OK;
 }
 
@@ -734,7 +767,7 @@ int enqueue_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs,
   // the tables, in one pinned block: segments | items | strips | checksum chunks (rows of 48, 64, 8 and 16 bytes)
   const size_t b_segs = (size_t)nseg * sizeof(sf::InflateSeg), b_items = count * sizeof(sf::InflateItem);
   const size_t b_strips = (size_t)P.nstrips * sizeof(sf::InflateStrip), b_sums = container ? (size_t)nseg * sizeof(sf::BatchChunk) : 0;
-  const size_t o_sums = (b_segs + b_items + b_strips + 15) / 16 * 16, bytes = o_sums + b_sums;
+  const size_t o_sums = al16(b_segs + b_items + b_strips), bytes = o_sums + b_sums;
   if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
   sf::InflateSeg* h_segs = (sf::InflateSeg*)ctx->h_tab;
   sf::InflateItem* h_items = (sf::InflateItem*)(ctx->h_tab + b_segs);
@@ -907,13 +940,14 @@ int enqueue_ranges(sfh_ctx* ctx, const sf::range::Plan& P, const RangeSource* fr
   return mark_call_end(ctx, s);
 }
 
-// The batched host-buffer calls' staging (sf_stage_plan.h): piece i lies at [off[i], off[i] + len[i]) of a packed layout of
-// `total` bytes in ctx->d_in (up) or ctx->d_out (down), and moves through the pinned h_stage, one copy and one wait per
+// ---- the host-buffer entry points' staging ("one staging path") ----
+// Pieces of a packed layout (sf_stage_plan.h) between the callers' buffers and the device, through the pinned h_stage: piece i
+// lies at [off[i], off[i] + len[i]) of `total` bytes at d_base (up) or ctx->d_out (down); one copy and one wait per
 // kStageBytes.  Down, len[i] == 0 skips piece i, and a stretch of kStageBytes that holds no other piece's bytes is not copied.
-int stage_up(sfh_ctx* ctx, const void* const* srcs, const uint64_t* len, const uint64_t* off, size_t count, uint64_t total,
-             hipStream_t s) {
+int stage_up(sfh_ctx* ctx, void* d_base, const void* const* srcs, const uint64_t* len, const uint64_t* off, size_t count,
+             uint64_t total, hipStream_t s) {
   return sf::stage::pack_up(ctx->h_stage, kStageBytes, srcs, len, off, count, total, [&](uint64_t p0, uint64_t n) -> int {
-    SF_HIP(hipMemcpyAsync(ctx->d_in + p0, ctx->h_stage, n, hipMemcpyHostToDevice, s), "H2D");
+    SF_HIP(hipMemcpyAsync((uint8_t*)d_base + p0, ctx->h_stage, n, hipMemcpyHostToDevice, s), "H2D");
     SF_HIP(hipStreamSynchronize(s), "stream sync");  // (the next piece refills h_stage)
     return SFH_OK;
   });
@@ -927,18 +961,100 @@ int stage_down(sfh_ctx* ctx, void* const* dsts, const uint64_t* len, const uint6
   });
 }
 
-// d_bstatus / h_bstatus hold `count` statuses
-int ensure_bstatus(sfh_ctx* ctx, size_t count) {
-  if (ctx->bstatus_cap >= count) return SFH_OK;
-  (void)hipFree(ctx->d_bstatus);
-  if (ctx->h_bstatus) (void)hipHostFree(ctx->h_bstatus);
-  ctx->d_bstatus = ctx->h_bstatus = nullptr;
-  ctx->bstatus_cap = 0;
-  if (hipMalloc(&ctx->d_bstatus, count * sizeof(uint32_t)) != hipSuccess ||
-      hipHostMalloc((void**)&ctx->h_bstatus, count * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-    return fail(ctx, SFH_E_NOMEM, "batch statuses", hipSuccess);
-  ctx->bstatus_cap = count;
+// A batched host-buffer call, on the context's stream: check, staged_up, the device path over d_srcs / d_dsts, the statuses,
+// staged_down.  The items lie packed in ctx->d_in at in_off, their output slots in ctx->d_out at out_off.
+struct Staged {
+  std::vector<uint64_t> in_off, out_off, got;  // count + 1 offsets each; got: what staged_down copies of every item
+  std::vector<const void*> d_srcs;
+  std::vector<void*> d_dsts;
+};
+// Up: the layout, the device staging for it, the pinned buffer, an idle context (wait_idle), and the items go up.  slot: the
+// bytes of ctx->d_out each item's output may take; null: the call has no output there, or lays it out later itself
+// (stream_batch_run, into out_off).
+int staged_up(sfh_ctx* ctx, Staged& B, size_t count, const void* const* srcs, const uint64_t* src_n, const uint64_t* slot) {
+  try {
+    B.in_off.resize(count + 1);
+    B.got.resize(count);
+    B.d_srcs.resize(count);
+    if (slot) B.out_off.resize(count + 1);
+    if (slot) B.d_dsts.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  sf::stage::pack_layout(src_n, count, B.in_off.data());
+  if (slot) sf::stage::pack_layout(slot, count, B.out_off.data());
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, std::max<uint64_t>(16, B.in_off[count]), "input staging");
+  if (!rc && slot) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, std::max<uint64_t>(16, B.out_off[count]), "output staging");
+  if (rc) return rc;
+  if (!ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
+    ctx->h_stage = nullptr;
+    return fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
+  }
+  if ((rc = wait_idle(ctx))) return rc;
+  if ((rc = stage_up(ctx, ctx->d_in, srcs, src_n, B.in_off.data(), count, B.in_off[count], ctx->stream))) return rc;
+  for (size_t i = 0; i < count; ++i) {
+    B.d_srcs[i] = ctx->d_in + B.in_off[i];
+    if (slot) B.d_dsts[i] = ctx->d_out + B.out_off[i];
+  }
   return SFH_OK;
+}
+// Down: n[i] bytes of item i's slot to dsts[i] -- of the items that have a destination and (status given) status 0.  Nothing is
+// written to any other item's, and nothing behind the last copied item's end comes down.
+int staged_down(sfh_ctx* ctx, Staged& B, size_t count, void* const* dsts, const uint64_t* n, const uint32_t* status) {
+  uint64_t end = 0;
+  for (size_t i = 0; i < count; ++i) {
+    B.got[i] = (dsts[i] && !(status && status[i])) ? n[i] : 0;
+    if (B.got[i]) end = B.out_off[i] + B.got[i];
+  }
+  return stage_down(ctx, dsts, B.got.data(), B.out_off.data(), count, end, ctx->stream);
+}
+
+// The single-item host calls: no layout and no pinned buffer -- src goes up to ctx->d_in with one copy from the caller's buffer
+// (d_out sized for out_n bytes), on an idle context as above; host_down fetches d_out[0, n) into dst and synchronises.
+int host_up(sfh_ctx* ctx, const void* src, size_t src_n, size_t out_n) {
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, std::max<size_t>(16, src_n), "input staging");
+  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, std::max<size_t>(16, out_n), "output staging");
+  if (!rc) rc = wait_idle(ctx);
+  if (rc) return rc;
+  if (src_n) SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, ctx->stream), "H2D");
+  return SFH_OK;
+}
+int host_down(sfh_ctx* ctx, void* dst, size_t n) {
+  if (!n) return SFH_OK;
+  SF_HIP(hipMemcpyAsync(dst, ctx->d_out, n, hipMemcpyDeviceToHost, ctx->stream), "D2H");
+  SF_HIP(hipStreamSynchronize(ctx->stream), "stream sync");
+  return SFH_OK;
+}
+
+// d_bstatus / h_bstatus hold `count` statuses; read_bstatus: the call's, behind its device path (synchronises s)
+int ensure_bstatus(sfh_ctx* ctx, size_t count) {
+  return grow_pair(ctx, &ctx->d_bstatus, &ctx->h_bstatus, &ctx->bstatus_cap, count, "batch statuses");
+}
+int read_bstatus(sfh_ctx* ctx, size_t count, uint32_t* status, hipStream_t s) {
+  SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy statuses");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  memcpy(status, ctx->h_bstatus, count * sizeof(uint32_t));
+  return SFH_OK;
+}
+
+// The indexed decoder's answer for a batch of one: its status and first failing segment (k_inflate_fold wrote them to
+// d_value[0..1]) -> *status, and the message.  Synchronises s.
+int read_decode_status(sfh_ctx* ctx, uint32_t* status, hipStream_t s) {
+  uint32_t res[2] = {0, 0};
+  SF_HIP(hipMemcpyAsync(res, ctx->d_value, sizeof res, hipMemcpyDeviceToHost, s), "copy status");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  *status = res[0];
+  if (res[0]) snprintf(ctx->err, sizeof ctx->err, "segment %u: DecompressStatus %u", res[1], res[0]);
+  return SFH_OK;
+}
+
+// gzip's ISIZE, for SFH_SIZE_FROM_TRAILER on host buffers (a stream too short for a trailer: 0, and the device, which reads the
+// wrapper, says what is wrong with it)
+uint64_t trailer_isize(const void* src, uint64_t src_n) {
+  const uint8_t* p = (const uint8_t*)src;
+  return src_n >= 18 ? (uint64_t)(p[src_n - 4] | (uint32_t)p[src_n - 3] << 8 | (uint32_t)p[src_n - 2] << 16 | (uint32_t)p[src_n - 1] << 24) : 0;
 }
 
 // ---- decoding without side information (sfh_recover_index_device, sfh_decompress_any*) ----
@@ -946,7 +1062,6 @@ int ensure_bstatus(sfh_ctx* ctx, size_t count) {
 constexpr size_t kAnyHead = 64, kAnyTot = 80, kAnyStatus = 112, kAnySmall = 128;
 inline uint64_t* any_head(sfh_ctx* c) { return (uint64_t*)(c->d_anysm + kAnyHead); }
 inline uint32_t* any_tot(sfh_ctx* c) { return (uint32_t*)(c->d_anysm + kAnyTot); }
-inline size_t al16(size_t b) { return (b + 15) / 16 * 16; }
 
 // The wrapper, read by k_inflate_head as the batch decoder reads it: *wst its status, *isize gzip's ISIZE; the body [b0, e) lands
 // in any_head.  dst_n: the size the caller asks for (SFH_SIZE_FROM_TRAILER: ISIZE is taken).  Synchronises s.
@@ -2134,58 +2249,25 @@ int sfh_compress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, cons
                        const uint64_t* dst_cap, uint64_t* out_n, const sfh_options* opt) {
   int rc = check_batch(ctx, count, srcs, src_n, dsts, dst_cap, out_n, opt, false);
   if (rc || count == 0) return rc;
-  // The items are packed into the device staging (sources 16-byte aligned, destinations a bound apart) and moved through the
-  // pinned buffer (stage_up, stage_down), with the device path over the staged items in between.
-  std::vector<uint64_t> in_off, out_off;
-  std::vector<const void*> d_srcs;
-  std::vector<void*> d_dsts;
+  std::vector<uint64_t> slot;  // an item's output slot: its bound
   try {
-    in_off.resize(count + 1);
-    out_off.resize(count + 1);
-    d_srcs.resize(count);
-    d_dsts.resize(count);
+    slot.resize(count);
   } catch (...) {
     return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
   }
-  for (size_t i = 0; i < count; ++i) {
-    in_off[i + 1] = (in_off[i] + src_n[i] + 15) / 16 * 16;
-    out_off[i + 1] = out_off[i] + sfh_compress_bound((size_t)src_n[i], 0);
-  }
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  for (size_t i = 0; i < count; ++i) slot[i] = sfh_compress_bound((size_t)src_n[i], 0);
+  Staged B;
   hipStream_t s = ctx->stream;
-  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
-  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_off[count], "output staging");
-  if (!rc && ctx->bn_cap < count) {
-    (void)hipFree(ctx->d_bn);
-    if (ctx->h_bn) (void)hipHostFree(ctx->h_bn);
-    ctx->d_bn = ctx->h_bn = nullptr;
-    ctx->bn_cap = 0;
-    if (hipMalloc(&ctx->d_bn, count * sizeof(uint64_t)) != hipSuccess ||
-        hipHostMalloc((void**)&ctx->h_bn, count * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess)
-      rc = fail(ctx, SFH_E_NOMEM, "batch sizes", hipSuccess);
-    else
-      ctx->bn_cap = count;
-  }
-  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
-    ctx->h_stage = nullptr;
-    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
-  }
-  if (rc) return rc;
-  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  if ((rc = stage_up(ctx, srcs, src_n, in_off.data(), count, in_off[count], s))) return rc;
-  for (size_t i = 0; i < count; ++i) {
-    d_srcs[i] = ctx->d_in + in_off[i];
-    d_dsts[i] = ctx->d_out + out_off[i];
-  }
-  if ((rc = enqueue_batch(ctx, count, d_srcs.data(), src_n, d_dsts.data(), ctx->d_bn, opt, s)) != SFH_OK) {
+  if ((rc = staged_up(ctx, B, count, srcs, src_n, slot.data()))) return rc;
+  if ((rc = grow_pair(ctx, &ctx->d_bn, &ctx->h_bn, &ctx->bn_cap, count, "batch sizes"))) return rc;
+  if ((rc = enqueue_batch(ctx, count, B.d_srcs.data(), src_n, B.d_dsts.data(), ctx->d_bn, opt, s)) != SFH_OK) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
   SF_HIP(hipMemcpyAsync(ctx->h_bn, ctx->d_bn, count * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "copy sizes");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
   for (size_t i = 0; i < count; ++i) out_n[i] = ctx->h_bn[i];
-  // down: [0, end of the last stream) of the output staging, each item's stream
-  return stage_down(ctx, dsts, out_n, out_off.data(), count, out_off[count - 1] + out_n[count - 1], s);
+  return staged_down(ctx, B, count, dsts, out_n, nullptr);  // each item's stream
 }
 
 int sfh_batch_index_size(const sfh_ctx* ctx, size_t* items, size_t* entries) {
@@ -2197,8 +2279,8 @@ int sfh_batch_index_size(const sfh_ctx* ctx, size_t* items, size_t* entries) {
 
 int sfh_copy_batch_index(sfh_ctx* ctx, uint64_t* index, uint32_t* subindex, uint32_t* block_bytes, int dst_on_device, void* stream) {
   if (!ctx || !ctx->bix_valid) return fail(ctx, SFH_E_INVALID_ARG, "batch index: the last call on this context was no compress batch", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   if (int rc = order_behind_last_call(ctx, s)) return rc;  // written by the batch call's kernels, maybe on another stream
   const hipMemcpyKind kind = dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   const size_t segs = ctx->bix_entries - ctx->bix_items;
@@ -2227,61 +2309,25 @@ int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, co
                          uint32_t container, uint32_t* status) {
   int rc = check_inflate_batch(ctx, count, srcs, src_n, index, subindex, dsts, dst_n, block_bytes, container, status, false);
   if (rc || count == 0) return rc;
-  // The items packed into the device staging (16-byte aligned) and moved through the pinned buffer (stage_up, stage_down);
-  // only the items whose status is 0 are copied out of it.
-  std::vector<uint64_t> in_off, out_off, got;
-  std::vector<const void*> d_srcs;
-  std::vector<void*> d_dsts;
-  size_t entries = 0, segs = 0;
-  try {
-    in_off.resize(count + 1);
-    out_off.resize(count + 1);
-    got.resize(count);
-    d_srcs.resize(count);
-    d_dsts.resize(count);
-  } catch (...) {
-    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
-  }
-  for (size_t i = 0; i < count; ++i) {
-    in_off[i + 1] = (in_off[i] + src_n[i] + 15) / 16 * 16;
-    out_off[i + 1] = (out_off[i] + dst_n[i] + 15) / 16 * 16;
-    segs += chunks_of((size_t)dst_n[i]);
-  }
-  entries = segs + count;
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  size_t segs = 0;
+  for (size_t i = 0; i < count; ++i) segs += chunks_of((size_t)dst_n[i]);
+  const size_t ix_bytes = (segs + count) * sizeof(uint64_t), sub_bytes = segs * SFH_SUBINDEX_WORDS * sizeof(uint32_t);
+  Staged B;
   hipStream_t s = ctx->stream;
-  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
-  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_off[count] ? out_off[count] : 16, "output staging");
-  if (!rc && index) rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, entries * sizeof(uint64_t), "index staging");
-  if (!rc && subindex) rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, segs * SFH_SUBINDEX_WORDS * sizeof(uint32_t), "sub-index staging");
+  if ((rc = staged_up(ctx, B, count, srcs, src_n, dst_n))) return rc;
+  if (index) rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, ix_bytes, "index staging");
+  if (!rc && subindex) rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, sub_bytes, "sub-index staging");
   if (!rc) rc = ensure_bstatus(ctx, count);
-  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
-    ctx->h_stage = nullptr;
-    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
-  }
   if (rc) return rc;
-  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  if ((rc = stage_up(ctx, srcs, src_n, in_off.data(), count, in_off[count], s))) return rc;
-  if (index) SF_HIP(hipMemcpyAsync(ctx->d_index, index, entries * sizeof(uint64_t), hipMemcpyHostToDevice, s), "H2D index");
-  if (subindex)
-    SF_HIP(hipMemcpyAsync(ctx->d_sub, subindex, segs * SFH_SUBINDEX_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, s), "H2D sub-index");
-  for (size_t i = 0; i < count; ++i) {
-    d_srcs[i] = ctx->d_in + in_off[i];
-    d_dsts[i] = ctx->d_out + out_off[i];
-  }
-  if ((rc = enqueue_inflate_batch(ctx, count, d_srcs.data(), src_n, index ? ctx->d_index : nullptr, subindex ? ctx->d_sub : nullptr,
-                                  d_dsts.data(), dst_n, block_bytes, container, ctx->d_bstatus, nullptr, s)) != SFH_OK) {
+  if (index) SF_HIP(hipMemcpyAsync(ctx->d_index, index, ix_bytes, hipMemcpyHostToDevice, s), "H2D index");
+  if (subindex) SF_HIP(hipMemcpyAsync(ctx->d_sub, subindex, sub_bytes, hipMemcpyHostToDevice, s), "H2D sub-index");
+  if ((rc = enqueue_inflate_batch(ctx, count, B.d_srcs.data(), src_n, index ? ctx->d_index : nullptr, subindex ? ctx->d_sub : nullptr,
+                                  B.d_dsts.data(), dst_n, block_bytes, container, ctx->d_bstatus, nullptr, s)) != SFH_OK) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
-  SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy statuses");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  for (size_t i = 0; i < count; ++i) {
-    status[i] = ctx->h_bstatus[i];
-    got[i] = status[i] == 0 ? dst_n[i] : 0;
-  }
-  // down: the packed output, each item with status 0
-  return stage_down(ctx, dsts, got.data(), out_off.data(), count, out_off[count], s);
+  if ((rc = read_bstatus(ctx, count, status, s))) return rc;
+  return staged_down(ctx, B, count, dsts, dst_n, status);
 }
 
 int sfh_decompress_ranges_device_async(sfh_ctx* ctx, const void* d_src, size_t src_n, const uint64_t* d_index,
@@ -2313,15 +2359,11 @@ int sfh_decompress_range_device(sfh_ctx* ctx, const void* d_src, size_t src_n, c
   uint32_t aligned_status = 0;  // (stands in for the device status word in the argument check)
   int rc = check_ranges(ctx, d_src, d_index, d_subindex, nseg, total_n, block_bytes, 1, &offset, &length, dsts, &aligned_status, true);
   if (rc) return rc;
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  if ((rc = ensure_bstatus(ctx, 1)) != SFH_OK) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if ((rc = begin_call(ctx, stream, &s)) || (rc = ensure_bstatus(ctx, 1))) return rc;
   rc = sfh_decompress_ranges_device_async(ctx, d_src, src_n, d_index, d_subindex, nseg, total_n, block_bytes, 1, &offset, &length,
                                           dsts, ctx->d_bstatus, s);
-  if (rc) return rc;
-  SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy status");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  *status = ctx->h_bstatus[0];
+  if (rc || (rc = read_bstatus(ctx, 1, status, s))) return rc;
   if (*status) snprintf(ctx->err, sizeof ctx->err, "range [%llu, +%llu): DecompressStatus %u", (unsigned long long)offset,
                         (unsigned long long)length, *status);
   return SFH_OK;
@@ -2334,114 +2376,63 @@ int sfh_decompress_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uin
   if (rc || count == 0) return rc;
   sf::range::Plan P;
   if ((rc = plan_ranges_checked(ctx, total_n, block_bytes, count, offsets, lengths, P)) != SFH_OK) return rc;
-  // Per decode span: its piece of the stream -- from the smallest to the largest of its index entries, clipped to src_n and
-  // rounded out to 16 bytes (a damaged index cannot send a row outside its piece: a row reads from its first entry on, and
-  // only when its second entry is not above the bytes readable) --, its index entries and its sub-index words, each packed span
-  // after span.  The destinations are packed as well, 16 bytes apart at least.
-  std::vector<uint64_t> p_lo, p_n, in_off, out_off, ix_off, got;
-  std::vector<const void*> p_src;
+  // The items are the decode spans: each one's piece of the stream (sf::range::source_piece), and behind them, through the
+  // same staging, its index entries and its sub-index words -- a span's rows are consecutive segments, so both are one slice
+  // from first_seg on (`piece`, `len`, `off`: the pieces of one upload after the other).
+  std::vector<sf::range::Piece> pc;
+  std::vector<const void*> piece;
+  std::vector<uint64_t> len, off;
   std::vector<RangeSource> from;
-  std::vector<void*> d_dsts;
   try {
-    p_lo.resize(count);
-    p_n.resize(count);
-    in_off.resize(count + 1);
-    out_off.resize(count + 1);
-    ix_off.resize(count + 1);
-    got.resize(count);
-    p_src.resize(count);
+    pc.resize(count);
+    piece.resize(count);
+    len.resize(count);
+    off.resize(count + 1);
     from.resize(count);
-    d_dsts.resize(count);
   } catch (...) {
     return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
   }
   for (size_t r = 0; r < count; ++r) {
-    const sf::range::Span& S = P.spans[r];
-    uint64_t lo = 0, hi = 0;
-    if (S.nrows) {
-      lo = hi = index[S.first_seg];
-      for (uint32_t k = 1; k <= S.nrows; ++k) {
-        lo = std::min(lo, index[S.first_seg + k]);
-        hi = std::max(hi, index[S.first_seg + k]);
-      }
-    }
-    lo = std::min<uint64_t>(lo, src_n) / 16 * 16;
-    hi = std::min<uint64_t>(src_n, (std::min<uint64_t>(hi, src_n) + 15) / 16 * 16);
-    p_lo[r] = lo;
-    p_n[r] = hi - lo;
-    p_src[r] = (const uint8_t*)src + lo;
-    in_off[r + 1] = (in_off[r] + p_n[r] + 15) / 16 * 16;
-    out_off[r + 1] = (out_off[r] + lengths[r] + 15) / 16 * 16;
-    ix_off[r + 1] = ix_off[r] + (S.nrows ? S.nrows + 1 : 0);
+    pc[r] = sf::range::source_piece(P.spans[r], index, src_n);
+    piece[r] = (const uint8_t*)src + pc[r].lo;
+    len[r] = pc[r].n;
   }
-  const size_t nrows = P.rows.size(), entries = (size_t)ix_off[count];
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  Staged B;
   hipStream_t s = ctx->stream;
-  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
-  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_off[count] ? out_off[count] : 16, "output staging");
-  if (!rc) rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, (entries ? entries : 1) * sizeof(uint64_t), "index staging");
-  if (!rc && subindex)
-    rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, (nrows ? nrows : 1) * SFH_SUBINDEX_WORDS * sizeof(uint32_t), "sub-index staging");
-  if (!rc) rc = ensure_bstatus(ctx, count);
-  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
-    ctx->h_stage = nullptr;
-    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
+  if ((rc = staged_up(ctx, B, count, piece.data(), len.data(), lengths))) return rc;
+  for (size_t r = 0; r < count; ++r) {
+    const sf::range::Span& S = P.spans[r];
+    piece[r] = index + S.first_seg;
+    len[r] = S.nrows ? (S.nrows + 1) * sizeof(uint64_t) : 0;
+    off[r + 1] = off[r] + len[r];
   }
+  const size_t sub_bytes = P.rows.size() * SFH_SUBINDEX_WORDS * sizeof(uint32_t);
+  rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, std::max<uint64_t>(sizeof(uint64_t), off[count]), "index staging");
+  if (!rc && subindex) rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, std::max<size_t>(SFH_SUBINDEX_WORDS * sizeof(uint32_t), sub_bytes), "sub-index staging");
+  if (!rc) rc = ensure_bstatus(ctx, count);
+  if (!rc) rc = stage_up(ctx, ctx->d_index, piece.data(), len.data(), off.data(), count, off[count], s);
   if (rc) return rc;
-  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  if ((rc = stage_up(ctx, p_src.data(), p_n.data(), in_off.data(), count, in_off[count], s))) return rc;
-  // the spans' index entries and sub-index words through the same staging
-  {
-    const size_t per = kStageBytes / sizeof(uint64_t);
-    uint64_t* h = (uint64_t*)ctx->h_stage;
-    size_t filled = 0, base = 0;  // entries in the staging, entries already on the device
-    auto flush = [&]() -> int {
-      if (!filled) return SFH_OK;
-      SF_HIP(hipMemcpyAsync(ctx->d_index + base, h, filled * sizeof(uint64_t), hipMemcpyHostToDevice, s), "H2D index");
-      SF_HIP(hipStreamSynchronize(s), "stream sync");
-      base += filled;
-      filled = 0;
-      return SFH_OK;
-    };
-    for (size_t r = 0; r < count; ++r) {
-      const sf::range::Span& S = P.spans[r];
-      for (size_t k = 0; S.nrows && k <= S.nrows; ++k) {
-        h[filled++] = index[S.first_seg + k];
-        if (filled == per && (rc = flush()) != SFH_OK) return rc;
-      }
-    }
-    if ((rc = flush()) != SFH_OK) return rc;
+  for (size_t r = 0; r < count; ++r) {
+    // (the base points pc[r].lo bytes in front of the piece: base + an index entry of the span is the uploaded byte)
+    const uint8_t* base = (const uint8_t*)((uintptr_t)B.d_srcs[r] - (uintptr_t)pc[r].lo);
+    const size_t row0 = (size_t)P.spans[r].row0 * SFH_SUBINDEX_WORDS;  // the span's first sub-index word in d_sub
+    from[r] = RangeSource{base, pc[r].lo + pc[r].n, ctx->d_index + off[r] / sizeof(uint64_t), subindex ? ctx->d_sub + row0 : nullptr};
   }
   if (subindex) {
-    const size_t per = kStageBytes / (SFH_SUBINDEX_WORDS * sizeof(uint32_t));
-    uint32_t* h = (uint32_t*)ctx->h_stage;
-    for (size_t g0 = 0; g0 < nrows; g0 += per) {
-      const size_t g1 = std::min(nrows, g0 + per);
-      for (size_t g = g0; g < g1; ++g)
-        memcpy(h + (g - g0) * SFH_SUBINDEX_WORDS, subindex + P.rows[g].seg * SFH_SUBINDEX_WORDS, SFH_SUBINDEX_WORDS * sizeof(uint32_t));
-      SF_HIP(hipMemcpyAsync(ctx->d_sub + g0 * SFH_SUBINDEX_WORDS, h, (g1 - g0) * SFH_SUBINDEX_WORDS * sizeof(uint32_t),
-                            hipMemcpyHostToDevice, s), "H2D sub-index");
-      SF_HIP(hipStreamSynchronize(s), "stream sync");
+    for (size_t r = 0; r < count; ++r) {
+      const sf::range::Span& S = P.spans[r];
+      piece[r] = subindex + S.first_seg * SFH_SUBINDEX_WORDS;
+      len[r] = (uint64_t)S.nrows * SFH_SUBINDEX_WORDS * sizeof(uint32_t);
+      off[r] = (uint64_t)S.row0 * SFH_SUBINDEX_WORDS * sizeof(uint32_t);
     }
+    if ((rc = stage_up(ctx, ctx->d_sub, piece.data(), len.data(), off.data(), count, sub_bytes, s))) return rc;
   }
-  for (size_t r = 0; r < count; ++r) {
-    // (the base points p_lo[r] bytes in front of the piece: base + an index entry of the span is the uploaded byte)
-    const uint8_t* base = (const uint8_t*)((uintptr_t)(ctx->d_in + in_off[r]) - (uintptr_t)p_lo[r]);
-    from[r] = RangeSource{base, p_lo[r] + p_n[r], ctx->d_index + ix_off[r], subindex ? ctx->d_sub + (size_t)P.spans[r].row0 * SFH_SUBINDEX_WORDS : nullptr};
-    d_dsts[r] = ctx->d_out + out_off[r];
-  }
-  if ((rc = enqueue_ranges(ctx, P, from.data(), d_dsts.data(), count, subindex != nullptr, ctx->d_bstatus, s)) != SFH_OK) {
+  if ((rc = enqueue_ranges(ctx, P, from.data(), B.d_dsts.data(), count, subindex != nullptr, ctx->d_bstatus, s)) != SFH_OK) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
-  SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy statuses");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  for (size_t r = 0; r < count; ++r) {
-    status[r] = ctx->h_bstatus[r];
-    got[r] = status[r] == 0 ? lengths[r] : 0;
-  }
-  // down: the packed output, each range with status 0
-  return stage_down(ctx, dsts, got.data(), out_off.data(), count, out_off[count], s);
+  if ((rc = read_bstatus(ctx, count, status, s))) return rc;
+  return staged_down(ctx, B, count, dsts, lengths, status);
 }
 
 uint32_t sfh_last_block_bytes(const sfh_ctx* ctx) { return (ctx && ctx->index_valid) ? ctx->last_block_bytes : 0u; }
@@ -2451,8 +2442,8 @@ size_t sfh_index_entries(const sfh_ctx* ctx) { return (ctx && ctx->index_valid) 
 int sfh_copy_index(sfh_ctx* ctx, uint64_t* dst, size_t entries, int dst_on_device, void* stream) {
   if (!ctx || !dst || !ctx->index_valid || entries != (size_t)ctx->last_chunks + 1)
     return fail(ctx, SFH_E_INVALID_ARG, "index: no compress call yet, or entries != segments + 1", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   if (int rc = order_behind_last_call(ctx, s)) return rc;  // the index is written by the last call's k_scan, maybe on another stream
   SF_HIP(hipMemcpyAsync(dst, ctx->ws.offsets, entries * sizeof(uint64_t),
                         dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s), "copy index");
@@ -2463,8 +2454,8 @@ int sfh_copy_index(sfh_ctx* ctx, uint64_t* dst, size_t entries, int dst_on_devic
 int sfh_copy_subindex(sfh_ctx* ctx, uint32_t* dst, size_t words, int dst_on_device, void* stream) {
   if (!ctx || !dst || !ctx->index_valid || words != (size_t)ctx->last_chunks * SFH_SUBINDEX_WORDS)
     return fail(ctx, SFH_E_INVALID_ARG, "sub-index: no compress call yet, or words != segments * 64", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   if (int rc = order_behind_last_call(ctx, s)) return rc;  // written by the last call's k_emit
   SF_HIP(hipMemcpyAsync(dst, ctx->ws.subidx, words * sizeof(uint32_t),
                         dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s), "copy sub-index");
@@ -2490,36 +2481,25 @@ int sfh_decompress_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const u
   if (int rc = enqueue_inflate_batch(ctx, 1, srcs, src_ns, d_index, d_subindex, dsts, dst_ns, &block_bytes, 0, ctx->d_value,
                                      ctx->d_value + 1, s))
     return rc;
-  uint32_t res[2] = {0, 0};
-  SF_HIP(hipMemcpyAsync(res, ctx->d_value, sizeof res, hipMemcpyDeviceToHost, s), "copy status");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  *status = res[0];
-  if (res[0]) snprintf(ctx->err, sizeof ctx->err, "segment %u: DecompressStatus %u", res[1], res[0]);
-  return SFH_OK;
+  return read_decode_status(ctx, status, s);
 }
 
 int sfh_decompress(sfh_ctx* ctx, const void* src, size_t src_n, const uint64_t* index, const uint32_t* subindex,
                    size_t nseg, void* dst, size_t dst_n, uint32_t block_bytes, uint32_t* status) {
   if (!ctx || !src || !index || !status || (!dst && dst_n)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  const size_t ix_bytes = (nseg + 1) * sizeof(uint64_t), sub_bytes = nseg * SFH_SUBINDEX_WORDS * sizeof(uint32_t);
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, src_n ? src_n : 16, "input staging");
-  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, dst_n ? dst_n : 16, "output staging");
-  if (!rc) rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, (nseg + 1) * sizeof(uint64_t), "index staging");
-  if (!rc && subindex) rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, nseg * SFH_SUBINDEX_WORDS * sizeof(uint32_t), "sub-index staging");
+  int rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, ix_bytes, "index staging");
+  if (!rc && subindex) rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, sub_bytes, "sub-index staging");
+  if (!rc) rc = host_up(ctx, src, src_n, dst_n);
   if (rc) return rc;
   hipStream_t s = ctx->stream;
-  if (src_n) SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, s), "H2D");
-  SF_HIP(hipMemcpyAsync(ctx->d_index, index, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s), "H2D index");
-  if (subindex)
-    SF_HIP(hipMemcpyAsync(ctx->d_sub, subindex, nseg * SFH_SUBINDEX_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, s), "H2D sub-index");
+  SF_HIP(hipMemcpyAsync(ctx->d_index, index, ix_bytes, hipMemcpyHostToDevice, s), "H2D index");
+  if (subindex) SF_HIP(hipMemcpyAsync(ctx->d_sub, subindex, sub_bytes, hipMemcpyHostToDevice, s), "H2D sub-index");
   rc = sfh_decompress_device(ctx, ctx->d_in, src_n, ctx->d_index, subindex ? ctx->d_sub : nullptr, nseg, ctx->d_out,
                              dst_n, block_bytes, status, s);
   if (rc) return rc;
-  if (*status == 0 && dst_n) {
-    SF_HIP(hipMemcpyAsync(dst, ctx->d_out, dst_n, hipMemcpyDeviceToHost, s), "D2H");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");
-  }
-  return SFH_OK;
+  return *status ? SFH_OK : host_down(ctx, dst, dst_n);
 }
 
 // ---- the dictzip table read back (sf_dz_plan.h) ----
@@ -2537,13 +2517,12 @@ int sfh_dz_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sfh_
                              void* stream) {
   if (!ctx || !info || (!d_src && src_n) || (!d_index && index_cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   if (((uintptr_t)d_src & 3) || ((uintptr_t)d_index & 7)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, index 8)", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  (void)hipGetLastError();  // see enqueue()
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   if (!ctx->d_dzinfo) {
     const hipError_t e = hipMalloc(&ctx->d_dzinfo, sizeof(sf::DzInfo));
     if (e != hipSuccess) return fail(ctx, SFH_E_NOMEM, "dictzip info slot", e);
   }
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   if (int rc = order_behind_last_call(ctx, s)) return rc;  // (the info slot is the context's)
   SF_HIP(sf::launch_dz_index((const uint8_t*)d_src, src_n, d_index, index_cap, ctx->d_dzinfo, s), "launch k_dz_index");
   sf::DzInfo r{};
@@ -2560,10 +2539,10 @@ int sfh_decompress_dz_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void
                              uint32_t* status, void* stream) {
   if (!ctx || (!d_src && src_n) || !dst_n_out || !status || (!d_dst && dst_cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   if (((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & 15)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, dst 16)", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   const size_t entries = (size_t)SFH_DZ_MAX_CHUNKS + 1;
   if (int rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, entries * sizeof(uint64_t), "index staging")) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   sfh_dz_info info{};
   if (int rc = sfh_dz_read_index_device(ctx, d_src, src_n, &info, ctx->d_index, entries, s)) return rc;
   *dst_n_out = 0;
@@ -2581,12 +2560,8 @@ int sfh_decompress_dz_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void
   if (int rc = enqueue_inflate_batch(ctx, 1, srcs, src_ns, ctx->d_index, nullptr, dsts, dst_ns, &bb, SFH_GZIP, ctx->d_value,
                                      ctx->d_value + 1, s))
     return rc;
-  uint32_t res[2] = {0, 0};
-  SF_HIP(hipMemcpyAsync(res, ctx->d_value, sizeof res, hipMemcpyDeviceToHost, s), "copy status");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  *status = res[0];
-  if (res[0] == 0) *dst_n_out = info.total_n;
-  else snprintf(ctx->err, sizeof ctx->err, "segment %u: DecompressStatus %u", res[1], res[0]);
+  if (int rc = read_decode_status(ctx, status, s)) return rc;
+  if (*status == 0) *dst_n_out = info.total_n;
   return SFH_OK;
 }
 
@@ -2606,18 +2581,10 @@ int sfh_decompress_dz(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, ui
   }
   if (H.total_n > dst_cap) return fail(ctx, SFH_E_DST_TOO_SMALL, "ISIZE above dst_cap", hipSuccess);
   const uint64_t out_n = H.total_n;
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, src_n ? src_n : 16, "input staging");
-  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_n ? out_n : 16, "output staging");
+  int rc = host_up(ctx, src, src_n, out_n);
+  if (!rc) rc = sfh_decompress_dz_device(ctx, ctx->d_in, src_n, ctx->d_out, out_n, dst_n_out, status, ctx->stream);
   if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  if (src_n) SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, s), "H2D");
-  if ((rc = sfh_decompress_dz_device(ctx, ctx->d_in, src_n, ctx->d_out, out_n, dst_n_out, status, s))) return rc;
-  if (*status == 0 && out_n) {
-    SF_HIP(hipMemcpyAsync(dst, ctx->d_out, out_n, hipMemcpyDeviceToHost, s), "D2H");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");
-  }
-  return SFH_OK;
+  return *status ? SFH_OK : host_down(ctx, dst, out_n);
 }
 
 int sfh_decompress_dz_ranges(sfh_ctx* ctx, const void* src, size_t src_n, size_t count, const uint64_t* offsets,
@@ -2691,9 +2658,8 @@ int sfh_bgzf_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sf
   if (!ctx || !info || (!d_src && src_n) || ((!d_member_off || !d_out_off) && cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   if (((uintptr_t)d_src & 3) || ((uintptr_t)d_member_off & 7) || ((uintptr_t)d_out_off & 7))
     return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, index arrays 8)", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  (void)hipGetLastError();  // see enqueue()
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   *info = sfh_bgzf_info{0, 0, 0, 0, 0};
   if (src_n == 0) {  // no members
     if (!cap) return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < members + 1", hipSuccess);
@@ -2724,9 +2690,8 @@ int bgzf_decode_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_ds
   *dst_n_out = 0;
   *status = 0;
   if (src_n == 0) return SFH_OK;
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  (void)hipGetLastError();  // see enqueue()
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   // the index, in the context's own arrays: the file has no more members than nodes
   uint32_t nn = 0;
   if (int rc = bgzf_count_nodes(ctx, (const uint8_t*)d_src, src_n, s, &nn)) return rc;
@@ -2843,19 +2808,10 @@ int sfh_decompress_bgzf(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, 
   if (I.members == 0) return SFH_OK;
   if (I.max_isize <= sf::kWideRow) {  // the device path: narrow rows, or wide ones for a file with a member above 32768 bytes
     const bool wide = I.max_isize > sf::kChunk;
-    SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-    int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, src_n, "input staging");
-    if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, I.total_n ? I.total_n : 16, "output staging");
+    int rc = host_up(ctx, src, src_n, I.total_n);
+    if (!rc) rc = bgzf_decode_device(ctx, ctx->d_in, src_n, ctx->d_out, I.total_n, dst_n_out, status, ctx->stream, wide ? sf::kWideRow : sf::kChunk);
     if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-    SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, s), "H2D");
-    if ((rc = bgzf_decode_device(ctx, ctx->d_in, src_n, ctx->d_out, I.total_n, dst_n_out, status, s, wide ? sf::kWideRow : sf::kChunk))) return rc;
-    if (*status == 0 && I.total_n) {
-      SF_HIP(hipMemcpyAsync(dst, ctx->d_out, I.total_n, hipMemcpyDeviceToHost, s), "D2H");
-      SF_HIP(hipStreamSynchronize(s), "stream sync");
-    }
-    return SFH_OK;
+    return *status ? SFH_OK : host_down(ctx, dst, I.total_n);
   }
   // a member above 64 KiB (gzip members with BGZF's extra field, but not BGZF): each one an item of the stream decoder, into a
   // buffer of the call's own so that dst is written only when every member decoded
@@ -2903,9 +2859,8 @@ int sfh_recover_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint
   if (dst_n == SFH_SIZE_FROM_TRAILER || !d_index || ((uintptr_t)d_index & 7) || nseg != (size_t)chunks_of((size_t)dst_n) ||
       nseg > ((size_t)1 << 31) - 1)
     return fail(ctx, SFH_E_INVALID_ARG, "index: 8-byte aligned, nseg = max(1, ceil(dst_n / 32768))", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  (void)hipGetLastError();  // see enqueue()
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   const uint8_t* src = (const uint8_t*)d_src;
   uint32_t wst = 0, isize = 0;
   bool ok = false;
@@ -2931,13 +2886,10 @@ int sfh_recover_index(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t cont
   if (!index || dst_n == SFH_SIZE_FROM_TRAILER || nseg != (size_t)chunks_of((size_t)dst_n))
     return fail(ctx, SFH_E_INVALID_ARG, "index, nseg = max(1, ceil(dst_n / 32768))", hipSuccess);
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, src_n ? src_n : 16, "input staging");
-  if (!rc) rc = grow(ctx, &ctx->d_anyix, &ctx->d_anyix_cap, (nseg + 1) * sizeof(uint64_t), "recovered index");
-  if (!rc && depends) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, nseg, "depends staging");
+  int rc = grow(ctx, &ctx->d_anyix, &ctx->d_anyix_cap, (nseg + 1) * sizeof(uint64_t), "recovered index");
+  if (!rc) rc = host_up(ctx, src, src_n, depends ? nseg : 0);  // (the flags come down through d_out)
   if (rc) return rc;
   hipStream_t s = ctx->stream;
-  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  if (src_n) SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, s), "H2D");
   if ((rc = sfh_recover_index_device(ctx, ctx->d_in, src_n, container, dst_n, ctx->d_anyix, nseg, depends ? ctx->d_out : nullptr, s)))
     return rc;
   SF_HIP(hipMemcpyAsync(index, ctx->d_anyix, (nseg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "D2H index");
@@ -2951,9 +2903,8 @@ int sfh_decompress_any_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uin
   if (int rc = check_any(ctx, d_src, src_n, container, dst_n, true)) return rc;
   if (!status || (!d_dst && dst_n) || ((uintptr_t)d_dst & 15))
     return fail(ctx, SFH_E_INVALID_ARG, "argument (status, dst 16-byte aligned)", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  (void)hipGetLastError();  // see enqueue()
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   const uint8_t* src = (const uint8_t*)d_src;
   uint32_t wst = 0, isize = 0;
   int rc = any_wrapper(ctx, src, src_n, container, dst_n, s, &wst, &isize);
@@ -2986,39 +2937,23 @@ int sfh_decompress_any(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t con
                        uint64_t dst_n, uint64_t* dst_n_out, uint32_t* status) {
   if (int rc = check_any(ctx, src, src_n, container, dst_n, false)) return rc;
   if (!status || (!dst && dst_cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
-  uint64_t out_n = dst_n;
-  if (dst_n == SFH_SIZE_FROM_TRAILER) {  // ISIZE (a stream too short for a trailer: the device reads the wrapper and says so)
-    const uint8_t* p = (const uint8_t*)src;
-    out_n = src_n >= 18 ? (uint64_t)(p[src_n - 4] | (uint32_t)p[src_n - 3] << 8 | (uint32_t)p[src_n - 2] << 16 |
-                                     (uint32_t)p[src_n - 1] << 24)
-                        : 0;
-  }
+  const uint64_t out_n = dst_n == SFH_SIZE_FROM_TRAILER ? trailer_isize(src, src_n) : dst_n;
   if (out_n > dst_cap) return fail(ctx, SFH_E_DST_TOO_SMALL, "dst_cap below the output size", hipSuccess);
   if (dst_n_out) *dst_n_out = out_n;
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, src_n ? src_n : 16, "input staging");
-  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_n ? out_n : 16, "output staging");
+  int rc = host_up(ctx, src, src_n, out_n);
+  if (!rc) rc = sfh_decompress_any_device(ctx, ctx->d_in, src_n, container, ctx->d_out, out_n, status, ctx->stream);
   if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  if (src_n) SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, s), "H2D");
-  if ((rc = sfh_decompress_any_device(ctx, ctx->d_in, src_n, container, ctx->d_out, out_n, status, s))) return rc;
-  if (*status == 0 && out_n) {
-    SF_HIP(hipMemcpyAsync(dst, ctx->d_out, out_n, hipMemcpyDeviceToHost, s), "D2H");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");
-  }
-  return SFH_OK;
+  return *status ? SFH_OK : host_down(ctx, dst, out_n);
 }
 
 int sfh_recover_index_batch_device(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, uint32_t container,
                                    const uint64_t* dst_n, uint64_t* d_index, uint32_t* status, void* stream) {
   int rc = check_any_batch(ctx, count, d_srcs, src_n, container, nullptr, nullptr, dst_n, d_index, true, status, true);
   if (rc || count == 0) return rc;
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  (void)hipGetLastError();  // see enqueue()
+  hipStream_t s;
+  if ((rc = begin_call(ctx, stream, &s))) return rc;
   AnyBatch R;
-  if ((rc = any_batch_recover(ctx, count, d_srcs, src_n, container, nullptr, dst_n, d_index, stream ? (hipStream_t)stream : ctx->stream, R)))
-    return rc;
+  if ((rc = any_batch_recover(ctx, count, d_srcs, src_n, container, nullptr, dst_n, d_index, s, R))) return rc;
   for (size_t i = 0; i < count; ++i) status[i] = R.st[i] ? SFH_ITEM_NOT_INDEXABLE : 0u;  // (a wrapper that does not parse too)
   return SFH_OK;
 }
@@ -3028,9 +2963,8 @@ int sfh_decompress_any_batch_device(sfh_ctx* ctx, size_t count, const void* cons
                                     uint32_t* status, void* stream) {
   int rc = check_any_batch(ctx, count, d_srcs, src_n, container, d_dsts, dst_cap, dst_n, nullptr, false, status, true);
   if (rc || count == 0) return rc;
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  (void)hipGetLastError();  // see enqueue()
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if ((rc = begin_call(ctx, stream, &s))) return rc;
   AnyBatch R;
   if ((rc = any_batch_recover(ctx, count, d_srcs, src_n, container, dst_cap, dst_n, nullptr, s, R))) return rc;
   if ((rc = any_batch_decode(ctx, count, d_srcs, src_n, container, d_dsts, ctx->d_anyix, s, R))) return rc;
@@ -3045,33 +2979,14 @@ int sfh_recover_index_batch(sfh_ctx* ctx, size_t count, const void* const* srcs,
                             const uint64_t* dst_n, uint64_t* index, uint32_t* status) {
   int rc = check_any_batch(ctx, count, srcs, src_n, container, nullptr, nullptr, dst_n, index, true, status, false);
   if (rc || count == 0) return rc;
-  std::vector<uint64_t> in_off;
-  std::vector<const void*> d_srcs;
   size_t entries = count;
-  try {
-    in_off.resize(count + 1);
-    d_srcs.resize(count);
-  } catch (...) {
-    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
-  }
-  for (size_t i = 0; i < count; ++i) {
-    in_off[i + 1] = (in_off[i] + src_n[i] + 15) / 16 * 16;
-    entries += chunks_of((size_t)dst_n[i]);
-  }
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  for (size_t i = 0; i < count; ++i) entries += chunks_of((size_t)dst_n[i]);
+  Staged B;
   hipStream_t s = ctx->stream;
-  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
-  if (!rc) rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, entries * sizeof(uint64_t), "index staging");
-  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
-    ctx->h_stage = nullptr;
-    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
-  }
-  if (rc) return rc;
-  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  if ((rc = stage_up(ctx, srcs, src_n, in_off.data(), count, in_off[count], s))) return rc;
-  for (size_t i = 0; i < count; ++i) d_srcs[i] = ctx->d_in + in_off[i];
+  if ((rc = staged_up(ctx, B, count, srcs, src_n, nullptr))) return rc;  // (no output staging: the index comes down by itself)
+  if ((rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, entries * sizeof(uint64_t), "index staging"))) return rc;
   AnyBatch R;
-  if ((rc = any_batch_recover(ctx, count, d_srcs.data(), src_n, container, nullptr, dst_n, ctx->d_index, s, R))) {
+  if ((rc = any_batch_recover(ctx, count, B.d_srcs.data(), src_n, container, nullptr, dst_n, ctx->d_index, s, R))) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
@@ -3086,51 +3001,24 @@ int sfh_decompress_any_batch(sfh_ctx* ctx, size_t count, const void* const* srcs
                              uint32_t* status) {
   int rc = check_any_batch(ctx, count, srcs, src_n, container, dsts, dst_cap, dst_n, nullptr, false, status, false);
   if (rc || count == 0) return rc;
-  // The items packed into the device staging (16-byte aligned) and moved through the pinned buffer (stage_up, stage_down);
-  // only the items whose status is 0 are copied out of it.  An item's slot is its output size (ISIZE is read here); one
-  // whose size is above its capacity gets no slot, and the device call reports it.
-  std::vector<uint64_t> in_off, out_off, slot, got;
-  std::vector<const void*> d_srcs;
-  std::vector<void*> d_dsts;
+  // An item's slot is its output size (ISIZE is read here); one whose size is above its capacity gets no slot, and the device
+  // call reports it.
+  std::vector<uint64_t> slot;
   try {
-    in_off.resize(count + 1);
-    out_off.resize(count + 1);
     slot.resize(count);
-    got.resize(count);
-    d_srcs.resize(count);
-    d_dsts.resize(count);
   } catch (...) {
     return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
   }
   for (size_t i = 0; i < count; ++i) {
-    uint64_t n = dst_n[i];
-    if (n == SFH_SIZE_FROM_TRAILER) {
-      const uint8_t* p = (const uint8_t*)srcs[i];
-      const uint64_t sn = src_n[i];
-      n = sn >= 18 ? (uint64_t)(p[sn - 4] | (uint32_t)p[sn - 3] << 8 | (uint32_t)p[sn - 2] << 16 | (uint32_t)p[sn - 1] << 24) : 0;
-    }
+    const uint64_t n = dst_n[i] == SFH_SIZE_FROM_TRAILER ? trailer_isize(srcs[i], src_n[i]) : dst_n[i];
     slot[i] = n <= dst_cap[i] ? n : 0;
-    in_off[i + 1] = (in_off[i] + src_n[i] + 15) / 16 * 16;
-    out_off[i + 1] = (out_off[i] + slot[i] + 15) / 16 * 16;
   }
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  Staged B;
   hipStream_t s = ctx->stream;
-  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
-  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, out_off[count] ? out_off[count] : 16, "output staging");
-  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
-    ctx->h_stage = nullptr;
-    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
-  }
-  if (rc) return rc;
-  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  if ((rc = stage_up(ctx, srcs, src_n, in_off.data(), count, in_off[count], s))) return rc;
-  for (size_t i = 0; i < count; ++i) {
-    d_srcs[i] = ctx->d_in + in_off[i];
-    d_dsts[i] = ctx->d_out + out_off[i];
-  }
+  if ((rc = staged_up(ctx, B, count, srcs, src_n, slot.data()))) return rc;
   AnyBatch R;
-  rc = any_batch_recover(ctx, count, d_srcs.data(), src_n, container, slot.data(), dst_n, nullptr, s, R);
-  if (!rc) rc = any_batch_decode(ctx, count, d_srcs.data(), src_n, container, d_dsts.data(), ctx->d_anyix, s, R);
+  rc = any_batch_recover(ctx, count, B.d_srcs.data(), src_n, container, slot.data(), dst_n, nullptr, s, R);
+  if (!rc) rc = any_batch_decode(ctx, count, B.d_srcs.data(), src_n, container, B.d_dsts.data(), ctx->d_anyix, s, R);
   if (rc) {
     (void)hipStreamSynchronize(s);
     return rc;
@@ -3138,9 +3026,8 @@ int sfh_decompress_any_batch(sfh_ctx* ctx, size_t count, const void* const* srcs
   for (size_t i = 0; i < count; ++i) {
     status[i] = R.st[i];
     if (dst_n_out) dst_n_out[i] = R.out_n[i];
-    got[i] = status[i] == 0 ? R.out_n[i] : 0;
   }
-  return stage_down(ctx, dsts, got.data(), out_off.data(), count, out_off[count], s);
+  return staged_down(ctx, B, count, dsts, R.out_n.data(), status);
 }
 
 int sfh_last_recover_stats(sfh_ctx* ctx, float ms[2], uint64_t counts[2]) {
@@ -3159,9 +3046,8 @@ int sfh_inflate_stream_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uin
     return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   if (((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & 15))
     return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, dst 16)", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  (void)hipGetLastError();  // see enqueue()
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   return stream_one(ctx, d_src, src_n, container, d_dst, dst_cap, false, dst_n_out, status, s);
 }
 
@@ -3170,18 +3056,10 @@ int sfh_inflate_stream(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t con
   if (!ctx) return SFH_E_INVALID_ARG;
   if ((!src && src_n) || container > SFH_GZIP || !dst_n_out || !status || (!dst && dst_cap))
     return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, src_n ? src_n : 16, "input staging");
+  int rc = host_up(ctx, src, src_n, 0);  // (the driver sizes d_out once it knows the output's)
+  if (!rc) rc = stream_one(ctx, ctx->d_in, src_n, container, dst, dst_cap, dst != nullptr, dst_n_out, status, ctx->stream);
   if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  if (src_n) SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, s), "H2D");
-  if ((rc = stream_one(ctx, ctx->d_in, src_n, container, dst, dst_cap, dst != nullptr, dst_n_out, status, s))) return rc;
-  if (dst && *status == 0 && *dst_n_out) {  // (staged: the one item lies at ctx->d_out)
-    SF_HIP(hipMemcpyAsync(dst, ctx->d_out, *dst_n_out, hipMemcpyDeviceToHost, s), "D2H");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");
-  }
-  return SFH_OK;
+  return (dst && *status == 0) ? host_down(ctx, dst, *dst_n_out) : SFH_OK;  // (staged: the one item lies at ctx->d_out)
 }
 
 int sfh_inflate_stream_batch_device(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n,
@@ -3189,9 +3067,8 @@ int sfh_inflate_stream_batch_device(sfh_ctx* ctx, size_t count, const void* cons
                                     uint32_t* status, void* stream) {
   int rc = check_stream_batch(ctx, count, d_srcs, src_n, container, d_dsts, dst_cap, dst_n_out, status, true);
   if (rc || count == 0) return rc;
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  (void)hipGetLastError();  // see enqueue()
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if ((rc = begin_call(ctx, stream, &s))) return rc;
   return stream_batch_run(ctx, count, d_srcs, src_n, container, d_dsts, dst_cap, false, nullptr, dst_n_out, status, s);
 }
 
@@ -3199,37 +3076,14 @@ int sfh_inflate_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs
                              void* const* dsts, const uint64_t* dst_cap, uint64_t* dst_n_out, uint32_t* status) {
   int rc = check_stream_batch(ctx, count, srcs, src_n, container, dsts, dst_cap, dst_n_out, status, false);
   if (rc || count == 0) return rc;
-  // The items packed into the device staging (16-byte aligned) and moved through the pinned buffer (stage_up, stage_down);
-  // only the items whose status is 0 are copied out (their output packed by size in ctx->d_out).
-  std::vector<uint64_t> in_off, out_off, got;
-  std::vector<const void*> d_srcs;
-  try {
-    in_off.resize(count + 1);
-    got.resize(count);
-    d_srcs.resize(count);
-  } catch (...) {
-    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
-  }
-  for (size_t i = 0; i < count; ++i) in_off[i + 1] = (in_off[i] + src_n[i] + 15) / 16 * 16;
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  Staged B;  // (the output: packed by its size in ctx->d_out, laid out by the driver once the sizes are known)
   hipStream_t s = ctx->stream;
-  rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, in_off[count] ? in_off[count] : 16, "input staging");
-  if (!rc && !ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
-    ctx->h_stage = nullptr;
-    rc = fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
-  }
-  if (rc) return rc;
-  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (it may still read the staging)
-  if ((rc = stage_up(ctx, srcs, src_n, in_off.data(), count, in_off[count], s))) return rc;
-  for (size_t i = 0; i < count; ++i) d_srcs[i] = ctx->d_in + in_off[i];
-  if ((rc = stream_batch_run(ctx, count, d_srcs.data(), src_n, container, dsts, dst_cap, true, &out_off, dst_n_out, status, s))) {
+  if ((rc = staged_up(ctx, B, count, srcs, src_n, nullptr))) return rc;
+  if ((rc = stream_batch_run(ctx, count, B.d_srcs.data(), src_n, container, dsts, dst_cap, true, &B.out_off, dst_n_out, status, s))) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
-  if (!dsts) return SFH_OK;
-  // down: the packed output, each decoded item with status 0
-  for (size_t i = 0; i < count; ++i) got[i] = (dsts[i] && status[i] == 0) ? dst_n_out[i] : 0;
-  return stage_down(ctx, dsts, got.data(), out_off.data(), count, out_off[count], s);
+  return dsts ? staged_down(ctx, B, count, dsts, dst_n_out, status) : SFH_OK;  // (no dsts: a size query)
 }
 
 int sfh_last_stream_stats(sfh_ctx* ctx, float ms[SFH_STREAM_NSTAGES], uint64_t counts[SFH_STREAM_NCOUNTS]) {
@@ -3263,9 +3117,8 @@ int sfh_checksum_device(sfh_ctx* ctx, const void* d_src, size_t n, uint32_t kind
   if (!ctx || (!d_src && n) || !out || (kind != SFH_ZLIB && kind != SFH_GZIP)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   if ((uintptr_t)d_src & 15) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 16)", hipSuccess);
   if (n > ((size_t)1 << 44)) return fail(ctx, SFH_E_INVALID_ARG, "input too large", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  (void)hipGetLastError();  // see enqueue()
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   const uint32_t nchunks = chunks_of(n);
   int rc = ensure_sums(ctx, nchunks);
   if (!rc) rc = order_behind_last_call(ctx, s);
@@ -3405,8 +3258,8 @@ int sfh_gather_streams(sfh_ctx* ctx, void* nccl_comm, int root, const void* d_st
   if ((rc = R.CommCount(nccl_comm, &nranks)) != 0) return comm_fail(ctx, "ncclCommCount", rc);
   if ((rc = R.CommUserRank(nccl_comm, &rank)) != 0) return comm_fail(ctx, "ncclCommUserRank", rc);
   if (root < 0 || root >= nranks || (rank == root && !d_out)) return fail(ctx, SFH_E_INVALID_ARG, "root / d_out", hipSuccess);
-  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  hipStream_t s;
+  if (int rc = begin_call(ctx, stream, &s)) return rc;
   // Every rank contributes {size, base, cap, its d_stream, its d_out}: sizes are what is gathered; base and cap must be the
   // same on all ranks, and the root's two addresses let EVERY rank judge the root's own placement -- so every rank reaches
   // the same verdict BEFORE any transfer is posted, and nobody is left waiting in a send whose receive was refused.
@@ -3509,7 +3362,7 @@ int sfh_debug_read(sfh_ctx* ctx, int what, void* host_dst, size_t bytes) {
   // further than it was allocated: the last call may be a decode on a context whose compressor arrays are smaller or absent
   const size_t nlast = std::min<size_t>(ctx->last_chunks, std::max<uint32_t>(ctx->batch_chunks, sf::kMaxStrip / sf::kChunk));
   const size_t nc = std::min<size_t>(nlast, ctx->cap_batch), nidx = std::min<size_t>(ctx->last_chunks, ctx->cap_chunks);
-  if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // whatever stream it ran on
+  if (int rc = wait_idle(ctx)) return rc;  // whatever stream the last call ran on
   const void* p = nullptr;
   size_t avail = 0;
   switch (what) {

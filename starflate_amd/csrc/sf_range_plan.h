@@ -18,6 +18,8 @@
 
 #include <vector>
 
+#include "sf_stage_plan.h"
+
 namespace sf {
 namespace range {
 
@@ -115,6 +117,28 @@ inline int plan_ranges(uint64_t total_n, uint32_t block_bytes, size_t count, con
   }
   close();
   return kPlanOk;
+}
+
+// The host-buffer call uploads, per decode span, only the piece of the stream its rows read: from the smallest to the largest
+// of the span's index entries (index[first_seg .. first_seg + nrows]), clipped to src_n and rounded out to 16 bytes.  A damaged
+// index cannot send a row outside its piece: a row reads from its first entry on, and only when its second entry is not above
+// the bytes readable.  A span without rows has the empty piece at 0.
+struct Piece {
+  uint64_t lo, n;  // bytes [lo, lo + n) of the stream; lo a multiple of 16
+};
+inline Piece source_piece(const Span& S, const uint64_t* index, uint64_t src_n) {
+  uint64_t lo = 0, hi = 0;
+  if (S.nrows) {
+    lo = hi = index[S.first_seg];
+    for (uint32_t k = 1; k <= S.nrows; ++k) {
+      const uint64_t e = index[S.first_seg + k];
+      lo = e < lo ? e : lo;
+      hi = e > hi ? e : hi;
+    }
+  }
+  lo = (lo < src_n ? lo : src_n) / 16 * 16;
+  hi = stage::al16(hi < src_n ? hi : src_n);
+  return Piece{lo, (hi < src_n ? hi : src_n) - lo};
 }
 
 }  // namespace range

@@ -1,6 +1,6 @@
 // sf_stage_plan.h -- the host-buffer entry points' way through one pinned staging buffer: `count` items lie packed in a device
-// buffer, item i at bytes [off[i], off[i] + len[i]) of it (off ascending, the ranges disjoint), and the packed layout
-// [0, total) moves in pieces of at most `piece` bytes, because the pinned buffer holds one piece.  An item may straddle any
+// buffer, item i at bytes [off[i], off[i] + len[i]) of it (off ascending, the ranges disjoint: pack_layout), and the packed
+// layout [0, total) moves in pieces of at most `piece` bytes, because the pinned buffer holds one piece.  An item may straddle any
 // number of pieces.  Plain C++, no HIP: the copy between the staging and the device is the caller's (`xfer`), so the tests
 // compile these loops for the host as well (tests/cpp/stage_plan_host.cpp).
 #pragma once
@@ -12,6 +12,16 @@
 
 namespace sf {
 namespace stage {
+
+// The packed layout itself: items lie 16 bytes aligned (the device paths' alignment rules hold for every item of the staging).
+inline uint64_t al16(uint64_t b) { return (b + 15) / 16 * 16; }
+
+// off[0 .. count] from `count` slot sizes: slot i is [off[i], off[i] + slot[i]), off[0] = 0, every offset a multiple of 16,
+// off[count] the bytes the layout takes.  (A slot of no bytes takes none: it shares its offset with the next one.)
+inline void pack_layout(const uint64_t* slot, size_t count, uint64_t* off) {
+  off[0] = 0;
+  for (size_t i = 0; i < count; ++i) off[i + 1] = al16(off[i] + slot[i]);
+}
 
 // The items with bytes in piece [p0, p1): f(i, at, in_piece, n) for bytes [at, at + n) of item i, which are bytes
 // [in_piece, in_piece + n) of the piece.  first: an item none before which reaches p0 (pieces are visited in order);
