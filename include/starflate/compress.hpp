@@ -174,6 +174,23 @@ inline auto bgzf_read_index(std::span<const std::byte> src) -> compat::expected<
   ix.has_eof = info.has_eof != 0;
   return ix;
 }
+/// Virtual offsets, as tabix and BAI indexes state them (coffset << 16 | uoffset), to offsets into the file's output and back
+/// (sfh_bgzf_voffsets_to_offsets, sfh_bgzf_offsets_to_voffsets: host arithmetic).  A virtual offset that names no member's first
+/// byte, or a byte behind its output, and an offset above total_bytes give UINT64_MAX in their slot.
+inline auto bgzf_voffsets_to_offsets(const bgzf_index& ix, std::span<const std::uint64_t> voffsets) -> std::vector<std::uint64_t> {
+  std::vector<std::uint64_t> out(voffsets.size(), ~std::uint64_t{0});
+  if (ix.member_off.empty() || ix.out_off.size() != ix.member_off.size()) return out;
+  (void)sfh_bgzf_voffsets_to_offsets(ix.member_off.data(), ix.out_off.data(), static_cast<std::uint32_t>(ix.members()), out.size(),
+                                     voffsets.data(), out.data());
+  return out;
+}
+inline auto bgzf_offsets_to_voffsets(const bgzf_index& ix, std::span<const std::uint64_t> offsets) -> std::vector<std::uint64_t> {
+  std::vector<std::uint64_t> out(offsets.size(), ~std::uint64_t{0});
+  if (ix.member_off.empty() || ix.out_off.size() != ix.member_off.size()) return out;
+  (void)sfh_bgzf_offsets_to_voffsets(ix.member_off.data(), ix.out_off.data(), static_cast<std::uint32_t>(ix.members()), out.size(),
+                                     offsets.data(), out.data());
+  return out;
+}
 
 /// One GPU context (device scratch, stream).  Not thread-safe; distinct objects are independent.
 class compressor {
@@ -412,6 +429,46 @@ class compressor {
     const int rc = sfh_decompress_dz_ranges(ctx_, src.data(), src.size(), 1, &offset, &len, dp, &st);
     if (rc != SFH_OK || st > 7) return DecompressStatus::Error;
     return static_cast<DecompressStatus>(st);
+  }
+  /// Random access into a BGZF file, given nothing but its bytes: output bytes [offset, offset + part.size()) into `part`
+  /// (sfh_decompress_bgzf_ranges: the members are walked on the host, only the members holding the range are uploaded and
+  /// decoded; each is checked for its wrapper, its ISIZE and the size of its body; no checksum is verified).  A refused call
+  /// or a device problem is Error; `part` is written only on Success.
+  auto decompress_bgzf_range(std::span<const std::byte> file, std::span<std::byte> part, std::uint64_t offset) -> DecompressStatus {
+    if (!ctx_) return DecompressStatus::Error;
+    void* dp[1] = {part.data()};
+    const std::uint64_t len = part.size();
+    std::uint32_t st = 0;
+    const int rc = sfh_decompress_bgzf_ranges(ctx_, file.data(), file.size(), nullptr, nullptr, nullptr, 1, &offset, &len, dp, &st);
+    if (rc != SFH_OK || st > 7) return DecompressStatus::Error;
+    return static_cast<DecompressStatus>(st);
+  }
+  /// Many ranges of one BGZF file in one call: bytes [offsets[r], offsets[r] + parts[r].size()) into parts[r] (any addresses,
+  /// not overlapping; ranges may overlap each other), range r's status into statuses[r]; one range's failure changes no other.
+  /// ix (nullable): bgzf_read_index()'s, reusable across calls; without one the members are walked first.  A refused call
+  /// (arguments, no device) is the return value; the statuses are then not written.
+  auto decompress_bgzf_ranges(std::span<const std::byte> file, std::span<const std::uint64_t> offsets,
+                              std::span<const std::span<std::byte>> parts, std::span<DecompressStatus> statuses,
+                              const bgzf_index* ix = nullptr) -> CompressStatus {
+    if (!ctx_) return init_;
+    const std::size_t k = offsets.size();
+    if (parts.size() != k || statuses.size() != k) return CompressStatus::InvalidArgument;
+    if (ix != nullptr && (ix->member_off.empty() || ix->out_off.size() != ix->member_off.size())) return CompressStatus::InvalidArgument;
+    std::vector<void*> dp(k);
+    std::vector<std::uint64_t> len(k);
+    std::vector<std::uint32_t> st(k);
+    for (std::size_t i = 0; i < k; ++i) {
+      dp[i] = parts[i].data();
+      len[i] = parts[i].size();
+    }
+    sfh_bgzf_info info{};
+    if (ix != nullptr) info = sfh_bgzf_info{ix->total_bytes, static_cast<std::uint32_t>(ix->members()), ix->max_isize, ix->has_eof ? 1U : 0U, 0U};
+    const int rc = sfh_decompress_bgzf_ranges(ctx_, file.data(), file.size(), ix ? ix->member_off.data() : nullptr,
+                                              ix ? ix->out_off.data() : nullptr, ix ? &info : nullptr, k, offsets.data(), len.data(),
+                                              dp.data(), st.data());
+    if (rc != SFH_OK) return detail::to_status(rc);
+    for (std::size_t i = 0; i < k; ++i) statuses[i] = st[i] > 7 ? DecompressStatus::Error : static_cast<DecompressStatus>(st[i]);
+    return CompressStatus::Success;
   }
   /// The index of a stream given alone, recovered on the GPU from its flush markers: offsets of its
   /// max(1, ceil(dst_size / 32768)) segments + 1; block_bytes 0 (unknown), no regions.  A stream that is not block-flushed

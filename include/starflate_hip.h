@@ -544,6 +544,65 @@ int sfh_decompress_bgzf_wide_device(sfh_ctx* ctx, const void* d_src, size_t src_
                                     uint32_t* status, void* stream);
 int sfh_decompress_bgzf(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, uint64_t dst_cap, uint64_t* dst_n_out,
                         uint32_t* status);
+/* ---- BGZF random access: byte ranges of a BGZF file's output, decoded for the members that hold them ----
+ * The file and its index (member_off, out_off, info: sfh_bgzf_read_index*, reusable across calls).  Range r is output bytes
+ * [offsets[r], offsets[r] + lengths[r]); with status[r] == 0, dsts[r][0, lengths[r]) holds exactly those bytes of what
+ * sfh_decompress_bgzf_wide_device writes for the whole file.  Offsets, lengths and destination addresses need no alignment
+ * (ranges can be gathered into a packed buffer); source ranges may overlap each other, destination ranges [dsts[r], dsts[r] +
+ * lengths[r]) may not.  A range of no bytes is status 0 and writes nothing.
+ * Work: members have no fixed size, so the member of an output byte is a binary search in out_off, run on the device.  The
+ * DECODE SPAN of a range is exactly the members it touches -- first = the smallest i with out_off[i + 1] > offset, last = the
+ * smallest j with out_off[j + 1] >= offset + length, empty members between them included -- because no match reaches before
+ * its member: a 4 KiB record costs one or two members.  Every member of a span is one row of the indexed decoder, narrow
+ * (32768) with info->max_isize <= 32768, else wide (65536), for the file as a whole; the rows get tokens and the byte stage
+ * writes of each only its window.  Every range is decoded by itself: ranges that share a member each pay for it.  The rows
+ * run in launch batches of SFH_BATCH_CHUNKS (wide: SFH_BATCH_CHUNKS / 2) rows, a span may cross a batch boundary, and the token
+ * scratch is one batch's (sfh_last_decode_scratch_bytes).
+ * Verified per member of a span: its gzip wrapper, that its ISIZE equals its indexed size, and that its body decodes to
+ * exactly that many bytes.  NO checksum is verified: a member's decoded bytes never reach global memory as a whole, so a
+ * range cannot verify a CRC-32.  status[r]: the DecompressStatus of the first failing member of r's span in file order, a
+ * member's wrapper before its body; 0 when none fails.  Damage outside a range's span changes neither its bytes nor its
+ * status; one range's failure changes no other range; nothing is written outside [dsts[r], dsts[r] + lengths[r]).  An index or
+ * info that disagrees with the file ends in a status (a member that does not lie inside the file, or whose indexed size
+ * exceeds the row width, is Error and nothing of it is read; a range that ends behind out_off[members] is Error): never a read
+ * beyond src_n or a write outside a destination.  The arrays must hold info->members + 1 entries.
+ * Refused (SFH_E_INVALID_ARG) before anything is enqueued: a null context; with count > 0 a null file, index array (device
+ * call), info, array or status, or a null destination with a non-zero length; a device pointer out of alignment (d_src 4,
+ * d_member_off 8, d_out_off 8, d_status 4); offsets[r] + lengths[r] above info->total_n (or overflowing); overlapping
+ * destinations; count above 2^31 - 1.  Spans of more than 2^31 - 1 rows altogether: SFH_E_INVALID_ARG as soon as the planner's
+ * row total is known (the device call: behind its first synchronisation, before any decoder kernel is enqueued).
+ * info->max_isize > 65536: SFH_E_NOT_INDEXABLE.  info->status != 0: every range gets that status, nothing is decoded.
+ * count == 0: SFH_OK.  Afterwards the context has no index, as after sfh_decompress*.
+ *
+ * sfh_decompress_bgzf_ranges_device: device buffers, on `stream` (NULL: the context's).  TWO host synchronisations: the row
+ * total (it sizes the row tables, the segment records and the number of launch batches), then the end of the call.  The
+ * statuses stay on the device: d_status, device uint32[count].
+ * sfh_decompress_bgzf_ranges: host buffers, synchronous, status[count] on the host; dsts[r] is written only when status[r]
+ * == 0.  member_off / out_off / info may all be NULL (all three or none): the members are walked on the host first
+ * (sfh_bgzf_read_index), and a file that does not parse gives every range the walk's status.  The whole file is NOT uploaded:
+ * for every span only its members' bytes [member_off[first], member_off[last + 1]) go up, clipped to src_n and rounded out
+ * to 16 bytes, packed piece after piece through the pinned staging; every row of a span carries a file base that points as far
+ * in front of the span's piece as the piece's first byte lies in the file (a per-span InflateSeg.src), so member offsets stay
+ * offsets into the file and what the kernels read is the uploaded copy.  The index (16 bytes per member) goes up whole. */
+int sfh_decompress_bgzf_ranges_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const uint64_t* d_member_off,
+                                      const uint64_t* d_out_off, const sfh_bgzf_info* info, size_t count, const uint64_t* offsets,
+                                      const uint64_t* lengths, void* const* d_dsts, uint32_t* d_status, void* stream);
+int sfh_decompress_bgzf_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uint64_t* member_off, const uint64_t* out_off,
+                               const sfh_bgzf_info* info, size_t count, const uint64_t* offsets, const uint64_t* lengths,
+                               void* const* dsts, uint32_t* status);
+/* Virtual offsets, as tabix and BAI indexes state them: v = coffset << 16 | uoffset.  Host arithmetic on a host index
+ * (member_off, out_off: members + 1 entries each), no context, no device.
+ * sfh_bgzf_voffsets_to_offsets: v -> out_off[i] + uoffset, where member_off[i] == coffset (a binary search) and uoffset <= the
+ * member's output bytes; coffset == member_off[members] with uoffset == 0 -> total_n; anything else -> UINT64_MAX in that
+ * slot, and the call still returns SFH_OK.
+ * sfh_bgzf_offsets_to_voffsets: o -> the member that holds byte o (the span rule's `first`: never an empty member for a byte
+ * that exists) and o's place in it; total_n -> member_off[members] << 16; o above total_n -> UINT64_MAX.  So
+ * to_offsets(to_voffsets(o)) == o for every o in [0, total_n].
+ * SFH_E_INVALID_ARG: a null index array, or with count > 0 a null array. */
+int sfh_bgzf_voffsets_to_offsets(const uint64_t* member_off, const uint64_t* out_off, uint32_t members, size_t count,
+                                 const uint64_t* voffsets, uint64_t* offsets);
+int sfh_bgzf_offsets_to_voffsets(const uint64_t* member_off, const uint64_t* out_off, uint32_t members, size_t count,
+                                 const uint64_t* offsets, uint64_t* voffsets);
 
 /* ---- decoding without side information ----
  * The segment index of a stream that is flushed every 32 KiB of output -- every stream sfh_compress* writes, and zlib's with

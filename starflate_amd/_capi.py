@@ -38,6 +38,7 @@ EXPORTS = [
     "sfh_bgzf_bound", "sfh_compress_bgzf_device_async", "sfh_compress_bgzf_device", "sfh_compress_bgzf",
     "sfh_bgzf_read_index", "sfh_bgzf_read_index_device", "sfh_decompress_bgzf_device", "sfh_decompress_bgzf",
     "sfh_decompress_bgzf_wide_device",
+    "sfh_decompress_bgzf_ranges_device", "sfh_decompress_bgzf_ranges", "sfh_bgzf_voffsets_to_offsets", "sfh_bgzf_offsets_to_voffsets",
     "sfh_recover_index_device", "sfh_recover_index", "sfh_decompress_any_device", "sfh_decompress_any", "sfh_last_recover_stats",
     "sfh_recover_index_batch_device", "sfh_recover_index_batch", "sfh_decompress_any_batch_device", "sfh_decompress_any_batch",
     "sfh_inflate_stream_device", "sfh_inflate_stream", "sfh_inflate_stream_batch_device", "sfh_inflate_stream_batch",
@@ -140,6 +141,15 @@ def lib():
     L.sfh_decompress_bgzf_wide_device.restype = C.c_int
     L.sfh_decompress_bgzf.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.sfh_decompress_bgzf.restype = C.c_int
+    u64 = C.POINTER(C.c_uint64)
+    L.sfh_decompress_bgzf_ranges_device.argtypes = [vp, vp, sz, vp, vp, C.POINTER(BgzfInfo), sz, u64, u64, C.POINTER(vp), vp, vp]
+    L.sfh_decompress_bgzf_ranges_device.restype = C.c_int
+    L.sfh_decompress_bgzf_ranges.argtypes = [vp, vp, sz, vp, vp, C.POINTER(BgzfInfo), sz, u64, u64, C.POINTER(vp), vp]
+    L.sfh_decompress_bgzf_ranges.restype = C.c_int
+    L.sfh_bgzf_voffsets_to_offsets.argtypes = [vp, vp, C.c_uint32, sz, vp, vp]
+    L.sfh_bgzf_voffsets_to_offsets.restype = C.c_int
+    L.sfh_bgzf_offsets_to_voffsets.argtypes = [vp, vp, C.c_uint32, sz, vp, vp]
+    L.sfh_bgzf_offsets_to_voffsets.restype = C.c_int
     L.sfh_compress.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]
     L.sfh_compress.restype = C.c_int
     L.sfh_compress_multi.argtypes = [C.POINTER(vp), C.c_int, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]

@@ -235,6 +235,66 @@ class Compressor:
                                                               C.byref(got), C.byref(st), C.c_void_p(s)))
         return out, int(got.value), int(st.value)
 
+    # ---- BGZF random access: byte ranges of a BGZF file's output (sfh_decompress_bgzf_ranges*) ----
+    def read_bgzf_ranges(self, bgzf, offsets, lengths, index=None):
+        """Host buffers: byte ranges of what a BGZF file holds -> (list of bytes, None where a range's status is not 0; uint32
+        status array).  index: bgzf_index()'s (member_off, out_off, info), reusable across calls; None: the members are walked on
+        the host first (a file that does not parse gives every range the walk's status).  Of the file only the members that
+        hold the ranges travel to the device; each is checked for its wrapper, its ISIZE and the size of its body.  No checksum
+        is verified (a range cannot verify one).  Offsets from a tabix / BAI index: bgzf_voffsets_to_offsets."""
+        src = _as_bytes(bgzf)
+        offs, lens = [int(o) for o in offsets], [int(m) for m in lengths]
+        if len(offs) != len(lens) or any(o < 0 or m < 0 for o, m in zip(offs, lens)):
+            raise ValueError("offsets and lengths: one non-negative pair per range")
+        k = len(offs)
+        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in lens]
+        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
+        st = np.zeros(max(k, 1), dtype=np.uint32)
+        if index is None:
+            moff = ooff = info = None
+        else:
+            moff, ooff, info = _bgzf_index_args(index)
+        self._check(self._lib.sfh_decompress_bgzf_ranges(
+            self._h, src.ctypes.data if src.size else None, src.size, moff.ctypes.data if moff is not None else None,
+            ooff.ctypes.data if ooff is not None else None, C.byref(info) if info is not None else None, k,
+            (C.c_uint64 * k)(*offs), (C.c_uint64 * k)(*lens), dp, st.ctypes.data))
+        return [dsts[i][: lens[i]].tobytes() if st[i] == 0 else None for i in range(k)], st[:k]
+
+    def read_bgzf_ranges_tensor(self, src, member_off, out_off, info, offsets, lengths, outs=None, stream=None):
+        """Device buffers: src (1-D uint8 CUDA tensor holding a BGZF file) and bgzf_index_tensor()'s member_off, out_off (int64
+        CUDA tensors of members + 1 entries) and info dict -> (outs, status).  outs: one uint8 tensor (or view, any alignment:
+        slices of one packed buffer will do) of at least lengths[i] bytes per range, not overlapping (default: new ones);
+        range i's bytes are outs[i][:lengths[i]]; status: an int32 tensor on the device, one DecompressStatus per range.  Two
+        host synchronisations of `stream` (default: the current one): the planner's row total, then the end of the call."""
+        import torch
+
+        self._check_tensor(src)
+        for t in (member_off, out_off):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
+                raise ValueError("member_off / out_off must be contiguous int64 CUDA tensors")
+        binfo = _bgzf_info_struct(info)
+        if member_off.numel() != binfo.members + 1 or out_off.numel() != binfo.members + 1:
+            raise ValueError("member_off / out_off must hold members + 1 entries")
+        offs, lens = [int(o) for o in offsets], [int(m) for m in lengths]
+        if len(offs) != len(lens) or any(o < 0 or m < 0 for o, m in zip(offs, lens)):
+            raise ValueError("offsets and lengths: one non-negative pair per range")
+        k = len(offs)
+        dev = torch.device("cuda", self.device)
+        if outs is None:
+            outs = [torch.empty(max(m, 1), dtype=torch.uint8, device=dev) for m in lens]
+        outs = list(outs)
+        if len(outs) != k or any(o.numel() < m for o, m in zip(outs, lens)):
+            raise ValueError("outs must hold one tensor of at least lengths[i] bytes per range")
+        for t in outs:
+            self._check_tensor(t)
+        status = torch.zeros(max(k, 1), dtype=torch.int32, device=dev)
+        dp = (C.c_void_p * k)(*[o.data_ptr() for o in outs])
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        self._check(self._lib.sfh_decompress_bgzf_ranges_device(
+            self._h, src.data_ptr(), src.numel(), member_off.data_ptr(), out_off.data_ptr(), C.byref(binfo), k,
+            (C.c_uint64 * k)(*offs), (C.c_uint64 * k)(*lens), dp, C.c_void_p(status.data_ptr()), C.c_void_p(s)))
+        return outs, status[:k]
+
     # ---- many independent items, each its own stream, in one call (sfh_compress_batch*) ----
     def compress_batch(self, items, strategy="auto", final_stream=True, lazy=True, stored_fast_path=True, container="raw",
                        block_bytes=0, effort="default"):
@@ -1210,6 +1270,59 @@ def bgzf_index(data):
     if rc:
         raise StarflateError(rc, "sfh_bgzf_read_index")
     return moff, ooff, _bgzf_info_dict(info)
+
+
+def _bgzf_info_struct(info):
+    """bgzf_index()'s info dict (or a BgzfInfo) -> sfh_bgzf_info; `status` (absent from the dict: 0) passes through"""
+    if isinstance(info, _capi.BgzfInfo):
+        return info
+    return _capi.BgzfInfo(int(info["total_n"]), int(info["members"]), int(info["max_isize"]), int(bool(info["has_eof"])),
+                          int(info.get("status", 0)))
+
+
+def _bgzf_index_args(index):
+    member_off, out_off, info = index
+    moff = np.ascontiguousarray(member_off, dtype=np.uint64).ravel()
+    ooff = np.ascontiguousarray(out_off, dtype=np.uint64).ravel()
+    binfo = _bgzf_info_struct(info)
+    if moff.size != binfo.members + 1 or ooff.size != binfo.members + 1:
+        raise ValueError("member_off / out_off must hold members + 1 entries")
+    return moff, ooff, binfo
+
+
+def _voffset_call(fn, member_off, out_off, values):
+    moff = np.ascontiguousarray(member_off, dtype=np.uint64).ravel()
+    ooff = np.ascontiguousarray(out_off, dtype=np.uint64).ravel()
+    if moff.size == 0 or moff.size != ooff.size:
+        raise ValueError("member_off / out_off must hold members + 1 entries")
+    src = np.ascontiguousarray(values, dtype=np.uint64).ravel()
+    out = np.zeros(src.size, dtype=np.uint64)
+    rc = fn(moff.ctypes.data, ooff.ctypes.data, moff.size - 1, src.size, src.ctypes.data if src.size else None,
+            out.ctypes.data if src.size else None)
+    if rc:
+        raise StarflateError(rc, fn.__name__)
+    return out
+
+
+def bgzf_voffsets_to_offsets(member_off, out_off, voffsets):
+    """The virtual offsets of a tabix / BAI index (coffset << 16 | uoffset) -> uint64 offsets into the file's output, by
+    bgzf_index()'s arrays; 2^64 - 1 where a virtual offset names no member's first byte or a byte behind its output.  Host
+    arithmetic, no device."""
+    return _voffset_call(_capi.lib().sfh_bgzf_voffsets_to_offsets, member_off, out_off, voffsets)
+
+
+def bgzf_offsets_to_voffsets(member_off, out_off, offsets):
+    """Offsets into a BGZF file's output -> virtual offsets: the member that holds the byte (never an empty one) and the
+    byte's place in it; total_n -> the file's end << 16; 2^64 - 1 above total_n.  Host arithmetic, no device."""
+    return _voffset_call(_capi.lib().sfh_bgzf_offsets_to_voffsets, member_off, out_off, offsets)
+
+
+def read_bgzf_ranges(bgzf, offsets, lengths, index=None, device=0):
+    """Byte ranges of what a BGZF file holds -> (list of bytes or None, status array) (Compressor.read_bgzf_ranges)."""
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    return c.read_bgzf_ranges(bgzf, offsets, lengths, index=index)
 
 
 def compress_bgzf(data, device=0, **options):

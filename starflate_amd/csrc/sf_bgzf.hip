@@ -14,7 +14,18 @@
 //   k_bgzf_scatter  reached nodes in order (rank = hops of node 0 - own hops): member_off, and the ISIZEs by rank
 //   k_bgzf_finish   one workgroup: the prefix sums of ISIZE (64-bit), the largest ISIZE, the EOF member, the info
 // All reads of the file are parse_member's, bounded by src_n, and the scan's aligned dwords below it.
+// Random access (sfh_decompress_bgzf_ranges*; the planner: sf_bgzf_range_plan.h), from the index the walk left on the device:
+//   k_bgzf_range_spans  one lane per range: the two binary searches in out_off -> its first member and its rows; the rows of
+//                       the call summed (64-bit).  Behind it an exclusive scan of the rows, and the call's one planning
+//                       synchronisation: the total sizes the row tables
+//   k_bgzf_range_rows   one lane per row: its range by a binary search in the scan, the member placed inside the bytes the
+//                       range may read, gzip_head on the member's own bytes with the ISIZE the index implies, and the decoder's
+//                       row exactly as k_bgzf_rows writes it (the stream is the FILE, implied entries and read limit absolute,
+//                       kSegWrapped) beside its write window, its strip of one and its wrapper status; per range its span
+//   k_bgzf_fold_spans   one wave per range: the first failing row in row order, a row's wrapper status before its body's
+// No checksum is verified there (see sf_bgzf_range_plan.h).
 #include "sf_bgzf_plan.h"
+#include "sf_bgzf_range_plan.h"
 #include "sf_device.h"
 
 namespace sf {
@@ -236,6 +247,83 @@ __global__ __launch_bounds__(KZ_FIN) void k_bgzf_first(const uint32_t* __restric
   }
 }
 
+
+constexpr uint32_t kNoMember = 0xFFFFFFFFu;  // plan[r] of a range the index does not hold
+
+__global__ __launch_bounds__(KZ_THREADS) void k_bgzf_range_spans(const BgzfRange* __restrict__ ranges, uint32_t n,
+                                                                 const uint64_t* __restrict__ out_off, uint32_t members,
+                                                                 uint32_t* __restrict__ plan, unsigned long long* __restrict__ total) {
+  const uint32_t r = blockIdx.x * KZ_THREADS + threadIdx.x;
+  uint32_t rows = 0;
+  if (r < n) {
+    const uint64_t off = ranges[r].offset, len = ranges[r].length;
+    const bgzf::Span S = bgzf::span_of(out_off, members, off, len);
+    // no rows: a range of no bytes inside the output, or one the index does not hold
+    const bool held = len ? S.rows != 0 : bgzf::range_inside(out_off, members, off, len);
+    plan[r] = held ? S.first : kNoMember;
+    plan[n + r] = rows = held ? S.rows : 0u;
+  }
+  const uint32_t sum = wave_sum(rows);
+  if ((threadIdx.x & 63) == 0 && sum) atomicAdd(total, (unsigned long long)sum);
+}
+
+__global__ __launch_bounds__(KZ_THREADS) void k_bgzf_range_rows(const BgzfRange* __restrict__ ranges, uint32_t n,
+                                                                const uint64_t* __restrict__ member_off,
+                                                                const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ plan,
+                                                                const uint32_t* __restrict__ row0, uint32_t nrows, uint32_t per_batch,
+                                                                uint32_t row_bytes, InflateSeg* __restrict__ segs,
+                                                                InflateClip* __restrict__ clips, InflateStrip* __restrict__ strips,
+                                                                uint64_t* __restrict__ implied, uint32_t* __restrict__ wst,
+                                                                InflateSpan* __restrict__ spans) {
+  const uint32_t g = blockIdx.x * KZ_THREADS + threadIdx.x;
+  if (g < n) spans[g] = InflateSpan{row0[g], plan[n + g]};  // (a range without rows has no row's lane: the first n lanes write the spans)
+  if (g >= nrows) return;
+  uint32_t lo = 0, hi = n - 1;  // the last range whose rows start at or before g: ranges without rows in front of it share its row0
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo + 1) / 2;
+    if (row0[mid] <= g) lo = mid;
+    else hi = mid - 1;
+  }
+  const BgzfRange R = ranges[lo];
+  const bgzf::RangeRow W = bgzf::row_of(out_off, plan[lo], g - row0[lo], R.offset, R.length);
+  const uint64_t a = member_off[W.member], e = member_off[W.member + 1];
+  // the member inside the bytes this range may read, and no more output than a row holds -- else nothing of it is read
+  uint32_t st = gz::kStOk, want = 0, isize = 0;
+  uint64_t n_m = 0, hdr = 0, end = 0;
+  if (a < R.src_lo || e < a || e > R.src_n || W.out_n > row_bytes) {
+    st = gz::kStError;
+  } else {
+    n_m = end = e - a;
+    gzip_head(R.src + a, n_m, W.out_n, st, hdr, end, want, isize);
+    if (st == gz::kStOk && isize != W.out_n) st = gz::kStError;  // (above it: gzip_head's DstTooSmall)
+  }
+  const bool ok = st == gz::kStOk;
+  uint64_t* ix = implied + 2 * (uint64_t)g;
+  ix[0] = ok ? a + hdr : 0;
+  ix[1] = ok ? a + end : 0;
+  segs[g] = InflateSeg{R.src, ix, nullptr, nullptr, ok ? a + n_m - 8 : 0, ok ? W.out_n : 0u, kSegWrapped};
+  clips[g] = InflateClip{R.dst + W.dst_off, ok ? W.lo : 0u, ok ? W.hi : 0u};
+  strips[g] = InflateStrip{g % per_batch, 1u};
+  wst[g] = st;
+}
+
+__global__ __launch_bounds__(64) void k_bgzf_fold_spans(const InflateSpan* __restrict__ spans, uint32_t n, const uint32_t* __restrict__ plan,
+                                                        const SegInfo* __restrict__ info, const uint32_t* __restrict__ wst,
+                                                        uint32_t* __restrict__ status) {
+  const uint32_t r = blockIdx.x, lane = threadIdx.x;
+  if (r >= n) return;
+  const InflateSpan S = spans[r];
+  uint32_t first = 0xFFFFFFFFu;
+  for (uint32_t k = lane; k < S.nrows && first == 0xFFFFFFFFu; k += 64)
+    if (wst[S.row0 + k] != gz::kStOk || info[S.row0 + k].status != 0) first = k;
+#pragma unroll
+  for (uint32_t d = 32; d; d >>= 1) first = min(first, (uint32_t)__shfl_xor((int)first, (int)d));
+  if (lane != 0) return;
+  uint32_t st = plan[r] == kNoMember ? gz::kStError : gz::kStOk;
+  if (first != 0xFFFFFFFFu) st = wst[S.row0 + first] != gz::kStOk ? wst[S.row0 + first] : info[S.row0 + first].status;
+  status[r] = st;
+}
+
 }  // namespace
 
 uint32_t bgzf_scan_blocks(uint64_t src_n) { return grid(src_n, KZ_BLOCK_BYTES); }
@@ -282,6 +370,29 @@ hipError_t launch_bgzf_walk(const uint8_t* src, uint64_t src_n, const uint32_t* 
 
 hipError_t launch_bgzf_first(const uint32_t* status, uint32_t m, uint32_t* res, hipStream_t s) {
   hipLaunchKernelGGL(k_bgzf_first, dim3(1), dim3(KZ_FIN), 0, s, status, m, res);
+  return hipGetLastError();
+}
+
+hipError_t launch_bgzf_range_spans(const BgzfRange* ranges, uint32_t n, const uint64_t* out_off, uint32_t members, uint32_t* plan,
+                                   unsigned long long* total, hipStream_t s) {
+  const hipError_t e = hipMemsetAsync(total, 0, sizeof *total, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_bgzf_range_spans, dim3(grid(n, KZ_THREADS)), dim3(KZ_THREADS), 0, s, ranges, n, out_off, members, plan, total);
+  return hipGetLastError();
+}
+
+hipError_t launch_bgzf_range_rows(const BgzfRange* ranges, uint32_t n, const uint64_t* member_off, const uint64_t* out_off,
+                                  const uint32_t* plan, const uint32_t* row0, uint32_t nrows, uint32_t per_batch, uint32_t row_bytes,
+                                  InflateSeg* segs, InflateClip* clips, InflateStrip* strips, uint64_t* implied, uint32_t* wst,
+                                  InflateSpan* spans, hipStream_t s) {
+  hipLaunchKernelGGL(k_bgzf_range_rows, dim3(grid(nrows > n ? nrows : n, KZ_THREADS)), dim3(KZ_THREADS), 0, s, ranges, n, member_off,
+                     out_off, plan, row0, nrows, per_batch, row_bytes, segs, clips, strips, implied, wst, spans);
+  return hipGetLastError();
+}
+
+hipError_t launch_bgzf_fold_spans(const InflateSpan* spans, uint32_t n, const uint32_t* plan, const SegInfo* info, const uint32_t* wst,
+                                  uint32_t* status, hipStream_t s) {
+  hipLaunchKernelGGL(k_bgzf_fold_spans, dim3(n), dim3(64), 0, s, spans, n, plan, info, wst, status);
   return hipGetLastError();
 }
 

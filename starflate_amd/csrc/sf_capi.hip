@@ -3,6 +3,7 @@
 #include "../../include/starflate_hip.h"
 #include "sf_any_plan.h"
 #include "sf_bgzf_plan.h"
+#include "sf_bgzf_range_plan.h"
 #include "sf_device.h"
 #include "sf_dz_plan.h"
 #include "sf_inflate_core.h"
@@ -43,7 +44,8 @@ struct sfh_ctx {
   uint8_t* d_bgzfwalk = nullptr;
   uint64_t* d_bgzfix = nullptr;
   uint8_t* d_bgzfrows = nullptr;
-  size_t d_bgzfcnt_cap = 0, d_bgzfwalk_cap = 0, d_bgzfix_cap = 0, d_bgzfrows_cap = 0;
+  uint8_t* d_bgzfrng = nullptr;  // sfh_decompress_bgzf_ranges*: the planner's per-range arrays (the rows: d_bgzfrows)
+  size_t d_bgzfcnt_cap = 0, d_bgzfwalk_cap = 0, d_bgzfix_cap = 0, d_bgzfrows_cap = 0, d_bgzfrng_cap = 0;
   uint64_t* d_index = nullptr;   // staging for the host-buffer decoder
   size_t d_index_cap = 0;
   uint32_t* d_sub = nullptr;
@@ -2057,6 +2059,7 @@ void sfh_destroy(sfh_ctx* ctx) {
   (void)hipFree(ctx->d_bgzfwalk);
   (void)hipFree(ctx->d_bgzfix);
   (void)hipFree(ctx->d_bgzfrows);
+  (void)hipFree(ctx->d_bgzfrng);
   (void)hipFree(ctx->d_index);
   (void)hipFree(ctx->d_sub);
   for (hipEvent_t e : ctx->ev_inf) (void)hipEventDestroy(e);
@@ -2850,6 +2853,230 @@ int sfh_decompress_bgzf(sfh_ctx* ctx, const void* src, size_t src_n, void* dst, 
   }
   memcpy(dst, out.data(), I.total_n);
   *dst_n_out = I.total_n;
+  return SFH_OK;
+}
+
+// ---- BGZF random access (sf_bgzf_range_plan.h; the kernels: sf_bgzf.hip) ----
+namespace {
+// Everything the calls check before they plan or enqueue anything (`dev`: device buffers and their alignment rules; the host
+// call may come without an index, and then `info` is the host walk's).
+int check_bgzf_ranges(sfh_ctx* ctx, const void* src, const uint64_t* member_off, const uint64_t* out_off, const sfh_bgzf_info* info,
+                      size_t count, const uint64_t* offsets, const uint64_t* lengths, void* const* dsts, const uint32_t* status,
+                      bool dev) {
+  if (!src || !member_off || !out_off || !info || !offsets || !lengths || !dsts || !status)
+    return fail(ctx, SFH_E_INVALID_ARG, "null array", hipSuccess);
+  if (count > ((size_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "too many ranges", hipSuccess);
+  if (dev && (((uintptr_t)src & 3) || ((uintptr_t)member_off & 7) || ((uintptr_t)out_off & 7) || ((uintptr_t)status & 3)))
+    return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, index arrays 8, status 4)", hipSuccess);
+  for (size_t r = 0; r < count; ++r) {
+    if (!dsts[r] && lengths[r]) return fail(ctx, SFH_E_INVALID_ARG, "null destination", hipSuccess);
+    if (offsets[r] > info->total_n || lengths[r] > info->total_n - offsets[r])
+      return fail(ctx, SFH_E_INVALID_ARG, "a range ends behind total_n", hipSuccess);
+  }
+  if (int rc = check_disjoint(ctx, dsts, lengths, count)) return rc;
+  if (info->max_isize > sf::kWideRow) return fail(ctx, SFH_E_NOT_INDEXABLE, "a member above 65536 bytes: not BGZF", hipSuccess);
+  return SFH_OK;
+}
+
+// Device buffers, arguments checked; ranges[r]: the call's range rows (what each reads: the file itself, or the host call's
+// per-span piece).  The rows go up in one copy; k_bgzf_range_spans and the scan plan on the device; the row total comes back
+// (the planning synchronisation); then the row tables, the token kernels (as they are) and the clipped byte stage batch after
+// batch, and the fold of every range's status.  Ends synchronised.
+int enqueue_bgzf_ranges(sfh_ctx* ctx, const sf::BgzfRange* ranges, size_t count, const uint64_t* d_member_off, const uint64_t* d_out_off,
+                        const sfh_bgzf_info* info, uint32_t* d_status, hipStream_t s) {
+  const uint32_t n = (uint32_t)count;
+  const bool wide = info->max_isize > sf::kChunk;
+  const uint32_t row = wide ? sf::kWideRow : sf::kChunk, per = sf::bgzf::rows_per_batch(ctx->batch_chunks, wide);
+  const size_t bytes = count * sizeof(sf::BgzfRange);
+  // plan u32[2n] | row0 u32[n] | the scan's scratch and total | the rows' total (64-bit) | spans
+  const size_t tmp_words = sf::any_scan_tmp_words(n);
+  const size_t o_row0 = 2 * count * sizeof(uint32_t), o_tmp = o_row0 + count * sizeof(uint32_t);
+  const size_t o_total = al16(o_tmp + (tmp_words + 1) * sizeof(uint32_t)), o_spans = o_total + 16;
+  int rc = stage_tables(ctx, bytes);
+  if (!rc) rc = grow(ctx, &ctx->d_bgzfrng, &ctx->d_bgzfrng_cap, o_spans + count * sizeof(sf::InflateSpan), "BGZF range plan");
+  if (rc) return rc;
+  memcpy(ctx->h_tab, ranges, bytes);
+  const sf::BgzfRange* t_ranges = (const sf::BgzfRange*)ctx->d_tab;
+  uint32_t* plan = (uint32_t*)ctx->d_bgzfrng;
+  uint32_t* row0 = (uint32_t*)(ctx->d_bgzfrng + o_row0);
+  uint32_t* tmp = (uint32_t*)(ctx->d_bgzfrng + o_tmp);
+  unsigned long long* d_rows = (unsigned long long*)(ctx->d_bgzfrng + o_total);
+  sf::InflateSpan* spans = (sf::InflateSpan*)(ctx->d_bgzfrng + o_spans);
+  ctx->index_valid = false;
+  ctx->bix_valid = false;
+  ctx->ev_inf_valid = false;
+  if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
+  SF_HIP(sf::launch_bgzf_range_spans(t_ranges, n, d_out_off, info->members, plan, d_rows, s), "launch k_bgzf_range_spans");
+  SF_HIP(sf::launch_scan_u32(plan + n, row0, n, tmp, tmp + tmp_words, s), "scan of the ranges' rows");
+  unsigned long long total = 0;
+  SF_HIP(hipMemcpyAsync(&total, d_rows, sizeof total, hipMemcpyDeviceToHost, s), "copy row total");
+  if ((rc = mark_call_end(ctx, s))) return rc;
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  if (total > sf::bgzf::kMaxRangeRows) return fail(ctx, SFH_E_INVALID_ARG, "decode spans of more than 2^31 - 1 members in one call", hipSuccess);
+  const uint32_t T = (uint32_t)total;
+  const size_t t1 = std::max<size_t>(T, 1);
+  const size_t o_clips = t1 * sizeof(sf::InflateSeg), o_strips = o_clips + t1 * sizeof(sf::InflateClip);
+  const size_t o_implied = o_strips + t1 * sizeof(sf::InflateStrip), o_wst = o_implied + t1 * 2 * sizeof(uint64_t);
+  rc = grow(ctx, &ctx->d_bgzfrows, &ctx->d_bgzfrows_cap, o_wst + t1 * sizeof(uint32_t), "BGZF decoder rows");
+  if (!rc) rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, t1 * sizeof(sf::SegInfo), "segment records");
+  if (!rc) rc = ensure_dtok(ctx, std::max(1u, std::min(T, per)) * (row / sf::kChunk));
+  if (rc) return rc;
+  uint8_t* R = ctx->d_bgzfrows;
+  sf::InflateSeg* segs = (sf::InflateSeg*)R;
+  sf::InflateClip* clips = (sf::InflateClip*)(R + o_clips);
+  sf::InflateStrip* strips = (sf::InflateStrip*)(R + o_strips);
+  uint64_t* implied = (uint64_t*)(R + o_implied);
+  uint32_t* wst = (uint32_t*)(R + o_wst);
+  ctx->last_chunks = T;
+  ctx->last_dtok_bytes = (size_t)std::min(T, per) * row * sizeof(uint32_t);
+  SF_HIP(sf::launch_bgzf_range_rows(t_ranges, n, d_member_off, d_out_off, plan, row0, T, per, row, segs, clips, strips, implied, wst, spans, s),
+         "launch k_bgzf_range_rows");
+  const uint64_t nbatches = sf::bgzf::range_batches(T, per);
+  for (uint64_t b = 0; b < nbatches; ++b) {
+    const size_t b0 = (size_t)(b * per);
+    const uint32_t nb = sf::bgzf::range_batch_rows(T, per, b);
+    sf::SegInfo* binfo = ctx->ws.seginfo + b0;
+    if (wide) {
+      SF_HIP(sf::launch_inflate_tokens_wide(segs + b0, nb, ctx->ws.tokens, binfo, !ctx->inflate_serial, s), "launch k_inflate_tokens");
+      SF_HIP(sf::launch_inflate_bytes_wide(segs + b0, clips + b0, strips + b0, nb, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes_clip");
+    } else {
+      SF_HIP(sf::launch_inflate_tokens(segs + b0, nb, ctx->ws.tokens, binfo, false, !ctx->inflate_serial, s), "launch k_inflate_tokens");
+      SF_HIP(sf::launch_inflate_bytes_clip(segs + b0, clips + b0, strips + b0, nb, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes_clip");
+    }
+  }
+  SF_HIP(sf::launch_bgzf_fold_spans(spans, n, plan, ctx->ws.seginfo, wst, d_status, s), "launch k_bgzf_fold_spans");
+  if ((rc = mark_call_end(ctx, s))) return rc;
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  return SFH_OK;
+}
+
+// info->status != 0: every range's status, nothing decoded
+int bgzf_ranges_all(sfh_ctx* ctx, uint32_t* d_status, size_t count, uint32_t st, hipStream_t s) {
+  if (int rc = order_behind_last_call(ctx, s)) return rc;
+  SF_HIP(hipMemsetD32Async((hipDeviceptr_t)d_status, (int)st, count, s), "statuses");
+  if (int rc = mark_call_end(ctx, s)) return rc;
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  snprintf(ctx->err, sizeof ctx->err, "BGZF members: DecompressStatus %u", st);
+  return SFH_OK;
+}
+}  // namespace
+
+int sfh_decompress_bgzf_ranges_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const uint64_t* d_member_off,
+                                      const uint64_t* d_out_off, const sfh_bgzf_info* info, size_t count, const uint64_t* offsets,
+                                      const uint64_t* lengths, void* const* d_dsts, uint32_t* d_status, void* stream) {
+  if (!ctx) return fail(ctx, SFH_E_INVALID_ARG, "argument (context)", hipSuccess);
+  if (count == 0) return SFH_OK;
+  int rc = check_bgzf_ranges(ctx, d_src, d_member_off, d_out_off, info, count, offsets, lengths, d_dsts, d_status, true);
+  if (rc) return rc;
+  hipStream_t s;
+  if ((rc = begin_call(ctx, stream, &s))) return rc;
+  if (info->status) return bgzf_ranges_all(ctx, d_status, count, info->status, s);
+  std::vector<sf::BgzfRange> ranges;
+  try {
+    ranges.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  for (size_t r = 0; r < count; ++r)
+    ranges[r] = sf::BgzfRange{offsets[r], lengths[r], (uint8_t*)d_dsts[r], (const uint8_t*)d_src, 0, src_n};
+  return enqueue_bgzf_ranges(ctx, ranges.data(), count, d_member_off, d_out_off, info, d_status, s);
+}
+
+int sfh_decompress_bgzf_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uint64_t* member_off, const uint64_t* out_off,
+                               const sfh_bgzf_info* info, size_t count, const uint64_t* offsets, const uint64_t* lengths,
+                               void* const* dsts, uint32_t* status) {
+  if (!ctx) return fail(ctx, SFH_E_INVALID_ARG, "argument (context)", hipSuccess);
+  if (count == 0) return SFH_OK;
+  const bool given = member_off || out_off || info;
+  if (given && !(member_off && out_off && info)) return fail(ctx, SFH_E_INVALID_ARG, "member_off, out_off, info: all three or none", hipSuccess);
+  if (!src || !status) return fail(ctx, SFH_E_INVALID_ARG, "null array", hipSuccess);
+  // without an index: the members on the host first
+  std::vector<uint64_t> w_moff, w_ooff;
+  sfh_bgzf_info w_info{};
+  if (!given) {
+    sf::bgzf::Info I;
+    (void)sf::bgzf::read_index((const uint8_t*)src, src_n, I, nullptr, nullptr, 0);  // the counts, or the status
+    if (I.status) {  // a file that does not parse: every range's status, whatever the ranges are
+      for (size_t r = 0; r < count; ++r) status[r] = I.status;
+      snprintf(ctx->err, sizeof ctx->err, "BGZF members: DecompressStatus %u", I.status);
+      return SFH_OK;
+    }
+    try {
+      w_moff.resize((size_t)I.members + 1);
+      w_ooff.resize((size_t)I.members + 1);
+    } catch (...) {
+      return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+    }
+    (void)sf::bgzf::read_index((const uint8_t*)src, src_n, I, w_moff.data(), w_ooff.data(), w_moff.size());
+    w_info = sfh_bgzf_info{I.total_n, I.members, I.max_isize, I.has_eof, I.status};
+    member_off = w_moff.data();
+    out_off = w_ooff.data();
+    info = &w_info;
+  }
+  int rc = check_bgzf_ranges(ctx, src, member_off, out_off, info, count, offsets, lengths, dsts, status, false);
+  if (rc) return rc;
+  if (info->status) {  // (nothing goes up)
+    for (size_t r = 0; r < count; ++r) status[r] = info->status;
+    snprintf(ctx->err, sizeof ctx->err, "BGZF members: DecompressStatus %u", info->status);
+    return SFH_OK;
+  }
+  // The items are the decode spans, planned here as the device plans them: each one's members' bytes (sf::bgzf::range_piece).
+  const uint32_t m = info->members;
+  std::vector<sf::bgzf::RangePiece> pc;
+  std::vector<const void*> piece;
+  std::vector<uint64_t> len;
+  std::vector<sf::BgzfRange> ranges;
+  try {
+    pc.resize(count);
+    piece.resize(count);
+    len.resize(count);
+    ranges.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  uint64_t rows = 0;
+  for (size_t r = 0; r < count; ++r) {
+    const sf::bgzf::Span S = sf::bgzf::span_of(out_off, m, offsets[r], lengths[r]);
+    rows += S.rows;
+    if (rows > sf::bgzf::kMaxRangeRows) return fail(ctx, SFH_E_INVALID_ARG, "decode spans of more than 2^31 - 1 members in one call", hipSuccess);
+    pc[r] = sf::bgzf::range_piece(member_off, S, src_n);
+    piece[r] = (const uint8_t*)src + pc[r].lo;
+    len[r] = pc[r].n;
+  }
+  Staged B;
+  hipStream_t s = ctx->stream;
+  if ((rc = staged_up(ctx, B, count, piece.data(), len.data(), lengths))) return rc;
+  const size_t ix_bytes = ((size_t)m + 1) * sizeof(uint64_t);
+  rc = grow(ctx, &ctx->d_bgzfix, &ctx->d_bgzfix_cap, 2 * ix_bytes, "BGZF index");
+  if (!rc) rc = ensure_bstatus(ctx, count);
+  if (rc) return rc;
+  uint64_t *d_moff = ctx->d_bgzfix, *d_ooff = ctx->d_bgzfix + (size_t)m + 1;
+  SF_HIP(hipMemcpyAsync(d_moff, member_off, ix_bytes, hipMemcpyHostToDevice, s), "H2D index");
+  SF_HIP(hipMemcpyAsync(d_ooff, out_off, ix_bytes, hipMemcpyHostToDevice, s), "H2D index");
+  for (size_t r = 0; r < count; ++r) {
+    // (the base points pc[r].lo bytes in front of the piece: base + a member offset of the span is the uploaded byte)
+    const uint8_t* base = (const uint8_t*)((uintptr_t)B.d_srcs[r] - (uintptr_t)pc[r].lo);
+    ranges[r] = sf::BgzfRange{offsets[r], lengths[r], (uint8_t*)B.d_dsts[r], base, pc[r].lo, pc[r].lo + pc[r].n};
+  }
+  if ((rc = enqueue_bgzf_ranges(ctx, ranges.data(), count, d_moff, d_ooff, info, ctx->d_bstatus, s)) != SFH_OK) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  if ((rc = read_bstatus(ctx, count, status, s))) return rc;
+  return staged_down(ctx, B, count, dsts, lengths, status);
+}
+
+int sfh_bgzf_voffsets_to_offsets(const uint64_t* member_off, const uint64_t* out_off, uint32_t members, size_t count,
+                                 const uint64_t* voffsets, uint64_t* offsets) {
+  if (!member_off || !out_off || (count && (!voffsets || !offsets))) return SFH_E_INVALID_ARG;
+  for (size_t k = 0; k < count; ++k) offsets[k] = sf::bgzf::voffset_to_offset(member_off, out_off, members, voffsets[k]);
+  return SFH_OK;
+}
+
+int sfh_bgzf_offsets_to_voffsets(const uint64_t* member_off, const uint64_t* out_off, uint32_t members, size_t count,
+                                 const uint64_t* offsets, uint64_t* voffsets) {
+  if (!member_off || !out_off || (count && (!offsets || !voffsets))) return SFH_E_INVALID_ARG;
+  for (size_t k = 0; k < count; ++k) voffsets[k] = sf::bgzf::offset_to_voffset(member_off, out_off, members, offsets[k]);
   return SFH_OK;
 }
 

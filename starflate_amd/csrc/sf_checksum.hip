@@ -398,37 +398,9 @@ __global__ __launch_bounds__(KW_THREADS) void k_wrap_batch(const uint32_t* __res
 
 // ---- sfh_decompress_batch*: the wrappers of the items, and every item's status ----
 // the reference's DecompressStatus values these kernels produce themselves (src/decompress.hpp:13-23)
-constexpr uint32_t kStOk = 0, kStError = 1, kStDstTooSmall = 4, kStSrcTooSmall = 5;
+constexpr uint32_t kStOk = 0, kStError = 1, kStSrcTooSmall = 5;
 
-// the gzip wrapper of the n bytes at p (any alignment) whose body decodes into dst_n bytes: container.hpp's checks in its
-// order.  st, hdr, end (= n), want and isize come in cleared
-__device__ __forceinline__ void gzip_head(const uint8_t* __restrict__ p, uint64_t n, uint64_t dst_n, uint32_t& st, uint64_t& hdr,
-                                          uint64_t& end, uint32_t& want, uint32_t& isize) {
-  if (n < 18) {
-    st = kStSrcTooSmall;
-  } else if (p[0] != 0x1F || p[1] != 0x8B || p[2] != 8 || (p[3] & 0xE0u) != 0) {
-    st = kStError;
-  } else {
-    const uint32_t flg = p[3];
-    end = n - 8;
-    uint64_t at = 10;
-    if (flg & 0x04u) {  // FEXTRA
-      if (at + 2 > end) st = kStSrcTooSmall;
-      else at += 2 + (p[at] | (uint32_t)p[at + 1] << 8);
-    }
-    for (uint32_t bit = 0x08u; st == kStOk && bit <= 0x10u; bit <<= 1) {  // FNAME, FCOMMENT: zero-terminated
-      if (!(flg & bit)) continue;
-      while (at < end && p[at] != 0) ++at;
-      ++at;
-    }
-    if (flg & 0x02u) at += 2;  // FHCRC
-    if (st == kStOk && at > end) st = kStSrcTooSmall;
-    hdr = at;
-    want = p[n - 8] | (uint32_t)p[n - 7] << 8 | (uint32_t)p[n - 6] << 16 | (uint32_t)p[n - 5] << 24;
-    isize = p[n - 4] | (uint32_t)p[n - 3] << 8 | (uint32_t)p[n - 2] << 16 | (uint32_t)p[n - 1] << 24;
-    if (st == kStOk && isize > dst_n) st = kStDstTooSmall;
-  }
-}
+// (gzip_head, the gzip wrapper's checks: sf_device.h -- k_bgzf_range_rows of sf_bgzf.hip runs them as well)
 
 // One lane per item, before the token kernels: the wrapper checks of include/starflate/container.hpp in its order (the
 // header, the stream long enough for it, gzip's ISIZE against the output), the trailer's checksum, and with an index its

@@ -255,6 +255,40 @@ struct InflateSpan {     // per range of the call (k_inflate_fold_spans)
   uint32_t row0, nrows;  // its rows in the call's segment records
 };
 static_assert(sizeof(InflateClip) == 16 && sizeof(InflateSpan) == 8, "range descriptor rows");
+// The reference's DecompressStatus values the wrapper checks produce (src/decompress.hpp:13-23).
+namespace gz {
+constexpr uint32_t kStOk = 0, kStError = 1, kStDstTooSmall = 4, kStSrcTooSmall = 5;
+}
+// the gzip wrapper of the n bytes at p (any alignment) whose body decodes into dst_n bytes: container.hpp's checks in its
+// order.  st, hdr, end (= n), want and isize come in cleared
+__device__ __forceinline__ void gzip_head(const uint8_t* __restrict__ p, uint64_t n, uint64_t dst_n, uint32_t& st, uint64_t& hdr,
+                                          uint64_t& end, uint32_t& want, uint32_t& isize) {
+  if (n < 18) {
+    st = gz::kStSrcTooSmall;
+  } else if (p[0] != 0x1F || p[1] != 0x8B || p[2] != 8 || (p[3] & 0xE0u) != 0) {
+    st = gz::kStError;
+  } else {
+    const uint32_t flg = p[3];
+    end = n - 8;
+    uint64_t at = 10;
+    if (flg & 0x04u) {  // FEXTRA
+      if (at + 2 > end) st = gz::kStSrcTooSmall;
+      else at += 2 + (p[at] | (uint32_t)p[at + 1] << 8);
+    }
+    for (uint32_t bit = 0x08u; st == gz::kStOk && bit <= 0x10u; bit <<= 1) {  // FNAME, FCOMMENT: zero-terminated
+      if (!(flg & bit)) continue;
+      while (at < end && p[at] != 0) ++at;
+      ++at;
+    }
+    if (flg & 0x02u) at += 2;  // FHCRC
+    if (st == gz::kStOk && at > end) st = gz::kStSrcTooSmall;
+    hdr = at;
+    want = p[n - 8] | (uint32_t)p[n - 7] << 8 | (uint32_t)p[n - 6] << 16 | (uint32_t)p[n - 5] << 24;
+    isize = p[n - 4] | (uint32_t)p[n - 3] << 8 | (uint32_t)p[n - 2] << 16 | (uint32_t)p[n - 1] << 24;
+    if (st == gz::kStOk && isize > dst_n) st = gz::kStDstTooSmall;
+  }
+}
+
 struct BatchTables {  // the device tables of one launch batch (null: the single call's implicit geometry)
   const BatchStrip* strips;
   uint32_t nstrips;
@@ -325,6 +359,28 @@ hipError_t launch_bgzf_rows_wide(const uint8_t* src, const uint64_t* member_off,
                                  uint32_t per_batch, uint8_t* dst, InflateSeg* segs, InflateItem* items, InflateClip* clips,
                                  InflateStrip* strips, BatchChunk* sums, uint64_t* implied, hipStream_t s);
 hipError_t launch_bgzf_first(const uint32_t* status, uint32_t m, uint32_t* res, hipStream_t s);
+// BGZF random access (sfh_decompress_bgzf_ranges*; sf_bgzf_range_plan.h).  One row per range of the call, built by the host:
+struct BgzfRange {
+  uint64_t offset, length;  // of the file's output
+  uint8_t* dst;             // any alignment
+  const uint8_t* src;       // the FILE's byte 0 as this range's rows see it (the host-buffer call: a base in front of the
+  uint64_t src_lo, src_n;   // span's uploaded piece), and the bytes [src_lo, src_n) of the file that are readable from it
+};
+static_assert(sizeof(BgzfRange) == 48, "range rows (the host packs them into one upload)");
+// plan[0 .. n): every range's first member, plan[n .. 2n): its rows (0 and first = 0xFFFFFFFF: a range the index does not
+// hold); *total (64-bit, zeroed by the launch) = the rows of the call
+hipError_t launch_bgzf_range_spans(const BgzfRange* ranges, uint32_t n, const uint64_t* out_off, uint32_t members, uint32_t* plan,
+                                   unsigned long long* total, hipStream_t s);
+// row0: the exclusive scan of the rows.  Per row its InflateSeg, write window, strip of one (numbered within its launch batch
+// of per_batch rows), implied entries and wrapper status; per range its InflateSpan.  row_bytes: kChunk or kWideRow
+hipError_t launch_bgzf_range_rows(const BgzfRange* ranges, uint32_t n, const uint64_t* member_off, const uint64_t* out_off,
+                                  const uint32_t* plan, const uint32_t* row0, uint32_t nrows, uint32_t per_batch, uint32_t row_bytes,
+                                  InflateSeg* segs, InflateClip* clips, InflateStrip* strips, uint64_t* implied, uint32_t* wst,
+                                  InflateSpan* spans, hipStream_t s);
+// every range's status: the first failing row of its span, a row's wrapper status before its body's; 1 for a range the
+// planner marked failed
+hipError_t launch_bgzf_fold_spans(const InflateSpan* spans, uint32_t n, const uint32_t* plan, const SegInfo* info, const uint32_t* wst,
+                                  uint32_t* status, hipStream_t s);
 hipError_t launch_checksum_batch_any(const BatchChunk* chunks, uint32_t nchunks, uint32_t* sums, hipStream_t s);  // CRC-32, any alignment
 // batched: sums[c] for the call's chunk table; one k_wrap workgroup per item (header at dst, trailer at d_total[out])
 hipError_t launch_checksum_batch(const BatchChunk* chunks, uint32_t nchunks, uint32_t kind, uint32_t* sums, hipStream_t s);
