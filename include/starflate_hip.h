@@ -624,7 +624,9 @@ int sfh_bgzf_offsets_to_voffsets(const uint64_t* member_off, const uint64_t* out
  * dst_n = SFH_SIZE_FROM_TRAILER with a gzip stream: the output size is ISIZE (members of 4 GiB and more need an explicit size).
  * The token scratch is 4 bytes per output byte of the whole call.  Synchronises `stream`.
  * sfh_decompress_any: host buffers (H2D, the same, D2H of dst when *status is 0); dst holds dst_cap bytes (dst_n above it, or an
- * ISIZE above it, is SFH_E_DST_TOO_SMALL); *dst_n_out (may be NULL) = the output size decoded to. */
+ * ISIZE above it, is SFH_E_DST_TOO_SMALL); *dst_n_out (may be NULL) = the output size decoded to.
+ * Each of these calls runs as the batch call below with one item, and synchronises `stream` as that call does.  A stream of
+ * more than 2^31 - 1 scan waves (8 KiB each: above 2^44 bytes) is SFH_E_INVALID_ARG. */
 #define SFH_SIZE_FROM_TRAILER UINT64_MAX
 int sfh_recover_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint32_t container, uint64_t dst_n, uint64_t* d_index,
                              size_t nseg, uint8_t* d_depends, void* stream);

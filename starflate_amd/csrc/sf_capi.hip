@@ -104,16 +104,14 @@ struct sfh_ctx {
   uint32_t* d_bstatus = nullptr; // sfh_decompress_batch: the statuses on the device and in pinned memory
   uint32_t* h_bstatus = nullptr;
   size_t bstatus_cap = 0;
-  // decoding without side information (sfh_recover_index_device, sfh_decompress_any*): a small fixed block (the wrapper row,
-  // the body, totals, status), the per-wave counts of the candidate scan, the node arrays of the walk, the recovered index and
-  // the per-segment arrays behind the token stage
-  uint8_t* d_anysm = nullptr;
+  // decoding without side information (sfh_recover_index*, sfh_decompress_any* and their _batch calls): the per-wave counts of
+  // the candidate scan, the node arrays of the walk, the recovered index and the per-segment arrays behind the token stage
   uint8_t* d_anycnt = nullptr;
   uint8_t* d_any = nullptr;
   uint8_t* d_anyseg = nullptr;
   uint64_t* d_anyix = nullptr;
   size_t d_anycnt_cap = 0, d_any_cap = 0, d_anyseg_cap = 0, d_anyix_cap = 0;
-  uint8_t* d_anyb = nullptr;     // the batched calls: every item's body, node ranges and indexable flag; the totals
+  uint8_t* d_anyb = nullptr;     // every item's body, node ranges and indexable flag; the totals
   size_t d_anyb_cap = 0;
   hipEvent_t ev_any[5] = {};
   float any_ms[2] = {0, 0};
@@ -247,6 +245,11 @@ int ensure_dtok(sfh_ctx* ctx, uint32_t nseg) {
 }
 
 uint32_t chunks_of(size_t n) { return n ? (uint32_t)((n + sf::kChunk - 1) / sf::kChunk) : 1u; }
+// the bytes of a stream in front of its trailer (zlib: Adler-32, gzip: CRC-32 and ISIZE): where its DEFLATE body ends at the latest
+inline uint64_t body_bytes(uint32_t container, uint64_t src_n) {
+  const uint64_t trailer = container == SFH_ZLIB ? 4 : container == SFH_GZIP ? 8 : 0;
+  return src_n > trailer ? src_n - trailer : 0;
+}
 
 // block_bytes = 0: SFH_DEFAULT_BLOCK_BYTES -- larger (SFH_LARGE_BLOCK_BYTES, SFH_CHAIN_BLOCK_BYTES with a chain effort)
 // while the input still fills the device four times over with such strips (a strip starts with an empty window: fewer
@@ -751,7 +754,6 @@ int enqueue_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs,
                           uint32_t container, uint32_t* d_status, uint32_t* d_first, hipStream_t s) {
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
   (void)hipGetLastError();  // see enqueue()
-  const uint64_t trailer = container == SFH_ZLIB ? 4 : container == SFH_GZIP ? 8 : 0;
   int rc = SFH_OK;
   if (!d_index && (rc = grow(ctx, &ctx->d_implied, &ctx->d_implied_cap, 2 * count * sizeof(uint64_t), "implied index")))
     return rc;
@@ -791,7 +793,7 @@ int enqueue_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs,
           const uint64_t* ix = d_index ? d_index + (g + i) : ctx->d_implied + 2 * i;
           uint8_t* out = (uint8_t*)d_dsts[i] + (uint64_t)k * sf::kChunk;
           const uint32_t on = sf::iplan::seg_out_n(dst_n[i], k);
-          const uint64_t body_n = container ? (src_n[i] > trailer ? src_n[i] - trailer : 0) : src_n[i];
+          const uint64_t body_n = body_bytes(container, src_n[i]);
           // (the segments are the call's in item order: the flattened sub-index holds segment g at g * SFH_SUBINDEX_WORDS)
           h_segs[g] = sf::InflateSeg{(const uint8_t*)d_srcs[i], ix, d_subindex ? d_subindex + (size_t)g * SFH_SUBINDEX_WORDS : nullptr,
                                      out, body_n, on,
@@ -1059,173 +1061,8 @@ uint64_t trailer_isize(const void* src, uint64_t src_n) {
   return src_n >= 18 ? (uint64_t)(p[src_n - 4] | (uint32_t)p[src_n - 3] << 8 | (uint32_t)p[src_n - 2] << 16 | (uint32_t)p[src_n - 1] << 24) : 0;
 }
 
-// ---- decoding without side information (sfh_recover_index_device, sfh_decompress_any*) ----
-// d_anysm: the wrapper row | the body [b0, e) | totals (nodes, M nodes, starts on the chain, rows) | the decoder's status
-constexpr size_t kAnyHead = 64, kAnyTot = 80, kAnyStatus = 112, kAnySmall = 128;
-inline uint64_t* any_head(sfh_ctx* c) { return (uint64_t*)(c->d_anysm + kAnyHead); }
-inline uint32_t* any_tot(sfh_ctx* c) { return (uint32_t*)(c->d_anysm + kAnyTot); }
-
-// The wrapper, read by k_inflate_head as the batch decoder reads it: *wst its status, *isize gzip's ISIZE; the body [b0, e) lands
-// in any_head.  dst_n: the size the caller asks for (SFH_SIZE_FROM_TRAILER: ISIZE is taken).  Synchronises s.
-int any_wrapper(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t container, uint64_t dst_n, hipStream_t s, uint32_t* wst,
-                uint32_t* isize) {
-  if (!ctx->d_anysm) SF_HIP(hipMalloc(&ctx->d_anysm, kAnySmall), "hipMalloc");
-  for (hipEvent_t& e : ctx->ev_any)
-    if (!e) SF_HIP(hipEventCreate(&e), "event");
-  if (int rc = order_behind_last_call(ctx, s)) return rc;
-  sf::InflateItem it{src, src_n, dst_n, any_head(ctx), nullptr, 0, 0, 0, 0, 0, 0};
-  SF_HIP(hipMemcpyAsync(ctx->d_anysm, &it, sizeof it, hipMemcpyHostToDevice, s), "H2D wrapper row");
-  SF_HIP(sf::launch_inflate_head((sf::InflateItem*)ctx->d_anysm, 1, container, nullptr, nullptr, s), "launch k_inflate_head");
-  SF_HIP(hipMemcpyAsync(&it, ctx->d_anysm, sizeof it, hipMemcpyDeviceToHost, s), "D2H wrapper row");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  *wst = it.wst;
-  *isize = it.isize;
-  return mark_call_end(ctx, s);
-}
-
-// The walk (after any_wrapper): d_index[0..nseg] of the body in any_head; *ok: the chain holds nseg segments.  Synchronises s.
-int any_walk(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t nseg, uint64_t* d_index, hipStream_t s, bool* ok) {
-  const bool prof = ctx->profiling != 0;
-  uint32_t* tot = any_tot(ctx);
-  ctx->any_ms[0] = ctx->any_ms[1] = 0;
-  ctx->any_counts[0] = ctx->any_counts[1] = 0;
-  if (nseg == 1) {
-    SF_HIP(sf::launch_any_single(any_head(ctx), d_index, tot + 4, s), "launch k_any_single");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");
-    *ok = true;
-    return SFH_OK;
-  }
-  const uint32_t nw = sf::any_scan_waves(src_n);
-  const size_t tw = sf::any_scan_tmp_words(nw);
-  int rc = grow(ctx, &ctx->d_anycnt, &ctx->d_anycnt_cap, (2 * (size_t)nw + tw) * sizeof(uint32_t), "candidate counts");
-  if (rc) return rc;
-  uint32_t* cn = (uint32_t*)ctx->d_anycnt;
-  uint32_t* cm = cn + nw;
-  uint32_t* tmp = cm + nw;
-  if (prof) SF_HIP(hipEventRecord(ctx->ev_any[0], s), "event");
-  SF_HIP(sf::launch_any_count(src, src_n, any_head(ctx), cn, cm, s), "launch k_any_scan");
-  SF_HIP(sf::launch_scan_u32(cn, cn, nw, tmp, tot + 0, s), "launch scan");
-  SF_HIP(sf::launch_scan_u32(cm, cm, nw, tmp, tot + 1, s), "launch scan");
-  if (prof) SF_HIP(hipEventRecord(ctx->ev_any[1], s), "event");
-  uint32_t h[2] = {0, 0};
-  SF_HIP(hipMemcpyAsync(h, tot, sizeof h, hipMemcpyDeviceToHost, s), "D2H node count");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  const uint32_t n = h[0], nm = h[1];
-  ctx->any_counts[0] = n;
-  if (n == 0) {  // an empty body (or a wrapper that did not parse): nothing to walk
-    *ok = false;
-    return SFH_OK;
-  }
-  // pos u64[n] | nxt_a, nxt_b u32[n+1] | minc, lbl, rank u32[n] | midx u32[nm+1] | tmp | flg, lab, mark u8[n]
-  const size_t ntw = sf::any_scan_tmp_words(n);
-  const size_t o_nxa = al16(8 * (size_t)n), o_nxb = o_nxa + al16(4 * ((size_t)n + 1)), o_minc = o_nxb + al16(4 * ((size_t)n + 1));
-  const size_t o_lbl = o_minc + al16(4 * (size_t)n), o_rank = o_lbl + al16(4 * (size_t)n), o_midx = o_rank + al16(4 * (size_t)n);
-  const size_t o_tmp = o_midx + al16(4 * ((size_t)nm + 1)), o_flg = o_tmp + al16(4 * ntw), o_lab = o_flg + al16(n), o_mark = o_lab + al16(n);
-  if ((rc = grow(ctx, &ctx->d_any, &ctx->d_any_cap, o_mark + al16(n), "walk nodes"))) return rc;
-  uint8_t* b = ctx->d_any;
-  uint64_t* pos = (uint64_t*)b;
-  if (prof) SF_HIP(hipEventRecord(ctx->ev_any[2], s), "event");
-  SF_HIP(sf::launch_any_nodes(src, src_n, any_head(ctx), cn, cm, pos, b + o_flg, (uint32_t*)(b + o_minc), (uint32_t*)(b + o_midx), s),
-         "launch k_any_scan");
-  if (prof) SF_HIP(hipEventRecord(ctx->ev_any[3], s), "event");
-  SF_HIP(sf::launch_any_walk(src, any_head(ctx), pos, b + o_flg, (uint32_t*)(b + o_minc), (uint32_t*)(b + o_midx), n, nm,
-                             (uint32_t*)(b + o_nxa), (uint32_t*)(b + o_nxb), b + o_lab, b + o_mark, (uint32_t*)(b + o_lbl),
-                             (uint32_t*)(b + o_rank), (uint32_t*)(b + o_tmp), tot + 2, d_index, nseg, tot + 4, s),
-         "launch k_any_walk");
-  if (prof) SF_HIP(hipEventRecord(ctx->ev_any[4], s), "event");
-  uint32_t starts = 0;
-  SF_HIP(hipMemcpyAsync(&starts, tot + 4, sizeof starts, hipMemcpyDeviceToHost, s), "D2H walk");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  if (prof) {
-    float a = 0, c = 0, w = 0;
-    SF_HIP(hipEventElapsedTime(&a, ctx->ev_any[0], ctx->ev_any[1]), "elapsed");
-    SF_HIP(hipEventElapsedTime(&c, ctx->ev_any[2], ctx->ev_any[3]), "elapsed");
-    SF_HIP(hipEventElapsedTime(&w, ctx->ev_any[3], ctx->ev_any[4]), "elapsed");
-    ctx->any_ms[0] = a + c;
-    ctx->any_ms[1] = w;
-  }
-  *ok = starts >= nseg;
-  return SFH_OK;
-}
-
-// The decoder on a recovered index (d_index[0..nseg], out_n bytes): one launch batch of the batch decoder's kernels over a
-// one-item table -- the token stage with the exact end rule and the reference's distance rule (a segment may reach back
-// 32 KiB, the first one nothing), then the rows of dependent segments, built on the device, for the byte stage (a grid of nseg
-// rows, the unused ones empty), the checksum and the fold into *d_status.  d_status null: the token stage and the rows only
-// (sfh_recover_index_device's depends).  Enqueues on s.
-int enqueue_any_decode(sfh_ctx* ctx, const uint8_t* src, size_t src_n, uint32_t container, uint8_t* d_dst, uint64_t out_n,
-                       uint32_t nseg, const uint64_t* d_index, uint8_t** depends_out, uint32_t* d_status, hipStream_t s) {
-  const uint64_t trailer = container == SFH_ZLIB ? 4 : container == SFH_GZIP ? 8 : 0;
-  const uint64_t body_n = container ? (src_n > trailer ? src_n - trailer : 0) : src_n;
-  const bool bytes = d_status != nullptr;
-  std::vector<sf::InflateSeg> segs;
-  std::vector<sf::BatchChunk> sums;  // (k_inflate_head cuts them down to a gzip's ISIZE, with or without the byte stage)
-  try {
-    segs.resize(nseg);
-    if (container) sums.resize(nseg);
-  } catch (...) {
-    return fail(ctx, SFH_E_NOMEM, "host memory for the descriptor tables", hipSuccess);
-  }
-  for (uint32_t k = 0; k < nseg; ++k) {
-    const uint64_t ob = (uint64_t)k * sf::kChunk;
-    const uint32_t on = (uint32_t)std::min<uint64_t>(sf::kChunk, out_n - std::min(out_n, ob));
-    const uint32_t hist = (k ? sf::kChunk : 0u) | (container ? sf::kSegWrapped : 0u) | (k + 1 < nseg ? sf::kSegExact : 0u);
-    segs[k] = sf::InflateSeg{src, d_index + k, nullptr, d_dst ? d_dst + ob : nullptr, body_n, on, hist};
-    if (!sums.empty()) sums[k] = sf::BatchChunk{d_dst ? d_dst + ob : nullptr, on, 0u};
-  }
-  const sf::InflateItem item{src, src_n, out_n, nullptr, d_index, 0, nseg, 0, 0, 0, 0};
-  int rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, (size_t)nseg * sizeof(sf::SegInfo), "segment records");
-  if (!rc) rc = ensure_dtok(ctx, nseg);
-  if (!rc && !sums.empty()) rc = ensure_sums(ctx, nseg);
-  // depends u8[nseg] | starts, excl u32[nseg] | tmp | rows InflateStrip[nseg]
-  const size_t tw = sf::any_scan_tmp_words(nseg);
-  const size_t o_st = al16(nseg), o_ex = o_st + al16(4 * (size_t)nseg), o_tmp = o_ex + al16(4 * (size_t)nseg);
-  const size_t o_rows = o_tmp + al16(4 * tw);
-  if (!rc) rc = grow(ctx, &ctx->d_anyseg, &ctx->d_anyseg_cap, o_rows + sizeof(sf::InflateStrip) * (size_t)nseg, "segment rows");
-  if (rc) return rc;
-  const size_t b_segs = segs.size() * sizeof(sf::InflateSeg), o_sums = al16(b_segs + sizeof item);
-  const size_t tab = o_sums + sums.size() * sizeof(sf::BatchChunk);
-  if ((rc = stage_tables(ctx, tab)) != SFH_OK) return rc;
-  memcpy(ctx->h_tab, segs.data(), b_segs);
-  memcpy(ctx->h_tab + b_segs, &item, sizeof item);
-  if (!sums.empty()) memcpy(ctx->h_tab + o_sums, sums.data(), sums.size() * sizeof(sf::BatchChunk));
-  sf::InflateSeg* t_segs = (sf::InflateSeg*)ctx->d_tab;
-  sf::InflateItem* t_item = (sf::InflateItem*)(ctx->d_tab + b_segs);
-  sf::BatchChunk* t_sums = (sf::BatchChunk*)(ctx->d_tab + o_sums);
-  uint8_t* sb = ctx->d_anyseg;
-  sf::InflateStrip* rows = (sf::InflateStrip*)(sb + o_rows);
-
-  ctx->index_valid = false;
-  ctx->bix_valid = false;
-  ctx->last_chunks = nseg;
-  ctx->last_dtok_bytes = (size_t)nseg * sf::kChunk * sizeof(uint32_t);
-  const bool prof = ctx->profiling != 0;
-  if ((rc = upload_tables(ctx, tab, s)) != SFH_OK) return rc;
-  ctx->ev_inf_valid = false;
-  if (prof && (rc = ensure_inflate_events(ctx, 1)) != SFH_OK) return rc;
-  hipEvent_t* ev = prof ? ctx->ev_inf.data() : nullptr;
-  SF_HIP(sf::launch_inflate_head(t_item, 1, container, t_segs, sums.empty() ? nullptr : t_sums, s), "launch k_inflate_head");
-  if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
-  SF_HIP(sf::launch_inflate_tokens_exact(t_segs, nseg, ctx->ws.tokens, ctx->ws.seginfo, !ctx->inflate_serial, s),
-         "launch k_inflate_tokens");
-  SF_HIP(sf::launch_any_rows(ctx->ws.seginfo, ctx->ws.tokens, nseg, sb, (uint32_t*)(sb + o_st), (uint32_t*)(sb + o_ex),
-                             (uint32_t*)(sb + o_tmp), any_tot(ctx) + 3, rows, s), "launch k_any_rows");
-  if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
-  if (depends_out) *depends_out = sb;
-  if (bytes) {
-    SF_HIP(sf::launch_inflate_bytes(t_segs, rows, nseg, ctx->ws.tokens, ctx->ws.seginfo, s), "launch k_inflate_bytes");
-    if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
-    if (container) SF_HIP(sf::launch_checksum_batch(t_sums, nseg, container, ctx->ws.sums, s), "launch k_checksum");
-    SF_HIP(sf::launch_inflate_fold(t_item, 1, ctx->ws.seginfo, ctx->ws.sums, container, d_status, nullptr, s), "launch k_inflate_fold");
-  } else if (ev) {
-    SF_HIP(hipEventRecord(ev[2], s), "event");
-  }
-  ctx->ev_inf_batches = 1;
-  ctx->ev_inf_valid = prof;
-  return mark_call_end(ctx, s);
-}
-
-// ---- many block-flushed streams in one call (sfh_recover_index_batch*, sfh_decompress_any_batch*) ----
+// ---- decoding without side information (sfh_recover_index*, sfh_decompress_any*, and their _batch calls) ----
+// One driver: a single stream is a call of one item.
 constexpr uint32_t kStDstTooSmall = 4;  // the reference's DecompressStatus::DstTooSmall
 
 // Everything a call checks before it enqueues anything (`dev`: device buffers, the single call's alignment rules).  dsts /
@@ -1274,7 +1111,7 @@ struct AnyBatch {
 // The recovery of a whole call: the wrappers (k_inflate_head over every item), one scan over every item that has more than one
 // segment, one walk over the concatenated node lists.  d_index: the flat index (zeroed first: the entries of an item that is
 // not indexable stay 0).  Synchronises s: after the wrappers only where ISIZE sizes the work, after the node count, after the
-// walk.  Arguments checked (check_any_batch).
+// walk.  Arguments checked (check_any_batch; the single calls: check_any, check_any_waves).
 int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, uint32_t container,
                       const uint64_t* dst_cap, const uint64_t* dst_n, uint64_t* d_index, hipStream_t s, AnyBatch& R) {
   const bool prof = ctx->profiling != 0;
@@ -1372,7 +1209,7 @@ int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, con
   }
   SF_HIP(hipMemsetAsync(d_index, 0, R.entries * sizeof(uint64_t), s), "clear the index");
   SF_HIP(hipMemsetAsync(ok, 0, (o_tot + 32) - o_ok, s), "clear the flags");
-  SF_HIP(sf::launch_any_single_batch(t_items, (uint32_t)count, heads, d_index, ok, s), "launch k_any_single");
+  SF_HIP(sf::launch_any_single(t_items, (uint32_t)count, heads, d_index, ok, s), "launch k_any_single");
   const uint32_t nwaves = (uint32_t)nw;
   if (nwaves) {
     const size_t tw = sf::any_scan_tmp_words(nwaves);
@@ -1381,7 +1218,7 @@ int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, con
     uint32_t* cm = cn + nwaves;
     uint32_t* tmp = cm + nwaves;
     if (prof) SF_HIP(hipEventRecord(ctx->ev_any[0], s), "event");
-    SF_HIP(sf::launch_any_count_batch(t_items, t_waves, heads, nwaves, cn, cm, s), "launch k_any_scan");
+    SF_HIP(sf::launch_any_count(t_items, t_waves, heads, nwaves, cn, cm, s), "launch k_any_scan");
     SF_HIP(sf::launch_scan_u32(cn, cn, nwaves, tmp, tot + 0, s), "launch scan");
     SF_HIP(sf::launch_scan_u32(cm, cm, nwaves, tmp, tot + 1, s), "launch scan");
     SF_HIP(sf::launch_any_ranges(t_items, (uint32_t)count, cn, cm, nwaves, tot, range, tot + 5, s), "launch k_any_ranges");
@@ -1401,10 +1238,10 @@ int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, con
     if ((rc = grow(ctx, &ctx->d_any, &ctx->d_any_cap, o_mark + w1, "walk nodes"))) return rc;
     uint8_t* b = ctx->d_any;
     if (prof) SF_HIP(hipEventRecord(ctx->ev_any[2], s), "event");
-    SF_HIP(sf::launch_any_nodes_batch(t_items, t_waves, heads, nwaves, cn, cm, (uint64_t*)b, b + o_flg, (uint32_t*)(b + o_minc),
+    SF_HIP(sf::launch_any_nodes(t_items, t_waves, heads, nwaves, cn, cm, (uint64_t*)b, b + o_flg, (uint32_t*)(b + o_minc),
                                       (uint32_t*)(b + o_midx), (uint32_t*)(b + o_item), s), "launch k_any_scan");
     if (prof) SF_HIP(hipEventRecord(ctx->ev_any[3], s), "event");
-    SF_HIP(sf::launch_any_walk_batch(t_items, heads, range, (uint32_t*)(b + o_item), (uint64_t*)b, b + o_flg, (uint32_t*)(b + o_minc),
+    SF_HIP(sf::launch_any_walk(t_items, heads, range, (uint32_t*)(b + o_item), (uint64_t*)b, b + o_flg, (uint32_t*)(b + o_minc),
                                      (uint32_t*)(b + o_midx), n, largest, (uint32_t*)(b + o_nxa), (uint32_t*)(b + o_nxb), b + o_lab,
                                      b + o_mark, (uint32_t*)(b + o_lbl), (uint32_t*)(b + o_rank), (uint32_t*)(b + o_tmp), tot + 2,
                                      d_index, ok, s), "launch k_any_walk");
@@ -1436,9 +1273,12 @@ int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, con
 // launch batch after launch batch of whole items (sf_any_plan.h) -- the token stage with the exact end rule and the
 // reference's distance rule, the rows of dependent segments built on the device over the batch's segment table, the byte
 // stage -- then the checksums and the fold.  The statuses land in R.st.  Synchronises s at the end.
+// d_depends given (sfh_recover_index_device, a call of one item, which is always one launch batch): the token stage and the
+// rows only -- the segments' depends flags are copied there, nothing is written through d_dsts (which may be null), and R.st
+// stays as it is.
 int any_batch_decode(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, uint32_t container,
-                     void* const* d_dsts, const uint64_t* d_index, hipStream_t s, AnyBatch& R) {
-  const uint64_t trailer = container == SFH_ZLIB ? 4 : container == SFH_GZIP ? 8 : 0;
+                     void* const* d_dsts, const uint64_t* d_index, hipStream_t s, AnyBatch& R, uint8_t* d_depends = nullptr) {
+  const bool bytes_stage = d_depends == nullptr;
   sf::aplan::Plan P;
   try {
     sf::aplan::plan_batches(count, R.out_n.data(), R.take.data(), ctx->batch_chunks, P);
@@ -1470,7 +1310,7 @@ int any_batch_decode(sfh_ctx* ctx, size_t count, const void* const* d_srcs, cons
   uint32_t g = 0, j = 0;
   for (size_t i = 0; i < count; ++i) {
     if (!R.take[i]) continue;
-    const uint64_t out_n = R.out_n[i], body_n = container ? (src_n[i] > trailer ? src_n[i] - trailer : 0) : src_n[i];
+    const uint64_t out_n = R.out_n[i], body_n = body_bytes(container, src_n[i]);
     const uint32_t n = sf::aplan::segments_of(out_n);
     const uint64_t* ix = d_index + R.ix0[i];
     h_items[j++] = sf::InflateItem{(const uint8_t*)d_srcs[i], src_n[i], out_n, nullptr, ix, g, n, 0, 0, 0, 0};
@@ -1478,7 +1318,7 @@ int any_batch_decode(sfh_ctx* ctx, size_t count, const void* const* d_srcs, cons
       const uint64_t ob = (uint64_t)k * sf::kChunk;
       const uint32_t on = (uint32_t)std::min<uint64_t>(sf::kChunk, out_n - std::min(out_n, ob));
       const uint32_t hist = (k ? sf::kChunk : 0u) | (container ? sf::kSegWrapped : 0u) | (k + 1 < n ? sf::kSegExact : 0u);
-      uint8_t* out = (uint8_t*)d_dsts[i] + ob;
+      uint8_t* out = bytes_stage ? (uint8_t*)d_dsts[i] + ob : nullptr;
       h_segs[g] = sf::InflateSeg{(const uint8_t*)d_srcs[i], ix + k, nullptr, out, body_n, on, hist};
       if (container) h_sums[g] = sf::BatchChunk{out, on, 0u};
     }
@@ -1500,24 +1340,30 @@ int any_batch_decode(sfh_ctx* ctx, size_t count, const void* const* d_srcs, cons
     if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
     SF_HIP(sf::launch_inflate_tokens_exact(t_segs + b.row0, b.nseg, ctx->ws.tokens, binfo, !ctx->inflate_serial, s),
            "launch k_inflate_tokens");
-    SF_HIP(sf::launch_any_rows_batch(t_segs + b.row0, binfo, ctx->ws.tokens, b.nseg, sb + o_dep, (uint32_t*)(sb + o_st),
+    SF_HIP(sf::launch_any_rows(t_segs + b.row0, binfo, ctx->ws.tokens, b.nseg, sb + o_dep, (uint32_t*)(sb + o_st),
                                      (uint32_t*)(sb + o_ex), (uint32_t*)(sb + o_tmp), d_nrows + bi, strips, s), "launch k_any_rows");
     if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
-    SF_HIP(sf::launch_inflate_bytes(t_segs + b.row0, strips, b.nseg, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes");
+    if (bytes_stage) SF_HIP(sf::launch_inflate_bytes(t_segs + b.row0, strips, b.nseg, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes");
     if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
   }
   ctx->ev_inf_batches = nb;
   ctx->ev_inf_valid = prof;
-  if (container) SF_HIP(sf::launch_checksum_batch(t_sums, nseg, container, ctx->ws.sums, s), "launch k_checksum");
-  SF_HIP(sf::launch_inflate_fold(t_items, nitems, ctx->ws.seginfo, ctx->ws.sums, container, ctx->d_bstatus, nullptr, s),
-         "launch k_inflate_fold");
+  // statuses u32[nitems] (not without the byte stage) | rows per batch u32[nb]
+  const size_t first = bytes_stage ? 0 : nitems;
+  if (bytes_stage) {
+    if (container) SF_HIP(sf::launch_checksum_batch(t_sums, nseg, container, ctx->ws.sums, s), "launch k_checksum");
+    SF_HIP(sf::launch_inflate_fold(t_items, nitems, ctx->ws.seginfo, ctx->ws.sums, container, ctx->d_bstatus, nullptr, s),
+           "launch k_inflate_fold");
+  } else {
+    SF_HIP(hipMemcpyAsync(d_depends, sb + o_dep, nseg, hipMemcpyDeviceToDevice, s), "copy depends");
+  }
   SF_HIP(hipMemcpyAsync(ctx->d_bstatus + nitems, d_nrows, nb * sizeof(uint32_t), hipMemcpyDeviceToDevice, s), "copy rows");
-  SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, ((size_t)nitems + nb) * sizeof(uint32_t), hipMemcpyDeviceToHost, s),
-         "copy statuses");
+  SF_HIP(hipMemcpyAsync(ctx->h_bstatus + first, ctx->d_bstatus + first, ((size_t)nitems + nb - first) * sizeof(uint32_t),
+                        hipMemcpyDeviceToHost, s), "copy statuses");
   if ((rc = mark_call_end(ctx, s)) != SFH_OK) return rc;
   SF_HIP(hipStreamSynchronize(s), "stream sync");
   j = 0;
-  for (size_t i = 0; i < count; ++i)
+  for (size_t i = 0; i < count && bytes_stage; ++i)
     if (R.take[i]) R.st[i] = ctx->h_bstatus[j++];
   for (uint32_t bi = 0; bi < nb; ++bi) ctx->any_counts[1] += ctx->h_bstatus[nitems + bi];
   return SFH_OK;
@@ -1541,20 +1387,7 @@ int check_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, cons
   }
   if (nc > ((uint64_t)1 << 31) - 1)
     return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 nominal chunks in one call (SFH_STREAM_CHUNK)", hipSuccess);
-  if (!dsts) return SFH_OK;
-  std::vector<size_t> ord;
-  try {
-    ord.reserve(count);
-  } catch (...) {
-    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
-  }
-  for (size_t i = 0; i < count; ++i)  // (an empty range is written nothing and overlaps nothing)
-    if (dst_cap[i]) ord.push_back(i);
-  std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return (uintptr_t)dsts[a] < (uintptr_t)dsts[b]; });
-  for (size_t k = 1; k < ord.size(); ++k)
-    if ((uintptr_t)dsts[ord[k - 1]] + dst_cap[ord[k - 1]] > (uintptr_t)dsts[ord[k]])
-      return fail(ctx, SFH_E_INVALID_ARG, "destination ranges overlap", hipSuccess);
-  return SFH_OK;
+  return dsts ? check_disjoint(ctx, dsts, dst_cap, count) : SFH_OK;
 }
 
 // The one driver: a single stream is a call of one item.  Arguments checked, count > 0.  Item i is decoded when dsts && dsts[i]
@@ -1908,6 +1741,14 @@ int check_any(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, u
   return SFH_OK;
 }
 
+// The single calls are the driver's calls of one item.  What check_any_batch refuses for a whole call -- a count of scan waves
+// that does not fit the driver's 32 bits -- is refused here for the one stream.
+int check_any_waves(sfh_ctx* ctx, size_t src_n) {
+  if (((uint64_t)src_n + 8191) / 8192 > ((uint64_t)1 << 31) - 1)
+    return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 scan waves (a stream above 2^44 bytes)", hipSuccess);
+  return SFH_OK;
+}
+
 }  // namespace
 
 // ---- one process per GPU: concatenation over RCCL (bound at run time: a host without RCCL still loads the library) ----
@@ -2087,7 +1928,6 @@ void sfh_destroy(sfh_ctx* ctx) {
   (void)hipFree(ctx->d_implied);
   (void)hipFree(ctx->d_bstatus);
   if (ctx->h_bstatus) (void)hipHostFree(ctx->h_bstatus);
-  (void)hipFree(ctx->d_anysm);
   (void)hipFree(ctx->d_anycnt);
   (void)hipFree(ctx->d_any);
   (void)hipFree(ctx->d_anyseg);
@@ -3086,25 +2926,16 @@ int sfh_recover_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint
   if (dst_n == SFH_SIZE_FROM_TRAILER || !d_index || ((uintptr_t)d_index & 7) || nseg != (size_t)chunks_of((size_t)dst_n) ||
       nseg > ((size_t)1 << 31) - 1)
     return fail(ctx, SFH_E_INVALID_ARG, "index: 8-byte aligned, nseg = max(1, ceil(dst_n / 32768))", hipSuccess);
+  if (int rc = check_any_waves(ctx, src_n)) return rc;
   hipStream_t s;
   if (int rc = begin_call(ctx, stream, &s)) return rc;
-  const uint8_t* src = (const uint8_t*)d_src;
-  uint32_t wst = 0, isize = 0;
-  bool ok = false;
-  int rc = any_wrapper(ctx, src, src_n, container, dst_n, s, &wst, &isize);
-  if (!rc && wst == 0) rc = any_walk(ctx, src, src_n, (uint32_t)nseg, d_index, s, &ok);
-  if (rc) return rc;
-  if (wst || !ok) return fail(ctx, SFH_E_NOT_INDEXABLE, wst ? "the wrapper header does not parse" : "not block-flushed every 32 KiB", hipSuccess);
-  if (d_depends) {
-    uint8_t* dep = nullptr;
-    if ((rc = enqueue_any_decode(ctx, src, src_n, container, nullptr, dst_n, (uint32_t)nseg, d_index, &dep, nullptr, s))) return rc;
-    SF_HIP(hipMemcpyAsync(d_depends, dep, nseg, hipMemcpyDeviceToDevice, s), "copy depends");
-    uint32_t rows = 0;
-    SF_HIP(hipMemcpyAsync(&rows, any_tot(ctx) + 3, sizeof rows, hipMemcpyDeviceToHost, s), "D2H rows");
-    SF_HIP(hipStreamSynchronize(s), "stream sync");
-    ctx->any_counts[1] = rows;
-  }
-  return SFH_OK;
+  const uint64_t n = src_n;
+  AnyBatch R;
+  if (int rc = any_batch_recover(ctx, 1, &d_src, &n, container, nullptr, &dst_n, d_index, s, R)) return rc;
+  if (R.st[0])
+    return fail(ctx, SFH_E_NOT_INDEXABLE, R.st[0] == SFH_ITEM_NOT_INDEXABLE ? "not block-flushed every 32 KiB" : "the wrapper header does not parse",
+                hipSuccess);
+  return d_depends ? any_batch_decode(ctx, 1, &d_src, &n, container, nullptr, d_index, s, R, d_depends) : SFH_OK;
 }
 
 int sfh_recover_index(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, uint64_t dst_n, uint64_t* index, size_t nseg,
@@ -3130,33 +2961,21 @@ int sfh_decompress_any_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uin
   if (int rc = check_any(ctx, d_src, src_n, container, dst_n, true)) return rc;
   if (!status || (!d_dst && dst_n) || ((uintptr_t)d_dst & 15))
     return fail(ctx, SFH_E_INVALID_ARG, "argument (status, dst 16-byte aligned)", hipSuccess);
+  if (int rc = check_any_waves(ctx, src_n)) return rc;
   hipStream_t s;
   if (int rc = begin_call(ctx, stream, &s)) return rc;
-  const uint8_t* src = (const uint8_t*)d_src;
-  uint32_t wst = 0, isize = 0;
-  int rc = any_wrapper(ctx, src, src_n, container, dst_n, s, &wst, &isize);
-  if (rc) return rc;
-  if (wst) {  // container.hpp's answer for the wrapper (SrcTooSmall, Error, DstTooSmall)
-    *status = wst;
+  // The call takes no capacity: the size asked for is the capacity, and no ISIZE is above the one of a size from the trailer.
+  const uint64_t n = src_n, cap = dst_n == SFH_SIZE_FROM_TRAILER ? UINT64_MAX : dst_n;
+  AnyBatch R;
+  if (int rc = any_batch_recover(ctx, 1, &d_src, &n, container, &cap, &dst_n, nullptr, s, R)) return rc;
+  if (R.st[0] == SFH_ITEM_NOT_INDEXABLE) return fail(ctx, SFH_E_NOT_INDEXABLE, "not block-flushed every 32 KiB", hipSuccess);
+  if (R.st[0]) {  // container.hpp's answer for the wrapper (SrcTooSmall, Error, DstTooSmall)
+    *status = R.st[0];
     return SFH_OK;
   }
-  const uint64_t out_n = dst_n == SFH_SIZE_FROM_TRAILER ? isize : dst_n;
-  const size_t nseg = chunks_of((size_t)out_n);
-  if (nseg > ((size_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 segments", hipSuccess);
-  if ((rc = grow(ctx, &ctx->d_anyix, &ctx->d_anyix_cap, (nseg + 1) * sizeof(uint64_t), "recovered index"))) return rc;
-  bool ok = false;
-  if ((rc = any_walk(ctx, src, src_n, (uint32_t)nseg, ctx->d_anyix, s, &ok))) return rc;
-  if (!ok) return fail(ctx, SFH_E_NOT_INDEXABLE, "not block-flushed every 32 KiB", hipSuccess);
-  uint32_t* d_status = (uint32_t*)(ctx->d_anysm + kAnyStatus);
-  if ((rc = enqueue_any_decode(ctx, src, src_n, container, (uint8_t*)d_dst, out_n, (uint32_t)nseg, ctx->d_anyix, nullptr, d_status, s)))
-    return rc;
-  uint32_t res[2] = {0, 0};  // status, rows
-  SF_HIP(hipMemcpyAsync(&res[0], d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy status");
-  SF_HIP(hipMemcpyAsync(&res[1], any_tot(ctx) + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy rows");
-  SF_HIP(hipStreamSynchronize(s), "stream sync");
-  *status = res[0];
-  ctx->any_counts[1] = res[1];
-  if (res[0]) snprintf(ctx->err, sizeof ctx->err, "DecompressStatus %u", res[0]);
+  if (int rc = any_batch_decode(ctx, 1, &d_src, &n, container, &d_dst, ctx->d_anyix, s, R)) return rc;
+  *status = R.st[0];
+  if (R.st[0]) snprintf(ctx->err, sizeof ctx->err, "DecompressStatus %u", R.st[0]);
   return SFH_OK;
 }
 

@@ -105,6 +105,15 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_add(v), 63);
 }
 
+// A pointer read from a row is a generic one to the compiler, and a load through it a FLAT load, which counts on lgkmcnt as
+// well as on vmcnt: k_inflate_tokens' waits for its LDS reads then also wait for the window loads in flight (token stage of a
+// 1 GiB stream, sub-indexed: 3.24 ms against 2.97 with the stream pointer a kernel argument).  Rows point to device
+// memory; said here, where a kernel takes a pointer out of its row, the accesses are global ones.
+template <class T>
+__device__ __forceinline__ T* row_ptr(T* p) {
+  return (T*)(__attribute__((address_space(1))) T*)(uintptr_t)p;
+}
+
 // per-chunk plan record written by K2, read by K3/K4
 struct ChunkPlan {
   uint32_t btype;        // 0 stored, 1 fixed, 2 dynamic
@@ -405,24 +414,10 @@ uint32_t any_scan_waves(uint64_t src_n);  // waves (per-wave counts) of k_any_sc
 size_t any_scan_tmp_words(uint32_t n);    // words of `tmp` launch_scan_u32 needs for n elements
 // exclusive scan of n uint32 (in-place allowed); *total: their sum (device)
 hipError_t launch_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* tmp, uint32_t* total, hipStream_t s);
-// head[0..1]: the body [b0, e).  count: nodes and M nodes per wave; nodes: write them (offsets = exclusive scans of the counts)
-hipError_t launch_any_count(const uint8_t* src, uint64_t src_n, const uint64_t* head, uint32_t* cnt_nodes, uint32_t* cnt_m,
-                            hipStream_t s);
-hipError_t launch_any_nodes(const uint8_t* src, uint64_t src_n, const uint64_t* head, uint32_t* node_off, uint32_t* m_off,
-                            uint64_t* pos, uint8_t* flg, uint32_t* minc, uint32_t* midx, hipStream_t s);
-// n >= 1 nodes, nm of them M: index[0..nseg] and res[0] = segment starts on the chain from b0
-hipError_t launch_any_walk(const uint8_t* src, const uint64_t* head, const uint64_t* pos, const uint8_t* flg, const uint32_t* minc,
-                           const uint32_t* midx, uint32_t n, uint32_t nm, uint32_t* nxt_a, uint32_t* nxt_b, uint8_t* lab,
-                           uint8_t* mark, uint32_t* lbl, uint32_t* rank, uint32_t* tmp, uint32_t* total, uint64_t* index,
-                           uint32_t nseg, uint32_t* res, hipStream_t s);
-hipError_t launch_any_single(const uint64_t* head, uint64_t* index, uint32_t* res, hipStream_t s);
-// behind the token stage: depends[seg], and the strip rows of k_inflate_bytes (nseg slots, the unused ones empty)
-hipError_t launch_any_rows(const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends, uint32_t* starts,
-                           uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows, hipStream_t s);
-// Many bodies in one call (sfh_recover_index_batch*, sfh_decompress_any_batch*): the scan runs one wave per 8 KiB of one item
-// (waves: the wave -> {item, piece} map, built by the host), the node list is the items' lists one after the other, each with
-// its own end sentinel, and the walk stays inside a node's item (range[item], written by launch_any_ranges).  heads: every
-// item's body [b0, e) (k_inflate_head's implied entries); index: flat, item i's nseg + 1 entries from items[i].ix0.
+// The bodies of a call (one stream is a call of one item): the scan runs one wave per 8 KiB of one item (waves: the wave ->
+// {item, piece} map, built by the host), the node list is the items' lists one after the other, each with its own end
+// sentinel, and the walk stays inside a node's item (range[item], written by launch_any_ranges).  heads: every item's body
+// [b0, e) (k_inflate_head's implied entries); index: flat, item i's nseg + 1 entries from items[i].ix0.
 struct AnyItem {
   const uint8_t* src;
   uint64_t src_n;
@@ -438,25 +433,27 @@ struct AnyRange {
   uint32_t n0, n1, m0, m1; // the item's nodes [n0, n1) and its sentinel n1; its M nodes [m0, m1) of the M list
 };
 static_assert(sizeof(AnyItem) == 40 && sizeof(AnyWave) == 8 && sizeof(AnyRange) == 16, "recovery descriptor rows");
-hipError_t launch_any_count_batch(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves,
-                                  uint32_t* cnt_nodes, uint32_t* cnt_m, hipStream_t s);
+// count: nodes and M nodes per wave; nodes: write them (offsets = exclusive scans of the counts)
+hipError_t launch_any_count(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves, uint32_t* cnt_nodes,
+                            uint32_t* cnt_m, hipStream_t s);
 // after the scans of the counts (tot[0], tot[1]: their totals): range[], and *largest = the largest item's nodes (zeroed before)
 hipError_t launch_any_ranges(const AnyItem* items, uint32_t nitems, const uint32_t* node_off, const uint32_t* m_off, uint32_t nwaves,
                              const uint32_t* tot, AnyRange* range, uint32_t* largest, hipStream_t s);
-hipError_t launch_any_nodes_batch(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves,
-                                  uint32_t* node_off, uint32_t* m_off, uint64_t* pos, uint8_t* flg, uint32_t* minc, uint32_t* midx,
-                                  uint32_t* item, hipStream_t s);
+hipError_t launch_any_nodes(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves, uint32_t* node_off,
+                            uint32_t* m_off, uint64_t* pos, uint8_t* flg, uint32_t* minc, uint32_t* midx, uint32_t* item,
+                            hipStream_t s);
 // ntot >= 1 nodes, sentinels included: the flat index and ok[item] = the item's chain holds its nseg segments
-hipError_t launch_any_walk_batch(const AnyItem* items, const uint64_t* heads, const AnyRange* range, const uint32_t* item,
-                                 const uint64_t* pos, const uint8_t* flg, const uint32_t* minc, const uint32_t* midx, uint32_t ntot,
-                                 uint32_t largest, uint32_t* nxt_a, uint32_t* nxt_b, uint8_t* lab, uint8_t* mark, uint32_t* lbl,
-                                 uint32_t* rank, uint32_t* tmp, uint32_t* total, uint64_t* index, uint32_t* ok, hipStream_t s);
-hipError_t launch_any_single_batch(const AnyItem* items, uint32_t nitems, const uint64_t* heads, uint64_t* index, uint32_t* ok,
-                                   hipStream_t s);
-// launch_any_rows over a launch batch's segment table: an item's first segment (no history) always starts a row
-hipError_t launch_any_rows_batch(const InflateSeg* segs, const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends,
-                                 uint32_t* starts, uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows,
-                                 hipStream_t s);
+hipError_t launch_any_walk(const AnyItem* items, const uint64_t* heads, const AnyRange* range, const uint32_t* item,
+                           const uint64_t* pos, const uint8_t* flg, const uint32_t* minc, const uint32_t* midx, uint32_t ntot,
+                           uint32_t largest, uint32_t* nxt_a, uint32_t* nxt_b, uint8_t* lab, uint8_t* mark, uint32_t* lbl,
+                           uint32_t* rank, uint32_t* tmp, uint32_t* total, uint64_t* index, uint32_t* ok, hipStream_t s);
+// the items of one segment: index [b0, e], ok
+hipError_t launch_any_single(const AnyItem* items, uint32_t nitems, const uint64_t* heads, uint64_t* index, uint32_t* ok,
+                             hipStream_t s);
+// behind the token stage, over a launch batch's segment table: depends[seg], and the strip rows of k_inflate_bytes (nseg slots,
+// the unused ones empty).  An item's first segment (no history) always starts a row.
+hipError_t launch_any_rows(const InflateSeg* segs, const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends,
+                           uint32_t* starts, uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows, hipStream_t s);
 // recovered index (sfh_decompress_any*): the token kernels with the EXACT end rule for rows flagged kSegExact
 hipError_t launch_inflate_tokens_exact(const InflateSeg* rows, uint32_t nseg, uint32_t* tokens, SegInfo* info, bool speculate,
                                        hipStream_t s);

@@ -52,15 +52,6 @@ constexpr uint32_t KB_LDS = KB_RING + KB_AUX;            // 52,000 B: three work
 static_assert(3 * KB_LDS <= 160 * 1024, "k_inflate_bytes: three workgroups per CU");
 static_assert(KB_SPAN <= KB_RING - kWindow && KB_RING % 16 == 0 && kChunk % 4 == 0, "ring geometry");
 
-// A pointer read from a row is a generic one to the compiler, and a load through it a FLAT load, which counts on lgkmcnt as
-// well as on vmcnt: the token loops' waits for their LDS reads then also wait for the window loads in flight (token stage of
-// a 1 GiB stream, sub-indexed: 3.24 ms against 2.97 with the stream pointer a kernel argument).  Rows point to device
-// memory; said here, where a kernel takes a pointer out of its row, the accesses are global ones.
-template <class T>
-__device__ __forceinline__ T* row_ptr(T* p) {
-  return (T*)(__attribute__((address_space(1))) T*)(uintptr_t)p;
-}
-
 // Segment `seg` of the launch batch is rows[seg]: its stream, index entries, size and history.
 // EXACT: a row flagged kSegExact decodes with decode_segment<true> (the recovered index's end rule).
 // ROW: tokens (and output bytes) a row holds at most -- the stride of the token scratch (kWideRow: BGZF members of up to 64 KiB).

@@ -1,18 +1,25 @@
-// sf_unindexed.hip -- the segment index of a block-flushed DEFLATE stream, recovered from the stream alone,
-// and the two device passes the decoder needs on such an index (sfh_recover_index_device, sfh_decompress_any*).
+// sf_unindexed.hip -- the segment index of block-flushed DEFLATE streams, recovered from the streams alone, and
+// the device pass the decoder needs on such an index.  One kernel set: the bodies of a call are scanned and walked together,
+// and a single stream (sfh_recover_index*, sfh_decompress_any*) is a call of one item (sfh_recover_index_batch*,
+// sfh_decompress_any_batch*).
 //
-//   k_any_scan<WRITE>  one pass over the body (the stream without its wrapper): every position p with [p-4, p) = 00 00 FF FF
+//   k_any_scan<WRITE>  one pass over every body (a stream without its wrapper): every position p with [p-4, p) = 00 00 FF FF
 //                      (M, the end of a flush) and every h with [h, h+5) = 00|01 00 80 FF 7F (H, the header of a stored block of
-//                      32 KiB), plus the body's first byte b0.  One wave per 8 KiB of stream; a wave-round with no hit costs
-//                      one ballot.  WRITE = 0 counts the wave's nodes, WRITE = 1 writes them in stream order at the wave's
-//                      offset (an exclusive scan of the counts): no atomics, the node list comes out sorted.
-//   k_any_succ         every node's successor on the walk (the walk rule) and how many segments the edge covers.
+//                      32 KiB), plus the body's first byte b0.  One wave per 8 KiB of ONE item's stream; a wave-round with no
+//                      hit costs one ballot.  WRITE = 0 counts the wave's nodes, WRITE = 1 writes them in stream order at the
+//                      wave's offset (an exclusive scan of the counts): no atomics, the node list comes out sorted, item
+//                      after item, each item's list closed by its end sentinel.
+//   k_any_ranges       per item, its nodes and its M nodes in the concatenated lists.
+//   k_any_succ         every node's successor on the walk (the walk rule), inside its item, and how many segments
+//                      the edge covers.
 //   k_any_jump         one round of pointer jumping that also spreads the mark "on the chain from b0": after round r every
-//                      node at most 2^(r+1) - 1 steps behind b0 is marked.  Nodes off the chain (flush markers and fake
-//                      headers inside stored payloads) are never marked, and a run of stored segments costs no serial steps.
-//   k_any_scatter      marked node of rank k (an exclusive scan of the edge labels) -> index[k] (and index[k+1] for the coded
-//                      segment a stored jump lands on).
-//   k_any_depends      after the token stage: per segment, does a match reach before its first byte?
+//                      node at most 2^(r+1) - 1 steps behind its item's b0 is marked.  Nodes off the chain (flush markers and
+//                      fake headers inside stored payloads) are never marked, and a run of stored segments costs no serial steps.
+//   k_any_scatter      marked node of rank k in its item (an exclusive scan of the edge labels) -> the item's index[k] (and
+//                      index[k+1] for the coded segment a stored jump lands on); at the sentinel, whether the chain holds the
+//                      item's segments.
+//   k_any_single       the items of one segment, which need no scan: index [b0, e].
+//   k_any_depends      after the token stage: per segment of a launch batch, does a match reach before its first byte?
 //   k_any_rows_*       strip rows for k_inflate_bytes: an independent segment and the dependent ones behind it.
 #include "sf_device.h"
 
@@ -61,46 +68,6 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
   return v;
 }
 
-// head[0], head[1]: the body [b0, e) (k_inflate_head's implied entries).  counts: per wave {nodes, M nodes}
-// (WRITE: their exclusive scans, node_off / m_off)
-template <bool WRITE>
-__global__ __launch_bounds__(KA_THREADS) void k_any_scan(const uint8_t* __restrict__ src, uint64_t src_n,
-                                                        const uint64_t* __restrict__ head, uint32_t nwaves,
-                                                        uint32_t* __restrict__ cnt_nodes, uint32_t* __restrict__ cnt_m,
-                                                        uint64_t* __restrict__ pos, uint8_t* __restrict__ flg,
-                                                        uint32_t* __restrict__ minc, uint32_t* __restrict__ midx) {
-  const uint32_t wave = blockIdx.x * (KA_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (wave >= nwaves) return;
-  const uint64_t b0 = head[0], e = head[1];
-  uint32_t nodes = WRITE ? cnt_nodes[wave] : 0u, ms = WRITE ? cnt_m[wave] : 0u;
-  const int64_t k0 = (int64_t)wave * (KA_WAVE_BYTES / 4);
-  for (uint32_t r = 0; r < KA_ROUNDS; ++r) {
-    const int64_t k = k0 + r * 64 + lane;
-    const uint32_t h = hits_at(src, src_n, b0, e, k);
-    if (__ballot(h != 0) == 0) continue;
-    const uint32_t pm = h & 15u, any = (h | (h >> 4) | (h >> 8)) & 15u;
-    const uint32_t n_incl = wave_incl_scan(__popc(any)), m_incl = wave_incl_scan(__popc(pm));
-    if constexpr (WRITE) {
-      uint32_t at = nodes + n_incl - __popc(any), mat = ms + m_incl - __popc(pm);
-      for (uint32_t j = 0; j < 4; ++j) {
-        if (!((any >> j) & 1u)) continue;
-        const bool is_m = (pm >> j) & 1u;
-        pos[at] = 4 * (uint64_t)k + j;
-        flg[at] = (is_m ? kNodeM : 0) | (((h >> (4 + j)) & 1u) ? kNodeH : 0);
-        if (is_m) midx[mat++] = at;
-        minc[at] = mat;  // M nodes at or before this one
-        ++at;
-      }
-    }
-    nodes += (uint32_t)__shfl((int)n_incl, 63, 64);
-    ms += (uint32_t)__shfl((int)m_incl, 63, 64);
-  }
-  if (!WRITE && lane == 0) {
-    cnt_nodes[wave] = nodes;
-    cnt_m[wave] = ms;
-  }
-}
-
 // where the segment after a stored segment at p starts: behind its 32 KiB, and behind the empty stored blocks a flush writes
 __device__ __forceinline__ uint64_t landing(const uint8_t* src, uint64_t p, uint64_t e) {
   uint64_t t = p + kStoredSeg;
@@ -117,82 +84,6 @@ __device__ __forceinline__ uint32_t lower_bound(const uint64_t* pos, uint32_t n,
     else hi = mid;
   }
   return lo;
-}
-
-// The walk rule: from a start s in H the next start is landing(s); from any other start, the first M after s.  A landing
-// that is no node is a coded segment's start whose own successor is the first M after it: that edge covers two segments.
-__global__ __launch_bounds__(KA_THREADS) void k_any_succ(const uint8_t* __restrict__ src, const uint64_t* __restrict__ head,
-                                                        const uint64_t* __restrict__ pos, const uint8_t* __restrict__ flg,
-                                                        const uint32_t* __restrict__ minc, const uint32_t* __restrict__ midx,
-                                                        uint32_t n, uint32_t nm, uint32_t* __restrict__ nxt,
-                                                        uint8_t* __restrict__ lab, uint8_t* __restrict__ mark) {
-  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
-  if (i > n) return;
-  if (i == n) {
-    nxt[n] = n;  // the end of the body
-    return;
-  }
-  const uint64_t e = head[1];
-  uint32_t s = n, l = 1;
-  if (flg[i] & kNodeH) {
-    const uint64_t t = landing(src, pos[i], e);
-    if (t < e) {
-      const uint32_t j = lower_bound(pos, n, t);
-      if (j < n && pos[j] == t) {
-        s = j;
-      } else {
-        const uint32_t mi = j < n ? minc[j] - (flg[j] & kNodeM) : nm;  // M nodes before j
-        s = mi < nm ? midx[mi] : n;
-        l = 2;
-      }
-    }
-  } else {
-    const uint32_t mi = minc[i];
-    s = mi < nm ? midx[mi] : n;
-  }
-  nxt[i] = s;
-  lab[i] = (uint8_t)l;
-  mark[i] = i == 0;
-}
-
-__global__ __launch_bounds__(KA_THREADS) void k_any_jump(const uint32_t* __restrict__ nxt, uint32_t* __restrict__ nxt2,
-                                                        uint8_t* mark, uint32_t n) {
-  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
-  if (i > n) return;
-  const uint32_t j = nxt[i];
-  // (a node marked by another lane of this round is on the chain as well: marks only ever spread along it)
-  if (i < n && j < n && mark[i]) mark[j] = 1;
-  nxt2[i] = nxt[j];
-}
-
-__global__ __launch_bounds__(KA_THREADS) void k_any_labels(const uint8_t* __restrict__ lab, const uint8_t* __restrict__ mark,
-                                                          uint32_t n, uint32_t* __restrict__ c) {
-  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
-  if (i < n) c[i] = mark[i] ? lab[i] : 0u;
-}
-
-// res[0]: segment starts on the chain (>= nseg: indexable)
-__global__ __launch_bounds__(KA_THREADS) void k_any_scatter(const uint8_t* __restrict__ src, const uint64_t* __restrict__ head,
-                                                           const uint64_t* __restrict__ pos, const uint8_t* __restrict__ lab,
-                                                           const uint8_t* __restrict__ mark, const uint32_t* __restrict__ rank,
-                                                           const uint32_t* __restrict__ total, uint32_t n, uint64_t* __restrict__ index,
-                                                           uint32_t nseg, uint32_t* __restrict__ res) {
-  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
-  if (i == 0) {
-    index[nseg] = head[1];
-    res[0] = *total;
-  }
-  if (i >= n || !mark[i]) return;
-  const uint32_t k = rank[i];
-  if (k < nseg) index[k] = pos[i];
-  if (lab[i] == 2 && k + 1 < nseg) index[k + 1] = landing(src, pos[i], head[1]);
-}
-
-// one segment: index [b0, e], res[0] = 1 (an empty body included: the decoder says what is wrong with it)
-__global__ void k_any_single(const uint64_t* __restrict__ head, uint64_t* __restrict__ index, uint32_t* __restrict__ res) {
-  index[0] = head[0];
-  index[1] = head[1];
-  res[0] = 1;
 }
 
 // ---- exclusive scan of uint32 (1024 per block, then the block sums in one workgroup, then the add) ----
@@ -248,74 +139,26 @@ __global__ __launch_bounds__(KS_T) void k_scan_add(uint32_t* __restrict__ out, u
     if (base + j < n) out[base + j] += add;
 }
 
-// ---- behind the token stage ----
-
-// one wave per segment: 1 when a match of it reaches before its first byte (segment 0 and failed or stored segments: 0)
-__global__ __launch_bounds__(64) void k_any_depends(const SegInfo* __restrict__ info, const uint32_t* __restrict__ tokens,
-                                                   uint8_t* __restrict__ depends, uint32_t* __restrict__ starts) {
-  const uint32_t seg = blockIdx.x, lane = threadIdx.x;
-  const SegInfo I = info[seg];
-  bool dep = false;
-  if (seg != 0 && I.status == inflate::kOk && !(I.raw & kSegRaw)) {
-    const uint32_t* tk = tokens + (uint64_t)seg * kChunk;
-    uint32_t out = 0;
-    for (uint32_t t0 = 0; t0 < I.ntok && !dep; t0 += 64) {
-      const uint32_t t = t0 + lane;
-      uint32_t len = 0, dist = 0;
-      if (t < I.ntok) {
-        const uint32_t tok = tk[t];
-        const bool m = (tok & inflate::kTokMatchBit) != 0;
-        len = m ? ((tok >> 16) & 0x7FFFu) + 3u : 1u;
-        dist = m ? (tok & 0xFFFFu) + 1u : 0u;
-      }
-      const uint32_t incl = wave_incl_scan(len);
-      dep = __ballot(dist > out + incl - len) != 0;  // (a literal has dist 0)
-      out += (uint32_t)__shfl((int)incl, 63, 64);
-    }
-  }
-  if (lane == 0) {
-    depends[seg] = dep ? 1 : 0;
-    starts[seg] = dep ? 0u : 1u;
-  }
-}
-
-// rows: row r starts at the r-th independent segment; slots past the last row are {0, 0} (the byte kernel's grid is nseg)
-__global__ __launch_bounds__(KA_THREADS) void k_any_rows_a(const uint32_t* __restrict__ starts, const uint32_t* __restrict__ excl,
-                                                          const uint32_t* __restrict__ nrows, uint32_t nseg,
-                                                          InflateStrip* __restrict__ rows) {
-  const uint32_t k = blockIdx.x * KA_THREADS + threadIdx.x;
-  if (k >= nseg) return;
-  if (k >= *nrows) rows[k] = InflateStrip{0, 0};
-  if (starts[k]) rows[excl[k]].seg0 = k;
-}
-__global__ __launch_bounds__(KA_THREADS) void k_any_rows_b(const uint32_t* __restrict__ starts, const uint32_t* __restrict__ excl,
-                                                          uint32_t nseg, InflateStrip* __restrict__ rows) {
-  const uint32_t k = blockIdx.x * KA_THREADS + threadIdx.x;
-  if (k >= nseg || !(k + 1 == nseg || starts[k + 1])) return;
-  const uint32_t r = excl[k] + starts[k] - 1;  // the row segment k belongs to
-  rows[r].nseg = k + 1 - rows[r].seg0;
-}
-
-// ---- many bodies in one call (sfh_recover_index_batch*, sfh_decompress_any_batch*) ----
+// ---- the bodies of a call ----
 // The node list is the items' lists one after the other, each closed by its own end sentinel (kNodeS, at the body's end e: the
 // last wave of an item writes it); item[at] names a node's item, range[item] its nodes [n0, n1) (n1: the sentinel) and its M
-// nodes [m0, m1) in the concatenated lists.  An item of one segment has no waves and no nodes (k_any_single's rule).
+// nodes [m0, m1) in the concatenated lists.  An item of one segment has no waves and no nodes (k_any_single).
 constexpr uint8_t kNodeS = 4;
 
 // one wave per 8 KiB of ONE item's stream (waves[wave] = {item, piece}): hits are tested against the item's own base and body,
 // so a pattern is never seen across two items that lie back to back
 template <bool WRITE>
-__global__ __launch_bounds__(KA_THREADS) void k_any_scan_batch(const AnyItem* __restrict__ items, const AnyWave* __restrict__ waves,
-                                                              const uint64_t* __restrict__ heads, uint32_t nwaves,
-                                                              uint32_t* __restrict__ cnt_nodes, uint32_t* __restrict__ cnt_m,
-                                                              uint64_t* __restrict__ pos, uint8_t* __restrict__ flg,
-                                                              uint32_t* __restrict__ minc, uint32_t* __restrict__ midx,
-                                                              uint32_t* __restrict__ item) {
+__global__ __launch_bounds__(KA_THREADS) void k_any_scan(const AnyItem* __restrict__ items, const AnyWave* __restrict__ waves,
+                                                         const uint64_t* __restrict__ heads, uint32_t nwaves,
+                                                         uint32_t* __restrict__ cnt_nodes, uint32_t* __restrict__ cnt_m,
+                                                         uint64_t* __restrict__ pos, uint8_t* __restrict__ flg,
+                                                         uint32_t* __restrict__ minc, uint32_t* __restrict__ midx,
+                                                         uint32_t* __restrict__ item) {
   const uint32_t wave = blockIdx.x * (KA_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (wave >= nwaves) return;
   const AnyWave W = waves[wave];
   const AnyItem I = items[W.item];
-  const uint8_t* src = I.src;
+  const uint8_t* src = row_ptr(I.src);  // (global loads, as with the stream a kernel argument)
   const uint64_t src_n = I.src_n, b0 = heads[2 * (size_t)W.item], e = heads[2 * (size_t)W.item + 1];
   uint32_t nodes = WRITE ? cnt_nodes[wave] : 0u, ms = WRITE ? cnt_m[wave] : 0u;
   const int64_t k0 = (int64_t)W.piece * (KA_WAVE_BYTES / 4);
@@ -359,9 +202,9 @@ __global__ __launch_bounds__(KA_THREADS) void k_any_scan_batch(const AnyItem* __
 
 // per item, from the scanned counts: its node and M ranges; tot[5]: the largest item's nodes (the rounds of the jump)
 __global__ __launch_bounds__(KA_THREADS) void k_any_ranges(const AnyItem* __restrict__ items, uint32_t nitems,
-                                                          const uint32_t* __restrict__ node_off, const uint32_t* __restrict__ m_off,
-                                                          uint32_t nwaves, const uint32_t* __restrict__ tot,
-                                                          AnyRange* __restrict__ range, uint32_t* __restrict__ largest) {
+                                                           const uint32_t* __restrict__ node_off, const uint32_t* __restrict__ m_off,
+                                                           uint32_t nwaves, const uint32_t* __restrict__ tot,
+                                                           AnyRange* __restrict__ range, uint32_t* __restrict__ largest) {
   const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
   if (i >= nitems) return;
   const AnyItem I = items[i];
@@ -377,14 +220,16 @@ __global__ __launch_bounds__(KA_THREADS) void k_any_ranges(const AnyItem* __rest
   range[i] = R;
 }
 
-// k_any_succ over the concatenated list: the search and the M lists are confined to the node's item, its sentinel is a
-// self-loop and the mark starts at the item's first node
-__global__ __launch_bounds__(KA_THREADS) void k_any_succ_batch(const AnyItem* __restrict__ items, const uint64_t* __restrict__ heads,
-                                                              const AnyRange* __restrict__ range, const uint32_t* __restrict__ item,
-                                                              const uint64_t* __restrict__ pos, const uint8_t* __restrict__ flg,
-                                                              const uint32_t* __restrict__ minc, const uint32_t* __restrict__ midx,
-                                                              uint32_t ntot, uint32_t* __restrict__ nxt, uint8_t* __restrict__ lab,
-                                                              uint8_t* __restrict__ mark) {
+// The walk rule: from a start s in H the next start is landing(s); from any other start, the first M after s.  A landing
+// that is no node is a coded segment's start whose own successor is the first M after it: that edge covers two segments.
+// Over the concatenated list: the search and the M lists are confined to the node's item, its sentinel is a self-loop and the
+// mark starts at the item's first node.
+__global__ __launch_bounds__(KA_THREADS) void k_any_succ(const AnyItem* __restrict__ items, const uint64_t* __restrict__ heads,
+                                                         const AnyRange* __restrict__ range, const uint32_t* __restrict__ item,
+                                                         const uint64_t* __restrict__ pos, const uint8_t* __restrict__ flg,
+                                                         const uint32_t* __restrict__ minc, const uint32_t* __restrict__ midx,
+                                                         uint32_t ntot, uint32_t* __restrict__ nxt, uint8_t* __restrict__ lab,
+                                                         uint8_t* __restrict__ mark) {
   const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
   if (i >= ntot) return;
   const uint32_t it = item[i];
@@ -421,14 +266,30 @@ __global__ __launch_bounds__(KA_THREADS) void k_any_succ_batch(const AnyItem* __
   mark[i] = i == R.n0;
 }
 
+__global__ __launch_bounds__(KA_THREADS) void k_any_jump(const uint32_t* __restrict__ nxt, uint32_t* __restrict__ nxt2,
+                                                         uint8_t* mark, uint32_t n) {
+  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (i > n) return;
+  const uint32_t j = nxt[i];
+  // (a node marked by another lane of this round is on the chain as well: marks only ever spread along it)
+  if (i < n && j < n && mark[i]) mark[j] = 1;
+  nxt2[i] = nxt[j];
+}
+
+__global__ __launch_bounds__(KA_THREADS) void k_any_labels(const uint8_t* __restrict__ lab, const uint8_t* __restrict__ mark,
+                                                           uint32_t n, uint32_t* __restrict__ c) {
+  const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (i < n) c[i] = mark[i] ? lab[i] : 0u;
+}
+
 // rank: the exclusive scan of the labels over the whole list; a node's segment is its rank minus the rank of its item's first
 // node, and the rank at the sentinel closes the item's chain total: ok[item] = the chain holds the item's nseg segments.
 // index: flat, every item's nseg + 1 entries from its ix0 (sfh_copy_batch_index's layout)
-__global__ __launch_bounds__(KA_THREADS) void k_any_scatter_batch(const AnyItem* __restrict__ items, const uint64_t* __restrict__ heads,
-                                                                 const AnyRange* __restrict__ range, const uint32_t* __restrict__ item,
-                                                                 const uint64_t* __restrict__ pos, const uint8_t* __restrict__ lab,
-                                                                 const uint8_t* __restrict__ mark, const uint32_t* __restrict__ rank,
-                                                                 uint32_t ntot, uint64_t* __restrict__ index, uint32_t* __restrict__ ok) {
+__global__ __launch_bounds__(KA_THREADS) void k_any_scatter(const AnyItem* __restrict__ items, const uint64_t* __restrict__ heads,
+                                                            const AnyRange* __restrict__ range, const uint32_t* __restrict__ item,
+                                                            const uint64_t* __restrict__ pos, const uint8_t* __restrict__ lab,
+                                                            const uint8_t* __restrict__ mark, const uint32_t* __restrict__ rank,
+                                                            uint32_t ntot, uint64_t* __restrict__ index, uint32_t* __restrict__ ok) {
   const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
   if (i >= ntot) return;
   const uint32_t it = item[i];
@@ -447,10 +308,10 @@ __global__ __launch_bounds__(KA_THREADS) void k_any_scatter_batch(const AnyItem*
   if (lab[i] == 2 && k + 1 < I.nseg) ix[k + 1] = landing(I.src, pos[i], e);
 }
 
-// the items of one segment: index [b0, e], indexable (k_any_single's rule)
-__global__ __launch_bounds__(KA_THREADS) void k_any_single_batch(const AnyItem* __restrict__ items, uint32_t nitems,
-                                                                const uint64_t* __restrict__ heads, uint64_t* __restrict__ index,
-                                                                uint32_t* __restrict__ ok) {
+// the items of one segment: index [b0, e], indexable (an empty body included: the decoder says what is wrong with it)
+__global__ __launch_bounds__(KA_THREADS) void k_any_single(const AnyItem* __restrict__ items, uint32_t nitems,
+                                                           const uint64_t* __restrict__ heads, uint64_t* __restrict__ index,
+                                                           uint32_t* __restrict__ ok) {
   const uint32_t i = blockIdx.x * KA_THREADS + threadIdx.x;
   if (i >= nitems || items[i].nwaves) return;
   index[items[i].ix0] = heads[2 * (size_t)i];
@@ -458,10 +319,13 @@ __global__ __launch_bounds__(KA_THREADS) void k_any_single_batch(const AnyItem* 
   ok[i] = 1;
 }
 
-// k_any_depends over a launch batch's segment table: an item's first segment (no history) always starts a row
-__global__ __launch_bounds__(64) void k_any_depends_batch(const InflateSeg* __restrict__ rows, const SegInfo* __restrict__ info,
-                                                         const uint32_t* __restrict__ tokens, uint8_t* __restrict__ depends,
-                                                         uint32_t* __restrict__ starts) {
+// ---- behind the token stage ----
+
+// one wave per segment of a launch batch's segment table: 1 when a match of it reaches before its first byte (an item's first
+// segment, which has no history and always starts a row, and failed or stored segments: 0)
+__global__ __launch_bounds__(64) void k_any_depends(const InflateSeg* __restrict__ rows, const SegInfo* __restrict__ info,
+                                                    const uint32_t* __restrict__ tokens, uint8_t* __restrict__ depends,
+                                                    uint32_t* __restrict__ starts) {
   const uint32_t seg = blockIdx.x, lane = threadIdx.x;
   const SegInfo I = info[seg];
   const bool first = (rows[seg].hist & ~(kSegWrapped | kSegExact)) == 0;
@@ -489,6 +353,23 @@ __global__ __launch_bounds__(64) void k_any_depends_batch(const InflateSeg* __re
   }
 }
 
+// rows: row r starts at the r-th independent segment; slots past the last row are {0, 0} (the byte kernel's grid is nseg)
+__global__ __launch_bounds__(KA_THREADS) void k_any_rows_a(const uint32_t* __restrict__ starts, const uint32_t* __restrict__ excl,
+                                                           const uint32_t* __restrict__ nrows, uint32_t nseg,
+                                                           InflateStrip* __restrict__ rows) {
+  const uint32_t k = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (k >= nseg) return;
+  if (k >= *nrows) rows[k] = InflateStrip{0, 0};
+  if (starts[k]) rows[excl[k]].seg0 = k;
+}
+__global__ __launch_bounds__(KA_THREADS) void k_any_rows_b(const uint32_t* __restrict__ starts, const uint32_t* __restrict__ excl,
+                                                           uint32_t nseg, InflateStrip* __restrict__ rows) {
+  const uint32_t k = blockIdx.x * KA_THREADS + threadIdx.x;
+  if (k >= nseg || !(k + 1 == nseg || starts[k + 1])) return;
+  const uint32_t r = excl[k] + starts[k] - 1;  // the row segment k belongs to
+  rows[r].nseg = k + 1 - rows[r].seg0;
+}
+
 inline uint32_t grid(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
 
 }  // namespace
@@ -504,61 +385,9 @@ hipError_t launch_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32
   return hipGetLastError();
 }
 
-hipError_t launch_any_count(const uint8_t* src, uint64_t src_n, const uint64_t* head, uint32_t* cnt_nodes, uint32_t* cnt_m,
-                            hipStream_t s) {
-  const uint32_t nw = any_scan_waves(src_n);
-  hipLaunchKernelGGL(k_any_scan<false>, dim3(grid(nw, KA_THREADS / 64)), dim3(KA_THREADS), 0, s, src, src_n, head, nw, cnt_nodes,
-                     cnt_m, (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
-  return hipGetLastError();
-}
-
-hipError_t launch_any_nodes(const uint8_t* src, uint64_t src_n, const uint64_t* head, uint32_t* node_off, uint32_t* m_off,
-                            uint64_t* pos, uint8_t* flg, uint32_t* minc, uint32_t* midx, hipStream_t s) {
-  const uint32_t nw = any_scan_waves(src_n);
-  hipLaunchKernelGGL(k_any_scan<true>, dim3(grid(nw, KA_THREADS / 64)), dim3(KA_THREADS), 0, s, src, src_n, head, nw, node_off,
-                     m_off, pos, flg, minc, midx);
-  return hipGetLastError();
-}
-
-hipError_t launch_any_walk(const uint8_t* src, const uint64_t* head, const uint64_t* pos, const uint8_t* flg, const uint32_t* minc,
-                           const uint32_t* midx, uint32_t n, uint32_t nm, uint32_t* nxt_a, uint32_t* nxt_b, uint8_t* lab,
-                           uint8_t* mark, uint32_t* lbl, uint32_t* rank, uint32_t* tmp, uint32_t* total, uint64_t* index,
-                           uint32_t nseg, uint32_t* res, hipStream_t s) {
-  hipLaunchKernelGGL(k_any_succ, dim3(grid((uint64_t)n + 1, KA_THREADS)), dim3(KA_THREADS), 0, s, src, head, pos, flg, minc, midx, n,
-                     nm, nxt_a, lab, mark);
-  // after round r the nodes up to 2^(r+1) - 1 steps behind b0 are marked; the chain has at most n nodes
-  for (uint64_t reach = 1; reach < n; reach <<= 1) {
-    hipLaunchKernelGGL(k_any_jump, dim3(grid((uint64_t)n + 1, KA_THREADS)), dim3(KA_THREADS), 0, s, nxt_a, nxt_b, mark, n);
-    std::swap(nxt_a, nxt_b);
-  }
-  hipLaunchKernelGGL(k_any_labels, dim3(grid(n, KA_THREADS)), dim3(KA_THREADS), 0, s, lab, mark, n, lbl);
-  hipError_t e = launch_scan_u32(lbl, rank, n, tmp, total, s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_any_scatter, dim3(grid(n ? n : 1, KA_THREADS)), dim3(KA_THREADS), 0, s, src, head, pos, lab, mark, rank, total,
-                     n, index, nseg, res);
-  return hipGetLastError();
-}
-
-hipError_t launch_any_single(const uint64_t* head, uint64_t* index, uint32_t* res, hipStream_t s) {
-  hipLaunchKernelGGL(k_any_single, dim3(1), dim3(1), 0, s, head, index, res);
-  return hipGetLastError();
-}
-
-hipError_t launch_any_rows(const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends, uint32_t* starts,
-                           uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows, hipStream_t s) {
-  hipLaunchKernelGGL(k_any_depends, dim3(nseg), dim3(64), 0, s, info, tokens, depends, starts);
-  hipError_t e = launch_scan_u32(starts, excl, nseg, tmp, nrows, s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_any_rows_a, dim3(grid(nseg, KA_THREADS)), dim3(KA_THREADS), 0, s, starts, excl, nrows, nseg, rows);
-  hipLaunchKernelGGL(k_any_rows_b, dim3(grid(nseg, KA_THREADS)), dim3(KA_THREADS), 0, s, starts, excl, nseg, rows);
-  return hipGetLastError();
-}
-
-// ---- many bodies in one call ----
-
-hipError_t launch_any_count_batch(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves,
-                                  uint32_t* cnt_nodes, uint32_t* cnt_m, hipStream_t s) {
-  hipLaunchKernelGGL(k_any_scan_batch<false>, dim3(grid(nwaves, KA_THREADS / 64)), dim3(KA_THREADS), 0, s, items, waves, heads, nwaves,
+hipError_t launch_any_count(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves,
+                            uint32_t* cnt_nodes, uint32_t* cnt_m, hipStream_t s) {
+  hipLaunchKernelGGL(k_any_scan<false>, dim3(grid(nwaves, KA_THREADS / 64)), dim3(KA_THREADS), 0, s, items, waves, heads, nwaves,
                      cnt_nodes, cnt_m, (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
                      (uint32_t*)nullptr);
   return hipGetLastError();
@@ -571,20 +400,21 @@ hipError_t launch_any_ranges(const AnyItem* items, uint32_t nitems, const uint32
   return hipGetLastError();
 }
 
-hipError_t launch_any_nodes_batch(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves,
-                                  uint32_t* node_off, uint32_t* m_off, uint64_t* pos, uint8_t* flg, uint32_t* minc, uint32_t* midx,
-                                  uint32_t* item, hipStream_t s) {
-  hipLaunchKernelGGL(k_any_scan_batch<true>, dim3(grid(nwaves, KA_THREADS / 64)), dim3(KA_THREADS), 0, s, items, waves, heads, nwaves,
+hipError_t launch_any_nodes(const AnyItem* items, const AnyWave* waves, const uint64_t* heads, uint32_t nwaves,
+                            uint32_t* node_off, uint32_t* m_off, uint64_t* pos, uint8_t* flg, uint32_t* minc, uint32_t* midx,
+                            uint32_t* item, hipStream_t s) {
+  hipLaunchKernelGGL(k_any_scan<true>, dim3(grid(nwaves, KA_THREADS / 64)), dim3(KA_THREADS), 0, s, items, waves, heads, nwaves,
                      node_off, m_off, pos, flg, minc, midx, item);
   return hipGetLastError();
 }
 
-hipError_t launch_any_walk_batch(const AnyItem* items, const uint64_t* heads, const AnyRange* range, const uint32_t* item,
-                                 const uint64_t* pos, const uint8_t* flg, const uint32_t* minc, const uint32_t* midx, uint32_t ntot,
-                                 uint32_t largest, uint32_t* nxt_a, uint32_t* nxt_b, uint8_t* lab, uint8_t* mark, uint32_t* lbl,
-                                 uint32_t* rank, uint32_t* tmp, uint32_t* total, uint64_t* index, uint32_t* ok, hipStream_t s) {
-  hipLaunchKernelGGL(k_any_succ_batch, dim3(grid(ntot, KA_THREADS)), dim3(KA_THREADS), 0, s, items, heads, range, item, pos, flg, minc,
+hipError_t launch_any_walk(const AnyItem* items, const uint64_t* heads, const AnyRange* range, const uint32_t* item,
+                           const uint64_t* pos, const uint8_t* flg, const uint32_t* minc, const uint32_t* midx, uint32_t ntot,
+                           uint32_t largest, uint32_t* nxt_a, uint32_t* nxt_b, uint8_t* lab, uint8_t* mark, uint32_t* lbl,
+                           uint32_t* rank, uint32_t* tmp, uint32_t* total, uint64_t* index, uint32_t* ok, hipStream_t s) {
+  hipLaunchKernelGGL(k_any_succ, dim3(grid(ntot, KA_THREADS)), dim3(KA_THREADS), 0, s, items, heads, range, item, pos, flg, minc,
                      midx, ntot, nxt_a, lab, mark);
+  // after round r the nodes up to 2^(r+1) - 1 steps behind an item's b0 are marked; a chain has at most `largest` nodes
   // (the list's last node is a sentinel: k_any_jump's n.  A sentinel it marks carries the label 0.)
   for (uint64_t reach = 1; reach < largest; reach <<= 1) {
     hipLaunchKernelGGL(k_any_jump, dim3(grid(ntot, KA_THREADS)), dim3(KA_THREADS), 0, s, nxt_a, nxt_b, mark, ntot - 1);
@@ -593,21 +423,21 @@ hipError_t launch_any_walk_batch(const AnyItem* items, const uint64_t* heads, co
   hipLaunchKernelGGL(k_any_labels, dim3(grid(ntot, KA_THREADS)), dim3(KA_THREADS), 0, s, lab, mark, ntot, lbl);
   hipError_t e = launch_scan_u32(lbl, rank, ntot, tmp, total, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_any_scatter_batch, dim3(grid(ntot, KA_THREADS)), dim3(KA_THREADS), 0, s, items, heads, range, item, pos, lab,
+  hipLaunchKernelGGL(k_any_scatter, dim3(grid(ntot, KA_THREADS)), dim3(KA_THREADS), 0, s, items, heads, range, item, pos, lab,
                      mark, rank, ntot, index, ok);
   return hipGetLastError();
 }
 
-hipError_t launch_any_single_batch(const AnyItem* items, uint32_t nitems, const uint64_t* heads, uint64_t* index, uint32_t* ok,
-                                   hipStream_t s) {
-  hipLaunchKernelGGL(k_any_single_batch, dim3(grid(nitems, KA_THREADS)), dim3(KA_THREADS), 0, s, items, nitems, heads, index, ok);
+hipError_t launch_any_single(const AnyItem* items, uint32_t nitems, const uint64_t* heads, uint64_t* index, uint32_t* ok,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(k_any_single, dim3(grid(nitems, KA_THREADS)), dim3(KA_THREADS), 0, s, items, nitems, heads, index, ok);
   return hipGetLastError();
 }
 
-hipError_t launch_any_rows_batch(const InflateSeg* segs, const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends,
-                                 uint32_t* starts, uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows,
-                                 hipStream_t s) {
-  hipLaunchKernelGGL(k_any_depends_batch, dim3(nseg), dim3(64), 0, s, segs, info, tokens, depends, starts);
+hipError_t launch_any_rows(const InflateSeg* segs, const SegInfo* info, const uint32_t* tokens, uint32_t nseg, uint8_t* depends,
+                           uint32_t* starts, uint32_t* excl, uint32_t* tmp, uint32_t* nrows, InflateStrip* rows,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(k_any_depends, dim3(nseg), dim3(64), 0, s, segs, info, tokens, depends, starts);
   hipError_t e = launch_scan_u32(starts, excl, nseg, tmp, nrows, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_any_rows_a, dim3(grid(nseg, KA_THREADS)), dim3(KA_THREADS), 0, s, starts, excl, nrows, nseg, rows);

@@ -427,5 +427,9 @@ def test_refusals_on_a_context(comp):
     assert lib.sfh_decompress_any_batch_device(h, m, (C.c_void_p * m)(*[sp] * m), (C.c_uint64 * m)(*[8] * m), 0,
                                                (C.c_void_p * m)(*[dp + 16 * i for i in range(m)]), (C.c_uint64 * m)(*[16] * m),
                                                (C.c_uint64 * m)(*[1 << 44] * m), None, (C.c_uint32 * m)(), None) == 0  # (each DstTooSmall)
+    # the single calls run on the same driver, which counts scan waves in 32 bits: a stream of 2^31 + 1 waves is refused
+    one = C.c_uint32(9)
+    assert lib.sfh_decompress_any_device(h, sp, (1 << 44) + 8192, 0, dp, 16, C.byref(one), None) == -1 and one.value == 9
+    assert lib.sfh_recover_index_device(h, sp, (1 << 44) + 8192, 0, 16, C.c_void_p(ixb.data_ptr()), 1, None, None) == -1
     torch.cuda.synchronize()
     assert list(st) == [9, 9] and (dst.cpu().numpy() == FILL).all() and not ixb.cpu().numpy().any()
