@@ -330,6 +330,16 @@ int sfh_copy_subindex(sfh_ctx* ctx, uint32_t* dst, size_t words, int dst_on_devi
  * 0 = 32768, every segment independent): a match of segment i may reach back to the first byte of its strip,
  * a farther one is InvalidDistance.  Returns SFH_OK when the kernels ran; *status is then the reference's
  * DecompressStatus (0 = Success) of the first failing segment in stream order; dst is complete only on 0.
+ * Which status a damaged segment gets: the serial decoder's (starflate::decompress, container.hpp) on the segment's own
+ * bytes with a capacity of the segment's output size -- its checks in its order, so a bit field cut short is Error, a code
+ * that needs bits behind the segment's end is InvalidLitOrLen / InvalidDistance, distance symbols 30 and 31 are
+ * InvalidLitOrLen -- on every path (sub-indexed, index only, batch, range, dictzip, BGZF, recovered index).  With the index
+ * alone no byte behind the segment changes the answer.  With a sub-index the region lanes are not held to the segment's last
+ * bit: a segment that an index entry cuts short is still decoded from the bytes behind it, and the failure is then the next
+ * segment's.  A match may reach the earlier segments of its strip as it may reach earlier output in a stream.
+ * Where a segment is not a stream: a final block that ends short of the segment's size is SrcTooSmall (the index promised
+ * more); well-formed non-final blocks that end on the segment's last bits are Success when they made its size, else
+ * SrcTooSmall (alone they would be InvalidBlockHeader: no header follows); a segment of no bytes is InvalidBlockHeader.
  * Synchronises `stream` (NULL = the ctx's own).
  * Scratch: the decoder keeps 4 bytes of tokens per output byte -- of ONE batch of whole strips, at most 1 GiB of output (round
  * 6; before: of the whole call): 4 GiB at most whatever dst_n is (sfh_last_decode_scratch_bytes), the two kernels alternating

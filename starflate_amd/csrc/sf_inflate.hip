@@ -572,6 +572,12 @@ __global__ __launch_bounds__(64, 2) void k_inflate_tokens_sub(const InflateSeg* 
     if (lane == 32 * h && live) {
       SegInfo si;
       si.status = status != inflate::kOk ? status : (fh ? first_st : (uint32_t)inflate::kOk);
+      if (si.status != inflate::kOk) {
+        // which status: the serial decoder's (the wave is done with the half's tables); a stream it has nothing against
+        // lies under a sub-index that disagrees with it: Error
+        uint32_t ended;
+        si.status = inflate::serial_verdict<L>(src, src_n, lo, hi, out_n, s_tab[h], hist, inflate::kError, ended);
+      }
       si.ntok = (status == inflate::kOk && !raw) ? total : 0u;
       si.raw = raw;
       si.out_n = out_n;

@@ -13,14 +13,20 @@
 //  * the HLIT+HDIST code lengths are one sequence (RFC 1951 3.2.7: a run may cross from the literal/length
 //    into the distance lengths); the reference reads two sequences (hazards A/B of SURVEY.md 8(c)).  Streams
 //    made by this library never contain such a run, so both decoders agree on them.
-//  * truncated input is SrcTooSmall and a code-length run past the end is Error, where the reference asserts.
+//  * a code-length run past the end is Error, where the reference asserts.
+// The token paths above are written for the good symbol; which status a damaged segment gets is decided on their failure
+// exit by serial_verdict below, the serial decoder's checks in the serial decoder's order.
 #pragma once
 #include <stdint.h>
 
 #if defined(__HIPCC__)
 #define SF_HD __host__ __device__ __forceinline__
+#define SF_HD_FREE __host__ __device__ inline                            // inlining left to the compiler
+#define SF_HD_COLD __host__ __device__ __forceinline__  // a failure exit (a call would cost the kernel its register budget)
 #else
 #define SF_HD inline
+#define SF_HD_FREE inline
+#define SF_HD_COLD inline
 #endif
 
 namespace sf {
@@ -544,6 +550,137 @@ SF_HD uint32_t decode_symbols(BitReader& br, const uint8_t* m, Sink& sink, uint3
   return br.overrun() ? (uint32_t)kSrcTooSmall : (uint32_t)kOk;
 }
 
+// ---- the failure exit: which status the serial decoder gives a damaged segment ----
+
+// The dynamic header as the serial decoder reads it (decompress.hpp: HLIT, HDIST, HCLEN, the code-length code, the literal /
+// length lengths and then the distance lengths as two sequences, each checked for over-subscription), tables into m.  Every
+// read is checked against the reader's nbits first, so no bit behind the segment decides anything.  Shared by the stream
+// decoder's block loop (sf_stream_core.h) and serial_verdict.
+template <class L>
+SF_HD_FREE uint32_t serial_dynamic(BitReader& br, uint8_t* m) {
+  if (br.nbits - br.bitpos < 14) return kError;
+  br.refill();
+  const uint32_t hlit = br.get(5), hdist = br.get(5), hclen = br.get(4) + 4;
+  if (br.nbits - br.bitpos < 3 * hclen) return kError;
+  const uint64_t clp = read_cl_lengths(br, hclen);
+  if (cl_kraft(clp) > 128u) return kError;
+  uint8_t* lut = m + L::kOffFastL + kOffClLut;
+  build_cl_lut(clp, lut);
+  uint8_t* lens = m + L::kOffLens;
+  for (uint32_t seq = 0; seq < 2; ++seq) {
+    const uint32_t n = seq ? hdist + 1 : hlit + 257;
+    uint8_t* out = lens + (seq ? 288 : 0);
+    uint32_t i = 0, kr = 0;
+    while (i < n) {
+      br.refill();
+      const uint32_t e = lut[br.peek(7)];
+      if (e == 0 || (e & 7u) > br.nbits - br.bitpos) return kInvalidLitOrLen;
+      br.drop(e & 7u);
+      const uint32_t sym = e >> 3;
+      if (sym < 16) {
+        out[i++] = (uint8_t)sym;
+        kr += sym ? 32768u >> sym : 0u;
+        continue;
+      }
+      const uint32_t xb = sym == 16 ? 2 : sym == 17 ? 3 : 7;
+      if (br.nbits - br.bitpos < xb) return kError;
+      const uint32_t rep = br.get(xb) + (sym == 18 ? 11 : 3);
+      if ((sym == 16 && i == 0) || i + rep > n) return kError;
+      const uint32_t v = sym == 16 ? out[i - 1] : 0u;
+      for (uint32_t k = 0; k < rep; ++k) out[i++] = (uint8_t)v;
+      kr += v ? rep * (32768u >> v) : 0u;
+    }
+    if (kr > 32768u) return kError;
+    for (uint32_t s = n; s < (seq ? 32u : 288u); ++s) out[s] = 0;
+  }
+  build_tables<L, true>(m);
+  build_tables<L, false>(m);
+  return kOk;
+}
+
+// The status of a segment that one of the token paths has refused with `refused` (non-zero): the serial decoder's
+// (container.hpp's decompress) on the segment's bytes alone with a capacity of out_n -- its checks in its order, every read
+// checked against the segment's last bit, nothing written.  The two places where a segment is not a stream (starflate_hip.h,
+// sfh_decompress_device): a final block that ends short of out_n is SrcTooSmall (ended = 1), and so is a segment of
+// well-formed non-final blocks whose bits end between two blocks short of out_n (the serial decoder: InvalidBlockHeader).
+// A segment the serial decoder has nothing against keeps `refused`: what was wrong is not in the stream (a sub-index that
+// disagrees with it, the end rule of a recovered index).  m: L::kBytes of table scratch, overwritten.
+template <class L>
+SF_HD_COLD uint32_t serial_verdict(const uint8_t* src, uint64_t src_n, uint64_t seg_begin, uint64_t seg_end, uint32_t out_n,
+                                   uint8_t* m, uint32_t hist, uint32_t refused, uint32_t& ended) {
+  ended = 0;
+  if (seg_begin > seg_end || seg_end > src_n) return kSrcTooSmall;  // not a segment of this stream
+  if (seg_begin == seg_end) return kInvalidBlockHeader;
+  BitReader br;
+  br.open(src, src_n, seg_begin, seg_end);
+  uint32_t pos = 0;
+  for (bool last = false; !last;) {
+    if (br.nbits - br.bitpos < 3) return pos == out_n ? refused : (uint32_t)kSrcTooSmall;  // (a segment holds 8 bits or more)
+    br.refill();
+    last = br.get(1) != 0;
+    const uint32_t type = br.get(2);
+    if (type == 3) return kInvalidBlockHeader;
+    if (type == 0) {
+      br.drop((8 - (br.bitpos & 7)) & 7);
+      if (br.nbits - br.bitpos < 32) return kError;
+      br.refill();
+      const uint32_t len = br.get(16);
+      br.refill();
+      const uint32_t nlen = br.get(16);
+      if ((len ^ nlen) != 0xFFFFu) return kNoCompressionLenMismatch;
+      if (br.nbits - br.bitpos < 8 * len) return kSrcTooSmall;
+      if (len > out_n - pos) return kDstTooSmall;
+      pos += len;
+      const uint32_t rel = br.bitpos >> 3;
+      br.bitpos += 8 * len;
+      br.seek(rel + len);
+      continue;
+    }
+    if (type == 1) {
+      read_tables<L>(br, m, 1);
+    } else {
+      const uint32_t st = serial_dynamic<L>(br, m);
+      if (st != kOk) return st;
+    }
+    for (;;) {
+      br.refill();
+      uint32_t sym;
+      const uint32_t l = decode_symbol<L, true>(m, br, sym);
+      if (l == 0 || l > br.nbits - br.bitpos) return kInvalidLitOrLen;
+      br.drop(l);
+      if (sym < 256) {
+        if (pos >= out_n) return kDstTooSmall;
+        ++pos;
+        continue;
+      }
+      if (sym == 256) break;
+      if (sym > 285) return kInvalidLitOrLen;
+      uint32_t lbase, lextra;
+      length_info(sym, lbase, lextra);
+      if (br.nbits - br.bitpos < lextra) return kError;
+      const uint32_t len = lbase + br.get(lextra);
+      br.refill();
+      uint32_t dsym;
+      const uint32_t dl = decode_symbol<L, false>(m, br, dsym);
+      if (dl == 0 || dl > br.nbits - br.bitpos) return kInvalidDistance;
+      br.drop(dl);
+      if (dsym > 29) return kInvalidLitOrLen;
+      uint32_t dbase, dextra;
+      distance_info(dsym, dbase, dextra);
+      if (br.nbits - br.bitpos < dextra) return kError;
+      const uint32_t dist = dbase + br.get(dextra);
+      if (dist > pos + hist) return kInvalidDistance;
+      if (len > out_n - pos) return kDstTooSmall;
+      pos += len;
+    }
+  }
+  if (pos != out_n) {
+    ended = 1;
+    return kSrcTooSmall;
+  }
+  return refused;
+}
+
 // Decodes the blocks of one segment: stream bytes [seg_begin, seg_end) of `src`, which must produce exactly
 // out_n bytes (at most what the caller's token row holds: 32768, or 65536 in a wide row).  Tokens go to tokens[0..ntok).  `m`: LaneLayout::kBytes of scratch.  hist: see decode_symbols.
 // EXACT (a recovered index): the segment is not the stream's last, so its blocks must end ON seg_end, none of
@@ -612,6 +749,7 @@ SF_HD SegmentResult decode_segment(const uint8_t* src, uint64_t src_n, uint64_t 
   }
   if (status == kOk && r.raw && sink.n != 0) status = kDstTooSmall;
   if (EXACT && status == kOk && (last || br.bitpos != br.nbits)) status = kError;
+  if (status != kOk) status = serial_verdict<LaneLayout>(src, src_n, seg_begin, seg_end, out_n, m, hist, status, r.ended);
   sink.flush();
   r.status = status;
   r.ntok = sink.n;

@@ -34,49 +34,6 @@ struct StreamReader {
   __device__ uint32_t rem() const { return br.nbits - br.bitpos; }  // exact while bitpos <= 2^30 + 2^20 (see the header)
 };
 
-// The dynamic header as the serial decoder reads it (decompress.hpp: HLIT, HDIST, HCLEN, the code-length code, the literal /
-// length lengths and then the distance lengths as two sequences, each checked for over-subscription), tables into m.
-__device__ uint32_t serial_dynamic(BitReader& br, uint8_t* m) {
-  if (br.nbits - br.bitpos < 14) return kError;
-  br.refill();
-  const uint32_t hlit = br.get(5), hdist = br.get(5), hclen = br.get(4) + 4;
-  if (br.nbits - br.bitpos < 3 * hclen) return kError;
-  const uint64_t clp = read_cl_lengths(br, hclen);
-  if (cl_kraft(clp) > 128u) return kError;
-  uint8_t* lut = m + LaneLayout::kOffFastL + kOffClLut;
-  build_cl_lut(clp, lut);
-  uint8_t* lens = m + LaneLayout::kOffLens;
-  for (uint32_t seq = 0; seq < 2; ++seq) {
-    const uint32_t n = seq ? hdist + 1 : hlit + 257;
-    uint8_t* out = lens + (seq ? 288 : 0);
-    uint32_t i = 0, kr = 0;
-    while (i < n) {
-      br.refill();
-      const uint32_t e = lut[br.peek(7)];
-      if (e == 0 || (e & 7u) > br.nbits - br.bitpos) return kInvalidLitOrLen;
-      br.drop(e & 7u);
-      const uint32_t sym = e >> 3;
-      if (sym < 16) {
-        out[i++] = (uint8_t)sym;
-        kr += sym ? 32768u >> sym : 0u;
-        continue;
-      }
-      const uint32_t xb = sym == 16 ? 2 : sym == 17 ? 3 : 7;
-      if (br.nbits - br.bitpos < xb) return kError;
-      const uint32_t rep = br.get(xb) + (sym == 18 ? 11 : 3);
-      if ((sym == 16 && i == 0) || i + rep > n) return kError;
-      const uint32_t v = sym == 16 ? out[i - 1] : 0u;
-      for (uint32_t k = 0; k < rep; ++k) out[i++] = (uint8_t)v;
-      kr += v ? rep * (32768u >> v) : 0u;
-    }
-    if (kr > 32768u) return kError;
-    for (uint32_t s = n; s < (seq ? 32u : 288u); ++s) out[s] = 0;
-  }
-  build_tables<LaneLayout, true>(m);
-  build_tables<LaneLayout, false>(m);
-  return kOk;
-}
-
 // A stored block's payload into the plane: `len` bytes at `from` (any address inside the stream) become `len` u16 entries at
 // `to` (2-byte aligned).  A head of single entries brings `to` to a 16-byte boundary; then 16 bytes per step: the source as
 // aligned dwords, one carried from step to step and funnelled to the source's byte offset, widened to 16 entries and written
@@ -153,7 +110,7 @@ __device__ void stream_decode(const uint8_t* src, uint64_t src_n, uint64_t b0, u
       read_lengths<LaneLayout>(br, m, 1);
       build_tables<LaneLayout, true>(m);
       build_tables<LaneLayout, false>(m);
-    } else if ((st = serial_dynamic(br, m)) != kOk) {
+    } else if ((st = serial_dynamic<LaneLayout>(br, m)) != kOk) {
       break;
     }
     for (;;) {

@@ -21,9 +21,25 @@ unsigned sfi_decode_segment(const unsigned char* src, unsigned long long src_n, 
   return r.status;
 }
 
+// as above with the history a strip's earlier segments give (hist) and, exact != 0, the end rule of a recovered index
+// (decode_segment<true>: the kernel rows flagged kSegExact)
+unsigned sfi_decode_segment_ex(const unsigned char* src, unsigned long long src_n, unsigned long long seg_begin,
+                               unsigned long long seg_end, unsigned out_n, unsigned hist, unsigned exact, unsigned* tokens_out,
+                               unsigned* ntok, unsigned* raw, unsigned long long* raw_off) {
+  alignas(16) static thread_local unsigned char mem[sf::inflate::LaneLayout::kBytes + 12];
+  std::memset(mem, 0xA5, sizeof mem);
+  const auto r = exact ? sf::inflate::decode_segment<true>(src, src_n, seg_begin, seg_end, out_n, tokens_out, mem, hist)
+                       : sf::inflate::decode_segment<false>(src, src_n, seg_begin, seg_end, out_n, tokens_out, mem, hist);
+  *ntok = r.ntok;
+  *raw = r.raw;
+  *raw_off = r.raw_off;
+  return r.status;
+}
+
 // the sub-indexed path of one segment, region after region as the 32 GPU lanes would: tokens land at their
-// compact positions (sub[2r+1] + k).  -> status; *ntok = tokens of the segment
-unsigned sfi_decode_segment_sub(const unsigned char* src, unsigned long long src_n, unsigned long long seg_begin,
+// compact positions (sub[2r+1] + k).  -> status; *ntok = tokens of the segment.  A refused segment's status is
+// serial_verdict's, as at the end of k_inflate_tokens_sub.
+static unsigned sub_regions(const unsigned char* src, unsigned long long src_n, unsigned long long seg_begin,
                                 unsigned long long seg_end, unsigned out_n, const unsigned* sub /*[32][2]*/,
                                 unsigned* tokens_out, unsigned* ntok, unsigned* raw, unsigned long long* raw_off) {
   alignas(16) static thread_local unsigned char mem[sf::inflate::LaneLayout::kBytes + 12];
@@ -44,6 +60,18 @@ unsigned sfi_decode_segment_sub(const unsigned char* src, unsigned long long src
                                     tokens_out + sub[2 * r + 1], mem, n);
     if (!st && r < 31 && sub[2 * r + 1] + n != sub[2 * r + 3]) st = sf::inflate::kError;
     if (r == 31) *ntok = sub[2 * r + 1] + n;
+  }
+  return st;
+}
+
+unsigned sfi_decode_segment_sub(const unsigned char* src, unsigned long long src_n, unsigned long long seg_begin,
+                                unsigned long long seg_end, unsigned out_n, const unsigned* sub /*[32][2]*/,
+                                unsigned* tokens_out, unsigned* ntok, unsigned* raw, unsigned long long* raw_off) {
+  unsigned st = sub_regions(src, src_n, seg_begin, seg_end, out_n, sub, tokens_out, ntok, raw, raw_off);
+  if (st) {
+    alignas(16) static thread_local unsigned char mem[sf::inflate::SharedLayout::kBytes + 12];
+    uint32_t ended;
+    st = sf::inflate::serial_verdict<sf::inflate::SharedLayout>(src, src_n, seg_begin, seg_end, out_n, mem, 0, sf::inflate::kError, ended);
   }
   return st;
 }

@@ -7,7 +7,9 @@ import zlib
 import numpy as np
 import pytest
 
+import malformed_cases as M
 import oracle_lib as O
+import stream_host as S
 from starflate_amd import _capi, synth
 
 pytestmark = pytest.mark.gpu
@@ -215,7 +217,9 @@ def test_malformed_segments_report_reference_statuses(compressor, starfleet):
     assert compressor.decompress(dyn, cut, data.size, block_bytes=32768)[1] != 0
     short = idx.copy()
     short[-1] -= np.uint64(40)  # last segment truncated
-    assert compressor.decompress(dyn[: int(short[-1])], short, data.size, block_bytes=32768)[1] in (5, 6, 7)
+    want = M.rule(S.serial, dyn[int(short[-2]): int(short[-1])], data.size - (nseg - 1) * CHUNK)[0]  # the serial decoder's
+    assert want in (1, 6, 7)
+    assert compressor.decompress(dyn[: int(short[-1])], short, data.size, block_bytes=32768)[1] == want
     rng = np.random.default_rng(3)
     noise = rng.integers(0, 256, dyn.size, dtype=np.uint8)
     assert compressor.decompress(noise, idx, data.size, block_bytes=32768)[1] != 0  # garbage never crashes, never reports success
@@ -300,7 +304,7 @@ def test_corrupted_streams_never_succeed_wrongly(compressor, starfleet):
     data = np.frombuffer(starfleet, np.uint8)
     stream = np.frombuffer(compressor.compress(data, strategy="dynamic", block_bytes=65536), np.uint8).copy()
     idx, sub = compressor.last_index(), compressor.last_subindex()
-    agree = 0
+    agree, statuses = 0, []
     for it in range(60):
         bad = stream.copy()
         for _ in range(int(rng.integers(1, 4))):
@@ -312,7 +316,13 @@ def test_corrupted_streams_never_succeed_wrongly(compressor, starfleet):
                 # the serial decoder must then also succeed with the same bytes (it reads the same blocks)
                 assert st_ref == 0 and w_ref == data.size and got == out_ref[: data.size].tobytes(), (it, s is not None)
                 agree += 1
+            # a failing status is the rule's (tests/malformed_cases.py), computed segment by segment in stream order.  With
+            # the sub-index a stream that the flips left decodable may disagree with its sub-index instead: Error
+            want = M.first_failing(S.serial, bad, idx, data.size, strip_segments=2)
+            statuses.append((it, s is not None, st, want))
+            assert st == want or (s is not None and want == 0 and st == 1), (it, s is not None, st, want)
     assert agree >= 0
+    assert any(w != 0 for _, _, _, w in statuses)
 
 
 def test_fuzz_decoder_on_zlib_and_own_streams(compressor):
