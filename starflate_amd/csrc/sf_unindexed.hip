@@ -17,7 +17,7 @@
 //                      fake headers inside stored payloads) are never marked, and a run of stored segments costs no serial steps.
 //   k_any_scatter      marked node of rank k in its item (an exclusive scan of the edge labels) -> the item's index[k] (and
 //                      index[k+1] for the coded segment a stored jump lands on); at the sentinel, whether the chain holds the
-//                      item's segments.
+//                      item's segments.  An item whose chain does not is written nowhere: its entries stay 0.
 //   k_any_single       the items of one segment, which need no scan: index [b0, e].
 //   k_any_depends      after the token stage: per segment of a launch batch, does a match reach before its first byte?
 //   k_any_rows_*       strip rows for k_inflate_bytes: an independent segment and the dependent ones behind it.
@@ -298,12 +298,13 @@ __global__ __launch_bounds__(KA_THREADS) void k_any_scatter(const AnyItem* __res
   const uint64_t e = heads[2 * (size_t)it + 1];
   uint64_t* ix = index + I.ix0;
   const uint32_t k = rank[i] - rank[R.n0];
+  const bool holds = rank[R.n1] - rank[R.n0] >= I.nseg;  // (an item whose chain is too short keeps its zeroed entries)
   if (i == R.n1) {
-    ix[I.nseg] = e;
-    ok[it] = k >= I.nseg ? 1u : 0u;
+    if (holds) ix[I.nseg] = e;
+    ok[it] = holds ? 1u : 0u;
     return;
   }
-  if (!mark[i]) return;
+  if (!mark[i] || !holds) return;
   if (k < I.nseg) ix[k] = pos[i];
   if (lab[i] == 2 && k + 1 < I.nseg) ix[k + 1] = landing(I.src, pos[i], e);
 }

@@ -86,6 +86,18 @@ def boundary_ranges(out_off, total, lengths=(0, 1, 3, 4, 5, 4096), reach=2):
     return sorted(out)
 
 
+def scale_ranges(out_off, total, count, seed=0, members=50):
+    """`count` ranges of a file of many small members: boundary_ranges of `members` boundaries in its middle (the first
+    `count` of them at most), the rest at random offsets with lengths 0 .. 200"""
+    mid = len(out_off) // 2
+    out = boundary_ranges(out_off[mid: mid + members], total, lengths=(0, 1, 3, 4, 5, 200))[:count]
+    rng = np.random.default_rng(seed)
+    while len(out) < count:
+        ln = int(rng.integers(0, 201))
+        out.append((int(rng.integers(0, total - ln + 1)), ln))
+    return out
+
+
 def narrow_case():
     data = BZ.text(sum(NARROW), seed=1)
     blob, moff, ooff = BZ.write(data, NARROW)

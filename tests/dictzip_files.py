@@ -1,6 +1,7 @@
 """A dictzip writer in Python for the tests of the table reader: zlib raw deflate, Z_FULL_FLUSH after every chunk, Z_FINISH,
 and a gzip header whose FEXTRA field carries the 'RA' table -- with the variations real files show (the final block inside
 or outside the last chunk's size, a file name, foreign subfields around 'RA', no chunk at all for an empty input)."""
+import functools
 import struct
 import zlib
 
@@ -68,6 +69,32 @@ VARIANTS = {
     "after": dict(after=(b"ZZ", b"")),
     "all": dict(final="outside", fname=b"a", before=(b"AB", b"\x01\x02\x03"), after=(b"CD", b"tail-of-extra")),
 }
+
+
+# ---- tables longer than k_dz_index's 1024 lanes (tests/test_gpu_walk_scale.py, tests/test_walk_scale_inputs.py) ----
+SCALE_CHUNKS = (1023, 1024, 1025, 2048, 2049, 4100)
+MAX_CHUNKS = 32762  # XLEN = 10 + 2 * CHCNT is 16 bits wide
+
+
+@functools.lru_cache(maxsize=None)
+def scale_file(chunks):
+    """-> (file, index): `chunks` chunks of zeros, level 1"""
+    return write(bytes(chunks * CHLEN), level=1)
+
+
+@functools.lru_cache(maxsize=None)
+def limit_file(chunks=MAX_CHUNKS, seed=3):
+    """-> (file, index): a header whose table holds `chunks` sizes of 20 .. 60 and an ISIZE to match, in front of that many
+    placeholder bytes: for the table reader alone, nothing in it decodes"""
+    sizes = [int(v) for v in np.random.default_rng(seed).integers(20, 61, chunks)]
+    ra = b"RA" + struct.pack("<HHHH", 6 + 2 * chunks, 1, CHLEN, chunks) + struct.pack(f"<{chunks}H", *sizes)
+    head = bytes([0x1F, 0x8B, 8, 4, 0, 0, 0, 0, 0, 0xFF]) + struct.pack("<H", len(ra)) + ra
+    out = head + bytes(sum(sizes)) + struct.pack("<II", 0, chunks * CHLEN)
+    index = [len(head)]
+    for s in sizes:
+        index.append(index[-1] + s)
+    assert index[-1] == len(out) - 8
+    return out, index
 
 
 def good_files(levels=(0, 6), sizes=SIZES):
