@@ -12,6 +12,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <span>
+#include <string_view>
 #include <utility>
 #include <vector>
 
@@ -192,6 +193,38 @@ inline auto bgzf_offsets_to_voffsets(const bgzf_index& ix, std::span<const std::
   return out;
 }
 
+/// ZIP archives (sfh_zip_read_index*, sfh_decompress_zip*, sfh_compress_zip*): the capacity compressor::compress_zip needs for
+/// items of these sizes under names of these lengths ...
+inline auto zip_bound(std::span<const std::uint64_t> sizes, std::span<const std::uint32_t> name_lens) -> std::size_t {
+  return sizes.size() == name_lens.size() ? sfh_zip_bound(sizes.size(), sizes.data(), name_lens.data()) : 0;
+}
+/// ... and the entry table of an archive in host memory (no device): sfh_zip_entry rows -- where every entry's data lies, its
+/// sizes, CRC-32, method and its own status (0, a DecompressStatus, or SFH_ZIP_ENTRY_UNSUPPORTED) -- and what sfh_zip_info
+/// says.  name(file, i): entry i's name, read where the table says it stands in the file.  An archive whose end record or
+/// directory does not parse is InvalidArgument.
+struct zip_index {
+  std::vector<sfh_zip_entry> entries;
+  std::uint64_t total_out{0};  // the packed layout's bytes: every entry at entries[i].out_off, 16-byte aligned
+  bool zip64{false};
+  [[nodiscard]] auto name(std::span<const std::byte> file, std::size_t i) const -> std::string_view {
+    const auto& e = entries[i];
+    if (e.name_off > file.size() || file.size() - e.name_off < e.name_len) return {};
+    return {reinterpret_cast<const char*>(file.data()) + e.name_off, e.name_len};
+  }
+};
+inline auto zip_read_index(std::span<const std::byte> file) -> compat::expected<zip_index, CompressStatus> {
+  sfh_zip_info info{};
+  (void)sfh_zip_read_index(file.data(), file.size(), &info, nullptr, 0);  // the count (SFH_E_DST_TOO_SMALL: it is there)
+  if (info.status != 0) return compat::unexpected{CompressStatus::InvalidArgument};
+  zip_index ix;
+  ix.entries.resize(static_cast<std::size_t>(info.entries));
+  const int rc = sfh_zip_read_index(file.data(), file.size(), &info, ix.entries.data(), ix.entries.size());
+  if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+  ix.total_out = info.total_out;
+  ix.zip64 = info.zip64 != 0;
+  return ix;
+}
+
 /// One GPU context (device scratch, stream).  Not thread-safe; distinct objects are independent.
 class compressor {
   sfh_ctx* ctx_{nullptr};
@@ -256,6 +289,46 @@ class compressor {
     if (rc != SFH_OK || st > 7) return DecompressStatus::Error;
     if (st == 0 && produced != nullptr) *produced = static_cast<std::size_t>(n);
     return static_cast<DecompressStatus>(st);
+  }
+  /// host spans: one ZIP archive of deflated entries, item i under names[i] (UTF-8, 1 to 65535 bytes), that unzip and zipfile
+  /// read (sfh_compress_zip).  dst.size() >= zip_bound(...); opt.container must be Raw and final_stream true.  Every entry's
+  /// body is byte for byte what compress_batch writes for that item with the same options.  No index afterwards.
+  auto compress_zip(std::span<const std::string_view> names, std::span<const std::span<const std::byte>> srcs,
+                    std::span<std::byte> dst, const compress_options& opt = {}) -> compat::expected<std::size_t, CompressStatus> {
+    if (!ctx_) return compat::unexpected{init_};
+    if (names.size() != srcs.size()) return compat::unexpected{CompressStatus::InvalidArgument};
+    const std::size_t k = srcs.size();
+    std::vector<const void*> sp(k);
+    std::vector<const char*> np(k);
+    std::vector<std::uint64_t> sn(k);
+    std::vector<std::uint32_t> nl(k);
+    for (std::size_t i = 0; i < k; ++i) {
+      sp[i] = srcs[i].data();
+      sn[i] = srcs[i].size();
+      np[i] = names[i].data();
+      nl[i] = names[i].size() > 65535 ? 65536U : static_cast<std::uint32_t>(names[i].size());  // (above the limit: refused)
+    }
+    const auto c = detail::to_c(opt);
+    std::size_t n = 0;
+    const int rc = sfh_compress_zip(ctx_, k, sp.data(), sn.data(), np.data(), nl.data(), dst.data(), dst.size(), &n, &c);
+    if (rc != SFH_OK) return compat::unexpected{detail::to_status(rc)};
+    return n;
+  }
+  /// Entries of a ZIP archive decoded (sfh_decompress_zip): entries[i] -- rows of zip_read_index(file), any subset in any order
+  /// -- into dsts[i] (dsts[i].size() >= its usize); statuses[i] = 0, the entry's DecompressStatus (a CRC-32 mismatch is 1), or
+  /// the status the index gave it (SFH_ZIP_ENTRY_UNSUPPORTED among them).  Only entries with status 0 are written.
+  auto decompress_zip(std::span<const std::byte> file, std::span<const sfh_zip_entry> entries, std::span<const std::span<std::byte>> dsts,
+                      std::span<std::uint32_t> statuses) -> CompressStatus {
+    if (!ctx_) return init_;
+    if (dsts.size() != entries.size() || statuses.size() != entries.size()) return CompressStatus::InvalidArgument;
+    const std::size_t k = entries.size();
+    std::vector<void*> dp(k);
+    std::vector<std::uint64_t> dn(k);
+    for (std::size_t i = 0; i < k; ++i) {
+      dp[i] = dsts[i].data();
+      dn[i] = dsts[i].size();
+    }
+    return detail::to_status(sfh_decompress_zip(ctx_, file.data(), file.size(), entries.data(), k, dp.data(), dn.data(), statuses.data()));
   }
   /// host spans, many independent items in one call: item i's stream goes to dsts[i] (dsts[i].size() >=
   /// compress_bound(srcs[i].size())), its size to sizes[i]; byte-identical to compress(srcs[i], dsts[i], opt).

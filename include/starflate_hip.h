@@ -614,6 +614,103 @@ int sfh_bgzf_voffsets_to_offsets(const uint64_t* member_off, const uint64_t* out
 int sfh_bgzf_offsets_to_voffsets(const uint64_t* member_off, const uint64_t* out_off, uint32_t members, size_t count,
                                  const uint64_t* offsets, uint64_t* voffsets);
 
+/* ---- ZIP archives (.zip, .npz, .jar, .whl, .docx, torch.save): stored and deflated entries, written and read ----
+ * (APPNOTE 6.3; all little-endian)
+ *   local header  50 4B 03 04 | need flags method time date | CRC-32 csize usize | name_len extra_len | name extra | data
+ *   directory     50 4B 01 02 | made need flags method time date | CRC-32 csize usize | name_len extra_len comment_len | disk
+ *                 attributes | local_off | name extra comment          (one record per entry, after the last entry's data)
+ *   end record    50 4B 05 06 | disks | entries | cd_size cd_off | comment; with saturated fields the ZIP64 end record
+ *                 (50 4B 06 06) and its locator (50 4B 06 07) stand in front of it
+ * THE READER.  The end record is the last position in the file's final 22 + 65535 bytes that holds the signature and whose
+ * comment ends the file; the directory is walked record by record from cd_off and must pass exactly `entries` records and end
+ * exactly where the (ZIP64) end record starts (archives with prepended data, multi-disk archives and a ZIP64 end record with
+ * an extensible data sector are Error).  An entry's sizes, CRC-32, method and flags are the directory's -- saturated sizes and
+ * offsets from its 0x0001 extra subfield -- so entries with a data descriptor need nothing special; its local header only
+ * places the data: data_off = local_off + 30 + the LOCAL header's name and extra lengths.
+ * info->status: 0; 5 (SrcTooSmall): src_n < 22; 1 (Error): every other structural failure.  With a non-zero status the counts
+ * are 0 and the table is not written.
+ * entry.status: 0; 5: the local header or [data_off, data_off + csize) reaches past cd_off; 1: no local signature, or a
+ * stored entry with csize != usize; SFH_ZIP_ENTRY_UNSUPPORTED -- a per-entry code, never a DecompressStatus, the counterpart of
+ * SFH_ITEM_NOT_INDEXABLE --: a method other than 0 and 8, or flag bit 0, 5, 6 or 13 (encryption, patch data).
+ * name_off: the name's position in the FILE (in the directory record).  out_off[i]: the running sum of (usize + 15) & ~15 --
+ * the packed layout in which every entry starts 16-byte aligned; total_out = its end.
+ * sfh_zip_read_index: host bytes, no context, no device.  SFH_E_DST_TOO_SMALL with the counts filled when cap < info->entries
+ *   (nothing else written); SFH_E_INVALID_ARG: a null pointer.
+ * sfh_zip_read_index_device: device bytes (d_src 4-byte aligned), the table on the HOST.  The file's tail (at most 22 + 65535 +
+ *   76 bytes), then the directory are copied down and walked there by the same code; the table goes up, k_zip_locals reads every
+ *   local header on the device, the table comes back: two synchronisations of `stream` (NULL = the ctx's own) when the directory
+ *   lies inside the tail, else three, whatever the archive holds.  The directory is a compact table at a stated place: there is no device walk of it ("ZIP"). */
+#define SFH_ZIP_ENTRY_UNSUPPORTED 0xFFFFFFF9u
+typedef struct sfh_zip_info {
+  uint64_t entries, cd_off, cd_size, total_out;
+  uint32_t zip64, status;
+} sfh_zip_info;
+typedef struct sfh_zip_entry { /* 64 bytes */
+  uint64_t local_off, data_off, csize, usize, out_off, name_off;
+  uint32_t crc32, status;
+  uint16_t method, flags, name_len, pad;
+} sfh_zip_entry;
+int sfh_zip_read_index(const void* src, size_t src_n, sfh_zip_info* info, sfh_zip_entry* entries, size_t cap);
+int sfh_zip_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sfh_zip_info* info, sfh_zip_entry* entries, size_t cap,
+                              void* stream);
+/* Decodes `count` entries of the file -- any subset of its index, in any order, an entry twice into two destinations if the
+ * caller likes -- entry i into d_dsts[i]; status[i] (host) is its DecompressStatus, or the entry's own non-zero index status,
+ * which it keeps.  No entry byte is copied or realigned on the way: an item of the decoders is the file with the entry's body
+ * range.  Method 0: k_zip_store, a gather copy in 16-byte stores.  Method 8: the index-free decoder of sfh_decompress_any_batch*
+ * (raw) -- every archive written here and every entry of at most 32 KiB takes it; an entry it finds not indexable goes through
+ * the stream decoder of sfh_inflate_stream_batch* with a capacity of usize, and so does an entry whose segments come up short
+ * of what usize promised.  A body that ends in order with fewer than usize bytes is 1 (Error); one that holds more than usize
+ * bytes is 4 (DstTooSmall: the serial decoder's status for a destination of usize bytes, and nothing is written behind them);
+ * usize above dst_cap[i] is 4 as well, and every entry that decoded has its CRC-32 computed on the device from its
+ * output and compared with the directory's: a mismatch is 1.  An empty entry's CRC-32 is 0.  The table is the caller's: an entry
+ * whose data range does not lie inside src_n is 5, and nothing of it is read; an entry of 4 GiB or more is
+ * SFH_ZIP_ENTRY_UNSUPPORTED here (the checksum fold counts an entry's bytes in 32 bits).
+ * One entry's failure changes no other entry's bytes or status; nothing is written outside [d_dsts[i], d_dsts[i] + dst_cap[i]),
+ * and for an entry that fails nothing is promised about its own destination.  Refused with SFH_E_INVALID_ARG before anything is
+ * enqueued: a null ctx; with count > 0 a null file or array, d_src not 4-byte or a destination not 16-byte aligned, a null
+ * destination with dst_cap > 0, overlapping destinations, more than 2^31 - 1 entries.  count == 0: SFH_OK.  Host
+ * synchronisations of `stream`: those of the two drivers (sfh_decompress_any_batch_device; sfh_inflate_stream_batch_device
+ * only when an entry needs it) and one for the checksums: not more with more entries.  Scratch: the drivers'.  Afterwards the ctx
+ * holds no index.  sfh_last_recover_stats / sfh_last_stream_stats describe the deflated entries' decode (zeros where a driver
+ * did not run).
+ * sfh_decompress_zip: host buffers; entries == NULL: the index is read here (sfh_zip_read_index) and entry i of it goes to
+ * dsts[i] (count must then be its entries; a file whose index fails gives every status that failure).  The file goes up whole,
+ * the entries are decoded into the packed layout of their rounded sizes and only those with status 0 are copied back. */
+int sfh_decompress_zip_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const sfh_zip_entry* entries, size_t count,
+                              void* const* d_dsts, const uint64_t* dst_cap, uint32_t* status, void* stream);
+int sfh_decompress_zip(sfh_ctx* ctx, const void* src, size_t src_n, const sfh_zip_entry* entries, size_t count, void* const* dsts,
+                       const uint64_t* dst_cap, uint32_t* status);
+/* THE WRITER: `count` items, each a deflated entry, in one archive that unzip and zipfile open.  Defining property: for every
+ * item, in order, the archive holds the local header -- version needed 20, flags 0x0800 (UTF-8 names), method 8, time 0, date
+ * 0x0021 (1980-01-01: deterministic, like gzip's MTIME 0), CRC-32, sizes, the name, no extra field -- followed byte for byte by
+ * what sfh_compress_batch writes for that item with container = SFH_RAW and the same options; then one directory record per item
+ * (version made by 20, no extra, no comment, attributes 0) and the 22-byte end record, with more than 65535 entries the ZIP64
+ * end record and locator (version needed 45) in front of it and the classic count saturated.
+ * The bodies are compressed one launch batch of whole items at a time (at most SFH_BATCH_CHUNKS chunks; a larger item alone)
+ * into context scratch of that batch's bound and packed behind each batch, so the scratch is one batch's.  The bound is per
+ * 32 KiB chunk, 37504 bytes, whatever an item holds: an item of one byte takes a slot of that size and two 32 KiB pieces of the
+ * pack's launch, so a launch batch of 32768 tiny items (thousands of scalars of an .npz) has 1.2 GB of scratch; SFH_BATCH_CHUNKS
+ * lowers it.
+ * opt: container must be SFH_RAW and final_stream 1; every strategy, effort, lazy, chain_depth and block_bytes of the batch call.
+ * SFH_E_INVALID_ARG before anything is enqueued: an empty name or one above 65535 bytes; an item of 2^32 - 1 bytes or more; local
+ * parts whose BOUNDS together reach 2^32 (offsets are not known before an asynchronous call, which cannot fail afterwards;
+ * ZIP64 offsets in the writer are out of scope); the batch call's own refusals (d_srcs 16-byte, d_dst 4-byte aligned).
+ * cap < sfh_zip_bound(...) is SFH_E_DST_TOO_SMALL.  sfh_zip_bound = the sum over the items of 30 + name_len + sfh_compress_bound(n,
+ * 0), plus the sum of 46 + name_len, plus 22 + 76 (0: the sum overflows).  count == 0 writes the 22-byte empty archive.
+ * Afterwards the ctx holds no index of either kind.
+ * sfh_compress_zip_device_async: the host arrays and the names are read before the call returns; *d_out_n (device) = the
+ * archive's bytes; the host does not wait for the stream (between two launch batches it waits, as the batch call does, for the
+ * previous batch's descriptor tables to have gone up).  sfh_compress_zip_device synchronises and returns the size;
+ * sfh_compress_zip takes host buffers, staged like sfh_compress_batch. */
+size_t sfh_zip_bound(size_t count, const uint64_t* src_n, const uint32_t* name_len);
+int sfh_compress_zip_device_async(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n,
+                                  const char* const* names, const uint32_t* name_len, void* d_dst, size_t cap, uint64_t* d_out_n,
+                                  const sfh_options* opt, void* stream);
+int sfh_compress_zip_device(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, const char* const* names,
+                            const uint32_t* name_len, void* d_dst, size_t cap, size_t* out_n, const sfh_options* opt, void* stream);
+int sfh_compress_zip(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, const char* const* names,
+                     const uint32_t* name_len, void* dst, size_t cap, size_t* out_n, const sfh_options* opt);
+
 /* ---- decoding without side information ----
  * The segment index of a stream that is flushed every 32 KiB of output -- every stream sfh_compress* writes, and zlib's with
  * Z_SYNC_FLUSH / Z_FULL_FLUSH every 32768 input bytes -- recovered from the stream itself: a coded segment ends with the empty

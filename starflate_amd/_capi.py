@@ -39,6 +39,8 @@ EXPORTS = [
     "sfh_bgzf_read_index", "sfh_bgzf_read_index_device", "sfh_decompress_bgzf_device", "sfh_decompress_bgzf",
     "sfh_decompress_bgzf_wide_device",
     "sfh_decompress_bgzf_ranges_device", "sfh_decompress_bgzf_ranges", "sfh_bgzf_voffsets_to_offsets", "sfh_bgzf_offsets_to_voffsets",
+    "sfh_zip_read_index", "sfh_zip_read_index_device", "sfh_decompress_zip_device", "sfh_decompress_zip", "sfh_zip_bound",
+    "sfh_compress_zip_device_async", "sfh_compress_zip_device", "sfh_compress_zip",
     "sfh_recover_index_device", "sfh_recover_index", "sfh_decompress_any_device", "sfh_decompress_any", "sfh_last_recover_stats",
     "sfh_recover_index_batch_device", "sfh_recover_index_batch", "sfh_decompress_any_batch_device", "sfh_decompress_any_batch",
     "sfh_inflate_stream_device", "sfh_inflate_stream", "sfh_inflate_stream_batch_device", "sfh_inflate_stream_batch",
@@ -64,6 +66,20 @@ class DzInfo(C.Structure):  # sfh_dz_info
 class BgzfInfo(C.Structure):  # sfh_bgzf_info
     _fields_ = [("total_n", C.c_uint64), ("members", C.c_uint32), ("max_isize", C.c_uint32), ("has_eof", C.c_uint32),
                 ("status", C.c_uint32)]
+
+
+class ZipInfo(C.Structure):  # sfh_zip_info
+    _fields_ = [("entries", C.c_uint64), ("cd_off", C.c_uint64), ("cd_size", C.c_uint64), ("total_out", C.c_uint64),
+                ("zip64", C.c_uint32), ("status", C.c_uint32)]
+
+
+class ZipEntry(C.Structure):  # sfh_zip_entry (64 bytes)
+    _fields_ = [("local_off", C.c_uint64), ("data_off", C.c_uint64), ("csize", C.c_uint64), ("usize", C.c_uint64),
+                ("out_off", C.c_uint64), ("name_off", C.c_uint64), ("crc32", C.c_uint32), ("status", C.c_uint32),
+                ("method", C.c_uint16), ("flags", C.c_uint16), ("name_len", C.c_uint16), ("pad", C.c_uint16)]
+
+
+ZIP_ENTRY_UNSUPPORTED = 0xFFFFFFF9  # SFH_ZIP_ENTRY_UNSUPPORTED: a per-entry status of the ZIP reader
 
 
 class DeviceProps(C.Structure):
@@ -150,6 +166,22 @@ def lib():
     L.sfh_bgzf_voffsets_to_offsets.restype = C.c_int
     L.sfh_bgzf_offsets_to_voffsets.argtypes = [vp, vp, C.c_uint32, sz, vp, vp]
     L.sfh_bgzf_offsets_to_voffsets.restype = C.c_int
+    L.sfh_zip_read_index.argtypes = [vp, sz, C.POINTER(ZipInfo), vp, sz]
+    L.sfh_zip_read_index.restype = C.c_int
+    L.sfh_zip_read_index_device.argtypes = [vp, vp, sz, C.POINTER(ZipInfo), vp, sz, vp]
+    L.sfh_zip_read_index_device.restype = C.c_int
+    L.sfh_decompress_zip_device.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp]
+    L.sfh_decompress_zip_device.restype = C.c_int
+    L.sfh_decompress_zip.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp]
+    L.sfh_decompress_zip.restype = C.c_int
+    L.sfh_zip_bound.argtypes = [sz, vp, vp]
+    L.sfh_zip_bound.restype = sz
+    L.sfh_compress_zip_device_async.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, C.POINTER(Options), vp]
+    L.sfh_compress_zip_device_async.restype = C.c_int
+    L.sfh_compress_zip_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, C.POINTER(sz), C.POINTER(Options), vp]
+    L.sfh_compress_zip_device.restype = C.c_int
+    L.sfh_compress_zip.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, C.POINTER(sz), C.POINTER(Options)]
+    L.sfh_compress_zip.restype = C.c_int
     L.sfh_compress.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]
     L.sfh_compress.restype = C.c_int
     L.sfh_compress_multi.argtypes = [C.POINTER(vp), C.c_int, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]

@@ -6,9 +6,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 # SFH_LIB=<path>: another build of the library (kernel experiments side by side: tools/exp/variants.sh)
 LIB_PATH = os.environ.get("SFH_LIB") or os.path.join(PKG_DIR, "libstarflate_hip.so")
-SOURCES = ["sf_kernels.hip", "sf_checksum.hip", "sf_inflate.hip", "sf_unindexed.hip", "sf_stream.hip", "sf_bgzf.hip", "sf_guard.hip", "sf_capi.hip"]
+SOURCES = ["sf_kernels.hip", "sf_checksum.hip", "sf_inflate.hip", "sf_unindexed.hip", "sf_stream.hip", "sf_bgzf.hip", "sf_zip.hip", "sf_guard.hip", "sf_capi.hip"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-Wall", "-Wextra", "-Werror"]
-HEADERS = [os.path.join(CSRC, "sf_device.h"), os.path.join(CSRC, "sf_inflate_core.h"), os.path.join(CSRC, "sf_stream_chain.h"), os.path.join(CSRC, "sf_stream_core.h"), os.path.join(CSRC, "sf_inflate_plan.h"), os.path.join(CSRC, "sf_any_plan.h"), os.path.join(CSRC, "sf_range_plan.h"), os.path.join(CSRC, "sf_dz_plan.h"), os.path.join(CSRC, "sf_bgzf_plan.h"), os.path.join(CSRC, "sf_bgzf_range_plan.h"), os.path.join(CSRC, "sf_stage_plan.h"),
+HEADERS = [os.path.join(CSRC, "sf_device.h"), os.path.join(CSRC, "sf_inflate_core.h"), os.path.join(CSRC, "sf_stream_chain.h"), os.path.join(CSRC, "sf_stream_core.h"), os.path.join(CSRC, "sf_inflate_plan.h"), os.path.join(CSRC, "sf_any_plan.h"), os.path.join(CSRC, "sf_range_plan.h"), os.path.join(CSRC, "sf_dz_plan.h"), os.path.join(CSRC, "sf_bgzf_plan.h"), os.path.join(CSRC, "sf_bgzf_range_plan.h"), os.path.join(CSRC, "sf_zip_plan.h"), os.path.join(CSRC, "sf_stage_plan.h"),
            os.path.join(os.path.dirname(PKG_DIR), "include", "starflate_hip.h")]
 
 

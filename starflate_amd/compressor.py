@@ -357,6 +357,122 @@ class Compressor:
         self._check(self._lib.sfh_copy_batch_index(self._h, idx.ctypes.data, sub.ctypes.data, bb.ctypes.data, 0, None))
         return idx, sub[: (e - k) * _capi.SUBINDEX_WORDS], bb[:k]
 
+    # ---- ZIP archives ----
+    @staticmethod
+    def zip_bound(sizes, name_lens):
+        return zip_bound(sizes, name_lens)
+
+    def compress_zip(self, items, strategy="auto", lazy=True, stored_fast_path=True, block_bytes=0, effort="default"):
+        """{name: bytes} or [(name, bytes)] -> one ZIP archive (bytes) of deflated entries, in that order; entry i's body is
+        byte for byte compress_batch(...)[i] with container="raw" and the same options."""
+        names, srcs = _zip_items(items)
+        k = len(srcs)
+        n = (C.c_uint64 * k)(*[a.size for a in srcs])
+        ln = (C.c_uint32 * k)(*[len(b) for b in names])
+        cap = self._lib.sfh_zip_bound(k, n, ln)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        sp = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a in srcs])
+        np_ = (C.c_char_p * k)(*names)
+        got = C.c_size_t()
+        opt = _capi.make_options(strategy, True, lazy, stored_fast_path, "raw", block_bytes, effort)
+        self._check(self._lib.sfh_compress_zip(self._h, k, sp, n, np_, ln, out.ctypes.data, cap, C.byref(got), C.byref(opt)))
+        return out[: got.value].tobytes()
+
+    def compress_zip_tensors(self, names, srcs, out=None, stream=None, strategy="auto", lazy=True, stored_fast_path=True,
+                             block_bytes=0, effort="default"):
+        """Device buffers: names (str or bytes) and 1-D uint8 tensors on this device -> (out, size).  Enqueued on `stream`
+        (default: the current one); size is an int64 tensor of one element on the device, valid once the stream gets there.
+        out defaults to a new tensor of zip_bound bytes."""
+        import torch
+
+        names = [b.encode("utf-8") if isinstance(b, str) else bytes(b) for b in names]
+        srcs = list(srcs)
+        if len(names) != len(srcs):
+            raise ValueError("one name per item")
+        for t in srcs:
+            self._check_tensor(t)
+        k = len(srcs)
+        dev = torch.device("cuda", self.device)
+        n = (C.c_uint64 * k)(*[t.numel() for t in srcs])
+        ln = (C.c_uint32 * k)(*[len(b) for b in names])
+        if out is None:
+            out = torch.empty(self._lib.sfh_zip_bound(k, n, ln), dtype=torch.uint8, device=dev)
+        self._check_tensor(out)
+        size = torch.empty(1, dtype=torch.int64, device=dev)
+        sp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in srcs])
+        np_ = (C.c_char_p * k)(*names)
+        opt = _capi.make_options(strategy, True, lazy, stored_fast_path, "raw", block_bytes, effort)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        self._check(self._lib.sfh_compress_zip_device_async(self._h, k, sp, n, np_, ln, C.c_void_p(out.data_ptr()), out.numel(),
+                                                            C.c_void_p(size.data_ptr()), C.byref(opt), C.c_void_p(s)))
+        return out, size
+
+    def zip_index_tensor(self, src, stream=None):
+        """The entry table of a ZIP archive on this device -> (info dict, entries): entries is a numpy structured array
+        (ZIP_ENTRY_DTYPE), on the host.  A file whose index fails: its status in info, no entries."""
+        import torch
+
+        self._check_tensor(src)
+        dev = torch.device("cuda", self.device)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        info = _capi.ZipInfo()
+        p = C.c_void_p(src.data_ptr()) if src.numel() else None
+        rc = self._lib.sfh_zip_read_index_device(self._h, p, src.numel(), C.byref(info), None, 0, C.c_void_p(s))
+        ents = np.zeros(info.entries, ZIP_ENTRY_DTYPE)
+        if rc == -2:
+            rc = self._lib.sfh_zip_read_index_device(self._h, p, src.numel(), C.byref(info), C.c_void_p(ents.ctypes.data), ents.size,
+                                                     C.c_void_p(s))
+        self._check(rc)
+        return _zip_info_dict(info), ents
+
+    def decompress_zip_tensors(self, src, entries, outs=None, stream=None):
+        """Entries (rows of a zip_index table, any subset in any order) of the archive `src` on this device -> (outs, statuses).
+        outs default to views of one packed buffer in which every entry starts 16-byte aligned (the layout of out_off for the
+        whole table); statuses: numpy uint32, 0 = decoded and its CRC-32 verified."""
+        import torch
+
+        self._check_tensor(src)
+        ents = np.ascontiguousarray(entries, dtype=ZIP_ENTRY_DTYPE).ravel()
+        k = ents.size
+        dev = torch.device("cuda", self.device)
+        if outs is None:
+            offs = np.concatenate([[0], np.cumsum((ents["usize"].astype(np.uint64) + np.uint64(15)) & ~np.uint64(15))]).astype(np.uint64)
+            buf = torch.empty(max(int(offs[-1]), 16), dtype=torch.uint8, device=dev)
+            outs = [buf[int(offs[i]): int(offs[i]) + int(ents["usize"][i])] for i in range(k)]
+        outs = list(outs)
+        if len(outs) != k:
+            raise ValueError("outs must hold one tensor per entry")
+        for t in outs:
+            self._check_tensor(t)
+        dp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in outs])
+        caps = (C.c_uint64 * k)(*[t.numel() for t in outs])
+        st = np.zeros(k, np.uint32)
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        self._check(self._lib.sfh_decompress_zip_device(self._h, C.c_void_p(src.data_ptr()) if src.numel() else None, src.numel(),
+                                                        C.c_void_p(ents.ctypes.data), k, dp, caps, C.c_void_p(st.ctypes.data), C.c_void_p(s)))
+        return outs, st
+
+    def decompress_zip(self, data, names=None):
+        """A ZIP archive (bytes-like) -> ({name: bytes}, statuses): every entry, or those called `names`; an entry whose
+        status is not 0 maps to None.  Raises StarflateError when the archive's index does not parse."""
+        src = _as_bytes(data)
+        info, ents = zip_index(src)
+        if info["status"]:
+            raise StarflateError(info["status"], f"ZIP index: DecompressStatus {info['status']}")
+        all_names = zip_names(src, ents)
+        if names is not None:
+            pick = [all_names.index(b if isinstance(b, str) else b.decode("utf-8")) for b in names]
+            ents = ents[pick]
+            all_names = [all_names[i] for i in pick]
+        k = ents.size
+        dsts = [np.empty(int(e["usize"]), dtype=np.uint8) for e in ents]
+        dp = (C.c_void_p * k)(*[d.ctypes.data if d.size else None for d in dsts])
+        caps = (C.c_uint64 * k)(*[d.size for d in dsts])
+        st = np.zeros(k, np.uint32)
+        self._check(self._lib.sfh_decompress_zip(self._h, src.ctypes.data, src.size, C.c_void_p(ents.ctypes.data), k, dp, caps,
+                                                 C.c_void_p(st.ctypes.data)))
+        return {nm: (d.tobytes() if not s else None) for nm, d, s in zip(all_names, dsts, st)}, st
+
     # ---- block index + GPU decompress (the reference's decompress(), /root/reference/src/decompress.hpp:63-71,
     #      for streams whose independently decodable 32 KiB segments are known) ----
     def last_block_bytes(self):
@@ -1342,6 +1458,66 @@ def decompress_bgzf(data, device=0):
     if st:
         raise StarflateError(st, f"DecompressStatus {st}")
     return out
+
+
+# ---- ZIP archives ----
+ZIP_ENTRY_UNSUPPORTED = _capi.ZIP_ENTRY_UNSUPPORTED  # a per-entry status: a method other than 0 and 8, or an encrypted entry
+ZIP_ENTRY_DTYPE = np.dtype([("local_off", "<u8"), ("data_off", "<u8"), ("csize", "<u8"), ("usize", "<u8"), ("out_off", "<u8"),
+                            ("name_off", "<u8"), ("crc32", "<u4"), ("status", "<u4"), ("method", "<u2"), ("flags", "<u2"),
+                            ("name_len", "<u2"), ("pad", "<u2")])  # sfh_zip_entry
+
+
+def _zip_items(items):
+    pairs = list(items.items()) if isinstance(items, dict) else list(items)
+    names = [b.encode("utf-8") if isinstance(b, str) else bytes(b) for b, _ in pairs]
+    return names, [_as_bytes(d) for _, d in pairs]
+
+
+def _zip_info_dict(info):
+    return {k: int(getattr(info, k)) for k, _ in info._fields_}
+
+
+def zip_bound(sizes, name_lens):
+    """sfh_zip_bound: the capacity compress_zip needs for items of these sizes and name lengths (bytes)"""
+    k = len(sizes)
+    return _capi.lib().sfh_zip_bound(k, (C.c_uint64 * k)(*[int(v) for v in sizes]), (C.c_uint32 * k)(*[int(v) for v in name_lens]))
+
+
+def zip_index(data):
+    """The entry table of a ZIP archive in host memory, no device: (info dict, entries as a ZIP_ENTRY_DTYPE array)."""
+    src = _as_bytes(data)
+    L = _capi.lib()
+    info = _capi.ZipInfo()
+    rc = L.sfh_zip_read_index(src.ctypes.data if src.size else None, src.size, C.byref(info), None, 0)
+    ents = np.zeros(info.entries, ZIP_ENTRY_DTYPE)
+    if rc == -2:
+        rc = L.sfh_zip_read_index(src.ctypes.data, src.size, C.byref(info), C.c_void_p(ents.ctypes.data), ents.size)
+    if rc:
+        raise StarflateError(rc, "sfh_zip_read_index")
+    return _zip_info_dict(info), ents
+
+
+def zip_names(data, entries):
+    """the entries' names (str: UTF-8 with flag bit 11, else CP437), read where the table says they stand in the file"""
+    src = _as_bytes(data)
+    return [src[int(e["name_off"]): int(e["name_off"]) + int(e["name_len"])].tobytes().decode("utf-8" if int(e["flags"]) & 0x800 else "cp437")
+            for e in entries]
+
+
+def compress_zip(items, device=0, **options):
+    """{name: bytes} or [(name, bytes)] -> a ZIP archive on the GPU (Compressor.compress_zip)."""
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    return c.compress_zip(items, **options)
+
+
+def decompress_zip(data, names=None, device=0):
+    """A ZIP archive -> ({name: bytes}, statuses) on the GPU (Compressor.decompress_zip)."""
+    c = _DEFAULT.get(device)
+    if c is None:
+        c = _DEFAULT[device] = Compressor(device)
+    return c.decompress_zip(data, names=names)
 
 
 def _as_bytes(data):

@@ -10,6 +10,7 @@
 #include "sf_inflate_plan.h"
 #include "sf_range_plan.h"
 #include "sf_stage_plan.h"
+#include "sf_zip_plan.h"
 
 #include <dlfcn.h>
 #include <stdio.h>
@@ -130,6 +131,16 @@ struct sfh_ctx {
   uint8_t* d_sbt = nullptr;
   uint8_t* d_sbr = nullptr;
   size_t d_sbt_cap = 0, d_sbr_cap = 0;
+  // ZIP (sfh_zip_read_index_device, sfh_decompress_zip*, sfh_compress_zip*), all on first use: the reader's tables (entry
+  // table; copy, piece, checksum and fold rows and the statuses); the writer's tables, pinned and on the device (ev_zip: the
+  // upload that reads the pinned ones), and the raw streams of one launch batch
+  uint8_t* d_zip = nullptr;
+  uint8_t* d_zipw = nullptr;
+  uint8_t* h_zipw = nullptr;
+  uint8_t* d_zipbody = nullptr;
+  size_t d_zip_cap = 0, d_zipw_cap = 0, h_zipw_cap = 0, d_zipbody_cap = 0;
+  hipEvent_t ev_zip = nullptr;
+  bool zipw_pending = false;
   char err[256] = {0};
 };
 
@@ -577,8 +588,10 @@ struct LaunchBatch {
 // Device buffers, arguments checked (check_batch).  The host builds the descriptor tables -- per strip, per chunk, per item
 // of a launch batch, and with a container per item of the call -- and uploads them in one copy; then every launch batch
 // runs k_lz77 .. k_emit over its rows, and with a container k_checksum / k_wrap run once over the call's rows.
+// crc_partials (raw items; sfh_compress_zip*): k_checksum leaves the CRC-32 partial of every chunk of the call in ws.sums, in
+// item order, and no wrapper is written.
 int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, void* const* d_dsts,
-                  uint64_t* d_out_n, const sfh_options* opt, hipStream_t s) {
+                  uint64_t* d_out_n, const sfh_options* opt, hipStream_t s, bool crc_partials = false) {
   sfh_options o;
   if (opt) o = *opt; else sfh_default_options(&o);
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
@@ -645,7 +658,7 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
   // the batch arrays hold the widest launch batch (at most a batch or a strip: ensure_compress_ws), the index arrays the call
   ctx->bix_valid = false;
   int rc = ensure_compress_ws(ctx, nchunks);
-  if (!rc && o.container) rc = ensure_sums(ctx, nchunks);
+  if (!rc && (o.container || crc_partials)) rc = ensure_sums(ctx, nchunks);
   if (!rc) rc = grow(ctx, &ctx->d_bix, &ctx->d_bix_cap, ((size_t)nchunks + count) * sizeof(uint64_t), "batch index");
   if (rc) return rc;
   const sf::Options ko = kernel_options(o, sf::kChunk);  // (strip_bytes: the strip table's)
@@ -701,6 +714,7 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
   }
   // (behind the launch batches and ahead of k_wrap_batch: d_out_n is still every stream's end before its trailer)
   SF_HIP(sf::launch_batch_index(d_chunks, d_ixrows, d_items, ctx->ws.offsets, d_out_n, nchunks, ctx->d_bix, s), "launch k_batch_index");
+  if (crc_partials) SF_HIP(sf::launch_checksum_batch(d_chunks, nchunks, SFH_GZIP, ctx->ws.sums, s), "launch k_checksum");
   if (o.container) {
     SF_HIP(sf::launch_checksum_batch(d_chunks, nchunks, o.container, ctx->ws.sums, s), "launch k_checksum");
     SF_HIP(sf::launch_wrap_batch(ctx->ws.sums, d_wraps, (uint32_t)count, o.container, d_out_n, s), "launch k_wrap");
@@ -1112,8 +1126,11 @@ struct AnyBatch {
 // segment, one walk over the concatenated node lists.  d_index: the flat index (zeroed first: the entries of an item that is
 // not indexable stay 0).  Synchronises s: after the wrappers only where ISIZE sizes the work, after the node count, after the
 // walk.  Arguments checked (check_any_batch; the single calls: check_any, check_any_waves).
+// bodies (raw items only; null: an item's body is all of it): every item's body [b0, e) inside its src_n bytes, two entries per
+// item, host memory that outlives the call's first synchronisation -- a ZIP entry's data inside the 4-byte aligned item around it.
 int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, uint32_t container,
-                      const uint64_t* dst_cap, const uint64_t* dst_n, uint64_t* d_index, hipStream_t s, AnyBatch& R) {
+                      const uint64_t* dst_cap, const uint64_t* dst_n, uint64_t* d_index, hipStream_t s, AnyBatch& R,
+                      const uint64_t* bodies = nullptr) {
   const bool prof = ctx->profiling != 0;
   ctx->any_ms[0] = ctx->any_ms[1] = 0;
   ctx->any_counts[0] = ctx->any_counts[1] = 0;
@@ -1181,6 +1198,7 @@ int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, con
     fill_scan_rows(ctx->h_tab + b_rows);
     if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
     SF_HIP(sf::launch_inflate_head((sf::InflateItem*)ctx->d_tab, (uint32_t)count, container, nullptr, nullptr, s), "launch k_inflate_head");
+    if (bodies) SF_HIP(hipMemcpyAsync(heads, bodies, 16 * count, hipMemcpyHostToDevice, s), "H2D bodies");  // (over the implied ones)
   } else {
     if ((rc = stage_tables(ctx, b_rows)) != SFH_OK) return rc;
     memcpy(ctx->h_tab, rows.data(), b_rows);
@@ -1399,7 +1417,8 @@ int check_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, cons
 // checksums.
 int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
                      void* const* dsts, const uint64_t* dst_cap, bool stage, std::vector<uint64_t>* out_off, uint64_t* dst_n_out,
-                     uint32_t* status, hipStream_t s) {
+                     uint32_t* status, hipStream_t s, const uint64_t* lead = nullptr) {
+  // lead (raw items only; null: none): bytes of item i in front of its body -- a ZIP entry's data inside the aligned item around it
   const bool prof = ctx->profiling != 0;
   for (float& m : ctx->stm_ms) m = 0;
   for (uint64_t& c : ctx->stm_counts) c = 0;
@@ -1454,11 +1473,11 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   uint64_t nc64 = 0;
   for (size_t i = 0; i < count; ++i) {
     if (container == SFH_RAW) {
-      if (src_n[i] == 0) {  // no header bits at all
+      if (src_n[i] == (lead ? lead[i] : 0)) {  // no header bits at all
         status[i] = sf::inflate::kInvalidBlockHeader;
         continue;
       }
-      body[2 * i] = 0;
+      body[2 * i] = lead ? lead[i] : 0;
       body[2 * i + 1] = src_n[i];
     } else if (head[i].wst) {
       status[i] = head[i].wst;
@@ -1940,6 +1959,11 @@ void sfh_destroy(sfh_ctx* ctx) {
   (void)hipFree(ctx->d_wins);
   (void)hipFree(ctx->d_sbt);
   (void)hipFree(ctx->d_sbr);
+  (void)hipFree(ctx->d_zip);
+  (void)hipFree(ctx->d_zipw);
+  (void)hipFree(ctx->d_zipbody);
+  if (ctx->h_zipw) (void)hipHostFree(ctx->h_zipw);
+  if (ctx->ev_zip) (void)hipEventDestroy(ctx->ev_zip);
   for (hipEvent_t e : ctx->ev_stm)
     if (e) (void)hipEventDestroy(e);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -2918,6 +2942,473 @@ int sfh_bgzf_offsets_to_voffsets(const uint64_t* member_off, const uint64_t* out
   if (!member_off || !out_off || (count && (!offsets || !voffsets))) return SFH_E_INVALID_ARG;
   for (size_t k = 0; k < count; ++k) voffsets[k] = sf::bgzf::offset_to_voffset(member_off, out_off, members, offsets[k]);
   return SFH_OK;
+}
+
+// ---- ZIP archives (sf_zip_plan.h, sf_zip.hip) ----
+static_assert(sizeof(sfh_zip_entry) == sizeof(sf::zip::Entry) && sizeof(sfh_zip_info) == sizeof(sf::zip::Info), "the plan's rows");
+
+int sfh_zip_read_index(const void* src, size_t src_n, sfh_zip_info* info, sfh_zip_entry* entries, size_t cap) {
+  if ((!src && src_n) || !info || (!entries && cap)) return SFH_E_INVALID_ARG;
+  return sf::zip::read_index((const uint8_t*)src, src_n, *(sf::zip::Info*)info, (sf::zip::Entry*)entries, cap);
+}
+
+int sfh_zip_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sfh_zip_info* info, sfh_zip_entry* entries, size_t cap,
+                              void* stream) {
+  if (!ctx) return SFH_E_INVALID_ARG;
+  if ((!d_src && src_n) || !info || (!entries && cap)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
+  if ((uintptr_t)d_src & 3) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4)", hipSuccess);
+  hipStream_t s;
+  int rc = begin_call(ctx, stream, &s);
+  if (rc) return rc;
+  namespace z = sf::zip;
+  z::Info& I = *(z::Info*)info;
+  I = z::Info{0, 0, 0, 0, 0, z::kStOk};
+  if (src_n < z::kEnd) {
+    I.status = z::kStSrcTooSmall;
+    return SFH_OK;
+  }
+  // (every return below that does not reach mark_call_end has either synchronised s or enqueued nothing on it)
+  if ((rc = order_behind_last_call(ctx, s))) return rc;
+  const uint8_t* file = (const uint8_t*)d_src;
+  std::vector<uint8_t> buf;
+  const size_t tail_n = std::min<size_t>(src_n, z::kTail);
+  try {
+    buf.resize(tail_n);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  SF_HIP(hipMemcpyAsync(buf.data(), file + (src_n - tail_n), tail_n, hipMemcpyDeviceToHost, s), "D2H the file's tail");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  z::End E;
+  if (z::read_end(buf.data(), tail_n, src_n, E) != z::kStOk) {
+    I.status = E.status;
+    return SFH_OK;
+  }
+  const uint8_t* cd = nullptr;  // the directory: inside the tail already, or copied down
+  if (E.cd_off >= src_n - tail_n) {
+    cd = buf.data() + (E.cd_off - (src_n - tail_n));
+  } else {
+    try {
+      buf.resize(E.cd_size);
+    } catch (...) {
+      return fail(ctx, SFH_E_NOMEM, "host memory for the directory", hipSuccess);
+    }
+    SF_HIP(hipMemcpyAsync(buf.data(), file + E.cd_off, E.cd_size, hipMemcpyDeviceToHost, s), "D2H the directory");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+    cd = buf.data();
+  }
+  uint64_t total = 0;
+  if (z::walk_central(cd, E.cd_size, E.cd_off, E.entries, nullptr, &total) != z::kStOk) {
+    I.status = z::kStError;
+    return SFH_OK;
+  }
+  I = z::Info{E.entries, E.cd_off, E.cd_size, total, E.zip64, z::kStOk};
+  if (cap < E.entries) return SFH_E_DST_TOO_SMALL;
+  if (E.entries == 0) return SFH_OK;
+  z::walk_central(cd, E.cd_size, E.cd_off, E.entries, (z::Entry*)entries, &total);
+  const size_t bytes = (size_t)E.entries * sizeof(z::Entry);
+  if ((rc = grow(ctx, &ctx->d_zip, &ctx->d_zip_cap, bytes, "entry table"))) return rc;
+  SF_HIP(hipMemcpyAsync(ctx->d_zip, entries, bytes, hipMemcpyHostToDevice, s), "H2D entry table");
+  SF_HIP(sf::launch_zip_locals(file, E.cd_off, (z::Entry*)ctx->d_zip, E.entries, s), "launch k_zip_locals");
+  SF_HIP(hipMemcpyAsync(entries, ctx->d_zip, bytes, hipMemcpyDeviceToHost, s), "D2H entry table");
+  if ((rc = mark_call_end(ctx, s))) return rc;
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  return SFH_OK;
+}
+
+namespace {
+// The decode of `count` entries of a device file into device destinations, arguments checked; statuses on the host.
+// Synchronises s.
+int zip_decode(sfh_ctx* ctx, const uint8_t* file, uint64_t src_n, const sfh_zip_entry* entries, size_t count, void* const* d_dsts,
+               const uint64_t* dst_cap, uint32_t* status, hipStream_t s) {
+  namespace z = sf::zip;
+  std::vector<sf::ZipCopy> copies;
+  std::vector<sf::ZipPiece> pieces;
+  std::vector<size_t> dfl;  // the deflated entries that go to the decoders, in call order
+  ctx->any_ms[0] = ctx->any_ms[1] = 0;
+  ctx->any_counts[0] = ctx->any_counts[1] = 0;
+  for (float& m : ctx->stm_ms) m = 0;
+  for (uint64_t& c : ctx->stm_counts) c = 0;
+  int rc = SFH_OK;
+  try {
+    uint64_t segs = 0, waves = 0, sum_rows = 0;
+    size_t live = 0;
+    for (size_t i = 0; i < count; ++i) {
+      const sfh_zip_entry& E = entries[i];
+      uint32_t st = E.status;
+      if (!st && E.method != 0 && E.method != 8) st = SFH_ZIP_ENTRY_UNSUPPORTED;
+      if (!st && (E.data_off > src_n || E.csize > src_n - E.data_off)) st = z::kStSrcTooSmall;
+      if (!st && E.method == 0 && E.csize != E.usize) st = z::kStError;
+      if (!st && E.usize > 0xFFFFFFFFull) st = SFH_ZIP_ENTRY_UNSUPPORTED;  // (the CRC-32 fold counts an entry's bytes in 32 bits)
+      if (!st && E.usize > dst_cap[i]) st = z::kStDstTooSmall;
+      status[i] = st;
+      if (st) continue;
+      ++live;
+      sum_rows += chunks_of((size_t)E.usize);
+      if (E.method == 0) {
+        const uint64_t np = (E.usize + z::kPiece - 1) / z::kPiece;
+        if (np > 0xFFFFFFFFull || copies.size() >= 0xFFFFFFFFull) return fail(ctx, SFH_E_INVALID_ARG, "too many pieces", hipSuccess);
+        for (uint64_t p = 0; p < np; ++p) pieces.push_back(sf::ZipPiece{(uint32_t)copies.size(), (uint32_t)p});
+        copies.push_back(sf::ZipCopy{file + E.data_off, (uint8_t*)d_dsts[i], E.usize});
+      } else {
+        dfl.push_back(i);
+        const uint32_t ns = chunks_of((size_t)E.usize);
+        segs += ns;
+        if (ns > 1) waves += ((E.data_off & 3) + E.csize + 8191) / 8192;
+      }
+    }
+    if (pieces.size() > 0x7FFFFFFFull || sum_rows > 0x7FFFFFFFull || segs > ((uint64_t)1 << 31) - 1 || waves > ((uint64_t)1 << 31) - 1)
+      return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 pieces, segments or scan waves in one call", hipSuccess);
+    if ((rc = order_behind_last_call(ctx, s))) return rc;
+    // one table for the call, sized before anything reads it: copy rows | piece rows | checksum rows | fold rows | statuses
+    const size_t b_copies = al16(copies.size() * sizeof(sf::ZipCopy)), b_pieces = al16(pieces.size() * sizeof(sf::ZipPiece));
+    const size_t o_sums = b_copies + b_pieces, o_fold = o_sums + al16((size_t)sum_rows * sizeof(sf::BatchChunk));
+    const size_t o_st = o_fold + al16(live * sizeof(sf::InflateItem));
+    if (ctx->d_zip_cap < o_st + 4 * live + 16 && ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");
+    if ((rc = grow(ctx, &ctx->d_zip, &ctx->d_zip_cap, o_st + 4 * live + 16, "ZIP decode rows"))) return rc;
+    uint8_t* T = ctx->d_zip;
+    // the stored entries: one gather copy (the rows are host vectors that live to the call's last synchronisation)
+    if (!copies.empty()) {
+      SF_HIP(hipMemcpyAsync(T, copies.data(), copies.size() * sizeof(sf::ZipCopy), hipMemcpyHostToDevice, s), "H2D copy rows");
+      SF_HIP(hipMemcpyAsync(T + b_copies, pieces.data(), pieces.size() * sizeof(sf::ZipPiece), hipMemcpyHostToDevice, s), "H2D piece rows");
+      SF_HIP(sf::launch_zip_store((const sf::ZipCopy*)T, (const sf::ZipPiece*)(T + b_copies), (uint32_t)pieces.size(), file, src_n, s),
+             "launch k_zip_store");
+    }
+    // the deflated entries: an item is the 4-byte aligned part of the file around the entry's data, its body the data
+    const size_t nd = dfl.size();
+    if (nd) {
+      std::vector<const void*> srcs(nd);
+      std::vector<void*> dsts(nd);
+      std::vector<uint64_t> sn(nd), un(nd), bodies(2 * nd), lead(nd), got(nd);
+      std::vector<uint32_t> st(nd);
+      for (size_t j = 0; j < nd; ++j) {
+        const sfh_zip_entry& E = entries[dfl[j]];
+        lead[j] = E.data_off & 3;
+        srcs[j] = file + (E.data_off - lead[j]);
+        sn[j] = lead[j] + E.csize;
+        un[j] = E.usize;
+        bodies[2 * j] = lead[j];
+        bodies[2 * j + 1] = sn[j];
+        dsts[j] = d_dsts[dfl[j]];
+      }
+      AnyBatch R;
+      if ((rc = any_batch_recover(ctx, nd, srcs.data(), sn.data(), SFH_RAW, un.data(), un.data(), nullptr, s, R, bodies.data()))) return rc;
+      if ((rc = any_batch_decode(ctx, nd, srcs.data(), sn.data(), SFH_RAW, dsts.data(), ctx->d_anyix, s, R))) return rc;
+      // what the walk could not index: the stream decoder, with a capacity of usize.  An entry whose segments came up short
+      // (SrcTooSmall: the index promised a segment more bytes than its blocks made) goes there as well -- a directory that states
+      // more bytes than the body holds is such an entry -- and gets the serial decoder's word on the body as a whole: a body that
+      // ends in order with other than usize bytes is Error, one that is cut short keeps SrcTooSmall.
+      std::vector<size_t> rest;
+      for (size_t j = 0; j < nd; ++j) {
+        status[dfl[j]] = R.st[j];
+        if (R.st[j] == SFH_ITEM_NOT_INDEXABLE || R.st[j] == z::kStSrcTooSmall) rest.push_back(j);
+      }
+      if (!rest.empty()) {
+        const size_t nr = rest.size();
+        uint64_t nc = 0;
+        for (size_t k = 0; k < nr; ++k) {
+          const size_t j = rest[k];
+          srcs[k] = srcs[j];
+          sn[k] = sn[j];
+          un[k] = un[j];
+          lead[k] = lead[j];
+          dsts[k] = dsts[j];
+          nc += (sn[k] + ctx->stream_chunk - 1) / ctx->stream_chunk + 1;
+        }
+        if (nc > ((uint64_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 nominal chunks (SFH_STREAM_CHUNK)", hipSuccess);
+        if ((rc = stream_batch_run(ctx, nr, srcs.data(), sn.data(), SFH_RAW, dsts.data(), un.data(), false, nullptr, got.data(), st.data(),
+                                   s, lead.data())))
+          return rc;
+        for (size_t k = 0; k < nr; ++k)
+          status[dfl[rest[k]]] = st[k] ? st[k] : got[k] != un[k] ? z::kStError : 0u;
+      }
+    }
+    // the CRC-32 of every entry that decoded: a partial per 32 KiB piece of its output, folded per entry against the directory's
+    std::vector<sf::BatchChunk> sums;
+    std::vector<sf::InflateItem> fold;
+    std::vector<size_t> fold_entry;
+    for (size_t i = 0; i < count; ++i) {
+      if (status[i]) continue;
+      const sfh_zip_entry& E = entries[i];
+      const uint32_t np = chunks_of((size_t)E.usize);
+      fold.push_back(sf::InflateItem{file, 0, E.usize, nullptr, nullptr, (uint32_t)sums.size(), 0, 0, E.crc32, (uint32_t)E.usize, 0});
+      fold_entry.push_back(i);
+      for (uint32_t p = 0; p < np; ++p) {
+        const uint64_t ob = (uint64_t)p * sf::kChunk;
+        // (an empty output: one empty row, at a real address)
+        sums.push_back(sf::BatchChunk{E.usize ? (const uint8_t*)d_dsts[i] + ob : file, (uint32_t)std::min<uint64_t>(sf::kChunk, E.usize - ob), 0u});
+      }
+    }
+    if (!fold.empty()) {
+      if ((rc = ensure_sums(ctx, (uint32_t)sums.size()))) return rc;
+      std::vector<uint32_t> fst(fold.size());
+      SF_HIP(hipMemcpyAsync(T + o_sums, sums.data(), sums.size() * sizeof(sf::BatchChunk), hipMemcpyHostToDevice, s), "H2D checksum rows");
+      SF_HIP(hipMemcpyAsync(T + o_fold, fold.data(), fold.size() * sizeof(sf::InflateItem), hipMemcpyHostToDevice, s), "H2D fold rows");
+      SF_HIP(sf::launch_checksum_batch((const sf::BatchChunk*)(T + o_sums), (uint32_t)sums.size(), SFH_GZIP, ctx->ws.sums, s), "launch k_checksum");
+      SF_HIP(sf::launch_inflate_fold((const sf::InflateItem*)(T + o_fold), (uint32_t)fold.size(), nullptr, ctx->ws.sums, SFH_GZIP,
+                                     (uint32_t*)(T + o_st), nullptr, s), "launch k_inflate_fold");
+      SF_HIP(hipMemcpyAsync(fst.data(), T + o_st, 4 * fold.size(), hipMemcpyDeviceToHost, s), "D2H checksums");
+      if ((rc = mark_call_end(ctx, s))) return rc;
+      SF_HIP(hipStreamSynchronize(s), "stream sync");
+      for (size_t f = 0; f < fold.size(); ++f) status[fold_entry[f]] = fst[f];
+    } else {
+      if ((rc = mark_call_end(ctx, s))) return rc;
+      SF_HIP(hipStreamSynchronize(s), "stream sync");
+    }
+  } catch (const std::bad_alloc&) {
+    (void)hipStreamSynchronize(s);
+    return fail(ctx, SFH_E_NOMEM, "host memory for the entry rows", hipSuccess);
+  }
+  ctx->index_valid = false;
+  ctx->bix_valid = false;
+  return SFH_OK;
+}
+
+int check_zip_decode(sfh_ctx* ctx, const void* src, size_t src_n, const sfh_zip_entry* entries, size_t count, void* const* dsts,
+                     const uint64_t* dst_cap, const uint32_t* status, bool dev) {
+  if (!ctx) return SFH_E_INVALID_ARG;
+  if (count == 0) return SFH_OK;
+  if ((!src && src_n) || (dev && !entries) || !dsts || !dst_cap || !status) return fail(ctx, SFH_E_INVALID_ARG, "null array", hipSuccess);
+  if (count > ((size_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "too many entries", hipSuccess);
+  if (dev && ((uintptr_t)src & 3)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4)", hipSuccess);
+  for (size_t i = 0; i < count; ++i) {
+    if (!dsts[i] && dst_cap[i]) return fail(ctx, SFH_E_INVALID_ARG, "null destination", hipSuccess);
+    if (dev && ((uintptr_t)dsts[i] & 15)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (dst 16)", hipSuccess);
+  }
+  return check_disjoint(ctx, dsts, dst_cap, count);
+}
+}  // namespace
+
+int sfh_decompress_zip_device(sfh_ctx* ctx, const void* d_src, size_t src_n, const sfh_zip_entry* entries, size_t count,
+                              void* const* d_dsts, const uint64_t* dst_cap, uint32_t* status, void* stream) {
+  int rc = check_zip_decode(ctx, d_src, src_n, entries, count, d_dsts, dst_cap, status, true);
+  if (rc || count == 0) return rc;
+  hipStream_t s;
+  if ((rc = begin_call(ctx, stream, &s))) return rc;
+  return zip_decode(ctx, (const uint8_t*)d_src, src_n, entries, count, d_dsts, dst_cap, status, s);
+}
+
+int sfh_decompress_zip(sfh_ctx* ctx, const void* src, size_t src_n, const sfh_zip_entry* entries, size_t count, void* const* dsts,
+                       const uint64_t* dst_cap, uint32_t* status) {
+  int rc = check_zip_decode(ctx, src, src_n, entries, count, dsts, dst_cap, status, false);
+  if (rc || count == 0) return rc;
+  std::vector<sfh_zip_entry> own;
+  std::vector<uint64_t> off, slot, got;
+  std::vector<void*> d_dsts;
+  try {
+    if (!entries) {  // walked here
+      sfh_zip_info info;
+      rc = sfh_zip_read_index(src, src_n, &info, nullptr, 0);
+      if (rc == SFH_OK && info.status) {
+        for (size_t i = 0; i < count; ++i) status[i] = info.status;
+        return SFH_OK;
+      }
+      if (info.entries != count) return fail(ctx, SFH_E_INVALID_ARG, "count is not the archive's number of entries", hipSuccess);
+      own.resize(count);
+      if ((rc = sfh_zip_read_index(src, src_n, &info, own.data(), count))) return fail(ctx, rc, "sfh_zip_read_index", hipSuccess);
+      entries = own.data();
+    }
+    off.resize(count + 1);
+    slot.resize(count);
+    got.resize(count);
+    d_dsts.resize(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
+  }
+  // every entry that can be decoded gets a slot of its size in the packed layout (sf_stage_plan.h); the others none
+  for (size_t i = 0; i < count; ++i)
+    slot[i] = (!entries[i].status && entries[i].usize <= dst_cap[i] && entries[i].usize <= 0xFFFFFFFFull) ? entries[i].usize : 0;
+  sf::stage::pack_layout(slot.data(), count, off.data());
+  if ((rc = host_up(ctx, src, src_n, (size_t)off[count]))) return rc;
+  if (!ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
+    ctx->h_stage = nullptr;
+    return fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
+  }
+  for (size_t i = 0; i < count; ++i) d_dsts[i] = ctx->d_out + off[i];
+  if ((rc = zip_decode(ctx, ctx->d_in, src_n, entries, count, d_dsts.data(), slot.data(), status, ctx->stream))) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  // (an entry without a slot: DstTooSmall against a capacity of 0 unless it had a status of its own; say what the caller's was)
+  uint64_t end = 0;
+  for (size_t i = 0; i < count; ++i) {
+    got[i] = (dsts[i] && !status[i]) ? entries[i].usize : 0;
+    if (got[i]) end = off[i] + got[i];
+  }
+  return stage_down(ctx, dsts, got.data(), off.data(), count, end, ctx->stream);
+}
+
+// ---- the writer ----
+size_t sfh_zip_bound(size_t count, const uint64_t* src_n, const uint32_t* name_len) {
+  if (count && (!src_n || !name_len)) return 0;
+  return (size_t)sf::zip::bound(count, src_n, name_len);
+}
+
+namespace {
+int check_zip_compress(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, const char* const* names,
+                       const uint32_t* name_len, const void* dst, size_t cap, const void* out_n, const sfh_options* opt, bool dev) {
+  if (!ctx) return SFH_E_INVALID_ARG;
+  if (check_opt(opt) || (opt && (opt->container != SFH_RAW || opt->final_stream != 1)))
+    return fail(ctx, SFH_E_INVALID_ARG, "ZIP: container SFH_RAW, final_stream 1", hipSuccess);
+  if (!dst || !out_n || (count && (!srcs || !src_n || !names || !name_len))) return fail(ctx, SFH_E_INVALID_ARG, "null array", hipSuccess);
+  if (dev && ((uintptr_t)dst & 3)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (dst 4)", hipSuccess);
+  if (count > ((size_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "too many items", hipSuccess);
+  uint64_t chunks = 0, locals = 0, dir = 0;
+  for (size_t i = 0; i < count; ++i) {
+    if ((!srcs[i] && src_n[i]) || !names[i]) return fail(ctx, SFH_E_INVALID_ARG, "null item pointer", hipSuccess);
+    if (dev && ((uintptr_t)srcs[i] & 15)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 16)", hipSuccess);
+    if (name_len[i] == 0 || name_len[i] > 65535) return fail(ctx, SFH_E_INVALID_ARG, "a name of 1 to 65535 bytes", hipSuccess);
+    if (src_n[i] >= sf::zip::kMaxItem) return fail(ctx, SFH_E_INVALID_ARG, "an item of 2^32 - 1 bytes or more (ZIP64 sizes: out of scope)", hipSuccess);
+    chunks += chunks_of((size_t)src_n[i]);
+    locals += sf::zip::kLocal + name_len[i] + sf::zip::body_bound(src_n[i]);
+    dir += sf::zip::kCentral + name_len[i];
+    if (locals + dir >= ((uint64_t)1 << 32))
+      return fail(ctx, SFH_E_INVALID_ARG, "the local parts' bounds and the directory reach 2^32 (ZIP64 offsets: out of scope)", hipSuccess);
+  }
+  if (chunks > ((uint64_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 chunks in one call", hipSuccess);
+  if (cap < sfh_zip_bound(count, src_n, name_len)) return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < sfh_zip_bound", hipSuccess);
+  return SFH_OK;
+}
+
+// Device buffers, arguments checked.  The tables -- item rows, the fold's rows, the pieces of every item's bound, the names -- are
+// built in pinned memory and go up with one copy; then launch batch after launch batch: the batch call's kernels into the
+// scratch slots (enqueue_batch, with the CRC-32 partials), the fold, the scan of the local parts, the pack; then the directory.
+int enqueue_zip(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, const char* const* names,
+                const uint32_t* name_len, uint8_t* d_dst, uint64_t* d_out_n, const sfh_options* opt, hipStream_t s) {
+  namespace z = sf::zip;
+  SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+  (void)hipGetLastError();
+  struct Group {
+    size_t i0, i1, p0, p1;
+    uint64_t slots;
+  };
+  std::vector<Group> groups;
+  std::vector<sf::ZipItem> items;
+  std::vector<sf::WrapItem> wraps;
+  std::vector<sf::ZipPiece> pieces;
+  std::vector<void*> slot_ptr;
+  uint64_t names_n = 0, widest = 16;
+  try {
+    items.resize(count);
+    wraps.resize(count);
+    slot_ptr.resize(count);
+    Group g{0, 0, 0, 0, 0};
+    uint32_t gchunks = 0;
+    auto close = [&](size_t i) {
+      if (i > g.i0) {
+        g.i1 = i;
+        g.p1 = pieces.size();
+        groups.push_back(g);
+        widest = std::max(widest, g.slots);
+      }
+      g = Group{i, i, pieces.size(), pieces.size(), 0};
+      gchunks = 0;
+    };
+    for (size_t i = 0; i < count; ++i) {
+      const uint32_t nc = chunks_of((size_t)src_n[i]);
+      if (gchunks && gchunks + nc > ctx->batch_chunks) close(i);
+      const uint64_t b = z::body_bound(src_n[i]);
+      items[i] = sf::ZipItem{names_n, g.slots, b, name_len[i], (uint32_t)src_n[i]};
+      wraps[i] = sf::WrapItem{nullptr, src_n[i], (uint32_t)i, gchunks, nc, 0};
+      for (uint64_t p = 0; p < (b + z::kPiece - 1) / z::kPiece; ++p) pieces.push_back(sf::ZipPiece{(uint32_t)i, (uint32_t)p});
+      g.slots += b;  // (a multiple of 16: every slot starts 16-byte aligned)
+      gchunks += nc;
+      names_n += name_len[i];
+    }
+    close(count);
+  } catch (...) {
+    return fail(ctx, SFH_E_NOMEM, "host memory for the descriptor tables", hipSuccess);
+  }
+  // uploaded: items | wraps | pieces | names; device only: out_n u64[count] | off u64[count] | carry u64 | crc u32[count]
+  const size_t o_wraps = count * sizeof(sf::ZipItem), o_pieces = o_wraps + count * sizeof(sf::WrapItem);
+  const size_t o_names = o_pieces + pieces.size() * sizeof(sf::ZipPiece), up = al16(o_names + names_n);
+  const size_t o_outn = up, o_off = o_outn + 8 * count, o_carry = o_off + 8 * count, o_crc = o_carry + 16, bytes = o_crc + 4 * count + 16;
+  if (!ctx->ev_zip) SF_HIP(hipEventCreateWithFlags(&ctx->ev_zip, hipEventDisableTiming), "event");
+  if (ctx->zipw_pending) SF_HIP(hipEventSynchronize(ctx->ev_zip), "wait for the previous call's table copy");  // (it reads h_zipw)
+  ctx->zipw_pending = false;
+  if (ctx->h_zipw_cap < up) {
+    if (ctx->h_zipw) (void)hipHostFree(ctx->h_zipw);
+    ctx->h_zipw = nullptr;
+    ctx->h_zipw_cap = 0;
+    if (hipHostMalloc((void**)&ctx->h_zipw, up, hipHostMallocDefault) != hipSuccess) return fail(ctx, SFH_E_NOMEM, "pinned ZIP tables", hipSuccess);
+    ctx->h_zipw_cap = up;
+  }
+  if ((ctx->d_zipw_cap < bytes || ctx->d_zipbody_cap < widest) && ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");
+  int rc = grow(ctx, &ctx->d_zipw, &ctx->d_zipw_cap, bytes, "ZIP tables");
+  if (!rc) rc = grow(ctx, &ctx->d_zipbody, &ctx->d_zipbody_cap, widest, "ZIP body scratch");
+  if (rc) return rc;
+  memcpy(ctx->h_zipw, items.data(), count * sizeof(sf::ZipItem));
+  memcpy(ctx->h_zipw + o_wraps, wraps.data(), count * sizeof(sf::WrapItem));
+  memcpy(ctx->h_zipw + o_pieces, pieces.data(), pieces.size() * sizeof(sf::ZipPiece));
+  for (size_t i = 0; i < count; ++i) memcpy(ctx->h_zipw + o_names + items[i].name_off, names[i], name_len[i]);
+  uint8_t* T = ctx->d_zipw;
+  const sf::ZipItem* t_items = (const sf::ZipItem*)T;
+  const sf::WrapItem* t_wraps = (const sf::WrapItem*)(T + o_wraps);
+  const sf::ZipPiece* t_pieces = (const sf::ZipPiece*)(T + o_pieces);
+  uint64_t* t_outn = (uint64_t*)(T + o_outn);
+  uint64_t* t_off = (uint64_t*)(T + o_off);
+  uint64_t* t_carry = (uint64_t*)(T + o_carry);
+  uint32_t* t_crc = (uint32_t*)(T + o_crc);
+  if ((rc = order_behind_last_call(ctx, s))) return rc;
+  if (up) {
+    SF_HIP(hipMemcpyAsync(T, ctx->h_zipw, up, hipMemcpyHostToDevice, s), "ZIP tables");
+    SF_HIP(hipEventRecord(ctx->ev_zip, s), "event");
+    ctx->zipw_pending = true;
+  }
+  SF_HIP(hipMemsetAsync(t_carry, 0, 16, s), "clear the carry");
+  if ((rc = mark_call_end(ctx, s))) return rc;  // (the batch calls below take their place behind this on s)
+  for (const Group& g : groups) {
+    const size_t n = g.i1 - g.i0;
+    for (size_t i = g.i0; i < g.i1; ++i) slot_ptr[i] = ctx->d_zipbody + items[i].slot_off;
+    if ((rc = enqueue_batch(ctx, n, d_srcs + g.i0, src_n + g.i0, slot_ptr.data() + g.i0, t_outn + g.i0, opt, s, true))) return rc;
+    SF_HIP(sf::launch_crc_items(ctx->ws.sums, t_wraps + g.i0, (uint32_t)n, t_crc, s), "launch k_crc_items");
+    SF_HIP(sf::launch_zip_place(t_items + g.i0, t_outn + g.i0, (uint32_t)n, t_off + g.i0, t_carry, s), "launch k_zip_place");
+    SF_HIP(sf::launch_zip_pack(t_items, t_pieces + g.p0, (uint32_t)(g.p1 - g.p0), T + o_names, t_outn, t_off, t_crc, ctx->d_zipbody,
+                               d_dst, s), "launch k_zip_pack");
+  }
+  SF_HIP(sf::launch_zip_wrap(t_items, T + o_names, t_outn, t_off, t_crc, count, names_n, t_carry, d_dst, d_out_n, s), "launch k_zip_wrap");
+  ctx->index_valid = false;
+  ctx->bix_valid = false;
+  return mark_call_end(ctx, s);
+}
+}  // namespace
+
+int sfh_compress_zip_device_async(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n,
+                                  const char* const* names, const uint32_t* name_len, void* d_dst, size_t cap, uint64_t* d_out_n,
+                                  const sfh_options* opt, void* stream) {
+  const int rc = check_zip_compress(ctx, count, d_srcs, src_n, names, name_len, d_dst, cap, d_out_n, opt, true);
+  if (rc) return rc;
+  return enqueue_zip(ctx, count, d_srcs, src_n, names, name_len, (uint8_t*)d_dst, d_out_n, opt, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int sfh_compress_zip_device(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uint64_t* src_n, const char* const* names,
+                            const uint32_t* name_len, void* d_dst, size_t cap, size_t* out_n, const sfh_options* opt, void* stream) {
+  int rc = check_zip_compress(ctx, count, d_srcs, src_n, names, name_len, d_dst, cap, out_n, opt, true);
+  if (rc) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+  if ((rc = enqueue_zip(ctx, count, d_srcs, src_n, names, name_len, (uint8_t*)d_dst, ctx->d_total, opt, s))) return rc;
+  SF_HIP(hipMemcpyAsync(ctx->h_total, ctx->d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "copy size");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  *out_n = (size_t)*ctx->h_total;
+  return SFH_OK;
+}
+
+int sfh_compress_zip(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, const char* const* names,
+                     const uint32_t* name_len, void* dst, size_t cap, size_t* out_n, const sfh_options* opt) {
+  int rc = check_zip_compress(ctx, count, srcs, src_n, names, name_len, dst, cap, out_n, opt, false);
+  if (rc) return rc;
+  Staged B;
+  hipStream_t s = ctx->stream;
+  if ((rc = staged_up(ctx, B, count, srcs, src_n, nullptr))) return rc;
+  if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, sfh_zip_bound(count, src_n, name_len), "output staging"))) return rc;
+  if ((rc = enqueue_zip(ctx, count, B.d_srcs.data(), src_n, names, name_len, ctx->d_out, ctx->d_total, opt, s))) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  SF_HIP(hipMemcpyAsync(ctx->h_total, ctx->d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "copy size");
+  SF_HIP(hipStreamSynchronize(s), "stream sync");
+  *out_n = (size_t)*ctx->h_total;
+  return host_down(ctx, dst, *out_n);
 }
 
 int sfh_recover_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint32_t container, uint64_t dst_n, uint64_t* d_index,

@@ -396,6 +396,13 @@ __global__ __launch_bounds__(KW_THREADS) void k_wrap_batch(const uint32_t* __res
   wrap_stream(sums + I.sum0, I.nchunks, I.n, kind, I.dst, total + I.out, nullptr, chunk_op);
 }
 
+// sfh_compress_zip*: the fold alone, one workgroup per item of a launch batch: the item's CRC-32 into crc[item.out]
+__global__ __launch_bounds__(KW_THREADS) void k_crc_items(const uint32_t* __restrict__ sums, const WrapItem* __restrict__ items,
+                                                          uint32_t* __restrict__ crc, uint32_t chunk_op) {
+  const WrapItem I = items[blockIdx.x];
+  wrap_stream(sums + I.sum0, I.nchunks, I.n, kChecksumCrc32, nullptr, nullptr, crc + I.out, chunk_op);
+}
+
 // ---- sfh_decompress_batch*: the wrappers of the items, and every item's status ----
 // the reference's DecompressStatus values these kernels produce themselves (src/decompress.hpp:13-23)
 constexpr uint32_t kStOk = 0, kStError = 1, kStSrcTooSmall = 5;
@@ -539,6 +546,11 @@ __global__ __launch_bounds__(KW_THREADS) void k_inflate_fold_wide(const InflateI
 }
 
 }  // namespace
+
+hipError_t launch_crc_items(const uint32_t* sums, const WrapItem* items, uint32_t nitems, uint32_t* crc, hipStream_t s) {
+  hipLaunchKernelGGL(k_crc_items, dim3(nitems), dim3(KW_THREADS), 0, s, sums, items, crc, kChunkOp);
+  return hipGetLastError();
+}
 
 hipError_t launch_inflate_head(InflateItem* items, uint32_t nitems, uint32_t container, InflateSeg* segs, BatchChunk* sums,
                                hipStream_t s) {

@@ -390,6 +390,8 @@ hipError_t launch_bgzf_range_rows(const BgzfRange* ranges, uint32_t n, const uin
 // planner marked failed
 hipError_t launch_bgzf_fold_spans(const InflateSpan* spans, uint32_t n, const uint32_t* plan, const SegInfo* info, const uint32_t* wst,
                                   uint32_t* status, hipStream_t s);
+// the batched fold alone (sfh_compress_zip*): crc[items[i].out] = the CRC-32 of item i from its chunks' partials
+hipError_t launch_crc_items(const uint32_t* sums, const WrapItem* items, uint32_t nitems, uint32_t* crc, hipStream_t s);
 hipError_t launch_checksum_batch_any(const BatchChunk* chunks, uint32_t nchunks, uint32_t* sums, hipStream_t s);  // CRC-32, any alignment
 // batched: sums[c] for the call's chunk table; one k_wrap workgroup per item (header at dst, trailer at d_total[out])
 hipError_t launch_checksum_batch(const BatchChunk* chunks, uint32_t nchunks, uint32_t kind, uint32_t* sums, hipStream_t s);
@@ -506,6 +508,39 @@ uint32_t stream_group(uint32_t n);  // chunks per group of the resolve; an item'
 hipError_t launch_stream_resolve(const uint16_t* plane, const StreamChunk* recs, const StreamItem* items,
                                  const StreamGroup* compose, uint32_t ncompose, const uint32_t* link, uint32_t nlink,
                                  const StreamGroup* resolve, uint32_t nresolve, uint16_t* tables, hipStream_t s);
+
+// sf_zip.hip: ZIP archives (sf_zip_plan.h; sfh_zip_read_index_device, sfh_decompress_zip*, sfh_compress_zip*)
+namespace zip {
+struct Entry;
+}
+struct ZipCopy {         // per stored entry of a decode call
+  const uint8_t* src;    // its data in the file (any alignment)
+  uint8_t* dst;          // 16-byte aligned
+  uint64_t n;
+};
+struct ZipPiece {        // per workgroup of a copy: 32 KiB piece `piece` of row `row`
+  uint32_t row, piece;
+};
+struct ZipItem {         // per item of a compress call
+  uint64_t name_off;     // its name in the names' bytes: the sum of the name lengths before it
+  uint64_t slot_off;     // its raw stream's slot in the scratch of its launch batch (16-byte aligned), and the slot's bytes
+  uint64_t slot_n;
+  uint32_t name_len, usize;
+};
+static_assert(sizeof(ZipCopy) == 24 && sizeof(ZipPiece) == 8 && sizeof(ZipItem) == 32, "ZIP descriptor rows");
+// one lane per entry: parse_local on the file's first `limit` bytes (the directory's first byte)
+hipError_t launch_zip_locals(const uint8_t* src, uint64_t limit, zip::Entry* entries, uint64_t n, hipStream_t s);
+// the stored entries' copy; file, file_n: what may be loaded around a source (the file up to its last byte's dword)
+hipError_t launch_zip_store(const ZipCopy* rows, const ZipPiece* pieces, uint32_t npieces, const uint8_t* file, uint64_t file_n,
+                            hipStream_t s);
+// the writer, behind a launch batch of n items: off[i] = where item i's local header goes (*carry: the end of the batches before,
+// moved on to this one's end); the pieces of the items' bounds, each copied as far as its stream reaches; and behind the last
+// batch the directory, the end record(s) and *total
+hipError_t launch_zip_place(const ZipItem* items, const uint64_t* out_n, uint32_t n, uint64_t* off, uint64_t* carry, hipStream_t s);
+hipError_t launch_zip_pack(const ZipItem* items, const ZipPiece* pieces, uint32_t npieces, const uint8_t* names, const uint64_t* out_n,
+                           const uint64_t* off, const uint32_t* crc, const uint8_t* slots, uint8_t* dst, hipStream_t s);
+hipError_t launch_zip_wrap(const ZipItem* items, const uint8_t* names, const uint64_t* out_n, const uint64_t* off, const uint32_t* crc,
+                           uint64_t n, uint64_t names_n, const uint64_t* carry, uint8_t* dst, uint64_t* total, hipStream_t s);
 
 // sf_guard.hip: does the LDS execute a returning atomic's lanes in ascending order (op 0: ds_wrxchg_rtn_b32, 1: ds_mskor_rtn_b32)?
 // d_result[0] = mismatches against the sequential model, [1] = positions checked
