@@ -8,8 +8,8 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("SFH_LIB") or os.path.join(PKG_DIR, "libstarflate_hip.so")
 SOURCES = ["sf_kernels.hip", "sf_checksum.hip", "sf_inflate.hip", "sf_unindexed.hip", "sf_stream.hip", "sf_bgzf.hip", "sf_zip.hip", "sf_guard.hip", "sf_capi.hip"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-Wall", "-Wextra", "-Werror"]
-HEADERS = [os.path.join(CSRC, "sf_device.h"), os.path.join(CSRC, "sf_inflate_core.h"), os.path.join(CSRC, "sf_stream_chain.h"), os.path.join(CSRC, "sf_stream_core.h"), os.path.join(CSRC, "sf_inflate_plan.h"), os.path.join(CSRC, "sf_any_plan.h"), os.path.join(CSRC, "sf_range_plan.h"), os.path.join(CSRC, "sf_dz_plan.h"), os.path.join(CSRC, "sf_bgzf_plan.h"), os.path.join(CSRC, "sf_bgzf_range_plan.h"), os.path.join(CSRC, "sf_zip_plan.h"), os.path.join(CSRC, "sf_stage_plan.h"),
-           os.path.join(os.path.dirname(PKG_DIR), "include", "starflate_hip.h")]
+# every header of csrc and the C-ABI header (what source_stamp() hashes): a header missing here would let needs_build() serve a stale library
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(os.path.dirname(PKG_DIR), "include", "starflate_hip.h")]
 
 
 def hipcc():

@@ -1,5 +1,8 @@
 // sf_capi.hip -- the C-ABI of include/starflate_hip.h over the kernels of sf_kernels.hip.
-// No torch types, no exceptions across the boundary; a ctx owns its device scratch.
+// No torch types, no exceptions across the boundary.  A ctx owns its device scratch: every buffer, pinned block, event and stream
+// below is a member that frees itself (sf_scratch.h), so sfh_destroy deletes the context and nothing else; one device buffer that
+// holds several arrays is laid out with sf::stage::Carve (sf_stage_plan.h).  The compressor's workspace (sf::Workspace: the
+// kernels' interface) stays raw pointers behind ensure_compress_ws / free_compress_ws, ensure_dtok and ensure_sums.
 #include "../../include/starflate_hip.h"
 #include "sf_any_plan.h"
 #include "sf_bgzf_plan.h"
@@ -9,6 +12,7 @@
 #include "sf_inflate_core.h"
 #include "sf_inflate_plan.h"
 #include "sf_range_plan.h"
+#include "sf_scratch.h"
 #include "sf_stage_plan.h"
 #include "sf_zip_plan.h"
 
@@ -22,9 +26,21 @@
 #include <thread>
 #include <vector>
 
+namespace {
+using sf::scratch::Buf;
+using sf::scratch::Event;
+using sf::scratch::Pair;
+using sf::scratch::Pinned;
+using sf::scratch::Stager;
+using sf::scratch::Stream;
+using sf::stage::al16;
+using sf::stage::Carve;
+void free_compress_ws(sfh_ctx* c);
+}  // namespace
+
 struct sfh_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;  // used when the caller passes no stream
+  Stream stream;                 // used when the caller passes no stream (declared first: destroyed behind every buffer and event)
   sf::Workspace ws{};
   uint32_t cap_chunks = 0;       // chunks of a call the compressor's index arrays (ws.offsets, ws.subidx) can hold
   uint32_t cap_batch = 0;        // chunks the compressor's batch arrays can hold
@@ -34,134 +50,108 @@ struct sfh_ctx {
   uint32_t last_chunks = 0;
   uint32_t last_block_bytes = 0; // strip size the last compress call used
   bool index_valid = false;      // ws.offsets holds the index of the last compress call
-  uint64_t* d_total = nullptr;   // own result slot for the synchronous entry points
-  uint64_t* h_total = nullptr;   // ... and the pinned word it is copied to (a pageable target is staged by the runtime)
-  uint32_t* d_value = nullptr;   // result slot of sfh_checksum_device; [2] for the decoder's status
-  sf::DzInfo* d_dzinfo = nullptr; // result slot of sfh_dz_read_index_device (on first use)
+  Buf<uint64_t> d_total;         // own result slot for the synchronous entry points
+  Pinned<uint64_t> h_total;      // ... and the pinned word it is copied to (a pageable target is staged by the runtime)
+  Buf<uint32_t> d_value;         // result slot of sfh_checksum_device; [2] for the decoder's status
+  Buf<sf::DzInfo> d_dzinfo;      // result slot of sfh_dz_read_index_device (on first use)
   // BGZF read (sfh_bgzf_read_index_device, sfh_decompress_bgzf_device), all on first use: the info slot; the scan's counts,
   // their scan and its scratch; the walk's node arrays; the decoder's own index; its rows, implied entries and statuses
-  sf::BgzfInfo* d_bgzfinfo = nullptr;
-  uint8_t* d_bgzfcnt = nullptr;
-  uint8_t* d_bgzfwalk = nullptr;
-  uint64_t* d_bgzfix = nullptr;
-  uint8_t* d_bgzfrows = nullptr;
-  uint8_t* d_bgzfrng = nullptr;  // sfh_decompress_bgzf_ranges*: the planner's per-range arrays (the rows: d_bgzfrows)
-  size_t d_bgzfcnt_cap = 0, d_bgzfwalk_cap = 0, d_bgzfix_cap = 0, d_bgzfrows_cap = 0, d_bgzfrng_cap = 0;
-  uint64_t* d_index = nullptr;   // staging for the host-buffer decoder
-  size_t d_index_cap = 0;
-  uint32_t* d_sub = nullptr;
-  size_t d_sub_cap = 0;
+  Buf<sf::BgzfInfo> d_bgzfinfo;
+  Buf<uint32_t> d_bgzfcnt;
+  Buf<uint8_t> d_bgzfwalk;
+  Buf<uint64_t> d_bgzfix;
+  Buf<uint8_t> d_bgzfrows;
+  Buf<uint8_t> d_bgzfrng;        // sfh_decompress_bgzf_ranges*: the planner's per-range arrays (the rows: d_bgzfrows)
+  Buf<uint64_t> d_index;         // staging for the host-buffer decoder
+  Buf<uint32_t> d_sub;
   // per-stage events of the last profiled decode call: SFH_INFLATE_NSTAGES + 1 per batch, grown on demand
-  std::vector<hipEvent_t> ev_inf;
+  std::vector<Event> ev_inf;
   uint32_t ev_inf_batches = 0;
   bool ev_inf_valid = false;
   size_t last_dtok_bytes = 0;    // bytes of decoder token scratch the last decode call used (bounded: one batch)
-  uint8_t* d_in = nullptr;       // staging for the host-buffer entry points (capacities in bytes): host_up, staged_up
-  uint8_t* d_out = nullptr;
-  size_t d_in_cap = 0, d_out_cap = 0;
+  Buf<uint8_t> d_in;             // staging for the host-buffer entry points: host_up, staged_up
+  Buf<uint8_t> d_out;
   int profiling = 0;
   int k1_stamps = 0;  // SFH_K1_STAMPS=1: diagnostic k_lz77 build with s_memtime stamps
   uint32_t batch_chunks = sf::kBatchChunks;  // SFH_BATCH_CHUNKS=<n>: smaller batches (tests of the batch loop)
   // per-kernel events of the last profiled call: kEvPerBatch per batch (before k_lz77, k_plan, k_scan, k_emit and after
   // k_emit), then one after the container kernels; grown on demand, reused by later calls
   static constexpr int kEvPerBatch = 5;
-  std::vector<hipEvent_t> ev;
+  std::vector<Event> ev;
   uint32_t ev_batches = 0;       // batches the last profiled call recorded
   bool ev_valid = false;
   // host-buffer path (sfh_compress): copies of one batch run beside the kernels of its neighbours
   static constexpr int kPipe = 4;
-  hipStream_t s_in = nullptr, s_out = nullptr;
-  hipEvent_t ev_in[kPipe] = {}, ev_batch[kPipe] = {};
-  uint64_t* h_tot = nullptr;     // pinned: the stream's end after each batch in flight
-  hipEvent_t ev_done = nullptr;  // end of the last call's device work: the next call, on any stream, starts behind it
+  Stream s_in, s_out;
+  Event ev_in[kPipe], ev_batch[kPipe];
+  Pinned<uint64_t> h_tot;        // the stream's end after each batch in flight
+  Event ev_done;                 // end of the last call's device work: the next call, on any stream, starts behind it
   bool busy = false;             // (the device scratch is shared by all calls on this ctx)
   hipStream_t last_stream = nullptr;
-  uint64_t* d_sizes = nullptr;   // sfh_gather_streams: the ranks' sizes on the device and in pinned memory
-  uint64_t* h_sizes = nullptr;
-  int sizes_cap = 0;
+  Pair<uint64_t> sizes;          // sfh_gather_streams: the ranks' records on the device and in pinned memory
   int order_ok[2] = {0, 0};      // sfh_lds_order_check per op (0 exchange: chains, 1 masked-or: recent): 0 not run, 1 holds, -1 does not
   int force_order_fail = 0;      // SFH_FORCE_ORDER_FAIL=1: the library's own check reports failure (tests)
   int inflate_serial = 0;        // SFH_INFLATE_SERIAL=1: index-only streams through the lane-serial kernel alone (tests, A/B)
-  // batched compression: the call's descriptor tables, built in pinned memory and uploaded with one copy; the next call
-  // refills the pinned rows only once that copy (ev_tab) has read them
-  uint8_t* h_tab = nullptr;
-  uint8_t* d_tab = nullptr;
-  size_t h_tab_cap = 0, d_tab_cap = 0;
-  hipEvent_t ev_tab = nullptr;
-  bool tab_pending = false;
-  uint8_t* h_stage = nullptr;    // the batched host calls (staged_up, staged_down): pinned staging of the packed items (kStageBytes)
-  uint64_t* d_bn = nullptr;      // sfh_compress_batch: the items' sizes on the device and in pinned memory
-  uint64_t* h_bn = nullptr;
-  size_t bn_cap = 0;             // items d_bn / h_bn hold
+  // the batched calls' descriptor tables (compress or decompress), built in pinned memory and uploaded with one copy
+  Stager tab{"pinned descriptor tables", "descriptor tables"};
+  Pinned<uint8_t> h_stage;       // the batched host calls (staged_up, staged_down): pinned staging of the packed items (kStageBytes)
+  Pair<uint64_t> bn;             // sfh_compress_batch: the items' sizes on the device and in pinned memory
   // the index of the last call when it was a compress batch (sfh_copy_batch_index): every item's entries, item after item, in
   // d_bix; the sub-index is ws.subidx (the call's chunks are the items' segments in order)
   bool bix_valid = false;
-  uint64_t* d_bix = nullptr;
-  size_t d_bix_cap = 0;
+  Buf<uint64_t> d_bix;
   size_t bix_items = 0, bix_entries = 0;
   std::vector<uint32_t> bix_block_bytes;
-  uint64_t* d_implied = nullptr; // sfh_decompress_batch* without an index: every item's two implied entries
-  size_t d_implied_cap = 0;
-  uint32_t* d_bstatus = nullptr; // sfh_decompress_batch: the statuses on the device and in pinned memory
-  uint32_t* h_bstatus = nullptr;
-  size_t bstatus_cap = 0;
+  Buf<uint64_t> d_implied;       // sfh_decompress_batch* without an index: every item's two implied entries
+  Pair<uint32_t> bstatus;        // sfh_decompress_batch: the statuses on the device and in pinned memory
   // decoding without side information (sfh_recover_index*, sfh_decompress_any* and their _batch calls): the per-wave counts of
   // the candidate scan, the node arrays of the walk, the recovered index and the per-segment arrays behind the token stage
-  uint8_t* d_anycnt = nullptr;
-  uint8_t* d_any = nullptr;
-  uint8_t* d_anyseg = nullptr;
-  uint64_t* d_anyix = nullptr;
-  size_t d_anycnt_cap = 0, d_any_cap = 0, d_anyseg_cap = 0, d_anyix_cap = 0;
-  uint8_t* d_anyb = nullptr;     // every item's body, node ranges and indexable flag; the totals
-  size_t d_anyb_cap = 0;
-  hipEvent_t ev_any[5] = {};
+  Buf<uint32_t> d_anycnt;
+  Buf<uint8_t> d_any;
+  Buf<uint8_t> d_anyseg;
+  Buf<uint64_t> d_anyix;
+  Buf<uint8_t> d_anyb;           // every item's body, node ranges and indexable flag; the totals
+  Event ev_any[5];
   float any_ms[2] = {0, 0};
   uint64_t any_counts[2] = {0, 0};
   // streams without flush points (sfh_inflate_stream*, one item or a batch): candidates (then: the records' items | the follow
   // list) | chunk records | the redo list; the symbol plane; the composed windows of the resolve
   uint64_t stream_chunk = 16384;  // SFH_STREAM_CHUNK=<bytes>: nominal chunk size S
-  uint8_t* d_stm = nullptr;
-  uint16_t* d_plane = nullptr;
-  uint16_t* d_wins = nullptr;
-  size_t d_stm_cap = 0, d_plane_cap = 0, d_wins_cap = 0;
-  hipEvent_t ev_stm[6] = {};
+  Buf<uint8_t> d_stm;
+  Buf<uint16_t> d_plane;
+  Buf<uint16_t> d_wins;
+  Event ev_stm[6];
   float stm_ms[SFH_STREAM_NSTAGES] = {};
   uint64_t stm_counts[SFH_STREAM_NCOUNTS] = {};
   // the wrapper rows and bodies | the item rows; a launch batch's group, checksum and fold rows and its statuses
-  uint8_t* d_sbt = nullptr;
-  uint8_t* d_sbr = nullptr;
-  size_t d_sbt_cap = 0, d_sbr_cap = 0;
+  Buf<uint8_t> d_sbt;
+  Buf<uint8_t> d_sbr;
   // ZIP (sfh_zip_read_index_device, sfh_decompress_zip*, sfh_compress_zip*), all on first use: the reader's tables (entry
-  // table; copy, piece, checksum and fold rows and the statuses); the writer's tables, pinned and on the device (ev_zip: the
-  // upload that reads the pinned ones), and the raw streams of one launch batch
-  uint8_t* d_zip = nullptr;
-  uint8_t* d_zipw = nullptr;
-  uint8_t* h_zipw = nullptr;
-  uint8_t* d_zipbody = nullptr;
-  size_t d_zip_cap = 0, d_zipw_cap = 0, h_zipw_cap = 0, d_zipbody_cap = 0;
-  hipEvent_t ev_zip = nullptr;
-  bool zipw_pending = false;
+  // table; copy, piece, checksum and fold rows and the statuses); the writer's tables, pinned and on the device (its own
+  // stager: enqueue_zip's batch calls use `tab`), and the raw streams of one launch batch
+  Buf<uint8_t> d_zip;
+  Stager zipw{"pinned ZIP tables", "ZIP tables"};
+  Buf<uint8_t> d_zipbody;
   char err[256] = {0};
+  // the compressor's workspace and the decoder's three arrays in it are raw fields of ws (the kernels' interface)
+  ~sfh_ctx() {
+    free_compress_ws(this);
+    (void)hipFree(ws.tokens);
+    (void)hipFree(ws.seginfo);
+    (void)hipFree(ws.sums);
+  }
 };
 
 namespace {
-
-using sf::stage::al16;
 
 int fail(sfh_ctx* c, int code, const char* what, hipError_t e) {
   if (c) snprintf(c->err, sizeof c->err, "%s: %s", what, e == hipSuccess ? "" : hipGetErrorString(e));
   return code;
 }
 
-#define SF_HIP(call, what)                                   \
-  do {                                                       \
-    hipError_t _e = (call);                                  \
-    if (_e != hipSuccess) return fail(ctx, SFH_E_HIP, what, _e); \
-  } while (0)
-
-// Grow-only device staging buffer: *p holds at least `bytes` afterwards (*cap_bytes tracks it).
+// the raw arrays of ws that are sized on their own (ensure_sums, ensure_seginfo): *p holds at least `bytes` afterwards
 template <class T>
-int grow(sfh_ctx* ctx, T** p, size_t* cap_bytes, size_t bytes, const char* what) {
+int grow_ws(sfh_ctx* ctx, T** p, size_t* cap_bytes, size_t bytes, const char* what) {
   if (*cap_bytes >= bytes) return SFH_OK;
   (void)hipFree(*p);
   *p = nullptr;
@@ -169,20 +159,6 @@ int grow(sfh_ctx* ctx, T** p, size_t* cap_bytes, size_t bytes, const char* what)
   const hipError_t e = hipMalloc(p, bytes);
   if (e != hipSuccess) return fail(ctx, SFH_E_NOMEM, what, e);
   *cap_bytes = bytes;
-  return SFH_OK;
-}
-
-// Grow-only device array with its pinned twin (what a call reads back per item): *d and *h hold `count` elements afterwards.
-template <class T>
-int grow_pair(sfh_ctx* ctx, T** d, T** h, size_t* cap, size_t count, const char* what) {
-  if (*cap >= count) return SFH_OK;
-  (void)hipFree(*d);
-  if (*h) (void)hipHostFree(*h);
-  *d = *h = nullptr;
-  *cap = 0;
-  if (hipMalloc(d, count * sizeof(T)) != hipSuccess || hipHostMalloc((void**)h, count * sizeof(T), hipHostMallocDefault) != hipSuccess)
-    return fail(ctx, SFH_E_NOMEM, what, hipSuccess);
-  *cap = count;
   return SFH_OK;
 }
 
@@ -210,7 +186,11 @@ void free_compress_ws(sfh_ctx* c) {
 
 // checksum partials: 4 bytes per chunk, needed without the rest of the workspace by sfh_checksum_device
 int ensure_sums(sfh_ctx* ctx, uint32_t nchunks) {
-  return grow(ctx, &ctx->ws.sums, &ctx->sums_cap, (size_t)nchunks * sizeof(uint32_t), "checksum scratch");
+  return grow_ws(ctx, &ctx->ws.sums, &ctx->sums_cap, (size_t)nchunks * sizeof(uint32_t), "checksum scratch");
+}
+// the decoders' segment records
+int ensure_seginfo(sfh_ctx* ctx, size_t nseg) {
+  return grow_ws(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, nseg * sizeof(sf::SegInfo), "segment records");
 }
 
 // The compressor's batch arrays hold min(nchunks, kBatchChunks) chunks, its index arrays (offsets, sub-index) every
@@ -302,6 +282,15 @@ int begin_call(sfh_ctx* ctx, void* stream, hipStream_t* s) {
 // decodes from d_index).  After a call that ended synchronised the event has fired and this returns at once.
 int wait_idle(sfh_ctx* ctx) {
   if (ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");
+  return SFH_OK;
+}
+// the timing events of a profiled call, grown on demand: `v` holds at least `need` afterwards
+int ensure_events(sfh_ctx* ctx, std::vector<Event>& v, size_t need) {
+  while (v.size() < need) {
+    Event e;
+    SF_HIP(hipEventCreate(&e.h), "event");
+    v.push_back(std::move(e));
+  }
   return SFH_OK;
 }
 
@@ -421,14 +410,7 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
   const uint32_t batch = std::max(per_strip, want / per_strip * per_strip);
   const uint32_t nbatches = (nchunks + batch - 1) / batch;
   ctx->ev_valid = false;
-  if (prof) {
-    const size_t need = (size_t)nbatches * sfh_ctx::kEvPerBatch + 1;
-    while (ctx->ev.size() < need) {
-      hipEvent_t e = nullptr;
-      SF_HIP(hipEventCreate(&e), "event");
-      ctx->ev.push_back(e);
-    }
-  }
+  if (prof && (rc = ensure_events(ctx, ctx->ev, (size_t)nbatches * sfh_ctx::kEvPerBatch + 1)) != SFH_OK) return rc;
   const size_t hdr = sf::wrapper_header_bytes(o.container, dictzip ? nchunks : 0u);
   if (pipe) pipe->copied = hdr;  // the wrapper header is written last (k_wrap) and copied last
   if (bgzf && n == 0) {  // the EOF member alone
@@ -465,7 +447,7 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
     sf::Options bo = ko;
     bo.final_stream = (last || bgzf) ? ko.final_stream : 0u;
     // every batch has its own events (recorded behind the wait for its input, so a kernel's time excludes the copy)
-    hipEvent_t* ev = prof ? &ctx->ev[(size_t)bi * sfh_ctx::kEvPerBatch] : nullptr;
+    Event* ev = prof ? &ctx->ev[(size_t)bi * sfh_ctx::kEvPerBatch] : nullptr;
     if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
     SF_HIP(sf::launch_lz77(bsrc, bn, nb, w, bo, s), "launch k_lz77");
     if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
@@ -502,33 +484,6 @@ int enqueue(sfh_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t cap, 
   return mark_call_end(ctx, s);
 }
 
-// The descriptor tables of a batched call (compress or decompress) are built in pinned memory and uploaded with one copy:
-// ctx->h_tab / ctx->d_tab hold at least `bytes` afterwards, and the previous call's copy has read h_tab (ev_tab) -- and, when
-// d_tab had to grow, its kernels have read d_tab.
-int stage_tables(sfh_ctx* ctx, size_t bytes) {
-  if (!ctx->ev_tab) SF_HIP(hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming), "event");
-  if (ctx->tab_pending) SF_HIP(hipEventSynchronize(ctx->ev_tab), "wait for the previous call's table copy");  // (it reads h_tab)
-  ctx->tab_pending = false;
-  if (ctx->h_tab_cap < bytes) {
-    if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
-    ctx->h_tab = nullptr;
-    ctx->h_tab_cap = 0;
-    const hipError_t e = hipHostMalloc((void**)&ctx->h_tab, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(ctx, SFH_E_NOMEM, "pinned descriptor tables", e);
-    ctx->h_tab_cap = bytes;
-  }
-  if (ctx->d_tab_cap < bytes && ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");  // (its kernels read d_tab)
-  return grow(ctx, &ctx->d_tab, &ctx->d_tab_cap, bytes, "descriptor tables");
-}
-// ... and once h_tab is filled: the call takes its place behind the previous one and the tables go up
-int upload_tables(sfh_ctx* ctx, size_t bytes, hipStream_t s) {
-  if (int rc = order_behind_last_call(ctx, s)) return rc;
-  SF_HIP(hipMemcpyAsync(ctx->d_tab, ctx->h_tab, bytes, hipMemcpyHostToDevice, s), "descriptor tables");
-  SF_HIP(hipEventRecord(ctx->ev_tab, s), "event");
-  ctx->tab_pending = true;
-  return SFH_OK;
-}
-
 // Destinations must not overlap: sorted by address, each ends before the next begins.  (A destination of no bytes is written
 // nothing and overlaps nothing: it is left out.)
 int check_disjoint(sfh_ctx* ctx, void* const* dsts, const uint64_t* lens, size_t count) {
@@ -550,13 +505,7 @@ int check_disjoint(sfh_ctx* ctx, void* const* dsts, const uint64_t* lens, size_t
 
 // the per-stage events of a profiled decode call: SFH_INFLATE_NSTAGES + 1 per launch batch
 int ensure_inflate_events(sfh_ctx* ctx, uint32_t nbatches) {
-  const size_t need = (size_t)nbatches * (SFH_INFLATE_NSTAGES + 1);
-  while (ctx->ev_inf.size() < need) {
-    hipEvent_t e = nullptr;
-    SF_HIP(hipEventCreate(&e), "event");
-    ctx->ev_inf.push_back(e);
-  }
-  return SFH_OK;
+  return ensure_events(ctx, ctx->ev_inf, (size_t)nbatches * (SFH_INFLATE_NSTAGES + 1));
 }
 
 // ---- batched compression (sfh_compress_batch*) ----
@@ -659,41 +608,34 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
   ctx->bix_valid = false;
   int rc = ensure_compress_ws(ctx, nchunks);
   if (!rc && (o.container || crc_partials)) rc = ensure_sums(ctx, nchunks);
-  if (!rc) rc = grow(ctx, &ctx->d_bix, &ctx->d_bix_cap, ((size_t)nchunks + count) * sizeof(uint64_t), "batch index");
+  if (!rc) rc = ctx->d_bix.grow(ctx, (size_t)nchunks + count, "batch index");
   if (rc) return rc;
   const sf::Options ko = kernel_options(o, sf::kChunk);  // (strip_bytes: the strip table's)
   if ((ko.chain_depth || ko.recent) && (rc = ensure_order(ctx, ko.recent ? 1 : 0)) != SFH_OK) return rc;
-  // the tables, in one pinned block: chunks | strips | items | wraps | index rows (rows of 16, 32 and 8 bytes)
-  const size_t b_chunks = chunks.size() * sizeof(sf::BatchChunk), b_strips = strips.size() * sizeof(sf::BatchStrip);
-  const size_t b_items = items.size() * sizeof(sf::BatchItem), b_wraps = wraps.size() * sizeof(sf::WrapItem);
-  const size_t b_ixrows = ixrows.size() * sizeof(sf::BatchIndexRow);
-  const size_t bytes = b_chunks + b_strips + b_items + b_wraps + b_ixrows;
-  if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
-  memcpy(ctx->h_tab, chunks.data(), b_chunks);
-  memcpy(ctx->h_tab + b_chunks, strips.data(), b_strips);
-  memcpy(ctx->h_tab + b_chunks + b_strips, items.data(), b_items);
-  memcpy(ctx->h_tab + b_chunks + b_strips + b_items, wraps.data(), b_wraps);
-  memcpy(ctx->h_tab + b_chunks + b_strips + b_items + b_wraps, ixrows.data(), b_ixrows);
-  const sf::BatchChunk* d_chunks = (const sf::BatchChunk*)ctx->d_tab;
-  const sf::BatchStrip* d_strips = (const sf::BatchStrip*)(ctx->d_tab + b_chunks);
-  sf::BatchItem* d_items = (sf::BatchItem*)(ctx->d_tab + b_chunks + b_strips);
-  const sf::WrapItem* d_wraps = (const sf::WrapItem*)(ctx->d_tab + b_chunks + b_strips + b_items);
-  const sf::BatchIndexRow* d_ixrows = (const sf::BatchIndexRow*)(ctx->d_tab + b_chunks + b_strips + b_items + b_wraps);
+  // the tables, in one pinned block: chunks | strips | items | wraps | index rows
+  Carve L;
+  const size_t o_chunks = L.add<sf::BatchChunk>(chunks.size()), o_strips = L.add<sf::BatchStrip>(strips.size());
+  const size_t o_items = L.add<sf::BatchItem>(items.size()), o_wraps = L.add<sf::WrapItem>(wraps.size());
+  const size_t o_ixrows = L.add<sf::BatchIndexRow>(ixrows.size()), bytes = L.bytes();
+  if ((rc = ctx->tab.stage(ctx, bytes)) != SFH_OK) return rc;
+  memcpy(ctx->tab.h + o_chunks, chunks.data(), chunks.size() * sizeof(sf::BatchChunk));
+  memcpy(ctx->tab.h + o_strips, strips.data(), strips.size() * sizeof(sf::BatchStrip));
+  memcpy(ctx->tab.h + o_items, items.data(), items.size() * sizeof(sf::BatchItem));
+  memcpy(ctx->tab.h + o_wraps, wraps.data(), wraps.size() * sizeof(sf::WrapItem));
+  memcpy(ctx->tab.h + o_ixrows, ixrows.data(), ixrows.size() * sizeof(sf::BatchIndexRow));
+  const sf::BatchChunk* d_chunks = Carve::at<const sf::BatchChunk>(ctx->tab.d, o_chunks);
+  const sf::BatchStrip* d_strips = Carve::at<const sf::BatchStrip>(ctx->tab.d, o_strips);
+  sf::BatchItem* d_items = Carve::at<sf::BatchItem>(ctx->tab.d, o_items);
+  const sf::WrapItem* d_wraps = Carve::at<const sf::WrapItem>(ctx->tab.d, o_wraps);
+  const sf::BatchIndexRow* d_ixrows = Carve::at<const sf::BatchIndexRow>(ctx->tab.d, o_ixrows);
 
   ctx->index_valid = false;  // a batch has no single index: the index functions refuse until the next single call
   ctx->last_chunks = lbs.back().nchunks;
   const bool prof = ctx->profiling != 0;
-  if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
+  if ((rc = ctx->tab.upload(ctx, bytes, s)) != SFH_OK) return rc;
   const uint32_t nbatches = (uint32_t)lbs.size();
   ctx->ev_valid = false;
-  if (prof) {
-    const size_t need = (size_t)nbatches * sfh_ctx::kEvPerBatch + 1;
-    while (ctx->ev.size() < need) {
-      hipEvent_t e = nullptr;
-      SF_HIP(hipEventCreate(&e), "event");
-      ctx->ev.push_back(e);
-    }
-  }
+  if (prof && (rc = ensure_events(ctx, ctx->ev, (size_t)nbatches * sfh_ctx::kEvPerBatch + 1)) != SFH_OK) return rc;
   const uint64_t hdr = sf::wrapper_header_bytes(o.container);
   for (uint32_t bi = 0; bi < nbatches; ++bi) {
     const LaunchBatch& b = lbs[bi];
@@ -701,7 +643,7 @@ int enqueue_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const u
     sf::Workspace w = ctx->ws;  // k_scan's offsets and k_emit's sub-index land at the batch's places in the call's index arrays
     w.offsets += b.c0;
     w.subidx += (size_t)b.c0 * 2 * sf::kSubRegions;
-    hipEvent_t* ev = prof ? &ctx->ev[(size_t)bi * sfh_ctx::kEvPerBatch] : nullptr;
+    Event* ev = prof ? &ctx->ev[(size_t)bi * sfh_ctx::kEvPerBatch] : nullptr;
     if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
     SF_HIP(sf::launch_lz77(nullptr, 0, b.nchunks, ctx->ws, ko, s, &bt), "launch k_lz77");
     if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
@@ -769,8 +711,7 @@ int enqueue_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs,
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
   (void)hipGetLastError();  // see enqueue()
   int rc = SFH_OK;
-  if (!d_index && (rc = grow(ctx, &ctx->d_implied, &ctx->d_implied_cap, 2 * count * sizeof(uint64_t), "implied index")))
-    return rc;
+  if (!d_index && (rc = ctx->d_implied.grow(ctx, 2 * count, "implied index"))) return rc;
   sf::iplan::Plan P;
   try {
     sf::iplan::plan_batches(count, dst_n, block_bytes, ctx->batch_chunks, P);
@@ -778,19 +719,19 @@ int enqueue_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs,
     return fail(ctx, SFH_E_NOMEM, "host memory for the launch batches", hipSuccess);
   }
   const uint32_t nseg = P.nseg;
-  rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, (size_t)nseg * sizeof(sf::SegInfo), "segment records");
+  rc = ensure_seginfo(ctx, (size_t)nseg);
   if (!rc) rc = ensure_dtok(ctx, P.widest);
   if (!rc && container) rc = ensure_sums(ctx, nseg);
   if (rc) return rc;
-  // the tables, in one pinned block: segments | items | strips | checksum chunks (rows of 48, 64, 8 and 16 bytes)
-  const size_t b_segs = (size_t)nseg * sizeof(sf::InflateSeg), b_items = count * sizeof(sf::InflateItem);
-  const size_t b_strips = (size_t)P.nstrips * sizeof(sf::InflateStrip), b_sums = container ? (size_t)nseg * sizeof(sf::BatchChunk) : 0;
-  const size_t o_sums = al16(b_segs + b_items + b_strips), bytes = o_sums + b_sums;
-  if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
-  sf::InflateSeg* h_segs = (sf::InflateSeg*)ctx->h_tab;
-  sf::InflateItem* h_items = (sf::InflateItem*)(ctx->h_tab + b_segs);
-  sf::InflateStrip* h_strips = (sf::InflateStrip*)(ctx->h_tab + b_segs + b_items);
-  sf::BatchChunk* h_sums = (sf::BatchChunk*)(ctx->h_tab + o_sums);
+  // the tables, in one pinned block: segments | items | strips | checksum chunks
+  Carve L;
+  const size_t o_segs = L.add<sf::InflateSeg>(nseg), o_items = L.add<sf::InflateItem>(count), o_strips = L.add<sf::InflateStrip>(P.nstrips);
+  const size_t o_sums = L.add<sf::BatchChunk>(container ? nseg : 0), bytes = L.bytes();
+  if ((rc = ctx->tab.stage(ctx, bytes)) != SFH_OK) return rc;
+  sf::InflateSeg* h_segs = Carve::at<sf::InflateSeg>(ctx->tab.h, o_segs);
+  sf::InflateItem* h_items = Carve::at<sf::InflateItem>(ctx->tab.h, o_items);
+  sf::InflateStrip* h_strips = Carve::at<sf::InflateStrip>(ctx->tab.h, o_strips);
+  sf::BatchChunk* h_sums = Carve::at<sf::BatchChunk>(ctx->tab.h, o_sums);
   uint32_t seg0 = 0;  // the item's first segment in the call; its first index entry: the items before have one more each
   for (size_t i = 0; i < count; ++i) {
     const uint32_t n = sf::iplan::segments_of(dst_n[i]);
@@ -815,17 +756,17 @@ int enqueue_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs,
           if (container) h_sums[g] = sf::BatchChunk{out, on, 0u};
           ++g;
         });
-  sf::InflateSeg* t_segs = (sf::InflateSeg*)ctx->d_tab;
-  sf::InflateItem* t_items = (sf::InflateItem*)(ctx->d_tab + b_segs);
-  const sf::InflateStrip* t_strips = (const sf::InflateStrip*)(ctx->d_tab + b_segs + b_items);
-  sf::BatchChunk* t_sums = (sf::BatchChunk*)(ctx->d_tab + o_sums);
+  sf::InflateSeg* t_segs = Carve::at<sf::InflateSeg>(ctx->tab.d, o_segs);
+  sf::InflateItem* t_items = Carve::at<sf::InflateItem>(ctx->tab.d, o_items);
+  const sf::InflateStrip* t_strips = Carve::at<const sf::InflateStrip>(ctx->tab.d, o_strips);
+  sf::BatchChunk* t_sums = Carve::at<sf::BatchChunk>(ctx->tab.d, o_sums);
 
   ctx->index_valid = false;  // the last call is now this one: what sfh_debug_read returns belongs to it
   ctx->bix_valid = false;
   ctx->last_chunks = nseg;
   ctx->last_dtok_bytes = (size_t)P.widest * sf::kChunk * sizeof(uint32_t);
   const bool prof = ctx->profiling != 0;
-  if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
+  if ((rc = ctx->tab.upload(ctx, bytes, s)) != SFH_OK) return rc;
   const uint32_t nbatches = (uint32_t)P.batches.size();
   ctx->ev_inf_valid = false;
   if (prof && (rc = ensure_inflate_events(ctx, nbatches)) != SFH_OK) return rc;
@@ -836,7 +777,7 @@ int enqueue_inflate_batch(sfh_ctx* ctx, size_t count, const void* const* d_srcs,
   for (uint32_t bi = 0; bi < nbatches; ++bi) {
     const sf::iplan::Batch& b = P.batches[bi];
     sf::SegInfo* binfo = ctx->ws.seginfo + b.row0;
-    hipEvent_t* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
+    Event* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
     if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
     SF_HIP(sf::launch_inflate_tokens(t_segs + b.row0, b.nseg, ctx->ws.tokens, binfo, d_subindex != nullptr, !ctx->inflate_serial, s),
            "launch k_inflate_tokens");
@@ -906,17 +847,17 @@ int enqueue_ranges(sfh_ctx* ctx, const sf::range::Plan& P, const RangeSource* fr
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
   (void)hipGetLastError();  // see enqueue()
   const size_t nrows = P.rows.size(), nstrips = P.strips.size();
-  const size_t b_segs = nrows * sizeof(sf::InflateSeg), b_clips = nrows * sizeof(sf::InflateClip);
-  const size_t b_strips = nstrips * sizeof(sf::InflateStrip), b_spans = count * sizeof(sf::InflateSpan);
-  const size_t bytes = b_segs + b_clips + b_strips + b_spans;
-  int rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, nrows * sizeof(sf::SegInfo), "segment records");
+  Carve L;  // segments | write windows | strips | spans
+  const size_t o_segs = L.add<sf::InflateSeg>(nrows), o_clips = L.add<sf::InflateClip>(nrows);
+  const size_t o_strips = L.add<sf::InflateStrip>(nstrips), o_spans = L.add<sf::InflateSpan>(count), bytes = L.bytes();
+  int rc = ensure_seginfo(ctx, nrows);
   if (!rc) rc = ensure_dtok(ctx, P.widest);
-  if (!rc) rc = stage_tables(ctx, bytes);
+  if (!rc) rc = ctx->tab.stage(ctx, bytes);
   if (rc) return rc;
-  sf::InflateSeg* h_segs = (sf::InflateSeg*)ctx->h_tab;
-  sf::InflateClip* h_clips = (sf::InflateClip*)(ctx->h_tab + b_segs);
-  sf::InflateStrip* h_strips = (sf::InflateStrip*)(ctx->h_tab + b_segs + b_clips);
-  sf::InflateSpan* h_spans = (sf::InflateSpan*)(ctx->h_tab + b_segs + b_clips + b_strips);
+  sf::InflateSeg* h_segs = Carve::at<sf::InflateSeg>(ctx->tab.h, o_segs);
+  sf::InflateClip* h_clips = Carve::at<sf::InflateClip>(ctx->tab.h, o_clips);
+  sf::InflateStrip* h_strips = Carve::at<sf::InflateStrip>(ctx->tab.h, o_strips);
+  sf::InflateSpan* h_spans = Carve::at<sf::InflateSpan>(ctx->tab.h, o_spans);
   for (size_t g = 0; g < nrows; ++g) {
     const sf::range::Row& w = P.rows[g];
     const RangeSource& f = from[w.range];
@@ -926,24 +867,24 @@ int enqueue_ranges(sfh_ctx* ctx, const sf::range::Plan& P, const RangeSource* fr
   }
   for (size_t k = 0; k < nstrips; ++k) h_strips[k] = sf::InflateStrip{P.strips[k].row0, P.strips[k].nrows};
   for (size_t r = 0; r < count; ++r) h_spans[r] = sf::InflateSpan{P.spans[r].row0, P.spans[r].nrows};
-  const sf::InflateSeg* t_segs = (const sf::InflateSeg*)ctx->d_tab;
-  const sf::InflateClip* t_clips = (const sf::InflateClip*)(ctx->d_tab + b_segs);
-  const sf::InflateStrip* t_strips = (const sf::InflateStrip*)(ctx->d_tab + b_segs + b_clips);
-  const sf::InflateSpan* t_spans = (const sf::InflateSpan*)(ctx->d_tab + b_segs + b_clips + b_strips);
+  const sf::InflateSeg* t_segs = Carve::at<const sf::InflateSeg>(ctx->tab.d, o_segs);
+  const sf::InflateClip* t_clips = Carve::at<const sf::InflateClip>(ctx->tab.d, o_clips);
+  const sf::InflateStrip* t_strips = Carve::at<const sf::InflateStrip>(ctx->tab.d, o_strips);
+  const sf::InflateSpan* t_spans = Carve::at<const sf::InflateSpan>(ctx->tab.d, o_spans);
 
   ctx->index_valid = false;
   ctx->bix_valid = false;
   ctx->last_chunks = (uint32_t)nrows;
   ctx->last_dtok_bytes = (size_t)P.widest * sf::kChunk * sizeof(uint32_t);
   const bool prof = ctx->profiling != 0;
-  if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
+  if ((rc = ctx->tab.upload(ctx, bytes, s)) != SFH_OK) return rc;
   const uint32_t nbatches = (uint32_t)P.batches.size();
   ctx->ev_inf_valid = false;
   if (prof && (rc = ensure_inflate_events(ctx, nbatches)) != SFH_OK) return rc;
   for (uint32_t bi = 0; bi < nbatches; ++bi) {
     const sf::range::Batch& b = P.batches[bi];
     sf::SegInfo* binfo = ctx->ws.seginfo + b.row0;
-    hipEvent_t* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
+    Event* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
     if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
     SF_HIP(sf::launch_inflate_tokens(t_segs + b.row0, b.nrows, ctx->ws.tokens, binfo, sub, !ctx->inflate_serial, s),
            "launch k_inflate_tokens");
@@ -1002,14 +943,11 @@ int staged_up(sfh_ctx* ctx, Staged& B, size_t count, const void* const* srcs, co
   sf::stage::pack_layout(src_n, count, B.in_off.data());
   if (slot) sf::stage::pack_layout(slot, count, B.out_off.data());
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, std::max<uint64_t>(16, B.in_off[count]), "input staging");
-  if (!rc && slot) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, std::max<uint64_t>(16, B.out_off[count]), "output staging");
+  int rc = ctx->d_in.grow(ctx, std::max<uint64_t>(16, B.in_off[count]), "input staging");
+  if (!rc && slot) rc = ctx->d_out.grow(ctx, std::max<uint64_t>(16, B.out_off[count]), "output staging");
+  if (!rc) rc = ctx->h_stage.grow(ctx, kStageBytes, "pinned staging");
+  if (!rc) rc = wait_idle(ctx);
   if (rc) return rc;
-  if (!ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
-    ctx->h_stage = nullptr;
-    return fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
-  }
-  if ((rc = wait_idle(ctx))) return rc;
   if ((rc = stage_up(ctx, ctx->d_in, srcs, src_n, B.in_off.data(), count, B.in_off[count], ctx->stream))) return rc;
   for (size_t i = 0; i < count; ++i) {
     B.d_srcs[i] = ctx->d_in + B.in_off[i];
@@ -1032,8 +970,8 @@ int staged_down(sfh_ctx* ctx, Staged& B, size_t count, void* const* dsts, const 
 // (d_out sized for out_n bytes), on an idle context as above; host_down fetches d_out[0, n) into dst and synchronises.
 int host_up(sfh_ctx* ctx, const void* src, size_t src_n, size_t out_n) {
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, std::max<size_t>(16, src_n), "input staging");
-  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, std::max<size_t>(16, out_n), "output staging");
+  int rc = ctx->d_in.grow(ctx, std::max<size_t>(16, src_n), "input staging");
+  if (!rc) rc = ctx->d_out.grow(ctx, std::max<size_t>(16, out_n), "output staging");
   if (!rc) rc = wait_idle(ctx);
   if (rc) return rc;
   if (src_n) SF_HIP(hipMemcpyAsync(ctx->d_in, src, src_n, hipMemcpyHostToDevice, ctx->stream), "H2D");
@@ -1046,14 +984,12 @@ int host_down(sfh_ctx* ctx, void* dst, size_t n) {
   return SFH_OK;
 }
 
-// d_bstatus / h_bstatus hold `count` statuses; read_bstatus: the call's, behind its device path (synchronises s)
-int ensure_bstatus(sfh_ctx* ctx, size_t count) {
-  return grow_pair(ctx, &ctx->d_bstatus, &ctx->h_bstatus, &ctx->bstatus_cap, count, "batch statuses");
-}
+// bstatus.d / bstatus.h hold `count` statuses; read_bstatus: the call's, behind its device path (synchronises s)
+int ensure_bstatus(sfh_ctx* ctx, size_t count) { return ctx->bstatus.grow(ctx, count, "batch statuses"); }
 int read_bstatus(sfh_ctx* ctx, size_t count, uint32_t* status, hipStream_t s) {
-  SF_HIP(hipMemcpyAsync(ctx->h_bstatus, ctx->d_bstatus, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy statuses");
+  SF_HIP(hipMemcpyAsync(ctx->bstatus.h, ctx->bstatus.d, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "copy statuses");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
-  memcpy(status, ctx->h_bstatus, count * sizeof(uint32_t));
+  memcpy(status, ctx->bstatus.h, count * sizeof(uint32_t));
   return SFH_OK;
 }
 
@@ -1149,15 +1085,16 @@ int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, con
   } catch (...) {
     return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
   }
-  for (hipEvent_t& e : ctx->ev_any)
-    if (!e) SF_HIP(hipEventCreate(&e), "event");
-  const size_t o_rng = 16 * count, o_ok = o_rng + sizeof(sf::AnyRange) * count, o_tot = al16(o_ok + 4 * count);
-  int rc = grow(ctx, &ctx->d_anyb, &ctx->d_anyb_cap, o_tot + 32, "recovery tables");
+  for (Event& e : ctx->ev_any)
+    if (!e) SF_HIP(hipEventCreate(&e.h), "event");
+  Carve A;
+  const size_t o_heads = A.add<uint64_t>(2 * count), o_rng = A.add<sf::AnyRange>(count), o_ok = A.add<uint32_t>(count), o_tot = A.add<uint32_t>(8);
+  int rc = ctx->d_anyb.grow(ctx, A.bytes(), "recovery tables");
   if (rc) return rc;
-  uint64_t* heads = (uint64_t*)ctx->d_anyb;
-  sf::AnyRange* range = (sf::AnyRange*)(ctx->d_anyb + o_rng);
-  uint32_t* ok = (uint32_t*)(ctx->d_anyb + o_ok);
-  uint32_t* tot = (uint32_t*)(ctx->d_anyb + o_tot);
+  uint64_t* heads = Carve::at<uint64_t>(ctx->d_anyb, o_heads);
+  sf::AnyRange* range = Carve::at<sf::AnyRange>(ctx->d_anyb, o_rng);
+  uint32_t* ok = Carve::at<uint32_t>(ctx->d_anyb, o_ok);
+  uint32_t* tot = Carve::at<uint32_t>(ctx->d_anyb, o_tot);
   for (size_t i = 0; i < count; ++i) {
     const bool tr = dst_n[i] == SFH_SIZE_FROM_TRAILER;
     trailer |= tr;
@@ -1182,29 +1119,34 @@ int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, con
     }
     R.entries = segs + count;
   };
-  auto fill_scan_rows = [&](uint8_t* at) {
-    memcpy(at, items.data(), count * sizeof(sf::AnyItem));
-    sf::AnyWave* wv = (sf::AnyWave*)(at + count * sizeof(sf::AnyItem));
+  // the scan's rows behind what L holds already: added, the block staged, the rows filled in
+  Carve L;
+  size_t o_items = 0, o_waves = 0;
+  auto stage_scan_rows = [&]() -> int {
+    o_items = L.add<sf::AnyItem>(count);
+    o_waves = L.add<sf::AnyWave>((size_t)nw);
+    if (int e = ctx->tab.stage(ctx, L.bytes())) return e;
+    memcpy(ctx->tab.h + o_items, items.data(), count * sizeof(sf::AnyItem));
+    sf::AnyWave* wv = Carve::at<sf::AnyWave>(ctx->tab.h, o_waves);
     for (size_t i = 0; i < count; ++i)
       for (uint32_t p = 0; p < items[i].nwaves; ++p) wv[items[i].wave0 + p] = sf::AnyWave{(uint32_t)i, p};
+    return SFH_OK;
   };
   const size_t b_rows = count * sizeof(sf::InflateItem);
-  size_t o_items = b_rows;
   if (!trailer) {
     geometry();
-    const size_t bytes = b_rows + count * sizeof(sf::AnyItem) + (size_t)nw * sizeof(sf::AnyWave);
-    if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
-    memcpy(ctx->h_tab, rows.data(), b_rows);
-    fill_scan_rows(ctx->h_tab + b_rows);
-    if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
-    SF_HIP(sf::launch_inflate_head((sf::InflateItem*)ctx->d_tab, (uint32_t)count, container, nullptr, nullptr, s), "launch k_inflate_head");
+    L.add<sf::InflateItem>(count);  // (the item rows: at 0)
+    if ((rc = stage_scan_rows()) != SFH_OK) return rc;
+    memcpy(ctx->tab.h, rows.data(), b_rows);
+    if ((rc = ctx->tab.upload(ctx, L.bytes(), s)) != SFH_OK) return rc;
+    SF_HIP(sf::launch_inflate_head(Carve::at<sf::InflateItem>(ctx->tab.d, 0), (uint32_t)count, container, nullptr, nullptr, s), "launch k_inflate_head");
     if (bodies) SF_HIP(hipMemcpyAsync(heads, bodies, 16 * count, hipMemcpyHostToDevice, s), "H2D bodies");  // (over the implied ones)
   } else {
-    if ((rc = stage_tables(ctx, b_rows)) != SFH_OK) return rc;
-    memcpy(ctx->h_tab, rows.data(), b_rows);
-    if ((rc = upload_tables(ctx, b_rows, s)) != SFH_OK) return rc;
-    SF_HIP(sf::launch_inflate_head((sf::InflateItem*)ctx->d_tab, (uint32_t)count, container, nullptr, nullptr, s), "launch k_inflate_head");
-    SF_HIP(hipMemcpyAsync(rows.data(), ctx->d_tab, b_rows, hipMemcpyDeviceToHost, s), "D2H wrapper rows");
+    if ((rc = ctx->tab.stage(ctx, b_rows)) != SFH_OK) return rc;
+    memcpy(ctx->tab.h, rows.data(), b_rows);
+    if ((rc = ctx->tab.upload(ctx, b_rows, s)) != SFH_OK) return rc;
+    SF_HIP(sf::launch_inflate_head(Carve::at<sf::InflateItem>(ctx->tab.d, 0), (uint32_t)count, container, nullptr, nullptr, s), "launch k_inflate_head");
+    SF_HIP(hipMemcpyAsync(rows.data(), ctx->tab.d, b_rows, hipMemcpyDeviceToHost, s), "D2H wrapper rows");
     SF_HIP(hipStreamSynchronize(s), "stream sync");
     for (size_t i = 0; i < count; ++i) {
       if (!R.st[i] && rows[i].wst) R.st[i] = rows[i].wst;
@@ -1213,26 +1155,23 @@ int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, con
     geometry();
     if (segs > ((uint64_t)1 << 31) - 1 || nw > ((uint64_t)1 << 31) - 1)
       return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 segments or scan waves in one call", hipSuccess);
-    const size_t bytes = count * sizeof(sf::AnyItem) + (size_t)nw * sizeof(sf::AnyWave);
-    if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
-    fill_scan_rows(ctx->h_tab);
-    if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
-    o_items = 0;
+    if ((rc = stage_scan_rows()) != SFH_OK) return rc;
+    if ((rc = ctx->tab.upload(ctx, L.bytes(), s)) != SFH_OK) return rc;
   }
-  const sf::AnyItem* t_items = (const sf::AnyItem*)(ctx->d_tab + o_items);
-  const sf::AnyWave* t_waves = (const sf::AnyWave*)(ctx->d_tab + o_items + count * sizeof(sf::AnyItem));
+  const sf::AnyItem* t_items = Carve::at<const sf::AnyItem>(ctx->tab.d, o_items);
+  const sf::AnyWave* t_waves = Carve::at<const sf::AnyWave>(ctx->tab.d, o_waves);
   if (!d_index) {
-    if ((rc = grow(ctx, &ctx->d_anyix, &ctx->d_anyix_cap, R.entries * sizeof(uint64_t), "recovered index"))) return rc;
+    if ((rc = ctx->d_anyix.grow(ctx, R.entries, "recovered index"))) return rc;
     d_index = ctx->d_anyix;
   }
   SF_HIP(hipMemsetAsync(d_index, 0, R.entries * sizeof(uint64_t), s), "clear the index");
-  SF_HIP(hipMemsetAsync(ok, 0, (o_tot + 32) - o_ok, s), "clear the flags");
+  SF_HIP(hipMemsetAsync(ok, 0, A.bytes() - o_ok, s), "clear the flags");
   SF_HIP(sf::launch_any_single(t_items, (uint32_t)count, heads, d_index, ok, s), "launch k_any_single");
   const uint32_t nwaves = (uint32_t)nw;
   if (nwaves) {
     const size_t tw = sf::any_scan_tmp_words(nwaves);
-    if ((rc = grow(ctx, &ctx->d_anycnt, &ctx->d_anycnt_cap, (2 * (size_t)nwaves + tw) * sizeof(uint32_t), "candidate counts"))) return rc;
-    uint32_t* cn = (uint32_t*)ctx->d_anycnt;
+    if ((rc = ctx->d_anycnt.grow(ctx, 2 * (size_t)nwaves + tw, "candidate counts"))) return rc;
+    uint32_t* cn = ctx->d_anycnt;
     uint32_t* cm = cn + nwaves;
     uint32_t* tmp = cm + nwaves;
     if (prof) SF_HIP(hipEventRecord(ctx->ev_any[0], s), "event");
@@ -1249,24 +1188,25 @@ int any_batch_recover(sfh_ctx* ctx, size_t count, const void* const* d_srcs, con
     for (size_t i = 0; i < count; ++i) scanned += items[i].nwaves ? 1u : 0u;
     ctx->any_counts[0] = n - scanned;
     // pos u64[n] | nxt_a, nxt_b, minc, lbl, rank, item u32[n] | midx u32[nm+1] | tmp | flg, lab, mark u8[n]
-    const size_t ntw = sf::any_scan_tmp_words(n), w4 = al16(4 * (size_t)n), w1 = al16(n);
-    const size_t o_nxa = al16(8 * (size_t)n), o_nxb = o_nxa + w4, o_minc = o_nxb + w4, o_lbl = o_minc + w4, o_rank = o_lbl + w4;
-    const size_t o_item = o_rank + w4, o_midx = o_item + w4, o_tmp = o_midx + al16(4 * ((size_t)nm + 1)), o_flg = o_tmp + al16(4 * ntw);
-    const size_t o_lab = o_flg + w1, o_mark = o_lab + w1;
-    if ((rc = grow(ctx, &ctx->d_any, &ctx->d_any_cap, o_mark + w1, "walk nodes"))) return rc;
+    Carve W;
+    const size_t o_pos = W.add<uint64_t>(n), o_nxa = W.add<uint32_t>(n), o_nxb = W.add<uint32_t>(n), o_minc = W.add<uint32_t>(n);
+    const size_t o_lbl = W.add<uint32_t>(n), o_rank = W.add<uint32_t>(n), o_item = W.add<uint32_t>(n), o_midx = W.add<uint32_t>((size_t)nm + 1);
+    const size_t o_tmp = W.add<uint32_t>(sf::any_scan_tmp_words(n)), o_flg = W.add<uint8_t>(n), o_lab = W.add<uint8_t>(n), o_mark = W.add<uint8_t>(n);
+    if ((rc = ctx->d_any.grow(ctx, W.bytes(), "walk nodes"))) return rc;
     uint8_t* b = ctx->d_any;
+    uint64_t* pos = Carve::at<uint64_t>(b, o_pos);
+    auto u32 = [b](size_t off) { return Carve::at<uint32_t>(b, off); };
     if (prof) SF_HIP(hipEventRecord(ctx->ev_any[2], s), "event");
-    SF_HIP(sf::launch_any_nodes(t_items, t_waves, heads, nwaves, cn, cm, (uint64_t*)b, b + o_flg, (uint32_t*)(b + o_minc),
-                                      (uint32_t*)(b + o_midx), (uint32_t*)(b + o_item), s), "launch k_any_scan");
+    SF_HIP(sf::launch_any_nodes(t_items, t_waves, heads, nwaves, cn, cm, pos, b + o_flg, u32(o_minc), u32(o_midx), u32(o_item), s),
+           "launch k_any_scan");
     if (prof) SF_HIP(hipEventRecord(ctx->ev_any[3], s), "event");
-    SF_HIP(sf::launch_any_walk(t_items, heads, range, (uint32_t*)(b + o_item), (uint64_t*)b, b + o_flg, (uint32_t*)(b + o_minc),
-                                     (uint32_t*)(b + o_midx), n, largest, (uint32_t*)(b + o_nxa), (uint32_t*)(b + o_nxb), b + o_lab,
-                                     b + o_mark, (uint32_t*)(b + o_lbl), (uint32_t*)(b + o_rank), (uint32_t*)(b + o_tmp), tot + 2,
-                                     d_index, ok, s), "launch k_any_walk");
+    SF_HIP(sf::launch_any_walk(t_items, heads, range, u32(o_item), pos, b + o_flg, u32(o_minc), u32(o_midx), n, largest, u32(o_nxa),
+                               u32(o_nxb), b + o_lab, b + o_mark, u32(o_lbl), u32(o_rank), u32(o_tmp), tot + 2, d_index, ok, s),
+           "launch k_any_walk");
     if (prof) SF_HIP(hipEventRecord(ctx->ev_any[4], s), "event");
   }
   SF_HIP(hipMemcpyAsync(okv.data(), ok, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "D2H walk");
-  if (!trailer && container) SF_HIP(hipMemcpyAsync(rows.data(), ctx->d_tab, b_rows, hipMemcpyDeviceToHost, s), "D2H wrapper rows");
+  if (!trailer && container) SF_HIP(hipMemcpyAsync(rows.data(), ctx->tab.d, b_rows, hipMemcpyDeviceToHost, s), "D2H wrapper rows");
   if ((rc = mark_call_end(ctx, s)) != SFH_OK) return rc;
   SF_HIP(hipStreamSynchronize(s), "stream sync");
   if (prof && nwaves) {
@@ -1308,23 +1248,24 @@ int any_batch_decode(sfh_ctx* ctx, size_t count, const void* const* d_srcs, cons
   ctx->ev_inf_valid = false;
   if (P.nseg == 0) return SFH_OK;
   const uint32_t nseg = P.nseg, nitems = P.nitems, nb = (uint32_t)P.batches.size(), wd = P.widest;
-  int rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, (size_t)nseg * sizeof(sf::SegInfo), "segment records");
+  int rc = ensure_seginfo(ctx, (size_t)nseg);
   if (!rc) rc = ensure_dtok(ctx, wd);
   if (!rc && container) rc = ensure_sums(ctx, nseg);
   if (!rc) rc = ensure_bstatus(ctx, (size_t)nitems + nb);
   // rows per batch u32[nb] | depends u8[wd] | starts, excl u32[wd] | tmp | rows InflateStrip[wd]
-  const size_t tw = sf::any_scan_tmp_words(wd);
-  const size_t o_dep = al16(4 * (size_t)nb), o_st = o_dep + al16(wd), o_ex = o_st + al16(4 * (size_t)wd), o_tmp = o_ex + al16(4 * (size_t)wd);
-  const size_t o_rows = o_tmp + al16(4 * tw);
-  if (!rc) rc = grow(ctx, &ctx->d_anyseg, &ctx->d_anyseg_cap, o_rows + sizeof(sf::InflateStrip) * (size_t)wd, "segment rows");
+  Carve D;
+  const size_t o_nrows = D.add<uint32_t>(nb), o_dep = D.add<uint8_t>(wd), o_st = D.add<uint32_t>(wd), o_ex = D.add<uint32_t>(wd);
+  const size_t o_tmp = D.add<uint32_t>(sf::any_scan_tmp_words(wd)), o_rows = D.add<sf::InflateStrip>(wd);
+  if (!rc) rc = ctx->d_anyseg.grow(ctx, D.bytes(), "segment rows");
   if (rc) return rc;
   // the tables, in one pinned block: segments | items | checksum chunks
-  const size_t b_segs = (size_t)nseg * sizeof(sf::InflateSeg), b_items = (size_t)nitems * sizeof(sf::InflateItem);
-  const size_t o_sums = al16(b_segs + b_items), bytes = o_sums + (container ? (size_t)nseg * sizeof(sf::BatchChunk) : 0);
-  if ((rc = stage_tables(ctx, bytes)) != SFH_OK) return rc;
-  sf::InflateSeg* h_segs = (sf::InflateSeg*)ctx->h_tab;
-  sf::InflateItem* h_items = (sf::InflateItem*)(ctx->h_tab + b_segs);
-  sf::BatchChunk* h_sums = (sf::BatchChunk*)(ctx->h_tab + o_sums);
+  Carve L;
+  const size_t o_segs = L.add<sf::InflateSeg>(nseg), o_items = L.add<sf::InflateItem>(nitems);
+  const size_t o_sums = L.add<sf::BatchChunk>(container ? nseg : 0), bytes = L.bytes();
+  if ((rc = ctx->tab.stage(ctx, bytes)) != SFH_OK) return rc;
+  sf::InflateSeg* h_segs = Carve::at<sf::InflateSeg>(ctx->tab.h, o_segs);
+  sf::InflateItem* h_items = Carve::at<sf::InflateItem>(ctx->tab.h, o_items);
+  sf::BatchChunk* h_sums = Carve::at<sf::BatchChunk>(ctx->tab.h, o_sums);
   uint32_t g = 0, j = 0;
   for (size_t i = 0; i < count; ++i) {
     if (!R.take[i]) continue;
@@ -1341,25 +1282,25 @@ int any_batch_decode(sfh_ctx* ctx, size_t count, const void* const* d_srcs, cons
       if (container) h_sums[g] = sf::BatchChunk{out, on, 0u};
     }
   }
-  sf::InflateSeg* t_segs = (sf::InflateSeg*)ctx->d_tab;
-  sf::InflateItem* t_items = (sf::InflateItem*)(ctx->d_tab + b_segs);
-  sf::BatchChunk* t_sums = (sf::BatchChunk*)(ctx->d_tab + o_sums);
+  sf::InflateSeg* t_segs = Carve::at<sf::InflateSeg>(ctx->tab.d, o_segs);
+  sf::InflateItem* t_items = Carve::at<sf::InflateItem>(ctx->tab.d, o_items);
+  sf::BatchChunk* t_sums = Carve::at<sf::BatchChunk>(ctx->tab.d, o_sums);
   uint8_t* sb = ctx->d_anyseg;
-  uint32_t* d_nrows = (uint32_t*)sb;
-  sf::InflateStrip* strips = (sf::InflateStrip*)(sb + o_rows);
+  uint32_t* d_nrows = Carve::at<uint32_t>(sb, o_nrows);
+  sf::InflateStrip* strips = Carve::at<sf::InflateStrip>(sb, o_rows);
   const bool prof = ctx->profiling != 0;
-  if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
+  if ((rc = ctx->tab.upload(ctx, bytes, s)) != SFH_OK) return rc;
   if (prof && (rc = ensure_inflate_events(ctx, nb)) != SFH_OK) return rc;
   SF_HIP(sf::launch_inflate_head(t_items, nitems, container, t_segs, container ? t_sums : nullptr, s), "launch k_inflate_head");
   for (uint32_t bi = 0; bi < nb; ++bi) {
     const sf::aplan::Batch& b = P.batches[bi];
     sf::SegInfo* binfo = ctx->ws.seginfo + b.row0;
-    hipEvent_t* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
+    Event* ev = prof ? &ctx->ev_inf[(size_t)bi * (SFH_INFLATE_NSTAGES + 1)] : nullptr;
     if (ev) SF_HIP(hipEventRecord(ev[0], s), "event");
     SF_HIP(sf::launch_inflate_tokens_exact(t_segs + b.row0, b.nseg, ctx->ws.tokens, binfo, !ctx->inflate_serial, s),
            "launch k_inflate_tokens");
-    SF_HIP(sf::launch_any_rows(t_segs + b.row0, binfo, ctx->ws.tokens, b.nseg, sb + o_dep, (uint32_t*)(sb + o_st),
-                                     (uint32_t*)(sb + o_ex), (uint32_t*)(sb + o_tmp), d_nrows + bi, strips, s), "launch k_any_rows");
+    SF_HIP(sf::launch_any_rows(t_segs + b.row0, binfo, ctx->ws.tokens, b.nseg, sb + o_dep, Carve::at<uint32_t>(sb, o_st),
+                               Carve::at<uint32_t>(sb, o_ex), Carve::at<uint32_t>(sb, o_tmp), d_nrows + bi, strips, s), "launch k_any_rows");
     if (ev) SF_HIP(hipEventRecord(ev[1], s), "event");
     if (bytes_stage) SF_HIP(sf::launch_inflate_bytes(t_segs + b.row0, strips, b.nseg, ctx->ws.tokens, binfo, s), "launch k_inflate_bytes");
     if (ev) SF_HIP(hipEventRecord(ev[2], s), "event");
@@ -1370,20 +1311,20 @@ int any_batch_decode(sfh_ctx* ctx, size_t count, const void* const* d_srcs, cons
   const size_t first = bytes_stage ? 0 : nitems;
   if (bytes_stage) {
     if (container) SF_HIP(sf::launch_checksum_batch(t_sums, nseg, container, ctx->ws.sums, s), "launch k_checksum");
-    SF_HIP(sf::launch_inflate_fold(t_items, nitems, ctx->ws.seginfo, ctx->ws.sums, container, ctx->d_bstatus, nullptr, s),
+    SF_HIP(sf::launch_inflate_fold(t_items, nitems, ctx->ws.seginfo, ctx->ws.sums, container, ctx->bstatus.d, nullptr, s),
            "launch k_inflate_fold");
   } else {
     SF_HIP(hipMemcpyAsync(d_depends, sb + o_dep, nseg, hipMemcpyDeviceToDevice, s), "copy depends");
   }
-  SF_HIP(hipMemcpyAsync(ctx->d_bstatus + nitems, d_nrows, nb * sizeof(uint32_t), hipMemcpyDeviceToDevice, s), "copy rows");
-  SF_HIP(hipMemcpyAsync(ctx->h_bstatus + first, ctx->d_bstatus + first, ((size_t)nitems + nb - first) * sizeof(uint32_t),
+  SF_HIP(hipMemcpyAsync(ctx->bstatus.d + nitems, d_nrows, nb * sizeof(uint32_t), hipMemcpyDeviceToDevice, s), "copy rows");
+  SF_HIP(hipMemcpyAsync(ctx->bstatus.h + first, ctx->bstatus.d + first, ((size_t)nitems + nb - first) * sizeof(uint32_t),
                         hipMemcpyDeviceToHost, s), "copy statuses");
   if ((rc = mark_call_end(ctx, s)) != SFH_OK) return rc;
   SF_HIP(hipStreamSynchronize(s), "stream sync");
   j = 0;
   for (size_t i = 0; i < count && bytes_stage; ++i)
-    if (R.take[i]) R.st[i] = ctx->h_bstatus[j++];
-  for (uint32_t bi = 0; bi < nb; ++bi) ctx->any_counts[1] += ctx->h_bstatus[nitems + bi];
+    if (R.take[i]) R.st[i] = ctx->bstatus.h[j++];
+  for (uint32_t bi = 0; bi < nb; ++bi) ctx->any_counts[1] += ctx->bstatus.h[nitems + bi];
   return SFH_OK;
 }
 
@@ -1431,8 +1372,8 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
       return fail(ctx, SFH_E_NOMEM, "host memory", hipSuccess);
     }
   }
-  for (hipEvent_t& e : ctx->ev_stm)
-    if (!e) SF_HIP(hipEventCreate(&e), "event");
+  for (Event& e : ctx->ev_stm)
+    if (!e) SF_HIP(hipEventCreate(&e.h), "event");
   auto lap = [&](int a, int b, int stage_ix) -> int {
     float ms = 0;
     SF_HIP(hipEventElapsedTime(&ms, ctx->ev_stm[a], ctx->ev_stm[b]), "elapsed");
@@ -1456,17 +1397,19 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   int rc = order_behind_last_call(ctx, s);
   if (rc) return rc;
   // the wrappers: k_inflate_head over every item, as any_wrapper reads one (a raw body is the whole item: no launch, no wait)
-  const size_t o_body = al16(sizeof(sf::InflateItem) * count), o_items = o_body + al16(16 * count);
-  if ((rc = grow(ctx, &ctx->d_sbt, &ctx->d_sbt_cap, o_items + sizeof(sf::StreamItem) * count, "stream item rows"))) return rc;
-  uint64_t* d_body = (uint64_t*)(ctx->d_sbt + o_body);
-  sf::StreamItem* d_items = (sf::StreamItem*)(ctx->d_sbt + o_items);
+  Carve T;  // wrapper rows | bodies | item rows
+  const size_t o_head = T.add<sf::InflateItem>(count), o_body = T.add<uint64_t>(2 * count), o_items = T.add<sf::StreamItem>(count);
+  if ((rc = ctx->d_sbt.grow(ctx, T.bytes(), "stream item rows"))) return rc;
+  sf::InflateItem* d_head = Carve::at<sf::InflateItem>(ctx->d_sbt, o_head);
+  uint64_t* d_body = Carve::at<uint64_t>(ctx->d_sbt, o_body);
+  sf::StreamItem* d_items = Carve::at<sf::StreamItem>(ctx->d_sbt, o_items);
   if (container != SFH_RAW) {
     for (size_t i = 0; i < count; ++i)
       head[i] = sf::InflateItem{(const uint8_t*)srcs[i], src_n[i], decodes(i) ? dst_cap[i] : kBig, d_body + 2 * i, nullptr, 0, 0,
                                 0, 0, 0, 0};
-    SF_HIP(hipMemcpyAsync(ctx->d_sbt, head.data(), sizeof(sf::InflateItem) * count, hipMemcpyHostToDevice, s), "H2D wrapper rows");
-    SF_HIP(sf::launch_inflate_head((sf::InflateItem*)ctx->d_sbt, (uint32_t)count, container, nullptr, nullptr, s), "launch k_inflate_head");
-    SF_HIP(hipMemcpyAsync(head.data(), ctx->d_sbt, sizeof(sf::InflateItem) * count, hipMemcpyDeviceToHost, s), "D2H wrapper rows");
+    SF_HIP(hipMemcpyAsync(d_head, head.data(), sizeof(sf::InflateItem) * count, hipMemcpyHostToDevice, s), "H2D wrapper rows");
+    SF_HIP(sf::launch_inflate_head(d_head, (uint32_t)count, container, nullptr, nullptr, s), "launch k_inflate_head");
+    SF_HIP(hipMemcpyAsync(head.data(), d_head, sizeof(sf::InflateItem) * count, hipMemcpyDeviceToHost, s), "D2H wrapper rows");
     SF_HIP(hipMemcpyAsync(body.data(), d_body, 16 * count, hipMemcpyDeviceToHost, s), "D2H bodies");
     SF_HIP(hipStreamSynchronize(s), "stream sync");
   }
@@ -1499,14 +1442,14 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   if (nc64 >= ((uint64_t)1 << 31)) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 nominal chunks (SFH_STREAM_CHUNK)", hipSuccess);
   const uint32_t nc = (uint32_t)nc64;
   // cand u64[nc] (then: the records' items u32[nc] | the follow list u32[nc]) | recs StreamChunk[nc] | list u32[nc]
-  const size_t o_rec = al16(8 * (size_t)nc), o_list = o_rec + al16(sizeof(sf::StreamChunk) * (size_t)nc);
-  const size_t stm_bytes = o_list + al16(4 * (size_t)nc);
-  if ((rc = grow(ctx, &ctx->d_stm, &ctx->d_stm_cap, stm_bytes, "stream chunk records"))) return rc;
-  uint64_t* d_cand = (uint64_t*)ctx->d_stm;
-  uint32_t* d_rec_item = (uint32_t*)ctx->d_stm;
+  Carve C;
+  const size_t o_cand = C.add<uint64_t>(nc), o_rec = C.add<sf::StreamChunk>(nc), o_list = C.add<uint32_t>(nc), stm_bytes = C.bytes();
+  if ((rc = ctx->d_stm.grow(ctx, stm_bytes, "stream chunk records"))) return rc;
+  uint64_t* d_cand = Carve::at<uint64_t>(ctx->d_stm, o_cand);
+  uint32_t* d_rec_item = Carve::at<uint32_t>(ctx->d_stm, o_cand);
   uint32_t* d_follow = d_rec_item + nc;
-  sf::StreamChunk* d_rec = (sf::StreamChunk*)(ctx->d_stm + o_rec);
-  uint32_t* d_list = (uint32_t*)(ctx->d_stm + o_list);
+  sf::StreamChunk* d_rec = Carve::at<sf::StreamChunk>(ctx->d_stm, o_rec);
+  uint32_t* d_list = Carve::at<uint32_t>(ctx->d_stm, o_list);
   std::vector<uint64_t> cand;
   std::vector<sf::StreamChunk> rec;
   std::vector<uint32_t> rec_item, chain(nl, 0);
@@ -1614,7 +1557,7 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
       }
     }
     (*out_off)[count] = o;
-    if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, std::max<uint64_t>(16, o), "output staging"))) return rc;
+    if ((rc = ctx->d_out.grow(ctx, std::max<uint64_t>(16, o), "output staging"))) return rc;
   }
   uint64_t cur = 0, peak = 0;
   for (uint32_t k = 0; k < nl; ++k) {
@@ -1653,8 +1596,8 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
     const size_t q0 = lb[b], q1 = lb[b + 1];
     const size_t wins_bytes = 2 * wins_n[b], plane_bytes = std::max<size_t>(16, 2 * plane_n[b]);
     peak = std::max<uint64_t>(peak, plane_bytes + wins_bytes);
-    if ((rc = grow(ctx, &ctx->d_plane, &ctx->d_plane_cap, plane_bytes, "symbol plane"))) return rc;
-    if (wins_bytes && (rc = grow(ctx, &ctx->d_wins, &ctx->d_wins_cap, wins_bytes, "stream windows"))) return rc;
+    if ((rc = ctx->d_plane.grow(ctx, plane_bytes / 2, "symbol plane"))) return rc;
+    if (wins_bytes && (rc = ctx->d_wins.grow(ctx, wins_bytes / 2, "stream windows"))) return rc;
     // D: the confirmed records of the batch's items
     wlist.clear();
     for (size_t q = q0; q < q1; ++q) {
@@ -1701,32 +1644,33 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
         for (uint32_t c = 0; c < nch; ++c) {
           const uint64_t ob = (uint64_t)c * sf::kChunk;
           // (an empty output: one empty row, at a real address)
-          sums.push_back(sf::BatchChunk{total[k] ? it.dst + ob : (const uint8_t*)ctx->d_plane, (uint32_t)std::min<uint64_t>(sf::kChunk, total[k] - ob), 0u});
+          sums.push_back(sf::BatchChunk{total[k] ? it.dst + ob : (const uint8_t*)ctx->d_plane.p, (uint32_t)std::min<uint64_t>(sf::kChunk, total[k] - ob), 0u});
         }
       }
     }
     if (resolve.empty()) continue;
     // compose | resolve | link | checksum rows | fold rows | fold statuses
-    const size_t o_res = al16(8 * compose.size()), o_link = o_res + al16(8 * resolve.size());
-    const size_t o_sums = o_link + al16(4 * link.size()), o_fold = o_sums + al16(sizeof(sf::BatchChunk) * sums.size());
-    const size_t o_fst = o_fold + al16(sizeof(sf::InflateItem) * fold.size()), rows_bytes = o_fst + al16(4 * fold.size());
-    if ((rc = grow(ctx, &ctx->d_sbr, &ctx->d_sbr_cap, rows_bytes, "stream group rows"))) return rc;
+    Carve G;
+    const size_t o_comp = G.add<sf::StreamGroup>(compose.size()), o_res = G.add<sf::StreamGroup>(resolve.size());
+    const size_t o_link = G.add<uint32_t>(link.size()), o_sums = G.add<sf::BatchChunk>(sums.size());
+    const size_t o_fold = G.add<sf::InflateItem>(fold.size()), o_fst = G.add<uint32_t>(fold.size());
+    if ((rc = ctx->d_sbr.grow(ctx, G.bytes(), "stream group rows"))) return rc;
     uint8_t* R = ctx->d_sbr;
-    SF_HIP(hipMemcpyAsync(R, compose.data(), 8 * compose.size(), hipMemcpyHostToDevice, s), "H2D group rows");
+    SF_HIP(hipMemcpyAsync(R + o_comp, compose.data(), 8 * compose.size(), hipMemcpyHostToDevice, s), "H2D group rows");
     SF_HIP(hipMemcpyAsync(R + o_res, resolve.data(), 8 * resolve.size(), hipMemcpyHostToDevice, s), "H2D group rows");
     if (!link.empty()) SF_HIP(hipMemcpyAsync(R + o_link, link.data(), 4 * link.size(), hipMemcpyHostToDevice, s), "H2D link rows");
-    SF_HIP(sf::launch_stream_resolve(ctx->d_plane, d_rec, d_items, (const sf::StreamGroup*)R, (uint32_t)compose.size(),
-                                     (const uint32_t*)(R + o_link), (uint32_t)link.size(), (const sf::StreamGroup*)(R + o_res),
+    SF_HIP(sf::launch_stream_resolve(ctx->d_plane, d_rec, d_items, Carve::at<const sf::StreamGroup>(R, o_comp), (uint32_t)compose.size(),
+                                     Carve::at<const uint32_t>(R, o_link), (uint32_t)link.size(), Carve::at<const sf::StreamGroup>(R, o_res),
                                      (uint32_t)resolve.size(), ctx->d_wins, s), "launch k_stream_resolve");
     if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[4], s), "event");
     if (!fold.empty()) {
       if ((rc = ensure_sums(ctx, (uint32_t)sums.size()))) return rc;
       SF_HIP(hipMemcpyAsync(R + o_sums, sums.data(), sizeof(sf::BatchChunk) * sums.size(), hipMemcpyHostToDevice, s), "H2D checksum rows");
       SF_HIP(hipMemcpyAsync(R + o_fold, fold.data(), sizeof(sf::InflateItem) * fold.size(), hipMemcpyHostToDevice, s), "H2D fold rows");
-      SF_HIP(sf::launch_checksum_batch((const sf::BatchChunk*)(R + o_sums), (uint32_t)sums.size(), container, ctx->ws.sums, s),
+      SF_HIP(sf::launch_checksum_batch(Carve::at<const sf::BatchChunk>(R, o_sums), (uint32_t)sums.size(), container, ctx->ws.sums, s),
              "launch k_checksum_batch");
-      SF_HIP(sf::launch_inflate_fold((const sf::InflateItem*)(R + o_fold), (uint32_t)fold.size(), nullptr, ctx->ws.sums, container,
-                                     (uint32_t*)(R + o_fst), nullptr, s), "launch k_inflate_fold");
+      SF_HIP(sf::launch_inflate_fold(Carve::at<const sf::InflateItem>(R, o_fold), (uint32_t)fold.size(), nullptr, ctx->ws.sums, container,
+                                     Carve::at<uint32_t>(R, o_fst), nullptr, s), "launch k_inflate_fold");
       bst.resize(fold.size());
       SF_HIP(hipMemcpyAsync(bst.data(), R + o_fst, 4 * fold.size(), hipMemcpyDeviceToHost, s), "D2H checksums");
     }
@@ -1879,16 +1823,13 @@ int sfh_create(sfh_ctx** out, int device) {
     const char* sc = getenv("SFH_STREAM_CHUNK");
     if (sc && atoll(sc) > 0) ctx->stream_chunk = (uint64_t)atoll(sc);
   }
-  hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess || (e = hipStreamCreate(&ctx->stream)) != hipSuccess ||
-      (e = hipMalloc(&ctx->d_total, sizeof(uint64_t))) != hipSuccess ||
-      (e = hipHostMalloc((void**)&ctx->h_total, sizeof(uint64_t), hipHostMallocDefault)) != hipSuccess ||
-      (e = hipMalloc(&ctx->d_value, 2 * sizeof(uint32_t))) != hipSuccess || (e = sf::init_kernels()) != hipSuccess ||
-      (e = sf::init_inflate_kernels()) != hipSuccess) {
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&ctx->stream.h) != hipSuccess || ctx->d_total.grow(ctx, 1, "result slot") ||
+      ctx->h_total.grow(ctx, 1, "result slot") || ctx->d_value.grow(ctx, 2, "result slot") || sf::init_kernels() != hipSuccess ||
+      sf::init_inflate_kernels() != hipSuccess) {
     sfh_destroy(ctx);
     return SFH_E_HIP;
   }
-  if (hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming) != hipSuccess) {
+  if (hipEventCreateWithFlags(&ctx->ev_done.h, hipEventDisableTiming) != hipSuccess) {
     sfh_destroy(ctx);
     return SFH_E_HIP;
   }
@@ -1906,68 +1847,7 @@ void sfh_destroy(sfh_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  free_compress_ws(ctx);
-  (void)hipFree(ctx->ws.tokens);
-  (void)hipFree(ctx->ws.seginfo);
-  (void)hipFree(ctx->ws.sums);
-  (void)hipFree(ctx->d_total);
-  if (ctx->h_total) (void)hipHostFree(ctx->h_total);
-  (void)hipFree(ctx->d_value);
-  (void)hipFree(ctx->d_dzinfo);
-  (void)hipFree(ctx->d_bgzfinfo);
-  (void)hipFree(ctx->d_bgzfcnt);
-  (void)hipFree(ctx->d_bgzfwalk);
-  (void)hipFree(ctx->d_bgzfix);
-  (void)hipFree(ctx->d_bgzfrows);
-  (void)hipFree(ctx->d_bgzfrng);
-  (void)hipFree(ctx->d_index);
-  (void)hipFree(ctx->d_sub);
-  for (hipEvent_t e : ctx->ev_inf) (void)hipEventDestroy(e);
-  (void)hipFree(ctx->d_in);
-  (void)hipFree(ctx->d_out);
-  for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
-  if (ctx->ev_done) (void)hipEventDestroy(ctx->ev_done);
-  for (int k = 0; k < sfh_ctx::kPipe; ++k) {
-    if (ctx->ev_in[k]) (void)hipEventDestroy(ctx->ev_in[k]);
-    if (ctx->ev_batch[k]) (void)hipEventDestroy(ctx->ev_batch[k]);
-  }
-  if (ctx->s_in) (void)hipStreamDestroy(ctx->s_in);
-  if (ctx->s_out) (void)hipStreamDestroy(ctx->s_out);
-  if (ctx->h_tot) (void)hipHostFree(ctx->h_tot);
-  (void)hipFree(ctx->d_sizes);
-  if (ctx->h_sizes) (void)hipHostFree(ctx->h_sizes);
-  if (ctx->ev_tab) (void)hipEventSynchronize(ctx->ev_tab);
-  if (ctx->h_tab) (void)hipHostFree(ctx->h_tab);
-  (void)hipFree(ctx->d_tab);
-  if (ctx->ev_tab) (void)hipEventDestroy(ctx->ev_tab);
-  if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-  (void)hipFree(ctx->d_bn);
-  if (ctx->h_bn) (void)hipHostFree(ctx->h_bn);
-  (void)hipFree(ctx->d_bix);
-  (void)hipFree(ctx->d_implied);
-  (void)hipFree(ctx->d_bstatus);
-  if (ctx->h_bstatus) (void)hipHostFree(ctx->h_bstatus);
-  (void)hipFree(ctx->d_anycnt);
-  (void)hipFree(ctx->d_any);
-  (void)hipFree(ctx->d_anyseg);
-  (void)hipFree(ctx->d_anyb);
-  (void)hipFree(ctx->d_anyix);
-  for (hipEvent_t e : ctx->ev_any)
-    if (e) (void)hipEventDestroy(e);
-  (void)hipFree(ctx->d_stm);
-  (void)hipFree(ctx->d_plane);
-  (void)hipFree(ctx->d_wins);
-  (void)hipFree(ctx->d_sbt);
-  (void)hipFree(ctx->d_sbr);
-  (void)hipFree(ctx->d_zip);
-  (void)hipFree(ctx->d_zipw);
-  (void)hipFree(ctx->d_zipbody);
-  if (ctx->h_zipw) (void)hipHostFree(ctx->h_zipw);
-  if (ctx->ev_zip) (void)hipEventDestroy(ctx->ev_zip);
-  for (hipEvent_t e : ctx->ev_stm)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;  // every member frees what it holds (sf_scratch.h), the context's stream last
 }
 
 const char* sfh_last_error(const sfh_ctx* ctx) { return ctx ? ctx->err : "null ctx"; }
@@ -2033,17 +1913,17 @@ int compress_host(sfh_ctx* ctx, const void* src, size_t n, void* dst, size_t cap
   if (dictzip && check_opt(opt, true)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   if (dictzip && cap < bound) return fail(ctx, SFH_E_DST_TOO_SMALL, "cap < sfh_compress_bound_container(n)", hipSuccess);
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = grow(ctx, &ctx->d_in, &ctx->d_in_cap, n ? n : 16, "input staging");
-  if (!rc) rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, bound, "output staging");
+  int rc = ctx->d_in.grow(ctx, n ? n : 16, "input staging");
+  if (!rc) rc = ctx->d_out.grow(ctx, bound, "output staging");
   if (rc) return rc;
   if (!ctx->s_in) {  // the copy streams, their events and the pinned size slots: on first use
-    SF_HIP(hipStreamCreateWithFlags(&ctx->s_in, hipStreamNonBlocking), "stream");
-    SF_HIP(hipStreamCreateWithFlags(&ctx->s_out, hipStreamNonBlocking), "stream");
+    SF_HIP(hipStreamCreateWithFlags(&ctx->s_in.h, hipStreamNonBlocking), "stream");
+    SF_HIP(hipStreamCreateWithFlags(&ctx->s_out.h, hipStreamNonBlocking), "stream");
     for (int k = 0; k < sfh_ctx::kPipe; ++k) {
-      SF_HIP(hipEventCreateWithFlags(&ctx->ev_in[k], hipEventDisableTiming), "event");
-      SF_HIP(hipEventCreateWithFlags(&ctx->ev_batch[k], hipEventDisableTiming), "event");
+      SF_HIP(hipEventCreateWithFlags(&ctx->ev_in[k].h, hipEventDisableTiming), "event");
+      SF_HIP(hipEventCreateWithFlags(&ctx->ev_batch[k].h, hipEventDisableTiming), "event");
     }
-    SF_HIP(hipHostMalloc((void**)&ctx->h_tot, sfh_ctx::kPipe * sizeof(uint64_t), hipHostMallocDefault), "pinned slots");
+    if (ctx->h_tot.grow(ctx, sfh_ctx::kPipe, "pinned slots")) return SFH_E_HIP;  // (this call's code for it, as before)
   }
   hipStream_t s = ctx->stream;
   // the staging buffers may still be read by copies of the previous call: they were all waited for below
@@ -2126,14 +2006,14 @@ int sfh_compress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, cons
   Staged B;
   hipStream_t s = ctx->stream;
   if ((rc = staged_up(ctx, B, count, srcs, src_n, slot.data()))) return rc;
-  if ((rc = grow_pair(ctx, &ctx->d_bn, &ctx->h_bn, &ctx->bn_cap, count, "batch sizes"))) return rc;
-  if ((rc = enqueue_batch(ctx, count, B.d_srcs.data(), src_n, B.d_dsts.data(), ctx->d_bn, opt, s)) != SFH_OK) {
+  if ((rc = ctx->bn.grow(ctx, count, "batch sizes"))) return rc;
+  if ((rc = enqueue_batch(ctx, count, B.d_srcs.data(), src_n, B.d_dsts.data(), ctx->bn.d, opt, s)) != SFH_OK) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
-  SF_HIP(hipMemcpyAsync(ctx->h_bn, ctx->d_bn, count * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "copy sizes");
+  SF_HIP(hipMemcpyAsync(ctx->bn.h, ctx->bn.d, count * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "copy sizes");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
-  for (size_t i = 0; i < count; ++i) out_n[i] = ctx->h_bn[i];
+  for (size_t i = 0; i < count; ++i) out_n[i] = ctx->bn.h[i];
   return staged_down(ctx, B, count, dsts, out_n, nullptr);  // each item's stream
 }
 
@@ -2182,14 +2062,14 @@ int sfh_decompress_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, co
   Staged B;
   hipStream_t s = ctx->stream;
   if ((rc = staged_up(ctx, B, count, srcs, src_n, dst_n))) return rc;
-  if (index) rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, ix_bytes, "index staging");
-  if (!rc && subindex) rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, sub_bytes, "sub-index staging");
+  if (index) rc = ctx->d_index.grow(ctx, segs + count, "index staging");
+  if (!rc && subindex) rc = ctx->d_sub.grow(ctx, segs * SFH_SUBINDEX_WORDS, "sub-index staging");
   if (!rc) rc = ensure_bstatus(ctx, count);
   if (rc) return rc;
   if (index) SF_HIP(hipMemcpyAsync(ctx->d_index, index, ix_bytes, hipMemcpyHostToDevice, s), "H2D index");
   if (subindex) SF_HIP(hipMemcpyAsync(ctx->d_sub, subindex, sub_bytes, hipMemcpyHostToDevice, s), "H2D sub-index");
-  if ((rc = enqueue_inflate_batch(ctx, count, B.d_srcs.data(), src_n, index ? ctx->d_index : nullptr, subindex ? ctx->d_sub : nullptr,
-                                  B.d_dsts.data(), dst_n, block_bytes, container, ctx->d_bstatus, nullptr, s)) != SFH_OK) {
+  if ((rc = enqueue_inflate_batch(ctx, count, B.d_srcs.data(), src_n, index ? ctx->d_index.p : nullptr, subindex ? ctx->d_sub.p : nullptr,
+                                  B.d_dsts.data(), dst_n, block_bytes, container, ctx->bstatus.d, nullptr, s)) != SFH_OK) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
@@ -2229,7 +2109,7 @@ int sfh_decompress_range_device(sfh_ctx* ctx, const void* d_src, size_t src_n, c
   hipStream_t s;
   if ((rc = begin_call(ctx, stream, &s)) || (rc = ensure_bstatus(ctx, 1))) return rc;
   rc = sfh_decompress_ranges_device_async(ctx, d_src, src_n, d_index, d_subindex, nseg, total_n, block_bytes, 1, &offset, &length,
-                                          dsts, ctx->d_bstatus, s);
+                                          dsts, ctx->bstatus.d, s);
   if (rc || (rc = read_bstatus(ctx, 1, status, s))) return rc;
   if (*status) snprintf(ctx->err, sizeof ctx->err, "range [%llu, +%llu): DecompressStatus %u", (unsigned long long)offset,
                         (unsigned long long)length, *status);
@@ -2274,8 +2154,8 @@ int sfh_decompress_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uin
     off[r + 1] = off[r] + len[r];
   }
   const size_t sub_bytes = P.rows.size() * SFH_SUBINDEX_WORDS * sizeof(uint32_t);
-  rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, std::max<uint64_t>(sizeof(uint64_t), off[count]), "index staging");
-  if (!rc && subindex) rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, std::max<size_t>(SFH_SUBINDEX_WORDS * sizeof(uint32_t), sub_bytes), "sub-index staging");
+  rc = ctx->d_index.grow(ctx, std::max<uint64_t>(1, off[count] / sizeof(uint64_t)), "index staging");
+  if (!rc && subindex) rc = ctx->d_sub.grow(ctx, std::max<size_t>(1, P.rows.size()) * SFH_SUBINDEX_WORDS, "sub-index staging");
   if (!rc) rc = ensure_bstatus(ctx, count);
   if (!rc) rc = stage_up(ctx, ctx->d_index, piece.data(), len.data(), off.data(), count, off[count], s);
   if (rc) return rc;
@@ -2294,7 +2174,7 @@ int sfh_decompress_ranges(sfh_ctx* ctx, const void* src, size_t src_n, const uin
     }
     if ((rc = stage_up(ctx, ctx->d_sub, piece.data(), len.data(), off.data(), count, sub_bytes, s))) return rc;
   }
-  if ((rc = enqueue_ranges(ctx, P, from.data(), B.d_dsts.data(), count, subindex != nullptr, ctx->d_bstatus, s)) != SFH_OK) {
+  if ((rc = enqueue_ranges(ctx, P, from.data(), B.d_dsts.data(), count, subindex != nullptr, ctx->bstatus.d, s)) != SFH_OK) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
@@ -2356,14 +2236,14 @@ int sfh_decompress(sfh_ctx* ctx, const void* src, size_t src_n, const uint64_t* 
   if (!ctx || !src || !index || !status || (!dst && dst_n)) return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   const size_t ix_bytes = (nseg + 1) * sizeof(uint64_t), sub_bytes = nseg * SFH_SUBINDEX_WORDS * sizeof(uint32_t);
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, ix_bytes, "index staging");
-  if (!rc && subindex) rc = grow(ctx, &ctx->d_sub, &ctx->d_sub_cap, sub_bytes, "sub-index staging");
+  int rc = ctx->d_index.grow(ctx, nseg + 1, "index staging");
+  if (!rc && subindex) rc = ctx->d_sub.grow(ctx, nseg * SFH_SUBINDEX_WORDS, "sub-index staging");
   if (!rc) rc = host_up(ctx, src, src_n, dst_n);
   if (rc) return rc;
   hipStream_t s = ctx->stream;
   SF_HIP(hipMemcpyAsync(ctx->d_index, index, ix_bytes, hipMemcpyHostToDevice, s), "H2D index");
   if (subindex) SF_HIP(hipMemcpyAsync(ctx->d_sub, subindex, sub_bytes, hipMemcpyHostToDevice, s), "H2D sub-index");
-  rc = sfh_decompress_device(ctx, ctx->d_in, src_n, ctx->d_index, subindex ? ctx->d_sub : nullptr, nseg, ctx->d_out,
+  rc = sfh_decompress_device(ctx, ctx->d_in, src_n, ctx->d_index, subindex ? ctx->d_sub.p : nullptr, nseg, ctx->d_out,
                              dst_n, block_bytes, status, s);
   if (rc) return rc;
   return *status ? SFH_OK : host_down(ctx, dst, dst_n);
@@ -2386,10 +2266,7 @@ int sfh_dz_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sfh_
   if (((uintptr_t)d_src & 3) || ((uintptr_t)d_index & 7)) return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, index 8)", hipSuccess);
   hipStream_t s;
   if (int rc = begin_call(ctx, stream, &s)) return rc;
-  if (!ctx->d_dzinfo) {
-    const hipError_t e = hipMalloc(&ctx->d_dzinfo, sizeof(sf::DzInfo));
-    if (e != hipSuccess) return fail(ctx, SFH_E_NOMEM, "dictzip info slot", e);
-  }
+  if (int rc = ctx->d_dzinfo.grow(ctx, 1, "dictzip info slot")) return rc;
   if (int rc = order_behind_last_call(ctx, s)) return rc;  // (the info slot is the context's)
   SF_HIP(sf::launch_dz_index((const uint8_t*)d_src, src_n, d_index, index_cap, ctx->d_dzinfo, s), "launch k_dz_index");
   sf::DzInfo r{};
@@ -2409,7 +2286,7 @@ int sfh_decompress_dz_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void
   hipStream_t s;
   if (int rc = begin_call(ctx, stream, &s)) return rc;
   const size_t entries = (size_t)SFH_DZ_MAX_CHUNKS + 1;
-  if (int rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, entries * sizeof(uint64_t), "index staging")) return rc;
+  if (int rc = ctx->d_index.grow(ctx, entries, "index staging")) return rc;
   sfh_dz_info info{};
   if (int rc = sfh_dz_read_index_device(ctx, d_src, src_n, &info, ctx->d_index, entries, s)) return rc;
   *dst_n_out = 0;
@@ -2492,12 +2369,9 @@ namespace {
 int bgzf_count_nodes(sfh_ctx* ctx, const uint8_t* d_src, size_t src_n, hipStream_t s, uint32_t* nn) {
   const uint32_t nb = sf::bgzf_scan_blocks(src_n);
   const size_t words = 2 * (size_t)nb + sf::any_scan_tmp_words(nb) + 1;
-  if (int rc = grow(ctx, &ctx->d_bgzfcnt, &ctx->d_bgzfcnt_cap, words * sizeof(uint32_t), "BGZF scan counts")) return rc;
-  if (!ctx->d_bgzfinfo) {
-    const hipError_t e = hipMalloc(&ctx->d_bgzfinfo, sizeof(sf::BgzfInfo));
-    if (e != hipSuccess) return fail(ctx, SFH_E_NOMEM, "BGZF info slot", e);
-  }
-  uint32_t* cnt = (uint32_t*)ctx->d_bgzfcnt;
+  if (int rc = ctx->d_bgzfcnt.grow(ctx, words, "BGZF scan counts")) return rc;
+  if (int rc = ctx->d_bgzfinfo.grow(ctx, 1, "BGZF info slot")) return rc;
+  uint32_t* cnt = ctx->d_bgzfcnt;
   uint32_t *off = cnt + nb, *tmp = off + nb, *total = tmp + sf::any_scan_tmp_words(nb);
   if (int rc = order_behind_last_call(ctx, s)) return rc;
   SF_HIP(sf::launch_bgzf_count(d_src, src_n, cnt, s), "launch k_bgzf_scan");
@@ -2510,8 +2384,8 @@ int bgzf_count_nodes(sfh_ctx* ctx, const uint8_t* d_src, size_t src_n, hipStream
 // ... and walked (one synchronisation): *r the info, member_off / out_off written when the file parses and cap holds them
 int bgzf_walk_nodes(sfh_ctx* ctx, const uint8_t* d_src, size_t src_n, uint32_t nn, uint64_t* d_member_off, uint64_t* d_out_off,
                     size_t cap, hipStream_t s, sf::BgzfInfo* r) {
-  if (int rc = grow(ctx, &ctx->d_bgzfwalk, &ctx->d_bgzfwalk_cap, sf::bgzf_walk_bytes(nn), "BGZF walk scratch")) return rc;
-  const uint32_t* off = (const uint32_t*)ctx->d_bgzfcnt + sf::bgzf_scan_blocks(src_n);
+  if (int rc = ctx->d_bgzfwalk.grow(ctx, sf::bgzf_walk_bytes(nn), "BGZF walk scratch")) return rc;
+  const uint32_t* off = ctx->d_bgzfcnt + sf::bgzf_scan_blocks(src_n);
   SF_HIP(sf::launch_bgzf_walk(d_src, src_n, off, nn, ctx->d_bgzfwalk, d_member_off, d_out_off, cap, ctx->d_bgzfinfo, s), "BGZF walk");
   SF_HIP(hipMemcpyAsync(r, ctx->d_bgzfinfo, sizeof *r, hipMemcpyDeviceToHost, s), "copy BGZF info");
   if (int rc = mark_call_end(ctx, s)) return rc;
@@ -2563,7 +2437,7 @@ int bgzf_decode_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_ds
   uint32_t nn = 0;
   if (int rc = bgzf_count_nodes(ctx, (const uint8_t*)d_src, src_n, s, &nn)) return rc;
   const size_t cap = (size_t)nn + 1;
-  if (int rc = grow(ctx, &ctx->d_bgzfix, &ctx->d_bgzfix_cap, 2 * cap * sizeof(uint64_t), "BGZF index")) return rc;
+  if (int rc = ctx->d_bgzfix.grow(ctx, 2 * cap, "BGZF index")) return rc;
   uint64_t *member_off = ctx->d_bgzfix, *out_off = ctx->d_bgzfix + cap;
   sf::BgzfInfo r{};
   if (int rc = bgzf_walk_nodes(ctx, (const uint8_t*)d_src, src_n, nn, member_off, out_off, cap, s, &r)) return rc;
@@ -2582,22 +2456,23 @@ int bgzf_decode_device(sfh_ctx* ctx, const void* d_src, size_t src_n, void* d_ds
   const uint32_t m = r.members, per = wide ? sf::bgzf::wide_batch(ctx->batch_chunks) : ctx->batch_chunks;
   if (wide && m > 0x7FFFFFFFu) return fail(ctx, SFH_E_INVALID_ARG, "2^31 members or more", hipSuccess);
   const uint32_t row = wide ? sf::kWideRow : sf::kChunk, nsums = (uint32_t)sf::bgzf::checksum_rows(m, wide);
-  const size_t o_items = (size_t)m * sizeof(sf::InflateSeg), o_clips = o_items + (size_t)m * sizeof(sf::InflateItem);
-  const size_t o_sums = o_clips + (size_t)m * sizeof(sf::InflateClip), o_implied = o_sums + (size_t)nsums * sizeof(sf::BatchChunk);
-  const size_t o_strips = o_implied + (size_t)m * 2 * sizeof(uint64_t), o_status = o_strips + (size_t)m * sizeof(sf::InflateStrip);
-  int rc = grow(ctx, &ctx->d_bgzfrows, &ctx->d_bgzfrows_cap, o_status + (size_t)m * sizeof(uint32_t), "BGZF decoder rows");
-  if (!rc) rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, (size_t)m * sizeof(sf::SegInfo), "segment records");
+  Carve L;
+  const size_t o_segs = L.add<sf::InflateSeg>(m), o_items = L.add<sf::InflateItem>(m), o_clips = L.add<sf::InflateClip>(m);
+  const size_t o_sums = L.add<sf::BatchChunk>(nsums), o_implied = L.add<uint64_t>(2 * (size_t)m), o_strips = L.add<sf::InflateStrip>(m);
+  const size_t o_status = L.add<uint32_t>(m);
+  int rc = ctx->d_bgzfrows.grow(ctx, L.bytes(), "BGZF decoder rows");
+  if (!rc) rc = ensure_seginfo(ctx, (size_t)m);
   if (!rc) rc = ensure_dtok(ctx, std::min(m, per) * (row / sf::kChunk));
   if (!rc) rc = ensure_sums(ctx, nsums);
   if (rc) return rc;
   uint8_t* R = ctx->d_bgzfrows;
-  sf::InflateSeg* segs = (sf::InflateSeg*)R;
-  sf::InflateItem* items = (sf::InflateItem*)(R + o_items);
-  sf::InflateClip* clips = (sf::InflateClip*)(R + o_clips);
-  sf::BatchChunk* sums = (sf::BatchChunk*)(R + o_sums);
-  uint64_t* implied = (uint64_t*)(R + o_implied);
-  sf::InflateStrip* strips = (sf::InflateStrip*)(R + o_strips);
-  uint32_t* d_status = (uint32_t*)(R + o_status);
+  sf::InflateSeg* segs = Carve::at<sf::InflateSeg>(R, o_segs);
+  sf::InflateItem* items = Carve::at<sf::InflateItem>(R, o_items);
+  sf::InflateClip* clips = Carve::at<sf::InflateClip>(R, o_clips);
+  sf::BatchChunk* sums = Carve::at<sf::BatchChunk>(R, o_sums);
+  uint64_t* implied = Carve::at<uint64_t>(R, o_implied);
+  sf::InflateStrip* strips = Carve::at<sf::InflateStrip>(R, o_strips);
+  uint32_t* d_status = Carve::at<uint32_t>(R, o_status);
   ctx->index_valid = false;
   ctx->bix_valid = false;
   ctx->ev_inf_valid = false;
@@ -2754,22 +2629,23 @@ int enqueue_bgzf_ranges(sfh_ctx* ctx, const sf::BgzfRange* ranges, size_t count,
   const size_t bytes = count * sizeof(sf::BgzfRange);
   // plan u32[2n] | row0 u32[n] | the scan's scratch and total | the rows' total (64-bit) | spans
   const size_t tmp_words = sf::any_scan_tmp_words(n);
-  const size_t o_row0 = 2 * count * sizeof(uint32_t), o_tmp = o_row0 + count * sizeof(uint32_t);
-  const size_t o_total = al16(o_tmp + (tmp_words + 1) * sizeof(uint32_t)), o_spans = o_total + 16;
-  int rc = stage_tables(ctx, bytes);
-  if (!rc) rc = grow(ctx, &ctx->d_bgzfrng, &ctx->d_bgzfrng_cap, o_spans + count * sizeof(sf::InflateSpan), "BGZF range plan");
+  Carve G;
+  const size_t o_plan = G.add<uint32_t>(2 * count), o_row0 = G.add<uint32_t>(count), o_tmp = G.add<uint32_t>(tmp_words + 1);
+  const size_t o_total = G.add<uint64_t>(2), o_spans = G.add<sf::InflateSpan>(count);  // (the total: a slot of 16 bytes)
+  int rc = ctx->tab.stage(ctx, bytes);
+  if (!rc) rc = ctx->d_bgzfrng.grow(ctx, G.bytes(), "BGZF range plan");
   if (rc) return rc;
-  memcpy(ctx->h_tab, ranges, bytes);
-  const sf::BgzfRange* t_ranges = (const sf::BgzfRange*)ctx->d_tab;
-  uint32_t* plan = (uint32_t*)ctx->d_bgzfrng;
-  uint32_t* row0 = (uint32_t*)(ctx->d_bgzfrng + o_row0);
-  uint32_t* tmp = (uint32_t*)(ctx->d_bgzfrng + o_tmp);
-  unsigned long long* d_rows = (unsigned long long*)(ctx->d_bgzfrng + o_total);
-  sf::InflateSpan* spans = (sf::InflateSpan*)(ctx->d_bgzfrng + o_spans);
+  memcpy(ctx->tab.h, ranges, bytes);
+  const sf::BgzfRange* t_ranges = Carve::at<const sf::BgzfRange>(ctx->tab.d, 0);
+  uint32_t* plan = Carve::at<uint32_t>(ctx->d_bgzfrng, o_plan);
+  uint32_t* row0 = Carve::at<uint32_t>(ctx->d_bgzfrng, o_row0);
+  uint32_t* tmp = Carve::at<uint32_t>(ctx->d_bgzfrng, o_tmp);
+  unsigned long long* d_rows = Carve::at<unsigned long long>(ctx->d_bgzfrng, o_total);
+  sf::InflateSpan* spans = Carve::at<sf::InflateSpan>(ctx->d_bgzfrng, o_spans);
   ctx->index_valid = false;
   ctx->bix_valid = false;
   ctx->ev_inf_valid = false;
-  if ((rc = upload_tables(ctx, bytes, s)) != SFH_OK) return rc;
+  if ((rc = ctx->tab.upload(ctx, bytes, s)) != SFH_OK) return rc;
   SF_HIP(sf::launch_bgzf_range_spans(t_ranges, n, d_out_off, info->members, plan, d_rows, s), "launch k_bgzf_range_spans");
   SF_HIP(sf::launch_scan_u32(plan + n, row0, n, tmp, tmp + tmp_words, s), "scan of the ranges' rows");
   unsigned long long total = 0;
@@ -2779,18 +2655,19 @@ int enqueue_bgzf_ranges(sfh_ctx* ctx, const sf::BgzfRange* ranges, size_t count,
   if (total > sf::bgzf::kMaxRangeRows) return fail(ctx, SFH_E_INVALID_ARG, "decode spans of more than 2^31 - 1 members in one call", hipSuccess);
   const uint32_t T = (uint32_t)total;
   const size_t t1 = std::max<size_t>(T, 1);
-  const size_t o_clips = t1 * sizeof(sf::InflateSeg), o_strips = o_clips + t1 * sizeof(sf::InflateClip);
-  const size_t o_implied = o_strips + t1 * sizeof(sf::InflateStrip), o_wst = o_implied + t1 * 2 * sizeof(uint64_t);
-  rc = grow(ctx, &ctx->d_bgzfrows, &ctx->d_bgzfrows_cap, o_wst + t1 * sizeof(uint32_t), "BGZF decoder rows");
-  if (!rc) rc = grow(ctx, &ctx->ws.seginfo, &ctx->seginfo_cap, t1 * sizeof(sf::SegInfo), "segment records");
+  Carve L;
+  const size_t o_segs = L.add<sf::InflateSeg>(t1), o_clips = L.add<sf::InflateClip>(t1), o_strips = L.add<sf::InflateStrip>(t1);
+  const size_t o_implied = L.add<uint64_t>(2 * t1), o_wst = L.add<uint32_t>(t1);
+  rc = ctx->d_bgzfrows.grow(ctx, L.bytes(), "BGZF decoder rows");
+  if (!rc) rc = ensure_seginfo(ctx, t1);
   if (!rc) rc = ensure_dtok(ctx, std::max(1u, std::min(T, per)) * (row / sf::kChunk));
   if (rc) return rc;
   uint8_t* R = ctx->d_bgzfrows;
-  sf::InflateSeg* segs = (sf::InflateSeg*)R;
-  sf::InflateClip* clips = (sf::InflateClip*)(R + o_clips);
-  sf::InflateStrip* strips = (sf::InflateStrip*)(R + o_strips);
-  uint64_t* implied = (uint64_t*)(R + o_implied);
-  uint32_t* wst = (uint32_t*)(R + o_wst);
+  sf::InflateSeg* segs = Carve::at<sf::InflateSeg>(R, o_segs);
+  sf::InflateClip* clips = Carve::at<sf::InflateClip>(R, o_clips);
+  sf::InflateStrip* strips = Carve::at<sf::InflateStrip>(R, o_strips);
+  uint64_t* implied = Carve::at<uint64_t>(R, o_implied);
+  uint32_t* wst = Carve::at<uint32_t>(R, o_wst);
   ctx->last_chunks = T;
   ctx->last_dtok_bytes = (size_t)std::min(T, per) * row * sizeof(uint32_t);
   SF_HIP(sf::launch_bgzf_range_rows(t_ranges, n, d_member_off, d_out_off, plan, row0, T, per, row, segs, clips, strips, implied, wst, spans, s),
@@ -2911,7 +2788,7 @@ int sfh_decompress_bgzf_ranges(sfh_ctx* ctx, const void* src, size_t src_n, cons
   hipStream_t s = ctx->stream;
   if ((rc = staged_up(ctx, B, count, piece.data(), len.data(), lengths))) return rc;
   const size_t ix_bytes = ((size_t)m + 1) * sizeof(uint64_t);
-  rc = grow(ctx, &ctx->d_bgzfix, &ctx->d_bgzfix_cap, 2 * ix_bytes, "BGZF index");
+  rc = ctx->d_bgzfix.grow(ctx, 2 * ((size_t)m + 1), "BGZF index");
   if (!rc) rc = ensure_bstatus(ctx, count);
   if (rc) return rc;
   uint64_t *d_moff = ctx->d_bgzfix, *d_ooff = ctx->d_bgzfix + (size_t)m + 1;
@@ -2922,7 +2799,7 @@ int sfh_decompress_bgzf_ranges(sfh_ctx* ctx, const void* src, size_t src_n, cons
     const uint8_t* base = (const uint8_t*)((uintptr_t)B.d_srcs[r] - (uintptr_t)pc[r].lo);
     ranges[r] = sf::BgzfRange{offsets[r], lengths[r], (uint8_t*)B.d_dsts[r], base, pc[r].lo, pc[r].lo + pc[r].n};
   }
-  if ((rc = enqueue_bgzf_ranges(ctx, ranges.data(), count, d_moff, d_ooff, info, ctx->d_bstatus, s)) != SFH_OK) {
+  if ((rc = enqueue_bgzf_ranges(ctx, ranges.data(), count, d_moff, d_ooff, info, ctx->bstatus.d, s)) != SFH_OK) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
@@ -3007,9 +2884,9 @@ int sfh_zip_read_index_device(sfh_ctx* ctx, const void* d_src, size_t src_n, sfh
   if (E.entries == 0) return SFH_OK;
   z::walk_central(cd, E.cd_size, E.cd_off, E.entries, (z::Entry*)entries, &total);
   const size_t bytes = (size_t)E.entries * sizeof(z::Entry);
-  if ((rc = grow(ctx, &ctx->d_zip, &ctx->d_zip_cap, bytes, "entry table"))) return rc;
+  if ((rc = ctx->d_zip.grow(ctx, bytes, "entry table"))) return rc;
   SF_HIP(hipMemcpyAsync(ctx->d_zip, entries, bytes, hipMemcpyHostToDevice, s), "H2D entry table");
-  SF_HIP(sf::launch_zip_locals(file, E.cd_off, (z::Entry*)ctx->d_zip, E.entries, s), "launch k_zip_locals");
+  SF_HIP(sf::launch_zip_locals(file, E.cd_off, Carve::at<z::Entry>(ctx->d_zip, 0), E.entries, s), "launch k_zip_locals");
   SF_HIP(hipMemcpyAsync(entries, ctx->d_zip, bytes, hipMemcpyDeviceToHost, s), "D2H entry table");
   if ((rc = mark_call_end(ctx, s))) return rc;
   SF_HIP(hipStreamSynchronize(s), "stream sync");
@@ -3061,18 +2938,18 @@ int zip_decode(sfh_ctx* ctx, const uint8_t* file, uint64_t src_n, const sfh_zip_
       return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 pieces, segments or scan waves in one call", hipSuccess);
     if ((rc = order_behind_last_call(ctx, s))) return rc;
     // one table for the call, sized before anything reads it: copy rows | piece rows | checksum rows | fold rows | statuses
-    const size_t b_copies = al16(copies.size() * sizeof(sf::ZipCopy)), b_pieces = al16(pieces.size() * sizeof(sf::ZipPiece));
-    const size_t o_sums = b_copies + b_pieces, o_fold = o_sums + al16((size_t)sum_rows * sizeof(sf::BatchChunk));
-    const size_t o_st = o_fold + al16(live * sizeof(sf::InflateItem));
-    if (ctx->d_zip_cap < o_st + 4 * live + 16 && ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");
-    if ((rc = grow(ctx, &ctx->d_zip, &ctx->d_zip_cap, o_st + 4 * live + 16, "ZIP decode rows"))) return rc;
+    Carve L;
+    const size_t o_copies = L.add<sf::ZipCopy>(copies.size()), o_pieces = L.add<sf::ZipPiece>(pieces.size());
+    const size_t o_sums = L.add<sf::BatchChunk>((size_t)sum_rows), o_fold = L.add<sf::InflateItem>(live), o_st = L.add<uint32_t>(live);
+    if (ctx->d_zip.cap < L.bytes() + 16 && (rc = wait_idle(ctx))) return rc;
+    if ((rc = ctx->d_zip.grow(ctx, L.bytes() + 16, "ZIP decode rows"))) return rc;
     uint8_t* T = ctx->d_zip;
     // the stored entries: one gather copy (the rows are host vectors that live to the call's last synchronisation)
     if (!copies.empty()) {
-      SF_HIP(hipMemcpyAsync(T, copies.data(), copies.size() * sizeof(sf::ZipCopy), hipMemcpyHostToDevice, s), "H2D copy rows");
-      SF_HIP(hipMemcpyAsync(T + b_copies, pieces.data(), pieces.size() * sizeof(sf::ZipPiece), hipMemcpyHostToDevice, s), "H2D piece rows");
-      SF_HIP(sf::launch_zip_store((const sf::ZipCopy*)T, (const sf::ZipPiece*)(T + b_copies), (uint32_t)pieces.size(), file, src_n, s),
-             "launch k_zip_store");
+      SF_HIP(hipMemcpyAsync(T + o_copies, copies.data(), copies.size() * sizeof(sf::ZipCopy), hipMemcpyHostToDevice, s), "H2D copy rows");
+      SF_HIP(hipMemcpyAsync(T + o_pieces, pieces.data(), pieces.size() * sizeof(sf::ZipPiece), hipMemcpyHostToDevice, s), "H2D piece rows");
+      SF_HIP(sf::launch_zip_store(Carve::at<const sf::ZipCopy>(T, o_copies), Carve::at<const sf::ZipPiece>(T, o_pieces), (uint32_t)pieces.size(),
+                                  file, src_n, s), "launch k_zip_store");
     }
     // the deflated entries: an item is the 4-byte aligned part of the file around the entry's data, its body the data
     const size_t nd = dfl.size();
@@ -3144,9 +3021,9 @@ int zip_decode(sfh_ctx* ctx, const uint8_t* file, uint64_t src_n, const sfh_zip_
       std::vector<uint32_t> fst(fold.size());
       SF_HIP(hipMemcpyAsync(T + o_sums, sums.data(), sums.size() * sizeof(sf::BatchChunk), hipMemcpyHostToDevice, s), "H2D checksum rows");
       SF_HIP(hipMemcpyAsync(T + o_fold, fold.data(), fold.size() * sizeof(sf::InflateItem), hipMemcpyHostToDevice, s), "H2D fold rows");
-      SF_HIP(sf::launch_checksum_batch((const sf::BatchChunk*)(T + o_sums), (uint32_t)sums.size(), SFH_GZIP, ctx->ws.sums, s), "launch k_checksum");
-      SF_HIP(sf::launch_inflate_fold((const sf::InflateItem*)(T + o_fold), (uint32_t)fold.size(), nullptr, ctx->ws.sums, SFH_GZIP,
-                                     (uint32_t*)(T + o_st), nullptr, s), "launch k_inflate_fold");
+      SF_HIP(sf::launch_checksum_batch(Carve::at<const sf::BatchChunk>(T, o_sums), (uint32_t)sums.size(), SFH_GZIP, ctx->ws.sums, s), "launch k_checksum");
+      SF_HIP(sf::launch_inflate_fold(Carve::at<const sf::InflateItem>(T, o_fold), (uint32_t)fold.size(), nullptr, ctx->ws.sums, SFH_GZIP,
+                                     Carve::at<uint32_t>(T, o_st), nullptr, s), "launch k_inflate_fold");
       SF_HIP(hipMemcpyAsync(fst.data(), T + o_st, 4 * fold.size(), hipMemcpyDeviceToHost, s), "D2H checksums");
       if ((rc = mark_call_end(ctx, s))) return rc;
       SF_HIP(hipStreamSynchronize(s), "stream sync");
@@ -3220,10 +3097,7 @@ int sfh_decompress_zip(sfh_ctx* ctx, const void* src, size_t src_n, const sfh_zi
     slot[i] = (!entries[i].status && entries[i].usize <= dst_cap[i] && entries[i].usize <= 0xFFFFFFFFull) ? entries[i].usize : 0;
   sf::stage::pack_layout(slot.data(), count, off.data());
   if ((rc = host_up(ctx, src, src_n, (size_t)off[count]))) return rc;
-  if (!ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, kStageBytes, hipHostMallocDefault) != hipSuccess) {
-    ctx->h_stage = nullptr;
-    return fail(ctx, SFH_E_NOMEM, "pinned staging", hipSuccess);
-  }
+  if ((rc = ctx->h_stage.grow(ctx, kStageBytes, "pinned staging"))) return rc;
   for (size_t i = 0; i < count; ++i) d_dsts[i] = ctx->d_out + off[i];
   if ((rc = zip_decode(ctx, ctx->d_in, src_n, entries, count, d_dsts.data(), slot.data(), status, ctx->stream))) {
     (void)hipStreamSynchronize(ctx->stream);
@@ -3320,41 +3194,28 @@ int enqueue_zip(sfh_ctx* ctx, size_t count, const void* const* d_srcs, const uin
     return fail(ctx, SFH_E_NOMEM, "host memory for the descriptor tables", hipSuccess);
   }
   // uploaded: items | wraps | pieces | names; device only: out_n u64[count] | off u64[count] | carry u64 | crc u32[count]
-  const size_t o_wraps = count * sizeof(sf::ZipItem), o_pieces = o_wraps + count * sizeof(sf::WrapItem);
-  const size_t o_names = o_pieces + pieces.size() * sizeof(sf::ZipPiece), up = al16(o_names + names_n);
-  const size_t o_outn = up, o_off = o_outn + 8 * count, o_carry = o_off + 8 * count, o_crc = o_carry + 16, bytes = o_crc + 4 * count + 16;
-  if (!ctx->ev_zip) SF_HIP(hipEventCreateWithFlags(&ctx->ev_zip, hipEventDisableTiming), "event");
-  if (ctx->zipw_pending) SF_HIP(hipEventSynchronize(ctx->ev_zip), "wait for the previous call's table copy");  // (it reads h_zipw)
-  ctx->zipw_pending = false;
-  if (ctx->h_zipw_cap < up) {
-    if (ctx->h_zipw) (void)hipHostFree(ctx->h_zipw);
-    ctx->h_zipw = nullptr;
-    ctx->h_zipw_cap = 0;
-    if (hipHostMalloc((void**)&ctx->h_zipw, up, hipHostMallocDefault) != hipSuccess) return fail(ctx, SFH_E_NOMEM, "pinned ZIP tables", hipSuccess);
-    ctx->h_zipw_cap = up;
-  }
-  if ((ctx->d_zipw_cap < bytes || ctx->d_zipbody_cap < widest) && ctx->busy) SF_HIP(hipEventSynchronize(ctx->ev_done), "wait for the last call");
-  int rc = grow(ctx, &ctx->d_zipw, &ctx->d_zipw_cap, bytes, "ZIP tables");
-  if (!rc) rc = grow(ctx, &ctx->d_zipbody, &ctx->d_zipbody_cap, widest, "ZIP body scratch");
+  Carve L;
+  const size_t o_items = L.add<sf::ZipItem>(count), o_wraps = L.add<sf::WrapItem>(count), o_pieces = L.add<sf::ZipPiece>(pieces.size());
+  const size_t o_names = L.add<uint8_t>(names_n), up = L.bytes();
+  const size_t o_outn = L.add<uint64_t>(count), o_off = L.add<uint64_t>(count), o_carry = L.add<uint64_t>(2), o_crc = L.add<uint32_t>(count);
+  int rc = ctx->zipw.stage(ctx, up, L.bytes() + 16 - up);
+  if (!rc && ctx->d_zipbody.cap < widest) rc = wait_idle(ctx);  // (the last call's kernels read it)
+  if (!rc) rc = ctx->d_zipbody.grow(ctx, widest, "ZIP body scratch");
   if (rc) return rc;
-  memcpy(ctx->h_zipw, items.data(), count * sizeof(sf::ZipItem));
-  memcpy(ctx->h_zipw + o_wraps, wraps.data(), count * sizeof(sf::WrapItem));
-  memcpy(ctx->h_zipw + o_pieces, pieces.data(), pieces.size() * sizeof(sf::ZipPiece));
-  for (size_t i = 0; i < count; ++i) memcpy(ctx->h_zipw + o_names + items[i].name_off, names[i], name_len[i]);
-  uint8_t* T = ctx->d_zipw;
-  const sf::ZipItem* t_items = (const sf::ZipItem*)T;
-  const sf::WrapItem* t_wraps = (const sf::WrapItem*)(T + o_wraps);
-  const sf::ZipPiece* t_pieces = (const sf::ZipPiece*)(T + o_pieces);
-  uint64_t* t_outn = (uint64_t*)(T + o_outn);
-  uint64_t* t_off = (uint64_t*)(T + o_off);
-  uint64_t* t_carry = (uint64_t*)(T + o_carry);
-  uint32_t* t_crc = (uint32_t*)(T + o_crc);
-  if ((rc = order_behind_last_call(ctx, s))) return rc;
-  if (up) {
-    SF_HIP(hipMemcpyAsync(T, ctx->h_zipw, up, hipMemcpyHostToDevice, s), "ZIP tables");
-    SF_HIP(hipEventRecord(ctx->ev_zip, s), "event");
-    ctx->zipw_pending = true;
-  }
+  uint8_t* H = ctx->zipw.h;
+  memcpy(H + o_items, items.data(), count * sizeof(sf::ZipItem));
+  memcpy(H + o_wraps, wraps.data(), count * sizeof(sf::WrapItem));
+  memcpy(H + o_pieces, pieces.data(), pieces.size() * sizeof(sf::ZipPiece));
+  for (size_t i = 0; i < count; ++i) memcpy(H + o_names + items[i].name_off, names[i], name_len[i]);
+  uint8_t* T = ctx->zipw.d;
+  const sf::ZipItem* t_items = Carve::at<const sf::ZipItem>(T, o_items);
+  const sf::WrapItem* t_wraps = Carve::at<const sf::WrapItem>(T, o_wraps);
+  const sf::ZipPiece* t_pieces = Carve::at<const sf::ZipPiece>(T, o_pieces);
+  uint64_t* t_outn = Carve::at<uint64_t>(T, o_outn);
+  uint64_t* t_off = Carve::at<uint64_t>(T, o_off);
+  uint64_t* t_carry = Carve::at<uint64_t>(T, o_carry);
+  uint32_t* t_crc = Carve::at<uint32_t>(T, o_crc);
+  if ((rc = up ? ctx->zipw.upload(ctx, up, s) : order_behind_last_call(ctx, s))) return rc;
   SF_HIP(hipMemsetAsync(t_carry, 0, 16, s), "clear the carry");
   if ((rc = mark_call_end(ctx, s))) return rc;  // (the batch calls below take their place behind this on s)
   for (const Group& g : groups) {
@@ -3400,7 +3261,7 @@ int sfh_compress_zip(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   Staged B;
   hipStream_t s = ctx->stream;
   if ((rc = staged_up(ctx, B, count, srcs, src_n, nullptr))) return rc;
-  if ((rc = grow(ctx, &ctx->d_out, &ctx->d_out_cap, sfh_zip_bound(count, src_n, name_len), "output staging"))) return rc;
+  if ((rc = ctx->d_out.grow(ctx, sfh_zip_bound(count, src_n, name_len), "output staging"))) return rc;
   if ((rc = enqueue_zip(ctx, count, B.d_srcs.data(), src_n, names, name_len, ctx->d_out, ctx->d_total, opt, s))) {
     (void)hipStreamSynchronize(s);
     return rc;
@@ -3435,7 +3296,7 @@ int sfh_recover_index(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t cont
   if (!index || dst_n == SFH_SIZE_FROM_TRAILER || nseg != (size_t)chunks_of((size_t)dst_n))
     return fail(ctx, SFH_E_INVALID_ARG, "index, nseg = max(1, ceil(dst_n / 32768))", hipSuccess);
   SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = grow(ctx, &ctx->d_anyix, &ctx->d_anyix_cap, (nseg + 1) * sizeof(uint64_t), "recovered index");
+  int rc = ctx->d_anyix.grow(ctx, nseg + 1, "recovered index");
   if (!rc) rc = host_up(ctx, src, src_n, depends ? nseg : 0);  // (the flags come down through d_out)
   if (rc) return rc;
   hipStream_t s = ctx->stream;
@@ -3521,7 +3382,7 @@ int sfh_recover_index_batch(sfh_ctx* ctx, size_t count, const void* const* srcs,
   Staged B;
   hipStream_t s = ctx->stream;
   if ((rc = staged_up(ctx, B, count, srcs, src_n, nullptr))) return rc;  // (no output staging: the index comes down by itself)
-  if ((rc = grow(ctx, &ctx->d_index, &ctx->d_index_cap, entries * sizeof(uint64_t), "index staging"))) return rc;
+  if ((rc = ctx->d_index.grow(ctx, entries, "index staging"))) return rc;
   AnyBatch R;
   if ((rc = any_batch_recover(ctx, count, B.d_srcs.data(), src_n, container, nullptr, dst_n, ctx->d_index, s, R))) {
     (void)hipStreamSynchronize(s);
@@ -3638,7 +3499,7 @@ int sfh_last_inflate_ms(sfh_ctx* ctx, float ms[SFH_INFLATE_NSTAGES]) {
   for (uint32_t b = 0; b < ctx->ev_inf_batches; ++b)  // a stage's time over every batch of the call
     for (int k = 0; k < SFH_INFLATE_NSTAGES; ++k) {
       float t = 0.f;
-      const hipEvent_t* ev = &ctx->ev_inf[(size_t)b * (SFH_INFLATE_NSTAGES + 1)];
+      const Event* ev = &ctx->ev_inf[(size_t)b * (SFH_INFLATE_NSTAGES + 1)];
       SF_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1]), "elapsed");
       ms[k] += t;
     }
@@ -3801,17 +3662,9 @@ int sfh_gather_streams(sfh_ctx* ctx, void* nccl_comm, int root, const void* d_st
   // same on all ranks, and the root's two addresses let EVERY rank judge the root's own placement -- so every rank reaches
   // the same verdict BEFORE any transfer is posted, and nobody is left waiting in a send whose receive was refused.
   constexpr int kRec = 5;
-  if (ctx->sizes_cap < nranks) {
-    (void)hipFree(ctx->d_sizes);
-    (void)hipHostFree(ctx->h_sizes);
-    ctx->d_sizes = ctx->h_sizes = nullptr;
-    ctx->sizes_cap = 0;
-    SF_HIP(hipMalloc(&ctx->d_sizes, ((size_t)nranks + 1) * kRec * sizeof(uint64_t)), "sizes");
-    SF_HIP(hipHostMalloc((void**)&ctx->h_sizes, ((size_t)nranks + 1) * kRec * sizeof(uint64_t), hipHostMallocDefault), "pinned sizes");
-    ctx->sizes_cap = nranks;
-  }
-  uint64_t* const d_mine = ctx->d_sizes + (size_t)nranks * kRec;  // this rank's record, behind the gathered ones
-  uint64_t* const h_mine = ctx->h_sizes + (size_t)nranks * kRec;
+  if (ctx->sizes.grow(ctx, ((size_t)nranks + 1) * kRec, "sizes")) return SFH_E_HIP;  // (this call's code for it, as before)
+  uint64_t* const d_mine = ctx->sizes.d + (size_t)nranks * kRec;  // this rank's record, behind the gathered ones
+  uint64_t* const h_mine = ctx->sizes.h + (size_t)nranks * kRec;
   h_mine[1] = base;
   h_mine[2] = cap;
   h_mine[3] = (uint64_t)(uintptr_t)d_stream;
@@ -3821,8 +3674,8 @@ int sfh_gather_streams(sfh_ctx* ctx, void* nccl_comm, int root, const void* d_st
   if (rc) return rc;
   SF_HIP(hipMemcpyAsync(d_mine + 1, h_mine + 1, (kRec - 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s), "record");
   SF_HIP(hipMemcpyAsync(d_mine, d_size, sizeof(uint64_t), hipMemcpyDeviceToDevice, s), "size word");
-  if ((rc = R.AllGather(d_mine, ctx->d_sizes, kRec, kNcclUint64, nccl_comm, s)) != 0) return comm_fail(ctx, "ncclAllGather", rc);
-  SF_HIP(hipMemcpyAsync(ctx->h_sizes, ctx->d_sizes, (size_t)nranks * kRec * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "sizes read-back");
+  if ((rc = R.AllGather(d_mine, ctx->sizes.d, kRec, kNcclUint64, nccl_comm, s)) != 0) return comm_fail(ctx, "ncclAllGather", rc);
+  SF_HIP(hipMemcpyAsync(ctx->sizes.h, ctx->sizes.d, (size_t)nranks * kRec * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "sizes read-back");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
   // (no exception may cross the C boundary: the offsets live in a nothrow allocation)
   struct Free { void operator()(uint64_t* p) const { free(p); } };
@@ -3831,7 +3684,7 @@ int sfh_gather_streams(sfh_ctx* ctx, void* nccl_comm, int root, const void* d_st
   uint64_t* const off = off_mem.get();
   bool agree = true;
   for (int r = 0; r < nranks; ++r) {
-    const uint64_t* rec = ctx->h_sizes + (size_t)r * kRec;
+    const uint64_t* rec = ctx->sizes.h + (size_t)r * kRec;
     h_sizes[r] = rec[0];
     agree = agree && rec[1] == base && rec[2] == cap;
   }
@@ -3842,7 +3695,7 @@ int sfh_gather_streams(sfh_ctx* ctx, void* nccl_comm, int root, const void* d_st
   {
     // the root's own stream: already at its place in d_out, or clear of everything the gather writes -- anything between
     // would be overwritten by a peer's bytes or copied onto itself
-    const uint64_t* rr = ctx->h_sizes + (size_t)root * kRec;
+    const uint64_t* rr = ctx->sizes.h + (size_t)root * kRec;
     const uint64_t rs = rr[3], ro = rr[4], rn = rr[0];
     const uint64_t w0 = ro + base, w1 = ro + off[(size_t)nranks];
     if (rn && rs != ro + off[(size_t)root] && rs < w1 && rs + rn > w0)
@@ -3876,7 +3729,7 @@ int sfh_last_stage_ms(sfh_ctx* ctx, float ms[SFH_NSTAGES]) {
   // summed over every batch of the call (a > 1 GiB device call or any host-buffer call runs several)
   for (int k = 0; k < SFH_NSTAGES; ++k) ms[k] = 0.f;
   for (uint32_t b = 0; b < ctx->ev_batches; ++b) {
-    const hipEvent_t* e = &ctx->ev[(size_t)b * sfh_ctx::kEvPerBatch];
+    const Event* e = &ctx->ev[(size_t)b * sfh_ctx::kEvPerBatch];
     for (int k = 0; k < 4; ++k) {
       float t = 0.f;
       SF_HIP(hipEventElapsedTime(&t, e[k], e[k + 1]), "elapsed");

@@ -1,8 +1,9 @@
 // sf_stage_plan.h -- the host-buffer entry points' way through one pinned staging buffer: `count` items lie packed in a device
 // buffer, item i at bytes [off[i], off[i] + len[i]) of it (off ascending, the ranges disjoint: pack_layout), and the packed
 // layout [0, total) moves in pieces of at most `piece` bytes, because the pinned buffer holds one piece.  An item may straddle any
-// number of pieces.  Plain C++, no HIP: the copy between the staging and the device is the caller's (`xfer`), so the tests
-// compile these loops for the host as well (tests/cpp/stage_plan_host.cpp).
+// number of pieces.  Also here, next to the 16-byte rounding: Carve, which lays the arrays of one scratch buffer out.  Plain C++,
+// no HIP: the copy between the staging and the device is the caller's (`xfer`), so the tests compile these loops for the host
+// as well (tests/cpp/stage_plan_host.cpp, tests/cpp/stage_layout_host.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -15,6 +16,22 @@ namespace stage {
 
 // The packed layout itself: items lie 16 bytes aligned (the device paths' alignment rules hold for every item of the staging).
 inline uint64_t al16(uint64_t b) { return (b + 15) / 16 * 16; }
+
+// One buffer carved into arrays, piece after piece: add<T>(count) is the offset of an array of `count` T -- always a multiple of
+// 16, whatever the pieces before it hold -- and bytes() what the pieces added so far take.  A host table and its device twin are
+// carved once and read with at<T>(base, off) from either base.
+struct Carve {
+  size_t end = 0;
+  template <class T>
+  size_t add(size_t count) {
+    const size_t off = end;
+    end = (size_t)al16(off + count * sizeof(T));
+    return off;
+  }
+  size_t bytes() const { return end; }
+  template <class T>
+  static T* at(uint8_t* base, size_t off) { return reinterpret_cast<T*>(base + off); }
+};
 
 // off[0 .. count] from `count` slot sizes: slot i is [off[i], off[i] + slot[i]), off[0] = 0, every offset a multiple of 16,
 // off[count] the bytes the layout takes.  (A slot of no bytes takes none: it shares its offset with the next one.)

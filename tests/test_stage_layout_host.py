@@ -1,7 +1,9 @@
 """Where the batched host-buffer entry points put their items, compiled for the host with every warning an error: the packed
 layout (starflate_amd/csrc/sf_stage_plan.h: pack_layout, the one place the 16-byte rounding is written) and the piece of the
 stream that sfh_decompress_ranges uploads for a decode span (sf_range_plan.h: source_piece).  Both are checked against the
-arithmetic the entry points used when each wrote it out by hand, restated here."""
+arithmetic the entry points used when each wrote it out by hand, restated here.  Carve (sf_stage_plan.h) is how the C-ABI lays
+several arrays out in one scratch buffer: every piece starts at a multiple of 16, and the totals the library reports
+(sfh_last_stream_stats, sfh_last_decode_scratch_bytes) are what the chained al16 sums gave before it."""
 import ctypes as C
 import os
 import subprocess
@@ -24,6 +26,12 @@ def lib(tmp_path_factory):
     L.sfl_pack_layout.restype = None
     L.sfl_source_piece.argtypes = [C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
     L.sfl_source_piece.restype = None
+    L.sfl_carve.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.sfl_carve.restype = C.c_uint64
+    L.sfl_carve_at.argtypes = [C.c_uint64]
+    L.sfl_carve_at.restype = C.c_uint64
+    L.sfl_stream_scratch.argtypes = [C.c_uint64, C.c_void_p]
+    L.sfl_stream_scratch.restype = None
     return L
 
 
@@ -120,3 +128,74 @@ def test_source_piece(lib, name):
         assert (lo, n) == (w_lo, w_hi - w_lo)
         if nrows == 0:
             assert (lo, n) == (0, 0)
+
+
+def al16(b):
+    return (b + 15) // 16 * 16
+
+
+def carve(L, pieces):
+    esize = np.asarray([e for e, _ in pieces] or [1], np.uint32)
+    count = np.asarray([c for _, c in pieces] or [0], np.uint64)
+    off = np.full(len(pieces) + 1, 0xDEAD, np.uint64)  # (+1: a guard word)
+    total = L.sfl_carve(esize.ctypes.data, count.ctypes.data, len(pieces), off.ctypes.data)
+    assert off[len(pieces)] == 0xDEAD and total != 2**64 - 1
+    return [int(v) for v in off[: len(pieces)]], int(total)
+
+
+# (element size, count) per piece: every element size the shim has a type for, counts 0 and 1 among them
+CARVES = {
+    "nothing": [],
+    "one byte": [(1, 1)],
+    "one empty piece": [(8, 0)],
+    "every size once": [(1, 1), (2, 1), (4, 1), (8, 1), (12, 1), (72, 1)],
+    "every size, odd counts": [(72, 3), (1, 17), (12, 5), (2, 9), (8, 3), (4, 1000), (1, 0), (4, 7)],
+    "empty pieces everywhere": [(4, 0), (1, 5), (8, 0), (8, 0), (12, 1), (2, 0)],
+    "aligned already": [(8, 2), (4, 4), (1, 16), (72, 2), (12, 4)],
+    "bytes around the alignment": [(1, 15), (1, 16), (1, 17), (1, 32769), (2, 1)],
+}
+
+
+@pytest.mark.parametrize("name", list(CARVES))
+def test_carve_pieces_are_aligned_disjoint_and_in_order(lib, name):
+    pieces = CARVES[name]
+    off, total = carve(lib, pieces)
+    at = 0  # what chaining al16 by hand gives: o_next = al16(o + bytes of the piece)
+    for (esize, count), o in zip(pieces, off):
+        assert o % 16 == 0
+        assert o == at  # in order, and behind the piece before it: disjoint
+        at = al16(o + esize * count)
+    assert total == at and total % 16 == 0
+    if pieces:
+        assert total >= off[-1] + pieces[-1][0] * pieces[-1][1]  # bytes() covers the last piece
+    else:
+        assert total == 0
+
+
+def test_carve_random(lib):
+    rng = np.random.default_rng(11)
+    for _ in range(200):
+        pieces = [(int(rng.choice([1, 2, 4, 8, 12, 72])), int(rng.choice([0, 1, int(rng.integers(0, 5000))]))) for _ in range(int(rng.integers(0, 12)))]
+        off, total = carve(lib, pieces)
+        at = 0
+        for (esize, count), o in zip(pieces, off):
+            assert o == at and o % 16 == 0
+            at = al16(o + esize * count)
+        assert total == at
+
+
+def test_carve_at_is_base_plus_offset(lib):
+    for o in (0, 16, 48):
+        assert lib.sfl_carve_at(o) == o
+
+
+@pytest.mark.parametrize("nc", [1, 2, 1000])
+def test_stream_scratch_total_is_the_chained_sum(lib, nc):
+    """cand | recs | list of the stream driver: the total it reports (sfh_last_stream_stats count 5, less the plane and windows)
+    is what al16(8 nc) + al16(sizeof(StreamChunk) nc) + al16(4 nc) was when the driver chained the offsets by hand."""
+    out = np.zeros(5, np.uint64)
+    lib.sfl_stream_scratch(nc, out.ctypes.data)
+    o_cand, o_rec, o_list, total, rec = (int(v) for v in out)
+    assert rec == 48  # sf_stream_chain.h
+    assert (o_cand, o_rec, o_list) == (0, al16(8 * nc), al16(8 * nc) + al16(rec * nc))
+    assert total == al16(8 * nc) + al16(rec * nc) + al16(4 * nc)
