@@ -625,7 +625,8 @@ class Compressor:
     def decompress_stream_tensor(self, stream, out_n=None, container="raw", out=None, hip_stream=None):
         """stream: 1-D uint8 CUDA tensor -> (out tensor of the decoded bytes, DecompressStatus int), decoded on the GPU from
         speculative block starts (no index, no flush points needed).  out_n: the output capacity (None: a size query first,
-        then exactly the output size); out: a uint8 CUDA tensor of at least out_n bytes.  Synchronises the stream."""
+        then exactly the output size -- gzip: ISIZE where that is more, the room a gzip decode asks for whatever its body
+        produces); out: a uint8 CUDA tensor of at least out_n bytes.  Synchronises the stream."""
         import torch
 
         self._check_tensor(stream)
@@ -638,7 +639,7 @@ class Compressor:
                                                             C.c_void_p(s)))
             if st.value:
                 return stream[:0], st.value
-            out_n = n.value
+            out_n = max(n.value, _gzip_room(stream, kind))
         out_n = int(out_n)
         if out is None:
             out = torch.empty(max(out_n, 1), dtype=torch.uint8, device=stream.device)
@@ -652,7 +653,9 @@ class Compressor:
 
     def decompress_stream(self, data, out_n=None, container="raw"):
         """Host buffers: a bytes-like raw / zlib / gzip stream (one member) -> (bytes, DecompressStatus int), on the GPU with no
-        index and no flush points.  out_n: the output capacity (None: a size query first).  b"" unless the status is 0."""
+        index and no flush points.  out_n: the output capacity (None: a size query first, then the queried size -- gzip: ISIZE
+        where that is more, so that a trailer that claims more than the body gives is Error, as with any dst that holds
+        ISIZE bytes).  b"" unless the status is 0."""
         src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
         kind = _container(container)
         st, n = C.c_uint32(0), C.c_uint64(0)
@@ -661,7 +664,7 @@ class Compressor:
             self._check(self._lib.sfh_inflate_stream(self._h, sp, src.size, kind, None, 0, C.byref(n), C.byref(st)))
             if st.value:
                 return b"", st.value
-            out_n = n.value
+            out_n = max(n.value, _gzip_room(src, kind))
         out_n = int(out_n)
         dst = np.empty(max(out_n, 1), dtype=np.uint8)
         self._check(self._lib.sfh_inflate_stream(self._h, sp, src.size, kind, dst.ctypes.data, out_n, C.byref(n), C.byref(st)))
@@ -680,7 +683,7 @@ class Compressor:
     def decompress_stream_batch(self, streams, sizes=None, container="raw"):
         """Host buffers: bytes-like raw / zlib / gzip streams (one member each) -> (list of bytes, list of DecompressStatus ints),
         every item exactly what decompress_stream gives for it alone.  sizes: the output capacities (None: a size-query call
-        first, then exactly the output sizes).  An item whose status is not 0 comes back as b""."""
+        first, then the queried sizes -- gzip: ISIZE where that is more).  An item whose status is not 0 comes back as b""."""
         srcs, n, caps, kind = _stream_batch_args(streams, sizes, container)
         k = len(srcs)
         sp = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a in srcs])
@@ -688,7 +691,7 @@ class Compressor:
         st = (C.c_uint32 * k)()
         if caps is None:
             self._check(self._lib.sfh_inflate_stream_batch(self._h, k, sp, n, kind, None, None, out_n, st))
-            caps = [int(out_n[i]) if st[i] == 0 else 0 for i in range(k)]
+            caps = [max(int(out_n[i]), _gzip_room(srcs[i], kind)) if st[i] == 0 else 0 for i in range(k)]
             live = [st[i] == 0 for i in range(k)]
             first = [int(st[i]) for i in range(k)]
         else:
@@ -704,7 +707,7 @@ class Compressor:
     def decompress_stream_batch_tensors(self, streams, sizes=None, container="raw", outs=None, hip_stream=None):
         """Device buffers: 1-D uint8 CUDA tensors -> (list of output tensors, list of DecompressStatus ints); each output is
         exactly the item's decoded bytes (empty unless its status is 0).  sizes: the output capacities (None: a size-query
-        call first); outs: one uint8 CUDA tensor of at least sizes[i] bytes per item (default: new ones).  Synchronises the
+        call first, then the queried sizes -- gzip: ISIZE where that is more); outs: one uint8 CUDA tensor of at least sizes[i] bytes per item (default: new ones).  Synchronises the
         stream."""
         import torch
 
@@ -722,7 +725,7 @@ class Compressor:
         live, first = [True] * k, [0] * k
         if sizes is None:
             self._check(self._lib.sfh_inflate_stream_batch_device(self._h, k, sp, n, kind, None, None, out_n, st, C.c_void_p(s)))
-            sizes = [int(out_n[i]) if st[i] == 0 else 0 for i in range(k)]
+            sizes = [max(int(out_n[i]), _gzip_room(streams[i], kind)) if st[i] == 0 else 0 for i in range(k)]
             live = [st[i] == 0 for i in range(k)]
             first = [int(st[i]) for i in range(k)]
         caps = [int(m) for m in sizes]
@@ -1233,6 +1236,16 @@ def _container(container):
     if kind not in (0, 1, 2):
         raise ValueError("container: raw, zlib or gzip")
     return kind
+
+
+def _gzip_room(stream, kind):
+    """the capacity a decode behind a size query needs beyond the queried size: container.hpp decodes a gzip body into the
+    first ISIZE bytes of a dst that holds at least ISIZE, so a trailer that claims more than the body produces is that
+    decode's Error, not a DstTooSmall of the caller's making.  stream: a numpy array or a CUDA tensor that passed its query."""
+    if kind != 2:
+        return 0
+    tail = stream[-4:]
+    return int.from_bytes((tail if isinstance(tail, np.ndarray) else tail.cpu().numpy()).tobytes(), "little")
 
 
 def _isize(tail, kind):

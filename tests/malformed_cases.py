@@ -587,6 +587,24 @@ def _bad_segment(writer, out_n, prefix, rng, tail=None):
     return seg, c.w + extra, head + bytes(c.out[len(head):])
 
 
+def class_behind(writer, head=b"", tail=None, final=True):
+    """a class written from a byte boundary behind good blocks whose output is `head` -> (its stream bytes, cut where the class
+    cuts; the output the class promises, head included; the good output in front of its damage).  final False: the class's
+    block header says "not final" (every class writes BFINAL as its first bit), for a class with more blocks behind it."""
+    c = Ctx(W.BitWriter(), bytearray(head))
+    extra = writer(c)
+    if tail:
+        tail(c)
+    seg = c.bw.bytes()
+    if c.cut is not None:
+        assert c.cut <= len(seg)
+        seg = seg[: c.cut]
+    if not final:
+        assert seg[0] & 1
+        seg[0] &= 0xFE
+    return seg, c.w + extra, bytes(c.out)
+
+
 def _good_segment(n, rng, final):
     c = Ctx(W.BitWriter(), bytearray())
     if final:  # a stream's last segment as a compressor leaves it: one final dynamic block

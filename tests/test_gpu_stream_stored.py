@@ -12,6 +12,7 @@ import deflate_writer as W
 import stream_host as H
 from starflate_amd import Compressor, synth
 from stream_cases import write_fixed
+from stream_lookalikes import look, stored_look_alikes
 
 pytestmark = pytest.mark.gpu
 
@@ -224,30 +225,6 @@ def _rev8(b):
     return int(f"{b:08b}"[::-1], 2)
 
 
-def _look(v, ln):
-    return bytes([v]) + ln.to_bytes(2, "little") + (ln ^ 0xFFFF).to_bytes(2, "little")
-
-
-def _stored_look_alikes(seed, nblocks=12, size=1500):
-    """stored blocks of `size` bytes whose payloads hold look-alikes, most of them with another look-alike where their payload
-    would end, so that the finder takes them: LEN inside the payload, LEN past the next true header (past the body in the last
-    two blocks), a chain of three in which each lands exactly on the next, and one with random bytes behind it"""
-    rng = np.random.default_rng(seed)
-    bw, out = W.BitWriter(), bytearray()
-    for b in range(nblocks):
-        p = bytearray(rng.integers(32, 256, size, dtype=np.uint8).tobytes())
-        p[40:45] = _look(0, 155)                     # inside the payload: 45 + 155 = 200
-        p[200:205] = _look(0, 60 + b)                # (random bytes behind it)
-        p[340:345] = _look(int(rng.integers(0, 32)), 2 * (size + 5) + 200 - 345)  # byte 200 of the block after the next
-        p[640:645] = _look(0, 300)                   # a chain of three: 645 + 300 = 945, 950 + 300 = 1250,
-        p[945:950] = _look(0, 300)
-        p[1250:1255] = _look(0, size + 5 + 200 - 1255)  # and from there to byte 200 of the next block
-        W.write_stored(bw, bytes(p))
-        out += p
-    W.write_stored(bw, b"", final=True)
-    return bw.bytes().tobytes(), bytes(out)
-
-
 def _fixed_look_alikes(nblocks=6):
     """fixed blocks of literals only: five 9-bit literals behind the 3 header bits put every 8-bit literal code on a stream byte
     of its own, the code's bits reversed.  The stream then holds `0x09 LEN NLEN` wherever the literals say so (bytes whose
@@ -266,7 +243,7 @@ def _fixed_look_alikes(nblocks=6):
         # one that ends on the next (292 = 35 + 0x0101), which runs past the block; three in a row, each ending on the next
         # one's first byte (862 = 605 + 0x0101, 1381 = 867 + 0x0202)
         for at, ln in ((30, 0x0101), (292, far), (600, 0x0101), (862, 0x0202), (1381, 0x0205)):
-            body[at: at + 5] = _look(0x09, ln)
+            body[at: at + 5] = look(0x09, ln)
         toks = [200] * 5 + [lit(x) for x in body]
         write_fixed(bw, toks)
         out += bytes(toks)
@@ -286,7 +263,7 @@ def _past_the_body():
         n = len(bw.bytes())
         at = 5 + 600  # the look-alike's v byte, in stream bytes
         ln = n - (at + 5) + extra
-        p[600:605] = _look(0, ln)
+        p[600:605] = look(0, ln)
         bw = W.BitWriter()
         W.write_stored(bw, bytes(p))
         W.write_stored(bw, b"xyz", final=True)
@@ -296,7 +273,7 @@ def _past_the_body():
 
 
 def test_look_alikes(small):
-    made = [_stored_look_alikes(1), _stored_look_alikes(2, nblocks=3, size=1300), _fixed_look_alikes()] + _past_the_body()
+    made = [stored_look_alikes(1), stored_look_alikes(2, nblocks=3, size=1300), _fixed_look_alikes()] + _past_the_body()
     for s, d in made:
         st, n, want = H.serial(s, "raw", len(d))
         assert st == OK and n == len(d) and want.tobytes() == d
