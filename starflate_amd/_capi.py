@@ -22,6 +22,7 @@ DBG_NTOK, DBG_TOKENS, DBG_HIST, DBG_PLAN, DBG_LENS, DBG_OFFSETS, DBG_STAMPS = ra
 DBG_SUBINDEX = 7
 DBG_ITEMS, DBG_NITEMS = 8, 9
 DBG_SEGINFO = 10
+DBG_RITEM = 11
 DEFAULT_BLOCK_BYTES = 262144
 LARGE_BLOCK_BYTES = 1 << 19
 CHAIN_BLOCK_BYTES = 1 << 20

@@ -1032,6 +1032,7 @@ class Compressor:
             _capi.DBG_SUBINDEX: ((nchunks, 32, 2), np.uint32),
             _capi.DBG_ITEMS: ((nchunks, CHUNK_BYTES), np.uint16),
             _capi.DBG_NITEMS: ((nchunks,), np.uint32),
+            _capi.DBG_RITEM: ((nchunks, 32), np.uint32),  # the item index of each region's first token
             _capi.DBG_SEGINFO: ((nchunks, 6), np.uint32),  # decoder: status, tokens, raw | serial << 1, bytes, raw offset (u64)
         }
         shape, dt = shapes[what]

@@ -3760,6 +3760,13 @@ int sfh_debug_read(sfh_ctx* ctx, int what, void* host_dst, size_t bytes) {
     case SFH_DBG_TOKENS: p = ctx->ws.tokens; avail = ctx->cap_dtok >= nlast ? nlast * sf::kChunk * 4 : 0; break;
     case SFH_DBG_ITEMS: p = ctx->ws.items; avail = nc * sf::kChunk * 2; break;
     case SFH_DBG_NITEMS: p = ctx->ws.nitems; avail = nc * 4; break;
+    case SFH_DBG_RITEM: {  // the high halves of the region words
+      if (!ctx->ws.rtok || bytes % 4 || bytes > nc * sf::kSubRegions * 4) return SFH_E_INVALID_ARG;
+      SF_HIP(hipSetDevice(ctx->device), "hipSetDevice");
+      SF_HIP(hipMemcpy(host_dst, ctx->ws.rtok, bytes, hipMemcpyDeviceToHost), "debug copy");
+      for (size_t k = 0; k < bytes / 4; ++k) static_cast<uint32_t*>(host_dst)[k] >>= 16;
+      return SFH_OK;
+    }
     case SFH_DBG_HIST: p = ctx->ws.hist; avail = nc * sf::kHistStride * 4; break;
     case SFH_DBG_PLAN: p = ctx->ws.plan; avail = nc * sizeof(sf::ChunkPlan); break;
     case SFH_DBG_OFFSETS: p = ctx->ws.offsets; avail = nidx * 8; break;

@@ -57,11 +57,16 @@ constexpr uint32_t kTokRegion = 0x40000000u; // decoder token: first token of a 
 // head = kItemTok | kItemHead | len-3, then dist-1 (15 bits, bit 15 clear).  Every item says what it is by itself (round 6;
 // before, a distance was "the item behind a head" and k_emit looked at every item's neighbour), and kItemHead sits right
 // above the byte: a token's low nine bits ARE its place in k_emit's table of literal and length codes.  The first item of a
-// parse region's first token also carries kItemRegion and the region's index in bits 9..13 (kItemRegionShift).
+// parse region's first token also carries kItemRegion and the region's index in bits 9..13 (kItemRegionShift): the format's
+// own record of the region starts (debug_tokens, the tests).  k_emit does not look for the flag: k_lz77 hands it the item
+// index of every region's first token beside the region's token count (Workspace::rtok, a region_word).
 constexpr uint32_t kItemTok = 0x8000u;     // a token's first item: a literal or a match head (clear: a distance)
 constexpr uint32_t kItemRegion = 0x4000u;
 constexpr uint32_t kItemRegionShift = 9;
 constexpr uint32_t kItemHead = 0x0100u;    // with kItemTok: a match head (len-3 in bits 0..7)
+// Workspace::rtok's word for one region: the tokens before it (low half) and the items before it (high half)
+static_assert(kChunk <= 0x8000u, "a chunk's token and item counts fit 16 bits each");
+constexpr uint32_t region_word(uint32_t tokens_before, uint32_t items_before) { return tokens_before | (items_before << 16); }
 
 constexpr uint32_t kChecksumAdler32 = 1;  // = SFH_ZLIB
 constexpr uint32_t kChecksumCrc32 = 2;    // = SFH_GZIP
@@ -170,7 +175,7 @@ struct Workspace {
   uint64_t* stamps;   // [nchunks][8], diagnostic build only (SFH_K1_STAMPS=1), else null
   uint32_t* sums;     // [nchunks] checksum partials (container modes / sfh_checksum_device)
   SegInfo* seginfo;   // [nchunks] decoder only
-  uint32_t* rtok;     // [nchunks][32] tokens before each 1024-byte parse region (K1 -> K4)
+  uint32_t* rtok;     // (batch) [nchunks][32] region_word: tokens | items << 16 before each 1024-byte parse region (K1 -> K4)
   uint32_t* subidx;   // [nchunks][32][2] sub-index: {bit offset of the region's first code, tokens before it}
 };
 

@@ -1352,9 +1352,12 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
       // items from the input in the rare case that the chunk is not stored (kItemsSkipped in nitems)
       static_assert(kSkipSpan == kRound, "the probe span is the chunk's first round");
       const bool skip_now = rc == 0 && fast_skip && (n - cstart) > kSkipSpan && (rtotal & 0xFFFFu) >= kSkipSpan - kSkipSlack;
-      // tokens before each 1024-byte sub-index region (two waves): where the decoder's region lanes start
+      // tokens before each 1024-byte sub-index region (two waves): where the decoder's region lanes start -- and, in the
+      // word's high half, the items before it: the index of its first token's item, where k_emit records the region's bit
+      // offset (region_word: both are at most kChunk)
       if (!skip_now && (wave & (kSubBytes / kRegion - 1)) == 0 && lane == 0)
-        rtok_out[chunk * kSubRegions + rc * kRSubs + wave / (kSubBytes / kRegion)] = tot_tok + (wbase & 0xFFFFu);
+        rtok_out[chunk * kSubRegions + rc * kRSubs + wave / (kSubBytes / kRegion)] =
+            region_word(tot_tok + (wbase & 0xFFFFu), tot_items + (wbase & 0xFFFFu) + (wbase >> 16));
       stamp(4);
       __builtin_amdgcn_s_setprio(0);  // emit, flush and the next round's stage: nothing waits for them
 
@@ -1454,7 +1457,10 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         }
         const uint32_t r_last = (r + kRoundsPerChunk - 1 < nrounds ? r + kRoundsPerChunk - 1 : nrounds - 1);  // the chunk's last round
         const uint32_t ctok = pstore ? 0u : clen;  // tokens = items = positions -- or none
-        if (t < kSubRegions) rtok_out[chunk * kSubRegions + t] = t * kSubBytes < ctok ? t * kSubBytes : ctok;
+        if (t < kSubRegions) {  // (an item is a position)
+          const uint32_t before = t * kSubBytes < ctok ? t * kSubBytes : ctok;
+          rtok_out[chunk * kSubRegions + t] = region_word(before, before);
+        }
         skip = true;
         lds_stale = true;
         stale_span = short_probe ? kSkipProbe : kSkipSpan;  // (the positions of this chunk the match phase went over)
@@ -1541,7 +1547,7 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         }
       if (t == 0) { ntok_out[chunk] = tot_tok; nitems_out[chunk] = tot_items | (skip ? kItemsSkipped : 0u); }
       const uint32_t covered = chunk_done ? kSubRegions : (rc + 1) * kRSubs;  // sub-index regions of the rounds that ran
-      if (t < kSubRegions && t >= covered) rtok_out[chunk * kSubRegions + t] = tot_tok;
+      if (t < kSubRegions && t >= covered) rtok_out[chunk * kSubRegions + t] = region_word(tot_tok, tot_items);
       stamp(6);
     }
     // the next round's first barrier orders this round's LDS reads before its writes
@@ -2339,7 +2345,7 @@ struct EmitLds {
   // 16 on cover whole multiples of 128)
   uint32_t tab[1024];
   uint32_t wtot[2][K4_WAVES];
-  uint32_t rtok[kSubRegions];
+  uint32_t rtab[2 * kSubRegions];  // per region: the tokens before it, then the item index of its first token
 };
 // 8 waves per SIMD = four 512-thread workgroups per CU (160 KiB of LDS) under strategy 0; the forced stage fits three (6 waves)
 template <uint32_t STAGE_WORDS>
@@ -2402,7 +2408,7 @@ __global__ __launch_bounds__(K4_THREADS, k4_waves_per_simd<STAGE_WORDS>()) void 
   uint32_t(&s_dcode)[32] = L.dcode;
   uint32_t(&s_tab)[1024] = L.tab;
   uint32_t(&s_wtot)[2][K4_WAVES] = L.wtot;
-  uint32_t(&s_rtok)[kSubRegions] = L.rtok;
+  uint32_t(&s_rtab)[2 * kSubRegions] = L.rtab;
   static_assert(K4_THREADS == 512, "one table entry per thread and kind");
   constexpr uint32_t kTabLit = 512, kTabLen = 768, kTabDistN = 510;
 
@@ -2432,7 +2438,7 @@ __global__ __launch_bounds__(K4_THREADS, k4_waves_per_simd<STAGE_WORDS>()) void 
   // what a coded chunk needs next, requested before the plan has arrived (a stored chunk does not use it): one memory
   // round trip for the plan and the tables together instead of two in a row
   uint32_t pre_code = t < 288 ? C.lcode[t] : (t < 320 ? C.dcode[t - 288] : 0u);
-  uint32_t pre_rtok = t < kSubRegions ? rtok[(uint64_t)chunk * kSubRegions + t] : 0u;
+  uint32_t pre_rtok = t < kSubRegions ? rtok[(uint64_t)chunk * kSubRegions + t] : 0u;  // (a region_word)
   const uint32_t pre_ntok = ntok_in[chunk], pre_nit = nitems_in[chunk];
   asm volatile("" : "+v"(pre_code), "+v"(pre_rtok));
 
@@ -2515,8 +2521,9 @@ __global__ __launch_bounds__(K4_THREADS, k4_waves_per_simd<STAGE_WORDS>()) void 
   if (t < 288) s_lcode[t] = pre_code;  // code | bits << 16
   else if (t < 320) s_dcode[t - 288] = pre_code;
   if (t < kSubRegions) {
-    s_rtok[t] = pre_rtok;
-    sub[2 * t + 1] = pre_rtok;
+    s_rtab[t] = pre_rtok & 0xFFFFu;
+    s_rtab[kSubRegions + t] = pre_rtok >> 16;
+    sub[2 * t + 1] = pre_rtok & 0xFFFFu;
   }
   __syncthreads();
   if (t < 256) {
@@ -2593,27 +2600,14 @@ __global__ __launch_bounds__(K4_THREADS, k4_waves_per_simd<STAGE_WORDS>()) void 
       ent[2 * j + 1] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(s_tab) + (by >> 16));
     }
     asm volatile("" : "+v"(ent[0]), "+v"(ent[1]), "+v"(ent[2]), "+v"(ent[3]), "+v"(ent[4]), "+v"(ent[5]), "+v"(ent[6]), "+v"(ent[7]));
-    // items that start a token AND carry the region flag (bits 15 and 14): rare (one in ~500).  Item k's bit in `starts`
-    // is sbit(k): the low halves' items at bits 0, 2, 4, 6, the high halves' at 16, 18, 20, 22
-    auto both = [](uint32_t w) { return w & (w << 1) & 0x80008000u; };
-    auto sbit = [](uint32_t k) { return (k & 1) ? 15 + k : k; };
-    uint32_t starts = (both(q.x) >> 15) | (both(q.y) >> 13) | (both(q.z) >> 11) | (both(q.w) >> 9);
     // @phase k4.last trips=0.24 note=a chunk's last, partial batch: ~17K items per chunk on text, 4096 per batch
     if (!full) {  // (uniform) a chunk's last batch: what lies behind the last item is no item -- an empty entry is no bits
       uint32_t left = nit - i0;  // (wraps to something huge for a thread wholly inside: every k is below it)
       left = i0 < nit ? left : 0u;
 #pragma unroll
-      for (uint32_t k = 0; k < K4_IPT; ++k) {
-        ent[k] = k < left ? ent[k] : 0u;
-        starts &= k < left ? ~0u : ~(1u << sbit(k));
-      }
+      for (uint32_t k = 0; k < K4_IPT; ++k) ent[k] = k < left ? ent[k] : 0u;
     }
     // @phase k4.price trips=1
-    // the first region start's item (none: 32, which is no sbit) and the bits in front of it, taken in the price loop; a
-    // lane with two starts would leave them to the walk below
-    const uint32_t s0 = starts ? (uint32_t)__builtin_ctz(starts) : 32u;
-    const bool walk = __ballot((starts & (starts - 1)) != 0) != 0;  // (uniform)
-    uint32_t off0 = 0;
 #pragma unroll
     for (uint32_t k = 0; k < K4_IPT; ++k) {
       const uint32_t en = ent[k];
@@ -2625,14 +2619,7 @@ __global__ __launch_bounds__(K4_THREADS, k4_waves_per_simd<STAGE_WORDS>()) void 
       // (an item's value and bit count together: left alone, the compiler computes every count first, for the scan, and
       // holds eight entries' fields until the values -- more than 64 VGPRs)
       asm volatile("" : "+v"(val[k]), "+v"(nb[k]));
-      off0 = s0 == sbit(k) ? mine : off0;
       mine += nb[k];
-    }
-    uint32_t region0;  // the start's region: its sub-index entry
-    {
-      const uint32_t j = (s0 >> 1) & 3u;
-      const uint32_t w = j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w;
-      region0 = (w >> ((s0 & 16u) + kItemRegionShift)) & 31u;
     }
     // @phase k4.scan trips=1
     const uint32_t incl = wave_incl_add(mine);
@@ -2649,47 +2636,68 @@ __global__ __launch_bounds__(K4_THREADS, k4_waves_per_simd<STAGE_WORDS>()) void 
     // and OR whole words, instead of one to three atomics per token
     const uint32_t pos = running + pre + incl - mine;
     // @phase k4.subindex trips=1
-    // k_lz77 flags the first token of every 1024-byte parse region (32 per chunk): its bit offset is the sub-index entry
-    if (walk) {
-      // @phase k4.subindex_walk trips=0 note=not reached by k_lz77's items
-      // the thread's items again (the batch's, not in registers any more), item by item.  k_lz77 never gives a lane two
-      // starts: every kSubBytes-th position starts a token and a token is at most 258 bytes in two items, so two region
-      // starts are at least 8 items apart and a lane's eight items begin at a multiple of 8.  The walk keeps k_emit right
-      // for any item stream, at the cost of one ballot per round.
-      const uint4 r = *reinterpret_cast<const uint4*>(it + i0);
-      const uint32_t rd[K4_IPT / 2] = {r.x, r.y, r.z, r.w};
-      uint32_t pk = pos;
+    // The bit offset of every 1024-byte parse region's first token is its sub-index entry.  k_lz77 names those tokens' items
+    // (s_rtab's second half, ascending; regions past the data: nit, which is no item).  A wave takes the entries that fall into
+    // its own 512 items of this batch.  (Nothing here looks at an item's kItemRegion flag.)
+    const uint32_t wi0 = b0 + wave * (64 * K4_IPT);  // (uniform) the wave's first item
+    const uint32_t rit = s_rtab[kSubRegions + (lane & (kSubRegions - 1))];
+    const bool mine_due = rit - wi0 < 64 * K4_IPT && rit < nit;
+    uint32_t due = (uint32_t)__ballot(mine_due);  // (lanes 32..63 repeat lanes 0..31)
+    if (__builtin_popcount(due) > 2) {
+      // @phase k4.subindex_many trips=0 note=long matches: a chunk of a few hundred items, up to 32 starts in one wave
+      // Many at once, lane r for region r: it fetches, from the lane that holds the item, that lane's position and the bits
+      // of its items in front of each slot -- seven running sums of at most 7 x 28 bits, a byte each
+      uint32_t a = nb[0] | nb[1] << 8 | nb[2] << 16 | nb[3] << 24, b = nb[4] | nb[5] << 8 | nb[6] << 16;
+      a += a << 8;
+      a += a << 16;  // bytes: the bits in front of slots 1, 2, 3, 4
+      b += b << 8;
+      b += b << 16;
+      b += (a >> 24) * 0x010101u;  // bytes: in front of slots 5, 6, 7
+      const uint32_t at = rit - wi0, from = ((at / K4_IPT) & 63u) * 4, slot = at & (K4_IPT - 1);
+      const uint32_t pos_o = (uint32_t)__builtin_amdgcn_ds_bpermute((int)from, (int)pos);
+      const uint32_t a_o = (uint32_t)__builtin_amdgcn_ds_bpermute((int)from, (int)a);
+      const uint32_t b_o = (uint32_t)__builtin_amdgcn_ds_bpermute((int)from, (int)b);
+      const uint32_t front = slot ? ((slot < 5 ? a_o : b_o) >> (8 * ((slot - 1) & 3u))) & 0xFFu : 0u;
+      if (mine_due && lane < kSubRegions) sub[2 * lane] = pos_o + front - 8 * sh;
+      due = 0;
+    }
+    while (due) {
+      // @phase k4.subindex_start trips=0.94 note=per region start: 32 per chunk of ~17K items on text
+      // One or two (text: 0.94 per wave and batch), one after the other (uniform): the lane that holds the item adds the
+      // bits of its items in front of it
+      const uint32_t r = (uint32_t)__builtin_ctz(due);
+      due &= due - 1;
+      const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)rit, (int)r) - wi0;  // (uniform) the item's place in the wave
+      // the slot is uniform, so "in front" is a scalar: one bit per item, spread into a mask (0 or all ones) that an item's
+      // count is AND-ed with
+      const uint32_t in_front = (1u << (at & (K4_IPT - 1))) - 1u;
+      uint32_t front = pos - 8 * sh;
 #pragma unroll
-      for (uint32_t k = 0; k < K4_IPT; ++k) {
-        const uint32_t e = (rd[k / 2] >> (16 * (k & 1))) & 0xFFFFu;
-        if ((e & (kItemTok | kItemRegion)) == (kItemTok | kItemRegion) && i0 + k < nit)
-          sub[2 * ((e >> kItemRegionShift) & 31u)] = pk - 8 * sh;
-        pk += nb[k];
-      }
-    } else if (starts) {
-      // @phase k4.subindex trips=1
-      sub[2 * region0] = pos + off0 - 8 * sh;
+      for (uint32_t k = 0; k + 1 < K4_IPT; ++k) front += nb[k] & (uint32_t)((int32_t)(in_front << (31 - k)) >> 31);
+      if (lane == at / K4_IPT) sub[2 * r] = front;
     }
     // @phase k4.pack trips=1
-    uint32_t wi = pos >> 5, ab = pos & 31;
-    uint64_t acc = 0;
+    // a 32-bit accumulator (fewer than 32 bits are held in front of an add) and the stage's word by its byte offset
+    uint32_t wb = (pos >> 5) << 2, ab = pos & 31, lo = 0;
     auto put = [&](uint32_t v32, uint32_t n) {
-      acc |= (uint64_t)v32 << ab;
+      const uint64_t v = (uint64_t)v32 << ab;
+      lo |= (uint32_t)v;
       ab += n;
       if (ab >= 32) {
-        atomicOr(&s_stage[wi++], (uint32_t)acc);
-        acc >>= 32;
+        atomicOr(reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(s_stage) + wb), lo);
+        lo = (uint32_t)(v >> 32);
+        wb += 4;
         ab -= 32;
       }
     };
 #pragma unroll
     for (uint32_t k = 0; k < K4_IPT; ++k) put(val[k], nb[k]);
-    if (ab) atomicOr(&s_stage[wi], (uint32_t)acc);
+    if (ab) atomicOr(reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(s_stage) + wb), lo);
     running += all;
   }
   __syncthreads();
   // @phase k4.flush trips=0 note=per chunk
-  if (t < kSubRegions && s_rtok[t] >= ntok) sub[2 * t] = running - 8 * sh;  // regions past the data: the end-of-block code
+  if (t < kSubRegions && s_rtab[t] >= ntok) sub[2 * t] = running - 8 * sh;  // regions past the data: the end-of-block code
   if (t == 0) {
     // end of block, then (unless this is the stream's final block) an empty stored
     // block 000 / pad / 00 00 FF FF to byte-align the next chunk
