@@ -1578,8 +1578,8 @@ __device__ __forceinline__ void or_bits(uint32_t* stage, uint32_t bitpos, uint64
   if (v2) atomicOr(&stage[w + 2], v2);
 }
 
-// 5 KiB per workgroup (one wave): the CU then holds a chunk in every one of its 32 wave slots, which is what a
-// latency-bound kernel wants.  Node weights fit 16 bits (a chunk has at most kChunk tokens + the end-of-block).
+// 5 KiB per workgroup (one wave): the CU then holds a chunk in every one of its 32 wave slots (eight waves per SIMD: the
+// sorting and finishing kernels keep the vector pipes busy).  Node weights fit 16 bits (a chunk has at most kChunk tokens + the end-of-block).
 // The tree arrays are only fully used by the literal/length tree; what comes after the two big trees (run-length
 // items, the code-length code's counts / codes / lengths) lives in their tails -- the code-length tree itself has
 // 19 leaves and touches w[0..36], parent[0..36] and key[0..18].
@@ -1635,18 +1635,53 @@ __device__ uint32_t sort_symbols(PlanSmem& S, const uint32_t* freq, uint32_t n, 
     __syncthreads();
     return 1;
   }
+  if constexpr (NG > 1) {
+    if (m <= 64) {
+      // the used keys fit one per lane: compacted through S.key (any order: the ranks sort them), every key then read back
+      // by the whole wave at a uniform address and counted against ONE key per lane -- a compare and an add per key,
+      // whatever groups the alphabet spans.  Lanes m..63 hold the pad (no key is smaller than ~0).
+      uint32_t before = 0;
+      if (lane >= m) S.key[lane] = 0xFFFFFFFFu;
+#pragma unroll
+      for (uint32_t g = 0; g < NG; ++g) {
+        const uint64_t used = __ballot(key[g] != 0xFFFFFFFFu);
+        const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(used >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)used, before));
+        if (key[g] != 0xFFFFFFFFu) S.key[pos] = key[g];
+        before += (uint32_t)__popcll(used);
+      }
+      __syncthreads();
+      const uint32_t ck = S.key[lane];
+      uint32_t r = 0;
+      for (uint32_t src = 0; src < m; src += 4) {  // (m <= 64: reads stay inside S.key[0..64), keys or pad)
+        const uint32_t k0 = S.key[src], k1 = S.key[src + 1], k2 = S.key[src + 2], k3 = S.key[src + 3];
+        r += k0 < ck;
+        r += k1 < ck;
+        r += k2 < ck;
+        r += k3 < ck;
+      }
+      __syncthreads();
+      if (lane < m) S.key[r] = ck;
+      __syncthreads();
+      return m;
+    }
+  }
   // rank sort ascending by (freq, symbol): every used key is broadcast once (v_readlane)
-  // and counted by the lanes holding larger keys -- no LDS round trips
+  // and counted by the lanes holding larger keys -- no LDS round trips.  A group without a used key (bytes 128..255 of
+  // text) has nothing to rank: it is left out on both sides (uniform tests).
+  uint64_t usedm[NG];
+#pragma unroll
+  for (uint32_t g = 0; g < NG; ++g) usedm[g] = __ballot(key[g] != 0xFFFFFFFFu);
 #pragma unroll
   for (uint32_t g2 = 0; g2 < NG; ++g2) {
     if (g2 * 64 >= n) break;
-    uint64_t used = __ballot(key[g2] != 0xFFFFFFFFu);
+    uint64_t used = usedm[g2];
     while (used) {
       const uint32_t src = (uint32_t)__builtin_ctzll(used);
       used &= used - 1;
       const uint32_t kk = (uint32_t)__builtin_amdgcn_readlane((int)key[g2], (int)src);
 #pragma unroll
-      for (uint32_t g = 0; g < NG; ++g) rank[g] += kk < key[g];
+      for (uint32_t g = 0; g < NG; ++g)
+        if (NG == 1 || usedm[g]) rank[g] += kk < key[g];
     }
   }
 #pragma unroll
@@ -1722,44 +1757,67 @@ __device__ __forceinline__ void merge_two_queue_lane(uint32_t m, RdW W, WrW SETW
 // rarest symbols (S.key[0..m) ascending).  m >= 2; S.cnt zeroed by sort_symbols.
 __device__ void finish_lengths(PlanSmem& S, uint32_t m, uint32_t maxbits, uint8_t* lens, uint32_t lane) {
   const uint32_t root = 2 * m - 2;
+  // rank marks for the dealing below: S.w is free here (the trees' weights are read by the merge alone; the code-length
+  // code's m <= 19 marks stay inside w_head)
+  uint8_t* const mark = reinterpret_cast<uint8_t*>(S.w);
   for (uint32_t k = lane; k < m; k += 64) {
     uint32_t d = 0, v = k;
     while (v != root) { v = S.parent[v]; ++d; }
     atomicAdd(&S.cnt[d < maxbits ? d : maxbits], 1u);
+    mark[k] = 0;
   }
   __syncthreads();
-  if (lane == 0) {
-    int32_t over = -(1 << maxbits);
-    for (uint32_t l = 1; l <= maxbits; ++l) over += (int32_t)(S.cnt[l] << (maxbits - l));
-    while (over > 0) {
-      uint32_t l = maxbits - 1;
-      while (S.cnt[l] == 0) --l;
-      S.cnt[l]--;
-      S.cnt[l + 1]++;
-      over -= 1 << (maxbits - l - 1);
+  // lane l (1..maxbits) takes cnt[l]; sums toward lane 0 run on the DPP network inside row 0 (row_shl:n = 0x100 + n: a
+  // lane adds the lane n above it; the other rows hold zeros)
+  const bool mine = lane - 1 < maxbits;
+  auto sum_from_above = [](uint32_t v) {
+    v = dpp_add_from<0x101, 0xF>(v);
+    v = dpp_add_from<0x102, 0xF>(v);
+    v = dpp_add_from<0x104, 0xF>(v);
+    v = dpp_add_from<0x108, 0xF>(v);
+    return v;
+  };
+  uint32_t c = mine ? S.cnt[lane] : 0u;
+  const uint32_t kraft = sum_from_above(c << ((maxbits - lane) & 31u));  // lane 0: the Kraft sum in units of 2^-maxbits
+  int32_t over = (int32_t)__builtin_amdgcn_readfirstlane((int)kraft) - (1 << maxbits);
+  if (over != 0) {  // (uniform; rare: the tree was deeper than maxbits)
+    if (lane == 0) {
+      while (over > 0) {
+        uint32_t l = maxbits - 1;
+        while (S.cnt[l] == 0) --l;
+        S.cnt[l]--;
+        S.cnt[l + 1]++;
+        over -= 1 << (maxbits - l - 1);
+      }
+      while (over < 0) {
+        S.cnt[maxbits]--;
+        S.cnt[maxbits - 1]++;
+        ++over;
+      }
     }
-    while (over < 0) {
-      S.cnt[maxbits]--;
-      S.cnt[maxbits - 1]++;
-      ++over;
-    }
+    __syncthreads();
+    c = mine ? S.cnt[lane] : 0u;
   }
-  __syncthreads();
   {
-    // lengths dealt longest-first to the rarest symbols: cumulative counts once, in registers
-    uint32_t cum[16];
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t l = 15; l >= 1; --l) {
-      c += l <= maxbits ? S.cnt[l] : 0u;
-      cum[l] = c;
-    }
-    for (uint32_t k = lane; k < m; k += 64) {
-      uint32_t l = 0;
-#pragma unroll
-      for (uint32_t q = 1; q <= 15; ++q)
-        if (k < cum[q]) l = q;  // cum is non-increasing in q: the last q with k < cum[q] is the largest such length
-      lens[S.key[k] & 511u] = (uint8_t)l;
+    // lengths dealt longest-first to the rarest symbols: length l goes to the ranks [cum[l + 1], cum[l]), cum[l] the
+    // count of lengths >= l.  Lane l marks the first of its ranks with 16 - l -- the marks grow with the rank -- and a
+    // running maximum over the ranks deals every rank its length: one scan per 64 ranks, no compare per length.
+    const uint32_t cum = sum_from_above(c);
+    if (c) mark[cum - c] = (uint8_t)(16 - lane);
+    __syncthreads();
+    uint32_t carry = 0;
+    for (uint32_t k0 = 0; k0 < m; k0 += 64) {  // (uniform trips: every lane takes part in the scan)
+      const uint32_t k = k0 + lane;
+      uint32_t v = k < m ? mark[k] : 0u;
+      v = max(v, dpp_from<0x111, 0xF>(v));
+      v = max(v, dpp_from<0x112, 0xF>(v));
+      v = max(v, dpp_from<0x114, 0xF>(v));
+      v = max(v, dpp_from<0x118, 0xF>(v));
+      v = max(v, dpp_from<0x142, 0xA>(v));
+      v = max(v, dpp_from<0x143, 0xC>(v));
+      v = max(v, carry);
+      carry = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+      if (k < m) lens[S.key[k] & 511u] = (uint8_t)(16 - v);
     }
   }
   __syncthreads();
@@ -1782,52 +1840,77 @@ __device__ void build_lengths(PlanSmem& S, const uint32_t* freq, uint32_t n, uin
 // canonical codes (RFC 1951 3.2.2 == huffman::table::canonicalize,
 // /root/reference/huffman/src/table.hpp:177-216), stored bit-reversed because the
 // decoder shifts code bits in MSB-first (huffman/src/decode.hpp:90-91).
-// out[s] = reversed code | len << 16.  n <= 320, all lanes call it.  Out of line: inlined at k_plan_finish's three
-// calls it spills scalar registers to lanes (plan stage 0.274 against 0.265 ms per GiB of text).
-__device__ __noinline__ void canonical_codes(const uint8_t* lens, uint32_t n, uint32_t* out, uint32_t lane) {
-  uint32_t base[16];
+// out[s] = reversed code | len << 16.  n <= 64 * NS, all lanes call it and all of them reach every cross-lane step.
+//
+// One counting pass.  A lane owns NS CONSECUTIVE symbols (5 for the 288 literal/length codes, 1 for the 32- and 19-symbol
+// codes), so a symbol's rank among its length is: the symbols of that length in earlier lanes + the lane's own earlier ones.
+// The lane counts its lengths into sixteen 8-bit fields, a 16-byte row of `scr` (the count a symbol finds there is the
+// number of the lane's own earlier symbols of its length); the row comes back as four dwords and is scanned on the DPP
+// network inside each 16-lane row (a row holds at most 80 symbols: no field overflows), and the totals of the earlier rows
+// (at most 240 a field) are kept APART from it -- their sum can pass 255 -- and added only after a symbol has taken its two
+// bytes out.  Lane 63 holds what gives bl_count; next[l] is a prefix sum over lanes 1..15 of bl_count[k] << (15 - k), shifted
+// back, and a symbol fetches its length's with ds_bpermute.  `scr`: 1,120 bytes of LDS nobody else uses during the call
+// (64 rows, 4 row bases, lane 63's totals).  Lengths are at most 15.
+constexpr uint32_t kCodesScratchWords = 256 + 16 + 8;
+static_assert(kCodesScratchWords <= 320, "canonical_codes' scratch is PlanSmem::freq");
+template <uint32_t NS>
+__device__ __forceinline__ void canonical_codes(const uint8_t* lens, uint32_t n, uint32_t* out, uint32_t* scr, uint32_t lane) {
+  __syncthreads();  // (lens are written, and scr is free, in every lane's eyes)
+  uint8_t* const row = reinterpret_cast<uint8_t*>(scr + 4 * lane);
 #pragma unroll
-  for (int l = 0; l < 16; ++l) base[l] = 0;
-  uint32_t rank[5], mylen[5];
+  for (uint32_t q = 0; q < 4; ++q) scr[4 * lane + q] = 0;
+  uint32_t len[NS], own[NS];
 #pragma unroll
-  for (uint32_t g = 0; g < 5; ++g) {
-    const uint32_t s = g * 64 + lane;
-    const uint32_t len = (g * 64 < n && s < n) ? lens[s] : 0u;
-    mylen[g] = len;
-    rank[g] = 0;
-    if (g * 64 < n) {
-#pragma unroll
-      for (uint32_t l = 1; l < 16; ++l) {
-        const uint64_t mask = __ballot(len == l);
-        if (len == l) rank[g] = base[l] + (uint32_t)__popcll(mask & ((1ull << lane) - 1));
-        base[l] += (uint32_t)__popcll(mask);
-      }
-    }
+  for (uint32_t j = 0; j < NS; ++j) {
+    const uint32_t s = NS * lane + j;
+    len[j] = s < n ? lens[s] : 0u;  // (nothing is read behind n; length 0 counts into field 0, which nobody uses)
+    own[j] = row[len[j]];
+    row[len[j]] = (uint8_t)(own[j] + 1);
   }
-  uint32_t next[16];
-  uint32_t code = 0;
-  next[0] = 0;
+  uint32_t incl[4], base[4];
 #pragma unroll
-  for (int l = 1; l < 16; ++l) {
-    code = (code + (l > 1 ? base[l - 1] : 0u)) << 1;
-    next[l] = code;
+  for (uint32_t q = 0; q < 4; ++q) {
+    const uint32_t c = scr[4 * lane + q];
+    uint32_t v = c;
+    v = dpp_add_from<0x111, 0xF>(v);
+    v = dpp_add_from<0x112, 0xF>(v);
+    v = dpp_add_from<0x114, 0xF>(v);
+    v = dpp_add_from<0x118, 0xF>(v);
+    uint32_t b = dpp_from<0x142, 0xA>(v);  // rows 1 and 3: the row before; lane 31 then has rows 0 + 1
+    b += dpp_from<0x143, 0xC>(v + b);      // rows 2 and 3: + rows 0 and 1
+    incl[q] = v;
+    base[q] = b;
+    scr[4 * lane + q] = v - c;  // exclusive inside the row
   }
+  uint32_t* const rbase = scr + 256 + 4 * (lane >> 4);
+  if ((lane & 15) == 0) {
 #pragma unroll
-  for (uint32_t g = 0; g < 5; ++g) {
-    const uint32_t s = g * 64 + lane;
-    if (s < n) {
-      uint32_t v = 0;
-      const uint32_t len = mylen[g];
-      if (len) {
-        uint32_t nx = 0;
+    for (uint32_t q = 0; q < 4; ++q) rbase[q] = base[q];
+  }
+  if (lane == 63) {
 #pragma unroll
-        for (uint32_t l = 1; l < 16; ++l)
-          if (len == l) nx = next[l];
-        const uint32_t c = nx + rank[g];
-        v = (__brev(c) >> (32 - len)) | (len << 16);
-      }
-      out[s] = v;
-    }
+    for (uint32_t q = 0; q < 4; ++q) { scr[272 + q] = incl[q]; scr[276 + q] = base[q]; }
+  }
+  __syncthreads();
+  const uint8_t* const tot = reinterpret_cast<const uint8_t*>(scr + 272);
+  const uint32_t l = lane & 15;
+  const uint32_t cnt = (lane - 1 < 15u) ? (uint32_t)tot[l] + tot[16 + l] : 0u;  // bl_count[lane], lanes 1..15 (it can reach 288)
+  const uint32_t y = cnt << (15 - l);
+  uint32_t p = y;
+  p = dpp_add_from<0x111, 0xF>(p);
+  p = dpp_add_from<0x112, 0xF>(p);
+  p = dpp_add_from<0x114, 0xF>(p);
+  p = dpp_add_from<0x118, 0xF>(p);
+  const uint32_t next = (p - y) >> (15 - l);  // lane l: sum over k < l of bl_count[k] << (l - k); lane 0: 0
+  const uint8_t* const rb = reinterpret_cast<const uint8_t*>(rbase);
+#pragma unroll
+  for (uint32_t j = 0; j < NS; ++j) {
+    const uint32_t s = NS * lane + j;
+    const uint32_t ln = len[j];
+    const uint32_t nx = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(ln << 2), (int)next);
+    const uint32_t c = nx + ((uint32_t)row[ln] + rb[ln] + own[j]);
+    const uint32_t v = ln ? ((__brev(c) >> (32 - ln)) | (ln << 16)) : 0u;
+    if (s < n) out[s] = v;
   }
 }
 
@@ -1837,11 +1920,14 @@ __device__ __noinline__ void canonical_codes(const uint8_t* lens, uint32_t n, ui
 // next start, items per run in closed form (zeros: 18 x 138, then 18 / 17 / literal zeros;
 // other values: the value, 16 x 6, then 16 / literals), item slots by a scan over the starts.
 // Writes rle_sym/rle_ext from `base` on, counts symbols into clfreq; returns the item count.
+// NG: the 64-symbol groups the sequence can span (5: literal/length lengths, 1: distance lengths; n <= 64 * NG).  A group in
+// which no run starts -- the unused bytes 128..255 of text are the inside of one run of zeros -- has no items: it is left out.
+template <uint32_t NG>
 __device__ uint32_t rle_parallel(PlanSmem& S, const uint8_t* lens, uint32_t n, uint32_t base, uint32_t lane) {
-  uint64_t Sm[5];
-  uint32_t val[5];
+  uint64_t Sm[NG];
+  uint32_t val[NG];
 #pragma unroll
-  for (uint32_t g = 0; g < 5; ++g) {
+  for (uint32_t g = 0; g < NG; ++g) {
     const uint32_t i = g * 64 + lane;
     const uint32_t cur = i < n ? lens[i] : 0xFFu;
     const uint32_t prev = (i > 0 && i < n) ? lens[i - 1] : 0xFEu;
@@ -1850,14 +1936,15 @@ __device__ uint32_t rle_parallel(PlanSmem& S, const uint8_t* lens, uint32_t n, u
   }
   uint32_t total = 0;
 #pragma unroll
-  for (uint32_t g = 0; g < 5; ++g) {
+  for (uint32_t g = 0; g < NG; ++g) {
     if (g * 64 >= n) break;
+    if (Sm[g] == 0) continue;  // (uniform)
     const uint32_t i = g * 64 + lane;
     const bool start = (Sm[g] >> lane) & 1;
     // next run start after i: in this group, else the first start of a later group, else n
     uint32_t later = n;
 #pragma unroll
-    for (uint32_t g2 = 4; g2 > g; --g2)
+    for (uint32_t g2 = NG - 1; g2 > g; --g2)
       if (Sm[g2]) later = g2 * 64 + (uint32_t)__builtin_ctzll(Sm[g2]);
     const uint64_t up = lane < 63 ? (Sm[g] >> (lane + 1)) : 0ull;
     uint32_t nxt = up ? i + 1 + (uint32_t)__builtin_ctzll(up) : later;
@@ -2109,13 +2196,13 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
     const uint64_t md = __ballot(lane < 30 && S.lens[288 + lane] != 0);
     hdist = md ? 64 - (uint32_t)__builtin_clzll(md) : 1u;
   }
-  const uint32_t nl = rle_parallel(S, S.lens, hlit, 0, lane);
-  const uint32_t nd = rle_parallel(S, S.lens + 288, hdist, nl, lane);
+  const uint32_t nl = rle_parallel<5>(S, S.lens, hlit, 0, lane);
+  const uint32_t nd = rle_parallel<1>(S, S.lens + 288, hdist, nl, lane);
   const uint32_t nitems = nl + nd;
   __syncthreads();
   stamp();  // 3 costs + RLE
   build_lengths(S, S.clfreq, 19, 7, S.cl_lens, lane);
-  canonical_codes(S.cl_lens, 19, S.cl_code, lane);
+  canonical_codes<1>(S.cl_lens, 19, S.cl_code, S.freq, lane);
   __syncthreads();
   stamp();  // 4 code-length code
   {
@@ -2178,8 +2265,8 @@ __device__ __forceinline__ void plan_chunk(uint64_t n_total, uint32_t nchunks,
     if (lane == 0) s_header[0] = fin ? 1u : 0u;
     __syncthreads();
   }
-  canonical_codes(S.lens, 288, C.lcode, lane);
-  canonical_codes(S.lens + 288, 32, C.dcode, lane);
+  canonical_codes<5>(S.lens, 288, C.lcode, S.freq, lane);
+  canonical_codes<1>(S.lens + 288, 32, C.dcode, S.freq, lane);
   const uint32_t hbits = bt == 2 ? dyn_hbits : 3;
   for (uint32_t k = lane; k < (hbits + 31) / 32; k += 64) C.header[k] = s_header[k];
   if (lane == 0) {
