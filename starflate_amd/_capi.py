@@ -10,6 +10,8 @@ from . import build as _build
 
 NSTAGES = 5
 INFLATE_NSTAGES = 2
+STREAM_NSTAGES = 5  # SFH_STREAM_NSTAGES, SFH_STREAM_NCOUNTS: sfh_last_stream_stats' arrays
+STREAM_NCOUNTS = 6
 SEGMENT_BYTES = 32768
 STRATEGY = {"auto": 0, "stored": 1, "fixed": 2, "dynamic": 3}
 CONTAINER = {"raw": 0, "zlib": 1, "gzip": 2}  # what the decoders take (to them a dictzip file is a gzip stream)
@@ -27,30 +29,6 @@ DEFAULT_BLOCK_BYTES = 262144
 LARGE_BLOCK_BYTES = 1 << 19
 CHAIN_BLOCK_BYTES = 1 << 20
 SUBINDEX_WORDS = 64
-
-# every symbol include/starflate_hip.h declares
-EXPORTS = [
-    "sfh_default_options", "sfh_device_count", "sfh_get_device_props", "sfh_create", "sfh_destroy", "sfh_last_error",
-    "sfh_compress_bound", "sfh_compress_bound_container", "sfh_dz_header_bytes", "sfh_compress", "sfh_compress_multi", "sfh_compress_device", "sfh_compress_device_async",
-    "sfh_compress_batch_device_async", "sfh_compress_batch", "sfh_batch_index_size", "sfh_copy_batch_index",
-    "sfh_decompress_batch_device_async", "sfh_decompress_batch",
-    "sfh_decompress_ranges_device_async", "sfh_decompress_range_device", "sfh_decompress_ranges",
-    "sfh_dz_read_index", "sfh_dz_read_index_device", "sfh_decompress_dz_device", "sfh_decompress_dz", "sfh_decompress_dz_ranges",
-    "sfh_bgzf_bound", "sfh_compress_bgzf_device_async", "sfh_compress_bgzf_device", "sfh_compress_bgzf",
-    "sfh_bgzf_read_index", "sfh_bgzf_read_index_device", "sfh_decompress_bgzf_device", "sfh_decompress_bgzf",
-    "sfh_decompress_bgzf_wide_device",
-    "sfh_decompress_bgzf_ranges_device", "sfh_decompress_bgzf_ranges", "sfh_bgzf_voffsets_to_offsets", "sfh_bgzf_offsets_to_voffsets",
-    "sfh_zip_read_index", "sfh_zip_read_index_device", "sfh_decompress_zip_device", "sfh_decompress_zip", "sfh_zip_bound",
-    "sfh_compress_zip_device_async", "sfh_compress_zip_device", "sfh_compress_zip",
-    "sfh_recover_index_device", "sfh_recover_index", "sfh_decompress_any_device", "sfh_decompress_any", "sfh_last_recover_stats",
-    "sfh_recover_index_batch_device", "sfh_recover_index_batch", "sfh_decompress_any_batch_device", "sfh_decompress_any_batch",
-    "sfh_inflate_stream_device", "sfh_inflate_stream", "sfh_inflate_stream_batch_device", "sfh_inflate_stream_batch",
-    "sfh_last_stream_stats",
-    "sfh_last_block_bytes", "sfh_index_entries", "sfh_copy_index", "sfh_copy_subindex", "sfh_decompress_device", "sfh_decompress", "sfh_last_inflate_ms", "sfh_last_decode_scratch_bytes",
-    "sfh_inflate_stage_name", "sfh_checksum_device", "sfh_crc32_combine", "sfh_adler32_combine",
-    "sfh_set_profiling", "sfh_last_stage_ms", "sfh_stage_name", "sfh_debug_read",
-    "sfh_gather_offsets", "sfh_gather_streams", "sfh_comm_ranks", "sfh_lds_order_check",
-]
 
 
 class Options(C.Structure):
@@ -89,6 +67,109 @@ class DeviceProps(C.Structure):
                 ("memory_bus_bits", C.c_uint32), ("clock_khz", C.c_uint32), ("total_memory", C.c_uint64)]
 
 
+def _prototypes():
+    """{symbol: (restype, argtypes)} of every function include/starflate_hip.h declares, parameter for parameter.  A pointer
+    is typed where callers hand over a ctypes array or a byref, and vp where they hand over an address (a context, a buffer,
+    a stream, a numpy array's data): tests and tools call these functions directly and rely on which is which."""
+    i, vp, sz, u32, u64 = C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64
+    vpp, szp, u32p, u64p, opt = C.POINTER(vp), C.POINTER(sz), C.POINTER(u32), C.POINTER(u64), C.POINTER(Options)
+    dz, bgzf, zinfo = C.POINTER(DzInfo), C.POINTER(BgzfInfo), C.POINTER(ZipInfo)
+    return {
+        "sfh_default_options": (None, [opt]),
+        "sfh_device_count": (i, []),
+        "sfh_get_device_props": (i, [i, C.POINTER(DeviceProps)]),
+        "sfh_create": (i, [vpp, i]),
+        "sfh_destroy": (None, [vp]),
+        "sfh_last_error": (C.c_char_p, [vp]),
+        "sfh_compress_bound": (sz, [sz, u32]),
+        "sfh_compress_bound_container": (sz, [sz, u32, u32]),
+        # seekable gzip (dictzip)
+        "sfh_dz_header_bytes": (sz, [sz]),
+        "sfh_dz_read_index": (i, [vp, sz, dz, vp, sz]),
+        "sfh_dz_read_index_device": (i, [vp, vp, sz, dz, vp, sz, vp]),
+        "sfh_decompress_dz_device": (i, [vp, vp, sz, vp, u64, u64p, u32p, vp]),
+        "sfh_decompress_dz": (i, [vp, vp, sz, vp, u64, u64p, u32p]),
+        "sfh_decompress_dz_ranges": (i, [vp, vp, sz, sz, u64p, u64p, vpp, vp]),
+        # BGZF
+        "sfh_bgzf_bound": (sz, [sz]),
+        "sfh_compress_bgzf_device_async": (i, [vp, vp, sz, vp, sz, vp, opt, vp]),
+        "sfh_compress_bgzf_device": (i, [vp, vp, sz, vp, sz, szp, opt, vp]),
+        "sfh_compress_bgzf": (i, [vp, vp, sz, vp, sz, szp, opt]),
+        "sfh_bgzf_read_index": (i, [vp, sz, bgzf, vp, vp, sz]),
+        "sfh_bgzf_read_index_device": (i, [vp, vp, sz, bgzf, vp, vp, sz, vp]),
+        "sfh_decompress_bgzf_device": (i, [vp, vp, sz, vp, u64, u64p, u32p, vp]),
+        "sfh_decompress_bgzf_wide_device": (i, [vp, vp, sz, vp, u64, u64p, u32p, vp]),
+        "sfh_decompress_bgzf": (i, [vp, vp, sz, vp, u64, u64p, u32p]),
+        "sfh_decompress_bgzf_ranges_device": (i, [vp, vp, sz, vp, vp, bgzf, sz, u64p, u64p, vpp, vp, vp]),
+        "sfh_decompress_bgzf_ranges": (i, [vp, vp, sz, vp, vp, bgzf, sz, u64p, u64p, vpp, vp]),
+        "sfh_bgzf_voffsets_to_offsets": (i, [vp, vp, u32, sz, vp, vp]),
+        "sfh_bgzf_offsets_to_voffsets": (i, [vp, vp, u32, sz, vp, vp]),
+        # ZIP archives
+        "sfh_zip_read_index": (i, [vp, sz, zinfo, vp, sz]),
+        "sfh_zip_read_index_device": (i, [vp, vp, sz, zinfo, vp, sz, vp]),
+        "sfh_decompress_zip_device": (i, [vp, vp, sz, vp, sz, vp, vp, vp, vp]),
+        "sfh_decompress_zip": (i, [vp, vp, sz, vp, sz, vp, vp, vp]),
+        "sfh_zip_bound": (sz, [sz, vp, vp]),
+        "sfh_compress_zip_device_async": (i, [vp, sz, vp, vp, vp, vp, vp, sz, vp, opt, vp]),
+        "sfh_compress_zip_device": (i, [vp, sz, vp, vp, vp, vp, vp, sz, szp, opt, vp]),
+        "sfh_compress_zip": (i, [vp, sz, vp, vp, vp, vp, vp, sz, szp, opt]),
+        # one stream, and many in one call
+        "sfh_compress": (i, [vp, vp, sz, vp, sz, szp, opt]),
+        "sfh_compress_multi": (i, [vpp, i, vp, sz, vp, sz, szp, opt]),
+        "sfh_compress_device": (i, [vp, vp, sz, vp, sz, szp, opt, vp]),
+        "sfh_compress_device_async": (i, [vp, vp, sz, vp, sz, vp, opt, vp]),
+        "sfh_compress_batch_device_async": (i, [vp, sz, vpp, u64p, vpp, u64p, vp, opt, vp]),
+        "sfh_compress_batch": (i, [vp, sz, vpp, u64p, vpp, u64p, u64p, opt]),
+        "sfh_batch_index_size": (i, [vp, szp, szp]),
+        "sfh_copy_batch_index": (i, [vp, vp, vp, vp, i, vp]),
+        # the indexed decoder: batches and ranges
+        "sfh_decompress_batch_device_async": (i, [vp, sz, vpp, u64p, vp, vp, vpp, u64p, vp, u32, vp, vp]),
+        "sfh_decompress_batch": (i, [vp, sz, vpp, u64p, vp, vp, vpp, u64p, vp, u32, vp]),
+        "sfh_decompress_ranges_device_async": (i, [vp, vp, sz, vp, vp, sz, u64, u32, sz, u64p, u64p, vpp, vp, vp]),
+        "sfh_decompress_range_device": (i, [vp, vp, sz, vp, vp, sz, u64, u32, u64, u64, vp, u32p, vp]),
+        "sfh_decompress_ranges": (i, [vp, vp, sz, vp, vp, sz, u64, u32, sz, u64p, u64p, vpp, vp]),
+        # decoding without side information
+        "sfh_recover_index_device": (i, [vp, vp, sz, u32, u64, vp, sz, vp, vp]),
+        "sfh_recover_index": (i, [vp, vp, sz, u32, u64, vp, sz, vp]),
+        "sfh_decompress_any_device": (i, [vp, vp, sz, u32, vp, u64, u32p, vp]),
+        "sfh_decompress_any": (i, [vp, vp, sz, u32, vp, u64, u64, u64p, u32p]),
+        "sfh_recover_index_batch_device": (i, [vp, sz, vpp, u64p, u32, u64p, vp, u32p, vp]),
+        "sfh_recover_index_batch": (i, [vp, sz, vpp, u64p, u32, u64p, vp, u32p]),
+        "sfh_decompress_any_batch_device": (i, [vp, sz, vpp, u64p, u32, vpp, u64p, u64p, u64p, u32p, vp]),
+        "sfh_decompress_any_batch": (i, [vp, sz, vpp, u64p, u32, vpp, u64p, u64p, u64p, u32p]),
+        "sfh_last_recover_stats": (i, [vp, C.POINTER(C.c_float * 2), C.POINTER(u64 * 2)]),
+        "sfh_inflate_stream_device": (i, [vp, vp, sz, u32, vp, u64, u64p, u32p, vp]),
+        "sfh_inflate_stream": (i, [vp, vp, sz, u32, vp, u64, u64p, u32p]),
+        "sfh_inflate_stream_batch_device": (i, [vp, sz, vpp, u64p, u32, vpp, u64p, u64p, u32p, vp]),
+        "sfh_inflate_stream_batch": (i, [vp, sz, vpp, u64p, u32, vpp, u64p, u64p, u32p]),
+        "sfh_last_stream_stats": (i, [vp, C.POINTER(C.c_float * STREAM_NSTAGES), C.POINTER(u64 * STREAM_NCOUNTS)]),
+        # multi-GPU gather
+        "sfh_gather_offsets": (i, [u64p, i, u64, u64, u64p]),
+        "sfh_comm_ranks": (i, [vp, C.POINTER(i), C.POINTER(i)]),
+        "sfh_gather_streams": (i, [vp, vp, i, vp, vp, vp, u64, u64, u64p, u64p, vp]),
+        # the last call's index, the single-stream indexed decoder, checksums, measurement
+        "sfh_last_block_bytes": (u32, [vp]),
+        "sfh_last_decode_scratch_bytes": (sz, [vp]),
+        "sfh_index_entries": (sz, [vp]),
+        "sfh_copy_index": (i, [vp, vp, sz, i, vp]),
+        "sfh_copy_subindex": (i, [vp, vp, sz, i, vp]),
+        "sfh_decompress_device": (i, [vp, vp, sz, vp, vp, sz, vp, sz, u32, u32p, vp]),
+        "sfh_decompress": (i, [vp, vp, sz, vp, vp, sz, vp, sz, u32, u32p]),
+        "sfh_last_inflate_ms": (i, [vp, C.POINTER(C.c_float * INFLATE_NSTAGES)]),
+        "sfh_inflate_stage_name": (C.c_char_p, [i]),
+        "sfh_checksum_device": (i, [vp, vp, sz, u32, u32p, vp]),
+        "sfh_crc32_combine": (u32, [u32, u32, u64]),
+        "sfh_adler32_combine": (u32, [u32, u32, u64]),
+        "sfh_set_profiling": (None, [vp, i]),
+        "sfh_last_stage_ms": (i, [vp, C.POINTER(C.c_float * NSTAGES)]),
+        "sfh_stage_name": (C.c_char_p, [i]),
+        "sfh_debug_read": (i, [vp, i, vp, sz]),
+        "sfh_lds_order_check": (i, [vp, u32, u32, u32, u64p, u64p]),
+    }
+
+
+PROTOTYPES = _prototypes()
+EXPORTS = list(PROTOTYPES)  # every symbol include/starflate_hip.h declares
 _LIB = None
 
 
@@ -111,177 +192,10 @@ def lib():
     except ImportError:
         pass
     L = C.CDLL(path)
-    vp, sz = C.c_void_p, C.c_size_t
-    L.sfh_default_options.argtypes = [C.POINTER(Options)]
-    L.sfh_default_options.restype = None
-    L.sfh_device_count.argtypes = []
-    L.sfh_device_count.restype = C.c_int
-    L.sfh_get_device_props.argtypes = [C.c_int, C.POINTER(DeviceProps)]
-    L.sfh_get_device_props.restype = C.c_int
-    L.sfh_create.argtypes = [C.POINTER(vp), C.c_int]
-    L.sfh_create.restype = C.c_int
-    L.sfh_destroy.argtypes = [vp]
-    L.sfh_destroy.restype = None
-    L.sfh_last_error.argtypes = [vp]
-    L.sfh_last_error.restype = C.c_char_p
-    L.sfh_compress_bound.argtypes = [sz, C.c_uint32]
-    L.sfh_compress_bound.restype = sz
-    L.sfh_compress_bound_container.argtypes = [sz, C.c_uint32, C.c_uint32]
-    L.sfh_compress_bound_container.restype = sz
-    L.sfh_dz_header_bytes.argtypes = [sz]
-    L.sfh_dz_header_bytes.restype = sz
-    L.sfh_dz_read_index.argtypes = [vp, sz, C.POINTER(DzInfo), vp, sz]
-    L.sfh_dz_read_index.restype = C.c_int
-    L.sfh_dz_read_index_device.argtypes = [vp, vp, sz, C.POINTER(DzInfo), vp, sz, vp]
-    L.sfh_dz_read_index_device.restype = C.c_int
-    L.sfh_decompress_dz_device.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), vp]
-    L.sfh_decompress_dz_device.restype = C.c_int
-    L.sfh_decompress_dz.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
-    L.sfh_decompress_dz.restype = C.c_int
-    L.sfh_decompress_dz_ranges.argtypes = [vp, vp, sz, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(vp), vp]
-    L.sfh_decompress_dz_ranges.restype = C.c_int
-    L.sfh_bgzf_bound.argtypes = [sz]
-    L.sfh_bgzf_bound.restype = sz
-    L.sfh_compress_bgzf_device_async.argtypes = [vp, vp, sz, vp, sz, vp, C.POINTER(Options), vp]
-    L.sfh_compress_bgzf_device_async.restype = C.c_int
-    L.sfh_compress_bgzf_device.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options), vp]
-    L.sfh_compress_bgzf_device.restype = C.c_int
-    L.sfh_compress_bgzf.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]
-    L.sfh_compress_bgzf.restype = C.c_int
-    L.sfh_bgzf_read_index.argtypes = [vp, sz, C.POINTER(BgzfInfo), vp, vp, sz]
-    L.sfh_bgzf_read_index.restype = C.c_int
-    L.sfh_bgzf_read_index_device.argtypes = [vp, vp, sz, C.POINTER(BgzfInfo), vp, vp, sz, vp]
-    L.sfh_bgzf_read_index_device.restype = C.c_int
-    L.sfh_decompress_bgzf_device.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), vp]
-    L.sfh_decompress_bgzf_device.restype = C.c_int
-    L.sfh_decompress_bgzf_wide_device.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), vp]
-    L.sfh_decompress_bgzf_wide_device.restype = C.c_int
-    L.sfh_decompress_bgzf.argtypes = [vp, vp, sz, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
-    L.sfh_decompress_bgzf.restype = C.c_int
-    u64 = C.POINTER(C.c_uint64)
-    L.sfh_decompress_bgzf_ranges_device.argtypes = [vp, vp, sz, vp, vp, C.POINTER(BgzfInfo), sz, u64, u64, C.POINTER(vp), vp, vp]
-    L.sfh_decompress_bgzf_ranges_device.restype = C.c_int
-    L.sfh_decompress_bgzf_ranges.argtypes = [vp, vp, sz, vp, vp, C.POINTER(BgzfInfo), sz, u64, u64, C.POINTER(vp), vp]
-    L.sfh_decompress_bgzf_ranges.restype = C.c_int
-    L.sfh_bgzf_voffsets_to_offsets.argtypes = [vp, vp, C.c_uint32, sz, vp, vp]
-    L.sfh_bgzf_voffsets_to_offsets.restype = C.c_int
-    L.sfh_bgzf_offsets_to_voffsets.argtypes = [vp, vp, C.c_uint32, sz, vp, vp]
-    L.sfh_bgzf_offsets_to_voffsets.restype = C.c_int
-    L.sfh_zip_read_index.argtypes = [vp, sz, C.POINTER(ZipInfo), vp, sz]
-    L.sfh_zip_read_index.restype = C.c_int
-    L.sfh_zip_read_index_device.argtypes = [vp, vp, sz, C.POINTER(ZipInfo), vp, sz, vp]
-    L.sfh_zip_read_index_device.restype = C.c_int
-    L.sfh_decompress_zip_device.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp]
-    L.sfh_decompress_zip_device.restype = C.c_int
-    L.sfh_decompress_zip.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp]
-    L.sfh_decompress_zip.restype = C.c_int
-    L.sfh_zip_bound.argtypes = [sz, vp, vp]
-    L.sfh_zip_bound.restype = sz
-    L.sfh_compress_zip_device_async.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, C.POINTER(Options), vp]
-    L.sfh_compress_zip_device_async.restype = C.c_int
-    L.sfh_compress_zip_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, C.POINTER(sz), C.POINTER(Options), vp]
-    L.sfh_compress_zip_device.restype = C.c_int
-    L.sfh_compress_zip.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, C.POINTER(sz), C.POINTER(Options)]
-    L.sfh_compress_zip.restype = C.c_int
-    L.sfh_compress.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]
-    L.sfh_compress.restype = C.c_int
-    L.sfh_compress_multi.argtypes = [C.POINTER(vp), C.c_int, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options)]
-    L.sfh_compress_multi.restype = C.c_int
-    L.sfh_compress_device.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(Options), vp]
-    L.sfh_compress_device.restype = C.c_int
-    L.sfh_compress_device_async.argtypes = [vp, vp, sz, vp, sz, vp, C.POINTER(Options), vp]
-    L.sfh_compress_device_async.restype = C.c_int
-    u64p = C.POINTER(C.c_uint64)
-    L.sfh_compress_batch_device_async.argtypes = [vp, sz, C.POINTER(vp), u64p, C.POINTER(vp), u64p, vp, C.POINTER(Options), vp]
-    L.sfh_compress_batch_device_async.restype = C.c_int
-    L.sfh_compress_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, C.POINTER(vp), u64p, u64p, C.POINTER(Options)]
-    L.sfh_compress_batch.restype = C.c_int
-    L.sfh_batch_index_size.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
-    L.sfh_batch_index_size.restype = C.c_int
-    L.sfh_copy_batch_index.argtypes = [vp, vp, vp, vp, C.c_int, vp]
-    L.sfh_copy_batch_index.restype = C.c_int
-    L.sfh_decompress_batch_device_async.argtypes = [vp, sz, C.POINTER(vp), u64p, vp, vp, C.POINTER(vp), u64p, vp, C.c_uint32, vp, vp]
-    L.sfh_decompress_batch_device_async.restype = C.c_int
-    L.sfh_decompress_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, vp, vp, C.POINTER(vp), u64p, vp, C.c_uint32, vp]
-    L.sfh_decompress_batch.restype = C.c_int
-    L.sfh_decompress_ranges_device_async.argtypes = [vp, vp, sz, vp, vp, sz, C.c_uint64, C.c_uint32, sz, u64p, u64p, C.POINTER(vp), vp, vp]
-    L.sfh_decompress_ranges_device_async.restype = C.c_int
-    L.sfh_decompress_range_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, vp,
-                                              C.POINTER(C.c_uint32), vp]
-    L.sfh_decompress_range_device.restype = C.c_int
-    L.sfh_decompress_ranges.argtypes = [vp, vp, sz, vp, vp, sz, C.c_uint64, C.c_uint32, sz, u64p, u64p, C.POINTER(vp), vp]
-    L.sfh_decompress_ranges.restype = C.c_int
-    L.sfh_recover_index_device.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint64, vp, sz, vp, vp]
-    L.sfh_recover_index_device.restype = C.c_int
-    L.sfh_recover_index.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint64, vp, sz, vp]
-    L.sfh_recover_index.restype = C.c_int
-    L.sfh_decompress_any_device.argtypes = [vp, vp, sz, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint32), vp]
-    L.sfh_decompress_any_device.restype = C.c_int
-    L.sfh_decompress_any.argtypes = [vp, vp, sz, C.c_uint32, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
-                                     C.POINTER(C.c_uint32)]
-    L.sfh_decompress_any.restype = C.c_int
-    u32p = C.POINTER(C.c_uint32)
-    L.sfh_recover_index_batch_device.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, u64p, vp, u32p, vp]
-    L.sfh_recover_index_batch_device.restype = C.c_int
-    L.sfh_recover_index_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, u64p, vp, u32p]
-    L.sfh_recover_index_batch.restype = C.c_int
-    L.sfh_decompress_any_batch_device.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, C.POINTER(vp), u64p, u64p, u64p, u32p, vp]
-    L.sfh_decompress_any_batch_device.restype = C.c_int
-    L.sfh_decompress_any_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, C.POINTER(vp), u64p, u64p, u64p, u32p]
-    L.sfh_decompress_any_batch.restype = C.c_int
-    L.sfh_last_recover_stats.argtypes = [vp, C.POINTER(C.c_float * 2), C.POINTER(C.c_uint64 * 2)]
-    L.sfh_last_recover_stats.restype = C.c_int
-    L.sfh_inflate_stream_device.argtypes = [vp, vp, sz, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), vp]
-    L.sfh_inflate_stream_device.restype = C.c_int
-    L.sfh_inflate_stream.argtypes = [vp, vp, sz, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
-    L.sfh_inflate_stream.restype = C.c_int
-    L.sfh_inflate_stream_batch_device.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, C.POINTER(vp), u64p, u64p,
-                                                  C.POINTER(C.c_uint32), vp]
-    L.sfh_inflate_stream_batch_device.restype = C.c_int
-    L.sfh_inflate_stream_batch.argtypes = [vp, sz, C.POINTER(vp), u64p, C.c_uint32, C.POINTER(vp), u64p, u64p, C.POINTER(C.c_uint32)]
-    L.sfh_inflate_stream_batch.restype = C.c_int
-    L.sfh_last_stream_stats.argtypes = [vp, C.POINTER(C.c_float * 5), C.POINTER(C.c_uint64 * 6)]
-    L.sfh_last_stream_stats.restype = C.c_int
-    L.sfh_gather_offsets.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
-    L.sfh_gather_offsets.restype = C.c_int
-    L.sfh_comm_ranks.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.sfh_comm_ranks.restype = C.c_int
-    L.sfh_gather_streams.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
-    L.sfh_gather_streams.restype = C.c_int
-    L.sfh_last_block_bytes.argtypes = [vp]
-    L.sfh_last_block_bytes.restype = C.c_uint32
-    L.sfh_last_decode_scratch_bytes.argtypes = [vp]
-    L.sfh_last_decode_scratch_bytes.restype = sz
-    L.sfh_index_entries.argtypes = [vp]
-    L.sfh_index_entries.restype = sz
-    L.sfh_copy_index.argtypes = [vp, vp, sz, C.c_int, vp]
-    L.sfh_copy_index.restype = C.c_int
-    L.sfh_copy_subindex.argtypes = [vp, vp, sz, C.c_int, vp]
-    L.sfh_copy_subindex.restype = C.c_int
-    L.sfh_decompress_device.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, C.c_uint32, C.POINTER(C.c_uint32), vp]
-    L.sfh_decompress_device.restype = C.c_int
-    L.sfh_decompress.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, C.c_uint32, C.POINTER(C.c_uint32)]
-    L.sfh_decompress.restype = C.c_int
-    L.sfh_last_inflate_ms.argtypes = [vp, C.POINTER(C.c_float * INFLATE_NSTAGES)]
-    L.sfh_last_inflate_ms.restype = C.c_int
-    L.sfh_inflate_stage_name.argtypes = [C.c_int]
-    L.sfh_inflate_stage_name.restype = C.c_char_p
-    L.sfh_checksum_device.argtypes = [vp, vp, sz, C.c_uint32, C.POINTER(C.c_uint32), vp]
-    L.sfh_checksum_device.restype = C.c_int
-    L.sfh_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
-    L.sfh_crc32_combine.restype = C.c_uint32
-    L.sfh_adler32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
-    L.sfh_adler32_combine.restype = C.c_uint32
-    L.sfh_set_profiling.argtypes = [vp, C.c_int]
-    L.sfh_set_profiling.restype = None
-    L.sfh_last_stage_ms.argtypes = [vp, C.POINTER(C.c_float * NSTAGES)]
-    L.sfh_last_stage_ms.restype = C.c_int
-    L.sfh_stage_name.argtypes = [C.c_int]
-    L.sfh_stage_name.restype = C.c_char_p
-    L.sfh_debug_read.argtypes = [vp, C.c_int, vp, sz]
-    L.sfh_debug_read.restype = C.c_int
-    L.sfh_lds_order_check.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    L.sfh_lds_order_check.restype = C.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
     _LIB = L
     return L
 

@@ -23,6 +23,56 @@ class StarflateError(RuntimeError):
         self.code = code
 
 
+# ---- marshalling for the C-ABI: one definition per idiom ----
+def _as_bytes(data):
+    """any bytes-like object or array -> a 1-D contiguous uint8 array over the same bytes (an array of another dtype is
+    converted value by value)"""
+    return np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).ravel()
+
+
+def _ptr(a):
+    """the address of a host array, null when it is empty or None (a CUDA tensor needs no such helper: an empty tensor's
+    data_ptr() is 0 already)"""
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _addr(a):
+    """the address of an optional host array or CUDA tensor: null for None only"""
+    if a is None:
+        return None
+    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+
+
+def _ptrs(arrays):
+    """void*[k] of host arrays' addresses: one _ptr per item"""
+    p = [_ptr(a) for a in arrays]
+    return (C.c_void_p * len(p))(*p)
+
+
+def _dptrs(tensors):
+    """void*[k] of CUDA tensors' addresses: null for an empty tensor (its data_ptr() is 0) and for None"""
+    p = [None if t is None else t.data_ptr() for t in tensors]
+    return (C.c_void_p * len(p))(*p)
+
+
+def _u64s(seq):
+    """uint64_t[k] of a sequence of ints"""
+    v = list(seq)
+    return (C.c_uint64 * len(v))(*v)
+
+
+def _host_dsts(sizes):
+    """one host destination per size, of one byte at least: its address is never null"""
+    return [np.empty(max(m, 1), dtype=np.uint8) for m in sizes]
+
+
+def _device_array(t, dtype):
+    """is t a contiguous CUDA tensor of that dtype ("int64", "int32")?"""
+    import torch
+
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == getattr(torch, dtype) and t.is_contiguous()
+
+
 class Compressor:
     """One sfh_ctx (one GPU). Not thread-safe; use one per thread / per rank."""
 
@@ -49,6 +99,61 @@ class Compressor:
         if rc:
             raise StarflateError(rc, self._lib.sfh_last_error(self._h).decode())
 
+    def _check_tensor(self, t):
+        import torch
+
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous()):
+            raise ValueError("expected a contiguous 1-D uint8 CUDA tensor")
+        if t.device.index != self.device:
+            raise ValueError(f"tensor is on cuda:{t.device.index}, compressor on cuda:{self.device}")
+
+    def _check_tensors(self, ts):
+        for t in ts:
+            self._check_tensor(t)
+
+    def _stream(self, stream, device=None):
+        """the void* of a stream handle; None: the current stream of this context's device (which _check_tensor pins every
+        tensor of a call to), or of `device`"""
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream(self.device if device is None else device).cuda_stream
+        return C.c_void_p(stream)
+
+    def _new(self, n, dtype="uint8", zeros=False):
+        """a new tensor of n elements on this context's device; zeros: for what a call may leave unwritten"""
+        import torch
+
+        return (torch.zeros if zeros else torch.empty)(n, dtype=getattr(torch, dtype), device=torch.device("cuda", self.device))
+
+    def _new_bytes(self, sizes):
+        """new uint8 tensors of these sizes on this context's device (a batch's outputs: torch and the device looked up once)"""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        return [torch.empty(m, dtype=torch.uint8, device=dev) for m in sizes]
+
+    def _out(self, out, n, floor=1):
+        """a call's output tensor: the caller's, or a new one of n bytes (`floor` at least)"""
+        if out is None:
+            out = self._new(max(int(n), floor))
+        self._check_tensor(out)
+        return out
+
+    def _outs(self, outs, sizes, noun, name=None):
+        """a call's output tensors, one per `noun` ("item", "range", "entry"): the caller's, or new ones of sizes[i] bytes (one
+        at least).  sizes: one entry per noun; where the call names that argument (`name`), the bytes each tensor must hold."""
+        if outs is None:
+            outs = self._new_bytes(max(m, 1) for m in sizes)
+        outs = list(outs)
+        if name is None:
+            if len(outs) != len(sizes):
+                raise ValueError(f"outs must hold one tensor per {noun}")
+        elif len(outs) != len(sizes) or any(o.numel() < m for o, m in zip(outs, sizes)):
+            raise ValueError(f"outs must hold one tensor of at least {name}[i] bytes per {noun}")
+        self._check_tensors(outs)
+        return outs
+
     @staticmethod
     def compress_bound(n):
         return _capi.lib().sfh_compress_bound(int(n), 0)
@@ -67,48 +172,44 @@ class Compressor:
     # ---- host buffers (PCIe inclusive) ----
     def compress(self, data, strategy="auto", final_stream=True, lazy=True, stored_fast_path=True, container="raw",
                  block_bytes=0, effort="default"):
-        src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        src = _as_bytes(data)
         cap = self._bound(src.size, container, block_bytes)
         dst = np.empty(cap, dtype=np.uint8)
         out_n = C.c_size_t(0)
         opt = _capi.make_options(strategy, final_stream, lazy, stored_fast_path, container, block_bytes, effort)
-        self._check(self._lib.sfh_compress(self._h, src.ctypes.data if src.size else None, src.size,
-                                           dst.ctypes.data, cap, C.byref(out_n), C.byref(opt)))
+        self._check(self._lib.sfh_compress(self._h, _ptr(src), src.size, dst.ctypes.data, cap, C.byref(out_n), C.byref(opt)))
         return dst[: out_n.value].tobytes()
 
     # ---- device buffers (torch uint8 CUDA tensors) ----
     def compress_tensor(self, src, out=None, strategy="auto", final_stream=True, lazy=True, stream=None,
                         stored_fast_path=True, container="raw", block_bytes=0, effort="default"):
         """src: 1-D uint8 tensor on this device. Returns (out tensor, stream byte count)."""
-        import torch
-
         self._check_tensor(src)
-        n = src.numel()
-        cap = self._bound(n, container, block_bytes)
-        if out is None:
-            out = torch.empty(cap, dtype=torch.uint8, device=src.device)
-        self._check_tensor(out)
+        cap = self._bound(src.numel(), container, block_bytes)
+        out = self._out(out, cap)
         out_n = C.c_size_t(0)
         opt = _capi.make_options(strategy, final_stream, lazy, stored_fast_path, container, block_bytes, effort)
-        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
-        self._check(self._lib.sfh_compress_device(self._h, src.data_ptr() if n else None, n, out.data_ptr(),
-                                                  out.numel(), C.byref(out_n), C.byref(opt), C.c_void_p(s)))
+        self._check(self._lib.sfh_compress_device(self._h, src.data_ptr(), src.numel(), out.data_ptr(), out.numel(), C.byref(out_n),
+                                                  C.byref(opt), self._stream(stream)))
         return out, out_n.value
 
-    def compress_tensor_async(self, src, out, size_out, strategy="auto", final_stream=True, lazy=True, stream=None,
-                              container="raw", block_bytes=0, effort="default"):
-        """Enqueue only. size_out: 1-element int64 CUDA tensor receiving the stream size."""
+    def _compress_async(self, fn, src, out, size_out, stream, **options):
+        """compress_tensor_async and compress_bgzf_tensor_async: the checks, then the enqueue of fn with make_options(**options)"""
         import torch
 
         self._check_tensor(src)
         self._check_tensor(out)
         if size_out.dtype not in (torch.int64, torch.uint64) or not size_out.is_cuda:
             raise ValueError("size_out must be a 1-element int64 CUDA tensor")
-        opt = _capi.make_options(strategy, final_stream, lazy, container=container, block_bytes=block_bytes, effort=effort)
-        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
-        n = src.numel()
-        self._check(self._lib.sfh_compress_device_async(self._h, src.data_ptr() if n else None, n, out.data_ptr(),
-                                                        out.numel(), size_out.data_ptr(), C.byref(opt), C.c_void_p(s)))
+        opt = _capi.make_options(**options)
+        self._check(fn(self._h, src.data_ptr(), src.numel(), out.data_ptr(), out.numel(), size_out.data_ptr(), C.byref(opt),
+                       self._stream(stream)))
+
+    def compress_tensor_async(self, src, out, size_out, strategy="auto", final_stream=True, lazy=True, stream=None,
+                              container="raw", block_bytes=0, effort="default"):
+        """Enqueue only. size_out: 1-element int64 CUDA tensor receiving the stream size."""
+        self._compress_async(self._lib.sfh_compress_device_async, src, out, size_out, stream, strategy=strategy,
+                             final_stream=final_stream, lazy=lazy, container=container, block_bytes=block_bytes, effort=effort)
 
     # ---- BGZF, the blocked gzip of bgzip / htslib: one member per 32 KiB of input, then the EOF member (sfh_compress_bgzf*) ----
     @staticmethod
@@ -122,42 +223,28 @@ class Compressor:
         dst = np.empty(cap, dtype=np.uint8)
         out_n = C.c_size_t(0)
         opt = _capi.make_options(strategy, True, lazy, stored_fast_path, "raw", 0, effort)
-        self._check(self._lib.sfh_compress_bgzf(self._h, src.ctypes.data if src.size else None, src.size, dst.ctypes.data, cap,
-                                                C.byref(out_n), C.byref(opt)))
+        self._check(self._lib.sfh_compress_bgzf(self._h, _ptr(src), src.size, dst.ctypes.data, cap, C.byref(out_n), C.byref(opt)))
         return dst[: out_n.value].tobytes()
 
     def compress_bgzf_tensor(self, src, out=None, strategy="auto", lazy=True, stream=None, stored_fast_path=True, effort="default",
                              **options):
         """src: 1-D uint8 tensor on this device.  Returns (out tensor, file byte count).  options: sfh_options fields the
         call refuses when set otherwise (container, final_stream, block_bytes), passed through for its refusals to be seen."""
-        import torch
-
         self._check_tensor(src)
-        n = src.numel()
         if out is None:
-            out = torch.empty(self.bgzf_bound(n), dtype=torch.uint8, device=src.device)
+            out = self._new(self.bgzf_bound(src.numel()))
         self._check_tensor(out)
         out_n = C.c_size_t(0)
         opt = _capi.make_options(strategy, options.get("final_stream", True), lazy, stored_fast_path, options.get("container", "raw"),
                                  options.get("block_bytes", 0), effort)
-        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
-        self._check(self._lib.sfh_compress_bgzf_device(self._h, src.data_ptr() if n else None, n, out.data_ptr(), out.numel(),
-                                                       C.byref(out_n), C.byref(opt), C.c_void_p(s)))
+        self._check(self._lib.sfh_compress_bgzf_device(self._h, src.data_ptr(), src.numel(), out.data_ptr(), out.numel(), C.byref(out_n),
+                                                       C.byref(opt), self._stream(stream)))
         return out, out_n.value
 
     def compress_bgzf_tensor_async(self, src, out, size_out, strategy="auto", lazy=True, stream=None, effort="default"):
         """Enqueue only, no host synchronisation.  size_out: 1-element int64 CUDA tensor receiving the file's size."""
-        import torch
-
-        self._check_tensor(src)
-        self._check_tensor(out)
-        if size_out.dtype not in (torch.int64, torch.uint64) or not size_out.is_cuda:
-            raise ValueError("size_out must be a 1-element int64 CUDA tensor")
-        opt = _capi.make_options(strategy, True, lazy, effort=effort)
-        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
-        n = src.numel()
-        self._check(self._lib.sfh_compress_bgzf_device_async(self._h, src.data_ptr() if n else None, n, out.data_ptr(), out.numel(),
-                                                             size_out.data_ptr(), C.byref(opt), C.c_void_p(s)))
+        self._compress_async(self._lib.sfh_compress_bgzf_device_async, src, out, size_out, stream, strategy=strategy,
+                             final_stream=True, lazy=lazy, effort=effort)
 
     def bgzf_index(self, data):
         """The members of a BGZF file -> (member_off, out_off, info dict): bgzf_index() at module level, on the host."""
@@ -167,17 +254,13 @@ class Compressor:
         """src: 1-D uint8 tensor on this device holding a BGZF file -> (member_off, out_off: int64 tensors of members + 1
         entries on the device, info dict), found on the device by pointer jumping (sfh_bgzf_read_index_device).  A file that
         does not parse raises StarflateError with its DecompressStatus."""
-        import torch
-
         self._check_tensor(src)
         n = src.numel()
-        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
         info = _capi.BgzfInfo()
         cap = n // 26 + 2  # (a member is 26 bytes at least)
-        moff = torch.empty(cap, dtype=torch.int64, device=src.device)
-        ooff = torch.empty(cap, dtype=torch.int64, device=src.device)
-        self._check(self._lib.sfh_bgzf_read_index_device(self._h, src.data_ptr() if n else None, n, C.byref(info), moff.data_ptr(),
-                                                         ooff.data_ptr(), cap, C.c_void_p(s)))
+        moff, ooff = self._new(cap, "int64"), self._new(cap, "int64")
+        self._check(self._lib.sfh_bgzf_read_index_device(self._h, src.data_ptr(), n, C.byref(info), moff.data_ptr(), ooff.data_ptr(), cap,
+                                                         self._stream(stream)))
         if info.status:
             raise StarflateError(info.status, f"BGZF members: DecompressStatus {info.status}")
         m = info.members + 1
@@ -197,43 +280,28 @@ class Compressor:
         cap = int(out_off[-1])
         dst = np.empty(max(cap, 1), dtype=np.uint8)
         got, st = C.c_uint64(0), C.c_uint32(0)
-        self._check(self._lib.sfh_decompress_bgzf(self._h, src.ctypes.data if src.size else None, src.size, dst.ctypes.data, cap,
-                                                  C.byref(got), C.byref(st)))
+        self._check(self._lib.sfh_decompress_bgzf(self._h, _ptr(src), src.size, dst.ctypes.data, cap, C.byref(got), C.byref(st)))
         return (dst[: got.value].tobytes() if st.value == 0 else b""), int(st.value)
+
+    def _decompress_bgzf_to(self, fn, src, total_n, out, stream):
+        """decompress_bgzf_tensor and decompress_bgzf_wide_tensor: the two differ in the library entry"""
+        self._check_tensor(src)
+        out = self._out(out, total_n, 16)
+        got, st = C.c_uint64(0), C.c_uint32(0)
+        self._check(fn(self._h, src.data_ptr(), src.numel(), out.data_ptr(), int(total_n), C.byref(got), C.byref(st), self._stream(stream)))
+        return out, int(got.value), int(st.value)
 
     def decompress_bgzf_tensor(self, src, total_n, out=None, stream=None):
         """src: 1-D uint8 tensor on this device holding a BGZF file of total_n output bytes (bgzf_index) -> (out tensor,
         bytes written, DecompressStatus int).  A member above 32 KiB raises StarflateError with code -8."""
-        import torch
-
-        self._check_tensor(src)
-        if out is None:
-            out = torch.empty(max(int(total_n), 16), dtype=torch.uint8, device=src.device)
-        self._check_tensor(out)
-        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
-        got, st = C.c_uint64(0), C.c_uint32(0)
-        n = src.numel()
-        self._check(self._lib.sfh_decompress_bgzf_device(self._h, src.data_ptr() if n else None, n, out.data_ptr(), int(total_n),
-                                                         C.byref(got), C.byref(st), C.c_void_p(s)))
-        return out, int(got.value), int(st.value)
+        return self._decompress_bgzf_to(self._lib.sfh_decompress_bgzf_device, src, total_n, out, stream)
 
     def decompress_bgzf_wide_tensor(self, src, total_n, out=None, stream=None):
         """decompress_bgzf_tensor for every conforming BGZF file: members of up to 65536 bytes (bgzip and htslib write 65280)
         decode on the device, in the indexed decoder's wide rows (sfh_decompress_bgzf_wide_device); a file without a member
         above 32 KiB takes decompress_bgzf_tensor's path.  A member claiming more than 65536 bytes raises StarflateError with
         code -8."""
-        import torch
-
-        self._check_tensor(src)
-        if out is None:
-            out = torch.empty(max(int(total_n), 16), dtype=torch.uint8, device=src.device)
-        self._check_tensor(out)
-        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
-        got, st = C.c_uint64(0), C.c_uint32(0)
-        n = src.numel()
-        self._check(self._lib.sfh_decompress_bgzf_wide_device(self._h, src.data_ptr() if n else None, n, out.data_ptr(), int(total_n),
-                                                              C.byref(got), C.byref(st), C.c_void_p(s)))
-        return out, int(got.value), int(st.value)
+        return self._decompress_bgzf_to(self._lib.sfh_decompress_bgzf_wide_device, src, total_n, out, stream)
 
     # ---- BGZF random access: byte ranges of a BGZF file's output (sfh_decompress_bgzf_ranges*) ----
     def read_bgzf_ranges(self, bgzf, offsets, lengths, index=None):
@@ -246,18 +314,22 @@ class Compressor:
         offs, lens = [int(o) for o in offsets], [int(m) for m in lengths]
         if len(offs) != len(lens) or any(o < 0 or m < 0 for o, m in zip(offs, lens)):
             raise ValueError("offsets and lengths: one non-negative pair per range")
-        k = len(offs)
-        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in lens]
-        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
-        st = np.zeros(max(k, 1), dtype=np.uint32)
         if index is None:
             moff = ooff = info = None
         else:
             moff, ooff, info = _bgzf_index_args(index)
-        self._check(self._lib.sfh_decompress_bgzf_ranges(
-            self._h, src.ctypes.data if src.size else None, src.size, moff.ctypes.data if moff is not None else None,
-            ooff.ctypes.data if ooff is not None else None, C.byref(info) if info is not None else None, k,
-            (C.c_uint64 * k)(*offs), (C.c_uint64 * k)(*lens), dp, st.ctypes.data))
+        return self._ranges_to_host(lens, lambda dp, st: self._lib.sfh_decompress_bgzf_ranges(
+            self._h, _ptr(src), src.size, _addr(moff), _addr(ooff), C.byref(info) if info is not None else None, len(offs),
+            _u64s(offs), _u64s(lens), dp, st))
+
+    def _ranges_to_host(self, lens, call):
+        """The host range readers' tail: a destination and a status per range, the library call -- call(the destinations'
+        void*[k], the status array's address) -- and its results: (list of bytes, None where a range's status is not 0; uint32
+        status array)."""
+        k = len(lens)
+        dsts = _host_dsts(lens)
+        st = np.zeros(max(k, 1), dtype=np.uint32)
+        self._check(call(_ptrs(dsts), st.ctypes.data))
         return [dsts[i][: lens[i]].tobytes() if st[i] == 0 else None for i in range(k)], st[:k]
 
     def read_bgzf_ranges_tensor(self, src, member_off, out_off, info, offsets, lengths, outs=None, stream=None):
@@ -266,12 +338,9 @@ class Compressor:
         slices of one packed buffer will do) of at least lengths[i] bytes per range, not overlapping (default: new ones);
         range i's bytes are outs[i][:lengths[i]]; status: an int32 tensor on the device, one DecompressStatus per range.  Two
         host synchronisations of `stream` (default: the current one): the planner's row total, then the end of the call."""
-        import torch
-
         self._check_tensor(src)
-        for t in (member_off, out_off):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
-                raise ValueError("member_off / out_off must be contiguous int64 CUDA tensors")
+        if not (_device_array(member_off, "int64") and _device_array(out_off, "int64")):
+            raise ValueError("member_off / out_off must be contiguous int64 CUDA tensors")
         binfo = _bgzf_info_struct(info)
         if member_off.numel() != binfo.members + 1 or out_off.numel() != binfo.members + 1:
             raise ValueError("member_off / out_off must hold members + 1 entries")
@@ -279,20 +348,11 @@ class Compressor:
         if len(offs) != len(lens) or any(o < 0 or m < 0 for o, m in zip(offs, lens)):
             raise ValueError("offsets and lengths: one non-negative pair per range")
         k = len(offs)
-        dev = torch.device("cuda", self.device)
-        if outs is None:
-            outs = [torch.empty(max(m, 1), dtype=torch.uint8, device=dev) for m in lens]
-        outs = list(outs)
-        if len(outs) != k or any(o.numel() < m for o, m in zip(outs, lens)):
-            raise ValueError("outs must hold one tensor of at least lengths[i] bytes per range")
-        for t in outs:
-            self._check_tensor(t)
-        status = torch.zeros(max(k, 1), dtype=torch.int32, device=dev)
-        dp = (C.c_void_p * k)(*[o.data_ptr() for o in outs])
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        outs = self._outs(outs, lens, "range", "lengths")
+        status = self._new(max(k, 1), "int32", zeros=True)
         self._check(self._lib.sfh_decompress_bgzf_ranges_device(
-            self._h, src.data_ptr(), src.numel(), member_off.data_ptr(), out_off.data_ptr(), C.byref(binfo), k,
-            (C.c_uint64 * k)(*offs), (C.c_uint64 * k)(*lens), dp, C.c_void_p(status.data_ptr()), C.c_void_p(s)))
+            self._h, src.data_ptr(), src.numel(), member_off.data_ptr(), out_off.data_ptr(), C.byref(binfo), k, _u64s(offs),
+            _u64s(lens), _dptrs(outs), status.data_ptr(), self._stream(stream)))
         return outs, status[:k]
 
     # ---- many independent items, each its own stream, in one call (sfh_compress_batch*) ----
@@ -300,17 +360,14 @@ class Compressor:
                        block_bytes=0, effort="default"):
         """Host buffers: a sequence of bytes-like items -> list of streams, item i's byte-identical to compress(items[i])
         with the same options (block_bytes=0 resolves per item)."""
-        srcs = [np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else np.ascontiguousarray(d, dtype=np.uint8).ravel()
-                for d in items]
+        srcs = [_as_bytes(d) for d in items]
         k = len(srcs)
-        n = (C.c_uint64 * k)(*[a.size for a in srcs])
         caps = [self.compress_bound(a.size) for a in srcs]
-        dsts = [np.empty(c, dtype=np.uint8) for c in caps]
-        sp = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a in srcs])
-        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
+        dsts = _host_dsts(caps)
         out_n = (C.c_uint64 * k)()
         opt = _capi.make_options(strategy, final_stream, lazy, stored_fast_path, container, block_bytes, effort)
-        self._check(self._lib.sfh_compress_batch(self._h, k, sp, n, dp, (C.c_uint64 * k)(*caps), out_n, C.byref(opt)))
+        self._check(self._lib.sfh_compress_batch(self._h, k, _ptrs(srcs), _u64s(a.size for a in srcs), _ptrs(dsts), _u64s(caps), out_n,
+                                                 C.byref(opt)))
         return [dsts[i][: out_n[i]].tobytes() for i in range(k)]
 
     def compress_batch_tensors(self, srcs, outs=None, stream=None, strategy="auto", final_stream=True, lazy=True,
@@ -318,29 +375,16 @@ class Compressor:
         """Device buffers: 1-D uint8 tensors on this device -> (outs, sizes).  Enqueued on `stream` (default: the current
         one) without a host synchronisation; sizes is an int64 tensor on the device, valid once the stream gets there.
         outs default to new tensors of compress_bound(n) bytes."""
-        import torch
-
         srcs = list(srcs)
-        for t in srcs:
-            self._check_tensor(t)
-        k = len(srcs)
-        dev = torch.device("cuda", self.device)
+        self._check_tensors(srcs)
         if outs is None:
-            outs = [torch.empty(self.compress_bound(t.numel()), dtype=torch.uint8, device=dev) for t in srcs]
-        outs = list(outs)
-        if len(outs) != k:
-            raise ValueError("outs must hold one tensor per item")
-        for t in outs:
-            self._check_tensor(t)
-        sizes = torch.empty(k, dtype=torch.int64, device=dev)  # (every entry is written by the call)
-        sp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in srcs])
-        dp = (C.c_void_p * k)(*[t.data_ptr() for t in outs])
-        n = (C.c_uint64 * k)(*[t.numel() for t in srcs])
-        caps = (C.c_uint64 * k)(*[t.numel() for t in outs])
+            outs = self._new_bytes(self.compress_bound(t.numel()) for t in srcs)
+        outs = self._outs(outs, srcs, "item")
+        sizes = self._new(len(srcs), "int64")  # (every entry is written by the call)
         opt = _capi.make_options(strategy, final_stream, lazy, stored_fast_path, container, block_bytes, effort)
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        self._check(self._lib.sfh_compress_batch_device_async(self._h, k, sp, n, dp, caps, C.c_void_p(sizes.data_ptr()),
-                                                              C.byref(opt), C.c_void_p(s)))
+        self._check(self._lib.sfh_compress_batch_device_async(
+            self._h, len(srcs), _dptrs(srcs), _u64s(t.numel() for t in srcs), _dptrs(outs), _u64s(t.numel() for t in outs),
+            sizes.data_ptr(), C.byref(opt), self._stream(stream)))
         return outs, sizes
 
     def last_batch_index(self):
@@ -367,15 +411,14 @@ class Compressor:
         byte for byte compress_batch(...)[i] with container="raw" and the same options."""
         names, srcs = _zip_items(items)
         k = len(srcs)
-        n = (C.c_uint64 * k)(*[a.size for a in srcs])
+        n = _u64s(a.size for a in srcs)
         ln = (C.c_uint32 * k)(*[len(b) for b in names])
         cap = self._lib.sfh_zip_bound(k, n, ln)
         out = np.empty(max(cap, 1), dtype=np.uint8)
-        sp = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a in srcs])
         np_ = (C.c_char_p * k)(*names)
         got = C.c_size_t()
         opt = _capi.make_options(strategy, True, lazy, stored_fast_path, "raw", block_bytes, effort)
-        self._check(self._lib.sfh_compress_zip(self._h, k, sp, n, np_, ln, out.ctypes.data, cap, C.byref(got), C.byref(opt)))
+        self._check(self._lib.sfh_compress_zip(self._h, k, _ptrs(srcs), n, np_, ln, out.ctypes.data, cap, C.byref(got), C.byref(opt)))
         return out[: got.value].tobytes()
 
     def compress_zip_tensors(self, names, srcs, out=None, stream=None, strategy="auto", lazy=True, stored_fast_path=True,
@@ -383,45 +426,34 @@ class Compressor:
         """Device buffers: names (str or bytes) and 1-D uint8 tensors on this device -> (out, size).  Enqueued on `stream`
         (default: the current one); size is an int64 tensor of one element on the device, valid once the stream gets there.
         out defaults to a new tensor of zip_bound bytes."""
-        import torch
-
         names = [b.encode("utf-8") if isinstance(b, str) else bytes(b) for b in names]
         srcs = list(srcs)
         if len(names) != len(srcs):
             raise ValueError("one name per item")
-        for t in srcs:
-            self._check_tensor(t)
+        self._check_tensors(srcs)
         k = len(srcs)
-        dev = torch.device("cuda", self.device)
-        n = (C.c_uint64 * k)(*[t.numel() for t in srcs])
+        n = _u64s(t.numel() for t in srcs)
         ln = (C.c_uint32 * k)(*[len(b) for b in names])
         if out is None:
-            out = torch.empty(self._lib.sfh_zip_bound(k, n, ln), dtype=torch.uint8, device=dev)
+            out = self._new(self._lib.sfh_zip_bound(k, n, ln))
         self._check_tensor(out)
-        size = torch.empty(1, dtype=torch.int64, device=dev)
-        sp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in srcs])
+        size = self._new(1, "int64")
         np_ = (C.c_char_p * k)(*names)
         opt = _capi.make_options(strategy, True, lazy, stored_fast_path, "raw", block_bytes, effort)
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        self._check(self._lib.sfh_compress_zip_device_async(self._h, k, sp, n, np_, ln, C.c_void_p(out.data_ptr()), out.numel(),
-                                                            C.c_void_p(size.data_ptr()), C.byref(opt), C.c_void_p(s)))
+        self._check(self._lib.sfh_compress_zip_device_async(self._h, k, _dptrs(srcs), n, np_, ln, out.data_ptr(), out.numel(),
+                                                            size.data_ptr(), C.byref(opt), self._stream(stream)))
         return out, size
 
     def zip_index_tensor(self, src, stream=None):
         """The entry table of a ZIP archive on this device -> (info dict, entries): entries is a numpy structured array
         (ZIP_ENTRY_DTYPE), on the host.  A file whose index fails: its status in info, no entries."""
-        import torch
-
         self._check_tensor(src)
-        dev = torch.device("cuda", self.device)
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        s = self._stream(stream)
         info = _capi.ZipInfo()
-        p = C.c_void_p(src.data_ptr()) if src.numel() else None
-        rc = self._lib.sfh_zip_read_index_device(self._h, p, src.numel(), C.byref(info), None, 0, C.c_void_p(s))
+        rc = self._lib.sfh_zip_read_index_device(self._h, src.data_ptr(), src.numel(), C.byref(info), None, 0, s)
         ents = np.zeros(info.entries, ZIP_ENTRY_DTYPE)
         if rc == -2:
-            rc = self._lib.sfh_zip_read_index_device(self._h, p, src.numel(), C.byref(info), C.c_void_p(ents.ctypes.data), ents.size,
-                                                     C.c_void_p(s))
+            rc = self._lib.sfh_zip_read_index_device(self._h, src.data_ptr(), src.numel(), C.byref(info), ents.ctypes.data, ents.size, s)
         self._check(rc)
         return _zip_info_dict(info), ents
 
@@ -429,27 +461,17 @@ class Compressor:
         """Entries (rows of a zip_index table, any subset in any order) of the archive `src` on this device -> (outs, statuses).
         outs default to views of one packed buffer in which every entry starts 16-byte aligned (the layout of out_off for the
         whole table); statuses: numpy uint32, 0 = decoded and its CRC-32 verified."""
-        import torch
-
         self._check_tensor(src)
         ents = np.ascontiguousarray(entries, dtype=ZIP_ENTRY_DTYPE).ravel()
         k = ents.size
-        dev = torch.device("cuda", self.device)
         if outs is None:
             offs = np.concatenate([[0], np.cumsum((ents["usize"].astype(np.uint64) + np.uint64(15)) & ~np.uint64(15))]).astype(np.uint64)
-            buf = torch.empty(max(int(offs[-1]), 16), dtype=torch.uint8, device=dev)
+            buf = self._new(max(int(offs[-1]), 16))
             outs = [buf[int(offs[i]): int(offs[i]) + int(ents["usize"][i])] for i in range(k)]
-        outs = list(outs)
-        if len(outs) != k:
-            raise ValueError("outs must hold one tensor per entry")
-        for t in outs:
-            self._check_tensor(t)
-        dp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in outs])
-        caps = (C.c_uint64 * k)(*[t.numel() for t in outs])
+        outs = self._outs(outs, ents, "entry")
         st = np.zeros(k, np.uint32)
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-        self._check(self._lib.sfh_decompress_zip_device(self._h, C.c_void_p(src.data_ptr()) if src.numel() else None, src.numel(),
-                                                        C.c_void_p(ents.ctypes.data), k, dp, caps, C.c_void_p(st.ctypes.data), C.c_void_p(s)))
+        self._check(self._lib.sfh_decompress_zip_device(self._h, src.data_ptr(), src.numel(), ents.ctypes.data, k, _dptrs(outs),
+                                                        _u64s(t.numel() for t in outs), st.ctypes.data, self._stream(stream)))
         return outs, st
 
     def decompress_zip(self, data, names=None):
@@ -466,11 +488,9 @@ class Compressor:
             all_names = [all_names[i] for i in pick]
         k = ents.size
         dsts = [np.empty(int(e["usize"]), dtype=np.uint8) for e in ents]
-        dp = (C.c_void_p * k)(*[d.ctypes.data if d.size else None for d in dsts])
-        caps = (C.c_uint64 * k)(*[d.size for d in dsts])
         st = np.zeros(k, np.uint32)
-        self._check(self._lib.sfh_decompress_zip(self._h, src.ctypes.data, src.size, C.c_void_p(ents.ctypes.data), k, dp, caps,
-                                                 C.c_void_p(st.ctypes.data)))
+        self._check(self._lib.sfh_decompress_zip(self._h, src.ctypes.data, src.size, ents.ctypes.data, k, _ptrs(dsts),
+                                                 _u64s(d.size for d in dsts), st.ctypes.data))
         return {nm: (d.tobytes() if not s else None) for nm, d, s in zip(all_names, dsts, st)}, st
 
     # ---- block index + GPU decompress (the reference's decompress(), /root/reference/src/decompress.hpp:63-71,
@@ -501,8 +521,7 @@ class Compressor:
         import torch
 
         idx = torch.empty(n, dtype=torch.int64, device=device)
-        s = torch.cuda.current_stream(idx.device).cuda_stream
-        self._check(self._lib.sfh_copy_index(self._h, idx.data_ptr(), n, 1, C.c_void_p(s)))
+        self._check(self._lib.sfh_copy_index(self._h, idx.data_ptr(), n, 1, self._stream(None, idx.device)))
         return idx
 
     def last_subindex(self, device=None):
@@ -519,8 +538,7 @@ class Compressor:
         import torch
 
         sub = torch.empty((nseg, 32, 2), dtype=torch.int32, device=device)
-        s = torch.cuda.current_stream(sub.device).cuda_stream
-        self._check(self._lib.sfh_copy_subindex(self._h, sub.data_ptr(), words, 1, C.c_void_p(s)))
+        self._check(self._lib.sfh_copy_subindex(self._h, sub.data_ptr(), words, 1, self._stream(None, sub.device)))
         return sub
 
     def decompress_tensor(self, stream, index, out_n, out=None, hip_stream=None, subindex=None, *, block_bytes):
@@ -532,36 +550,31 @@ class Compressor:
         import torch
 
         self._check_tensor(stream)
-        if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int64 and index.is_contiguous()):
+        if not _device_array(index, "int64"):
             raise ValueError("index must be a contiguous int64 CUDA tensor")
         nseg = index.numel() - 1
-        if out is None:
-            out = torch.empty(max(int(out_n), 1), dtype=torch.uint8, device=stream.device)
-        self._check_tensor(out)
+        out = self._out(out, out_n)
         if out.numel() < out_n:
             raise ValueError("out is smaller than out_n")
         st = C.c_uint32(0)
-        s = torch.cuda.current_stream(stream.device).cuda_stream if hip_stream is None else hip_stream
         if subindex is not None and not (subindex.is_cuda and subindex.dtype == torch.int32 and subindex.is_contiguous()
                                          and subindex.numel() == nseg * _capi.SUBINDEX_WORDS):
             raise ValueError("subindex must be a contiguous int32 CUDA tensor of segments * 64 words")
-        self._check(self._lib.sfh_decompress_device(self._h, stream.data_ptr(), stream.numel(), index.data_ptr(),
-                                                    subindex.data_ptr() if subindex is not None else None, nseg,
+        self._check(self._lib.sfh_decompress_device(self._h, stream.data_ptr(), stream.numel(), index.data_ptr(), _addr(subindex), nseg,
                                                     out.data_ptr() if out_n else None, int(out_n), int(block_bytes),
-                                                    C.byref(st), C.c_void_p(s)))
+                                                    C.byref(st), self._stream(hip_stream)))
         return out[:out_n], st.value
 
     def decompress(self, data, index, out_n, subindex=None, *, block_bytes):
         """Host buffers: bytes-like stream + numpy uint64 index [+ numpy uint32 sub-index] -> (bytes, DecompressStatus int)."""
-        src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        src = _as_bytes(data)
         idx = np.ascontiguousarray(index, dtype=np.uint64)
         dst = np.empty(max(int(out_n), 1), dtype=np.uint8)
         st = C.c_uint32(0)
         sub = None if subindex is None else np.ascontiguousarray(subindex, dtype=np.uint32)
         if sub is not None and sub.size != (idx.size - 1) * _capi.SUBINDEX_WORDS:
             raise ValueError("subindex must hold segments * 64 words")
-        self._check(self._lib.sfh_decompress(self._h, src.ctypes.data, src.size, idx.ctypes.data,
-                                             sub.ctypes.data if sub is not None else None, idx.size - 1,
+        self._check(self._lib.sfh_decompress(self._h, src.ctypes.data, src.size, idx.ctypes.data, _addr(sub), idx.size - 1,
                                              dst.ctypes.data if out_n else None, int(out_n), int(block_bytes), C.byref(st)))
         return (dst[:out_n].tobytes() if st.value == 0 else b""), st.value
 
@@ -570,48 +583,38 @@ class Compressor:
         """stream: 1-D uint8 CUDA tensor (exactly the compressed bytes), out_n: its decoded size -> (index int64 CUDA tensor of
         segments + 1 offsets, depends uint8 CUDA tensor: 1 where a match of the segment reaches before its first byte).
         A stream that is not block-flushed every 32 KiB raises StarflateError with code -8 (SFH_E_NOT_INDEXABLE)."""
-        import torch
-
         self._check_tensor(stream)
         nseg = max(1, -(-int(out_n) // CHUNK_BYTES))
-        index = torch.empty(nseg + 1, dtype=torch.int64, device=stream.device)
-        depends = torch.empty(nseg, dtype=torch.uint8, device=stream.device)
-        s = torch.cuda.current_stream(stream.device).cuda_stream if hip_stream is None else hip_stream
+        index, depends = self._new(nseg + 1, "int64"), self._new(nseg)
         self._check(self._lib.sfh_recover_index_device(self._h, stream.data_ptr(), stream.numel(), _container(container),
-                                                       int(out_n), index.data_ptr(), nseg, depends.data_ptr(), C.c_void_p(s)))
+                                                       int(out_n), index.data_ptr(), nseg, depends.data_ptr(), self._stream(hip_stream)))
         return index, depends
 
     def decompress_any_tensor(self, stream, out_n=None, container="raw", out=None, hip_stream=None):
         """stream: 1-D uint8 CUDA tensor; out_n: decoded size (None: gzip's ISIZE) -> (out tensor, DecompressStatus int).
         No index, no block_bytes: the stream's own flush markers give the segments.  Not block-flushed: StarflateError -8."""
-        import torch
-
         self._check_tensor(stream)
         kind = _container(container)
         if out_n is None:
             out_n = _isize(stream[-4:].cpu().numpy().tobytes() if stream.numel() >= 4 else b"", kind)
-        if out is None:
-            out = torch.empty(max(int(out_n), 1), dtype=torch.uint8, device=stream.device)
-        self._check_tensor(out)
+        out = self._out(out, out_n)
         if out.numel() < out_n:
             raise ValueError("out is smaller than out_n")
         st = C.c_uint32(0)
-        s = torch.cuda.current_stream(stream.device).cuda_stream if hip_stream is None else hip_stream
         self._check(self._lib.sfh_decompress_any_device(self._h, stream.data_ptr(), stream.numel(), kind,
                                                         out.data_ptr() if out_n else None, int(out_n), C.byref(st),
-                                                        C.c_void_p(s)))
+                                                        self._stream(hip_stream)))
         return out[:out_n], st.value
 
     def decompress_any(self, data, out_n=None, container="raw"):
         """Host buffers: a bytes-like raw / zlib / gzip stream -> (bytes, DecompressStatus int), on the GPU without an index;
         out_n None: gzip's ISIZE.  Not block-flushed every 32 KiB: StarflateError -8 (decompress() falls back instead)."""
-        src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        src = _as_bytes(data)
         kind = _container(container)
         n = _isize(src[-4:].tobytes(), kind) if out_n is None else int(out_n)
         dst = np.empty(max(n, 1), dtype=np.uint8)
         st = C.c_uint32(0)
-        self._check(self._lib.sfh_decompress_any(self._h, src.ctypes.data if src.size else None, src.size, kind, dst.ctypes.data,
-                                                 n, n, None, C.byref(st)))
+        self._check(self._lib.sfh_decompress_any(self._h, _ptr(src), src.size, kind, dst.ctypes.data, n, n, None, C.byref(st)))
         return (dst[:n].tobytes() if st.value == 0 else b""), st.value
 
     def last_recover_stats(self):
@@ -627,28 +630,23 @@ class Compressor:
         speculative block starts (no index, no flush points needed).  out_n: the output capacity (None: a size query first,
         then exactly the output size -- gzip: ISIZE where that is more, the room a gzip decode asks for whatever its body
         produces); out: a uint8 CUDA tensor of at least out_n bytes.  Synchronises the stream."""
-        import torch
-
         self._check_tensor(stream)
         kind = _container(container)
-        s = torch.cuda.current_stream(stream.device).cuda_stream if hip_stream is None else hip_stream
+        s = self._stream(hip_stream)
         st, n = C.c_uint32(0), C.c_uint64(0)
-        src = stream.data_ptr() if stream.numel() else None
+        src = stream.data_ptr()
         if out_n is None:
-            self._check(self._lib.sfh_inflate_stream_device(self._h, src, stream.numel(), kind, None, 0, C.byref(n), C.byref(st),
-                                                            C.c_void_p(s)))
+            self._check(self._lib.sfh_inflate_stream_device(self._h, src, stream.numel(), kind, None, 0, C.byref(n), C.byref(st), s))
             if st.value:
                 return stream[:0], st.value
             out_n = max(n.value, _gzip_room(stream, kind))
         out_n = int(out_n)
-        if out is None:
-            out = torch.empty(max(out_n, 1), dtype=torch.uint8, device=stream.device)
-        self._check_tensor(out)
+        out = self._out(out, out_n)
         if out.numel() < out_n or out.numel() == 0:
             raise ValueError("out is smaller than out_n (or empty)")
         # (always a real pointer: a null dst with a capacity of 0 is the C interface's size query, which checks no trailer)
         self._check(self._lib.sfh_inflate_stream_device(self._h, src, stream.numel(), kind, out.data_ptr(), out_n, C.byref(n),
-                                                        C.byref(st), C.c_void_p(s)))
+                                                        C.byref(st), s))
         return (out[: n.value] if st.value == 0 else out[:0]), st.value
 
     def decompress_stream(self, data, out_n=None, container="raw"):
@@ -656,10 +654,10 @@ class Compressor:
         index and no flush points.  out_n: the output capacity (None: a size query first, then the queried size -- gzip: ISIZE
         where that is more, so that a trailer that claims more than the body gives is Error, as with any dst that holds
         ISIZE bytes).  b"" unless the status is 0."""
-        src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        src = _as_bytes(data)
         kind = _container(container)
         st, n = C.c_uint32(0), C.c_uint64(0)
-        sp = src.ctypes.data if src.size else None
+        sp = _ptr(src)
         if out_n is None:
             self._check(self._lib.sfh_inflate_stream(self._h, sp, src.size, kind, None, 0, C.byref(n), C.byref(st)))
             if st.value:
@@ -672,8 +670,8 @@ class Compressor:
 
     def last_stream_stats(self):
         """The last decompress_stream* call: per-stage ms (with profiling on, else zeros) and the chunk counts."""
-        ms = (C.c_float * 5)()
-        cnt = (C.c_uint64 * 6)()
+        ms = (C.c_float * _capi.STREAM_NSTAGES)()
+        cnt = (C.c_uint64 * _capi.STREAM_NCOUNTS)()
         self._check(self._lib.sfh_last_stream_stats(self._h, C.byref(ms), C.byref(cnt)))
         names = ("find_ms", "count_ms", "write_ms", "resolve_ms", "checksum_ms")
         keys = ("chunks", "candidates", "confirmed", "repair_rounds", "longest_chunk", "scratch_bytes")
@@ -686,7 +684,7 @@ class Compressor:
         first, then the queried sizes -- gzip: ISIZE where that is more).  An item whose status is not 0 comes back as b""."""
         srcs, n, caps, kind = _stream_batch_args(streams, sizes, container)
         k = len(srcs)
-        sp = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a in srcs])
+        sp = _ptrs(srcs)
         out_n = (C.c_uint64 * k)()
         st = (C.c_uint32 * k)()
         if caps is None:
@@ -696,11 +694,11 @@ class Compressor:
             first = [int(st[i]) for i in range(k)]
         else:
             live, first = [True] * k, [0] * k
-        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in caps]
+        dsts = _host_dsts(caps)
         # (an item that failed its size query is asked again as a query of its own: a null destination)
-        dp = (C.c_void_p * k)(*[d.ctypes.data if ok else None for d, ok in zip(dsts, live)])
+        dp = _ptrs(d if ok else None for d, ok in zip(dsts, live))
         if k:
-            self._check(self._lib.sfh_inflate_stream_batch(self._h, k, sp, n, kind, dp, (C.c_uint64 * k)(*caps), out_n, st))
+            self._check(self._lib.sfh_inflate_stream_batch(self._h, k, sp, n, kind, dp, _u64s(caps), out_n, st))
         stats = [int(st[i]) if live[i] else first[i] for i in range(k)]
         return [dsts[i][: out_n[i]].tobytes() if stats[i] == 0 else b"" for i in range(k)], stats
 
@@ -709,40 +707,29 @@ class Compressor:
         exactly the item's decoded bytes (empty unless its status is 0).  sizes: the output capacities (None: a size-query
         call first, then the queried sizes -- gzip: ISIZE where that is more); outs: one uint8 CUDA tensor of at least sizes[i] bytes per item (default: new ones).  Synchronises the
         stream."""
-        import torch
-
         streams = list(streams)
-        for t in streams:
-            self._check_tensor(t)
+        self._check_tensors(streams)
         kind = _container(container)
         k = len(streams)
-        dev = torch.device("cuda", self.device)
-        s = torch.cuda.current_stream(dev).cuda_stream if hip_stream is None else hip_stream
-        sp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in streams])
-        n = (C.c_uint64 * k)(*[t.numel() for t in streams])
+        s = self._stream(hip_stream)
+        sp = _dptrs(streams)
+        n = _u64s(t.numel() for t in streams)
         out_n = (C.c_uint64 * k)()
         st = (C.c_uint32 * k)()
         live, first = [True] * k, [0] * k
         if sizes is None:
-            self._check(self._lib.sfh_inflate_stream_batch_device(self._h, k, sp, n, kind, None, None, out_n, st, C.c_void_p(s)))
+            self._check(self._lib.sfh_inflate_stream_batch_device(self._h, k, sp, n, kind, None, None, out_n, st, s))
             sizes = [max(int(out_n[i]), _gzip_room(streams[i], kind)) if st[i] == 0 else 0 for i in range(k)]
             live = [st[i] == 0 for i in range(k)]
             first = [int(st[i]) for i in range(k)]
         caps = [int(m) for m in sizes]
         if len(caps) != k or any(m < 0 for m in caps):
             raise ValueError("sizes must hold one non-negative capacity per stream")
-        if outs is None:
-            outs = [torch.empty(max(m, 1), dtype=torch.uint8, device=dev) for m in caps]
-        outs = list(outs)
-        if len(outs) != k or any(o.numel() < m for o, m in zip(outs, caps)):
-            raise ValueError("outs must hold one tensor of at least sizes[i] bytes per item")
-        for t in outs:
-            self._check_tensor(t)
-        dp = (C.c_void_p * k)(*[o.data_ptr() if ok else None for o, ok in zip(outs, live)])
+        outs = self._outs(outs, caps, "item", "sizes")
+        dp = _dptrs(o if ok else None for o, ok in zip(outs, live))
         if k:
             self._check(self._lib.sfh_inflate_stream_batch_device(self._h, k, sp, n, kind, dp,
-                                                                  (C.c_uint64 * k)(*[m if ok else 0 for m, ok in zip(caps, live)]),
-                                                                  out_n, st, C.c_void_p(s)))
+                                                                  _u64s(m if ok else 0 for m, ok in zip(caps, live)), out_n, st, s))
         stats = [int(st[i]) if live[i] else first[i] for i in range(k)]
         return [outs[i][: out_n[i]] if stats[i] == 0 else outs[i][:0] for i in range(k)], stats
 
@@ -756,12 +743,10 @@ class Compressor:
         k = len(srcs)
         if k == 0:
             return [], []
-        sp = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a in srcs])
-        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in caps]
-        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
+        dsts = _host_dsts(caps)
         out_n = (C.c_uint64 * k)()
         st = (C.c_uint32 * k)()
-        self._check(self._lib.sfh_decompress_any_batch(self._h, k, sp, n, kind, dp, (C.c_uint64 * k)(*caps), want, out_n, st))
+        self._check(self._lib.sfh_decompress_any_batch(self._h, k, _ptrs(srcs), n, kind, _ptrs(dsts), _u64s(caps), want, out_n, st))
         return [dsts[i][: out_n[i]].tobytes() if st[i] == 0 else b"" for i in range(k)], [int(v) for v in st]
 
     def decompress_any_batch_tensors(self, streams, sizes=None, container="raw", outs=None, hip_stream=None):
@@ -769,8 +754,6 @@ class Compressor:
         decoded bytes (empty unless its status is 0).  sizes: the decoded sizes (None: gzip's ISIZE, read on the device; outs
         is then required and gives the capacities); outs: one uint8 CUDA tensor (16-byte aligned) of at least sizes[i] bytes
         per item (default: new ones).  Synchronises the stream."""
-        import torch
-
         streams = list(streams)
         kind = _container(container)
         k = len(streams)
@@ -784,53 +767,35 @@ class Compressor:
             want = [int(m) for m in sizes]
             if len(want) != k or any(m < 0 or m > (1 << 44) for m in want):
                 raise ValueError("sizes must hold one size in [0, 2^44] per stream")
-        for t in streams:
-            self._check_tensor(t)
-        dev = torch.device("cuda", self.device)
-        s = torch.cuda.current_stream(dev).cuda_stream if hip_stream is None else hip_stream
-        if outs is None:
-            outs = [torch.empty(max(m, 1), dtype=torch.uint8, device=dev) for m in want]
-        outs = list(outs)
-        if len(outs) != k or (sizes is not None and any(o.numel() < m for o, m in zip(outs, want))):
-            raise ValueError("outs must hold one tensor of at least sizes[i] bytes per item")
-        for t in outs:
-            self._check_tensor(t)
+        self._check_tensors(streams)
+        # (sizes=None: outs give the capacities, none of which is too small to ask the trailer)
+        outs = self._outs(outs, want if sizes is not None else [0] * k, "item", "sizes")
         if k == 0:
             return [], []
-        sp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in streams])
-        n = (C.c_uint64 * k)(*[t.numel() for t in streams])
-        dp = (C.c_void_p * k)(*[o.data_ptr() for o in outs])
-        caps = (C.c_uint64 * k)(*[o.numel() for o in outs])
         out_n = (C.c_uint64 * k)()
         st = (C.c_uint32 * k)()
-        self._check(self._lib.sfh_decompress_any_batch_device(self._h, k, sp, n, kind, dp, caps, (C.c_uint64 * k)(*want), out_n, st,
-                                                              C.c_void_p(s)))
+        self._check(self._lib.sfh_decompress_any_batch_device(
+            self._h, k, _dptrs(streams), _u64s(t.numel() for t in streams), kind, _dptrs(outs), _u64s(o.numel() for o in outs),
+            _u64s(want), out_n, st, self._stream(hip_stream)))
         return [outs[i][: out_n[i]] if st[i] == 0 else outs[i][:0] for i in range(k)], [int(v) for v in st]
 
     def recover_index_batch(self, streams, sizes, container="raw", hip_stream=None):
         """streams: 1-D uint8 CUDA tensors, sizes: their decoded sizes -> (index: one int64 CUDA tensor, last_batch_index()'s
         flat layout -- item i's segments + 1 offsets behind those of the items before it -- and a list of statuses: 0, or
         ITEM_NOT_INDEXABLE for an item that is not block-flushed every 32 KiB, whose entries are 0)."""
-        import torch
-
         streams = list(streams)
         kind = _container(container)
         want = [int(m) for m in sizes]
         k = len(streams)
         if len(want) != k or any(m < 0 or m > (1 << 44) for m in want):
             raise ValueError("sizes must hold one size in [0, 2^44] per stream")
-        for t in streams:
-            self._check_tensor(t)
-        dev = torch.device("cuda", self.device)
-        s = torch.cuda.current_stream(dev).cuda_stream if hip_stream is None else hip_stream
+        self._check_tensors(streams)
         entries = sum(max(1, -(-m // CHUNK_BYTES)) + 1 for m in want)
-        index = torch.zeros(max(entries, 1), dtype=torch.int64, device=dev)
+        index = self._new(max(entries, 1), "int64", zeros=True)
         st = (C.c_uint32 * max(k, 1))()
         if k:
-            sp = (C.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in streams])
-            n = (C.c_uint64 * k)(*[t.numel() for t in streams])
-            self._check(self._lib.sfh_recover_index_batch_device(self._h, k, sp, n, kind, (C.c_uint64 * k)(*want), index.data_ptr(),
-                                                                 st, C.c_void_p(s)))
+            self._check(self._lib.sfh_recover_index_batch_device(self._h, k, _dptrs(streams), _u64s(t.numel() for t in streams), kind,
+                                                                 _u64s(want), index.data_ptr(), st, self._stream(hip_stream)))
         return index[:entries], [int(st[i]) for i in range(k)]
 
     # ---- many independent streams, each decoded into its own buffer, in one call (sfh_decompress_batch*) ----
@@ -840,13 +805,10 @@ class Compressor:
         most 32768 (each stream one segment: pages from other tools).  An item whose status is not 0 comes back as b""."""
         srcs, n, dst_n, idx, sub, bb, kind = _batch_inflate_args(streams, sizes, index, subindex, block_bytes, container)
         k = len(srcs)
-        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in dst_n]
-        sp = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a in srcs])
-        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
+        dsts = _host_dsts(dst_n)
         st = np.zeros(max(k, 1), dtype=np.uint32)
-        self._check(self._lib.sfh_decompress_batch(
-            self._h, k, sp, n, idx.ctypes.data if idx is not None else None, sub.ctypes.data if sub is not None else None, dp,
-            (C.c_uint64 * k)(*dst_n), bb.ctypes.data if bb is not None else None, kind, st.ctypes.data))
+        self._check(self._lib.sfh_decompress_batch(self._h, k, _ptrs(srcs), n, _addr(idx), _addr(sub), _ptrs(dsts), _u64s(dst_n),
+                                                   _addr(bb), kind, st.ctypes.data))
         return [dsts[i][: dst_n[i]].tobytes() if st[i] == 0 else b"" for i in range(k)], [int(v) for v in st[:k]]
 
     def decompress_batch_tensors(self, streams, sizes, index=None, subindex=None, block_bytes=None, container="raw",
@@ -855,33 +817,18 @@ class Compressor:
         a host synchronisation.  index: int64 CUDA tensor, subindex: int32 CUDA tensor (last_batch_index()'s layout), or
         None; block_bytes: a host sequence.  outs: one uint8 tensor per item of at least sizes[i] bytes (default: new ones;
         each item's decoded bytes are outs[i][:sizes[i]]); status: an int32 tensor on the device, one DecompressStatus per item."""
-        import torch
-
         streams = list(streams)
-        for t in streams:
-            self._check_tensor(t)
+        self._check_tensors(streams)
         dst_n, bb, kind = _batch_lengths(len(streams), sizes, None if index is None else index.numel(),
                                          None if subindex is None else subindex.numel(), block_bytes, container)
         k = len(streams)
-        for t, dt in ((index, torch.int64), (subindex, torch.int32)):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
-                raise ValueError("index / subindex must be contiguous int64 / int32 CUDA tensors")
-        dev = torch.device("cuda", self.device)
-        if outs is None:
-            outs = [torch.empty(max(m, 1), dtype=torch.uint8, device=dev) for m in dst_n]
-        outs = list(outs)
-        if len(outs) != k or any(o.numel() < m for o, m in zip(outs, dst_n)):
-            raise ValueError("outs must hold one tensor of at least sizes[i] bytes per item")
-        for t in outs:
-            self._check_tensor(t)
-        status = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-        sp = (C.c_void_p * k)(*[t.data_ptr() for t in streams])
-        dp = (C.c_void_p * k)(*[o.data_ptr() for o in outs])
-        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        if not ((index is None or _device_array(index, "int64")) and (subindex is None or _device_array(subindex, "int32"))):
+            raise ValueError("index / subindex must be contiguous int64 / int32 CUDA tensors")
+        outs = self._outs(outs, dst_n, "item", "sizes")
+        status = self._new(max(k, 1), "int32")
         self._check(self._lib.sfh_decompress_batch_device_async(
-            self._h, k, sp, (C.c_uint64 * k)(*[t.numel() for t in streams]), index.data_ptr() if index is not None else None,
-            subindex.data_ptr() if subindex is not None else None, dp, (C.c_uint64 * k)(*dst_n),
-            bb.ctypes.data if bb is not None else None, kind, C.c_void_p(status.data_ptr()), C.c_void_p(s)))
+            self._h, k, _dptrs(streams), _u64s(t.numel() for t in streams), _addr(index), _addr(subindex), _dptrs(outs), _u64s(dst_n),
+            _addr(bb), kind, status.data_ptr(), self._stream(stream)))
         return outs, status[:k]
 
     # ---- random access: byte ranges of one indexed stream's output (sfh_decompress_range*) ----
@@ -896,18 +843,13 @@ class Compressor:
         output size and the ranges -> (list of bytes, None where a range's status is not 0; uint32 status array).  Of the
         stream only the ranges' decode spans travel to the device: from the start of the strip (block_bytes, required as in
         decompress) holding a range's first byte to the segment holding its last."""
-        src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).ravel()
+        src = _as_bytes(data)
         idx = np.ascontiguousarray(index, dtype=np.uint64).ravel()
         sub = None if subindex is None else np.ascontiguousarray(subindex, dtype=np.uint32).ravel()
         total_n, offs, lens, nseg = _range_lengths(total_n, offsets, lengths, idx.size, None if sub is None else sub.size, block_bytes)
-        k = len(offs)
-        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in lens]
-        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
-        st = np.zeros(max(k, 1), dtype=np.uint32)
-        self._check(self._lib.sfh_decompress_ranges(
-            self._h, src.ctypes.data if src.size else None, src.size, idx.ctypes.data, sub.ctypes.data if sub is not None else None,
-            nseg, total_n, int(block_bytes), k, (C.c_uint64 * k)(*offs), (C.c_uint64 * k)(*lens), dp, st.ctypes.data))
-        return [dsts[i][: lens[i]].tobytes() if st[i] == 0 else None for i in range(k)], st[:k]
+        return self._ranges_to_host(lens, lambda dp, st: self._lib.sfh_decompress_ranges(
+            self._h, _ptr(src), src.size, idx.ctypes.data, _addr(sub), nseg, total_n, int(block_bytes), len(offs), _u64s(offs),
+            _u64s(lens), dp, st))
 
     def decompress_ranges_tensors(self, stream, index, total_n, offsets, lengths, outs=None, subindex=None, hip_stream=None, *,
                                   block_bytes):
@@ -916,32 +858,19 @@ class Compressor:
         one) without a host synchronisation.  outs: one uint8 tensor (or view, any alignment: slices of one packed buffer will
         do) of at least lengths[i] bytes per range, not overlapping (default: new ones); range i's bytes are
         outs[i][:lengths[i]]; status: an int32 tensor on the device, one DecompressStatus per range."""
-        import torch
-
         self._check_tensor(stream)
-        for t, dt in ((index, torch.int64), (subindex, torch.int32)):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
-                raise ValueError("index / subindex must be contiguous int64 / int32 CUDA tensors")
+        if not ((index is None or _device_array(index, "int64")) and (subindex is None or _device_array(subindex, "int32"))):
+            raise ValueError("index / subindex must be contiguous int64 / int32 CUDA tensors")
         if index is None:
             raise ValueError("an index is required")
         total_n, offs, lens, nseg = _range_lengths(total_n, offsets, lengths, index.numel(),
                                                    None if subindex is None else subindex.numel(), block_bytes)
         k = len(offs)
-        dev = torch.device("cuda", self.device)
-        if outs is None:
-            outs = [torch.empty(max(m, 1), dtype=torch.uint8, device=dev) for m in lens]
-        outs = list(outs)
-        if len(outs) != k or any(o.numel() < m for o, m in zip(outs, lens)):
-            raise ValueError("outs must hold one tensor of at least lengths[i] bytes per range")
-        for t in outs:
-            self._check_tensor(t)
-        status = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
-        dp = (C.c_void_p * k)(*[o.data_ptr() for o in outs])
-        s = torch.cuda.current_stream(dev).cuda_stream if hip_stream is None else hip_stream
+        outs = self._outs(outs, lens, "range", "lengths")
+        status = self._new(max(k, 1), "int32")
         self._check(self._lib.sfh_decompress_ranges_device_async(
-            self._h, stream.data_ptr(), stream.numel(), index.data_ptr(), subindex.data_ptr() if subindex is not None else None,
-            nseg, total_n, int(block_bytes), k, (C.c_uint64 * k)(*offs), (C.c_uint64 * k)(*lens), dp,
-            C.c_void_p(status.data_ptr()), C.c_void_p(s)))
+            self._h, stream.data_ptr(), stream.numel(), index.data_ptr(), _addr(subindex), nseg, total_n, int(block_bytes), k,
+            _u64s(offs), _u64s(lens), _dptrs(outs), status.data_ptr(), self._stream(hip_stream)))
         return outs, status[:k]
 
     # ---- seekable gzip: files written with container="dictzip", read with nothing but their bytes (sfh_decompress_dz*) ----
@@ -969,13 +898,8 @@ class Compressor:
         return self._read_ranges(*_dz_range_args(data, offsets, lengths))
 
     def _read_ranges(self, src, offs, lens):
-        k = len(offs)
-        dsts = [np.empty(max(m, 1), dtype=np.uint8) for m in lens]
-        dp = (C.c_void_p * k)(*[d.ctypes.data for d in dsts])
-        st = np.zeros(max(k, 1), dtype=np.uint32)
-        self._check(self._lib.sfh_decompress_dz_ranges(self._h, src.ctypes.data, src.size, k, (C.c_uint64 * k)(*offs),
-                                                       (C.c_uint64 * k)(*lens), dp, st.ctypes.data))
-        return [dsts[i][: lens[i]].tobytes() if st[i] == 0 else None for i in range(k)], st[:k]
+        return self._ranges_to_host(lens, lambda dp, st: self._lib.sfh_decompress_dz_ranges(
+            self._h, src.ctypes.data, src.size, len(offs), _u64s(offs), _u64s(lens), dp, st))
 
     def inflate_ms(self):
         ms = (C.c_float * _capi.INFLATE_NSTAGES)()
@@ -984,32 +908,18 @@ class Compressor:
 
     def checksum_tensor(self, src, kind, stream=None):
         """kind "zlib" -> Adler-32, "gzip" -> CRC-32 of a 1-D uint8 tensor on this device (GPU kernels)."""
-        import torch
-
         self._check_tensor(src)
         out = C.c_uint32(0)
-        s = torch.cuda.current_stream(src.device).cuda_stream if stream is None else stream
-        n = src.numel()
-        self._check(self._lib.sfh_checksum_device(self._h, src.data_ptr() if n else None, n, _capi.CONTAINER[kind],
-                                                  C.byref(out), C.c_void_p(s)))
+        self._check(self._lib.sfh_checksum_device(self._h, src.data_ptr(), src.numel(), _capi.CONTAINER[kind], C.byref(out),
+                                                  self._stream(stream)))
         return out.value
-
-    def _check_tensor(self, t):
-        import torch
-
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous()):
-            raise ValueError("expected a contiguous 1-D uint8 CUDA tensor")
-        if t.device.index != self.device:
-            raise ValueError(f"tensor is on cuda:{t.device.index}, compressor on cuda:{self.device}")
 
     # ---- measurement / inspection ----
     def lds_order_check(self, op, blocks=256, iters=50):
         """sfh_lds_order_check: does the LDS execute a returning atomic's lanes in ascending order on this device (op 0:
         ds_wrxchg_rtn_b32, the chain efforts; op 1: ds_mskor_rtn_b32, effort "recent")? -> (mismatches, positions checked)"""
         bad, n = C.c_uint64(0), C.c_uint64(0)
-        rc = self._lib.sfh_lds_order_check(self._h, int(op), int(blocks), int(iters), C.byref(bad), C.byref(n))
-        if rc:
-            raise StarflateError(rc, self._lib.sfh_last_error(self._h).decode())
+        self._check(self._lib.sfh_lds_order_check(self._h, int(op), int(blocks), int(iters), C.byref(bad), C.byref(n)))
         return bad.value, n.value
 
     def set_profiling(self, on=True):
@@ -1069,14 +979,13 @@ def compress_multi(compressors, data, strategy="auto", final_stream=True, lazy=T
     """One process, several contexts (normally one per GPU): contiguous shards compressed concurrently, one stream
     out -- bit-identical to a single Compressor.compress call (sfh_compress_multi)."""
     L = _capi.lib()
-    src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    src = _as_bytes(data)
     cap = L.sfh_compress_bound(src.size, 0)
     dst = np.empty(cap, dtype=np.uint8)
     out_n = C.c_size_t(0)
     opt = _capi.make_options(strategy, final_stream, lazy, stored_fast_path, container, block_bytes)
     handles = (C.c_void_p * len(compressors))(*[c._h for c in compressors])
-    rc = L.sfh_compress_multi(handles, len(compressors), src.ctypes.data if src.size else None, src.size, dst.ctypes.data, cap,
-                              C.byref(out_n), C.byref(opt))
+    rc = L.sfh_compress_multi(handles, len(compressors), _ptr(src), src.size, dst.ctypes.data, cap, C.byref(out_n), C.byref(opt))
     if rc:
         raise StarflateError(rc, "; ".join(L.sfh_last_error(c._h).decode() for c in compressors))
     return dst[: out_n.value].tobytes()
@@ -1159,13 +1068,12 @@ def _range_args(index, total_n, offsets, lengths, subindex, block_bytes):
 def _batch_inflate_args(streams, sizes, index, subindex, block_bytes, container):
     """decompress_batch's host arguments, checked (_batch_lengths): (sources, src_n, dst_n, index, subindex, block_bytes,
     container) as the C-ABI takes them."""
-    srcs = [np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else np.ascontiguousarray(d, dtype=np.uint8).ravel()
-            for d in streams]
+    srcs = [_as_bytes(d) for d in streams]
     idx = None if index is None else np.ascontiguousarray(index, dtype=np.uint64).ravel()
     sub = None if subindex is None else np.ascontiguousarray(subindex, dtype=np.uint32).ravel()
     dst_n, bb, kind = _batch_lengths(len(srcs), sizes, None if idx is None else idx.size, None if sub is None else sub.size,
                                      block_bytes, container)
-    return srcs, (C.c_uint64 * len(srcs))(*[a.size for a in srcs]), dst_n, idx, sub, bb, kind
+    return srcs, _u64s(a.size for a in srcs), dst_n, idx, sub, bb, kind
 
 
 def _stream_batch_args(streams, sizes, container):
@@ -1173,8 +1081,7 @@ def _stream_batch_args(streams, sizes, container):
     None, container code)."""
     if isinstance(streams, (bytes, bytearray, memoryview, np.ndarray)):
         raise ValueError("streams: a sequence of bytes-like streams")
-    srcs = [np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else np.ascontiguousarray(d, dtype=np.uint8).ravel()
-            for d in streams]
+    srcs = [_as_bytes(d) for d in streams]
     if not isinstance(container, str) or container not in _capi.CONTAINER:
         raise ValueError(f"container must be one of {sorted(_capi.CONTAINER)}")
     caps = None
@@ -1184,7 +1091,7 @@ def _stream_batch_args(streams, sizes, container):
             raise ValueError(f"{len(srcs)} streams but {len(caps)} sizes")
         if any(m < 0 or m > (1 << 44) for m in caps):
             raise ValueError("sizes must lie in [0, 2^44]")
-    return srcs, (C.c_uint64 * len(srcs))(*[a.size for a in srcs]), caps, _capi.CONTAINER[container]
+    return srcs, _u64s(a.size for a in srcs), caps, _capi.CONTAINER[container]
 
 
 def _any_batch_args(streams, sizes, container):
@@ -1192,8 +1099,7 @@ def _any_batch_args(streams, sizes, container):
     takes it, capacities, container code).  sizes=None: gzip's ISIZE, which also gives the capacities here."""
     if isinstance(streams, (bytes, bytearray, memoryview, np.ndarray)):
         raise ValueError("streams: a sequence of bytes-like streams")
-    srcs = [np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else np.ascontiguousarray(d, dtype=np.uint8).ravel()
-            for d in streams]
+    srcs = [_as_bytes(d) for d in streams]
     if not isinstance(container, str) or container not in _capi.CONTAINER:
         raise ValueError(f"container must be one of {sorted(_capi.CONTAINER)}")
     kind = _capi.CONTAINER[container]
@@ -1210,25 +1116,34 @@ def _any_batch_args(streams, sizes, container):
         if any(m < 0 or m > (1 << 44) for m in caps):
             raise ValueError("sizes must lie in [0, 2^44]")
         want = caps
-    return srcs, (C.c_uint64 * k)(*[a.size for a in srcs]), (C.c_uint64 * k)(*want), caps, kind
+    return srcs, _u64s(a.size for a in srcs), _u64s(want), caps, kind
 
 
 _DEFAULT = {}
 
 
-def compress(data, device=0, **kw):
-    """bytes-like -> raw DEFLATE bytes, through the GPU (host buffers, PCIe inclusive)."""
+def _default(device):
+    """the module-level functions' context of that device, created at its first use"""
     c = _DEFAULT.get(device)
     if c is None:
         c = _DEFAULT[device] = Compressor(device)
+    return c
+
+
+def _raise_on_status(st):
+    if st:
+        raise StarflateError(st, f"DecompressStatus {st}")
+
+
+def compress(data, device=0, **kw):
+    """bytes-like -> raw DEFLATE bytes, through the GPU (host buffers, PCIe inclusive)."""
+    c = _default(device)
     return c.compress(data, **kw)
 
 
 def compress_batch(items, device=0, **kw):
     """A sequence of bytes-like items -> one stream per item, all in one call (Compressor.compress_batch)."""
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     return c.compress_batch(items, **kw)
 
 
@@ -1260,24 +1175,18 @@ def decompress(data, out_n=None, container="raw", device=0):
     """One stream given alone -> bytes, on the GPU (Compressor.decompress_any): the segment index is recovered from the
     stream's flush markers.  A status other than Success raises StarflateError; so does a stream that is not block-flushed
     every 32 KiB (code -8): such a stream is the serial decoder's."""
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     out, st = c.decompress_any(data, out_n, container)
-    if st:
-        raise StarflateError(st, f"DecompressStatus {st}")
+    _raise_on_status(st)
     return out
 
 
 def decompress_stream(data, container="raw", out_n=None, device=0):
     """One raw / zlib / gzip stream with no index and no flush points -> bytes, on the GPU (Compressor.decompress_stream).
     A status other than Success raises StarflateError."""
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     out, st = c.decompress_stream(data, out_n, container)
-    if st:
-        raise StarflateError(st, f"DecompressStatus {st}")
+    _raise_on_status(st)
     return out
 
 
@@ -1285,9 +1194,7 @@ def decompress_batch(streams, sizes, device=0, **kw):
     """Streams and their decoded sizes -> (list of bytes, list of statuses), all in one call (Compressor.decompress_batch).
     The arguments are checked before a device is touched."""
     _batch_inflate_args(streams, sizes, kw.get("index"), kw.get("subindex"), kw.get("block_bytes"), kw.get("container", "raw"))
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     return c.decompress_batch(streams, sizes, **kw)
 
 
@@ -1295,9 +1202,7 @@ def decompress_stream_batch(streams, sizes=None, container="raw", device=0):
     """Raw / zlib / gzip streams with no index and no flush points -> (list of bytes, list of statuses), all in one call
     (Compressor.decompress_stream_batch).  The arguments are checked before a device is touched."""
     _stream_batch_args(streams, sizes, container)
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     return c.decompress_stream_batch(streams, sizes, container)
 
 
@@ -1309,9 +1214,7 @@ def decompress_any_batch(streams, sizes=None, container="raw", device=0, fallbac
     device is touched."""
     _, _, _, caps, _ = _any_batch_args(streams, sizes, container)
     streams = list(streams)
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     outs, sts = c.decompress_any_batch(streams, sizes, container)
     rest = [i for i, st in enumerate(sts) if st == ITEM_NOT_INDEXABLE] if fallback else []
     if rest:
@@ -1325,12 +1228,9 @@ def decompress_range(data, index, total_n, offset, length, subindex=None, *, blo
     """Output bytes [offset, offset + length) of an indexed stream -> bytes (Compressor.decompress_range).  The arguments are
     checked before a device is touched; a status other than Success raises StarflateError."""
     _range_args(index, total_n, [offset], [length], subindex, block_bytes)
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     out, st = c.decompress_range(data, index, total_n, offset, length, subindex, block_bytes=block_bytes)
-    if st:
-        raise StarflateError(st, f"DecompressStatus {st}")
+    _raise_on_status(st)
     return out
 
 
@@ -1338,9 +1238,7 @@ def decompress_ranges(data, index, total_n, offsets, lengths, subindex=None, *, 
     """Many ranges of one indexed stream -> (list of bytes or None, status array), all in one call
     (Compressor.decompress_ranges).  The arguments are checked before a device is touched."""
     _range_args(index, total_n, offsets, lengths, subindex, block_bytes)
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     return c.decompress_ranges(data, index, total_n, offsets, lengths, subindex, block_bytes=block_bytes)
 
 
@@ -1352,7 +1250,7 @@ def dictzip_index(data):
     src = _as_bytes(data)
     index = np.zeros(_capi.DZ_MAX_CHUNKS + 1, dtype=np.uint64)
     info = _capi.DzInfo()
-    rc = _capi.lib().sfh_dz_read_index(src.ctypes.data if src.size else None, src.size, C.byref(info), index.ctypes.data, index.size)
+    rc = _capi.lib().sfh_dz_read_index(_ptr(src), src.size, C.byref(info), index.ctypes.data, index.size)
     if rc:
         raise StarflateError(rc, "no dictzip table of 32 KiB chunks in the gzip header")
     if info.status:
@@ -1365,17 +1263,14 @@ def decompress_dictzip(data, device=0):
     whose table the indexed decoder cannot use (dictzip's own default chunk length, or no table at all) is decoded by
     decompress_stream(data, container="gzip") instead, as decompress_any_batch(fallback=True) does for its items.  A status
     other than Success raises StarflateError."""
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     try:
         out, st = c.decompress_dictzip(data)
     except StarflateError as e:
         if e.code != _capi.E_NOT_INDEXABLE:
             raise
         return decompress_stream(data, container="gzip", device=device)
-    if st:
-        raise StarflateError(st, f"DecompressStatus {st}")
+    _raise_on_status(st)
     return out
 
 
@@ -1391,12 +1286,12 @@ def bgzf_index(data):
     src = _as_bytes(data)
     info = _capi.BgzfInfo()
     L = _capi.lib()
-    rc = L.sfh_bgzf_read_index(src.ctypes.data if src.size else None, src.size, C.byref(info), None, None, 0)  # the count
+    rc = L.sfh_bgzf_read_index(_ptr(src), src.size, C.byref(info), None, None, 0)  # the count
     if info.status:
         raise StarflateError(info.status, f"BGZF members: DecompressStatus {info.status}")
     moff = np.zeros(info.members + 1, dtype=np.uint64)
     ooff = np.zeros(info.members + 1, dtype=np.uint64)
-    rc = L.sfh_bgzf_read_index(src.ctypes.data if src.size else None, src.size, C.byref(info), moff.ctypes.data, ooff.ctypes.data, moff.size)
+    rc = L.sfh_bgzf_read_index(_ptr(src), src.size, C.byref(info), moff.ctypes.data, ooff.ctypes.data, moff.size)
     if rc:
         raise StarflateError(rc, "sfh_bgzf_read_index")
     return moff, ooff, _bgzf_info_dict(info)
@@ -1427,8 +1322,7 @@ def _voffset_call(fn, member_off, out_off, values):
         raise ValueError("member_off / out_off must hold members + 1 entries")
     src = np.ascontiguousarray(values, dtype=np.uint64).ravel()
     out = np.zeros(src.size, dtype=np.uint64)
-    rc = fn(moff.ctypes.data, ooff.ctypes.data, moff.size - 1, src.size, src.ctypes.data if src.size else None,
-            out.ctypes.data if src.size else None)
+    rc = fn(moff.ctypes.data, ooff.ctypes.data, moff.size - 1, src.size, _ptr(src), _ptr(out))
     if rc:
         raise StarflateError(rc, fn.__name__)
     return out
@@ -1449,28 +1343,21 @@ def bgzf_offsets_to_voffsets(member_off, out_off, offsets):
 
 def read_bgzf_ranges(bgzf, offsets, lengths, index=None, device=0):
     """Byte ranges of what a BGZF file holds -> (list of bytes or None, status array) (Compressor.read_bgzf_ranges)."""
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     return c.read_bgzf_ranges(bgzf, offsets, lengths, index=index)
 
 
 def compress_bgzf(data, device=0, **options):
     """bytes-like -> a BGZF file on the GPU (Compressor.compress_bgzf)."""
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     return c.compress_bgzf(data, **options)
 
 
 def decompress_bgzf(data, device=0):
     """A BGZF file -> bytes, on the GPU (Compressor.decompress_bgzf).  A status other than Success raises StarflateError."""
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     out, st = c.decompress_bgzf(data)
-    if st:
-        raise StarflateError(st, f"DecompressStatus {st}")
+    _raise_on_status(st)
     return out
 
 
@@ -1494,7 +1381,7 @@ def _zip_info_dict(info):
 def zip_bound(sizes, name_lens):
     """sfh_zip_bound: the capacity compress_zip needs for items of these sizes and name lengths (bytes)"""
     k = len(sizes)
-    return _capi.lib().sfh_zip_bound(k, (C.c_uint64 * k)(*[int(v) for v in sizes]), (C.c_uint32 * k)(*[int(v) for v in name_lens]))
+    return _capi.lib().sfh_zip_bound(k, _u64s(int(v) for v in sizes), (C.c_uint32 * k)(*[int(v) for v in name_lens]))
 
 
 def zip_index(data):
@@ -1502,7 +1389,7 @@ def zip_index(data):
     src = _as_bytes(data)
     L = _capi.lib()
     info = _capi.ZipInfo()
-    rc = L.sfh_zip_read_index(src.ctypes.data if src.size else None, src.size, C.byref(info), None, 0)
+    rc = L.sfh_zip_read_index(_ptr(src), src.size, C.byref(info), None, 0)
     ents = np.zeros(info.entries, ZIP_ENTRY_DTYPE)
     if rc == -2:
         rc = L.sfh_zip_read_index(src.ctypes.data, src.size, C.byref(info), C.c_void_p(ents.ctypes.data), ents.size)
@@ -1520,22 +1407,14 @@ def zip_names(data, entries):
 
 def compress_zip(items, device=0, **options):
     """{name: bytes} or [(name, bytes)] -> a ZIP archive on the GPU (Compressor.compress_zip)."""
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     return c.compress_zip(items, **options)
 
 
 def decompress_zip(data, names=None, device=0):
     """A ZIP archive -> ({name: bytes}, statuses) on the GPU (Compressor.decompress_zip)."""
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     return c.decompress_zip(data, names=names)
-
-
-def _as_bytes(data):
-    return np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).ravel()
 
 
 def _dz_range_args(data, offsets, lengths):
@@ -1550,7 +1429,5 @@ def read_ranges(data, offsets, lengths, device=0):
     """Byte ranges of what a dictzip file holds, given nothing but its bytes -> (list of bytes or None, status array)
     (Compressor.read_ranges).  The header and the ranges are checked before a device is touched."""
     args = _dz_range_args(data, offsets, lengths)
-    c = _DEFAULT.get(device)
-    if c is None:
-        c = _DEFAULT[device] = Compressor(device)
+    c = _default(device)
     return c._read_ranges(*args)

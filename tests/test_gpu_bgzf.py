@@ -98,6 +98,17 @@ def test_host_buffers_write_the_same_file(comp, made):
     assert starflate_amd.compress_bgzf(made["text", 32769, "chain"][0], effort="best") == made["text", 32769, "chain"][1]
 
 
+def test_index_method_is_the_module_function(comp, made):
+    """Compressor.bgzf_index: the host walk of starflate_amd.bgzf_index, on the smallest files"""
+    for n in (0, 1, 32769):
+        blob = made["text", n, "default"][1]
+        (gm, go, ginfo), (wm, wo, winfo) = comp.bgzf_index(blob), starflate_amd.bgzf_index(blob)
+        assert np.array_equal(gm, wm) and np.array_equal(go, wo) and ginfo == winfo, n
+        moff, ooff, widest, eof = BZ.walk(blob)
+        assert list(gm) == list(moff) and list(go) == list(ooff), n
+        assert ginfo == {"total_n": n, "members": len(moff) - 1, "max_isize": widest, "has_eof": bool(eof)}, n
+
+
 def test_async_call_on_a_callers_stream(comp, made):
     data, blob = made["text", 3 * 32768 + 5, "default"]
     stream = torch.cuda.Stream()

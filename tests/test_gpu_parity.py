@@ -443,6 +443,25 @@ def test_container_wrappers(compressor, starfleet, container):
         compressor.compress(b"abc", container=container, final_stream=False)
 
 
+def test_wrapper_bytes_around_a_raw_stream(compressor):
+    """wrapper_bytes: header and trailer around the raw stream give the container stream the kernels write, which zlib's
+    wrapper-checking inflate accepts; the smallest inputs alone and as one batch"""
+    from starflate_amd import wrapper_bytes
+
+    items = [synth.gen_text(n, seed=n + 1).tobytes() if n else b"" for n in (0, 1, 32769)]
+    raws = [compressor.compress(d) for d in items]
+    assert compressor.compress_batch(items) == raws
+    for kind, checksum, wbits in (("zlib", zlib.adler32, 15), ("gzip", zlib.crc32, 31)):
+        wrapped = []
+        for d, raw in zip(items, raws):
+            head, tail = wrapper_bytes(kind, checksum(d), len(d))
+            wrapped.append(head + raw + tail)
+            assert wrapped[-1] == compressor.compress(d, container=kind), (kind, len(d))
+            assert zlib.decompress(wrapped[-1], wbits) == d, (kind, len(d))
+        assert compressor.compress_batch(items, container=kind) == wrapped, kind
+    assert wrapper_bytes("raw", 0, 5) == (b"", b"")
+
+
 def test_checksum_kernels_match_zlib(compressor):
     """sfh_checksum_device against zlib.crc32 / zlib.adler32 (and the oracle's bit-serial definitions) on
     empty, sub-chunk, ragged, all-0xFF (Adler worst case) and > 1024-chunk inputs; combine rules."""

@@ -44,6 +44,14 @@ def test_bound_arithmetic():
     assert lib.sfh_zip_bound(1, None, None) == 0
 
 
+def test_bound_on_the_class_is_the_function():
+    """Compressor.zip_bound (a static method: no context) on the smallest items and on a batch of them"""
+    lib = _capi.lib()
+    for sizes, lens in (([0], [1]), ([1], [1]), ([32769], [3]), ([0, 1, 32769], [1, 2, 3])):
+        want = sum(30 + k + lib.sfh_compress_bound(n, 0) for n, k in zip(sizes, lens)) + sum(46 + k for k in lens) + 22 + 76
+        assert starflate_amd.Compressor.zip_bound(sizes, lens) == want == starflate_amd.zip_bound(sizes, lens)
+
+
 def test_host_walk_through_the_library():
     for name, blob in Z.foreign_archives().items():
         info, ents = starflate_amd.zip_index(blob)
