@@ -231,11 +231,30 @@ __device__ __forceinline__ uint32_t entry_rel(uint32_t v) {
 // BATCH (sfh_compress_batch*): the strip's bytes, size and first chunk come from the launch batch's strip table (src,
 // n_total and strip_bytes are unused); the rest is the same kernel.  The choice is made in the prologue, at compile
 // time: the single call's instantiations are the code they were.
+// The COLD ARGUMENTS: what only a chunk's end, the empty input and the diagnostic build use.  As parameters of their own each
+// holds two scalar registers through every round; as the kernel's FIRST parameter the block lies at the start of the kernarg
+// segment, and the code that needs a member loads it from there, with a scalar load, where it needs it (k1_cold below).
+struct K1Cold {
+  uint32_t* nitems_out;
+  uint32_t* ntok_out;
+  uint32_t* hist_out;
+  uint64_t* stamps;
+};
+static_assert(sizeof(K1Cold) == 32 && alignof(K1Cold) == 8, "k1_cold(): the block is the kernarg segment's first 32 bytes");
+using K1ColdPtr = const __attribute__((address_space(4))) K1Cold*;
+// (pinned: the compiler hoists loads from the kernarg segment to the kernel's entry otherwise, which is what this is here to undo)
+__device__ __forceinline__ K1ColdPtr k1_cold() {
+  K1ColdPtr p = (K1ColdPtr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
 template <bool STAMPS, bool DEPTH2, bool NEAR, bool STRIDE2, bool LONG, bool CHAIN = false, bool RECENT = false, bool BATCH = false>
 __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREADS / 256) void k_lz77(
-    const uint8_t* __restrict__ src, uint64_t n_total, uint32_t strip_bytes, uint16_t* __restrict__ items,
-    uint32_t* __restrict__ nitems_out, uint32_t* __restrict__ ntok_out, uint32_t* __restrict__ hist_out,
-    uint32_t* __restrict__ rtok_out, uint32_t lazy, uint32_t fast_skip, uint64_t* __restrict__ stamps,
+    // LOAD-BEARING POSITION: K1Cold must stay the FIRST parameter -- k1_cold() reads it at offset 0 of the kernarg segment, by
+    // no name; behind any other parameter the chunk end would write through whatever lies there (launch_lz77 passes it first)
+    [[maybe_unused]] K1Cold cold_args, const uint8_t* __restrict__ src, uint64_t n_total,
+    uint32_t strip_bytes, uint16_t* __restrict__ items, uint32_t* __restrict__ rtok_out, uint32_t lazy, uint32_t fast_skip,
     uint32_t chain_depth, const BatchStrip* __restrict__ strips) {
   static_assert(!CHAIN || (!STRIDE2 && !LONG && DEPTH2 && NEAR), "chains: every position searched, no step tables");
   static_assert(!RECENT || (!LONG && !CHAIN && DEPTH2 && NEAR), "recent: the step tables' search patterns (stride 2 or every position)");
@@ -302,6 +321,9 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
   auto load4 = [&](uint32_t pos) -> uint32_t {
     if (pos + 4 <= n) return *reinterpret_cast<const uint32_t*>(sp + pos);
     // @phase +tail trips=0 note=the strip's last bytes, byte by byte
+    // (from an opaque copy of the position: what this path derives from it and from n -- end tests, byte addresses -- is
+    // hoisted out of the round loop otherwise, ten scalar registers that spill for a path a strip takes once)
+    asm volatile("" : "+v"(pos));
     uint32_t w = 0;
     for (uint32_t b = 0; pos + b < n; ++b) w |= (uint32_t)sp[pos + b] << (8 * b);
     return w;
@@ -385,6 +407,10 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
     {
       uint4* s4 = reinterpret_cast<uint4*>(smem + L_DATA);
       const bool reload = lds_stale;  // (uniform)
+      // (the rare branches -- EARLY: the strip's first round and the reload -- work from an opaque copy of t and, the reload, of
+      // the round's position: their addresses and lane tests are hoisted out of the round loop otherwise, into registers that spill)
+      uint32_t tr = t;
+      asm volatile("" : "+v"(tr));
       const bool placed = EARLY && staged;  // (uniform) the previous round has done it all but the prefetch (never ahead of a reload)
       if (placed) {
       } else if (reload) {
@@ -398,31 +424,29 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         constexpr uint32_t kReach = 320, kRoundUnits = (kRound + kLook) / 16;
         static_assert(kReach >= 258 + kCap + 32 && (kSkipSpan + kReach) / 16 < K1_THREADS - 1 && kRoundUnits < K1_THREADS - 1, "reload: two units per thread, the last thread a third");
         const uint32_t wunits = (stale_span + kReach) / 16;
-        const uint8_t* const wp = sp + (rb - kWindow);
         // (... and the window's LAST bytes: the byte in front of the round's first position is looked at whenever a match
         // starts there -- the odd neighbour's byte check of a near candidate, the run test of the wave-wide extension)
-        // (EARLY: from an opaque copy of t -- with the stage this short the addresses of this rare path are hoisted out of the
-        // round loop otherwise, into registers that spill)
-        uint32_t tr = t;
-        if constexpr (EARLY) asm volatile("" : "+v"(tr));
-        if (rb + kRound + kLook <= n) {
+        uint32_t rbr = rb;
+        asm volatile("" : "+s"(rbr));
+        const uint8_t* const wp = sp + (rbr - kWindow);
+        if (rbr + kRound + kLook <= n) {
           if (tr < wunits) s4[tr] = reinterpret_cast<const uint4*>(wp)[tr];
           if (tr < kRoundUnits) s4[kWindow / 16 + tr] = reinterpret_cast<const uint4*>(wp)[kWindow / 16 + tr];
           if (tr == K1_THREADS - 1) s4[kWindow / 16 - 1] = reinterpret_cast<const uint4*>(wp)[kWindow / 16 - 1];
         } else {  // the strip ends inside: word by word, zeros beyond the end
-          for (uint32_t i = tr; i < 4 * wunits; i += K1_THREADS) s_data[i] = load4(rb - kWindow + 4 * i);
-          for (uint32_t i = tr; i < 4 * kRoundUnits; i += K1_THREADS) s_data[kWindow / 4 + i] = load4(rb + 4 * i);
-          if (tr == K1_THREADS - 1) s_data[kWindow / 4 - 1] = load4(rb - 4);
+          for (uint32_t i = tr; i < 4 * wunits; i += K1_THREADS) s_data[i] = load4(rbr - kWindow + 4 * i);
+          for (uint32_t i = tr; i < 4 * kRoundUnits; i += K1_THREADS) s_data[kWindow / 4 + i] = load4(rbr + 4 * i);
+          if (tr == K1_THREADS - 1) s_data[kWindow / 4 - 1] = load4(rbr - 4);
         }
         lds_stale = false;
       } else {
-        const uint4 c0 = s4[kOff + t], c1 = s4[kOff + K1_THREADS + t];
+        const uint4 c0 = s4[kOff + tr], c1 = s4[kOff + K1_THREADS + tr];
         uint4 c2 = make_uint4(0, 0, 0, 0);
-        if (t < kUnits - 2 * K1_THREADS) c2 = s4[kOff + 2 * K1_THREADS + t];
+        if (tr < kUnits - 2 * K1_THREADS) c2 = s4[kOff + 2 * K1_THREADS + tr];
         __syncthreads();  // every read of the old window (this shift, the previous round's emit) precedes the writes
-        s4[t] = c0;
-        s4[K1_THREADS + t] = c1;
-        if (t < kUnits - 2 * K1_THREADS) s4[2 * K1_THREADS + t] = c2;
+        s4[tr] = c0;
+        s4[K1_THREADS + tr] = c1;
+        if (tr < kUnits - 2 * K1_THREADS) s4[2 * K1_THREADS + tr] = c2;
       }
       if (!reload && !placed) *reinterpret_cast<uint2*>(&s_data[(kWindow + kLook) / 4 + 2 * t]) = make_uint2(pre_lo, pre_hi);
       // (RECENT asks for them behind the match phase, whose serial pass wants the registers: parse and emit hide the latency)
@@ -449,7 +473,9 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         // behind a chunk that took the stored fast path: kSkipProbe positions are searched, the rest of the span has no match
         static_assert(kSkipProbe % STEP == 0 && kSkipProbe < kSkipSpan && kSkipSpan == kRound, "short probe: whole steps of the chunk's first round");
         nsteps = nsteps < kSkipProbe / STEP ? nsteps : kSkipProbe / STEP;
-        for (uint32_t idx = kSkipProbe / 8 + t; idx < kRound / 8; idx += K1_THREADS) s_len4[idx] = 0;  // (the steps that run write below this)
+        uint32_t tp = t;  // (opaque: a rare path's lane test does not belong in the round loop's registers)
+        asm volatile("" : "+v"(tp));
+        for (uint32_t idx = kSkipProbe / 8 + tp; idx < kRound / 8; idx += K1_THREADS) s_len4[idx] = 0;  // (the steps that run write below this)
       }
       const uint32_t K = kWindow + ebase * STEP - rb;  // LDS byte address of a coded position = entry_pos(code) + K (mod 2^32)
       // The CU's two workgroups are in different phases most of the time.  The match phase is the long one and the one
@@ -783,7 +809,11 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         // after that step's insertions, the winner, its extension, the results.  The half that did the first part
         // inserts the step: its position and, with STRIDE2, the odd position behind it (whose bytes it has in registers
         // anyway).  Every thread is busy in every interval; a search costs one thread two.
-        const uint32_t grp = wave >> 3;                   // (uniform) this wave's half
+        // (from an opaque copy of the wave's number: hoisted out of the round loop, "second half" is a 64-bit mask that spills
+        // and comes back over two lane reads in front of the pair loop; made here it is one scalar compare)
+        uint32_t wv = wave;
+        asm volatile("" : "+s"(wv));
+        const uint32_t grp = wv >> 3;                     // (uniform) this wave's half
         const uint32_t tp = t & 511u;                     // index in the half
         const uint32_t ps = STRIDE2 ? 2 * tp : tp;        // the thread's searched position within a step
         const uint32_t to_rend = kRegion - (ps & (kRegion - 1));  // ... and how far its parse region's end is
@@ -1034,7 +1064,12 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         // @phase match.tail trips=1
         // STRIDE2: the last position of the last step that ran is odd and has no successor in its step: no match.  Its length
         // lives in the low half of the byte behind the step's (nobody wrote it in this round; after all steps it is the pad)
-        if (STRIDE2 && t == 0 && nsteps < kRound / STEP) smem[L_LEN4 + nsteps * (STEP / 2)] = 0;
+        // (a strip's last round only: the uniform test first, the lane test from an opaque copy of t -- not a mask kept through the rounds)
+        if (STRIDE2 && nsteps < kRound / STEP) {
+          uint32_t t0 = t;
+          asm volatile("" : "+v"(t0));
+          if (t0 == 0) smem[L_LEN4 + nsteps * (STEP / 2)] = 0;
+        }
       }
       // @phase parse.begin trips=1 note=barrier, staged-distance load
       __builtin_amdgcn_s_setprio(1);  // the parse: behind the other workgroup's match, ahead of its emit
@@ -1097,7 +1132,11 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
       uint32_t c0 = 0, c1 = 0, k0 = 0, k1 = 0;         // a byte per position: 4-bit length (0..13) | 0x80 where T says take
       // (uniform per wave) behind a chunk that took the stored fast path only the first kSkipProbe positions of the span were
       // searched: the waves behind them have nothing to parse -- every position a literal
-      const bool lit_wave = short_probe && rc == 0 && wave >= kSkipProbe / kRegion;
+      // (wp_, lz: opaque copies of the wave's number and of `lazy` -- what the take pass derives from them is made here, in
+      // scalar instructions, and not kept through the rounds in registers that spill: five lane reads per round before)
+      uint32_t wp_ = wave, lz = lazy;
+      asm volatile("" : "+s"(wp_), "+s"(lz));
+      const bool lit_wave = short_probe && rc == 0 && wp_ >= kSkipProbe / kRegion;
       if (!lit_wave) {
         // lazy deferral looks up to `lazy` positions ahead, inside the region and the input
         uint64_t W;
@@ -1127,7 +1166,7 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         c1 = __builtin_amdgcn_perm(lo4, le, 0x07030602u);                      // positions 4..7
         const uint32_t c2 = __builtin_amdgcn_perm(ho4, he, 0x05010400u);       // positions 8..11
         // uniform: which look-aheads count (lazy = 0..3)
-        const uint32_t m1 = lazy >= 1 ? 0x80808080u : 0u, m2 = lazy >= 2 ? 0x80808080u : 0u, m3 = lazy >= 3 ? 0x80808080u : 0u;
+        const uint32_t m1 = lz >= 1 ? 0x80808080u : 0u, m2 = lz >= 2 ? 0x80808080u : 0u, m3 = lz >= 3 ? 0x80808080u : 0u;
         auto take4 = [&](uint32_t cur, uint32_t nx) {  // cur: four positions, nx: the four behind them
           const uint32_t a1 = __builtin_amdgcn_alignbyte(nx, cur, 1), a2 = __builtin_amdgcn_alignbyte(nx, cur, 2),
                          a3 = __builtin_amdgcn_alignbyte(nx, cur, 3);
@@ -1375,7 +1414,9 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
           s2[2 * kRound / 8 + t] = sh_2;
           s2[3 * kRound / 8 + t] = B_early;
           // (the look-ahead, by the four threads whose prefetched bytes land on it: their own read, then their own write)
-          if (t >= K1_THREADS - kLook / 8) s2[kWindow / 8 + t - (K1_THREADS - kLook / 8)] = s2[(kWindow + kRound) / 8 + t - (K1_THREADS - kLook / 8)];
+          uint32_t tq = t;  // (opaque: the test of four threads is made here, not kept as a mask that spills)
+          asm volatile("" : "+v"(tq));
+          if (tq >= K1_THREADS - kLook / 8) s2[kWindow / 8 + tq - (K1_THREADS - kLook / 8)] = s2[(kWindow + kRound) / 8 + tq - (K1_THREADS - kLook / 8)];
           *reinterpret_cast<uint2*>(&s_data[(kWindow + kLook) / 4 + 2 * t]) = make_uint2(pre_lo, pre_hi);
           age(rb + kRound);  // (the next round's position; K of this round is not used again)
           staged = true;
@@ -1390,8 +1431,14 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
         // Round 6, STORED BY THE PROBE (specification: probe_span_is_noise, fast_skip == 2: the block type is ours to choose):
         // a full chunk whose probe span's BYTES are as good as uniform -- their entropy, the plan's fixed point, within
         // kStoreMargin bytes of the span -- has no tokens at all, which k_plan stores; its other 24 KiB are never fetched.
-        const uint32_t clen = (n - cstart) < kChunk ? (n - cstart) : kChunk;  // the chunk's bytes
-        const uint2 B = EARLY ? B_early : *reinterpret_cast<const uint2*>(&s_bytes[kWindow + 8 * t]);  // (pb = 8 t)
+        // Everything here works from OPAQUE copies of the thread index and the chunk's position (tc, lc, cs): thread-constant
+        // lane tests and addresses of this block are hoisted out of the round loop otherwise -- nine 64-bit lane masks and a
+        // dozen scalars, all spilled, for code the bench text never runs ("register budget").
+        uint32_t tc = t, cs = cstart;
+        asm volatile("" : "+v"(tc), "+s"(cs));
+        const uint32_t lc = tc & 63u;
+        const uint32_t clen = (n - cs) < kChunk ? (n - cs) : kChunk;  // the chunk's bytes
+        const uint2 B = EARLY ? B_early : *reinterpret_cast<const uint2*>(&s_bytes[kWindow + 8 * tc]);  // (pb = 8 t)
         bool pstore = false;  // (uniform)
         if (clen == kChunk) {
           // The byte counts.  On the histogram itself a wave's 64 random bytes pile up on the LDS banks (one atomic
@@ -1402,16 +1449,16 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
           static_assert(256 * 32 * 4 <= kWindow && kWindow / 16 == 2 * K1_THREADS, "the copies fill the window");
           static_assert(kRoundsPerChunk == 4, "the fast path's loads");
           uint4* const z4 = reinterpret_cast<uint4*>(smem + L_DATA);
-          z4[t] = make_uint4(0, 0, 0, 0);
-          z4[K1_THREADS + t] = make_uint4(0, 0, 0, 0);
+          z4[tc] = make_uint4(0, 0, 0, 0);
+          z4[K1_THREADS + tc] = make_uint4(0, 0, 0, 0);
           __syncthreads();
-          uint32_t* const rep = s_data + (lane & 31u);
+          uint32_t* const rep = s_data + (lc & 31u);
           auto count8 = [&](uint32_t lo, uint32_t hi) {
 #pragma unroll
             for (uint32_t j = 0; j < 8; ++j) atomicAdd(&rep[(((j < 4 ? lo : hi) >> (8 * (j & 3))) & 0xFFu) * 32u], 1u);
           };
           auto fold = [&]() -> uint32_t {
-            const uint4 p = z4[2 * t], q = z4[2 * t + 1];  // thread t: copies 8 (t mod 4) .. + 8 of byte value t / 4
+            const uint4 p = z4[2 * tc], q = z4[2 * tc + 1];  // thread t: copies 8 (t mod 4) .. + 8 of byte value t / 4
             uint32_t sum = (p.x + p.y) + (p.z + p.w) + (q.x + q.y) + (q.z + q.w);
             sum += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sum, 0xB1 /* quad_perm:[1,0,3,2] */, 0xF, 0xF, true);
             sum += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sum, 0x4E /* quad_perm:[2,3,0,1] */, 0xF, 0xF, true);
@@ -1421,11 +1468,11 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
           __syncthreads();
           if (fast_skip > 1) {
             const uint32_t f = fold();
-            uint32_t e = ((t & 3u) == 0 && f) ? f * (est_log2(kSkipSpan) - est_log2(f)) : 0u;
+            uint32_t e = ((tc & 3u) == 0 && f) ? f * (est_log2(kSkipSpan) - est_log2(f)) : 0u;
             e = wave_sum(e);
-            if (lane == 0) s_wtot[wave] = e;  // (its last readers are behind two barriers)
+            if (lc == 0) s_wtot[wave] = e;  // (its last readers are behind two barriers)
             __syncthreads();
-            const uint32_t ent = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_sum(lane < K1_WAVES ? s_wtot[lane] : 0u));
+            const uint32_t ent = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_sum(lc < K1_WAVES ? s_wtot[lc] : 0u));
             pstore = ((ent >> 8) + 7) / 8 + kStoreMargin >= kSkipSpan;
           }
           if (!pstore) {
@@ -1434,32 +1481,32 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
             // rest comes in two loads; the last kLook bytes of the last span belong to the next chunk -- or to nobody
             uint2 w[kRoundsPerChunk - 1];
             w[0] = make_uint2(pre_lo, pre_hi);
-            w[1] = *reinterpret_cast<const uint2*>(sp + cstart + 2 * kRound + kLook + 8 * t);
+            w[1] = *reinterpret_cast<const uint2*>(sp + cs + 2 * kRound + kLook + 8 * tc);
             w[2] = make_uint2(0, 0);
-            const bool tail = 8 * t + kLook < kRound;
-            if (tail) w[2] = *reinterpret_cast<const uint2*>(sp + cstart + 3 * kRound + kLook + 8 * t);
-            const uint32_t look = t < kLook / 4 ? s_data[(kWindow + kRound) / 4 + t] : 0u;
+            const bool tail = 8 * tc + kLook < kRound;
+            if (tail) w[2] = *reinterpret_cast<const uint2*>(sp + cs + 3 * kRound + kLook + 8 * tc);
+            const uint32_t look = tc < kLook / 4 ? s_data[(kWindow + kRound) / 4 + tc] : 0u;
             count8(w[0].x, w[0].y);
             count8(w[1].x, w[1].y);
             if (tail) count8(w[2].x, w[2].y);
-            if (t < kLook / 4) {
+            if (tc < kLook / 4) {
 #pragma unroll
               for (uint32_t j = 0; j < 4; ++j) atomicAdd(&rep[((look >> (8 * j)) & 0xFFu) * 32u], 1u);
             }
             __syncthreads();
             const uint32_t sum = fold();
-            if ((t & 3u) == 0) s_hist[t >> 2] = sum;  // (this chunk has counted nothing else: its first round's emit was dropped)
+            if ((tc & 3u) == 0) s_hist[tc >> 2] = sum;  // (this chunk has counted nothing else: its first round's emit was dropped)
           }
         } else {  // a strip's short last chunk: byte by byte
 #pragma unroll
           for (uint32_t k = 0; k < 8; ++k) atomicAdd(&s_hist[((k < 4 ? B.x : B.y) >> (8 * (k & 3))) & 0xFFu], 1u);
-          for (uint32_t pos = cstart + kRound + t; pos < cstart + clen; pos += K1_THREADS) atomicAdd(&s_hist[sp[pos]], 1u);
+          for (uint32_t pos = cs + kRound + tc; pos < cs + clen; pos += K1_THREADS) atomicAdd(&s_hist[sp[pos]], 1u);
         }
         const uint32_t r_last = (r + kRoundsPerChunk - 1 < nrounds ? r + kRoundsPerChunk - 1 : nrounds - 1);  // the chunk's last round
         const uint32_t ctok = pstore ? 0u : clen;  // tokens = items = positions -- or none
-        if (t < kSubRegions) {  // (an item is a position)
-          const uint32_t before = t * kSubBytes < ctok ? t * kSubBytes : ctok;
-          rtok_out[chunk * kSubRegions + t] = region_word(before, before);
+        if (tc < kSubRegions) {  // (an item is a position)
+          const uint32_t before = tc * kSubBytes < ctok ? tc * kSubBytes : ctok;
+          rtok_out[chunk * kSubRegions + tc] = region_word(before, before);
         }
         skip = true;
         lds_stale = true;
@@ -1537,30 +1584,44 @@ __global__ __launch_bounds__(K1_THREADS, CHAIN ? K1_THREADS / 256 : 2 * K1_THREA
     // @phase chunk.end trips=0.25 note=once per chunk of four rounds
     // ---- end of a chunk: its counts and histogram go out, the histogram starts over ----
     if (chunk_done || rc == kRoundsPerChunk - 1 || r + 1 == nrounds) {
+      // (the cold arguments, asked for in front of the barrier: the round trip passes in its wait)
+      const K1ColdPtr cold = k1_cold();
+      uint32_t* const hist_out = cold->hist_out;
+      uint32_t* const ntok_out = cold->ntok_out;
+      uint32_t* const nitems_out = cold->nitems_out;
       __syncthreads();  // this round's histogram updates are complete
+      // (once per chunk: from an opaque copy of t, so that its lane tests are made here and not kept, spilled, through the rounds)
+      uint32_t te = t;
+      asm volatile("" : "+v"(te));
       // (a chunk stored by its probe -- taken in one go, no tokens -- has counted nothing and has no histogram: k_plan goes by
       // its token count)
       if (!(chunk_done && tot_tok == 0))
-        for (uint32_t idx = t; idx < kHistStride; idx += K1_THREADS) {
+        for (uint32_t idx = te; idx < kHistStride; idx += K1_THREADS) {
           hist_out[(uint64_t)chunk * kHistStride + idx] = s_hist[idx];
           s_hist[idx] = (idx == 256) ? 1u : 0u;
         }
-      if (t == 0) { ntok_out[chunk] = tot_tok; nitems_out[chunk] = tot_items | (skip ? kItemsSkipped : 0u); }
+      if (te == 0) { ntok_out[chunk] = tot_tok; nitems_out[chunk] = tot_items | (skip ? kItemsSkipped : 0u); }
       const uint32_t covered = chunk_done ? kSubRegions : (rc + 1) * kRSubs;  // sub-index regions of the rounds that ran
-      if (t < kSubRegions && t >= covered) rtok_out[chunk * kSubRegions + t] = region_word(tot_tok, tot_items);
+      if (te < kSubRegions && te >= covered) rtok_out[chunk * kSubRegions + te] = region_word(tot_tok, tot_items);
       stamp(6);
     }
     // the next round's first barrier orders this round's LDS reads before its writes
   }
   // @phase (prologue/epilogue) trips=0
   if (nrounds == 0) {  // empty input: one empty chunk
+    const K1ColdPtr cold = k1_cold();
+    uint32_t* const hist_out = cold->hist_out;
+    uint32_t* const ntok_out = cold->ntok_out;
+    uint32_t* const nitems_out = cold->nitems_out;
     for (uint32_t idx = t; idx < kHistStride; idx += K1_THREADS) hist_out[(uint64_t)chunk0 * kHistStride + idx] = (idx == 256) ? 1u : 0u;
     if (t == 0) { ntok_out[chunk0] = 0; nitems_out[chunk0] = 0; }
     if (t < kSubRegions) rtok_out[chunk0 * kSubRegions + t] = 0;
   }
   if constexpr (STAMPS) {
-    if (t == 0)
+    if (t == 0) {
+      uint64_t* const stamps = k1_cold()->stamps;
       for (int k = 0; k < 8; ++k) stamps[(uint64_t)strip * 8 + k] = st_acc[k];
+    }
   }
 }
 
@@ -2831,8 +2892,9 @@ hipError_t launch_lz77(const uint8_t* src, uint64_t n, uint32_t nchunks, const W
   const uint32_t nstrips = bt ? bt->nstrips : (nchunks + per - 1) / per;
   const BatchStrip* strips = bt ? bt->strips : nullptr;
   const auto launch = [&](auto kernel, uint64_t* stamps) {
-    hipLaunchKernelGGL(kernel, dim3(nstrips), dim3(K1_THREADS), 0, s, src, n, opt.strip_bytes, ws.items, ws.nitems, ws.ntok,
-                       ws.hist, ws.rtok, opt.lazy, opt.fast_skip, stamps, opt.chain_depth, strips);
+    // (K1Cold first, always: k_lz77 reads it from the start of its kernarg segment, see k1_cold())
+    hipLaunchKernelGGL(kernel, dim3(nstrips), dim3(K1_THREADS), 0, s, K1Cold{ws.nitems, ws.ntok, ws.hist, stamps}, src, n,
+                       opt.strip_bytes, ws.items, ws.rtok, opt.lazy, opt.fast_skip, opt.chain_depth, strips);
   };
   // k_lz77 (with stamps in the diagnostic build), or a batch's k_lz77<.., BATCH> (no stamps)
 #define SF_K1(D2, NR, S2, LG, CH, RC)                                                                                     \
