@@ -116,6 +116,7 @@ inline auto to_status(int rc) -> CompressStatus {
   }
 }
 /// what the decoders' `container` argument takes: to them a dictzip file is a gzip stream
+static_assert(static_cast<std::uint32_t>(Container::GzipMembers) == SFH_GZIP_MEMBERS);  // (the stream decoders only)
 inline auto to_c(Container c) -> std::uint32_t { return c == Container::Dictzip ? SFH_GZIP : static_cast<std::uint32_t>(c); }
 inline auto to_c(const compress_options& o) -> sfh_options {
   sfh_options c;
@@ -634,6 +635,9 @@ class compressor {
   /// decompress(src, dst, container)'s, except that a zlib dst may be larger than the output (the Adler-32 covers the bytes
   /// produced; container.hpp checks it over all of dst); *produced (may be null) = the bytes the body produced.  A problem on the device side
   /// (no device, allocation) is DecompressStatus::Error; there is no host fallback.
+  /// Container::GzipMembers (here and in decompress_stream_batch only): a file of gzip members, every member decoded behind
+  /// the one before it -- decompress_members()'s statuses and bytes, with the one difference starflate_hip.h states (the
+  /// trailers' values are checked after every body has decoded).
   auto decompress_stream(std::span<const std::byte> src, std::span<std::byte> dst, Container container, std::size_t* produced = nullptr)
       -> DecompressStatus {
     if (produced) *produced = 0;

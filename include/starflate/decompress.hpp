@@ -174,13 +174,10 @@ inline auto read_lengths(huffman::bit_span& bits, const huffman::table<std::uint
 
 }  // namespace detail
 
-/// Decompresses raw DEFLATE `src` into `dst` (sized by the caller to the exact output length).
-/// produced (optional): bytes written -- an extra the reference does not report (src/decompress.hpp:63-64).
-inline auto decompress(std::span<const std::byte> src, std::span<std::byte> dst, std::ptrdiff_t* produced)
-    -> DecompressStatus {
-  huffman::bit_span bits{src};
-  std::ptrdiff_t written_here{};
-  std::ptrdiff_t& written = produced ? *produced : written_here;
+namespace detail {
+
+/// the blocks of one raw DEFLATE stream from the front of `bits`, up to and including its BFINAL block
+inline auto inflate_stream(huffman::bit_span& bits, std::span<std::byte> dst, std::ptrdiff_t& written) -> DecompressStatus {
   written = 0;
   for (bool was_final = false; !was_final;) {
     const auto header = detail::read_header(bits);
@@ -219,6 +216,28 @@ inline auto decompress(std::span<const std::byte> src, std::span<std::byte> dst,
     }
   }
   return DecompressStatus::Success;
+}
+
+}  // namespace detail
+
+/// Decompresses raw DEFLATE `src` into `dst` (sized by the caller to the exact output length).
+/// produced (optional): bytes written -- an extra the reference does not report (src/decompress.hpp:63-64).
+inline auto decompress(std::span<const std::byte> src, std::span<std::byte> dst, std::ptrdiff_t* produced)
+    -> DecompressStatus {
+  huffman::bit_span bits{src};
+  std::ptrdiff_t written_here{};
+  return detail::inflate_stream(bits, dst, produced ? *produced : written_here);
+}
+
+/// The same, for a stream that something follows: `dst` may be larger than the output, and *consumed is the number of bytes
+/// of `src` up to and including the one that holds the stream's last bit (meaningful on Success only).
+inline auto decompress(std::span<const std::byte> src, std::span<std::byte> dst, std::ptrdiff_t* produced, std::size_t* consumed)
+    -> DecompressStatus {
+  huffman::bit_span bits{src};
+  std::ptrdiff_t written_here{};
+  const auto st = detail::inflate_stream(bits, dst, produced ? *produced : written_here);
+  *consumed = src.size() - static_cast<std::size_t>(std::ranges::size(bits)) / CHAR_BIT;
+  return st;
 }
 
 inline auto decompress(std::span<const std::byte> src, std::span<std::byte> dst) -> DecompressStatus {

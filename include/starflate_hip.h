@@ -61,12 +61,17 @@ enum sfh_container {
   SFH_RAW = 0,  /* RFC 1951 only: what the reference's decompress() reads */
   SFH_ZLIB = 1, /* RFC 1950: 78 9C, stream, Adler-32 big-endian */
   SFH_GZIP = 2, /* RFC 1952: 1F 8B 08 00, MTIME 0, XFL 0, OS 255, stream, CRC-32, ISIZE (both little-endian) */
-  SFH_DICTZIP = 3 /* SFH_GZIP at block_bytes = 32768 whose header carries dictzip(1)'s random-access table (FLG = FEXTRA, an
+  SFH_DICTZIP = 3, /* SFH_GZIP at block_bytes = 32768 whose header carries dictzip(1)'s random-access table (FLG = FEXTRA, an
                      'RA' subfield: VER 1, CHLEN 32768, CHCNT, the compressed bytes of every 32 KiB chunk; "Seekable gzip" below).
                      In sfh_options.container of sfh_compress, sfh_compress_device and sfh_compress_device_async ONLY: the
                      batched calls, sfh_compress_multi and the gathered multi-process path refuse it (SFH_E_INVALID_ARG; out of
                      scope so far), and so does every decoder's `container` argument -- to a decoder such a file is an SFH_GZIP
                      stream (FEXTRA is skipped); sfh_dz_read_index* / sfh_decompress_dz* read the table */
+  SFH_GZIP_MEMBERS = 4 /* a file of gzip members (RFC 1952 2.2), zero bytes allowed behind each: `cat a.gz b.gz`, the joined items
+                          of sfh_compress_batch(SFH_GZIP), WARC files, BGZF without its 'BC' field.  Taken by sfh_inflate_stream,
+                          sfh_inflate_stream_device, sfh_inflate_stream_batch and sfh_inflate_stream_batch_device ONLY ("Files of
+                          gzip members" below); every other decoder and every compress call refuses it (SFH_E_INVALID_ARG, before
+                          anything is enqueued), and sfh_compress_bound_container answers 0 */
 };
 
 typedef struct sfh_options {
@@ -809,7 +814,28 @@ int sfh_last_recover_stats(sfh_ctx* ctx, float ms[2], uint64_t counts[2]);
  * plane, rounded up to 16 entries, 16 bytes at least) and 64 KiB per group of about sqrt(chunks) chunks beyond the first
  * (sfh_last_decode_scratch_bytes; the size query: the first term only).  After a non-zero *status sfh_last_error reads
  * "DecompressStatus N".
- * sfh_inflate_stream: host buffers (H2D, the same, D2H of dst when *status is 0); dst == NULL with dst_cap == 0 is the size query. */
+ * sfh_inflate_stream: host buffers (H2D, the same, D2H of dst when *status is 0); dst == NULL with dst_cap == 0 is the size query.
+ *
+ * Files of gzip members (container = SFH_GZIP_MEMBERS; these four calls only).  src is a series of gzip members, each with its
+ * own header, body, CRC-32 and ISIZE, zero bytes allowed behind every trailer (tape padding, as gzip and Python skip it).
+ * *status and *dst_n_out are what container.hpp's decompress_members(src, dst[dst_cap]) -- its Container::GzipMembers case --
+ * gives: every member decodes behind the one before it, dst may be larger than the output, a member has no history (a match
+ * that reaches before its member's first byte is InvalidDistance), output beyond dst_cap is DstTooSmall, an empty src, a
+ * trailer of fewer than 8 bytes or fewer than 18 bytes behind the zero bytes are SrcTooSmall, anything else that is no gzip
+ * header behind a trailer is Error, and so is an ISIZE (modulo 2^32) or a CRC-32 that does not match its member's own output.
+ * Empty members count.  After a non-zero *status *dst_n_out is not specified.
+ * ONE DIFFERENCE from the host function: it checks a member's trailer before it reads the next member; here the trailers'
+ * values are checked after every body of the item has decoded.  A file in which one member's CRC-32 or ISIZE is wrong AND a
+ * later member's header or body is faulty has the later fault's status here and Error there; both are non-zero.
+ * The size query returns the total output size and the first structural problem -- a bad header behind a trailer or a short
+ * trailer included --; ISIZE and CRC-32 values are the decode call's to check.
+ * The file is decoded as one stream: where a member ends, the decoding lane steps over trailer, padding and header and goes on,
+ * and the start of a member's body is a chunk candidate as well, so a file of many small members is cut as finely as one large
+ * stream.  Scratch: 16 bytes per candidate and 32 bytes per member more; the checksums run per member, all members of a
+ * launch batch in one launch, and the call has one host synchronisation more than above (the chunks' member counts, behind
+ * the chain rounds), however many members there are.  More than 2^31 - 1 members in a call: SFH_E_INVALID_ARG once the count pass knows, before any
+ * byte is written.  A member whose output is 4 GiB or more is not supported (its checksum is not folded correctly).
+ * Which reader for which file: INTEGRATION.md. */
 int sfh_inflate_stream_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint32_t container, void* d_dst, uint64_t dst_cap,
                               uint64_t* dst_n_out, uint32_t* status, void* stream);
 int sfh_inflate_stream(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, void* dst, uint64_t dst_cap,
@@ -887,8 +913,15 @@ enum sfh_debug_what {
                            lane-serial kernel, bytes, offset of a stored segment's bytes (u64)} */
   SFH_DBG_RITEM = 11, /* compressor: uint32[32] per chunk, the item index of each 1024-byte region's first token (regions
                          past the data: nitems) */
-  SFH_DBG_STAMPS = 6   /* uint64[2][nchunks][8] (k_lz77, k_plan); only with env SFH_K1_STAMPS=1 at sfh_create
+  SFH_DBG_STAMPS = 6,  /* uint64[2][nchunks][8] (k_lz77, k_plan); only with env SFH_K1_STAMPS=1 at sfh_create
                           (diagnostic k_lz77 build: cycles per phase, never a timing claim) */
+  SFH_DBG_STREAM_MEMBERS = 12 /* the member table of the last call when that was an sfh_inflate_stream* call with SFH_GZIP_MEMBERS
+                          (after any other call: SFH_E_INVALID_ARG): uint64 count, then count records of 32 bytes {uint64 src_end
+                          (the offset just past the member's trailer), uint64 out_end, uint32 crc32, uint32 isize (the trailer's
+                          values), uint32 item, uint32 status (0, or 1: the trailer does not match the member's output)}.  Offsets
+                          are relative to the item; records in call order, an item's members in file order; only items whose
+                          bodies decoded have records (a size query has none).  bytes >= 8: the count, and as many whole records
+                          as fit */
 };
 int sfh_debug_read(sfh_ctx* ctx, int what, void* host_dst, size_t bytes);
 

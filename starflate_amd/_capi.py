@@ -16,6 +16,7 @@ SEGMENT_BYTES = 32768
 STRATEGY = {"auto": 0, "stored": 1, "fixed": 2, "dynamic": 3}
 CONTAINER = {"raw": 0, "zlib": 1, "gzip": 2}  # what the decoders take (to them a dictzip file is a gzip stream)
 COMPRESS_CONTAINER = dict(CONTAINER, dictzip=3)  # ... and the single-stream compress calls: SFH_DICTZIP
+STREAM_CONTAINER = dict(CONTAINER, gzip_members=4)  # ... and the decompress_stream* family: SFH_GZIP_MEMBERS
 DZ_MAX_CHUNKS = 32762  # SFH_DZ_MAX_CHUNKS
 E_NOT_INDEXABLE = -8  # SFH_E_NOT_INDEXABLE
 SIZE_FROM_TRAILER = (1 << 64) - 1  # SFH_SIZE_FROM_TRAILER
@@ -25,6 +26,7 @@ DBG_SUBINDEX = 7
 DBG_ITEMS, DBG_NITEMS = 8, 9
 DBG_SEGINFO = 10
 DBG_RITEM = 11
+DBG_STREAM_MEMBERS = 12
 DEFAULT_BLOCK_BYTES = 262144
 LARGE_BLOCK_BYTES = 1 << 19
 CHAIN_BLOCK_BYTES = 1 << 20

@@ -631,7 +631,7 @@ class Compressor:
         then exactly the output size -- gzip: ISIZE where that is more, the room a gzip decode asks for whatever its body
         produces); out: a uint8 CUDA tensor of at least out_n bytes.  Synchronises the stream."""
         self._check_tensor(stream)
-        kind = _container(container)
+        kind = _stream_container(container)
         s = self._stream(hip_stream)
         st, n = C.c_uint32(0), C.c_uint64(0)
         src = stream.data_ptr()
@@ -655,7 +655,7 @@ class Compressor:
         where that is more, so that a trailer that claims more than the body gives is Error, as with any dst that holds
         ISIZE bytes).  b"" unless the status is 0."""
         src = _as_bytes(data)
-        kind = _container(container)
+        kind = _stream_container(container)
         st, n = C.c_uint32(0), C.c_uint64(0)
         sp = _ptr(src)
         if out_n is None:
@@ -709,7 +709,7 @@ class Compressor:
         stream."""
         streams = list(streams)
         self._check_tensors(streams)
-        kind = _container(container)
+        kind = _stream_container(container)
         k = len(streams)
         s = self._stream(hip_stream)
         sp = _dptrs(streams)
@@ -1082,8 +1082,8 @@ def _stream_batch_args(streams, sizes, container):
     if isinstance(streams, (bytes, bytearray, memoryview, np.ndarray)):
         raise ValueError("streams: a sequence of bytes-like streams")
     srcs = [_as_bytes(d) for d in streams]
-    if not isinstance(container, str) or container not in _capi.CONTAINER:
-        raise ValueError(f"container must be one of {sorted(_capi.CONTAINER)}")
+    if not isinstance(container, str) or container not in _capi.STREAM_CONTAINER:
+        raise ValueError(f"container must be one of {sorted(_capi.STREAM_CONTAINER)}")
     caps = None
     if sizes is not None:
         caps = [int(m) for m in sizes]
@@ -1091,7 +1091,7 @@ def _stream_batch_args(streams, sizes, container):
             raise ValueError(f"{len(srcs)} streams but {len(caps)} sizes")
         if any(m < 0 or m > (1 << 44) for m in caps):
             raise ValueError("sizes must lie in [0, 2^44]")
-    return srcs, _u64s(a.size for a in srcs), caps, _capi.CONTAINER[container]
+    return srcs, _u64s(a.size for a in srcs), caps, _capi.STREAM_CONTAINER[container]
 
 
 def _any_batch_args(streams, sizes, container):
@@ -1148,9 +1148,21 @@ def compress_batch(items, device=0, **kw):
 
 
 def _container(container):
+    if isinstance(container, str) and container not in _capi.CONTAINER:
+        raise ValueError(f"container must be one of {sorted(_capi.CONTAINER)}")
     kind = _capi.CONTAINER[container] if isinstance(container, str) else int(container)
     if kind not in (0, 1, 2):
         raise ValueError("container: raw, zlib or gzip")
+    return kind
+
+
+def _stream_container(container):
+    """the decompress_stream* family's: _container's, and gzip_members (SFH_GZIP_MEMBERS)"""
+    if isinstance(container, str) and container not in _capi.STREAM_CONTAINER:
+        raise ValueError(f"container must be one of {sorted(_capi.STREAM_CONTAINER)}")
+    kind = _capi.STREAM_CONTAINER[container] if isinstance(container, str) else int(container)
+    if kind not in (0, 1, 2, 4):
+        raise ValueError("container: raw, zlib, gzip or gzip_members")
     return kind
 
 
@@ -1175,6 +1187,7 @@ def decompress(data, out_n=None, container="raw", device=0):
     """One stream given alone -> bytes, on the GPU (Compressor.decompress_any): the segment index is recovered from the
     stream's flush markers.  A status other than Success raises StarflateError; so does a stream that is not block-flushed
     every 32 KiB (code -8): such a stream is the serial decoder's."""
+    _container(container)
     c = _default(device)
     out, st = c.decompress_any(data, out_n, container)
     _raise_on_status(st)

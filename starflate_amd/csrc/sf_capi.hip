@@ -126,6 +126,11 @@ struct sfh_ctx {
   // the wrapper rows and bodies | the item rows; a launch batch's group, checksum and fold rows and its statuses
   Buf<uint8_t> d_sbt;
   Buf<uint8_t> d_sbr;
+  // files of gzip members (SFH_GZIP_MEMBERS): the write pass's member rows, and the last such call's table on the host
+  // (SFH_DBG_STREAM_MEMBERS; valid until the next call of any kind ends)
+  Buf<uint8_t> d_smem;
+  std::vector<sf::StreamMember> stm_members;
+  bool stm_members_valid = false;
   // ZIP (sfh_zip_read_index_device, sfh_decompress_zip*, sfh_compress_zip*), all on first use: the reader's tables (entry
   // table; copy, piece, checksum and fold rows and the statuses); the writer's tables, pinned and on the device (its own
   // stager: enqueue_zip's batch calls use `tab`), and the raw streams of one launch batch
@@ -265,6 +270,7 @@ int mark_call_end(sfh_ctx* ctx, hipStream_t s) {
   SF_HIP(hipEventRecord(ctx->ev_done, s), "event");
   ctx->busy = true;
   ctx->last_stream = s;
+  ctx->stm_members_valid = false;
   return SFH_OK;
 }
 // What opens a device entry point: the context's device is current, whatever launch error an earlier caller on this thread
@@ -1329,10 +1335,13 @@ int any_batch_decode(sfh_ctx* ctx, size_t count, const void* const* d_srcs, cons
 }
 
 // ---- streams without flush points (sfh_inflate_stream*, sfh_inflate_stream_batch*; sf_stream.hip) ----
+// the containers these calls take, and no other: the decoders', and a file of gzip members
+bool stream_container(uint32_t container) { return container <= SFH_GZIP || container == SFH_GZIP_MEMBERS; }
+
 // Everything a batched call checks before it enqueues anything (`dev`: device buffers, the single call's alignment rules).
 int check_stream_batch(sfh_ctx* ctx, size_t count, const void* const* srcs, const uint64_t* src_n, uint32_t container,
                        void* const* dsts, const uint64_t* dst_cap, const uint64_t* dst_n_out, const uint32_t* status, bool dev) {
-  if (!ctx || container > SFH_GZIP) return fail(ctx, SFH_E_INVALID_ARG, "argument (container)", hipSuccess);
+  if (!ctx || !stream_container(container)) return fail(ctx, SFH_E_INVALID_ARG, "argument (container)", hipSuccess);
   if (count == 0) return SFH_OK;
   if (!srcs || !src_n || !dst_n_out || !status || (dsts && !dst_cap)) return fail(ctx, SFH_E_INVALID_ARG, "null array", hipSuccess);
   const uint64_t S = ctx->stream_chunk;
@@ -1360,6 +1369,17 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
                      void* const* dsts, const uint64_t* dst_cap, bool stage, std::vector<uint64_t>* out_off, uint64_t* dst_n_out,
                      uint32_t* status, hipStream_t s, const uint64_t* lead = nullptr) {
   // lead (raw items only; null: none): bytes of item i in front of its body -- a ZIP entry's data inside the aligned item around it
+  // members: every item is a file of gzip members.  Its wrapper is its first member's header (wrap: the container whose head
+  // and checksum kernels serve), its body reaches to its last byte, its records have side rows, and its trailers are checked
+  // per member behind each launch batch ("Files of members")
+  const bool members = container == SFH_GZIP_MEMBERS;
+  const uint32_t wrap = members ? (uint32_t)SFH_GZIP : container;
+  ctx->stm_members.clear();
+  const auto call_end = [&]() -> int {
+    const int rc = mark_call_end(ctx, s);
+    ctx->stm_members_valid = !rc && members;
+    return rc;
+  };
   const bool prof = ctx->profiling != 0;
   for (float& m : ctx->stm_ms) m = 0;
   for (uint64_t& c : ctx->stm_counts) c = 0;
@@ -1405,10 +1425,10 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   sf::StreamItem* d_items = Carve::at<sf::StreamItem>(ctx->d_sbt, o_items);
   if (container != SFH_RAW) {
     for (size_t i = 0; i < count; ++i)
-      head[i] = sf::InflateItem{(const uint8_t*)srcs[i], src_n[i], decodes(i) ? dst_cap[i] : kBig, d_body + 2 * i, nullptr, 0, 0,
-                                0, 0, 0, 0};
+      head[i] = sf::InflateItem{(const uint8_t*)srcs[i], src_n[i], decodes(i) && !members ? dst_cap[i] : kBig, d_body + 2 * i,
+                                nullptr, 0, 0, 0, 0, 0, 0};  // (members: the last trailer's ISIZE says nothing about the file)
     SF_HIP(hipMemcpyAsync(d_head, head.data(), sizeof(sf::InflateItem) * count, hipMemcpyHostToDevice, s), "H2D wrapper rows");
-    SF_HIP(sf::launch_inflate_head(d_head, (uint32_t)count, container, nullptr, nullptr, s), "launch k_inflate_head");
+    SF_HIP(sf::launch_inflate_head(d_head, (uint32_t)count, wrap, nullptr, nullptr, s), "launch k_inflate_head");
     SF_HIP(hipMemcpyAsync(head.data(), d_head, sizeof(sf::InflateItem) * count, hipMemcpyDeviceToHost, s), "D2H wrapper rows");
     SF_HIP(hipMemcpyAsync(body.data(), d_body, 16 * count, hipMemcpyDeviceToHost, s), "D2H bodies");
     SF_HIP(hipStreamSynchronize(s), "stream sync");
@@ -1426,7 +1446,7 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
       status[i] = head[i].wst;
       continue;
     }
-    const uint64_t bn = body[2 * i + 1] - body[2 * i];
+    const uint64_t bn = (members ? src_n[i] : body[2 * i + 1]) - body[2 * i];
     sf::StreamItem it{};
     it.src = (const uint8_t*)srcs[i];
     it.src_n = src_n[i];
@@ -1438,13 +1458,19 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
     items.push_back(it);
   }
   const uint32_t nl = (uint32_t)live.size();
-  if (nl == 0) return mark_call_end(ctx, s);
+  if (nl == 0) return call_end();
   if (nc64 >= ((uint64_t)1 << 31)) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 nominal chunks (SFH_STREAM_CHUNK)", hipSuccess);
   const uint32_t nc = (uint32_t)nc64;
-  // cand u64[nc] (then: the records' items u32[nc] | the follow list u32[nc]) | recs StreamChunk[nc] | list u32[nc]
+  // cand u64[nc] (then: the records' items u32[nc] | the follow list u32[nc]) | recs StreamChunk[nc] | list u32[nc] | members:
+  // side StreamSide[nc]
   Carve C;
-  const size_t o_cand = C.add<uint64_t>(nc), o_rec = C.add<sf::StreamChunk>(nc), o_list = C.add<uint32_t>(nc), stm_bytes = C.bytes();
+  const size_t o_cand = C.add<uint64_t>(nc), o_rec = C.add<sf::StreamChunk>(nc), o_list = C.add<uint32_t>(nc);
+  const size_t o_side = C.add<sf::StreamSide>(members ? nc : 0);
+  size_t stm_bytes = C.bytes();
   if ((rc = ctx->d_stm.grow(ctx, stm_bytes, "stream chunk records"))) return rc;
+  sf::StreamSide* d_side = members ? Carve::at<sf::StreamSide>(ctx->d_stm, o_side) : nullptr;
+  sf::StreamMember* d_mem = nullptr;
+  std::vector<sf::StreamSide> side;
   uint64_t* d_cand = Carve::at<uint64_t>(ctx->d_stm, o_cand);
   uint32_t* d_rec_item = Carve::at<uint32_t>(ctx->d_stm, o_cand);
   uint32_t* d_follow = d_rec_item + nc;
@@ -1463,7 +1489,7 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   // A: candidates, every item's nominal chunks at once
   SF_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(sf::StreamItem) * nl, hipMemcpyHostToDevice, s), "H2D item rows");
   if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[0], s), "event");
-  SF_HIP(sf::launch_stream_find(d_items, nl, nc, S, d_cand, s), "launch k_stream_find");
+  SF_HIP(sf::launch_stream_find(d_items, nl, nc, S, d_cand, s, members), "launch k_stream_find");
   if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[1], s), "event");
   SF_HIP(hipMemcpyAsync(cand.data(), d_cand, 8 * (size_t)nc, hipMemcpyDeviceToHost, s), "D2H candidates");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
@@ -1485,7 +1511,7 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   SF_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(sf::StreamItem) * nl, hipMemcpyHostToDevice, s), "H2D item rows");
   SF_HIP(hipMemcpyAsync(d_rec_item, rec_item.data(), 4 * (size_t)M, hipMemcpyHostToDevice, s), "H2D record items");
   SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
-  SF_HIP(sf::launch_stream_decode(false, d_items, d_rec_item, d_rec, nullptr, M, false, nullptr, s), "launch k_stream_decode");
+  SF_HIP(sf::launch_stream_decode(false, d_items, d_rec_item, d_rec, nullptr, M, false, nullptr, s, d_side), "launch k_stream_decode");
   SF_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s), "D2H chunk records");
   SF_HIP(hipStreamSynchronize(s), "stream sync");
   std::vector<char> done(nl, 0);
@@ -1509,15 +1535,24 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
     SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
     SF_HIP(hipMemcpyAsync(d_list, redo.data(), 4 * redo.size(), hipMemcpyHostToDevice, s), "H2D repair list");
     SF_HIP(hipMemcpyAsync(d_follow, follow.data(), 4 * follow.size(), hipMemcpyHostToDevice, s), "H2D follow list");
-    SF_HIP(sf::launch_stream_decode(false, d_items, d_rec_item, d_rec, d_list, (uint32_t)redo.size(), false, nullptr, s),
+    SF_HIP(sf::launch_stream_decode(false, d_items, d_rec_item, d_rec, d_list, (uint32_t)redo.size(), false, nullptr, s, d_side),
            "launch k_stream_decode");
-    SF_HIP(sf::launch_stream_decode(false, d_items, d_rec_item, d_rec, d_follow, (uint32_t)follow.size(), true, nullptr, s),
+    SF_HIP(sf::launch_stream_decode(false, d_items, d_rec_item, d_rec, d_follow, (uint32_t)follow.size(), true, nullptr, s, d_side),
            "launch k_stream_decode");
     SF_HIP(hipMemcpyAsync(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, s), "D2H chunk records");
     SF_HIP(hipStreamSynchronize(s), "stream sync");
   }
   if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[2], s), "event");
-  std::vector<uint64_t> total(nl, 0);
+  if (members) {  // the side rows as the last decode of each record left them
+    try {
+      side.resize(M);
+    } catch (...) {
+      return fail(ctx, SFH_E_NOMEM, "host memory for the side rows", hipSuccess);
+    }
+    SF_HIP(hipMemcpyAsync(side.data(), d_side, sizeof(sf::StreamSide) * (size_t)M, hipMemcpyDeviceToHost, s), "D2H side rows");
+    SF_HIP(hipStreamSynchronize(s), "stream sync");
+  }
+  std::vector<uint64_t> total(nl, 0), mem0(nl + 1, 0);  // mem0: an item's first member row (decoded items only)
   uint64_t longest = 0, confirmed = 0;
   for (uint32_t k = 0; k < nl; ++k) {
     sf::StreamItem& it = items[k];
@@ -1531,6 +1566,13 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
     confirmed += chain[k];
     dst_n_out[live[k]] = total[k];
     if (!decodes(live[k])) status[live[k]] = rec[it.r0 + chain[k] - 1].status;
+    mem0[k + 1] = members && decodes(live[k]) ? sf::stream_member_scan(rec.data(), side.data(), it.r0, chain[k], mem0[k]) : mem0[k];
+  }
+  if (mem0[nl] > ((uint64_t)1 << 31) - 1) return fail(ctx, SFH_E_INVALID_ARG, "more than 2^31 - 1 members in one call", hipSuccess);
+  if (mem0[nl]) {
+    if ((rc = ctx->d_smem.grow(ctx, sizeof(sf::StreamMember) * mem0[nl], "member rows"))) return rc;
+    d_mem = Carve::at<sf::StreamMember>(ctx->d_smem, 0);
+    stm_bytes += sizeof(sf::StreamMember) * mem0[nl];
   }
   ctx->stm_counts[0] = nc;
   ctx->stm_counts[1] = M;
@@ -1552,7 +1594,7 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
     for (size_t i = 0, k = 0; i < count; ++i) {
       (*out_off)[i] = o;
       if (k < nl && live[k] == i) {
-        if (decodes(i)) o += al16(std::min(total[k], container == SFH_GZIP ? (uint64_t)head[i].isize : dst_cap[i]));
+        if (decodes(i)) o += al16(std::min(total[k], container == SFH_GZIP ? (uint64_t)head[i].isize : dst_cap[i]));  // (as it.cap)
         ++k;
       }
     }
@@ -1586,7 +1628,10 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
   if (!dec.empty()) {
     SF_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(sf::StreamItem) * nl, hipMemcpyHostToDevice, s), "H2D item rows");
     SF_HIP(hipMemcpyAsync(d_rec, rec.data(), rec_bytes, hipMemcpyHostToDevice, s), "H2D chunk records");
+    if (members) SF_HIP(hipMemcpyAsync(d_side, side.data(), sizeof(sf::StreamSide) * (size_t)M, hipMemcpyHostToDevice, s), "H2D side rows");
   }
+  std::vector<sf::StreamMember> mrow;  // members: a launch batch's member rows, and per fold row its member in them
+  std::vector<uint32_t> fold_mem, whole;  // whole: the batch's items whose bodies decoded
   std::vector<uint32_t> wlist, link, bst;
   std::vector<sf::StreamGroup> compose, resolve;
   std::vector<sf::BatchChunk> sums;
@@ -1607,11 +1652,21 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
     const uint32_t ra = items[dec[q0]].r0, rb = items[dec[q1 - 1]].r0 + items[dec[q1 - 1]].m;
     if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[2], s), "event");
     SF_HIP(hipMemcpyAsync(d_list, wlist.data(), 4 * wlist.size(), hipMemcpyHostToDevice, s), "H2D write list");
-    SF_HIP(sf::launch_stream_decode(true, d_items, d_rec_item, d_rec, d_list, (uint32_t)wlist.size(), false, ctx->d_plane, s),
+    SF_HIP(sf::launch_stream_decode(true, d_items, d_rec_item, d_rec, d_list, (uint32_t)wlist.size(), false, ctx->d_plane, s, d_side,
+                                    d_mem),
            "launch k_stream_decode");
     if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[3], s), "event");
     SF_HIP(hipMemcpyAsync(rec.data() + ra, d_rec + ra, sizeof(sf::StreamChunk) * (size_t)(rb - ra), hipMemcpyDeviceToHost, s),
            "D2H chunk records");
+    const uint64_t ma = mem0[dec[q0]], mb = mem0[dec[q1 - 1] + 1];  // the batch's member rows (an item not decoded has none)
+    if (members && mb > ma) {
+      try {
+        mrow.resize(mb - ma);
+      } catch (...) {
+        return fail(ctx, SFH_E_NOMEM, "host memory for the member rows", hipSuccess);
+      }
+      SF_HIP(hipMemcpyAsync(mrow.data(), d_mem + ma, sizeof(sf::StreamMember) * (mb - ma), hipMemcpyDeviceToHost, s), "D2H member rows");
+    }
     SF_HIP(hipStreamSynchronize(s), "stream sync");
     if (prof && (rc = lap(2, 3, 2))) return rc;
     // the statuses; E / F for the items that decoded, then their checksums
@@ -1621,6 +1676,8 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
     sums.clear();
     fold.clear();
     fold_item.clear();
+    fold_mem.clear();
+    whole.clear();
     for (size_t q = q0; q < q1; ++q) {
       const uint32_t k = dec[q];
       const sf::StreamItem& it = items[k];
@@ -1636,7 +1693,25 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
         resolve.push_back(sf::StreamGroup{k, g});
       }
       if (ng > 1) link.push_back(k);
-      if (container) {
+      if (members) {
+        whole.push_back(k);
+        // one fold row per member, its checksum rows of at most 32 KiB from wherever its output starts; ISIZE from the row
+        uint64_t o = 0;
+        for (uint64_t r = mem0[k]; r < mem0[k + 1]; ++r) {
+          sf::StreamMember& m = mrow[r - ma];
+          const uint64_t n = m.out_end - o;
+          m.item = (uint32_t)i;
+          m.status = m.isize != (uint32_t)n;
+          if (m.status) status[i] = sf::inflate::kError;
+          fold.push_back(sf::InflateItem{it.src, it.src_n, n, nullptr, nullptr, (uint32_t)sums.size(), 0, 0, m.crc32,
+                                         (uint32_t)std::min<uint64_t>(n, 0xFFFFFFFFu), 0});
+          fold_item.push_back((uint32_t)i);
+          fold_mem.push_back((uint32_t)(r - ma));
+          for (uint64_t ob = 0; ob < n || ob == 0; ob += sf::kChunk)
+            sums.push_back(sf::BatchChunk{n ? it.dst + o + ob : (const uint8_t*)ctx->d_plane.p, (uint32_t)std::min<uint64_t>(sf::kChunk, n - ob), 0u});
+          o = m.out_end;
+        }
+      } else if (container) {
         const uint32_t nch = chunks_of((size_t)total[k]);
         fold.push_back(sf::InflateItem{it.src, it.src_n, total[k], nullptr, nullptr, (uint32_t)sums.size(), 0, 0, head[i].want,
                                        (uint32_t)total[k], 0});
@@ -1667,21 +1742,40 @@ int stream_batch_run(sfh_ctx* ctx, size_t count, const void* const* srcs, const 
       if ((rc = ensure_sums(ctx, (uint32_t)sums.size()))) return rc;
       SF_HIP(hipMemcpyAsync(R + o_sums, sums.data(), sizeof(sf::BatchChunk) * sums.size(), hipMemcpyHostToDevice, s), "H2D checksum rows");
       SF_HIP(hipMemcpyAsync(R + o_fold, fold.data(), sizeof(sf::InflateItem) * fold.size(), hipMemcpyHostToDevice, s), "H2D fold rows");
-      SF_HIP(sf::launch_checksum_batch(Carve::at<const sf::BatchChunk>(R, o_sums), (uint32_t)sums.size(), container, ctx->ws.sums, s),
-             "launch k_checksum_batch");
-      SF_HIP(sf::launch_inflate_fold(Carve::at<const sf::InflateItem>(R, o_fold), (uint32_t)fold.size(), nullptr, ctx->ws.sums, container,
+      if (members)
+        SF_HIP(sf::launch_checksum_batch_any(Carve::at<const sf::BatchChunk>(R, o_sums), (uint32_t)sums.size(), ctx->ws.sums, s),
+               "launch k_checksum_batch");
+      else
+        SF_HIP(sf::launch_checksum_batch(Carve::at<const sf::BatchChunk>(R, o_sums), (uint32_t)sums.size(), container, ctx->ws.sums, s),
+               "launch k_checksum_batch");
+      SF_HIP(sf::launch_inflate_fold(Carve::at<const sf::InflateItem>(R, o_fold), (uint32_t)fold.size(), nullptr, ctx->ws.sums, wrap,
                                      Carve::at<uint32_t>(R, o_fst), nullptr, s), "launch k_inflate_fold");
       bst.resize(fold.size());
       SF_HIP(hipMemcpyAsync(bst.data(), R + o_fst, 4 * fold.size(), hipMemcpyDeviceToHost, s), "D2H checksums");
     }
     if (prof) SF_HIP(hipEventRecord(ctx->ev_stm[5], s), "event");
     SF_HIP(hipStreamSynchronize(s), "stream sync");
-    for (size_t f = 0; f < fold.size(); ++f) status[fold_item[f]] = bst[f];
+    for (size_t f = 0; f < fold.size(); ++f) {
+      if (!members) {
+        status[fold_item[f]] = bst[f];
+      } else if (bst[f]) {  // (an item's status: its first member that fails either check, and both are Error)
+        status[fold_item[f]] = bst[f];
+        mrow[fold_mem[f]].status = 1;
+      }
+    }
+    if (members) {  // the table: the rows of the items whose bodies decoded, in call order
+      try {
+        for (const uint32_t k : whole)
+          ctx->stm_members.insert(ctx->stm_members.end(), mrow.begin() + (mem0[k] - ma), mrow.begin() + (mem0[k + 1] - ma));
+      } catch (...) {
+        return fail(ctx, SFH_E_NOMEM, "host memory for the member table", hipSuccess);
+      }
+    }
     if (prof && ((rc = lap(3, 4, 3)) || (rc = lap(4, 5, 4)))) return rc;
   }
   ctx->stm_counts[5] = stm_bytes + peak;
   ctx->last_dtok_bytes = ctx->stm_counts[5];
-  return mark_call_end(ctx, s);
+  return call_end();
 }
 
 // A single stream: the driver with count == 1 (dst null: the size query; stage: dst is a host buffer, the bytes land at
@@ -3440,7 +3534,7 @@ int sfh_last_recover_stats(sfh_ctx* ctx, float ms[2], uint64_t counts[2]) {
 int sfh_inflate_stream_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uint32_t container, void* d_dst, uint64_t dst_cap,
                               uint64_t* dst_n_out, uint32_t* status, void* stream) {
   if (!ctx) return SFH_E_INVALID_ARG;
-  if ((!d_src && src_n) || container > SFH_GZIP || !dst_n_out || !status || (!d_dst && dst_cap))
+  if ((!d_src && src_n) || !stream_container(container) || !dst_n_out || !status || (!d_dst && dst_cap))
     return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   if (((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & 15))
     return fail(ctx, SFH_E_INVALID_ARG, "device pointer alignment (src 4, dst 16)", hipSuccess);
@@ -3452,7 +3546,7 @@ int sfh_inflate_stream_device(sfh_ctx* ctx, const void* d_src, size_t src_n, uin
 int sfh_inflate_stream(sfh_ctx* ctx, const void* src, size_t src_n, uint32_t container, void* dst, uint64_t dst_cap,
                        uint64_t* dst_n_out, uint32_t* status) {
   if (!ctx) return SFH_E_INVALID_ARG;
-  if ((!src && src_n) || container > SFH_GZIP || !dst_n_out || !status || (!dst && dst_cap))
+  if ((!src && src_n) || !stream_container(container) || !dst_n_out || !status || (!dst && dst_cap))
     return fail(ctx, SFH_E_INVALID_ARG, "argument", hipSuccess);
   int rc = host_up(ctx, src, src_n, 0);  // (the driver sizes d_out once it knows the output's)
   if (!rc) rc = stream_one(ctx, ctx->d_in, src_n, container, dst, dst_cap, dst != nullptr, dst_n_out, status, ctx->stream);
@@ -3747,6 +3841,14 @@ const char* sfh_stage_name(int stage) {
 }
 
 int sfh_debug_read(sfh_ctx* ctx, int what, void* host_dst, size_t bytes) {
+  if (ctx && host_dst && what == SFH_DBG_STREAM_MEMBERS) {  // host memory, whatever the last compress call was
+    if (!ctx->stm_members_valid || bytes < 8) return SFH_E_INVALID_ARG;
+    const uint64_t count = ctx->stm_members.size();
+    memcpy(host_dst, &count, 8);
+    const size_t fit = std::min<size_t>(count, (bytes - 8) / sizeof(sf::StreamMember));
+    if (fit) memcpy(static_cast<uint8_t*>(host_dst) + 8, ctx->stm_members.data(), fit * sizeof(sf::StreamMember));
+    return SFH_OK;
+  }
   if (!ctx || !host_dst || !ctx->last_chunks) return SFH_E_INVALID_ARG;
   // per-batch arrays hold the last batch of the call (all of it for up to kBatchChunks chunks); each array is read no
   // further than it was allocated: the last call may be a decode on a context whose compressor arrays are smaller or absent

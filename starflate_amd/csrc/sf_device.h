@@ -500,14 +500,17 @@ struct StreamGroup {     // compose / resolve: one workgroup per (item, group)
   uint32_t item, g;
 };
 static_assert(sizeof(StreamItem) == 88 && sizeof(StreamGroup) == 8, "stream item rows");
-// one wave per nominal chunk of the call (nc), its item found by a search over items[].c0
+// one wave per nominal chunk of the call (nc), its item found by a search over items[].c0.  members: every item is a file of
+// gzip members (b0: the first header's end, the body reaches to src_n), and a member's body start is a candidate too
 hipError_t launch_stream_find(const StreamItem* items, uint32_t nitems, uint32_t nc, uint64_t step_bytes, uint64_t* cand,
-                              hipStream_t s);
+                              hipStream_t s, bool members = false);
 // list (nullable: 0..n-1): the records to decode; rec_item[r]: record r's row in items.  follow: one lane per list entry goes on
 // into the records after it while their links break, within its item's records (see k_stream_decode).  write: the exact pass
-// into plane + the item's offset
+// into plane + the item's offset.  side (null: no item is a file of gzip members; else every item is): the records' side rows,
+// and mem, the write pass's member rows (sf_stream_chain.h)
 hipError_t launch_stream_decode(bool write, const StreamItem* items, const uint32_t* rec_item, StreamChunk* recs,
-                                const uint32_t* list, uint32_t n, bool follow, uint16_t* plane, hipStream_t s);
+                                const uint32_t* list, uint32_t n, bool follow, uint16_t* plane, hipStream_t s,
+                                StreamSide* side = nullptr, StreamMember* mem = nullptr);
 uint32_t stream_group(uint32_t n);  // chunks per group of the resolve; an item's tables: (groups - 1) * 32768 u16
 // compose rows (every group but an item's last), link (one workgroup per item of more than one group), resolve rows (all)
 hipError_t launch_stream_resolve(const uint16_t* plane, const StreamChunk* recs, const StreamItem* items,

@@ -1,4 +1,4 @@
-// sf_stream.hip -- raw, zlib or gzip streams (one member each) decoded on the GPU with no side information and no flush points
+// sf_stream.hip -- raw, zlib or gzip streams (one member each), or files of gzip members, decoded on the GPU with no side information and no flush points
 // (sfh_inflate_stream*, sfh_inflate_stream_batch*; DESIGN.md 3a "Streams without flush points").  A call holds one item or
 // many; a single stream is a call of one item.  Each kernel reads its item's stream, body (the stream without its wrapper),
 // plane, capacity and output from a StreamItem row (sf_device.h).  The body is cut into chunks at speculative block starts, the
@@ -34,13 +34,33 @@
 // (a stored block with non-zero padding is not); fixed blocks are not, three header bits being no evidence, so a Z_FIXED
 // stream is decoded by one lane: slow, but correct.  A stored block's payload goes into the plane 16 bytes per step (copy_stored).  Bit positions and output counts are 64-bit; the 32-bit BitReader is re-opened before its position passes 2^30.
 // Scratch: 2 bytes per output byte (the plane), 64 KiB per group, 60 bytes per nominal chunk.
+//
+// A file of gzip members (SFH_GZIP_MEMBERS; every item of such a call is one) is ONE body from its first header's end to its
+// last byte: where a member's BFINAL block ends, the lane hops over the trailer, the zero bytes and the next header
+// (sf_members.h) and decodes on, so chunks, chain and resolve are the single member's.  Three things are added.  Find: a
+// nominal chunk's candidate may also be the body start behind a member head whose header ends inside the chunk's range.  The
+// side rows (sf_stream_chain.h): the count pass counts the members each chunk closes, the host's scan gives each chunk its
+// first member row and the output offset at which the member open at its start began, and the write pass refuses a distance
+// that reaches before that offset -- so no window marker leaves its member, and compose, link and resolve stay as they are --
+// and writes one member row per member it closes: the trailer's CRC-32 and ISIZE, which the host then checks per member.
+// Scratch: 16 bytes per record and 32 per member more.
 #include "sf_stream_core.h"
 
 namespace sf {
 
 namespace {
 
+// members mode: the body bit behind the member head at body byte `byte`, if one stands there and its header ends before hi_bit
+__device__ __forceinline__ uint64_t member_body_candidate(const StreamItem& I, uint64_t byte, uint64_t hi_bit) {
+  const uint64_t at = I.b0 + byte;
+  if (!members::head_candidate(I.src, at, I.src_n)) return kNoCandidate;
+  uint32_t st;
+  const uint64_t bit = 8 * (members::header_end(I.src, at, I.src_n, st) - I.b0);
+  return bit < hi_bit ? bit : kNoCandidate;
+}
+
 // one wave per nominal chunk row of the call; the row's item is the last whose first row c0 is at or before it
+template <bool MEMBERS>
 __global__ __launch_bounds__(KF_THREADS) void k_stream_find(const StreamItem* __restrict__ items, uint32_t nitems, uint32_t nc,
                                                             uint64_t step_bits, uint64_t* __restrict__ cand) {
   __shared__ uint8_t s_lut[KF_THREADS][128];
@@ -79,6 +99,15 @@ __global__ __launch_bounds__(KF_THREADS) void k_stream_find(const StreamItem* __
       if (lane == 0) cand[r] = at + (uint64_t)(__ffsll((unsigned long long)b) - 1);
       return;
     }
+    if (MEMBERS) {  // no block start in these 64 bits: a member head at one of their 8 bytes?
+      const uint64_t v = (lane & 7) == 0 && p < hi_bit ? member_body_candidate(I, p >> 3, hi_bit) : kNoCandidate;
+      const uint64_t mb = __ballot(v != kNoCandidate);
+      if (mb) {
+        const uint64_t first = __shfl(v, __ffsll((unsigned long long)mb) - 1);
+        if (lane == 0) cand[r] = first;
+        return;
+      }
+    }
   }
   if (lane == 0) cand[r] = kNoCandidate;
 }
@@ -90,11 +119,12 @@ __global__ __launch_bounds__(KF_THREADS) void k_stream_find(const StreamItem* __
 // end, so a repair never runs into the next item.  A run of false candidates (stored blocks full of DEFLATE data put one in
 // nearly every nominal chunk) is then mended in one round instead of one link per round; the other lanes' speculative repairs
 // of the round have finished (an earlier launch), so no record is written by two lanes.
-template <bool WRITE>
+template <bool WRITE, bool MEMBERS>
 __global__ __launch_bounds__(KS_LANES) void k_stream_decode(const StreamItem* __restrict__ items,
                                                             const uint32_t* __restrict__ rec_item, StreamChunk* __restrict__ recs,
                                                             const uint32_t* __restrict__ list, uint32_t n, bool follow,
-                                                            uint16_t* __restrict__ plane) {
+                                                            uint16_t* __restrict__ plane, StreamSide* __restrict__ side,
+                                                            StreamMember* __restrict__ mem) {
   extern __shared__ __align__(16) uint8_t s_tables[];
   const uint32_t k = blockIdx.x * KS_LANES + threadIdx.x;
   if (k >= n) return;
@@ -111,7 +141,11 @@ __global__ __launch_bounds__(KS_LANES) void k_stream_decode(const StreamItem* __
       a.limit = a.end;  // (as stream_chain_round: the same decode)
       b.start = a.end;
     }
-    stream_decode<WRITE>(I.src, I.src_n, I.b0, I.body_n, recs[j], tab, WRITE ? plane + I.plane : plane, I.cap);
+    if (MEMBERS)
+      stream_decode<WRITE, true>(I.src, I.src_n, I.b0, I.body_n, recs[j], tab, WRITE ? plane + I.plane : plane, I.cap, side + j, mem,
+                                 rec_item[j]);
+    else
+      stream_decode<WRITE, false>(I.src, I.src_n, I.b0, I.body_n, recs[j], tab, WRITE ? plane + I.plane : plane, I.cap);
     if (!follow) break;  // (follow: b.start >= b.limit is an empty chunk)
   }
 }
@@ -191,21 +225,29 @@ __global__ __launch_bounds__(KR_THREADS) void k_stream_resolve(const uint16_t* _
 }  // namespace
 
 hipError_t launch_stream_find(const StreamItem* items, uint32_t nitems, uint32_t nc, uint64_t step_bytes, uint64_t* cand,
-                              hipStream_t s) {
+                              hipStream_t s, bool members) {
   if (nc == 0) return hipSuccess;
   const uint32_t per = KF_THREADS / 64;
-  hipLaunchKernelGGL(k_stream_find, dim3((nc + per - 1) / per), dim3(KF_THREADS), 0, s, items, nitems, nc, 8 * step_bytes, cand);
+  if (members)
+    hipLaunchKernelGGL(k_stream_find<true>, dim3((nc + per - 1) / per), dim3(KF_THREADS), 0, s, items, nitems, nc, 8 * step_bytes, cand);
+  else
+    hipLaunchKernelGGL(k_stream_find<false>, dim3((nc + per - 1) / per), dim3(KF_THREADS), 0, s, items, nitems, nc, 8 * step_bytes, cand);
   return hipGetLastError();
 }
 
 hipError_t launch_stream_decode(bool write, const StreamItem* items, const uint32_t* rec_item, StreamChunk* recs,
-                                const uint32_t* list, uint32_t n, bool follow, uint16_t* plane, hipStream_t s) {
+                                const uint32_t* list, uint32_t n, bool follow, uint16_t* plane, hipStream_t s, StreamSide* side,
+                                StreamMember* mem) {
   if (n == 0) return hipSuccess;
   const dim3 grid((n + KS_LANES - 1) / KS_LANES), block(KS_LANES);
-  if (write)
-    hipLaunchKernelGGL(k_stream_decode<true>, grid, block, KS_LDS, s, items, rec_item, recs, list, n, follow, plane);
+  if (write && side)
+    hipLaunchKernelGGL((k_stream_decode<true, true>), grid, block, KS_LDS, s, items, rec_item, recs, list, n, follow, plane, side, mem);
+  else if (write)
+    hipLaunchKernelGGL((k_stream_decode<true, false>), grid, block, KS_LDS, s, items, rec_item, recs, list, n, follow, plane, side, mem);
+  else if (side)
+    hipLaunchKernelGGL((k_stream_decode<false, true>), grid, block, KS_LDS, s, items, rec_item, recs, list, n, follow, plane, side, mem);
   else
-    hipLaunchKernelGGL(k_stream_decode<false>, grid, block, KS_LDS, s, items, rec_item, recs, list, n, follow, plane);
+    hipLaunchKernelGGL((k_stream_decode<false, false>), grid, block, KS_LDS, s, items, rec_item, recs, list, n, follow, plane, side, mem);
   return hipGetLastError();
 }
 

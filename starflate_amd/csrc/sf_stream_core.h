@@ -4,6 +4,7 @@
 #include "sf_device.h"
 
 #include "sf_inflate_core.h"
+#include "sf_members.h"
 
 namespace sf {
 
@@ -70,16 +71,44 @@ __device__ __forceinline__ void copy_stored(uint16_t* __restrict__ to, const uin
 }
 
 // Blocks of one chunk (see the header).  WRITE: the exact rules, and the symbol plane from plane[c.base].
-template <bool WRITE>
+// MEMBERS (a file of gzip members; the body reaches to the file's end): a BFINAL block closes a member, not the chunk.  The lane
+// hops (sf_members.h) over the trailer, the zero bytes and the next header and goes on in the next body while the chunk's
+// range lasts; final_ is the file's end.  side: the chunk's side row.  The count pass leaves in it how many members the chunk
+// closed and where in its output the last of them ended; the write pass finds there where the member open at the chunk's
+// start began in the item's output (a match may reach no further back) and the first row of mem that is the chunk's to
+// write, one row per member it closes (item: the chunk's item row, for the host to place the rows).
+template <bool WRITE, bool MEMBERS>
 __device__ void stream_decode(const uint8_t* src, uint64_t src_n, uint64_t b0, uint64_t body_n, StreamChunk& c, uint8_t* m,
-                              uint16_t* __restrict__ plane, uint64_t cap) {
+                              uint16_t* __restrict__ plane, uint64_t cap, StreamSide* side = nullptr,
+                              StreamMember* __restrict__ mem = nullptr, uint32_t item = 0) {
   StreamReader rd;
   rd.open(src, src_n, b0, body_n, c.start);
   BitReader& br = rd.br;
   const uint64_t base = c.base;
   uint64_t pos = 0;
   uint32_t st = kOk, fin = 0;
-  while (!fin && rd.abs() < c.limit) {
+  uint64_t member0 = 0;               // MEMBERS, WRITE: where the open member began in the item's output
+  uint32_t closed = 0, eof = 0;       // MEMBERS: members closed so far, the file's end
+  uint64_t closed_at = 0;
+  if (MEMBERS && WRITE) member0 = side->at;
+  for (;;) {
+    if (fin) {
+      if (!MEMBERS) break;
+      const members::Hop h = members::hop(src, src_n, 8 * b0 + rd.abs());
+      if (h.st != kOk && h.src_end == 0) { st = h.st; break; }  // no trailer
+      if (WRITE) {
+        if (closed >= side->n) { st = kError; break; }  // (the count pass closed fewer: never)
+        mem[side->first + closed] = StreamMember{h.src_end, base + pos, h.crc32, h.isize, item, 0u};
+        member0 = base + pos;
+      }
+      ++closed;
+      closed_at = pos;
+      if (h.end) { eof = 1; break; }
+      if (h.st != kOk) { st = h.st; break; }
+      rd.open(src, src_n, b0, body_n, 8 * (h.next - b0));
+      fin = 0;
+    }
+    if (rd.abs() >= c.limit) break;
     if (br.bitpos > kRebase) rd.open(src, src_n, b0, body_n, rd.abs());
     if (rd.rem() < 3) { st = kInvalidBlockHeader; break; }
     br.refill();
@@ -146,7 +175,7 @@ __device__ void stream_decode(const uint8_t* src, uint64_t src_n, uint64_t b0, u
       if (rd.rem() < dextra) { st = kError; break; }
       const uint32_t dist = dbase + br.get(dextra);
       if (WRITE) {
-        if (dist > base + pos) { st = kInvalidDistance; break; }
+        if (dist > base + pos - member0) { st = kInvalidDistance; break; }
         if (cap - (base + pos) < len) { st = kDstTooSmall; break; }
         if (pos + len > c.out) { st = kError; break; }
         uint16_t* to = plane + base + pos;
@@ -168,8 +197,9 @@ __device__ void stream_decode(const uint8_t* src, uint64_t src_n, uint64_t b0, u
   }
   c.end = rd.abs();
   c.status = st;
-  c.final_ = fin;
+  c.final_ = MEMBERS ? eof : fin;
   if (!WRITE) c.out = pos;
+  if (MEMBERS && !WRITE) *side = StreamSide{closed_at, closed, 0u};
 }
 
 // T <- the window after chunk c, from T = the window before it (entries: literal bytes, or 0x8000 | k, entry k of a base window)
